@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- benchmark of the MI355X audio matcher on BASELINE.json's configs.
 
-  python bench.py --gpus N --steps K --warmup W [--config {2,3,4}]
+  python bench.py --gpus N --steps K --warmup W [--config {2,3,4}] [--dump-outputs DIR]
 
 --config 2 (default, BASELINE configs[1] shape per GPU / configs[2] with --total-haystacks 1000):
     one 10 s mono 44.1 kHz f32 needle against 1 h haystacks resident in HBM, f32 arithmetic;
@@ -134,6 +134,10 @@ class Workload:
     def check(self, k, res):
         assert [p.start for p in res] == plant_offsets(k, self.sr), (k, res)
 
+    def peak_lists(self, res):
+        """One haystack's result as a list of peak lists, one per needle."""
+        return [res]
+
     def units_per_haystack(self):
         return float(self.h) * self.n_needles
 
@@ -200,6 +204,9 @@ class MultiNeedleWorkload(Workload):
     def check(self, k, res):
         for j, r in enumerate(res):
             assert [p.start for p in r] == self.plants(k, j), (k, j, r)
+
+    def peak_lists(self, res):
+        return res
 
     def kernel_bytes(self, dense=False, main_only=False):
         g = self.geo
@@ -359,7 +366,51 @@ def parse_args():
     ap.add_argument("--half-pipeline", type=int, nargs="?", const=1, default=0,
                     help="BASELINE configs[4] precision on the --config 2 workload (not the headline): 1 = work matrix stored as "
                          "f16, 2 = butterflies in packed f16 as well; with --config 4 the level to use (default 2)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="after the timed steps, write the peak lists the last timed step returned as DIR/peaks_*.npy "
+                         "(inputs are seeded: two builds compare output for output)")
     return ap.parse_args()
+
+
+DUMP_BUDGET_BYTES = 60 << 20        # array data of one --dump-outputs (the .npy headers fit in what is left of 64 MB)
+
+
+def dump_outputs(R, out_dir: str, rows):
+    """--dump-outputs: what the last timed step returned, every rank's part, written by rank 0.
+    rows = [(haystack k, [peaks against needle j, for every needle j])] of this rank.  The records keep the
+    library's buffer layout: peaks_count[i, j] records per (haystack peaks_haystack[i], needle j), then
+    peaks_start / _end (float64, exact) and peaks_height / _prominence (the library's f32) in that order.
+    Above the budget a fixed, seeded sample of whole haystacks is written."""
+    import numpy as np
+    mine = [(k, [[(p.start, p.end, p.height, p.prominence) for p in lst] for lst in per]) for k, per in rows]
+    rows = sorted((r for part in R.gather(mine) for r in part), key=lambda r: r[0])
+    if R.rank != 0:
+        return
+
+    def nbytes(row):
+        return 8 + 8 * len(row[1]) + 24 * sum(len(lst) for lst in row[1])
+
+    if sum(map(nbytes, rows)) > DUMP_BUDGET_BYTES:
+        kept, total = [], 0
+        for i in np.random.default_rng(0).permutation(len(rows)):
+            if total + nbytes(rows[i]) > DUMP_BUDGET_BYTES:
+                break
+            kept.append(rows[i])
+            total += nbytes(rows[i])
+        rows = sorted(kept, key=lambda r: r[0])
+    n_needles = len(rows[0][1]) if rows else 0
+    recs = [p for _, per in rows for lst in per for p in lst]
+    arrays = {
+        "peaks_haystack": np.array([k for k, _ in rows], np.float64),
+        "peaks_count": np.array([[len(lst) for lst in per] for _, per in rows], np.float64).reshape(len(rows), n_needles),
+        "peaks_start": np.array([p[0] for p in recs], np.float64),
+        "peaks_end": np.array([p[1] for p in recs], np.float64),
+        "peaks_height": np.array([p[2] for p in recs], np.float32),
+        "peaks_prominence": np.array([p[3] for p in recs], np.float32),
+    }
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 def free_port() -> int:
@@ -434,7 +485,7 @@ def strong_batch(am, R, W, total, steps, ranks_per_device=1):
     """`steps` passes over a batch of `total` haystacks, haystack k on rank k mod world.
     Resident waves: what fits the per-GPU budget is generated on device (untimed), matched
     with one batch call (timed), verified, and its buffers reused for the next wave.
-    Returns (seconds of this rank summed over waves and steps, wave size)."""
+    Returns (seconds of this rank summed over waves and steps, wave size, [(k, result)] of the last step)."""
     device = W.device
     mine = shard(total, R.rank, R.world)
     per_wave = max(1, int(RESIDENT_BUDGET_BYTES // ranks_per_device // W.hay_bytes))
@@ -445,6 +496,7 @@ def strong_batch(am, R, W, total, steps, ranks_per_device=1):
     # every rank goes through the same number of waves (an empty one still takes part in the barrier)
     n_waves = max(1, int(R.max_all(float((len(mine) + n_buf - 1) // n_buf))))
     for _ in range(steps):
+        last = []
         for wi in range(n_waves):
             wave = mine[wi * n_buf:(wi + 1) * n_buf]
             if wave and wave != resident:             # a shard that fits one wave is generated once
@@ -459,10 +511,11 @@ def strong_batch(am, R, W, total, steps, ranks_per_device=1):
             local += time.perf_counter() - t0
             for k, r in zip(wave, res):
                 W.check(k, r)
+            last += zip(wave, res)
     for b in bufs:
         b.free()
     R.barrier()
-    return local, n_buf
+    return local, n_buf, last
 
 
 def long_haystack_leg(am, R, W, hours, steps, warmup):
@@ -470,7 +523,7 @@ def long_haystack_leg(am, R, W, hours, steps, warmup):
     instead of threads): rank r generates the samples of its part on its device (untimed), then per step: every rank
     matches its windows (am_match_part_device), the unmerged peaks are gathered on the host, rank 0 runs the one
     sort + overshadow pass (am_merge_peaks).  Returns (seconds per step: max over ranks incl. gather and merge,
-    offsets_ok, part description)."""
+    offsets_ok, part description, haystack samples, planted hits, the last step's merged peaks -- None off rank 0)."""
     device = W.device
     sr, s = W.sr, W.s
     n = int(hours * 3600 * sr)
@@ -504,7 +557,7 @@ def long_haystack_leg(am, R, W, hours, steps, warmup):
     ok = R.rank != 0 or [q.start for q in res] == plants
     desc = R.gather({"rank": R.rank, "windows": nw, "first_window": w0, "samples": cnt, "seconds": round(local, 6)})
     buf.free()
-    return dt / steps, ok, desc, n, len(plants)
+    return dt / steps, ok, desc, n, len(plants), res
 
 
 def device_identity(device: int) -> str:
@@ -518,6 +571,8 @@ def main():
     args = parse_args()
     if args.gpus < 1:
         raise SystemExit("bench.py: --gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("bench.py: --steps must be >= 1 and --warmup >= 0")
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         sys.exit(spawn_ranks(args))
     R = Rank(args)
@@ -583,8 +638,10 @@ def main():
             raise SystemExit("bench.py: --long-haystack runs the config 2 workload")
         am.set_option("profile_mask", 1 << KN.index(dom))
         with am.Profile(device) as prof:
-            per_step, ok, parts, n_long, n_plants = long_haystack_leg(am, R, W, args.long_haystack, args.steps, args.warmup)
+            per_step, ok, parts, n_long, n_plants, merged = long_haystack_leg(am, R, W, args.long_haystack, args.steps, args.warmup)
             dom_ms, dom_launches = prof.query(dom)
+        if args.dump_outputs:
+            dump_outputs(R, args.dump_outputs, [(0, [merged])] if R.rank == 0 else [])
         if R.rank == 0:
             # rank 0's K2: its part's block pairs go through the row kernel in launches of at most `pairs_per_group`
             # pairs (each launch reads the needle spectrum once): bytes of all launches of a step over their time
@@ -653,6 +710,7 @@ def main():
         R.barrier()
         for res in results:
             check(res)
+        last = [(k, r) for (k, _), r in zip(hays, results[-1])]
         hay_per_rank_step = B
         units_per_step = W.units_per_haystack() * B * R.world
     else:
@@ -660,7 +718,7 @@ def main():
         am.set_option("profile_every", max(1, args.profile_every))
         strong_batch(am, R, W, args.total_haystacks, max(1, min(args.warmup, 1)), rpd)
         with am.Profile(device) as prof:
-            local_dt, wave = strong_batch(am, R, W, args.total_haystacks, args.steps, rpd)
+            local_dt, wave, last = strong_batch(am, R, W, args.total_haystacks, args.steps, rpd)
             dom_timed = prof.query(dom)
         units_per_step = W.units_per_haystack() * args.total_haystacks
         hay_per_rank_step = len(shard(args.total_haystacks, R.rank, R.world))
@@ -675,6 +733,8 @@ def main():
 
     dt = R.max_all(local_dt)
     per_rank = R.gather(round(local_dt, 6))
+    if args.dump_outputs:
+        dump_outputs(R, args.dump_outputs, [(k, W.peak_lists(r)) for k, r in last])
 
     # untimed: per-kernel breakdown of a few steps (every launch bracketed by events)
     am.set_option("profile_mask", -1)
@@ -689,7 +749,7 @@ def main():
     # the north-star batch as an extra leg: 1000 haystacks, strong scaling, one pass
     batch_1000 = None
     if not strong and not args.no_batch_1000 and args.config in (1, 2):
-        b_local, b_wave = strong_batch(am, R, W, 1000, 1, rpd)
+        b_local, b_wave, _ = strong_batch(am, R, W, 1000, 1, rpd)
         b_dt = R.max_all(b_local)
         b_parts = R.gather(round(b_local, 6))
         batch_1000 = {"value": 1000.0 * h / b_dt, "unit": "samples/s", "scaling": "strong", "n_gpus": devices_used,

@@ -219,6 +219,35 @@ def test_bench_workloads_state_their_design_bytes():
     assert bench.plan_geometry(441000, 158760000, 22, tail_block=1)["tail_n_fft"] == 0                   # a forced plan is taken as it is
 
 
+def test_bench_dump_outputs_layout(tmp_path, monkeypatch):
+    """`bench.py --dump-outputs DIR`: the peak lists of the last timed step as float32 / float64 .npy files, haystacks
+    in order, per (haystack, needle) counts ahead of the records; above the budget a seeded sample of whole haystacks."""
+    import types
+    sys.path.insert(0, ROOT)
+    sys.path.insert(0, os.path.join(ROOT, "audio-matcher_amd", "python"))
+    import bench
+    from audiomatch_amd import Peak
+    R = types.SimpleNamespace(rank=0, gather=lambda obj: [obj])
+    rows = [(k, [[Peak(100 * k + i, 100 * k + i + 1, 0.1 + i, 0.25) for i in range(j)] for j in range(3)]) for k in (7, 2, 5)]
+
+    def load(d):
+        return {f[:-4]: np.load(d / f) for f in os.listdir(d)}
+
+    bench.dump_outputs(R, str(tmp_path / "all"), rows)
+    a = load(tmp_path / "all")
+    assert sorted(a) == ["peaks_count", "peaks_end", "peaks_haystack", "peaks_height", "peaks_prominence", "peaks_start"]
+    assert all(v.dtype in (np.float32, np.float64) for v in a.values())
+    assert a["peaks_haystack"].tolist() == [2, 5, 7] and a["peaks_count"].tolist() == [[0, 1, 2]] * 3
+    assert a["peaks_start"].tolist() == [200, 200, 201, 500, 500, 501, 700, 700, 701]
+    assert a["peaks_end"].tolist() == [s + 1 for s in a["peaks_start"].tolist()]
+    assert a["peaks_height"].dtype == np.float32 and a["peaks_height"].tolist() == [np.float32(h) for h in [0.1, 0.1, 1.1] * 3]
+    monkeypatch.setattr(bench, "DUMP_BUDGET_BYTES", 2 * (8 + 3 * 8 + 3 * 24))
+    for d in ("s1", "s2"):
+        bench.dump_outputs(R, str(tmp_path / d), rows)
+    s1, s2 = load(tmp_path / "s1"), load(tmp_path / "s2")
+    assert len(s1["peaks_haystack"]) == 2 and all(np.array_equal(s1[k], s2[k]) for k in s1)
+
+
 def test_isa_has_no_store_data_hazard(tmp_path):
     """The gfx950 store-data hazard of DESIGN.md section 3: no >64-bit store in the compiled
     kernels may have one of its data VGPRs overwritten after fewer than two wait states
