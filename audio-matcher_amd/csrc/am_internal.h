@@ -1,0 +1,387 @@
+// am_internal.h -- what the host files of libaudiomatch_amd.so share: the context, plans, options, the
+// needle handle, the engine's request types and the helpers more than one file calls.
+#pragma once
+#include <algorithm>
+#include <atomic>
+#include <cfloat>
+#include <cmath>
+#include <cstdio>
+#include <cstring>
+#include <map>
+#include <mutex>
+#include <string>
+#include <vector>
+
+#include "am_kernels.h"
+
+namespace am {
+
+// ---------------------------------------------------------------------------
+extern thread_local std::string t_err;   // am_last_error_string
+int fail(int code, const std::string& msg);
+int hip_fail(hipError_t e, const char* what);
+#define AM_HIP(call)                                         \
+    do {                                                     \
+        hipError_t e_ = (call);                              \
+        if (e_ != hipSuccess) return hip_fail(e_, #call);    \
+    } while (0)
+
+// progress hooks (audio_matcher.rs:102-117, 129); a call works on the snapshot it takes on entry
+struct Hooks {
+    am_progress_fn fn = nullptr;
+    void* user = nullptr;
+    am_chunk_progress_fn chunk_fn = nullptr;
+    void* chunk_user = nullptr;
+};
+Hooks snapshot_hooks();
+
+// The options of am_set_option, as every entry point sees them: read once, on entry (snapshot_opts), so that a
+// concurrent am_set_option never changes a call half way; "log_n" and "half_pipeline" can also be fixed per needle
+// handle (am_needle_set_option), which wins over the default.  Each member is one row of the option table
+// (am_context.hip), which says what it means.
+struct Opts {
+    long long log_n, pairs_per_group, half, batch_overlap, needle_group, dense, device_redo, debug_no_realloc, debug_redo_arm_at;
+    long long peak_filter_order, distance_rule, tail_window, surrounding_from, k3_group, pick_group, tail_block, host_pick_wait;
+    long long profile_mask, profile_every, pick_priority;
+    PeakPolicy peak_policy() const { return PeakPolicy{(int)peak_filter_order, (int)(distance_rule & 1), (int)((distance_rule >> 1) & 1)}; }
+};
+static const float kHalfGain = 1024.0f;      // keeps the stored values of a normalised score near 1
+static const double kMinEfficiency = 0.75;  // hop / N the auto plan accepts
+static const int kLogNMin = 10, kLogNMax = 23;
+// needles longer than this run on N = 2^22 (measured crossover between 2 and 5 s of 44.1 kHz
+// audio, tools/needle_sweep.py, profiles/r03/needle_sweep.txt: 2 s 0.674 against 0.685 ms per hour of
+// audio, 5 s 0.725 against 0.702)
+static const long long kWideFromSamples = 140000;
+// needles longer than this run on N = 2^23 = 1024 x 8192 (measured crossover between 30 and 36 s of 44.1 kHz
+// audio, profiles/r03/needle_sweep.txt: the 1024-row column kernels cost more per point, the hop is longer)
+static const long long kWidestFromSamples = 1500000;
+// Needles longer than this (half a 2^23 transform) are cut into segments of at most 2^22 samples:
+// corr(hay, needle)[j] = sum_i corr(hay, segment_i)[j + offset_i], every segment on the register kernels
+// of the 2^23 plan (hop efficiency of at least one half), the partial sums added up in the score array by
+// K3 (MyConvolve::correlate accepts any length, audio_matcher.rs:414-457).
+static const long long kSegmentFrom = 1ll << 22;
+static const long long kSegmentLen = 1ll << 22;
+
+// ---------------------------------------------------------------------------
+// While a batch is being queued (kernels of earlier haystacks still running, or not yet started) no
+// scratch buffer may move: hipFree waits for the device (the overlap of pick and transforms stalls) and a
+// buffer whose contents a later launch still expects would be lost (round 3, gpurun_out/r03q: a peak lost
+// to a flag buffer re-allocated under a running pick).  match_many / match_multi_many size everything
+// before their queueing loops; with the option "debug_no_realloc" an ensure() that would still have to
+// allocate inside such a loop fails the call instead (tests/test_gpu_round4.py).
+extern thread_local int t_no_realloc;
+struct QueueingScope {
+    bool on;
+    explicit QueueingScope(bool enable) : on(enable) { if (on) ++t_no_realloc; }
+    ~QueueingScope() { end(); }
+    void end() { if (on) { --t_no_realloc; on = false; } }
+    QueueingScope(const QueueingScope&) = delete;
+    QueueingScope& operator=(const QueueingScope&) = delete;
+};
+int realloc_refused(const char* what, size_t bytes, size_t cap);
+
+struct DevBuf {
+    void* p = nullptr;
+    size_t cap = 0;
+    int ensure(size_t bytes) {
+        if (bytes <= cap) return AM_OK;
+        if (t_no_realloc > 0) return realloc_refused("a device", bytes, cap);
+        release();
+        size_t want = bytes + bytes / 8;
+        hipError_t e = hipMalloc(&p, want);
+        if (e != hipSuccess) {
+            e = hipMalloc(&p, bytes);
+            want = bytes;
+            if (e != hipSuccess) { p = nullptr; return hip_fail(e, "hipMalloc(scratch)"); }
+        }
+        cap = want;
+        return AM_OK;
+    }
+    void release() {
+        if (p) (void)hipFree(p);
+        p = nullptr; cap = 0;
+    }
+};
+struct HostBuf {
+    void* p = nullptr;
+    size_t cap = 0;
+    unsigned flags = hipHostMallocDefault;
+    int ensure(size_t bytes) {
+        if (bytes <= cap) return AM_OK;
+        if (t_no_realloc > 0) return realloc_refused("a pinned host", bytes, cap);
+        release();
+        hipError_t e = hipHostMalloc(&p, bytes, flags);
+        if (e != hipSuccess) { p = nullptr; return hip_fail(e, "hipHostMalloc"); }
+        cap = bytes;
+        return AM_OK;
+    }
+    void release() {
+        if (p) (void)hipHostFree(p);
+        p = nullptr; cap = 0;
+    }
+};
+
+struct Plan {
+    PlanDev dev{};
+    float2* tables = nullptr;  // one allocation holding the four tables
+    unsigned* mf = nullptr;    // constant tables of the matrix-core row kernel (N2 = 8192 only)
+};
+
+struct ProfRec { int name; hipEvent_t e0, e1; };
+enum { KN_K1 = 0, KN_K2, KN_K3, KN_STATS, KN_PEAKS, KN_OTHER, KN_COUNT };
+
+struct Ctx {
+    int device = -1;
+    hipStream_t stream = nullptr;
+    hipStream_t stream2 = nullptr;           // peak pick of haystack k beside the transforms of k+1 (batches)
+    hipStream_t stream_tail = nullptr;       // a haystack's odd last block on the smaller plan, beside its main pass (run_tail_block)
+    hipEvent_t ev_fork = nullptr, ev_join = nullptr;
+    DevBuf work_tail, tail_scores, tail_stats;   // (a batch computes the tails of up to kMaxTailBatch haystacks per launch: two alternating halves)
+    DevBuf work_tail2;                           // several needles: the tail's inverse rows, one matrix per needle of a group
+    std::recursive_mutex mu;
+    std::map<int, Plan> plans;
+    DevBuf work, work2, scores, stats, stats32, wflags, segs, peaks, io_in, io_out, sum, arena_cur, wide_ctl, wide_list, wide_tiles;
+    // second set of the score-side buffers: in a batch the peak pick of haystack k runs on
+    // stream2 beside the transforms of haystack k+1, which then need their own set
+    DevBuf scores_b, stats_b, stats32_b, wflags_b, peaks_b;
+    // device-side redo (batches): a second work matrix, so that the inverse rows of haystack k are still there
+    // when its pick has found chunks whose certificate failed, and the per-pair "run again" flags of both sets
+    DevBuf work_b, redo_pairs[2];
+    // several needles: the K3s of a needle group run as ONE launch, every needle of the group with score-side
+    // buffers of its own; two such sets alternate (the picks of group g beside the transforms of group g + 1)
+    DevBuf grp_scores[2 * kMaxNeedleGroup], grp_stats32[2 * kMaxNeedleGroup], grp_wflags[2 * kMaxNeedleGroup];
+    DevBuf grp_stats[kMaxNeedleGroup];   // tile summaries of the group's picks (one set: picks run one group after the other)
+    HostBuf failcnt;   // host-visible: one byte per chunk of a call, set when the chunk failed its certificate
+    hipEvent_t ev_k3[2] = {nullptr, nullptr}, ev_pick[2] = {nullptr, nullptr};
+    HostBuf pinned;
+    // Per-chunk result headers live in coherent pinned host memory that the peak
+    // kernel writes directly (a few KB per haystack): no device-to-host copy
+    // sits between the last kernel and the host's wake-up.
+    HostBuf hdr;
+    HostBuf spill;   // spill arena of the single-chunk passes (same kind of memory)
+    HostBuf badflag; // one word per haystack of a call: "some score was not finite"
+    DevBuf ranges, range_flags;   // work area of the non-finite-sample search (rare path)
+    DevBuf big;                   // lists, sort keys and bucket table of a chunk with more than AM_MAX_PEAKS_PER_CHUNK peaks (rare path)
+    // the chunk list currently resident in `segs` (re-uploaded only when it changes)
+    std::vector<Segment> segs_resident;
+    // profiling
+    bool prof = false;
+    std::vector<ProfRec> pending;
+    std::vector<hipEvent_t> pool;
+    double prof_ms[KN_COUNT] = {0};
+    uint64_t prof_n[KN_COUNT] = {0};
+    uint64_t prof_seq[KN_COUNT] = {0};   // launches of the class seen while profiling is on (option profile_every)
+};
+
+// Events that order the library's streams of ONE device among themselves (the pick behind K3, K3 behind the pick that
+// last read its score set, the tail stream) and the events that time kernels: without the system-scope fence a default
+// event performs when it is recorded (a write-back and invalidation of the caches).  Nothing here needs that fence:
+// kernel boundaries order device memory by themselves, and what the host reads (result headers in pinned memory) it
+// reads behind a hipStreamSynchronize.  Measured -0.7 % on the headline, near the noise: what an event costs a stream
+// is its barrier packet, 4 - 8 us of a kernel boundary, fence or not (profiles/r04/event_gaps.txt).
+#ifndef AM_EVENT_NO_SYSTEM_FENCE
+#define AM_EVENT_NO_SYSTEM_FENCE 1
+#endif
+constexpr unsigned kSyncEvent = hipEventDisableTiming | (AM_EVENT_NO_SYSTEM_FENCE ? hipEventDisableSystemFence : 0u);
+
+int get_ctx(int device, Ctx** out);
+struct ProfScope {
+    Ctx* c; int name; hipStream_t st; hipEvent_t e0 = nullptr, e1 = nullptr;
+    bool on;
+    ProfScope(Ctx* c_, int name_, hipStream_t st_ = nullptr);   // (am_context.hip: reads the options profile_mask / profile_every)
+    ~ProfScope() {
+        if (on) { (void)hipEventRecord(e1, st); c->pending.push_back({name, e0, e1}); }
+    }
+};
+hipError_t copy_on_stream(Ctx* c, void* dst, const void* src, size_t bytes, hipMemcpyKind kind);
+// force_logN1: another factorisation than the production one (am_debug_column_bench: 2^23 as 512 x 16384)
+int get_plan(Ctx* c, int logN, const Plan** out, int force_logN1 = 0);
+
+}  // namespace am
+
+// ---------------------------------------------------------------------------
+struct am_needle {
+    am::Ctx* ctx = nullptr;
+    float* d_needle = nullptr;
+    size_t n = 0;
+    float inv_autocorr = 0.f;
+    std::map<int, float2*> spectra;  // logN -> conj(H)/N in pipeline layout
+    std::map<int, unsigned*> spectra16;   // logN -> the same as scaled __half2 points (half_pipeline = 2)
+    std::map<int, unsigned*> spectra16m;  // logN -> the same conjugated, in [a'][b'][c'] order (option k2_mfma)
+    // Lowest chunk minimum of each of the last few haystacks matched with this needle (index 0:
+    // unscaled scores, 1: AM_SCALE_LIB).  Bounds the raw-score write threshold from above, so that a
+    // score array that drifts slowly (chunk minimum in another block pair than a tile's scores)
+    // stays inside its certificate; a ring, so that one unusual haystack is forgotten again.
+    static constexpr int kRecent = 8;
+    float recent_min[2][kRecent];
+    int recent_n[2] = {0, 0}, recent_pos[2] = {0, 0};
+    void remember_min(int sm, float v) {
+        recent_min[sm][recent_pos[sm]] = v;
+        recent_pos[sm] = (recent_pos[sm] + 1) % kRecent;
+        if (recent_n[sm] < kRecent) ++recent_n[sm];
+    }
+    // haystacks left for which the ring takes the LOWEST chunk minimum (after a haystack in which many chunks
+    // failed their certificate: a drifting score array); otherwise, where a failed chunk is redone on the
+    // device, it takes the median -- the background level -- so that a few chunks with deep dips (a hit whose
+    // autocorrelation has negative lobes) do not make every later haystack write all its scores
+    int conservative_left[2] = {0, 0};
+    // haystacks left for which a batch queues the device-side redo (a K3 launch that looks at the pairs' flags and
+    // a second pick per haystack: 1.6 % of the headline's time when nothing ever fails).  Armed by a failed
+    // certificate -- of an earlier call, or of an earlier haystack of the same call as soon as its flag has
+    // arrived in host memory; until then such a chunk is redone from the host, as in single calls.
+    int redo_armed_left[2] = {0, 0};
+    float hist_min(int sm) const {
+        float m = FLT_MAX;
+        for (int i = 0; i < recent_n[sm]; ++i) m = std::min(m, recent_min[sm][i]);
+        return m;
+    }
+    // per-handle overrides of the process-wide option defaults (-1 = follow the default)
+    long long opt_log_n = -1, opt_half = -1;
+    // Needle partitioning (needles longer than kSegmentFrom samples): sub-handles over slices of d_needle
+    // (not owned), each with its own spectra; segment i starts at sample seg_off[i] of the needle.
+    std::vector<am_needle*> segments;
+    std::vector<long long> seg_off;
+    bool owns_data = true;
+};
+
+namespace am {
+
+// The overlap-save engine: scores[j] = factor * sum_n X[j + n - lead] needle[n]
+// When a ScanRequest is given and the plan supports it, K3 also writes the level-0
+// (min,max) summary into the chosen set's stats32 and `fused` becomes true.
+struct ScanRequest {
+    float margin;            // in: a run's raw scores are written when its maximum reaches min(its K3 tile's minimum, hist_min) + margin; < 0: all
+    float hist_min;          // in: lowest chunk minimum of the needle's recent haystacks (FLT_MAX: none)
+    long long seg_c, seg_d;  // in: chunk geometry (scores i*seg_c .. i*seg_c + seg_d)
+    int set;                 // in: which set of score-side buffers (0, or 1 in an overlapped batch)
+    hipEvent_t before_k3;    // in: K3 must not overwrite that set before this event (or null)
+    // in: restrict the launch to the blocks that produce scores [range_a, range_b) (range_b = 0:
+    // everything).  Used to redo single chunks with theta = -inf in place.
+    long long range_a, range_b;
+    int* bad;                // in: host-visible word the summary kernels of the pick set when a score is not finite, or null
+    // in (streaming ingest): summary / flag buffers owned by the caller instead of the context's sets, and
+    // "launch nothing" (every pair was computed while the samples arrived; only describe what is there)
+    DevBuf* ext_stats32; DevBuf* ext_side;
+    // in (streaming ingest): the block count the side buffer is laid out for (0: this launch's own).  The
+    // thresholds sit behind the ballots, i.e. at an offset that depends on the block count: early pairs are
+    // launched under the layout of the announced length and the final pass must keep that layout even
+    // when the real length gives fewer blocks.
+    long long side_nblocks;
+    bool skip_launch;
+    bool tail_by_caller;     // in: the caller computes a TailPlan's scores itself (match_many, several haystacks per launch): main pass only
+    bool no_scan;            // in: only the block restriction (range_a, range_b) applies; K3 writes plain scores
+    bool work_by_set;        // in: the work matrix of set 1 is the context's second one (kept for a device-side redo)
+    // out: what a second K3 launch over the same work matrix needs (valid when redo_ok)
+    bool redo_ok;
+    Job redo_job; PlanDev redo_pl; float redo_scale; int redo_half; int redo_npairs; const float2* redo_work; ScanCfg redo_cfg;
+    bool fused;              // out: K3 produced stats32 / wflags
+    SparseScores sparse;     // out: description of what was written
+};
+struct Geometry {
+    int logN;
+    long long N, hop, nblocks, npairs;
+};
+// The odd last block.  Two blocks share one complex transform, so a haystack with an odd number of blocks pays a
+// whole pair for its last, usually part-filled block (1 h at 44.1 kHz against a 10 s needle: 42.2 blocks of the
+// 2^22 plan = 22 pairs, 2.3 % of the points for nothing).  When the scores behind the last even block boundary T fit
+// into one pair of a smaller plan that has the fused scan, the main pass stops at T and those scores come from
+// that plan, computed on a stream of their own beside the main pass (run_tail_block): every run written, and the
+// main layout's ballots / thresholds of the block they belong to preset to "all written", so that the peak pick
+// sees one score array with one geometry.  Which blocks a haystack gets depends on its own length only: its bits
+// do not depend on the batch it travels in.
+struct TailPlan {
+    bool on;
+    long long T;      // first score of the tail (a multiple of the main plan's hop, hence of kTile)
+    Geometry g;       // the smaller plan's layout for scores [T, out_count): one pair
+};
+// Half-precision levels (option "half_pipeline"): 1 = the work matrix travels through HBM as f16,
+// butterflies in f32; 2 = K2's butterflies in packed f16 as well.  The scales keep every stored
+// or f16-computed value inside f16's range: level 1 normalises K2's product by the needle energy
+// (times a fixed gain); level 2 scales the row by 2^-7 on the way into K2 (a full-scale tone then
+// peaks at 2^15 in the forward spectrum) and the needle spectrum to an rms of 1/8 per bin.  K3
+// divides the scales out in f32.
+struct HalfScale {
+    int level;
+    float pre, hscale;
+    float k3(float factor) const { return level ? factor / (hscale * pre) : factor; }
+};
+// What the transforms of one haystack need of the context's scratch buffers, so that a batch can size them
+// once, for its largest haystack, before anything is queued (see QueueingScope).  Also builds the plan and
+// the needle spectrum the haystack will use (building one runs kernels and waits for them).
+struct Footprint {
+    size_t work = 0, stats32 = 0, side = 0, work_tail = 0;
+    long long npairs = 0;
+    void take(const Footprint& f) {
+        work = std::max(work, f.work); stats32 = std::max(stats32, f.stats32); side = std::max(side, f.side);
+        work_tail = std::max(work_tail, f.work_tail);
+        npairs = std::max(npairs, f.npairs);
+    }
+};
+// One part of a haystack that is split over several devices (am_match_part_device, am_pool_match_long*): the
+// buffer holds the samples from window `first_window` on, only its first `max_windows` windows belong to
+// this part (the samples behind them are the last window's overlap), and the peaks come back unmerged, in
+// window order, at their positions in the whole haystack -- calc_chunks up to audio_matcher.rs:131.
+struct PartSpec {
+    size_t max_windows;
+    uint64_t first_sample;            // position of the part's first sample in the whole haystack
+    size_t chunk_base, chunk_total;   // for the per-chunk progress events: this part's first window, windows of the whole haystack
+    std::vector<am_peak>* raw;        // out
+};
+// Streaming ingest (am_match_stream_*): the block pairs [0, pairs_done) of the one haystack were
+// computed while its samples arrived, into buffers the stream object owns.
+struct StreamPre {
+    float* scores;
+    DevBuf* stats32; DevBuf* side;
+    long long pairs_done;
+    long long layout_nblocks;   // the block count the early pairs laid the side buffer out for (ScanRequest::side_nblocks)
+};
+
+inline const void* advance_src(const void* src, size_t elements) {
+    // one f32 mono sample and one interleaved i16 stereo frame are both 4 bytes
+    return static_cast<const char*>(src) + 4 * elements;
+}
+
+// ---- am_context.hip ----
+Opts snapshot_opts(const am_needle* h);
+int check_needle(const am_needle* h);
+HalfScale half_scale(const am_needle* h, const Opts& o, const PlanDev& pl);
+int needle_k2_spectrum(am_needle* h, const Opts& o, const Plan* pl, const float2** hc, HalfScale* hs);
+
+// ---- am_correlate.hip ----
+int plan_geometry(size_t s, long long out_count, const Opts& o, Geometry* g);
+bool tail_plan(size_t s, long long out_count, const Opts& o, const Geometry& g, TailPlan* t);
+Job tail_job(const TailPlan& t, const void* d_src, long long src_len, long long out_count, int src_kind);
+size_t sparse_bytes(long long nblocks, const PlanDev& pl);
+void fill_scan_cfg(ScanCfg* cfg, void* stats32, void* side, long long nblocks, const PlanDev& pl, float margin, float hist_min,
+                   long long seg_c, long long seg_d);
+SparseScores sparse_view(const ScanCfg& cfg, long long hop, const PlanDev& pl);
+bool needle_is_segmented(const am_needle* h, const Opts& o);
+float write_margin(const Opts& o, const am_match_params* p);
+int run_correlation(am_needle* h, const Opts& o, const void* d_src, long long src_len, long long lead,
+                    float* d_dst, long long out_count, float factor, ScanRequest* scan_req = nullptr, int src_kind = 0);
+int correlation_footprint(am_needle* h, const Opts& o, long long out_count, Footprint* f);
+int nonfinite_flags(Ctx* c, const float* d_src, const Segment* ranges, int n, int* flags);
+float scale_factor(const am_needle* h, int scale, size_t w);
+void make_segments(size_t len, size_t s, const am_match_params* p, bool drop_tail, std::vector<Segment>& segs,
+                   std::vector<size_t>* widths = nullptr, size_t max_windows = (size_t)-1);
+int upload_segments(Ctx* c, const std::vector<Segment>& segs);
+int prepare_results(Ctx* c, size_t nhdr, size_t arena_entries, PeakArena* arena);
+int launch_pick(Ctx* c, const float* d_scores, long long n_scores, int seg_off, int nsegs,
+                float min_prom, long long min_dist, const ScanRequest* scan, int hdr_off,
+                const PeakArena& arena, const PeakPolicy& pol, hipStream_t st = nullptr, bool only_failed = false);
+int pick_chunk_big(Ctx* c, const float* d_scores, long long n_scores, int seg_idx, const Segment& sg,
+                   float min_prom, long long min_dist, const ScanRequest* scan, float seg_min,
+                   std::vector<am_peak>& all, const PeakPolicy& pol);
+int merge_peaks(std::vector<am_peak>& all, const am_match_params* p, bool from_filtered, am_peak* out, size_t cap, size_t* n_out);
+void append_header_peaks(const SegHeader& hd, const PeakArena& arena, std::vector<am_peak>& all);
+
+// ---- am_engine.hip ----
+int match_many(am_needle* h, const void* const* d_hays, const size_t* lens, size_t n_hay,
+               const am_match_params* p, am_peak* out, size_t cap_per_hay, size_t* n_out, int src_kind = 0,
+               size_t index_base = 0, size_t index_stride = 1, bool fire_hooks = true, const StreamPre* pre = nullptr,
+               const PartSpec* part = nullptr);
+int match_multi_many(am_needle* const* needles, size_t nn, const void* const* d_hays, const size_t* lens, size_t n_hay,
+                     int src_kind, const am_match_params* p, am_peak* out, size_t cap_per_pair, size_t* n_out,
+                     size_t index_base = 0, size_t index_stride = 1);
+
+}  // namespace am

@@ -398,6 +398,13 @@ int am_debug_column_bench(int device, int wide, int npairs, int iters, int dense
  *   "device_redo" (0/1, default 1): in a batch, chunks whose sparse-score certificate fails get their dense
  *       inverse pass on the device, beside the next haystack's transforms; 0 = the host path does it
  *       after the call's kernels (results are identical; for measurements).
+ *   "k3_group" (0/1, default 1): in am_match_multi_*, the inverse passes (K3) of a needle group run as one launch
+ *       (0: one launch per needle; results are identical, for measurements).
+ *   "pick_group" (0/1, default 1): ... and so do the group's peak picks (0: four small launches per needle).
+ *   "k2_mfma" (0/1, default 0, or the environment variable AM_K2_MFMA): with half_pipeline = 2, the row transform
+ *       (K2) of the 8192-point rows runs on the matrix cores (v_mfma_f32_16x16x32_f16); for measurements.
+ *   "pick_stream_priority" (0/1, default 0): the peak pick's stream gets the lowest stream priority, so that its
+ *       workgroups fill what the transforms leave free; read when a device's context is created.
  *   The rules of the path that no source or test available offline pins (the crates find_peaks 0.1 and common are
  *   not in the reference tree).  Defaults (0) = the documented choices of oracle/oracle.c; every
  *   alternative is implemented in the kernels, on the host and in the test checker (same switches), DESIGN.md

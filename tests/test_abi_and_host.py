@@ -48,22 +48,40 @@ def test_pure_host_entry_points(amlib):
     assert L.am_correlate_len(3, 7, int(amlib.Mode.Valid), C.byref(n)) == 0 and n.value == 1   # saturating_sub + 1
     assert L.am_correlate_len(0, 3, 2, C.byref(n)) == amlib.AM_ERR_INVALID_ARG
     assert L.am_set_option(b"log_n", 99) == amlib.AM_ERR_INVALID_ARG
+    assert L.am_last_error_string() == b"log_n out of range"   # (raised beside the option table; read where the ABI is)
     assert L.am_set_option(b"nonsense", 1) == amlib.AM_ERR_INVALID_ARG
     assert b"unknown" in L.am_last_error_string()
     assert L.am_set_option(b"log_n", 0) == 0
     assert amlib.get_option("pairs_per_group") >= 1
-    # every documented option reads back what was set (and its default afterwards); values are clamped to their range
+    # errors raised in the pool's and the merge's code reach am_last_error_string as well
+    p = amlib.Config().params(8000, amlib.Scale.LIB)
+    v = [C.c_size_t(0) for _ in range(4)]
+    assert L.am_long_plan(100000, 8000, C.byref(p), 0, 0, *[C.byref(x) for x in v]) == amlib.AM_ERR_INVALID_ARG
+    assert L.am_last_error_string() == b"bad part"
+    assert L.am_merge_peaks(None, None, 0, None, 0, None) == amlib.AM_ERR_INVALID_ARG
+    assert L.am_last_error_string() == b"null pointer"
+    # every option reads back what was set (and its default afterwards); values are clamped to their range
     for key, default, other in (("tail_block", 1, 0), ("host_pick_wait", 1, 0), ("profile_every", 1, 5), ("dense_scores", 0, 1),
                                 ("device_redo", 1, 0), ("batch_overlap", 1, 0), ("k3_group", 1, 0), ("pick_group", 1, 0),
                                 ("peak_filter_order", 0, 1), ("distance_rule", 0, 3), ("tail_window", 0, 1), ("surrounding_from", 0, 1),
-                                ("debug_no_realloc", 0, 1), ("debug_redo_arm_at", -2, 3)):
+                                ("debug_no_realloc", 0, 1), ("debug_redo_arm_at", -2, 3), ("log_n", 0, 16), ("pairs_per_group", 64, 8),
+                                ("profile_mask", -1, 5), ("half_pipeline", 0, 2), ("needle_group", 8, 3), ("pick_stream_priority", 0, 1)):
         assert amlib.get_option(key) == default, key
         amlib.set_option(key, other)
         assert amlib.get_option(key) == other, key
         amlib.set_option(key, default)
         assert amlib.get_option(key) == default, key
+    k2_mfma = amlib.get_option("k2_mfma")   # (its initial value comes from the environment, AM_K2_MFMA)
+    amlib.set_option("k2_mfma", 1 - k2_mfma)
+    assert amlib.get_option("k2_mfma") == 1 - k2_mfma
+    amlib.set_option("k2_mfma", k2_mfma)
+    assert amlib.get_option("k2_mfma") == k2_mfma
     amlib.set_option("profile_every", 0)
     assert amlib.get_option("profile_every") == 1
+    for key, value, text in (("needle_group", 9, b"needle_group out of range"), ("pairs_per_group", 0, b"pairs_per_group out of range"),
+                             ("distance_rule", 4, b"distance_rule out of range")):
+        assert L.am_set_option(key.encode(), value) == amlib.AM_ERR_INVALID_ARG
+        assert L.am_last_error_string().startswith(text), key
 
 
 def test_no_device_fails_loudly(amlib):

@@ -361,9 +361,11 @@ def test_error_codes(gpu):
     assert L.am_match(algo._h, x.ctypes.data, x.size, C.byref(p), buf, 4, C.byref(n)) == 0
     p.scale = 3
     assert L.am_match(algo._h, x.ctypes.data, x.size, C.byref(p), buf, 4, C.byref(n)) == gpu.AM_ERR_INVALID_ARG
+    assert L.am_last_error_string() == b"bad scale"          # (raised in the batch engine)
     p = gpu.Config().params(8000, gpu.Scale.LIB)
     p.chunk = 0
     assert L.am_match(algo._h, x.ctypes.data, x.size, C.byref(p), buf, 4, C.byref(n)) == gpu.AM_ERR_INVALID_ARG
+    assert L.am_last_error_string() == b"chunk must be > 0"
     h = C.c_void_p()
     assert L.am_needle_create(99, x.ctypes.data, 8, C.byref(h)) == gpu.AM_ERR_NO_DEVICE
     assert L.am_needle_create(0, x.ctypes.data, 0, C.byref(h)) == gpu.AM_ERR_INVALID_ARG

@@ -497,7 +497,7 @@ def test_matrix_core_row_kernel_is_result_equivalent(gpu, oracle):
 # the odd last block on the smaller plan (option tail_block, on by default)
 # ---------------------------------------------------------------------------
 def tail_geometry(s):
-    """Hops of the 2^22 plan and of the 2^21 plan for a needle of s samples (am_api.hip, plan_geometry)."""
+    """Hops of the 2^22 plan and of the 2^21 plan for a needle of s samples (am_correlate.hip, plan_geometry)."""
     hop = ((1 << 22) - s + 1) // 1024 * 1024
     hop_t = ((1 << 21) - s + 1) // 1024 * 1024
     return hop, hop_t

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """ms per hour of audio for needles of 0.5 .. 120 s, on the automatic plan and on forced
-N = 2^21 / 2^22 / 2^23 (plan policy of am_api.hip pick_log_n).  Warmed-up clocks."""
+N = 2^21 / 2^22 / 2^23 (plan policy of am_correlate.hip pick_log_n).  Warmed-up clocks."""
 import sys
 import time
 
