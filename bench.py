@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- benchmark of the MI355X audio matcher on BASELINE.json's configs.
 
-  python bench.py --gpus N --steps K --warmup W [--config {2,3,4}] [--dump-outputs DIR]
+  python bench.py --gpus N --steps K --warmup W [--config {2,3,4}] [--dump-outputs DIR] [--full]
 
 --config 2 (default, BASELINE configs[1] shape per GPU / configs[2] with --total-haystacks 1000):
     one 10 s mono 44.1 kHz f32 needle against 1 h haystacks resident in HBM, f32 arithmetic;
@@ -22,10 +22,16 @@ without it the parent process -- before it makes any HIP call -- starts N fresh 
 independent, so ranks shard them with no data-path collective (no RCCL traffic);
 torch.distributed (gloo) carries only the barriers and the max-over-ranks of the timed region.
 
-Default mode: weak scaling (fixed work per rank).  With --config 2 every run also measures the
-north-star batch -- 1000 haystacks sharded k mod N over the ranks, strong scaling -- once and
-reports it as "batch_1000" (never as `value`); `--total-haystacks T` makes that strong-scaling
-batch the timed step itself, for every config.
+Default mode: weak scaling (fixed work per rank); `--total-haystacks T` makes a strong-scaling
+batch of T haystacks, sharded k mod N over the ranks, the timed step itself, for every config.
+
+A plain run does only what its line needs: set up, ramp, warm up, time the steps, write
+--dump-outputs, print the line.  `--full` adds, untimed and after the timed region:
+  * the per-kernel breakdown (roofline_pipeline.kernel_ms_per_haystack and .dominant_by_time);
+  * with --config 2 in weak scaling: the north-star batch -- 1000 haystacks sharded k mod N, strong
+    scaling, one pass -- as "batch_1000" (never as `value`), and, on one rank, the side measurements;
+  * on one rank: the CPU baselines.
+--no-batch-1000, --no-extra-legs and --no-cpu-baseline leave one of these out of a --full run.
 
 Prints ONE JSON line on rank 0.
 """
@@ -349,14 +355,17 @@ def parse_args():
     ap.add_argument("--long-haystack", type=float, default=0.0, metavar="HOURS",
                     help="strong scaling on ONE haystack of this many hours (SURVEY.md 8e, second sentence): rank r matches the "
                          "window range am_long_plan gives it (am_match_part_device), rank 0 merges (am_merge_peaks); config 2 only")
-    ap.add_argument("--no-batch-1000", action="store_true", help="skip the extra 1000-haystack strong-scaling leg")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region also run the per-kernel breakdown, the 1000-haystack strong-scaling leg, the "
+                         "side measurements and the CPU baselines (a plain run prints the headline line only)")
+    ap.add_argument("--no-batch-1000", action="store_true", help="--full: skip the extra 1000-haystack strong-scaling leg")
     ap.add_argument("--dry-shard", action="store_true",
                     help="print every rank's shard of --total-haystacks (default 1000) and stop before any GPU work")
     ap.add_argument("--allow-shared-devices", action="store_true",
                     help="(accepted for older command lines) ranks that share a GPU are always allowed as a rehearsal: the line "
                          "then reports n_gpus = devices actually used and carries a warning")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extra-legs", action="store_true", help="skip the dense / non-white / host-buffer side measurements")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baselines")
+    ap.add_argument("--no-extra-legs", action="store_true", help="--full: skip the dense / non-white / host-buffer side measurements")
     ap.add_argument("--cpu-chunks", type=int, default=0, help="chunks in the CPU sample (0 = three per thread, at most the whole hour)")
     ap.add_argument("--profile-every", type=int, default=5,
                     help="the timed region brackets every n-th launch of the dominant kernel with HIP events (an event pair costs "
@@ -722,33 +731,37 @@ def main():
             dom_timed = prof.query(dom)
         units_per_step = W.units_per_haystack() * args.total_haystacks
         hay_per_rank_step = len(shard(args.total_haystacks, R.rank, R.world))
-        # a resident set for the untimed per-kernel breakdown below
-        buf = am.DeviceBuffer(device, W.hay_bytes)
-        W.fill(buf, R.rank)
-        hays = [(R.rank, buf)]
-        ptrs = [buf.ptr]
-
-        def step():
-            return W.match(ptrs)
 
     dt = R.max_all(local_dt)
     per_rank = R.gather(round(local_dt, 6))
     if args.dump_outputs:
         dump_outputs(R, args.dump_outputs, [(k, W.peak_lists(r)) for k, r in last])
 
-    # untimed: per-kernel breakdown of a few steps (every launch bracketed by events)
-    am.set_option("profile_mask", -1)
-    am.set_option("profile_every", 1)
-    extra_steps = 3
-    with am.Profile(device) as prof:
-        for _ in range(extra_steps):
-            step()
-        kern = {name: (prof.query(name)[0] / extra_steps, prof.query(name)[1] // extra_steps) for name in KN}
-    n_hay_step = len(ptrs)
+    # --full, untimed: per-kernel breakdown of a few steps (every launch bracketed by events)
+    kern = None
+    if args.full:
+        if strong:
+            # a resident set for the breakdown
+            buf = am.DeviceBuffer(device, W.hay_bytes)
+            W.fill(buf, R.rank)
+            hays = [(R.rank, buf)]
+            ptrs = [buf.ptr]
 
-    # the north-star batch as an extra leg: 1000 haystacks, strong scaling, one pass
+            def step():
+                return W.match(ptrs)
+
+        am.set_option("profile_mask", -1)
+        am.set_option("profile_every", 1)
+        extra_steps = 3
+        with am.Profile(device) as prof:
+            for _ in range(extra_steps):
+                step()
+            kern = {name: (prof.query(name)[0] / extra_steps, prof.query(name)[1] // extra_steps) for name in KN}
+        n_hay_step = len(ptrs)
+
+    # --full: the north-star batch as an extra leg: 1000 haystacks, strong scaling, one pass
     batch_1000 = None
-    if not strong and not args.no_batch_1000 and args.config in (1, 2):
+    if args.full and not strong and not args.no_batch_1000 and args.config in (1, 2):
         b_local, b_wave, _ = strong_batch(am, R, W, 1000, 1, rpd)
         b_dt = R.max_all(b_local)
         b_parts = R.gather(round(b_local, 6))
@@ -811,8 +824,8 @@ def main():
                               "survey_model_frac": survey_gbs / HBM_PEAK_GBS,
                               "pmc_bytes_per_haystack": pmc_total,
                               "pmc_frac": (pmc_total * hay_per_rank_step * args.steps / local_dt / 1e9 / HBM_PEAK_GBS) if pmc_total else None,
-                              "dominant_by_time": max(KN, key=lambda n_: kern[n_][0]),
-                              "kernel_ms_per_haystack": {n_: v[0] / n_hay_step for n_, v in kern.items()},
+                              **({"dominant_by_time": max(KN, key=lambda n_: kern[n_][0]),
+                                  "kernel_ms_per_haystack": {n_: v[0] / n_hay_step for n_, v in kern.items()}} if kern else {}),
                               "kernel_bytes_per_haystack": per_hay_bytes},
     }
     if rpd > 1:
@@ -822,9 +835,9 @@ def main():
         out["config"]["warning"] = f"timed region {timed_ms:.1f} ms < 100 ms: raise --steps or --haystacks-per-step"
     if batch_1000 is not None:
         out["batch_1000"] = batch_1000
-    if R.world == 1 and not strong and not args.no_extra_legs and args.config in (1, 2):
+    if args.full and R.world == 1 and not strong and not args.no_extra_legs and args.config in (1, 2):
         out["side_measurements"] = side_measurements(am, device, W.algo, W.needle, W.params, hays, s, h, args.steps)
-    if R.world == 1 and not args.no_cpu_baseline:
+    if args.full and R.world == 1 and not args.no_cpu_baseline:
         threads = min(os.cpu_count() or 1, 16)
         chunks = args.cpu_chunks or min(3 * threads, HAY_S // CHUNK_S)
         out["cpu_baseline"] = cpu_baseline(chunks, threads, "reference")

@@ -8,8 +8,8 @@ part=${2:-all}     # "a": bench lines, kernel stats, PMC passes; "b": everything
 mkdir -p "$out"
 cd /tmp && export TMPDIR=/tmp && cd - > /dev/null
 if [ "$part" != "b" ]; then
-python3 bench.py > "$out/bench.json" 2> "$out/bench.err" || exit 1
-lean="--no-cpu-baseline --no-extra-legs --no-batch-1000"
+python3 bench.py --full > "$out/bench.json" 2> "$out/bench.err" || exit 1
+lean="--full --no-cpu-baseline --no-extra-legs --no-batch-1000"
 python3 bench.py --config 3 $lean > "$out/bench_config3.json" 2> "$out/bench_config3.err" || exit 1
 python3 bench.py --config 4 $lean > "$out/bench_config4.json" 2> "$out/bench_config4.err" || exit 1
 for cfg in 2 3 4; do
@@ -26,7 +26,7 @@ for cfg in 2 3 4; do
 done
 fi
 [ "$part" = "a" ] && { echo collected part a; exit 0; }
-lean="--no-cpu-baseline --no-extra-legs --no-batch-1000"
+lean="--full --no-cpu-baseline --no-extra-legs --no-batch-1000"
 for level in 1 2; do
   python3 bench.py $lean --half-pipeline $level > "$out/bench_half$level.json" 2> "$out/bench_half$level.err" || exit 1
 done

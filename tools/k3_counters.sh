@@ -7,7 +7,7 @@ set -o pipefail
 out=${1:-gpurun_out/k3c}
 mkdir -p "$out"
 cd /tmp && export TMPDIR=/tmp && cd - > /dev/null
-lean="--no-cpu-baseline --no-extra-legs --no-batch-1000 --steps 1 --warmup 1 --ramp-steps 0 --haystacks-per-step 3"
+lean="--full --no-cpu-baseline --no-extra-legs --no-batch-1000 --steps 1 --warmup 1 --ramp-steps 0 --haystacks-per-step 3"
 i=0
 # two counters of one hardware block per pass (five TCC counters in one pass exceed what the block can
 # collect: rocprofv3 aborts and then hangs), every pass under its own time limit

@@ -6,7 +6,7 @@ set -o pipefail
 out=${1:-gpurun_out/sq}
 mkdir -p "$out"
 cd /tmp && export TMPDIR=/tmp && cd - > /dev/null
-lean="--no-cpu-baseline --no-extra-legs --no-batch-1000 --steps 1 --warmup 1 --ramp-steps 0 --haystacks-per-step 3"
+lean="--full --no-cpu-baseline --no-extra-legs --no-batch-1000 --steps 1 --warmup 1 --ramp-steps 0 --haystacks-per-step 3"
 i=0
 for set in "SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_WAVES" \
            "SQ_INSTS_VALU SQ_INSTS_LDS SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_INSTS_SALU SQ_ACTIVE_INST_VALU" \
