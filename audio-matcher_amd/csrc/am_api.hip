@@ -69,6 +69,7 @@ static int correlate_impl(const am_needle* hc, const float* within, size_t w, in
     if (!within || !out_len || w == 0) return fail(AM_ERR_INVALID_ARG, "within must be non-empty");
     if (mode < AM_MODE_FULL || mode > AM_MODE_VALID) return fail(AM_ERR_INVALID_ARG, "bad mode");
     if (scale < AM_SCALE_NONE || scale > AM_SCALE_MY) return fail(AM_ERR_INVALID_ARG, "bad scale");
+    if ((rc = norm_check(norm_spec(h, snapshot_opts(h)), scale))) return rc;
     const size_t s = h->n;
     const size_t len = mode_len(w, s, mode);
     *out_len = len;
@@ -88,7 +89,9 @@ static int correlate_impl(const am_needle* hc, const float* within, size_t w, in
         d_out = (float*)c->io_out.p;
     }
     Opts o = snapshot_opts(h);
-    if ((rc = run_correlation(h, o, d_in, (long long)w, lead, d_out, (long long)len, scale_factor(h, scale, w)))) return rc;
+    const NormSpec nrm = norm_spec(h, o);
+    const float factor = nrm.on ? norm_factor(nrm) : scale_factor(h, scale, w);
+    if ((rc = run_correlation(h, o, d_in, (long long)w, lead, d_out, (long long)len, factor))) return rc;
     if (o.half) {
         // a half-precision transform can leave f16's range (see match_many): look at the result once and
         // compute it again in f32 if it holds a non-finite value (a bad input is dealt with below)
@@ -97,9 +100,11 @@ static int correlate_impl(const am_needle* hc, const float* within, size_t w, in
         if ((rc = nonfinite_flags(c, d_out, &whole, 1, &flag))) return rc;
         if (flag) {
             o.half = 0;
-            if ((rc = run_correlation(h, o, d_in, (long long)w, lead, d_out, (long long)len, scale_factor(h, scale, w)))) return rc;
+            if ((rc = run_correlation(h, o, d_in, (long long)w, lead, d_out, (long long)len, factor))) return rc;
         }
     }
+    // score_norm: every output divided by its window's energy (the zero padding of Full / Same counts as zeros)
+    if (nrm.on && (rc = normalise_scores(c, c->stream, nrm, d_in, (long long)w, 0, lead, (long long)s, d_out, 0, (long long)len))) return rc;
     // A NaN or an infinity in `within` makes every output of the reference's one transform per
     // window NaN (audio_matcher.rs:414-457); overlap-save confines it to the block pairs around
     // it.  Look at the window once and give the reference's answer.
@@ -172,6 +177,7 @@ int am_match_multi_device(const am_needle* const* needles, size_t n_needles, con
     am_needle* h0 = const_cast<am_needle*>(needles[0]);
     int rc = check_needle(h0);
     if (rc) return rc;
+    if (snapshot_opts(h0).score_norm) return fail(AM_ERR_INVALID_ARG, AM_NORM_UNSUPPORTED);
     std::lock_guard<std::recursive_mutex> lk(h0->ctx->mu);
     const void* src = d_haystack;
     return match_multi_many(const_cast<am_needle* const*>(needles), n_needles, &src, &len, 1, AM_FMT_F32_MONO, p, out, cap_per_needle, n_out);
@@ -189,6 +195,7 @@ int am_match_multi_batch_device(const am_needle* const* needles, size_t n_needle
     int rc = check_needle(h0);
     if (rc) return rc;
     if (n_hay == 0) return AM_OK;
+    if (snapshot_opts(h0).score_norm) return fail(AM_ERR_INVALID_ARG, AM_NORM_UNSUPPORTED);
     std::lock_guard<std::recursive_mutex> lk(h0->ctx->mu);
     return match_multi_many(const_cast<am_needle* const*>(needles), n_needles, d_haystacks, lens, n_hay, sample_format, p,
                             out, cap_per_pair, n_out);

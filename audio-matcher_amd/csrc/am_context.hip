@@ -46,6 +46,8 @@ static const char* opt_every(long long& v) { v = v < 1 ? 1 : v; return nullptr; 
 static const char* opt_arm_at(long long& v) { v = v < -1 ? -2 : v; return nullptr; }
 static const char* opt_needle_group(long long& v) { return v < 1 || v > kMaxNeedleGroup ? "needle_group out of range" : nullptr; }
 static const char* opt_pairs(long long& v) { return v < 1 || v > 64 ? "pairs_per_group out of range" : nullptr; }
+static const char* opt_score_norm(long long& v) { return v < 0 || v > 1 ? "score_norm out of range (0 = off, 1 = NCC)" : nullptr; }
+static const char* opt_floor_db(long long& v) { return v < 0 || v > 200 ? "score_norm_floor_db out of range (0..200)" : nullptr; }
 static const char* opt_distance(long long& v) {
     return v < 0 || v > 3 ? "distance_rule out of range (bit 0: inclusive, bit 1: between plateau starts)" : nullptr;
 }
@@ -70,6 +72,8 @@ static Option g_options[] = {
     {"device_redo", {1}, opt_bool, &Opts::device_redo},               // 0 = failed certificates are redone by the host path only (experiments)
     {"tail_block", {1}, opt_bool, &Opts::tail_block},                 // 1 = a haystack's last, odd block goes through the next smaller plan (TailPlan); 0 = as half of a full pair
     {"dense_scores", {0}, opt_bool, &Opts::dense},                    // 1 = K3 writes every raw score (theta = -inf): the worst case of the sparse-score path
+    {"score_norm", {0}, opt_score_norm, &Opts::score_norm},           // 1 = scores normalised by the window energy as well (NCC, am_norm.hip)
+    {"score_norm_floor_db", {60}, opt_floor_db, &Opts::score_norm_floor_db},   // ... a window more than this many dB below the needle scores 0
     // test hooks (defaults = production behaviour)
     {"debug_no_realloc", {0}, opt_bool, &Opts::debug_no_realloc},     // 1 = a scratch buffer that would be (re)allocated while a call is queueing fails the call
     {"debug_redo_arm_at", {-2}, opt_arm_at, &Opts::debug_redo_arm_at},   // >= 0: the device-side redo of a batch arms at that haystack; -1: never; -2: when a failure is seen
@@ -88,12 +92,13 @@ static Option* find_option(const char* key) {
     return nullptr;
 }
 
-// every option's value now, with the handle's own "log_n" / "half_pipeline" (>= 0) over the defaults
+// every option's value now, with the handle's own "log_n" / "half_pipeline" / "score_norm" (>= 0) over the defaults
 Opts snapshot_opts(const am_needle* h) {
     Opts o;
     for (const Option& r : g_options) o.*r.field = r.value.load(std::memory_order_relaxed);
     if (h && h->opt_log_n >= 0) o.log_n = h->opt_log_n;
     if (h && h->opt_half >= 0) o.half = h->opt_half;
+    if (h && h->opt_score_norm >= 0) o.score_norm = h->opt_score_norm;
     return o;
 }
 
@@ -404,6 +409,7 @@ static int create_needle_common(Ctx* c, float* d_needle, size_t n, am_needle** o
     double ss = 0.0;
     for (double v : part) ss += v;
     h->inv_autocorr = (float)(1.0 / ss);   // audio_matcher.rs:321-329
+    h->energy = ss;
     *out = h;
     return AM_OK;
 }
@@ -500,7 +506,7 @@ int am_shutdown(void) {
                           &c->peaks, &c->io_in, &c->io_out, &c->sum, &c->arena_cur, &c->wide_ctl, &c->wide_list, &c->wide_tiles})
             b->release();
         for (HostBuf* b : {&c->pinned, &c->hdr, &c->spill, &c->badflag, &c->failcnt}) b->release();
-        c->ranges.release(); c->range_flags.release(); c->big.release();
+        c->ranges.release(); c->range_flags.release(); c->big.release(); c->norm_blk.release();
         c->work_tail.release(); c->tail_scores.release(); c->tail_stats.release(); c->work_tail2.release();
         for (int i = 0; i < 2 * kMaxNeedleGroup; ++i) { c->grp_scores[i].release(); c->grp_stats32[i].release(); c->grp_wflags[i].release(); }
         for (int i = 0; i < kMaxNeedleGroup; ++i) c->grp_stats[i].release();
@@ -589,14 +595,19 @@ int am_needle_set_option(am_needle* h, const char* key, long long value) {
         h->opt_log_n = value < 0 ? -1 : value; return AM_OK;
     }
     if (!strcmp(key, "half_pipeline")) { h->opt_half = value < 0 ? -1 : (value >= 2 ? 2 : (value ? 1 : 0)); return AM_OK; }
-    return fail(AM_ERR_INVALID_ARG, "unknown per-handle option (log_n, half_pipeline)");
+    if (!strcmp(key, "score_norm")) {
+        if (value > 1) return fail(AM_ERR_INVALID_ARG, "score_norm out of range (-1 = default, 0 = off, 1 = NCC)");
+        h->opt_score_norm = value < 0 ? -1 : value; return AM_OK;
+    }
+    return fail(AM_ERR_INVALID_ARG, "unknown per-handle option (log_n, half_pipeline, score_norm)");
 }
 int am_needle_get_option(const am_needle* h, const char* key, long long* value) {
     if (!h || !h->ctx || !key || !value) return fail(AM_ERR_INVALID_ARG, "null pointer");
     std::lock_guard<std::recursive_mutex> lk(h->ctx->mu);
     if (!strcmp(key, "log_n")) { *value = h->opt_log_n; return AM_OK; }
     if (!strcmp(key, "half_pipeline")) { *value = h->opt_half; return AM_OK; }
-    return fail(AM_ERR_INVALID_ARG, "unknown per-handle option (log_n, half_pipeline)");
+    if (!strcmp(key, "score_norm")) { *value = h->opt_score_norm; return AM_OK; }
+    return fail(AM_ERR_INVALID_ARG, "unknown per-handle option (log_n, half_pipeline, score_norm)");
 }
 
 }  // extern "C"

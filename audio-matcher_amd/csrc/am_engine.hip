@@ -161,9 +161,10 @@ static int match_alone(am_needle* h, const void* d_hay, size_t len, const am_mat
 // One window or chunk of match_many correlated and picked on its own, synchronously: `n_scores` scores of `src`
 // into the context's set-0 score buffer, chunk `seg_idx` of the resident list (bounds `sg`) picked into the spare
 // header with a spill arena of its own, its peaks appended to `all`, shifted by `shift` samples.
+// With score_norm on (`nrm`), the chunk's scores are normalised before the pick, which then summarises them itself.
 static int pick_alone(am_needle* h, const Opts& o, const am_match_params* p, const void* src, long long src_len, float factor,
                       ScanRequest& req, long long n_scores, int seg_idx, const Segment& sg, int spare_hdr, uint64_t shift, int src_kind,
-                      std::vector<am_peak>& all) {
+                      const NormSpec& nrm, std::vector<am_peak>& all) {
     Ctx* c = h->ctx;
     const PeakPolicy pol = o.peak_policy();
     int rc;
@@ -175,6 +176,11 @@ static int pick_alone(am_needle* h, const Opts& o, const am_match_params* p, con
     if ((rc = c->scores.ensure((size_t)n_scores * sizeof(float)))) return rc;
     float* d_scores = (float*)c->scores.p;
     if ((rc = run_correlation(h, o, src, src_len, 0, d_scores, n_scores, factor, &req, src_kind))) return rc;
+    if (nrm.on) {
+        if ((rc = normalise_scores(c, c->stream, nrm, src, src_len, src_kind, 0, (long long)h->n, d_scores, sg.a, std::min(sg.b, n_scores))))
+            return rc;
+        req.fused = false;
+    }
     if ((rc = launch_pick(c, d_scores, n_scores, seg_idx, 1, p->min_prominence, (long long)p->min_distance, &req, spare_hdr, own, pol))) return rc;
     AM_HIP(hipStreamSynchronize(c->stream));
     const SegHeader& hd = static_cast<const SegHeader*>(c->hdr.p)[spare_hdr];
@@ -310,8 +316,15 @@ int match_many(am_needle* h, const void* const* d_hays, const size_t* lens, size
     const size_t s = h->n;
     if (p->chunk == 0) return fail(AM_ERR_INVALID_ARG, "chunk must be > 0");
     if (p->scale < AM_SCALE_NONE || p->scale > AM_SCALE_MY) return fail(AM_ERR_INVALID_ARG, "bad scale");
+    // Option score_norm: K3 writes every raw score scaled by 1 / sqrt(needle energy), and each haystack's scores are
+    // divided by their windows' energies on the pick's stream before its pick, which summarises them itself.  The
+    // sparse-score certificate bounds raw scores only, and the needle's score history (hist_min) is neither read nor fed.
+    const NormSpec nrm = norm_spec(h, o);
+    if (nrm.on && (pre || part)) return fail(AM_ERR_INVALID_ARG, AM_NORM_UNSUPPORTED);
+    int rc = norm_check(nrm, p->scale);
+    if (rc) return rc;
     const bool my = p->scale == AM_SCALE_MY;
-    const float factor = scale_factor(h, p->scale, (size_t)(p->chunk + p->overlap));
+    const float factor = nrm.on ? norm_factor(nrm) : scale_factor(h, p->scale, (size_t)(p->chunk + p->overlap));
     // Raw scores are written only for the 32-score runs whose maximum reaches their K3 tile's write
     // threshold: the tile's own minimum in the block plus half a prominence (am_fft.hip, k3_finish).
     // The peak kernel certifies per chunk that every threshold was low enough; a chunk that fails
@@ -319,9 +332,9 @@ int match_many(am_needle* h, const void* const* d_hays, const size_t* lens, size
     // run written.
     const int sm = p->scale == AM_SCALE_LIB ? 1 : 0;
     ScanRequest scan{};
-    scan.margin = write_margin(o, p);
+    scan.margin = nrm.on ? -1.0f : write_margin(o, p);
     const bool sparse_ok = scan.margin >= 0.0f;
-    scan.hist_min = h->hist_min(sm);   // (of the haystacks before this call: the whole batch is queued before any result is back)
+    scan.hist_min = nrm.on ? FLT_MAX : h->hist_min(sm);   // (of the haystacks before this call: the whole batch is queued before any result is back)
     scan.seg_c = (long long)p->chunk;
     scan.seg_d = (long long)(p->chunk + p->overlap) - (long long)s;
     for (size_t k = 0; k < n_hay; ++k) n_out[G(k)] = 0;
@@ -332,7 +345,6 @@ int match_many(am_needle* h, const void* const* d_hays, const size_t* lens, size
     const size_t nsegs = segs.size();
     if (nsegs == 0 && cp.short_segs.empty()) return AM_OK;
     if (cp.too_many(1)) return fail(AM_ERR_INVALID_ARG, "chunk size too small for this haystack (more than 2^18 chunks)");
-    int rc;
     size_t n_active = 0;
     for (size_t k = 0; k < n_hay; ++k) n_active += cp.ns(k) > 0;
     ScoreSets sets(c, o, n_active);
@@ -399,6 +411,11 @@ int match_many(am_needle* h, const void* const* d_hays, const size_t* lens, size
     int* h_bad = static_cast<int*>(c->badflag.p);
     memset(h_bad, 0, sizeof(int) * n_hay);
     if ((rc = c->failcnt.ensure(nsegs + 1))) return rc;
+    if (nrm.on) {   // (the block energies of the largest haystack, before anything is queued)
+        size_t max_len = 0;
+        for (size_t k = 0; k < n_hay; ++k) if (cp.ns(k) > 0) max_len = std::max(max_len, lens[k]);
+        if ((rc = norm_reserve(c, (long long)max_len))) return rc;
+    }
     unsigned char* h_fail = static_cast<unsigned char*>(c->failcnt.p);
     memset(h_fail, 0, nsegs + 1);
     // A chunk whose certificate fails is redone on the device when the batch overlaps picks and transforms:
@@ -502,8 +519,16 @@ int match_many(am_needle* h, const void* const* d_hays, const size_t* lens, size
             scan.sparse.fail_flags = h_fail + seg_off[k];
             scan.sparse.redo_pairs = (redo_armed && scan.redo_ok) ? d_redo : nullptr;
         }
+        ScanRequest pick_req = scan;
+        if (nrm.on) {
+            // behind K3 and the tail's commit (both ordered before the pick's stream by now), in front of the pick; the
+            // samples are the caller's (or io_in, which nothing overwrites before this call has drained)
+            if ((rc = normalise_scores(c, sets.pick_stream(), nrm, d_hays[k], (long long)lens[k], src_kind, 0, (long long)s, d_scores, 0, out_count)))
+                return rc;
+            pick_req.fused = false;
+        }
         if ((rc = launch_pick(c, d_scores, out_count, seg_off[k], ns, p->min_prominence,
-                              (long long)p->min_distance, &scan, seg_off[k], arena, pol, sets.pick_stream()))) return rc;
+                              (long long)p->min_distance, &pick_req, seg_off[k], arena, pol, sets.pick_stream()))) return rc;
         if (scan.fused && scan.sparse.redo_pairs) {
             ScanCfg cfg = scan.redo_cfg;
             cfg.margin = -1.0f;
@@ -538,7 +563,7 @@ int match_many(am_needle* h, const void* const* d_hays, const size_t* lens, size
         // tone, concentrates in a few bins).  The haystack is matched again in f32, after every other
         // result of this call has been collected (the pass reuses the call's result area).
         if (h_bad[k] && o.half) { retry_f32.push_back(k); continue; }
-        if (!my && !h_bad[k] && s1 > s0) {   // (a haystack with non-finite scores teaches the threshold nothing)
+        if (!my && !nrm.on && !h_bad[k] && s1 > s0) {   // (a haystack with non-finite scores teaches the threshold nothing; NCC scores are no raw scores)
             std::vector<float> mins;
             int failed = 0;
             for (int i = s0; i < s1; ++i) { mins.push_back(h_hdr[i].seg_min); failed += h_fail[i] != 0; }
@@ -573,7 +598,7 @@ int match_many(am_needle* h, const void* const* d_hays, const size_t* lens, size
                 ScanRequest one{};
                 one.margin = -1.0f;
                 if ((rc = pick_alone(h, o, p, advance_src(d_hays[k], (size_t)sg.a), (long long)cp.widths[i], factor, one, sg.b - sg.a,
-                                     local_seg, Segment{0, sg.b - sg.a}, spare_hdr, (uint64_t)sg.a, src_kind, all))) return rc;
+                                     local_seg, Segment{0, sg.b - sg.a}, spare_hdr, (uint64_t)sg.a, src_kind, nrm, all))) return rc;
                 continue;
             }
             if (!(h_hdr[i].overflow & 7)) { append_header_peaks(h_hdr[i], arena, all); continue; }
@@ -586,7 +611,7 @@ int match_many(am_needle* h, const void* const* d_hays, const size_t* lens, size
             ScanRequest full = scan;
             full.margin = -1.0f;
             full.range_a = sg.a; full.range_b = sg.b;
-            if ((rc = pick_alone(h, o, p, d_hays[k], (long long)lens[k], factor, full, out_count, i, sg, spare_hdr, 0, src_kind, all))) return rc;
+            if ((rc = pick_alone(h, o, p, d_hays[k], (long long)lens[k], factor, full, out_count, i, sg, spare_hdr, 0, src_kind, nrm, all))) return rc;
         }
         // second pass (MyConvolve scaling only): the shorter windows at the end of the haystack, at their offsets (audio_matcher.rs:126)
         for (int i = cp.short_off[k]; i < cp.short_off[k + 1]; ++i) {
@@ -594,7 +619,7 @@ int match_many(am_needle* h, const void* const* d_hays, const size_t* lens, size
             ScanRequest one{};
             one.margin = -1.0f;
             if ((rc = pick_alone(h, o, p, advance_src(d_hays[k], (size_t)sg.a), (long long)cp.short_w[i], scale_factor(h, p->scale, cp.short_w[i]),
-                                 one, sg.b - sg.a, (int)nsegs + i, Segment{0, sg.b - sg.a}, spare_hdr, (uint64_t)sg.a, src_kind, all))) return rc;
+                                 one, sg.b - sg.a, (int)nsegs + i, Segment{0, sg.b - sg.a}, spare_hdr, (uint64_t)sg.a, src_kind, nrm, all))) return rc;
         }
         if (part) {   // unmerged, in window order (audio_matcher.rs:132-133), at their positions in the whole haystack
             for (am_peak& q : all) { q.start += part->first_sample; q.end += part->first_sample; }
@@ -641,6 +666,7 @@ int match_multi_many(am_needle* const* needles, size_t nn, const void* const* d_
         if (!needles[j] || needles[j]->ctx != c) return fail(AM_ERR_INVALID_ARG, "needles must live on one device");
         if (needles[j]->n != s) return fail(AM_ERR_INVALID_ARG, "am_match_multi: needles must have equal length");
     }
+    if (o.score_norm) return fail(AM_ERR_INVALID_ARG, AM_NORM_UNSUPPORTED);
     if (p->chunk == 0) return fail(AM_ERR_INVALID_ARG, "chunk must be > 0");
     if (p->scale != AM_SCALE_NONE && p->scale != AM_SCALE_LIB)
         return fail(AM_ERR_INVALID_ARG, "am_match_multi supports AM_SCALE_NONE and AM_SCALE_LIB");

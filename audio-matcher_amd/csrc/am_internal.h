@@ -43,6 +43,7 @@ struct Opts {
     long long log_n, pairs_per_group, half, batch_overlap, needle_group, dense, device_redo, debug_no_realloc, debug_redo_arm_at;
     long long peak_filter_order, distance_rule, tail_window, surrounding_from, k3_group, pick_group, tail_block, host_pick_wait;
     long long profile_mask, profile_every, pick_priority;
+    long long score_norm, score_norm_floor_db;
     PeakPolicy peak_policy() const { return PeakPolicy{(int)peak_filter_order, (int)(distance_rule & 1), (int)((distance_rule >> 1) & 1)}; }
 };
 static const float kHalfGain = 1024.0f;      // keeps the stored values of a normalised score near 1
@@ -141,6 +142,7 @@ struct Ctx {
     std::recursive_mutex mu;
     std::map<int, Plan> plans;
     DevBuf work, work2, scores, stats, stats32, wflags, segs, peaks, io_in, io_out, sum, arena_cur, wide_ctl, wide_list, wide_tiles;
+    DevBuf norm_blk;   // block energies of the haystack being normalised (option score_norm; used on one stream at a time)
     // second set of the score-side buffers: in a batch the peak pick of haystack k runs on
     // stream2 beside the transforms of haystack k+1, which then need their own set
     DevBuf scores_b, stats_b, stats32_b, wflags_b, peaks_b;
@@ -205,6 +207,7 @@ struct am_needle {
     float* d_needle = nullptr;
     size_t n = 0;
     float inv_autocorr = 0.f;
+    double energy = 0.0;   // sum(needle^2) in f64 (launch_sumsq): the needle's half of the score_norm denominator
     std::map<int, float2*> spectra;  // logN -> conj(H)/N in pipeline layout
     std::map<int, unsigned*> spectra16;   // logN -> the same as scaled __half2 points (half_pipeline = 2)
     std::map<int, unsigned*> spectra16m;  // logN -> the same conjugated, in [a'][b'][c'] order (option k2_mfma)
@@ -236,7 +239,7 @@ struct am_needle {
         return m;
     }
     // per-handle overrides of the process-wide option defaults (-1 = follow the default)
-    long long opt_log_n = -1, opt_half = -1;
+    long long opt_log_n = -1, opt_half = -1, opt_score_norm = -1;
     // Needle partitioning (needles longer than kSegmentFrom samples): sub-handles over slices of d_needle
     // (not owned), each with its own spectra; segment i starts at sample seg_off[i] of the needle.
     std::vector<am_needle*> segments;
@@ -346,6 +349,18 @@ Opts snapshot_opts(const am_needle* h);
 int check_needle(const am_needle* h);
 HalfScale half_scale(const am_needle* h, const Opts& o, const PlanDev& pl);
 int needle_k2_spectrum(am_needle* h, const Opts& o, const Plan* pl, const float2** hc, HalfScale* hs);
+
+// ---- am_norm.hip ----
+// Option "score_norm" as a call sees it: on, the needle's energy and the floor (scores of windows with less energy are 0)
+struct NormSpec { bool on; double energy, thr; };
+NormSpec norm_spec(const am_needle* h, const Opts& o);
+int norm_check(const NormSpec& ns, int scale);   // AM_ERR_INVALID_ARG unless the scale is AM_SCALE_LIB (when on)
+float norm_factor(const NormSpec& ns);           // K3's factor under score_norm: 1 / sqrt(needle energy)
+int norm_reserve(Ctx* c, long long max_src_len);
+// scores [a, b) of the window sequence of src (window of score t = [t - lead, t - lead + s)), normalised in place on `st`
+int normalise_scores(Ctx* c, hipStream_t st, const NormSpec& ns, const void* src, long long src_len, int src_kind, long long lead,
+                     long long s, float* scores, long long a, long long b);
+#define AM_NORM_UNSUPPORTED "score_norm: not supported by this entry point"
 
 // ---- am_correlate.hip ----
 int plan_geometry(size_t s, long long out_count, const Opts& o, Geometry* g);

@@ -257,4 +257,25 @@ hipError_t launch_synth_pcm16(hipStream_t st, int16_t* out, uint32_t seed, uint3
 hipError_t launch_add_pcm16(hipStream_t st, int16_t* dst, const int16_t* src, long long frames);
 hipError_t launch_pcm_downmix(hipStream_t st, const int16_t* in, long long frames, float* out);
 
+// ---- am_norm.hip: window-energy normalisation (option "score_norm") ----
+constexpr int kNormBlock = 1024;   // samples per block energy
+constexpr int kNormTile = 2048;    // scores per workgroup of the normalising kernel
+inline long long norm_blocks(long long src_len) { return (src_len + kNormBlock - 1) / kNormBlock; }
+// blk[i] = sum of x^2 over samples [i kNormBlock, (i + 1) kNormBlock) in f64, non-finite samples as 0
+hipError_t launch_block_energy(hipStream_t st, const void* src, long long src_len, int src_kind, double* blk);
+// scores[t], t in [a, b), window [t - lead, t - lead + s) of src: multiplied by 1 / sqrt(window energy), or 0 when that
+// energy is below thr; non-finite scores are left as they are
+struct NormJob {
+    const void* src;
+    long long src_len;
+    int src_kind;
+    long long lead, s;
+    const double* blk;   // launch_block_energy of src
+    long long nblk;
+    double thr;
+    float* scores;
+    long long a, b;
+};
+hipError_t launch_norm_scores(hipStream_t st, const NormJob& j);
+
 }  // namespace am

@@ -1,0 +1,204 @@
+// am_norm.hip -- window-energy normalised scores (option "score_norm", include/audiomatch.h):
+//   ncc(t) = corr(t) / sqrt(sum(needle^2) * sum_{i=t-lead}^{t-lead+S-1} x_i^2),  x = 0 outside [0, len)
+// K3 writes corr(t) / sqrt(sum(needle^2)) (norm_factor); the kernels here divide by the window's own energy.
+//
+// Two kernels on the stream that will read the scores:
+//   block_energy   one f64 sum(x^2) per block of kNormBlock samples (non-finite samples count as 0)
+//   norm_scores    one workgroup per tile of kNormTile consecutive scores.  A window's energy is assembled only from
+//                  non-negative pieces: the whole blocks every window of the tile covers, plus a suffix sum over the
+//                  tile's head span and a prefix sum over its tail span (f64 scans in LDS).  No difference of a global
+//                  prefix array: over an hour at full scale P(t+S) - P(t) cancels to about 1e-8, which is above the
+//                  floor of a quiet needle, and a window of digital silence must come out as exactly 0.
+//                  Needles shorter than kNormTile + 2 kNormBlock take a direct path: one local prefix scan over the
+//                  tile's kNormTile + S - 1 samples.
+// Every score depends on its index, the samples and the needle only (tiles start at multiples of kNormTile of the
+// score array, the reductions run in a fixed order): a haystack's bits do not depend on the batch it travels in.
+#include "am_internal.h"
+
+namespace am {
+
+namespace {
+
+constexpr int kNormThreads = 256;
+constexpr int kNormPer = kNormTile / kNormThreads;               // scores per thread
+constexpr int kNormSpan = kNormTile + (kNormTile + 2 * kNormBlock);   // LDS span of the direct path (longest)
+static_assert(kNormTile % kNormThreads == 0, "tile must split evenly over the workgroup");
+static_assert(kNormBlock % kNormThreads == 0, "block must split evenly over the workgroup");
+
+// (l as f32 + r as f32) * 0.5 * (1 / 65535), the down-mix K1 applies (am_fft.hip, downmix_s16), bit for bit
+__device__ __forceinline__ float norm_downmix(short2 lr) {
+    return __fmul_rn((float)((int)lr.x + (int)lr.y), 0.5f * (1.0f / 65535.0f));
+}
+// x_i^2 in f64 (exact for an f32 x); 0 outside [0, len) and for a non-finite sample
+__device__ __forceinline__ double norm_sq(const void* __restrict__ src, long long i, long long len, int kind) {
+    if (i < 0 || i >= len) return 0.0;
+    const float v = kind ? norm_downmix(static_cast<const short2*>(src)[i]) : static_cast<const float*>(src)[i];
+    if (!__builtin_isfinite(v)) return 0.0;
+    const double d = (double)v;
+    return d * d;
+}
+__device__ __forceinline__ long long floor_div(long long x, long long b) { return x >= 0 ? x / b : -((-x + b - 1) / b); }
+
+// Sum of one value per thread, in a fixed order (every thread gets the result).  `ws`: kNormThreads / 64 doubles.
+__device__ double block_sum(double v, double* ws) {
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    if (lane == 0) ws[w] = v;
+    __syncthreads();
+    double t = 0.0;
+    for (int i = 0; i < kNormThreads / 64; ++i) t += ws[i];
+    __syncthreads();
+    return t;
+}
+
+// In-place inclusive scan of buf[0 .. n): prefix sums (REV = false) or suffix sums (REV = true).  Thread i takes a
+// contiguous run of the (logical) sequence; its start value is the wave's exclusive scan of the runs before plus the
+// totals of the waves before.  Every entry is a sum of non-negative terms (no subtraction).
+template <bool REV>
+__device__ void block_scan(double* buf, int n, double* ws) {
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const int per = (n + kNormThreads - 1) / kNormThreads;
+    const int lo = min(tid * per, n), hi = min(lo + per, n);
+    double s = 0.0;
+    for (int q = lo; q < hi; ++q) s += buf[REV ? n - 1 - q : q];
+    double incl = s;
+    for (int off = 1; off < 64; off <<= 1) {
+        const double v = __shfl_up(incl, off, 64);
+        if (lane >= off) incl += v;
+    }
+    double excl = __shfl_up(incl, 1, 64);
+    if (lane == 0) excl = 0.0;
+    if (lane == 63) ws[w] = incl;
+    __syncthreads();
+    double run = 0.0;
+    for (int i = 0; i < w; ++i) run += ws[i];
+    run += excl;
+    for (int q = lo; q < hi; ++q) {
+        const int k = REV ? n - 1 - q : q;
+        run += buf[k];
+        buf[k] = run;
+    }
+    __syncthreads();
+}
+
+__global__ __launch_bounds__(kNormThreads) void block_energy_kernel(const void* __restrict__ src, long long len, int kind, double* __restrict__ blk) {
+    __shared__ double ws[kNormThreads / 64];
+    const long long base = (long long)blockIdx.x * kNormBlock;
+    double s = 0.0;
+    for (int r = 0; r < kNormBlock / kNormThreads; ++r) s += norm_sq(src, base + threadIdx.x + r * kNormThreads, len, kind);
+    s = block_sum(s, ws);
+    if (threadIdx.x == 0) blk[blockIdx.x] = s;
+}
+
+__global__ __launch_bounds__(kNormThreads) void norm_scores_kernel(NormJob j, long long tile0) {
+    __shared__ double buf[kNormSpan];
+    __shared__ double ws[kNormThreads / 64];
+    const int tid = threadIdx.x;
+    const long long t0 = (tile0 + blockIdx.x) * kNormTile;
+    const long long u0 = t0 - j.lead;   // first sample of the tile's first window
+    const long long S = j.s, B = kNormBlock;
+    double e[kNormPer];
+    if (S >= kNormTile + 2 * kNormBlock) {
+        // shared whole blocks [A, Z): A at or behind every window start of the tile, Z at or before every window end
+        const long long A = floor_div(u0 + kNormTile - 1 + B - 1, B) * B;
+        const long long Z = floor_div(u0 + S, B) * B;
+        // head pieces [u, A): suffix sums over [u0, A)
+        const int nh = (int)(A - u0);
+        for (int q = tid; q < nh; q += kNormThreads) buf[q] = norm_sq(j.src, u0 + q, j.src_len, j.src_kind);
+        __syncthreads();
+        block_scan<true>(buf, nh, ws);
+        for (int r = 0; r < kNormPer; ++r) {
+            const int k = tid + r * kNormThreads;
+            e[r] = k < nh ? buf[k] : 0.0;
+        }
+        __syncthreads();
+        // the whole blocks
+        const long long jlo = max(A / B, 0ll), jhi = min(Z / B, j.nblk);
+        double m = 0.0;
+        for (long long q = jlo + tid; q < jhi; q += kNormThreads) m += j.blk[q];
+        m = block_sum(m, ws);
+        // tail pieces [Z, u + S): prefix sums over [Z, u0 + kNormTile - 1 + S)
+        const int nt = (int)(u0 + kNormTile - 1 + S - Z);
+        for (int q = tid; q < nt; q += kNormThreads) buf[q] = norm_sq(j.src, Z + q, j.src_len, j.src_kind);
+        __syncthreads();
+        block_scan<false>(buf, nt, ws);
+        for (int r = 0; r < kNormPer; ++r) {
+            const long long k = u0 + tid + r * kNormThreads + S - Z;   // tail piece length
+            e[r] = (e[r] + m) + (k > 0 ? buf[k - 1] : 0.0);
+        }
+    } else {
+        // direct path: one prefix scan over the tile's samples [u0, u0 + kNormTile - 1 + S)
+        const int n = (int)(kNormTile - 1 + S);
+        for (int q = tid; q < n; q += kNormThreads) buf[q] = norm_sq(j.src, u0 + q, j.src_len, j.src_kind);
+        __syncthreads();
+        block_scan<false>(buf, n, ws);
+        for (int r = 0; r < kNormPer; ++r) {
+            const int k = tid + r * kNormThreads;
+            e[r] = buf[k + S - 1] - (k > 0 ? buf[k - 1] : 0.0);   // (local sums: a window of zeros gives exactly 0)
+        }
+    }
+    for (int r = 0; r < kNormPer; ++r) {
+        const long long t = t0 + tid + r * kNormThreads;
+        if (t < j.a || t >= j.b) continue;
+        const float raw = j.scores[t];
+        if (!__builtin_isfinite(raw)) continue;   // (a non-finite score stays what it is: the callers' classification reads it)
+        const double E = e[r];
+        j.scores[t] = (E >= j.thr && E > 0.0) ? (float)((double)raw / sqrt(E)) : 0.0f;
+    }
+}
+
+}  // namespace
+
+hipError_t launch_block_energy(hipStream_t st, const void* src, long long src_len, int src_kind, double* blk) {
+    const long long nblk = norm_blocks(src_len);
+    if (nblk <= 0) return hipSuccess;
+    hipLaunchKernelGGL(block_energy_kernel, dim3((unsigned)nblk), dim3(kNormThreads), 0, st, src, src_len, src_kind, blk);
+    return hipGetLastError();
+}
+
+hipError_t launch_norm_scores(hipStream_t st, const NormJob& j) {
+    if (j.b <= j.a) return hipSuccess;
+    const long long tile0 = j.a / kNormTile, tile1 = (j.b + kNormTile - 1) / kNormTile;
+    hipLaunchKernelGGL(norm_scores_kernel, dim3((unsigned)(tile1 - tile0)), dim3(kNormThreads), 0, st, j, tile0);
+    return hipGetLastError();
+}
+
+// ---- host side -------------------------------------------------------------------------------------------------------
+
+NormSpec norm_spec(const am_needle* h, const Opts& o) {
+    NormSpec ns{};
+    ns.on = o.score_norm != 0;
+    ns.energy = h->energy;
+    ns.thr = h->energy * std::pow(10.0, -(double)o.score_norm_floor_db / 10.0);
+    return ns;
+}
+
+int norm_check(const NormSpec& ns, int scale) {
+    if (ns.on && scale != AM_SCALE_LIB)
+        return fail(AM_ERR_INVALID_ARG, "score_norm = 1 requires scale = AM_SCALE_LIB (the needle energy is divided out of the scores)");
+    return AM_OK;
+}
+
+float norm_factor(const NormSpec& ns) {
+    return ns.energy > 0.0 ? (float)(1.0 / std::sqrt(ns.energy)) : 0.0f;
+}
+
+int norm_reserve(Ctx* c, long long max_src_len) {
+    return c->norm_blk.ensure(sizeof(double) * (size_t)std::max<long long>(norm_blocks(max_src_len), 1));
+}
+
+int normalise_scores(Ctx* c, hipStream_t st, const NormSpec& ns, const void* src, long long src_len, int src_kind, long long lead,
+                     long long s, float* scores, long long a, long long b) {
+    if (b <= a) return AM_OK;
+    int rc;
+    if ((rc = norm_reserve(c, src_len))) return rc;
+    NormJob j{};
+    j.src = src; j.src_len = src_len; j.src_kind = src_kind; j.lead = lead; j.s = s;
+    j.blk = static_cast<const double*>(c->norm_blk.p); j.nblk = norm_blocks(src_len);
+    j.thr = ns.thr; j.scores = scores; j.a = a; j.b = b;
+    { ProfScope ps(c, KN_OTHER, st); AM_HIP(launch_block_energy(st, src, src_len, src_kind, static_cast<double*>(c->norm_blk.p))); }
+    { ProfScope ps(c, KN_OTHER, st); AM_HIP(launch_norm_scores(st, j)); }
+    return AM_OK;
+}
+
+}  // namespace am

@@ -231,6 +231,7 @@ int pool_run(am_pool* pool, const PoolJob& job, const void* const* hays, const s
              am_peak* out, size_t cap, size_t* n_out, bool host) {
     if (!pool || !hays || !lens || !p || !n_out || (!out && cap)) return fail(AM_ERR_INVALID_ARG, "null pointer");
     if (job.fmt != AM_FMT_F32_MONO && job.fmt != AM_FMT_S16_STEREO) return fail(AM_ERR_INVALID_ARG, "bad sample format");
+    if (job.multi && snapshot_opts(nullptr).score_norm) return fail(AM_ERR_INVALID_ARG, AM_NORM_UNSUPPORTED);
     std::lock_guard<std::mutex> lk(pool->mu);
     const size_t nslots = pool->slots.size();
     const size_t nn = pool->slots.empty() ? 0 : pool->slots[0].needles.size();
@@ -329,6 +330,7 @@ int am_match_part_device(const am_needle* hc, const void* d_part, size_t n_sampl
     if (rc) return rc;
     if (!p || !n_out || (!out && cap)) return fail(AM_ERR_INVALID_ARG, "null pointer");
     if (sample_format != AM_FMT_F32_MONO && sample_format != AM_FMT_S16_STEREO) return fail(AM_ERR_INVALID_ARG, "bad sample format");
+    if (snapshot_opts(h).score_norm) return fail(AM_ERR_INVALID_ARG, AM_NORM_UNSUPPORTED);
     *n_out = 0;
     if (n_windows == 0 || n_samples == 0) return AM_OK;
     if (!d_part) return fail(AM_ERR_INVALID_ARG, "null pointer");
@@ -425,12 +427,14 @@ int pool_long(am_pool* pool, const void* host_hay, const void* const* d_parts, s
 int am_pool_match_long(am_pool* pool, const void* haystack, size_t len, int sample_format, const am_match_params* p,
                        am_peak* out, size_t cap, size_t* n_out) {
     if (!haystack && len) return fail(AM_ERR_INVALID_ARG, "null pointer");
+    if (snapshot_opts(nullptr).score_norm) return fail(AM_ERR_INVALID_ARG, AM_NORM_UNSUPPORTED);
     return pool_long(pool, haystack, nullptr, len, sample_format, p, out, cap, n_out);
 }
 
 int am_pool_match_long_device(am_pool* pool, const void* const* d_parts, size_t len, int sample_format, const am_match_params* p,
                               am_peak* out, size_t cap, size_t* n_out) {
     if (!d_parts) return fail(AM_ERR_INVALID_ARG, "null pointer");
+    if (snapshot_opts(nullptr).score_norm) return fail(AM_ERR_INVALID_ARG, AM_NORM_UNSUPPORTED);
     return pool_long(pool, nullptr, d_parts, len, sample_format, p, out, cap, n_out);
 }
 

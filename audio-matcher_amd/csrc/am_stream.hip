@@ -73,6 +73,7 @@ int am_match_stream_begin(const am_needle* hc, int sample_format, size_t expecte
     if (sample_format != AM_FMT_F32_MONO && sample_format != AM_FMT_S16_STEREO) return fail(AM_ERR_INVALID_ARG, "bad sample format");
     if (p->chunk == 0) return fail(AM_ERR_INVALID_ARG, "chunk must be > 0");
     if (p->scale < AM_SCALE_NONE || p->scale > AM_SCALE_MY) return fail(AM_ERR_INVALID_ARG, "bad scale");
+    if (snapshot_opts(h).score_norm) return fail(AM_ERR_INVALID_ARG, AM_NORM_UNSUPPORTED);
     Ctx* c = h->ctx;
     std::lock_guard<std::recursive_mutex> lk(c->mu);
     am_stream* st = new am_stream();
@@ -220,6 +221,7 @@ int am_match_stream_finish(am_stream* st, am_peak* out, size_t cap, size_t* n_ou
     am_needle* h = st->h;
     int rc = check_needle(h);
     if (rc) return rc;
+    if (snapshot_opts(h).score_norm) return fail(AM_ERR_INVALID_ARG, AM_NORM_UNSUPPORTED);
     Ctx* c = h->ctx;
     std::lock_guard<std::recursive_mutex> lk(c->mu);
     *n_out = 0;

@@ -71,12 +71,35 @@ struct Arguments {
     int always_answer = -1;                   // common::args::input::Inputs: -y -> 1, -n -> 0, else ask
     int verbosity = 1;                        // OutputLevel: --silent 0, default 1 (info), --debug 2, --trace 3
     int device = 0;                           // extension: GPU ordinal
+    bool normalize = false;                   // extension: --normalize, window-energy normalised scores (option "score_norm")
+    std::optional<int> normalize_floor_db;    // extension: --normalize-floor DB (option "score_norm_floor_db", 0..200)
+    bool help = false;                        // --help
 
     std::uint64_t chunk_size_ms() const { return chunk_ms.value_or(60ull * 1000); }
     std::uint64_t distance_msec() const { return distance_ms.value_or(8ull * 60 * 1000); }
 };
 
 struct ArgError : std::runtime_error { using std::runtime_error::runtime_error; };
+
+inline const char* usage_text() {
+    return "usage: audiomatch <FILE>... --snippet <FILE> [options]\n"
+           "  -p, --prominence P     minimal prominence of a hit, in percent (default 13)\n"
+           "  --distance D           minimal distance between hits (default 8m)\n"
+           "  --chunk-size D         length of one chunk (default 60s)\n"
+           "  -o, --out FILE         label file (one input file only); --no-out: none\n"
+           "  --dry-run              print the label file instead of writing it\n"
+           "  --skip-existing        skip inputs whose label file exists\n"
+           "  -y, --yes / -n, --no   answer questions without asking\n"
+           "  --silent, --debug, --trace   output level\n"
+           "  --device N             GPU ordinal (default 0)\n"
+           "  --normalize            score every offset by normalised cross-correlation (NCC): the correlation divided\n"
+           "                         by the energies of the snippet AND of the window it is compared with, in [-1, 1].\n"
+           "                         Hits no longer depend on the recording's level; the prominence is then a fraction\n"
+           "                         of a perfect match, not of the snippet's energy (default: off)\n"
+           "  --normalize-floor DB   with --normalize: windows more than DB decibels below the snippet's energy score 0\n"
+           "                         (0..200, default 60)\n"
+           "  --help                 this text\n";
+}
 
 inline Arguments parse_arguments(int argc, const char* const* argv) {
     Arguments a;
@@ -106,6 +129,16 @@ inline Arguments parse_arguments(int argc, const char* const* argv) {
         else if (s == "--debug") a.verbosity = 2;
         else if (s == "--trace") a.verbosity = 3;
         else if (s == "--device") a.device = std::atoi(need(i).c_str());
+        else if (s == "--normalize") a.normalize = true;
+        else if (s == "--normalize-floor") {
+            const std::string v = need(i);
+            char* end = nullptr;
+            const long db = std::strtol(v.c_str(), &end, 10);
+            if (v.empty() || *end != '\0' || db < 0 || db > 200)
+                throw ArgError("invalid value '" + v + "' for --normalize-floor (whole decibels, 0..200)");
+            a.normalize_floor_db = (int)db;
+        }
+        else if (s == "-h" || s == "--help") { a.help = true; return a; }
         else if (!s.empty() && s[0] == '-' && s != "-") throw ArgError("unknown option " + s);
         else if (!s.empty()) a.within.push_back(s);
     }

@@ -39,6 +39,10 @@ int main(int argc, char** argv) {
         std::fprintf(stderr, "error: %s\n", e.what());
         return 2;
     }
+    if (args.help) {
+        std::printf("%s", usage_text());
+        return 0;
+    }
     try {
         const Pcm snippet = read_wav(args.snippet);                           // mod.rs:29
         const std::uint32_t sr = snippet.sample_rate;
@@ -47,6 +51,10 @@ int main(int argc, char** argv) {
         am_needle* algo = nullptr;                                            // mod.rs:34: LibConvolve::new
         if (am_needle_create(args.device, sample_data.data(), sample_data.size(), &algo) != AM_OK)
             throw std::runtime_error(std::string("am_needle_create: ") + am_last_error_string());
+        if (args.normalize_floor_db && am_set_option("score_norm_floor_db", *args.normalize_floor_db) != AM_OK)
+            throw std::runtime_error(std::string("--normalize-floor: ") + am_last_error_string());
+        if (args.normalize && am_needle_set_option(algo, "score_norm", 1) != AM_OK)
+            throw std::runtime_error(std::string("--normalize: ") + am_last_error_string());
         if (args.verbosity >= 2) am_set_progress_callback(progress, nullptr);
         int rc_all = 0;
         for (const std::string& main_file : args.within) {                    // mod.rs:42

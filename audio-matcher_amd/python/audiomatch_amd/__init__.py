@@ -369,15 +369,27 @@ class Config:
             overshadow_distance_s=self.distance_s, scale=int(scale))
 
 
-class HipConvolve:
-    """CorrelateAlgo<f32> (audio_matcher.rs:65-76) backed by the HIP library."""
+# Option keys of window-energy normalised scores (NCC, include/audiomatch.h): "score_norm" 0 = off, 1 = NCC (process
+# default, or per handle: HipConvolve(score_norm=...)); "score_norm_floor_db": windows more than that many dB below the
+# needle score 0.
+OPT_SCORE_NORM = "score_norm"
+OPT_SCORE_NORM_FLOOR_DB = "score_norm_floor_db"
 
-    def __init__(self, sample_data, device: int = 0):
+
+class HipConvolve:
+    """CorrelateAlgo<f32> (audio_matcher.rs:65-76) backed by the HIP library.
+
+    score_norm: None follows the process default; True / False fixes this handle's "score_norm" (NCC scores,
+    which need the LIB scale)."""
+
+    def __init__(self, sample_data, device: int = 0, score_norm=None):
         a = np.ascontiguousarray(sample_data, dtype=np.float32)
         self.device = device
         self._h = C.c_void_p()
         _check(lib().am_needle_create(device, a.ctypes.data, a.size, C.byref(self._h)))
         self.sample_len = int(a.size)
+        if score_norm is not None:
+            self.set_option(OPT_SCORE_NORM, int(bool(score_norm)))
 
     @classmethod
     def from_device(cls, device: int, ptr: int, n: int) -> "HipConvolve":
@@ -407,7 +419,7 @@ class HipConvolve:
         return [Peak(int(b.start), int(b.end), float(b.height), float(b.prominence)) for b in buf[:n.value]]
 
     def set_option(self, key: str, value: int):
-        """Per-handle "log_n" / "half_pipeline" (-1 = follow the process default)."""
+        """Per-handle "log_n" / "half_pipeline" / "score_norm" (-1 = follow the process default)."""
         _check(lib().am_needle_set_option(self._h, key.encode(), int(value)))
 
     def get_option(self, key: str) -> int:
@@ -572,7 +584,9 @@ class Pool:
     """The haystack loop of matcher::run (matcher/mod.rs:42-87) over several GPUs: the needle
     replicated per device, haystack k matched on slot k mod n (am_pool_*)."""
 
-    def __init__(self, sample_data, devices=None):
+    def __init__(self, sample_data, devices=None, score_norm=None):
+        """score_norm: None follows the process default ("score_norm"); True / False fixes it on every slot's
+        needle handle (NCC scores, which need the LIB scale)."""
         a = np.ascontiguousarray(sample_data, dtype=np.float32)
         self._p = C.c_void_p()
         if devices is None:
@@ -583,6 +597,11 @@ class Pool:
         n = C.c_size_t(0)
         _check(lib().am_pool_size(self._p, C.byref(n)))
         self.size = n.value
+        if score_norm is not None:
+            for slot in range(self.size):
+                h = C.c_void_p()
+                _check(lib().am_pool_slot(self._p, slot, None, C.byref(h)))
+                _check(lib().am_needle_set_option(h, OPT_SCORE_NORM.encode(), int(bool(score_norm))))
 
     def device_of(self, slot: int) -> int:
         d = C.c_int(0)
@@ -740,10 +759,20 @@ def match_multi_device(algos, ptr: int, length: int, params: AmMatchParams, cap_
              for b in buf[i * cap_per_needle: i * cap_per_needle + counts[i]]] for i in range(k)]
 
 
-def calc_chunks(sr: int, m_samples, algo_with_sample: HipConvolve, scale: bool, config: Config):
-    """audio_matcher.rs:88-141 on the GPU: returns peaks sorted by position.start."""
+def calc_chunks(sr: int, m_samples, algo_with_sample: HipConvolve, scale: bool, config: Config, ncc: bool = False):
+    """audio_matcher.rs:88-141 on the GPU: returns peaks sorted by position.start.
+
+    ncc: window-energy normalised scores for this call (option "score_norm" on the handle, restored afterwards);
+    needs scale = True."""
     params = config.params(sr, Scale.LIB if scale else Scale.NONE)
-    return algo_with_sample.match(m_samples, params)
+    if not ncc:
+        return algo_with_sample.match(m_samples, params)
+    keep = algo_with_sample.get_option(OPT_SCORE_NORM)
+    algo_with_sample.set_option(OPT_SCORE_NORM, 1)
+    try:
+        return algo_with_sample.match(m_samples, params)
+    finally:
+        algo_with_sample.set_option(OPT_SCORE_NORM, keep)
 
 
 PROGRESS_FN = C.CFUNCTYPE(None, C.c_void_p, C.c_size_t, C.c_int, C.c_size_t)

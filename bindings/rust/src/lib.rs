@@ -117,6 +117,11 @@ extern "C" {
 pub const AM_FMT_F32_MONO: c_int = 0;
 pub const AM_FMT_S16_STEREO: c_int = 1;
 
+/// Option keys of window-energy normalised scores (audiomatch.h): "score_norm" (0 = off, 1 = NCC; process default
+/// through am_set_option, per handle through am_needle_set_option) and "score_norm_floor_db" (0..200, default 60).
+pub const AM_OPT_SCORE_NORM: &str = "score_norm";
+pub const AM_OPT_SCORE_NORM_FLOOR_DB: &str = "score_norm_floor_db";
+
 #[repr(C)]
 pub struct AmStream {
     _private: [u8; 0],

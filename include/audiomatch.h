@@ -423,9 +423,34 @@ int am_debug_column_bench(int device, int wide, int npairs, int iters, int dense
  *       loop; this makes a violation visible); "debug_redo_arm_at" (k >= 0: the device-side redo of a batch is
  *       armed from haystack k of the call on; -1: never; -2, the default: when a failed certificate has been
  *       seen) -- pins the otherwise timing-dependent choice between the device and the host redo path. */
+/*
+ * Window-energy normalised scores (normalised cross-correlation, NCC):
+ *   "score_norm" (0/1, default 0): 1 = every score a call returns or picks from is
+ *       ncc(t) = corr(t) / sqrt( sum(needle^2) * sum_{i=t}^{t+S-1} x_i^2 )      in [-1, 1]
+ *     instead of the LibConvolve score corr(t) / sum(needle^2).  x is the sample sequence the call correlates (for
+ *     AM_FMT_S16_STEREO the down-mix exactly as above), 0 outside [0, len): the zero padding of AM_MODE_FULL / _SAME
+ *     counts as zeros.  sum(needle^2) is the needle's f64 energy (the needle against itself scores 1 within 1e-6).
+ *     The score no longer grows with the level of the haystack: one prominence bound serves recordings of any level
+ *     ("Normalised scores").  Requires scale == AM_SCALE_LIB (any other scale: AM_ERR_INVALID_ARG).
+ *     Also per needle handle (am_needle_set_option); pools use the process default (their needles are internal).
+ *     Supported by am_correlate*, am_match, am_match_device, am_match_batch_device, am_match_pcm16*,
+ *     am_pool_match_batch and am_pool_match_batch_pcm16 (and their _device forms).  NOT supported -- AM_ERR_INVALID_ARG,
+ *     "score_norm: not supported by this entry point" -- by am_match_multi*, am_pool_match_multi*, am_match_stream_*,
+ *     am_match_part_device and am_pool_match_long*.  am_find_peaks is unaffected.
+ *     Non-finite samples cost exactly the windows that hold them (they count as 0 in every other window's energy); a
+ *     haystack's result is the same bit pattern alone, in a batch and on any pool; chunking, "tail_window", the peak
+ *     rules and the overshadow filter apply to the NCC scores unchanged; "half_pipeline" keeps its offsets and
+ *     tolerances.  The needle's write-threshold history (sparse raw scores) is neither read nor fed by such calls:
+ *     their transforms write every raw score.
+ *   "score_norm_floor_db" (0..200, default 60; process-wide): a window whose energy is more than that many dB below
+ *     the needle's, E_w < E_n * 10^(-floor/10), scores exactly 0.  Digital silence gives 0 (never NaN or inf).  The
+ *     floor exists because the transform's absolute error scales with the energy of the whole overlap-save block,
+ *     not with the energy of the window: in a near-silent window next to loud material that rounding residue,
+ *     divided by the window's tiny energy, could otherwise show up as a hit.
+ */
 int am_set_option(const char* key, long long value);
 int am_get_option(const char* key, long long* value);
-/* "log_n" and "half_pipeline" per needle handle: -1 = follow the process default (initial
+/* "log_n", "half_pipeline" and "score_norm" per needle handle: -1 = follow the process default (initial
  * state), otherwise the handle's own value, which wins over the default. */
 int am_needle_set_option(am_needle* h, const char* key, long long value);
 int am_needle_get_option(const am_needle* h, const char* key, long long* value);

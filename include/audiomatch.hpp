@@ -67,6 +67,11 @@ struct Config {
 };
 
 // trait CorrelateAlgo<f32> (audio_matcher.rs:65-76)
+// option keys of window-energy normalised scores (audiomatch.h): HipConvolve::set_option(kOptScoreNorm, 1) for NCC
+// on one handle, am_set_option for the process default and the floor
+constexpr const char* kOptScoreNorm = "score_norm";
+constexpr const char* kOptScoreNormFloorDb = "score_norm_floor_db";
+
 class CorrelateAlgo {
 public:
     virtual ~CorrelateAlgo() = default;
@@ -107,7 +112,7 @@ public:
         return out;
     }
     const am_needle* handle() const { return h_; }
-    // per-handle "log_n" / "half_pipeline" (-1 = follow the process default)
+    // per-handle "log_n" / "half_pipeline" / "score_norm" (-1 = follow the process default)
     void set_option(const char* key, long long value) { check(am_needle_set_option(h_, key, value)); }
 
 private:
