@@ -507,6 +507,8 @@ int am_shutdown(void) {
             b->release();
         for (HostBuf* b : {&c->pinned, &c->hdr, &c->spill, &c->badflag, &c->failcnt}) b->release();
         c->ranges.release(); c->range_flags.release(); c->big.release(); c->norm_blk.release();
+        for (DevBuf* b : {&c->hit_tab, &c->hit_parts, &c->hit_flags, &c->hit_out, &c->hit_stage}) b->release();
+        c->hit_io.release();
         c->work_tail.release(); c->tail_scores.release(); c->tail_stats.release(); c->work_tail2.release();
         for (int i = 0; i < 2 * kMaxNeedleGroup; ++i) { c->grp_scores[i].release(); c->grp_stats32[i].release(); c->grp_wflags[i].release(); }
         for (int i = 0; i < kMaxNeedleGroup; ++i) c->grp_stats[i].release();

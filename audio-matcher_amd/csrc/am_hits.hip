@@ -1,0 +1,261 @@
+// am_hits.hip -- per-hit scoring (am_hit_scores*, include/audiomatch.h): for a hit at t, needle n[0 .. S) and the
+// haystack's samples x (the down-mix for AM_FMT_S16_STEREO), in f64:
+//   corr(u) = sum_{i<S} x[u + i] n[i] at u = t - 1, t, t + 1,   E_w = sum_{i<S} x[t + i]^2
+// and from those the exact NCC, the least-squares gain, the window level and a parabolic sub-sample position.
+//
+// Two kernels on the context's stream:
+//   hit_slices    one workgroup per slice of kHitSlice needle samples of one hit (blockIdx.x = slice, blockIdx.y =
+//                 hit): stages x over the slice plus one sample each side in LDS, accumulates the four sums from that
+//                 one read and writes one partial record (four doubles, one 64-bit store each, and a flag word).
+//   hit_combine   one wave per hit: adds the hit's partials in slice order and writes its am_hit_score.
+// A hit's result depends on its needle, the samples it reads and the floor only (the slices of a hit start at
+// multiples of kHitSlice of the needle, every reduction runs in a fixed order): the single, batch and host forms agree
+// bit for bit, whatever else a call holds.
+#include "am_internal.h"
+
+namespace am {
+
+namespace {
+
+constexpr int kHitThreads = 256;
+constexpr int kHitPer = kHitSlice / kHitThreads;   // needle samples per thread and slice
+static_assert(kHitSlice % kHitThreads == 0, "slice must split evenly over the workgroup");
+
+// Sums of four values per thread, each in a fixed order (every thread gets the results).
+__device__ void hit_block_sum4(double v[4]) {
+    __shared__ double ws[4][kHitThreads / 64];
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    for (int k = 0; k < 4; ++k) {
+        for (int off = 32; off > 0; off >>= 1) v[k] += __shfl_xor(v[k], off, 64);
+        if (lane == 0) ws[k][w] = v[k];
+    }
+    __syncthreads();
+    for (int k = 0; k < 4; ++k) {
+        double t = 0.0;
+        for (int i = 0; i < kHitThreads / 64; ++i) t += ws[k][i];
+        v[k] = t;
+    }
+}
+
+// x[t + u] of a hit's window pointer, read through the global address space (u may be -1)
+typedef __attribute__((address_space(1))) const float gfloat;
+typedef __attribute__((address_space(1))) const unsigned guint;   // (one i16 stereo frame)
+template <int KIND>
+__device__ __forceinline__ float hit_sample(const void* win, long long u) {
+    return KIND ? norm_downmix(__builtin_bit_cast(short2, ((guint*)win)[u])) : ((gfloat*)win)[u];
+}
+
+template <int KIND>
+__global__ __launch_bounds__(kHitThreads) void hit_slices_kernel(const HitDesc* __restrict__ hits, long long hit0,
+                                                                 double* __restrict__ parts, unsigned* __restrict__ pflags) {
+    __shared__ float xs[kHitSlice + 2];
+    const HitDesc d = hits[hit0 + blockIdx.y];
+    const long long i0 = (long long)blockIdx.x * kHitSlice;
+    if (i0 >= d.s) return;   // (a shorter needle than the launch's longest: whole workgroups leave together)
+    const int tid = threadIdx.x;
+    const int m = (int)min((long long)kHitSlice, d.s - i0);
+    // every load of the slice in flight at once: xs[q] = x[t + i0 - 1 + q] (q < m + 2, 0 where the hit reads no
+    // sample) and the thread's needle samples n[i0 + q]
+    gfloat* nd = (gfloat*)d.needle + i0;
+    const long long ulo = (d.edge & 1) ? -1 : 0, uhi = (d.edge & 2) ? d.s + 1 : d.s;   // the samples the hit reads
+    float xv[kHitPer], nv[kHitPer];
+#pragma unroll
+    for (int r = 0; r < kHitPer; ++r) {
+        const int q = tid + r * kHitThreads;
+        const long long u = i0 - 1 + q;
+        xv[r] = q < m + 2 && u >= ulo && u < uhi ? hit_sample<KIND>(d.win, u) : 0.0f;
+        nv[r] = q < m ? nd[q] : 0.0f;
+    }
+    float xt = 0.0f;
+    if (tid < 2) {
+        const int q = kHitSlice + tid;
+        const long long u = i0 - 1 + q;
+        xt = q < m + 2 && u >= ulo && u < uhi ? hit_sample<KIND>(d.win, u) : 0.0f;
+    }
+#pragma unroll
+    for (int r = 0; r < kHitPer; ++r) xs[tid + r * kHitThreads] = xv[r];
+    if (tid < 2) xs[kHitSlice + tid] = xt;
+    __syncthreads();
+    double c0 = 0.0, c1 = 0.0, c2 = 0.0, ew = 0.0;
+    bool bad = false;
+#pragma unroll
+    for (int r = 0; r < kHitPer; ++r) {
+        const int q = tid + r * kHitThreads;
+        if (q < m) {
+            const float n = nv[r], xm = xs[q], x = xs[q + 1], xp = xs[q + 2];
+            const double dn = (double)n, dx = (double)x;
+            c0 += (double)xm * dn;   // (a product of two f32 values is exact in f64)
+            c1 += dx * dn;
+            c2 += (double)xp * dn;
+            ew += dx * dx;
+            bad |= !__builtin_isfinite(x) || !__builtin_isfinite(n);
+        }
+    }
+    const int any_bad = __syncthreads_or(bad ? 1 : 0);
+    double v[4] = {c0, c1, c2, ew};
+    hit_block_sum4(v);
+    // one 64-bit store per lane: no record leaves as one wide store (tools/check_store_hazard.py)
+    const long long p = d.part0 + blockIdx.x;
+    if (tid < 4) parts[4 * p + tid] = v[tid];
+    else if (tid == 4) pflags[p] = (unsigned)any_bad;
+}
+
+// One wave per hit: the lanes fetch 64 partial records at a time into LDS, lane 0 adds them in slice order.
+__global__ __launch_bounds__(64) void hit_combine_kernel(const HitDesc* __restrict__ hits, const double* __restrict__ parts,
+                                                         const unsigned* __restrict__ pflags, am_hit_score* __restrict__ out) {
+    __shared__ double ps[4][64];
+    __shared__ unsigned fs[64];
+    const long long h = blockIdx.x;
+    const int lane = threadIdx.x;
+    const HitDesc d = hits[h];
+    const long long ns = (d.s + kHitSlice - 1) / kHitSlice;
+    double a = 0.0, b = 0.0, c = 0.0, ew = 0.0;
+    unsigned bad = 0;
+    for (long long k0 = 0; k0 < ns; k0 += 64) {
+        const long long k = k0 + lane;
+        if (k < ns) {
+            const long long p = d.part0 + k;
+            for (int j = 0; j < 4; ++j) ps[j][lane] = parts[4 * p + j];
+            fs[lane] = pflags[p];
+        }
+        __syncthreads();
+        if (lane == 0) {
+            const int cnt = (int)min(64ll, ns - k0);
+            for (int i = 0; i < cnt; ++i) {
+                a += ps[0][i];
+                b += ps[1][i];
+                c += ps[2][i];
+                ew += ps[3][i];
+                bad |= fs[i];
+            }
+        }
+        __syncthreads();
+    }
+    if (lane != 0) return;
+    const double nan = __builtin_nan("");
+    double pos = (double)d.t;
+    float ncc, gain, wdb;
+    unsigned flags = 0;
+    if (bad) {
+        flags = AM_HIT_NONFINITE;
+        ncc = gain = wdb = (float)nan;
+    } else {
+        const double den = a - 2.0 * b + c;
+        if ((d.edge & 3) != 3 || !__builtin_isfinite(a) || !__builtin_isfinite(c) || !(den < 0.0)) {
+            flags |= AM_HIT_UNREFINED;
+        } else {
+            const double delta = 0.5 * (a - c) / den;
+            pos += fmin(fmax(delta, -0.5), 0.5);
+        }
+        if (ew == 0.0 || ew < d.thr) {
+            flags |= AM_HIT_BELOW_FLOOR;
+            ncc = 0.0f;
+        } else {
+            ncc = (float)(b / sqrt(d.en * ew));
+        }
+        gain = d.en > 0.0 ? (float)(b / d.en) : 0.0f;
+        wdb = ew == 0.0 ? -__builtin_inff() : (float)(10.0 * log10(ew / d.en));
+    }
+    am_hit_score* o = out + h;
+    o->position = pos;
+    o->ncc = ncc;
+    o->gain = gain;
+    o->window_db = wdb;
+    o->flags = flags;
+}
+
+}  // namespace
+
+hipError_t launch_hit_scores(hipStream_t st, const HitDesc* d_hits, long long n, long long max_slices, int kind, double* parts,
+                             unsigned* pflags, am_hit_score* d_out) {
+    if (n <= 0) return hipSuccess;
+    for (long long h0 = 0; h0 < n; h0 += kHitMaxGridY) {   // (more hits than one grid column holds: a few launches)
+        const long long nh = std::min<long long>(kHitMaxGridY, n - h0);
+        if (kind) hipLaunchKernelGGL(hit_slices_kernel<1>, dim3((unsigned)max_slices, (unsigned)nh), dim3(kHitThreads), 0, st, d_hits, h0, parts, pflags);
+        else hipLaunchKernelGGL(hit_slices_kernel<0>, dim3((unsigned)max_slices, (unsigned)nh), dim3(kHitThreads), 0, st, d_hits, h0, parts, pflags);
+        hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return e;
+    }
+    hipLaunchKernelGGL(hit_combine_kernel, dim3((unsigned)n), dim3(64), 0, st, d_hits, (const double*)parts, (const unsigned*)pflags, d_out);
+    return hipGetLastError();
+}
+
+// ---- host side -------------------------------------------------------------------------------------------------------
+
+int hit_check_format(int sample_format) {
+    if (sample_format != AM_FMT_F32_MONO && sample_format != AM_FMT_S16_STEREO) return fail(AM_ERR_INVALID_ARG, "bad sample format");
+    return AM_OK;
+}
+
+std::string hit_pair_name(const HitWhere& w) {
+    if (w.pair < 0) return "";
+    return "pair " + std::to_string(w.pair) + " (haystack " + std::to_string(w.hay) + ", needle " + std::to_string(w.needle) + "): ";
+}
+
+int hit_check_device(const void* p, int device, const HitWhere& where) {
+    hipPointerAttribute_t a{};
+    const hipError_t e = hipPointerGetAttributes(&a, p);
+    if (e != hipSuccess || (a.type != hipMemoryTypeDevice && a.type != hipMemoryTypeManaged)) {
+        if (e != hipSuccess) (void)hipGetLastError();
+        return fail(AM_ERR_INVALID_ARG, hit_pair_name(where) + "haystack: not device memory");
+    }
+    if (a.device != device)
+        return fail(AM_ERR_INVALID_ARG, hit_pair_name(where) + "haystack: on device " + std::to_string(a.device) + ", the needle on device " +
+                                            std::to_string(device));
+    return AM_OK;
+}
+
+
+int hit_desc(const am_needle* h, const void* hay, size_t len, int sample_format, const am_peak& pk, double thr,
+             const HitWhere& where, HitDesc* d) {
+    const size_t s = h->n;
+    if (pk.start > len || s > len - pk.start)   // (the message is built only here: a call's cost does not grow with it)
+        return fail(AM_ERR_INVALID_ARG, hit_pair_name(where) + "hit " + std::to_string(where.hit) + ": start + needle length > haystack length (" +
+                                            std::to_string(pk.start) + " + " + std::to_string(s) + " > " + std::to_string(len) + ")");
+    d->win = advance_src(hay, (size_t)pk.start);
+    d->needle = h->d_needle;
+    d->s = (long long)s;
+    d->kind = sample_format == AM_FMT_S16_STEREO ? 1 : 0;
+    d->edge = (pk.start > 0 ? 1 : 0) | (pk.start + s < len ? 2 : 0);
+    d->t = (long long)pk.start;
+    d->en = h->energy;
+    d->thr = thr;
+    d->part0 = 0;
+    return AM_OK;
+}
+
+double hit_floor(const am_needle* h) {
+    return norm_spec(h, snapshot_opts(h)).thr;
+}
+
+int score_hits(Ctx* c, std::vector<HitDesc>& hits, am_hit_score* const* out) {
+    const long long n = (long long)hits.size();
+    if (n == 0) return AM_OK;
+    long long total = 0, max_slices = 0;
+    for (HitDesc& d : hits) {
+        const long long ns = (d.s + kHitSlice - 1) / kHitSlice;
+        d.part0 = total;
+        total += ns;
+        max_slices = std::max(max_slices, ns);
+    }
+    int rc;
+    if ((rc = c->hit_tab.ensure(sizeof(HitDesc) * (size_t)n)) || (rc = c->hit_parts.ensure(4 * sizeof(double) * (size_t)total)) ||
+        (rc = c->hit_flags.ensure(sizeof(unsigned) * (size_t)total)) || (rc = c->hit_out.ensure(sizeof(am_hit_score) * (size_t)n)) ||
+        (rc = c->hit_io.ensure(std::max(sizeof(HitDesc), sizeof(am_hit_score)) * (size_t)n)))
+        return rc;
+    // (the copies go through pinned memory: no staging in the runtime, which is most of a small call's time)
+    std::memcpy(c->hit_io.p, hits.data(), sizeof(HitDesc) * (size_t)n);
+    AM_HIP(hipMemcpyAsync(c->hit_tab.p, c->hit_io.p, sizeof(HitDesc) * (size_t)n, hipMemcpyHostToDevice, c->stream));
+    {
+        ProfScope ps(c, KN_OTHER, c->stream);
+        AM_HIP(launch_hit_scores(c->stream, static_cast<const HitDesc*>(c->hit_tab.p), n, max_slices, hits[0].kind, static_cast<double*>(c->hit_parts.p),
+                                 static_cast<unsigned*>(c->hit_flags.p), static_cast<am_hit_score*>(c->hit_out.p)));
+    }
+    AM_HIP(hipMemcpyAsync(c->hit_io.p, c->hit_out.p, sizeof(am_hit_score) * (size_t)n, hipMemcpyDeviceToHost, c->stream));
+    AM_HIP(hipStreamSynchronize(c->stream));
+    const am_hit_score* res = static_cast<const am_hit_score*>(c->hit_io.p);
+    for (long long i = 0; i < n; ++i) *out[i] = res[i];
+    return AM_OK;
+}
+
+}  // namespace am

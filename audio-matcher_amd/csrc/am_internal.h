@@ -143,6 +143,8 @@ struct Ctx {
     std::map<int, Plan> plans;
     DevBuf work, work2, scores, stats, stats32, wflags, segs, peaks, io_in, io_out, sum, arena_cur, wide_ctl, wide_list, wide_tiles;
     DevBuf norm_blk;   // block energies of the haystack being normalised (option score_norm; used on one stream at a time)
+    DevBuf hit_tab, hit_parts, hit_flags, hit_out, hit_stage;   // per-hit scoring (am_hits.hip): hit table, partials, results, staged spans
+    HostBuf hit_io;                                              // ... and the pinned host side of the table and the results
     // second set of the score-side buffers: in a batch the peak pick of haystack k runs on
     // stream2 beside the transforms of haystack k+1, which then need their own set
     DevBuf scores_b, stats_b, stats32_b, wflags_b, peaks_b;
@@ -361,6 +363,22 @@ int norm_reserve(Ctx* c, long long max_src_len);
 int normalise_scores(Ctx* c, hipStream_t st, const NormSpec& ns, const void* src, long long src_len, int src_kind, long long lead,
                      long long s, float* scores, long long a, long long b);
 #define AM_NORM_UNSUPPORTED "score_norm: not supported by this entry point"
+
+// ---- am_hits.hip ----
+int hit_check_format(int sample_format);
+double hit_floor(const am_needle* h);   // the floor on E_w the NCC path applies (process option score_norm_floor_db)
+// Which hit of a call (for error messages): hit `hit` of pair `pair` = (haystack `hay`, needle `needle`), pair < 0: a
+// single-haystack call
+struct HitWhere { long long pair; size_t hay, needle, hit; };
+std::string hit_pair_name(const HitWhere& w);   // "pair p (haystack k, needle j): ", or "" for a single-haystack call
+// AM_ERR_INVALID_ARG (message: names the pair of `where`) unless p is device memory of `device`
+int hit_check_device(const void* p, int device, const HitWhere& where);
+// the table entry of hit pk of haystack `hay` (its samples from element 0; `len` elements), or AM_ERR_INVALID_ARG
+// (message: names `where`) when the needle does not fit behind pk.start
+int hit_desc(const am_needle* h, const void* hay, size_t len, int sample_format, const am_peak& pk, double thr,
+             const HitWhere& where, HitDesc* d);
+// scores every hit of `hits` in one launch sequence on c's stream; out[i]: host destination of hit i
+int score_hits(Ctx* c, std::vector<HitDesc>& hits, am_hit_score* const* out);
 
 // ---- am_correlate.hip ----
 int plan_geometry(size_t s, long long out_count, const Opts& o, Geometry* g);

@@ -257,6 +257,12 @@ hipError_t launch_synth_pcm16(hipStream_t st, int16_t* out, uint32_t seed, uint3
 hipError_t launch_add_pcm16(hipStream_t st, int16_t* dst, const int16_t* src, long long frames);
 hipError_t launch_pcm_downmix(hipStream_t st, const int16_t* in, long long frames, float* out);
 
+// (l as f32 + r as f32) * 0.5 * (1 / 65535), the down-mix K1 applies (am_fft.hip, downmix_s16), bit for bit: what
+// am_norm.hip and am_hits.hip read an i16 stereo frame as
+__device__ __forceinline__ float norm_downmix(short2 lr) {
+    return __fmul_rn((float)((int)lr.x + (int)lr.y), 0.5f * (1.0f / 65535.0f));
+}
+
 // ---- am_norm.hip: window-energy normalisation (option "score_norm") ----
 constexpr int kNormBlock = 1024;   // samples per block energy
 constexpr int kNormTile = 2048;    // scores per workgroup of the normalising kernel
@@ -277,5 +283,23 @@ struct NormJob {
     long long a, b;
 };
 hipError_t launch_norm_scores(hipStream_t st, const NormJob& j);
+
+// ---- am_hits.hip: per-hit scoring (am_hit_scores*) ----
+constexpr int kHitSlice = 4096;                   // needle samples per workgroup of the slice kernel
+constexpr long long kHitMaxGridY = 65535;         // hits per launch of the slice kernel (grid.y)
+// One hit of a call, as the kernels read it (the call's hit table, uploaded once)
+struct HitDesc {
+    const void* win;      // device: sample t of the haystack (f32 mono, or an i16 stereo frame for kind 1)
+    const float* needle;  // device: the whole needle
+    long long s;          // needle length
+    int kind;             // 0 = f32 mono, 1 = i16 stereo (one kind per launch)
+    int edge;             // bit 0: x[t - 1] exists, bit 1: x[t + s] exists
+    long long t;          // the hit's start in the haystack
+    double en, thr;       // sum(needle^2), the floor on the window's energy
+    long long part0;      // first partial record of the hit
+};
+// parts: 4 doubles per slice (corr(t - 1), corr(t), corr(t + 1), E_w), pflags: one word per slice; d_out: n records
+hipError_t launch_hit_scores(hipStream_t st, const HitDesc* d_hits, long long n, long long max_slices, int kind, double* parts,
+                             unsigned* pflags, am_hit_score* d_out);
 
 }  // namespace am

@@ -25,10 +25,6 @@ constexpr int kNormSpan = kNormTile + (kNormTile + 2 * kNormBlock);   // LDS spa
 static_assert(kNormTile % kNormThreads == 0, "tile must split evenly over the workgroup");
 static_assert(kNormBlock % kNormThreads == 0, "block must split evenly over the workgroup");
 
-// (l as f32 + r as f32) * 0.5 * (1 / 65535), the down-mix K1 applies (am_fft.hip, downmix_s16), bit for bit
-__device__ __forceinline__ float norm_downmix(short2 lr) {
-    return __fmul_rn((float)((int)lr.x + (int)lr.y), 0.5f * (1.0f / 65535.0f));
-}
 // x_i^2 in f64 (exact for an f32 x); 0 outside [0, len) and for a non-finite sample
 __device__ __forceinline__ double norm_sq(const void* __restrict__ src, long long i, long long len, int kind) {
     if (i < 0 || i >= len) return 0.0;

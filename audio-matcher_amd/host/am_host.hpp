@@ -73,6 +73,7 @@ struct Arguments {
     int device = 0;                           // extension: GPU ordinal
     bool normalize = false;                   // extension: --normalize, window-energy normalised scores (option "score_norm")
     std::optional<int> normalize_floor_db;    // extension: --normalize-floor DB (option "score_norm_floor_db", 0..200)
+    std::optional<float> min_confidence;      // extension: --min-confidence X, drop hits whose exact NCC is below X (am_hit_scores, 0..1)
     bool help = false;                        // --help
 
     std::uint64_t chunk_size_ms() const { return chunk_ms.value_or(60ull * 1000); }
@@ -98,6 +99,9 @@ inline const char* usage_text() {
            "                         of a perfect match, not of the snippet's energy (default: off)\n"
            "  --normalize-floor DB   with --normalize: windows more than DB decibels below the snippet's energy score 0\n"
            "                         (0..200, default 60)\n"
+           "  --min-confidence X     drop every hit whose normalised cross-correlation with the snippet, computed\n"
+           "                         exactly for the hit's own window, is below X (0..1); with --debug, print each\n"
+           "                         hit's position, ncc, gain and window level (default: keep every hit)\n"
            "  --help                 this text\n";
 }
 
@@ -137,6 +141,14 @@ inline Arguments parse_arguments(int argc, const char* const* argv) {
             if (v.empty() || *end != '\0' || db < 0 || db > 200)
                 throw ArgError("invalid value '" + v + "' for --normalize-floor (whole decibels, 0..200)");
             a.normalize_floor_db = (int)db;
+        }
+        else if (s == "--min-confidence") {
+            const std::string v = need(i);
+            char* end = nullptr;
+            const float x = std::strtof(v.c_str(), &end);
+            if (v.empty() || *end != '\0' || !(x >= 0.0f && x <= 1.0f))
+                throw ArgError("invalid value '" + v + "' for --min-confidence (a number in 0..1)");
+            a.min_confidence = x;
         }
         else if (s == "-h" || s == "--help") { a.help = true; return a; }
         else if (!s.empty() && s[0] == '-' && s != "-") throw ArgError("unknown option " + s);

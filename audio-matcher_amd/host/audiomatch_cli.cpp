@@ -83,6 +83,20 @@ int main(int argc, char** argv) {
                 rc = am_match(algo, m_samples.data(), m_samples.size(), &p, peaks.data(), peaks.size(), &n);
             }
             if (rc != AM_OK) throw std::runtime_error(std::string("am_match: ") + am_last_error_string());
+            if (args.min_confidence && n > 0) {                               // extension: --min-confidence
+                std::vector<am_hit_score> sc(n);
+                if (am_hit_scores(algo, m_samples.data(), m_samples.size(), AM_FMT_F32_MONO, peaks.data(), n, sc.data()) != AM_OK)
+                    throw std::runtime_error(std::string("am_hit_scores: ") + am_last_error_string());
+                size_t kept = 0;
+                for (size_t i = 0; i < n; ++i) {
+                    if (args.verbosity >= 2)
+                        std::printf("hit %zu: position %.3f ncc %.6f gain %.6g window %.2f dB%s\n", i + 1, sc[i].position,
+                                    (double)sc[i].ncc, (double)sc[i].gain, (double)sc[i].window_db,
+                                    sc[i].ncc >= *args.min_confidence ? "" : " (dropped)");
+                    if (sc[i].ncc >= *args.min_confidence) peaks[kept++] = peaks[i];   // (a NaN ncc is dropped too)
+                }
+                n = kept;
+            }
             if (args.verbosity >= 1)
                 for (const auto& line : offset_lines(peaks.data(), n, sr)) std::printf("%s\n", line.c_str());   // mod.rs:89
             if (out_path) {                                                   // mod.rs:92-99

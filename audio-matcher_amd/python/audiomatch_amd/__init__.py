@@ -53,6 +53,14 @@ class AmPeak(C.Structure):
                 ("height", C.c_float), ("prominence", C.c_float)]
 
 
+class AmHitScore(C.Structure):     # am_hit_score (include/audiomatch.h, per-hit scoring)
+    _fields_ = [("position", C.c_double), ("ncc", C.c_float), ("gain", C.c_float),
+                ("window_db", C.c_float), ("flags", C.c_uint32)]
+
+
+AM_HIT_UNREFINED, AM_HIT_BELOW_FLOOR, AM_HIT_NONFINITE = 1, 2, 4
+
+
 class AmMatchParams(C.Structure):
     _fields_ = [("sr", C.c_uint32), ("chunk", C.c_uint64), ("overlap", C.c_uint64),
                 ("min_prominence", C.c_float), ("min_distance", C.c_uint64),
@@ -171,6 +179,13 @@ _SIGNATURES = {
     "am_profile_enable": (C.c_int, [C.c_int, C.c_int]),
     "am_profile_reset": (C.c_int, [C.c_int]),
     "am_profile_query": (C.c_int, [C.c_int, C.c_char_p, C.POINTER(C.c_double), C.POINTER(C.c_uint64)]),
+    "am_hit_scores_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.POINTER(AmPeak), C.c_size_t,
+                                       C.POINTER(AmHitScore)]),
+    "am_hit_scores": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.POINTER(AmPeak), C.c_size_t,
+                                C.POINTER(AmHitScore)]),
+    "am_hit_scores_batch_device": (C.c_int, [C.POINTER(C.c_void_p), C.c_size_t, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t),
+                                             C.c_size_t, C.c_int, C.POINTER(AmPeak), C.c_size_t, C.POINTER(C.c_size_t),
+                                             C.POINTER(AmHitScore)]),
     "am_set_option": (C.c_int, [C.c_char_p, C.c_longlong]),
     "am_get_option": (C.c_int, [C.c_char_p, C.POINTER(C.c_longlong)]),
 }
@@ -337,6 +352,25 @@ def find_peaks(y_data, min_prominence: float, min_distance: int = 0, device: int
     return [Peak(int(b.start), int(b.end), float(b.height), float(b.prominence)) for b in buf[:n.value]]
 
 
+@dataclass
+class HitScore:
+    """am_hit_score: exact NCC, least-squares gain, window level and sub-sample position of one hit."""
+    position: float
+    ncc: float
+    gain: float
+    window_db: float
+    flags: int
+
+
+def _peak_array(peaks):
+    k = len(peaks)
+    return (AmPeak * max(1, k))(*[AmPeak(int(q.start), int(q.end), float(q.height), float(q.prominence)) for q in peaks])
+
+
+def _hit_scores(buf, idx):
+    return [HitScore(buf[i].position, buf[i].ncc, buf[i].gain, buf[i].window_db, int(buf[i].flags)) for i in idx]
+
+
 # ---------------------------------------------------------------------------
 @dataclass
 class Peak:
@@ -493,6 +527,30 @@ class HipConvolve:
         _check(lib().am_match_batch_device(self._h, arr_p, arr_l, k, C.byref(params), buf,
                                            cap_per_hay, counts))
         return _split_batch(buf, counts, k, cap_per_hay)
+
+
+    # -- per-hit scoring --
+    def hit_scores(self, haystack, peaks):
+        """am_hit_scores: score `peaks` (Peak / AmPeak) of a host haystack -- an f32 array, or an i16 (frames, 2) array
+        of interleaved stereo.  Only the hits' spans are copied to the device."""
+        a = np.asarray(haystack)
+        if a.dtype == np.int16:
+            a = np.ascontiguousarray(a)
+            fmt, length = Fmt.S16_STEREO, a.size // 2
+        else:
+            a = np.ascontiguousarray(a, dtype=np.float32)
+            fmt, length = Fmt.F32_MONO, a.size
+        k = len(peaks)
+        out = (AmHitScore * max(1, k))()
+        _check(lib().am_hit_scores(self._h, a.ctypes.data, length, int(fmt), _peak_array(peaks), k, out))
+        return _hit_scores(out, range(k))
+
+    def hit_scores_device(self, ptr: int, length: int, peaks, fmt: int = Fmt.F32_MONO):
+        """am_hit_scores_device: score `peaks` of a haystack resident on this needle's device."""
+        k = len(peaks)
+        out = (AmHitScore * max(1, k))()
+        _check(lib().am_hit_scores_device(self._h, ptr, length, int(fmt), _peak_array(peaks), k, out))
+        return _hit_scores(out, range(k))
 
 
 class MatchStream:
@@ -694,6 +752,28 @@ def match_multi_batch_device(algos, ptrs, lengths, params: AmMatchParams, fmt: i
     counts = (C.c_size_t * max(1, k * nn))()
     _check(lib().am_match_multi_batch_device(handles, nn, arr_p, arr_l, k, int(fmt), C.byref(params), buf, cap_per_pair, counts))
     return _split_pairs(buf, counts, k, nn, cap_per_pair)
+
+
+def hit_scores_batch_device(algos, ptrs, lengths, peaks_per_pair, fmt: int = Fmt.F32_MONO):
+    """am_hit_scores_batch_device: peaks_per_pair[k][j] = the hits of haystack k against needle j (the shape
+    match_multi_batch_device returns; needles may differ in length); result [k][j] = their HitScores."""
+    nn, k = len(algos), len(ptrs)
+    cap = max([1] + [len(peaks_per_pair[h][j]) for h in range(k) for j in range(nn)])
+    handles = (C.c_void_p * max(1, nn))(*[a._h for a in algos])
+    arr_p = (C.c_void_p * max(1, k))(*ptrs)
+    arr_l = (C.c_size_t * max(1, k))(*lengths)
+    buf = (AmPeak * max(1, cap * k * nn))()
+    counts = (C.c_size_t * max(1, k * nn))()
+    for h in range(k):
+        for j in range(nn):
+            q = h * nn + j
+            counts[q] = len(peaks_per_pair[h][j])
+            for i, p in enumerate(peaks_per_pair[h][j]):
+                buf[q * cap + i] = AmPeak(int(p.start), int(p.end), float(p.height), float(p.prominence))
+    out = (AmHitScore * max(1, cap * k * nn))()
+    _check(lib().am_hit_scores_batch_device(handles, nn, arr_p, arr_l, k, int(fmt), buf, cap, counts, out))
+    return [[_hit_scores(out, range((h * nn + j) * cap, (h * nn + j) * cap + counts[h * nn + j])) for j in range(nn)]
+            for h in range(k)]
 
 
 class MultiPool:

@@ -33,6 +33,20 @@ pub struct AmMatchParams {
     pub scale: c_int,
 }
 
+/// am_hit_score: the result of per-hit scoring (24 bytes)
+#[repr(C)]
+#[derive(Clone, Copy, Default, Debug)]
+pub struct AmHitScore {
+    pub position: f64,
+    pub ncc: f32,
+    pub gain: f32,
+    pub window_db: f32,
+    pub flags: u32,
+}
+pub const AM_HIT_UNREFINED: u32 = 1;
+pub const AM_HIT_BELOW_FLOOR: u32 = 2;
+pub const AM_HIT_NONFINITE: u32 = 4;
+
 pub const AM_OK: c_int = 0;
 pub const AM_ERR_CAPACITY: c_int = 2;
 
@@ -104,6 +118,19 @@ extern "C" {
     pub fn am_pool_match_multi_batch(
         pool: *mut AmPool, haystacks: *const *const std::ffi::c_void, lens: *const usize, n_hay: usize, sample_format: c_int,
         p: *const AmMatchParams, out: *mut AmPeak, cap_per_pair: usize, n_out: *mut usize,
+    ) -> c_int;
+    /// per-hit scoring: exact NCC, gain, window level and sub-sample position of each hit (audiomatch.h)
+    pub fn am_hit_scores(
+        h: *const AmNeedle, haystack: *const std::ffi::c_void, len: usize, sample_format: c_int, peaks: *const AmPeak, n: usize,
+        out: *mut AmHitScore,
+    ) -> c_int;
+    pub fn am_hit_scores_device(
+        h: *const AmNeedle, d_haystack: *const std::ffi::c_void, len: usize, sample_format: c_int, peaks: *const AmPeak, n: usize,
+        out: *mut AmHitScore,
+    ) -> c_int;
+    pub fn am_hit_scores_batch_device(
+        needles: *const *const AmNeedle, n_needles: usize, d_haystacks: *const *const std::ffi::c_void, lens: *const usize,
+        n_hay: usize, sample_format: c_int, peaks: *const AmPeak, cap_per_pair: usize, n_peaks: *const usize, out: *mut AmHitScore,
     ) -> c_int;
     /// calc_chunks on the lazy sample iterator (audio_matcher.rs:88-104, mp3_reader.rs:13-41)
     pub fn am_match_stream_begin(
@@ -226,6 +253,20 @@ impl HipConvolve {
         }
         buf.truncate(n);
         Ok(buf)
+    }
+
+    /// Per-hit scoring (am_hit_scores) of `peaks` found in the host haystack `m_samples`: exact NCC, gain, window
+    /// level and sub-sample position, one record per peak.  Only the hits' spans are copied to the device.
+    pub fn hit_scores(&self, m_samples: &[f32], peaks: &[AmPeak]) -> Result<Vec<AmHitScore>, Box<dyn std::error::Error>> {
+        let mut out = vec![AmHitScore::default(); peaks.len()];
+        let rc = unsafe {
+            am_hit_scores(self.h, m_samples.as_ptr() as *const std::ffi::c_void, m_samples.len(), AM_FMT_F32_MONO, peaks.as_ptr(),
+                          peaks.len(), out.as_mut_ptr())
+        };
+        if rc != AM_OK {
+            return Err(am_err(rc));
+        }
+        Ok(out)
     }
 
     /// `calc_chunks` on decoded stereo PCM frames (interleaved i16, as minimp3 delivers them):

@@ -185,6 +185,51 @@ int am_match_pcm16_batch_device(const am_needle* h, const int16_t* const* d_inte
                                 size_t n_hay, const am_match_params* p,
                                 am_peak* out, size_t cap_per_hay, size_t* n_out);
 
+/* ---- per-hit scoring ----------------------------------------------------------- */
+/* A level-independent confidence and a sub-sample position for the few hits a match returned, from ANY entry point
+ * (the reference reports integer offsets and the LibConvolve height only, matcher/mod.rs:110-125).  For a hit with
+ * t = peak.start, needle n[0 .. S) (the handle's whole needle, partitioned handles included) and the haystack's samples
+ * x (f32 mono, or for AM_FMT_S16_STEREO the down-mix (l + r) * 0.5 * (1/65535) bit for bit as above), in f64:
+ *     corr(u) = sum_{i<S} x[u + i] n[i],   E_n = sum n^2 (the needle's energy),   E_w = sum_{i<S} x[t + i]^2
+ *   position   t + d,  d = 0.5 (a - c) / (a - 2b + c) clamped to [-0.5, 0.5], a, b, c = corr(t - 1), corr(t), corr(t + 1)
+ *              (the vertex of the parabola through the three scores).  d = 0 and flag AM_HIT_UNREFINED when t = 0,
+ *              when t + S = len, when a - 2b + c >= 0 (no maximum), or when x[t - 1] or x[t + S] is not finite.
+ *   ncc        corr(t) / sqrt(E_n E_w) in [-1, 1]; 0 with flag AM_HIT_BELOW_FLOOR when E_w = 0 or
+ *              E_w < E_n 10^(-score_norm_floor_db / 10) -- the floor of the NCC scores, the process option at call time.
+ *   gain       corr(t) / E_n: the least-squares factor of the needle in the window (0 if E_n = 0); the default
+ *              (AM_SCALE_LIB) height of the hit.
+ *   window_db  10 log10(E_w / E_n); -inf for a silent window.
+ *   flags      AM_HIT_*.  AM_HIT_NONFINITE: a sample of x[t .. t + S) or of the needle is not finite; ncc, gain and
+ *              window_db are then NaN, position = t and no other flag is set.
+ * A hit's result depends on the needle, the samples it reads and the floor only -- not on the other hits of the call,
+ * the batch or the entry point: the three forms below agree bit for bit.  The cost is proportional to the number of
+ * hits times S (about 4 (S + 2) bytes of haystack per hit), not to the haystack's length.
+ * peaks and out are host memory, out[i] scores peaks[i]; len counts samples (frames for AM_FMT_S16_STEREO).
+ * AM_ERR_INVALID_ARG, naming the hit (and pair): a null pointer with n > 0, an unknown sample format,
+ * peak.start + S > len, a haystack on another device than the needle.  n = 0: AM_OK, nothing launched. */
+enum { AM_HIT_UNREFINED = 1, AM_HIT_BELOW_FLOOR = 2, AM_HIT_NONFINITE = 4 };
+typedef struct am_hit_score {
+    double position;   /* t + d, sub-sample start of the hit */
+    float ncc;         /* exact normalised correlation */
+    float gain;        /* least-squares gain of the needle in the window */
+    float window_db;   /* window energy over needle energy, dB */
+    uint32_t flags;    /* AM_HIT_* */
+} am_hit_score;        /* 24 bytes, no padding */
+/* the haystack resident on the needle's device */
+int am_hit_scores_device(const am_needle* h, const void* d_haystack, size_t len, int sample_format,
+                         const am_peak* peaks, size_t n, am_hit_score* out);
+/* the haystack in host memory: only the spans [t - 1, t + S + 1) of the hits are copied (merged where they overlap) */
+int am_hit_scores(const am_needle* h, const void* haystack, size_t len, int sample_format,
+                  const am_peak* peaks, size_t n, am_hit_score* out);
+/* The result layout of am_match_multi_batch_device (n_needles = 1: of am_match_batch_device and
+ * am_match_pcm16_batch_device, unchanged): pair (haystack k, needle j) at k * n_needles + j, cap_per_pair slots per
+ * pair, min(n_peaks[pair], cap_per_pair) hits scored per pair, out laid out like peaks (other slots untouched).
+ * Needles may differ in length; needles and haystacks on one device.  Every hit of the call in one launch sequence.
+ * Pool results: score each slot's hits with that slot's needle (am_pool_slot). */
+int am_hit_scores_batch_device(const am_needle* const* needles, size_t n_needles,
+                               const void* const* d_haystacks, const size_t* lens, size_t n_hay, int sample_format,
+                               const am_peak* peaks, size_t cap_per_pair, const size_t* n_peaks, am_hit_score* out);
+
 /* ---- streaming ingest ---------------------------------------------------------- */
 /* calc_chunks consumes a lazy ExactSizeIterator<Item = f32> (audio_matcher.rs:88-97): the decoder
  * yields frames (mp3_reader.rs:13-41) and the windows are cut as they arrive (:104).  The same

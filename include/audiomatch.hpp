@@ -112,6 +112,19 @@ public:
         return out;
     }
     const am_needle* handle() const { return h_; }
+    // per-hit scoring (am_hit_scores): exact NCC, gain, window level and sub-sample position of each of `peaks`, found in
+    // the host haystack of `sample_format` (len in samples / frames); am_hit_scores_device for a resident haystack
+    std::vector<am_hit_score> hit_scores(const void* haystack, std::size_t len, int sample_format, const std::vector<am_peak>& peaks) const {
+        std::vector<am_hit_score> out(peaks.size());
+        check(am_hit_scores(h_, haystack, len, sample_format, peaks.data(), peaks.size(), out.data()));
+        return out;
+    }
+    std::vector<am_hit_score> hit_scores_device(const void* d_haystack, std::size_t len, int sample_format,
+                                                const std::vector<am_peak>& peaks) const {
+        std::vector<am_hit_score> out(peaks.size());
+        check(am_hit_scores_device(h_, d_haystack, len, sample_format, peaks.data(), peaks.size(), out.data()));
+        return out;
+    }
     // per-handle "log_n" / "half_pipeline" / "score_norm" (-1 = follow the process default)
     void set_option(const char* key, long long value) { check(am_needle_set_option(h_, key, value)); }
 
