@@ -395,7 +395,7 @@ int check_needle(const am_needle* h) {
     return AM_OK;
 }
 
-static int create_needle_common(Ctx* c, float* d_needle, size_t n, am_needle** out) {
+int create_needle_common(Ctx* c, float* d_needle, size_t n, am_needle** out) {
     am_needle* h = new am_needle();
     h->ctx = c; h->d_needle = d_needle; h->n = n;
     const int parts = sumsq_parts((long long)n);
@@ -509,6 +509,8 @@ int am_shutdown(void) {
         c->ranges.release(); c->range_flags.release(); c->big.release(); c->norm_blk.release();
         for (DevBuf* b : {&c->hit_tab, &c->hit_parts, &c->hit_flags, &c->hit_out, &c->hit_stage}) b->release();
         c->hit_io.release();
+        for (auto& kv : c->rs_taps) kv.second.release();
+        c->rs_taps.clear();
         c->work_tail.release(); c->tail_scores.release(); c->tail_stats.release(); c->work_tail2.release();
         for (int i = 0; i < 2 * kMaxNeedleGroup; ++i) { c->grp_scores[i].release(); c->grp_stats32[i].release(); c->grp_wflags[i].release(); }
         for (int i = 0; i < kMaxNeedleGroup; ++i) c->grp_stats[i].release();

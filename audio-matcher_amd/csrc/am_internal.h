@@ -145,6 +145,7 @@ struct Ctx {
     DevBuf norm_blk;   // block energies of the haystack being normalised (option score_norm; used on one stream at a time)
     DevBuf hit_tab, hit_parts, hit_flags, hit_out, hit_stage;   // per-hit scoring (am_hits.hip): hit table, partials, results, staged spans
     HostBuf hit_io;                                              // ... and the pinned host side of the table and the results
+    std::map<std::pair<int, int>, DevBuf> rs_taps;               // sample-rate conversion: the polyphase table of each (L, M)
     // second set of the score-side buffers: in a batch the peak pick of haystack k runs on
     // stream2 beside the transforms of haystack k+1, which then need their own set
     DevBuf scores_b, stats_b, stats32_b, wflags_b, peaks_b;
@@ -349,6 +350,8 @@ inline const void* advance_src(const void* src, size_t elements) {
 // ---- am_context.hip ----
 Opts snapshot_opts(const am_needle* h);
 int check_needle(const am_needle* h);
+// a handle over d_needle (n samples, owned by the handle from here on, freed if this fails) with its energy measured
+int create_needle_common(Ctx* c, float* d_needle, size_t n, am_needle** out);
 HalfScale half_scale(const am_needle* h, const Opts& o, const PlanDev& pl);
 int needle_k2_spectrum(am_needle* h, const Opts& o, const Plan* pl, const float2** hc, HalfScale* hs);
 

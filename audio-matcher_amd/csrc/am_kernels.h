@@ -302,4 +302,24 @@ struct HitDesc {
 hipError_t launch_hit_scores(hipStream_t st, const HitDesc* d_hits, long long n, long long max_slices, int kind, double* parts,
                              unsigned* pflags, am_hit_score* d_out);
 
+// ---- am_resample.hip: sample-rate conversion (am_resample*) ----
+constexpr int kRsThreads = 256;
+constexpr int kRsJ = 8;          // outputs per work item: k, k + W, ..., k + 7 W (one phase, its taps read once)
+constexpr int kRsTc = 8;         // taps per register chunk; the table's rows are padded to a multiple of it
+// One launch: outputs [0, n_out) of x = src (f32 mono, or the down-mix of i16 stereo frames for kind 1).  Workgroup b
+// produces the W * kRsJ outputs from k0 = b * W * kRsJ on; work item w < W (a multiple of L) the outputs k0 + w + jj W.
+struct ResampleJob {
+    const void* src;
+    long long n_in;
+    float* dst;
+    long long n_out;
+    const float* taps;   // device, [L][ts]: taps[p][t] = h[p + t L - H] while p + t L <= 2H, else 0
+    int L, M, H, ts;
+    int W;
+    int xs_cap;          // floats of input staged in LDS per workgroup (0: every sample read through the cache)
+    int tab_lds;         // 1: the table is staged in LDS (rows padded to ts + 1 floats)
+    int vec;             // 1: src is 16-byte aligned (the staging loads read 4 samples / frames at a time)
+};
+hipError_t launch_resample(hipStream_t st, const ResampleJob& j, int kind);
+
 }  // namespace am

@@ -74,6 +74,7 @@ struct Arguments {
     bool normalize = false;                   // extension: --normalize, window-energy normalised scores (option "score_norm")
     std::optional<int> normalize_floor_db;    // extension: --normalize-floor DB (option "score_norm_floor_db", 0..200)
     std::optional<float> min_confidence;      // extension: --min-confidence X, drop hits whose exact NCC is below X (am_hit_scores, 0..1)
+    bool resample = false;                    // extension: --resample, bring the snippet to each main file's rate (am_needle_create_resampled)
     bool help = false;                        // --help
 
     std::uint64_t chunk_size_ms() const { return chunk_ms.value_or(60ull * 1000); }
@@ -102,6 +103,8 @@ inline const char* usage_text() {
            "  --min-confidence X     drop every hit whose normalised cross-correlation with the snippet, computed\n"
            "                         exactly for the hit's own window, is below X (0..1); with --debug, print each\n"
            "                         hit's position, ncc, gain and window level (default: keep every hit)\n"
+           "  --resample             match main files of any sample rate: the snippet is resampled to each file's rate\n"
+           "                         (scipy's resample_poly filter); without it, a rate mismatch stops the run\n"
            "  --help                 this text\n";
 }
 
@@ -150,6 +153,7 @@ inline Arguments parse_arguments(int argc, const char* const* argv) {
                 throw ArgError("invalid value '" + v + "' for --min-confidence (a number in 0..1)");
             a.min_confidence = x;
         }
+        else if (s == "--resample") a.resample = true;
         else if (s == "-h" || s == "--help") { a.help = true; return a; }
         else if (!s.empty() && s[0] == '-' && s != "-") throw ArgError("unknown option " + s);
         else if (!s.empty()) a.within.push_back(s);

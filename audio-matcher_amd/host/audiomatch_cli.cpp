@@ -4,6 +4,7 @@
 // decoding (minimp3) is outside the accelerated path.
 #include <cstdio>
 #include <iostream>
+#include <map>
 #include <sys/stat.h>
 
 #include "am_host.hpp"
@@ -48,13 +49,15 @@ int main(int argc, char** argv) {
         const std::uint32_t sr = snippet.sample_rate;
         const double s_duration = (double)snippet.frames() / (double)sr;      // mod.rs:30 (mp3_duration)
         const std::vector<float> sample_data = to_mono_f32(snippet, args.device);   // mod.rs:32
-        am_needle* algo = nullptr;                                            // mod.rs:34: LibConvolve::new
-        if (am_needle_create(args.device, sample_data.data(), sample_data.size(), &algo) != AM_OK)
+        am_needle* snippet_algo = nullptr;                                    // mod.rs:34: LibConvolve::new
+        if (am_needle_create(args.device, sample_data.data(), sample_data.size(), &snippet_algo) != AM_OK)
             throw std::runtime_error(std::string("am_needle_create: ") + am_last_error_string());
         if (args.normalize_floor_db && am_set_option("score_norm_floor_db", *args.normalize_floor_db) != AM_OK)
             throw std::runtime_error(std::string("--normalize-floor: ") + am_last_error_string());
-        if (args.normalize && am_needle_set_option(algo, "score_norm", 1) != AM_OK)
+        if (args.normalize && am_needle_set_option(snippet_algo, "score_norm", 1) != AM_OK)
             throw std::runtime_error(std::string("--normalize: ") + am_last_error_string());
+        // extension --resample: one handle per main-file rate other than the snippet's, made on first use and kept
+        std::map<std::uint32_t, am_needle*> resampled;
         if (args.verbosity >= 2) am_set_progress_callback(progress, nullptr);
         int rc_all = 0;
         for (const std::string& main_file : args.within) {                    // mod.rs:42
@@ -69,12 +72,29 @@ int main(int argc, char** argv) {
             if (args.verbosity >= (args.within.size() == 1 ? 3 : 1))
                 std::printf("preparing data of '%s'\n", main_file.c_str());
             const Pcm m = read_wav(main_file);                                // mod.rs:71
-            if (m.sample_rate != sr) {                                        // mod.rs:72-74 SampleRateMismatch
+            am_needle* algo = snippet_algo;
+            if (m.sample_rate != sr && !args.resample) {                      // mod.rs:72-74 SampleRateMismatch
                 std::fprintf(stderr, "sample rate of snippet (%u) and main file (%u) don't match\n", sr, m.sample_rate);
                 return 3;
             }
+            if (m.sample_rate != sr) {                                        // extension: --resample
+                am_needle*& h = resampled[m.sample_rate];
+                if (!h) {
+                    if (am_needle_create_resampled(args.device, sample_data.data(), sample_data.size(), AM_FMT_F32_MONO, sr, m.sample_rate, &h) != AM_OK)
+                        throw std::runtime_error(std::string("am_needle_create_resampled: ") + am_last_error_string());
+                    if (args.normalize && am_needle_set_option(h, "score_norm", 1) != AM_OK)
+                        throw std::runtime_error(std::string("--normalize: ") + am_last_error_string());
+                }
+                algo = h;
+            }
+            const std::uint32_t m_sr = m.sample_rate;
             const std::vector<float> m_samples = to_mono_f32(m, args.device);
-            const am_match_params p = make_params(args, sr, s_duration);      // mod.rs:81-87
+            am_match_params p = make_params(args, m_sr, s_duration);          // mod.rs:81-87
+            if (m_sr != sr) {                                                 // the overlap = the resampled snippet's length
+                size_t s_len = 0;
+                am_needle_len(algo, &s_len);
+                p.overlap = s_len;
+            }
             std::vector<am_peak> peaks(1024);
             size_t n = 0;
             int rc = am_match(algo, m_samples.data(), m_samples.size(), &p, peaks.data(), peaks.size(), &n);
@@ -98,9 +118,9 @@ int main(int argc, char** argv) {
                 n = kept;
             }
             if (args.verbosity >= 1)
-                for (const auto& line : offset_lines(peaks.data(), n, sr)) std::printf("%s\n", line.c_str());   // mod.rs:89
+                for (const auto& line : offset_lines(peaks.data(), n, m_sr)) std::printf("%s\n", line.c_str());   // mod.rs:89
             if (out_path) {                                                   // mod.rs:92-99
-                const std::string text = format_labels(timelabel_from_peaks(peaks.data(), n, sr, 7.0, "Segment #"));
+                const std::string text = format_labels(timelabel_from_peaks(peaks.data(), n, m_sr, 7.0, "Segment #"));
                 if (args.dry_run) {
                     std::printf("would write to '%s':\n%s", out_path->c_str(), text.c_str());
                 } else {
@@ -110,7 +130,8 @@ int main(int argc, char** argv) {
                 }
             }
         }
-        am_needle_destroy(algo);
+        am_needle_destroy(snippet_algo);
+        for (auto& kv : resampled) am_needle_destroy(kv.second);
         return rc_all;
     } catch (const std::exception& e) {
         std::fprintf(stderr, "error: %s\n", e.what());

@@ -186,6 +186,13 @@ _SIGNATURES = {
     "am_hit_scores_batch_device": (C.c_int, [C.POINTER(C.c_void_p), C.c_size_t, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t),
                                              C.c_size_t, C.c_int, C.POINTER(AmPeak), C.c_size_t, C.POINTER(C.c_size_t),
                                              C.POINTER(AmHitScore)]),
+    "am_resample_len": (C.c_int, [C.c_size_t, C.c_uint32, C.c_uint32, C.POINTER(C.c_size_t)]),
+    "am_resample": (C.c_int, [C.c_int, C.c_void_p, C.c_size_t, C.c_int, C.c_uint32, C.c_uint32, C.c_void_p, C.c_size_t,
+                              C.POINTER(C.c_size_t)]),
+    "am_resample_device": (C.c_int, [C.c_int, C.c_void_p, C.c_size_t, C.c_int, C.c_uint32, C.c_uint32, C.c_void_p,
+                                     C.c_size_t, C.POINTER(C.c_size_t)]),
+    "am_needle_create_resampled": (C.c_int, [C.c_int, C.c_void_p, C.c_size_t, C.c_int, C.c_uint32, C.c_uint32,
+                                             C.POINTER(C.c_void_p)]),
     "am_set_option": (C.c_int, [C.c_char_p, C.c_longlong]),
     "am_get_option": (C.c_int, [C.c_char_p, C.POINTER(C.c_longlong)]),
 }
@@ -342,6 +349,44 @@ def pcm_s16_stereo_to_mono(interleaved: np.ndarray, device: int = 0) -> np.ndarr
     return out
 
 
+def _samples(x):
+    """(array, format, length) of a host signal: f32 mono, or int16 interleaved stereo (flat or (frames, 2))."""
+    a = np.asarray(x)
+    if a.dtype == np.int16:
+        a = np.ascontiguousarray(a)
+        return a, Fmt.S16_STEREO, a.size // 2
+    a = np.ascontiguousarray(a, dtype=np.float32)
+    return a, Fmt.F32_MONO, a.size
+
+
+def resample_len(n_in: int, src_rate: int, dst_rate: int) -> int:
+    """am_resample_len: ceil(n_in * L / M), L / M = dst_rate / src_rate in lowest terms (pure host function)."""
+    n = C.c_size_t(0)
+    _check(lib().am_resample_len(int(n_in), int(src_rate), int(dst_rate), C.byref(n)))
+    return n.value
+
+
+def resample(x, src_rate: int, dst_rate: int, device: int = 0) -> np.ndarray:
+    """am_resample: x (f32 mono, or int16 interleaved stereo, flat or (frames, 2)) from src_rate to dst_rate, as
+    scipy.signal.resample_poly(x, L, M) computes it (include/audiomatch.h); f32 mono out."""
+    a, fmt, length = _samples(x)
+    n = resample_len(length, src_rate, dst_rate)
+    out = np.empty(n, dtype=np.float32)
+    got = C.c_size_t(0)
+    _check(lib().am_resample(device, a.ctypes.data, length, int(fmt), int(src_rate), int(dst_rate), out.ctypes.data, n,
+                             C.byref(got)))
+    return out
+
+
+def resample_device(device: int, src_ptr: int, n_in: int, src_rate: int, dst_rate: int, dst_ptr: int, cap: int,
+                    fmt: int = Fmt.F32_MONO) -> int:
+    """am_resample_device on resident buffers; returns the output length."""
+    got = C.c_size_t(0)
+    _check(lib().am_resample_device(device, src_ptr, int(n_in), int(fmt), int(src_rate), int(dst_rate), dst_ptr, int(cap),
+                                    C.byref(got)))
+    return got.value
+
+
 def find_peaks(y_data, min_prominence: float, min_distance: int = 0, device: int = 0, cap: int = 65536):
     """audio_matcher.rs:221-230 on the GPU; peaks by descending height."""
     a = np.ascontiguousarray(y_data, dtype=np.float32)
@@ -443,6 +488,23 @@ class HipConvolve:
         self._h = C.c_void_p()
         _check(lib().am_needle_create_pcm16(device, a.ctypes.data, a.size // 2, C.byref(self._h)))
         self.sample_len = int(a.size // 2)
+        return self
+
+    @classmethod
+    def resampled(cls, needle, src_rate: int, dst_rate: int, device: int = 0, score_norm=None) -> "HipConvolve":
+        """am_needle_create_resampled: the needle (f32, or int16 interleaved stereo) brought from src_rate to the
+        haystack's dst_rate; the same handle as HipConvolve(resample(needle, src_rate, dst_rate))."""
+        a, fmt, length = _samples(needle)
+        self = cls.__new__(cls)
+        self.device = device
+        self._h = C.c_void_p()
+        _check(lib().am_needle_create_resampled(device, a.ctypes.data, length, int(fmt), int(src_rate), int(dst_rate),
+                                                C.byref(self._h)))
+        n = C.c_size_t(0)
+        _check(lib().am_needle_len(self._h, C.byref(n)))
+        self.sample_len = int(n.value)
+        if score_norm is not None:
+            self.set_option(OPT_SCORE_NORM, int(bool(score_norm)))
         return self
 
     def match_pcm16(self, interleaved, params: AmMatchParams, cap: int = 4096):

@@ -54,6 +54,7 @@ extern "C" {
     pub fn am_last_error_string() -> *const c_char;
     pub fn am_needle_create(device: c_int, needle: *const f32, n: usize, out: *mut *mut AmNeedle) -> c_int;
     pub fn am_needle_destroy(h: *mut AmNeedle);
+    pub fn am_needle_len(h: *const AmNeedle, n: *mut usize) -> c_int;
     pub fn am_needle_inv_autocorr(h: *const AmNeedle, out: *mut f32) -> c_int;
     pub fn am_correlate_len(w: usize, s: usize, mode: c_int, out_len: *mut usize) -> c_int;
     pub fn am_correlate(
@@ -118,6 +119,20 @@ extern "C" {
     pub fn am_pool_match_multi_batch(
         pool: *mut AmPool, haystacks: *const *const std::ffi::c_void, lens: *const usize, n_hay: usize, sample_format: c_int,
         p: *const AmMatchParams, out: *mut AmPeak, cap_per_pair: usize, n_out: *mut usize,
+    ) -> c_int;
+    /// sample-rate conversion: scipy.signal.resample_poly(x, L, M) with its default window (audiomatch.h)
+    pub fn am_resample_len(n_in: usize, src_rate: u32, dst_rate: u32, n_out: *mut usize) -> c_int;
+    pub fn am_resample(
+        device: c_int, input: *const std::ffi::c_void, n_in: usize, sample_format: c_int, src_rate: u32, dst_rate: u32,
+        out: *mut f32, cap: usize, n_out: *mut usize,
+    ) -> c_int;
+    pub fn am_resample_device(
+        device: c_int, d_in: *const std::ffi::c_void, n_in: usize, sample_format: c_int, src_rate: u32, dst_rate: u32,
+        d_out: *mut f32, cap: usize, n_out: *mut usize,
+    ) -> c_int;
+    pub fn am_needle_create_resampled(
+        device: c_int, needle: *const std::ffi::c_void, n: usize, sample_format: c_int, src_rate: u32, dst_rate: u32,
+        out: *mut *mut AmNeedle,
     ) -> c_int;
     /// per-hit scoring: exact NCC, gain, window level and sub-sample position of each hit (audiomatch.h)
     pub fn am_hit_scores(
@@ -189,6 +204,27 @@ impl HipConvolve {
             return Err(am_err(rc));
         }
         Ok(Self { h, len: sample_data.len() })
+    }
+
+    /// `LibConvolve::new` on a snippet recorded at `src_rate`, brought to the haystack's `dst_rate` on the GPU
+    /// (am_needle_create_resampled): matching then runs on haystacks of that rate, offsets in their samples.  The
+    /// reference stops with CliError::SampleRateMismatch instead (matcher/mod.rs:72-74).
+    pub fn new_resampled(sample_data: &[f32], src_rate: u32, dst_rate: u32) -> Result<Self, Box<dyn std::error::Error>> {
+        let mut h = std::ptr::null_mut();
+        let rc = unsafe {
+            am_needle_create_resampled(0, sample_data.as_ptr() as *const std::ffi::c_void, sample_data.len(), AM_FMT_F32_MONO,
+                                       src_rate, dst_rate, &mut h)
+        };
+        if rc != AM_OK {
+            return Err(am_err(rc));
+        }
+        let mut len = 0usize;
+        let rc = unsafe { am_needle_len(h, &mut len) };
+        if rc != AM_OK {
+            unsafe { am_needle_destroy(h) };
+            return Err(am_err(rc));
+        }
+        Ok(Self { h, len })
     }
 
     /// The same from decoded stereo PCM (`frame.data`, mp3_reader.rs:28): no CPU down-mix pass.

@@ -264,6 +264,44 @@ int am_pcm_s16_stereo_to_mono(int device, const int16_t* interleaved, size_t fra
 int am_pcm_s16_stereo_to_mono_device(int device, const int16_t* d_interleaved, size_t frames,
                                      float* d_out);
 
+/* ---- sample-rate conversion ---------------------------------------------- */
+/* The reference refuses a snippet and a main file of different rates (matcher/mod.rs:72-74,
+ * CliError::SampleRateMismatch).  These entry points bring a signal to another rate, normally the needle to the
+ * haystack's rate: offsets then stay integers in haystack samples and every match, pool, hit-scoring and streaming
+ * entry point works on the result unchanged.
+ *
+ * Let g = gcd(src_rate, dst_rate), L = dst_rate / g, M = src_rate / g, R = max(L, M), H = 10 R, c = 1 / R.  The filter,
+ * computed on the host in f64 and stored as f32:
+ *     h[j] = L * w[j] / sum_i w[i],   w[j] = c * sinc(c j) * I0(5 sqrt(1 - (j/H)^2)) / I0(5),   j = -H .. H
+ * (sinc(x) = sin(pi x) / (pi x)).  The output length is n_out = ceil(n_in * L / M) and the output
+ *     y[k] = sum over n in [0, n_in) with |k M - n L| <= H of  x[n] * h[k M - n L]
+ * which is scipy.signal.resample_poly(x, L, M) with its default window (('kaiser', 5.0), half_len = 10 max(L, M)).
+ *   x          f32 mono, or for AM_FMT_S16_STEREO the down-mix (l + r) * 0.5 * (1/65535) bit for bit as above; n_in counts
+ *              samples, or frames for AM_FMT_S16_STEREO.
+ *   src_rate == dst_rate: y = x, the input's bits (f32) or the down-mix's bits (i16).
+ *   Non-finite samples spread, by IEEE arithmetic, to the outputs whose support holds them and to no others; the
+ *   matcher then drops exactly those windows, as for any haystack.
+ *   Accumulation is f32 in one fixed order: every entry point gives the same bits for the same input, and
+ *   max |y - y_f64| <= 1e-5 max |x|.  Index arithmetic is 64-bit.
+ *   AM_ERR_INVALID_ARG: a rate outside [1, 768000], R > 8192 (every pair of 8, 11.025, 12, 16, 22.05, 24, 32, 44.1, 48,
+ *   64, 88.2, 96, 176.4, 192 and 384 kHz is within it; the worst, 11025 <-> 384000, has R = 5120), an unknown sample
+ *   format, a null pointer.  The filter table of each (L, M) is built once per device and kept until am_shutdown. */
+/* pure host function (no device), like am_correlate_len: n_out = ceil(n_in * L / M); n_in = 0 gives 0 */
+int am_resample_len(size_t n_in, uint32_t src_rate, uint32_t dst_rate, size_t* n_out);
+/* Host memory in and out.  *n_out receives the output length; on AM_ERR_CAPACITY (cap < n_out) nothing is written
+ * but *n_out, the required length.  n_in = 0: AM_OK, *n_out = 0, nothing launched. */
+int am_resample(int device, const void* in, size_t n_in, int sample_format, uint32_t src_rate, uint32_t dst_rate,
+                float* out, size_t cap, size_t* n_out);
+/* the same on device pointers (resident on `device`, not overlapping); complete when the call returns.  One call
+ * brings a whole haystack to another rate, e.g. a batch of mixed-rate archives to one rate for am_match_batch_device. */
+int am_resample_device(int device, const void* d_in, size_t n_in, int sample_format, uint32_t src_rate, uint32_t dst_rate,
+                       float* d_out, size_t cap, size_t* n_out);
+/* LibConvolve::new(sample_data) (audio_matcher.rs:289) on a needle brought from src_rate to dst_rate: the handle
+ * am_needle_create gives on am_resample's output, bit for bit (am_needle_len reports n_out).  Everything downstream is
+ * unchanged.  Pools keep their own am_pool_create*: pass them am_resample's output. */
+int am_needle_create_resampled(int device, const void* needle, size_t n, int sample_format, uint32_t src_rate,
+                               uint32_t dst_rate, am_needle** out);
+
 /* ---- device memory plumbing (for hosts without their own HIP allocator) -- */
 int am_device_malloc(int device, size_t bytes, void** out);
 int am_device_free(int device, void* p);

@@ -66,6 +66,17 @@ struct Config {
     }
 };
 
+// sample-rate conversion (am_resample, audiomatch.h): x (f32 mono, or interleaved i16 stereo with AM_FMT_S16_STEREO;
+// n samples / frames) from src_rate to dst_rate, as scipy.signal.resample_poly computes it
+inline std::vector<float> resample(const void* x, std::size_t n, int sample_format, std::uint32_t src_rate, std::uint32_t dst_rate,
+                                   int device = 0) {
+    std::size_t len = 0;
+    check(am_resample_len(n, src_rate, dst_rate, &len));
+    std::vector<float> out(len);
+    check(am_resample(device, x, n, sample_format, src_rate, dst_rate, out.data(), out.size(), &len));
+    return out;
+}
+
 // trait CorrelateAlgo<f32> (audio_matcher.rs:65-76)
 // option keys of window-energy normalised scores (audiomatch.h): HipConvolve::set_option(kOptScoreNorm, 1) for NCC
 // on one handle, am_set_option for the process default and the floor
@@ -90,6 +101,11 @@ class HipConvolve final : public CorrelateAlgo {
 public:
     explicit HipConvolve(const std::vector<float>& sample_data, int device = 0) {
         check(am_needle_create(device, sample_data.data(), sample_data.size(), &h_));
+    }
+    // am_needle_create_resampled: the needle (f32 mono, or interleaved i16 stereo with AM_FMT_S16_STEREO; n samples /
+    // frames) brought from src_rate to the haystack's dst_rate
+    HipConvolve(const void* needle, std::size_t n, int sample_format, std::uint32_t src_rate, std::uint32_t dst_rate, int device = 0) {
+        check(am_needle_create_resampled(device, needle, n, sample_format, src_rate, dst_rate, &h_));
     }
     HipConvolve(const HipConvolve&) = delete;
     HipConvolve& operator=(const HipConvolve&) = delete;
