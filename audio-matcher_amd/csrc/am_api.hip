@@ -201,6 +201,56 @@ int am_match_multi_batch_device(const am_needle* const* needles, size_t n_needle
                             out, cap_per_pair, n_out);
 }
 
+// ---- several needles of any lengths (match_multi_many with `varlen`) ----
+static int check_multi_varlen(const am_needle* const* needles, size_t n_needles, int sample_format, const am_match_params* p, am_needle** h0) {
+    if (!needles || n_needles == 0 || !p) return fail(AM_ERR_INVALID_ARG, "null pointer");
+    if (sample_format != AM_FMT_F32_MONO && sample_format != AM_FMT_S16_STEREO) return fail(AM_ERR_INVALID_ARG, "bad sample format");
+    for (size_t k = 0; k < n_needles; ++k)
+        if (!needles[k] || !needles[k]->ctx) return fail(AM_ERR_INVALID_ARG, "null needle handle");
+    for (size_t k = 1; k < n_needles; ++k)
+        if (needles[k]->ctx != needles[0]->ctx) return fail(AM_ERR_INVALID_ARG, "needles must live on one device");
+    *h0 = const_cast<am_needle*>(needles[0]);
+    int rc = check_needle(*h0);
+    if (rc) return rc;
+    if (snapshot_opts(*h0).score_norm) return fail(AM_ERR_INVALID_ARG, AM_NORM_UNSUPPORTED);
+    return AM_OK;
+}
+
+int am_match_multi_varlen_batch_device(const am_needle* const* needles, size_t n_needles, const uint64_t* overlaps,
+                                       const void* const* d_haystacks, const size_t* lens, size_t n_hay,
+                                       int sample_format, const am_match_params* p,
+                                       am_peak* out, size_t cap_per_pair, size_t* n_out) {
+    if (!d_haystacks || !lens || !n_out || (!out && cap_per_pair)) return fail(AM_ERR_INVALID_ARG, "null pointer");
+    am_needle* h0 = nullptr;
+    int rc = check_multi_varlen(needles, n_needles, sample_format, p, &h0);
+    if (rc) return rc;
+    if (n_hay == 0) return AM_OK;
+    std::lock_guard<std::recursive_mutex> lk(h0->ctx->mu);
+    return match_multi_many(const_cast<am_needle* const*>(needles), n_needles, d_haystacks, lens, n_hay, sample_format, p,
+                            out, cap_per_pair, n_out, 0, 1, overlaps, true);
+}
+
+int am_match_multi_varlen(const am_needle* const* needles, size_t n_needles, const uint64_t* overlaps,
+                          const void* haystack, size_t len, int sample_format, const am_match_params* p,
+                          am_peak* out, size_t cap_per_needle, size_t* n_out) {
+    if (!haystack || !n_out || (!out && cap_per_needle)) return fail(AM_ERR_INVALID_ARG, "null pointer");
+    am_needle* h0 = nullptr;
+    int rc = check_multi_varlen(needles, n_needles, sample_format, p, &h0);
+    if (rc) return rc;
+    if (len == 0) {
+        for (size_t j = 0; j < n_needles; ++j) n_out[j] = 0;
+        return AM_OK;
+    }
+    Ctx* c = h0->ctx;
+    std::lock_guard<std::recursive_mutex> lk(c->mu);
+    const size_t bytes = len * (sample_format == AM_FMT_S16_STEREO ? 2 * sizeof(int16_t) : sizeof(float));
+    if ((rc = c->io_in.ensure(bytes))) return rc;
+    AM_HIP(copy_on_stream(c, c->io_in.p, haystack, bytes, hipMemcpyHostToDevice));
+    const void* d_in = c->io_in.p;
+    return match_multi_many(const_cast<am_needle* const*>(needles), n_needles, &d_in, &len, 1, sample_format, p, out, cap_per_needle, n_out,
+                            0, 1, overlaps, true);
+}
+
 // ---- the same three entry points on interleaved i16 stereo PCM: the down-mix of
 // mp3_reader.rs:28-37 happens inside K1's loads, so the haystack is read once ----
 int am_match_pcm16_device(const am_needle* hc, const int16_t* d_interleaved, size_t frames,

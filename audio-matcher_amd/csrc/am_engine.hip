@@ -1,5 +1,5 @@
 // am_engine.hip -- the batch engines: match_many (one needle against a batch of haystacks) and match_multi_many
-// (several needles of one length), with what they share: the chunk plan, the two score sets, the tails of a batch.
+// (several needles, of one length or of any lengths), with what they share: the chunk plan, the two score sets, the tails of a batch.
 // Host-side mirror of the reference's driver (paths relative to the reference):
 //   calc_chunks            src/matcher/audio_matcher.rs:88-141
 //   is_overshadowed        src/matcher/audio_matcher.rs:143-160
@@ -650,21 +650,25 @@ int match_many(am_needle* h, const void* const* d_hays, const size_t* lens, size
 // (k2_rows_r16_group), each needle with its own inverse rows, K3 (fused scan) and peak pick.  The
 // pick of (haystack, needle) runs on the second stream beside the next needle's K3 / the next
 // haystack's K1 and K2; the score-side buffers alternate between two sets, as in match_many.
-// Needles must share one length so that they share the block layout.
+// Needles must share one length, unless `varlen` (am_match_multi_varlen*): then every haystack has ONE block layout,
+// that of the longest needle -- hop N - S_max + 1 on the plan it would pick -- and a shorter needle's spectrum on it is
+// that of the needle zero-padded to S_max (the zeros change none of its scores t <= len - S_j, nor its energy).  The
+// main pass reaches the shortest needle's last score; needle j's scores end at len - S_j + 1 (K3Group::out_count: the
+// partial sums behind it are neither written, summarised nor picked), and each needle has a chunk plan of its own (its
+// length, overlap overlaps[j]), result headers and redo.  The needles are grouped longest first.
 // Result slot of (haystack k of the caller's batch, needle j): G(k) * nn + j.
 int match_multi_many(am_needle* const* needles, size_t nn, const void* const* d_hays, const size_t* lens, size_t n_hay,
                      int src_kind, const am_match_params* p, am_peak* out, size_t cap_per_pair, size_t* n_out,
-                     size_t index_base, size_t index_stride) {
+                     size_t index_base, size_t index_stride, const uint64_t* overlaps, bool varlen) {
     am_needle* h0 = needles[0];
     Ctx* c = h0->ctx;
     const Opts o = snapshot_opts(h0);
     const PeakPolicy pol = o.peak_policy();
     const Hooks hooks = snapshot_hooks();
     auto G = [&](size_t k) { return index_base + k * index_stride; };
-    const size_t s = h0->n;
     for (size_t j = 0; j < nn; ++j) {
         if (!needles[j] || needles[j]->ctx != c) return fail(AM_ERR_INVALID_ARG, "needles must live on one device");
-        if (needles[j]->n != s) return fail(AM_ERR_INVALID_ARG, "am_match_multi: needles must have equal length");
+        if (!varlen && needles[j]->n != h0->n) return fail(AM_ERR_INVALID_ARG, "am_match_multi: needles must have equal length");
     }
     if (o.score_norm) return fail(AM_ERR_INVALID_ARG, AM_NORM_UNSUPPORTED);
     if (p->chunk == 0) return fail(AM_ERR_INVALID_ARG, "chunk must be > 0");
@@ -672,29 +676,75 @@ int match_multi_many(am_needle* const* needles, size_t nn, const void* const* d_
         return fail(AM_ERR_INVALID_ARG, "am_match_multi supports AM_SCALE_NONE and AM_SCALE_LIB");
     for (size_t k = 0; k < n_hay; ++k)
         for (size_t j = 0; j < nn; ++j) n_out[G(k) * nn + j] = 0;
+    // needle j's parameters: the call's, with its own overlap
+    std::vector<am_match_params> pj(nn, *p);
+    if (overlaps)
+        for (size_t j = 0; j < nn; ++j) pj[j].overlap = overlaps[j];
     int rc, worst = AM_OK;
-    if (needle_is_segmented(h0, o)) {
-        // partitioned needles (longer than kSegmentFrom samples) share nothing here: pair by pair
+    // partitioned needles (longer than kSegmentFrom samples) share nothing here: pair by pair; the others go in groups,
+    // longest first (a stable order: needles of one length keep the caller's)
+    std::vector<size_t> ord;
+    bool any_segmented = false;
+    for (size_t j = 0; j < nn; ++j) {
+        if (needle_is_segmented(needles[j], o)) any_segmented = true;
+        else ord.push_back(j);
+    }
+    if (any_segmented)
         for (size_t k = 0; k < n_hay; ++k)
             for (size_t j = 0; j < nn; ++j)
-                if ((rc = match_alone(needles[j], d_hays[k], lens[k], p, out, cap_per_pair, G(k) * nn + j, n_out, src_kind, nullptr, &worst)))
+                if (needle_is_segmented(needles[j], o) &&
+                    (rc = match_alone(needles[j], d_hays[k], lens[k], &pj[j], out, cap_per_pair, G(k) * nn + j, n_out, src_kind, nullptr, &worst)))
                     return rc;
-        return worst;
-    }
+    if (ord.empty()) return worst;
+    std::stable_sort(ord.begin(), ord.end(), [&](size_t a, size_t b) { return needles[a]->n > needles[b]->n; });
+    const size_t m = ord.size();                        // grouped needles; local index i is needle ord[i]
+    const size_t s = needles[ord[0]]->n;                // the longest: the block layout's
+    const size_t s_min = needles[ord[m - 1]]->n;        // the shortest: the layout's score count
     const int sm = p->scale == AM_SCALE_LIB ? 1 : 0;
-    ChunkPlan cp;
-    plan_chunks(s, d_hays, lens, n_hay, p, o, false, (size_t)-1, &cp);
-    const std::vector<int>& seg_off = cp.seg_off;
-    const size_t nsegs = cp.segs.size();
-    if (nsegs == 0) return AM_OK;
-    if (cp.too_many(nn)) return fail(AM_ERR_INVALID_ARG, "chunk size too small for this batch (too many chunks)");
+    // one chunk plan per distinct (length, overlap); their chunk lists back to back in the resident list, needle i's
+    // result headers at hdr_base[i] + (its plan's chunk index)
+    std::vector<ChunkPlan> cps;
+    std::vector<std::pair<size_t, uint64_t>> keys;
+    std::vector<int> plan_of(m), seg_base, hdr_base(m);
+    for (size_t i = 0; i < m; ++i) {
+        const size_t j = ord[i];
+        const std::pair<size_t, uint64_t> key(needles[j]->n, pj[j].overlap);
+        const size_t u = (size_t)(std::find(keys.begin(), keys.end(), key) - keys.begin());
+        if (u == keys.size()) {
+            keys.push_back(key);
+            cps.emplace_back();
+            plan_chunks(key.first, d_hays, lens, n_hay, &pj[j], o, false, (size_t)-1, &cps.back());
+        }
+        plan_of[i] = (int)u;
+    }
+    std::vector<Segment> all_segs;
+    size_t max_scores = 0, max_segs = 1, nhdr = 0;
+    bool too_many = false;
+    for (const ChunkPlan& cpu : cps) {
+        seg_base.push_back((int)all_segs.size());
+        all_segs.insert(all_segs.end(), cpu.segs.begin(), cpu.segs.end());
+        max_scores = std::max(max_scores, cpu.max_scores);
+        max_segs = std::max(max_segs, cpu.max_segs);
+        too_many = too_many || cpu.too_many(1);
+    }
+    for (size_t i = 0; i < m; ++i) { hdr_base[i] = (int)nhdr; nhdr += cps[plan_of[i]].segs.size(); }
+    if (nhdr == 0) return worst;
+    if (too_many || nhdr > (size_t)1 << 24) return fail(AM_ERR_INVALID_ARG, "chunk size too small for this batch (too many chunks)");
+    auto plan_i = [&](size_t i) -> const ChunkPlan& { return cps[plan_of[i]]; };
+    auto seg_of = [&](size_t k, size_t i) { return seg_base[plan_of[i]] + plan_i(i).seg_off[k]; };
+    // result headers of (haystack k, needle i): the needle's, the haystack's slice inside
+    auto hdr_of = [&](size_t k, size_t i) { return hdr_base[i] + plan_i(i).seg_off[k]; };
+    // chunks of haystack k for the progress callbacks: the most any needle has
+    auto ns_max = [&](size_t k) { int n = 0; for (const ChunkPlan& cpu : cps) n = std::max(n, cpu.ns(k)); return n; };
+    // the scores needle i has in haystack k (<= 0: the haystack is shorter than the needle)
+    auto count_of = [&](size_t k, size_t i) { return (long long)lens[k] - (long long)needles[ord[i]]->n + 1; };
     // each haystack's block layout
     std::vector<Geometry> geo(n_hay);
     std::vector<TailPlan> tails(n_hay);   // the odd last block on the 2^21 plan (TailPlan), for haystacks whose needle groups all take the grouped K3
     size_t max_matrix = 0, max_wflags = 0, max_tail = 0;
     for (size_t k = 0; k < n_hay; ++k) {
-        if (cp.ns(k) == 0) continue;
-        const long long out_count = (long long)(lens[k] - s + 1);
+        if (ns_max(k) == 0) continue;
+        const long long out_count = (long long)(lens[k] - s_min + 1);
         if ((rc = plan_geometry(s, out_count, o, &geo[k]))) return rc;
         max_matrix = std::max(max_matrix, (size_t)geo[k].npairs * (size_t)geo[k].N);
         { const Plan* plk = nullptr; if ((rc = get_plan(c, geo[k].logN, &plk))) return rc; max_wflags = std::max(max_wflags, sparse_bytes(geo[k].nblocks, plk->dev)); }
@@ -707,22 +757,22 @@ int match_multi_many(am_needle* const* needles, size_t nn, const void* const* d_
         const Plan* pl = nullptr;
         int rc2 = get_plan(c, logN, &pl);
         std::vector<const float2*>& v = hcs[logN];
-        v.resize(nn);
+        v.resize(m);
         HalfScale hs;
-        for (size_t j = 0; j < nn && !rc2; ++j) rc2 = needle_k2_spectrum(needles[j], o, pl, &v[j], &hs);
+        for (size_t i = 0; i < m && !rc2; ++i) rc2 = needle_k2_spectrum(needles[ord[i]], o, pl, &v[i], &hs);
         return rc2;
     };
     for (size_t k = 0; k < n_hay; ++k)
-        if (cp.ns(k) > 0 && (rc = spectra(geo[k].logN))) return rc;
+        if (ns_max(k) > 0 && (rc = spectra(geo[k].logN))) return rc;
     const size_t group_opt = (size_t)std::min<long long>(std::max<long long>(1, o.needle_group), kMaxNeedleGroup);
     // The tail needs every needle group of the haystack on the grouped-K3 path (the other paths keep the full layout):
     // f32, groups of at least two needles each, the 512-row plan with a 256-row tail.
     {
-        const bool groups_ok = o.k3_group && group_opt > 1 && nn > 1 && !o.half && (nn % group_opt) != 1 && c->stream_tail != nullptr;
+        const bool groups_ok = o.k3_group && group_opt > 1 && m > 1 && !o.half && (m % group_opt) != 1 && c->stream_tail != nullptr;
         for (size_t k = 0; k < n_hay; ++k) {
             if (!tails[k].on) continue;
             const Plan* plk = nullptr;
-            if (cp.ns(k) == 0 || !groups_ok || !tail_batchable(tails[k]) || get_plan(c, geo[k].logN, &plk) || !plan_is_c512(plk->dev)) {
+            if (ns_max(k) == 0 || !groups_ok || !tail_batchable(tails[k]) || get_plan(c, geo[k].logN, &plk) || !plan_is_c512(plk->dev)) {
                 tails[k].on = false;
                 continue;
             }
@@ -731,56 +781,53 @@ int match_multi_many(am_needle* const* needles, size_t nn, const void* const* d_
         }
         if (max_tail) {
             if ((rc = c->work_tail.ensure(std::max(c->work_tail.cap, max_tail * sizeof(float2))))) return rc;
-            if ((rc = c->work_tail2.ensure(std::min(group_opt, nn) * max_tail * sizeof(float2)))) return rc;
+            if ((rc = c->work_tail2.ensure(std::min(group_opt, m) * max_tail * sizeof(float2)))) return rc;
         }
     }
     size_t n_pairs_active = 0;
-    for (size_t k = 0; k < n_hay; ++k) n_pairs_active += cp.ns(k) > 0 ? nn : 0;
+    for (size_t k = 0; k < n_hay; ++k) n_pairs_active += ns_max(k) > 0 ? m : 0;
     ScoreSets sets(c, o, n_pairs_active);
     if ((rc = c->work.ensure(max_matrix * sizeof(float2)))) return rc;
-    if ((rc = c->work2.ensure(std::min(group_opt, nn) * max_matrix * sizeof(float2)))) return rc;
-    if ((rc = sets.size(cp.max_scores, cp.max_segs))) return rc;
+    if ((rc = c->work2.ensure(std::min(group_opt, m) * max_matrix * sizeof(float2)))) return rc;
+    if ((rc = sets.size(max_scores, max_segs))) return rc;
     for (int set = 0; set < sets.count(); ++set) {
-        if ((rc = (set ? c->stats32_b : c->stats32).ensure((cp.max_scores + 31) / 32 * sizeof(float2)))) return rc;
+        if ((rc = (set ? c->stats32_b : c->stats32).ensure((max_scores + 31) / 32 * sizeof(float2)))) return rc;
         if ((rc = (set ? c->wflags_b : c->wflags).ensure(max_wflags))) return rc;
     }
     // one K3 launch per needle group: every needle of a group (two groups in flight) has its own score-side buffers
-    const size_t k3_group = (o.k3_group && group_opt > 1 && nn > 1 && !o.half && max_wflags > 0) ? std::min(group_opt, nn) : 0;
+    const size_t k3_group = (o.k3_group && group_opt > 1 && m > 1 && !o.half && max_wflags > 0) ? std::min(group_opt, m) : 0;
     for (size_t i = 0; i < k3_group * (size_t)sets.count(); ++i) {
         const size_t slot = i < k3_group ? i : kMaxNeedleGroup + (i - k3_group);
-        if ((rc = c->grp_scores[slot].ensure(cp.max_scores * sizeof(float)))) return rc;
-        if ((rc = c->grp_stats32[slot].ensure((cp.max_scores + 31) / 32 * sizeof(float2)))) return rc;
+        if ((rc = c->grp_scores[slot].ensure(max_scores * sizeof(float)))) return rc;
+        if ((rc = c->grp_stats32[slot].ensure((max_scores + 31) / 32 * sizeof(float2)))) return rc;
         if ((rc = c->grp_wflags[slot].ensure(max_wflags))) return rc;
     }
     if (k3_group && o.pick_group) {   // ... and the scratch of the group's picks, which run as one set of launches
-        const size_t total = k3_group * cp.max_segs;
+        const size_t total = k3_group * max_segs;
         for (size_t z = 0; z < k3_group; ++z)
-            if ((rc = c->grp_stats[z].ensure((cp.max_scores + kTile - 1) / kTile * sizeof(float2)))) return rc;
+            if ((rc = c->grp_stats[z].ensure((max_scores + kTile - 1) / kTile * sizeof(float2)))) return rc;
         if ((rc = c->wide_ctl.ensure(total * 24))) return rc;
         if ((rc = c->wide_list.ensure(total * AM_MAX_PEAKS_PER_CHUNK * sizeof(am_peak)))) return rc;
         if ((rc = c->wide_tiles.ensure(total * kWideTileList * sizeof(int)))) return rc;
         if ((rc = c->peaks.ensure(total * AM_MAX_PEAKS_PER_CHUNK * sizeof(am_peak)))) return rc;
     }
     PeakArena arena{};
-    if ((rc = prepare_results(c, nsegs * nn, nsegs * nn * 8 + 4096, &arena))) return rc;
-    if ((rc = upload_segments(c, cp.segs))) return rc;
+    if ((rc = prepare_results(c, nhdr, nhdr * 8 + 4096, &arena))) return rc;
+    if ((rc = upload_segments(c, all_segs))) return rc;
     if ((rc = c->badflag.ensure(sizeof(int) * n_hay))) return rc;
     int* h_bad = static_cast<int*>(c->badflag.p);
     memset(h_bad, 0, sizeof(int) * n_hay);
     SegHeader* h_hdr = static_cast<SegHeader*>(c->hdr.p);
-    // result headers of (haystack k, needle j): nsegs entries per needle, the haystack's slice inside
-    auto hdr_of = [&](size_t k, size_t j) { return (int)(j * nsegs) + seg_off[k]; };
     const float margin = write_margin(o, p);
     QueueingScope queueing(o.debug_no_realloc != 0);
     for (size_t k = 0; k < n_hay; ++k) {
-        const int ns = cp.ns(k);
-        if (ns == 0) continue;
-        if (hooks.fn) hooks.fn(hooks.user, G(k), 0, (size_t)ns);
+        if (ns_max(k) == 0) continue;
+        if (hooks.fn) hooks.fn(hooks.user, G(k), 0, (size_t)ns_max(k));
         const Geometry& g = geo[k];
         const Plan* pl = nullptr;
         if ((rc = get_plan(c, g.logN, &pl))) return rc;
         const std::vector<const float2*>& hc = hcs[g.logN];
-        const long long out_count = (long long)(lens[k] - s + 1);
+        const long long out_count = (long long)(lens[k] - s_min + 1);
         const int half = (o.half && (plan_is_r16(pl->dev) || plan_is_c512(pl->dev))) ? (o.half >= 2 ? 2 : 1) : 0;
         const size_t group = (!half && plan_k2_has_group(pl->dev)) ? group_opt : 1;
         const size_t matrix = (size_t)g.npairs * (size_t)g.N;
@@ -802,21 +849,21 @@ int match_multi_many(am_needle* const* needles, size_t nn, const void* const* d_
             ProfScope ps(c, KN_OTHER);
             AM_HIP(launch_k1(c->stream, job_t, 1, (float2*)c->work_tail.p, plt->dev, 0));
         }
-        for (size_t j = 0; j < nn; ++j) {
-            am_needle* h = needles[j];
-            const size_t in_group = j % group;
+        for (size_t i = 0; i < m; ++i) {
+            am_needle* h = needles[ord[i]];
+            const size_t in_group = i % group;
             const float2* inv_rows = (const float2*)c->work2.p + in_group * matrix;   // this needle's inverse rows
-            const size_t gn = std::min(group, nn - (j - in_group));
+            const size_t gn = std::min(group, m - (i - in_group));
             if (group > 1 && in_group == 0) {
                 K2Group grp{};
                 grp.n = (int)gn;
-                for (int q = 0; q < grp.n; ++q) { grp.hc[q] = hc[j + q]; grp.dst[q] = (float2*)c->work2.p + (size_t)q * matrix; }
+                for (int q = 0; q < grp.n; ++q) { grp.hc[q] = hc[i + q]; grp.dst[q] = (float2*)c->work2.p + (size_t)q * matrix; }
                 { ProfScope ps(c, KN_K2); AM_HIP(launch_k2_group(c->stream, main_pairs, (const float2*)c->work.p, grp, pl->dev)); }
                 if (tail.on) {
                     K2Group gt{};
                     gt.n = (int)gn;
                     const std::vector<const float2*>& hct = hcs[tail.g.logN];
-                    for (int q = 0; q < gt.n; ++q) { gt.hc[q] = hct[j + q]; gt.dst[q] = (float2*)c->work_tail2.p + (size_t)q * (size_t)tail.g.N; }
+                    for (int q = 0; q < gt.n; ++q) { gt.hc[q] = hct[i + q]; gt.dst[q] = (float2*)c->work_tail2.p + (size_t)q * (size_t)tail.g.N; }
                     ProfScope ps(c, KN_OTHER);
                     AM_HIP(launch_k2_group(c->stream, 1, (const float2*)c->work_tail.p, gt, plt->dev));
                 }
@@ -830,26 +877,34 @@ int match_multi_many(am_needle* const* needles, size_t nn, const void* const* d_
                 kg.n = (int)gn;
                 ScanRequest scans[kMaxNeedleGroup];
                 ScanCfg common{};
+                bool same_plan = true, same_edges = true;
                 for (size_t q = 0; q < gn; ++q) {
-                    am_needle* hq = needles[j + q];
+                    am_needle* hq = needles[ord[i + q]];
                     const size_t slot = (size_t)set * kMaxNeedleGroup + q;
                     ScanRequest& sc = scans[q];
                     sc = ScanRequest{};
                     sc.set = 0;          // (the picks of a call run one after the other: they share the pick's own scratch)
                     sc.margin = margin; sc.hist_min = hq->hist_min(sm);
-                    sc.seg_c = (long long)p->chunk; sc.seg_d = (long long)(p->chunk + p->overlap) - (long long)s;
+                    sc.seg_c = (long long)p->chunk; sc.seg_d = (long long)(p->chunk + pj[ord[i + q]].overlap) - (long long)hq->n;
                     sc.bad = (src_kind == 0 || o.half) ? &h_bad[k] : nullptr;
                     sc.fused = true;
                     ScanCfg cfg{};
                     fill_scan_cfg(&cfg, c->grp_stats32[slot].p, c->grp_wflags[slot].p, g.nblocks, pl->dev, margin, sc.hist_min, sc.seg_c, sc.seg_d);
                     sc.sparse = sparse_view(cfg, g.hop, pl->dev);
                     if (q == 0) common = cfg;
+                    same_plan = same_plan && plan_of[i + q] == plan_of[i];
+                    same_edges = same_edges && cfg.seg_d == common.seg_d;
                     kg.work[q] = (const float2*)c->work2.p + q * matrix;
                     kg.dst[q] = (float*)c->grp_scores[slot].p;
                     kg.stats32[q] = cfg.stats32; kg.wbits[q] = cfg.wbits; kg.tile_theta[q] = cfg.tile_theta;
                     kg.hist_min[q] = cfg.hist_min;
                     kg.out_scale[q] = half_scale(hq, o, pl->dev).k3(scale_factor(hq, p->scale, 1));
+                    kg.out_count[q] = std::max(0ll, std::min(count_of(k, i + q), job.out_count));
+                    kg.seg_d[q] = cfg.seg_d;
                 }
+                kg.seg_c = common.seg_c; kg.inv_c = common.inv_c;
+                // members whose chunk edges differ work them out themselves: no edge table from the launch's geometry
+                if (!same_edges) common.seg_c = 0;
                 // K3 overwrites this set's scores and summaries: the picks that last read them must be done
                 if ((rc = sets.wait_pick(false))) return rc;
                 { ProfScope ps(c, KN_K3); AM_HIP(launch_k3_group(c->stream, job, main_pairs, kg, pl->dev, common)); }
@@ -859,7 +914,10 @@ int match_multi_many(am_needle* const* needles, size_t nn, const void* const* d_
                         kt.work[q] = (const float2*)c->work_tail2.p + q * (size_t)tail.g.N;
                         kt.dst[q] = kg.dst[q] + tail.T; kt.stats32[q] = kg.stats32[q] + tail.T / 32;
                         kt.wbits[q] = nullptr; kt.tile_theta[q] = nullptr; kt.hist_min[q] = FLT_MAX;
+                        kt.out_count[q] = std::max(0ll, count_of(k, i + q) - tail.T);
+                        kt.seg_d[q] = 0;
                     }
+                    kt.seg_c = 0; kt.inv_c = 0.0;
                     ScanCfg dense{};
                     dense.stats32 = kt.stats32[0]; dense.margin = -1.0f; dense.hist_min = FLT_MAX;
                     ProfScope ps(c, KN_OTHER);
@@ -868,26 +926,31 @@ int match_multi_many(am_needle* const* needles, size_t nn, const void* const* d_
                         AM_HIP(launch_tail_preset_group(c->stream, kg, (long long)(g.nblocks - 1), pl->dev.logN1, pl->dev.logN2));
                 }
                 if ((rc = sets.k3_done())) return rc;
-                if (o.pick_group) {
+                if (o.pick_group && same_plan && plan_i(i).ns(k) > 0) {   // (one chunk list for the whole group)
                     int hoff[kMaxNeedleGroup];
-                    for (size_t q = 0; q < gn; ++q) hoff[q] = hdr_of(k, j + q);
-                    if ((rc = launch_pick_group(c, kg, out_count, seg_off[k], ns, p->min_prominence, (long long)p->min_distance, scans[0].sparse,
-                                                scans[0].bad, hoff, arena, pol, sets.pick_stream()))) return rc;
+                    for (size_t q = 0; q < gn; ++q) hoff[q] = hdr_of(k, i + q);
+                    if ((rc = launch_pick_group(c, kg, count_of(k, i), seg_of(k, i), plan_i(i).ns(k), p->min_prominence, (long long)p->min_distance,
+                                                scans[0].sparse, scans[0].bad, hoff, arena, pol, sets.pick_stream()))) return rc;
                 } else
                 for (size_t q = 0; q < gn; ++q)
-                    if ((rc = launch_pick(c, kg.dst[q], out_count, seg_off[k], ns, p->min_prominence, (long long)p->min_distance,
-                                          &scans[q], hdr_of(k, j + q), arena, pol, sets.pick_stream()))) return rc;
+                    if (plan_i(i + q).ns(k) > 0 &&
+                        (rc = launch_pick(c, kg.dst[q], count_of(k, i + q), seg_of(k, i + q), plan_i(i + q).ns(k), p->min_prominence,
+                                          (long long)p->min_distance, &scans[q], hdr_of(k, i + q), arena, pol, sets.pick_stream()))) return rc;
                 if ((rc = sets.pick_done())) return rc;
                 continue;
             }
+            const int ns = plan_i(i).ns(k);
+            if (ns == 0) continue;   // (a haystack shorter than this needle: nothing to correlate)
             float* d_scores = sets.scores();
-            job.dst = d_scores;
+            Job jn = job;   // (this needle's scores end before the layout's: tails only run on the grouped path)
+            jn.dst = d_scores;
+            jn.out_count = std::min(count_of(k, i), job.out_count);
             ScanRequest scan{};
             scan.set = set;
             scan.margin = margin;
             scan.hist_min = h->hist_min(sm);
             scan.seg_c = (long long)p->chunk;
-            scan.seg_d = (long long)(p->chunk + p->overlap) - (long long)s;
+            scan.seg_d = (long long)(p->chunk + pj[ord[i]].overlap) - (long long)h->n;
             scan.bad = (src_kind == 0 || o.half) ? &h_bad[k] : nullptr;   // (i16 frames are always finite; an f16 transform can overflow)
             scan.fused = fused;
             scan.sparse = SparseScores{nullptr, nullptr, nullptr, (int)g.hop, pl->dev.logN2, pl->dev.logN1, 1.0 / (double)g.hop};
@@ -901,14 +964,14 @@ int match_multi_many(am_needle* const* needles, size_t nn, const void* const* d_
             const HalfScale hs = half_scale(h, o, pl->dev);
             if (group == 1) {
                 ProfScope ps(c, KN_K2);
-                AM_HIP(launch_k2(c->stream, (int)g.npairs, (float2*)c->work.p, hc[j], pl->dev, (float2*)c->work2.p, hs.level, hs.hscale, hs.pre));
+                AM_HIP(launch_k2(c->stream, (int)g.npairs, (float2*)c->work.p, hc[i], pl->dev, (float2*)c->work2.p, hs.level, hs.hscale, hs.pre));
             }
             // K3 overwrites this set's scores and summaries: the pick that last read them must be done
             if ((rc = sets.wait_pick(false))) return rc;
-            { ProfScope ps(c, KN_K3); AM_HIP(launch_k3(c->stream, job, (int)g.npairs, inv_rows, pl->dev, hs.k3(factor), cfg, half)); }
+            { ProfScope ps(c, KN_K3); AM_HIP(launch_k3(c->stream, jn, (int)g.npairs, inv_rows, pl->dev, hs.k3(factor), cfg, half)); }
             if ((rc = sets.k3_done())) return rc;
-            if ((rc = launch_pick(c, d_scores, out_count, seg_off[k], ns, p->min_prominence, (long long)p->min_distance,
-                                  &scan, hdr_of(k, j), arena, pol, sets.pick_stream()))) return rc;
+            if ((rc = launch_pick(c, d_scores, count_of(k, i), seg_of(k, i), ns, p->min_prominence, (long long)p->min_distance,
+                                  &scan, hdr_of(k, i), arena, pol, sets.pick_stream()))) return rc;
             if ((rc = sets.pick_done())) return rc;
         }
     }
@@ -917,10 +980,11 @@ int match_multi_many(am_needle* const* needles, size_t nn, const void* const* d_
     std::vector<am_peak> all;
     std::vector<std::pair<size_t, size_t>> redo;
     for (size_t k = 0; k < n_hay; ++k) {
-        const int ns = cp.ns(k);
-        if (ns == 0) continue;
-        for (size_t j = 0; j < nn; ++j) {
-            const SegHeader* hd = h_hdr + hdr_of(k, j);
+        for (size_t i = 0; i < m; ++i) {
+            const int ns = plan_i(i).ns(k);
+            if (ns == 0) continue;
+            const size_t j = ord[i];
+            const SegHeader* hd = h_hdr + hdr_of(k, i);
             const size_t slot = G(k) * nn + j;
             // Non-finite samples poison whole block pairs for every needle (see match_many): such a
             // haystack goes through the single-needle path, which gives every window the reference's
@@ -928,26 +992,26 @@ int match_multi_many(am_needle* const* needles, size_t nn, const void* const* d_
             // AM_MAX_PEAKS_PER_CHUNK peaks in a chunk.
             bool again = h_bad[k] != 0;
             float lowest = FLT_MAX;
-            for (int i = 0; i < ns && !again; ++i) {
-                if (hd[i].overflow & 7) again = true;
-                lowest = std::min(lowest, hd[i].seg_min);
+            for (int q = 0; q < ns && !again; ++q) {
+                if (hd[q].overflow & 7) again = true;
+                lowest = std::min(lowest, hd[q].seg_min);
             }
             if (!again) needles[j]->remember_min(sm, lowest);
             if (again) { redo.emplace_back(k, j); continue; }
             all.clear();
-            for (int i = 0; i < ns; ++i) append_header_peaks(hd[i], arena, all);
-            rc = merge_peaks(all, p, o.surrounding_from != 0, out ? out + slot * cap_per_pair : nullptr, cap_per_pair, &n_out[slot]);
+            for (int q = 0; q < ns; ++q) append_header_peaks(hd[q], arena, all);
+            rc = merge_peaks(all, &pj[j], o.surrounding_from != 0, out ? out + slot * cap_per_pair : nullptr, cap_per_pair, &n_out[slot]);
             if (rc == AM_ERR_CAPACITY) worst = rc;
             else if (rc) return rc;
         }
     }
     // the single-needle path reuses the result area: it runs after everything else has been collected
     for (const auto& kj : redo)
-        if ((rc = match_alone(needles[kj.second], d_hays[kj.first], lens[kj.first], p, out, cap_per_pair, G(kj.first) * nn + kj.second, n_out,
-                              src_kind, nullptr, &worst))) return rc;
+        if ((rc = match_alone(needles[kj.second], d_hays[kj.first], lens[kj.first], &pj[kj.second], out, cap_per_pair, G(kj.first) * nn + kj.second,
+                              n_out, src_kind, nullptr, &worst))) return rc;
     if (hooks.fn)
         for (size_t k = 0; k < n_hay; ++k)
-            if (cp.ns(k) > 0) hooks.fn(hooks.user, G(k), 1, (size_t)cp.ns(k));
+            if (ns_max(k) > 0) hooks.fn(hooks.user, G(k), 1, (size_t)ns_max(k));
     return worst;
 }
 

@@ -2084,10 +2084,10 @@ __global__ void __launch_bounds__(256, AM_K3_WGS)
 k3_cols_inv_r16_group(Job job, PlanDev pl, ScanCfg scan, K3Group grp) {
     extern __shared__ float4 lds4[];
     const unsigned z = blockIdx.y;
-    job.dst = grp.dst[z];
+    job.dst = grp.dst[z]; job.out_count = grp.out_count[z];
     ScanCfg mine;
     mine.stats32 = grp.stats32[z]; mine.wbits = grp.wbits[z]; mine.tile_theta = grp.tile_theta[z]; mine.hist_min = grp.hist_min[z];
-    mine.margin = scan.margin; mine.seg_c = scan.seg_c; mine.seg_d = scan.seg_d; mine.inv_c = scan.inv_c;
+    mine.margin = scan.margin; mine.seg_c = grp.seg_c; mine.seg_d = grp.seg_d[z]; mine.inv_c = grp.inv_c;
     mine.only_pairs = nullptr; mine.redo_tiles = 0; mine.edges_n = 0;
     k3_cols_inv_r16_tile<0, false>(blockIdx.x, lds4, job, grp.work[z], pl, grp.out_scale[z], mine, &scan);
 }
@@ -2544,10 +2544,10 @@ __global__ void __launch_bounds__(512, 2)
 k3_cols_inv_c512_group(Job job, PlanDev pl, ScanCfg scan, K3Group grp) {
     extern __shared__ float4 lds4[];
     const unsigned z = blockIdx.y;
-    job.dst = grp.dst[z];
+    job.dst = grp.dst[z]; job.out_count = grp.out_count[z];
     ScanCfg mine;   // (the scalar fields k3_finish reads; the edge table stays in the kernel argument: `geo`)
     mine.stats32 = grp.stats32[z]; mine.wbits = grp.wbits[z]; mine.tile_theta = grp.tile_theta[z]; mine.hist_min = grp.hist_min[z];
-    mine.margin = scan.margin; mine.seg_c = scan.seg_c; mine.seg_d = scan.seg_d; mine.inv_c = scan.inv_c;
+    mine.margin = scan.margin; mine.seg_c = grp.seg_c; mine.seg_d = grp.seg_d[z]; mine.inv_c = grp.inv_c;
     mine.only_pairs = nullptr; mine.redo_tiles = 0; mine.edges_n = 0;
     k3_cols_inv_c512_tile<0, false>(blockIdx.x, lds4, job, grp.work[z], pl, grp.out_scale[z], mine, &scan);
 }
@@ -3226,6 +3226,7 @@ hipError_t launch_tail_commit(hipStream_t st, const float* tail_scores, float* s
 
 hipError_t launch_k3_group(hipStream_t st, const Job& job, int npairs, const K3Group& grp, const PlanDev& pl, const ScanCfg& scan_in) {
     if (!plan_k3_has_group(pl) || grp.n < 1 || grp.n > kMaxNeedleGroup || scan_in.stats32 == nullptr) return hipErrorInvalidValue;
+    for (int z = 0; z < grp.n; ++z) if (grp.out_count[z] > job.out_count) return hipErrorInvalidValue;   // (beyond the layout's blocks)
     ScanCfg scan = scan_in;
     scan.only_pairs = nullptr;
     fill_edges(job, npairs, scan);

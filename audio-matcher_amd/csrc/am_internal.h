@@ -418,6 +418,6 @@ int match_many(am_needle* h, const void* const* d_hays, const size_t* lens, size
                const PartSpec* part = nullptr);
 int match_multi_many(am_needle* const* needles, size_t nn, const void* const* d_hays, const size_t* lens, size_t n_hay,
                      int src_kind, const am_match_params* p, am_peak* out, size_t cap_per_pair, size_t* n_out,
-                     size_t index_base = 0, size_t index_stride = 1);
+                     size_t index_base = 0, size_t index_stride = 1, const uint64_t* overlaps = nullptr, bool varlen = false);
 
 }  // namespace am

@@ -125,6 +125,14 @@ struct K3Group {
     float* tile_theta[kMaxNeedleGroup];
     float hist_min[kMaxNeedleGroup];
     float out_scale[kMaxNeedleGroup];
+    // Needles of different lengths on one block layout (am_match_multi_varlen*): member z's scores end at out_count[z]
+    // (scores at or beyond it are neither stored nor summarised, balloted or thresholded), its chunk edges are
+    // i * seg_c and i * seg_c + seg_d[z].  The launch's own job.out_count / scan.seg_c / seg_d are those of the layout
+    // (scan.seg_c = 0 when the members' edges differ: every member then works out its own edges).
+    long long out_count[kMaxNeedleGroup];
+    long long seg_d[kMaxNeedleGroup];
+    long long seg_c;
+    double inv_c;
 };
 bool plan_k3_has_group(const PlanDev& pl);
 // The odd last blocks of several haystacks of a batch (am_api.hip, TailPlan) as ONE launch each of K1 / K2 / K3 on the

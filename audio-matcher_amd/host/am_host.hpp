@@ -59,7 +59,8 @@ inline std::optional<std::uint64_t> parse_duration_ms(const std::string& arg) {
 // ---- src/matcher/args.rs:9-77 --------------------------------------------------
 struct Arguments {
     std::vector<std::string> within;          // positional FILEs
-    std::string snippet;                      // --snippet FILE
+    std::string snippet;                      // --snippet FILE (the first one given)
+    std::vector<std::string> snippets;        // extension: every --snippet FILE, in order (several: one am_match_multi_varlen per file)
     float prominence = 13.0f;                 // -p/--prominence, default 13 (:19)
     std::optional<std::uint64_t> distance_ms; // --distance (default 8 min, :73-76)
     std::optional<std::uint64_t> chunk_ms;    // --chunk-size (default 60 s, :70-72)
@@ -84,7 +85,12 @@ struct Arguments {
 struct ArgError : std::runtime_error { using std::runtime_error::runtime_error; };
 
 inline const char* usage_text() {
-    return "usage: audiomatch <FILE>... --snippet <FILE> [options]\n"
+    return "usage: audiomatch <FILE>... --snippet <FILE> [--snippet <FILE>]... [options]\n"
+           "  --snippet FILE         the snippet to find; give it several times to find several snippets (of any\n"
+           "                         lengths) in one pass per file: each uses an overlap of its own length, the offset\n"
+           "                         lines are prefixed by the snippet's file name, the label file is made from the hits\n"
+           "                         of all snippets sorted by start (equal starts in --snippet order); --resample and\n"
+           "                         --min-confidence apply to each snippet, --normalize matches them one by one\n"
            "  -p, --prominence P     minimal prominence of a hit, in percent (default 13)\n"
            "  --distance D           minimal distance between hits (default 8m)\n"
            "  --chunk-size D         length of one chunk (default 60s)\n"
@@ -121,7 +127,10 @@ inline Arguments parse_arguments(int argc, const char* const* argv) {
     };
     for (int i = 1; i < argc; ++i) {
         const std::string s = argv[i];
-        if (s == "--snippet") a.snippet = need(i);
+        if (s == "--snippet") {
+            a.snippets.push_back(need(i));
+            if (a.snippets.size() == 1) a.snippet = a.snippets[0];
+        }
         else if (s == "-p" || s == "--prominence") a.prominence = std::strtof(need(i).c_str(), nullptr);
         else if (s == "--distance") a.distance_ms = dur(need(i), "--distance");
         else if (s == "--chunk-size") a.chunk_ms = dur(need(i), "--chunk-size");

@@ -1,7 +1,8 @@
-// audiomatch_cli.cpp -- `audio-matcher <haystack...> --snippet <needle>` on the GPU library:
+// audiomatch_cli.cpp -- `audio-matcher <haystack...> --snippet <needle>...` on the GPU library:
 // the per-file loop of matcher::run (src/matcher/mod.rs:17-104) with the argument surface of
 // src/matcher/args.rs:9-77.  Input files are WAV (PCM16 stereo/mono or float32 mono): MP3
 // decoding (minimp3) is outside the accelerated path.
+#include <algorithm>
 #include <cstdio>
 #include <iostream>
 #include <map>
@@ -32,6 +33,165 @@ static void progress(void*, size_t k, int stage, size_t n_chunks) {          // 
     std::fprintf(stderr, "Progress: file %zu %s (%zu chunks)\n", k, stage == 0 ? "started" : "finished", n_chunks);
 }
 
+static std::string base_name(const std::string& path) {
+    const auto slash = path.find_last_of('/');
+    return slash == std::string::npos ? path : path.substr(slash + 1);
+}
+
+// extension: several --snippet files.  Each main file is matched by ONE am_match_multi_varlen call (the snippets may
+// differ in length: each uses an overlap of its own length at the main file's rate, as make_params does for one);
+// with --normalize, which that call refuses, snippet by snippet with am_match.  The label file is timelabel_from_peaks
+// over the hits of all snippets, sorted by start (equal starts in --snippet order).
+static int run_multi(const Arguments& args) {
+    struct Snip {
+        std::string name;
+        std::uint32_t sr = 0;
+        double duration = 0.0;
+        std::vector<float> data;
+        am_needle* h = nullptr;
+        std::map<std::uint32_t, am_needle*> resampled;
+    };
+    std::vector<Snip> snips(args.snippets.size());
+    auto release = [&]() {
+        for (Snip& sn : snips) {
+            if (sn.h) am_needle_destroy(sn.h);
+            for (auto& kv : sn.resampled) am_needle_destroy(kv.second);
+        }
+    };
+    try {
+        if (args.normalize_floor_db && am_set_option("score_norm_floor_db", *args.normalize_floor_db) != AM_OK)
+            throw std::runtime_error(std::string("--normalize-floor: ") + am_last_error_string());
+        for (size_t j = 0; j < snips.size(); ++j) {
+            Snip& sn = snips[j];
+            const Pcm pcm = read_wav(args.snippets[j]);
+            sn.name = base_name(args.snippets[j]);
+            sn.sr = pcm.sample_rate;
+            sn.duration = (double)pcm.frames() / (double)sn.sr;
+            sn.data = to_mono_f32(pcm, args.device);
+            if (am_needle_create(args.device, sn.data.data(), sn.data.size(), &sn.h) != AM_OK)
+                throw std::runtime_error(std::string("am_needle_create: ") + am_last_error_string());
+            if (args.normalize && am_needle_set_option(sn.h, "score_norm", 1) != AM_OK)
+                throw std::runtime_error(std::string("--normalize: ") + am_last_error_string());
+        }
+        if (args.verbosity >= 2) am_set_progress_callback(progress, nullptr);
+        int rc_all = 0;
+        for (const std::string& main_file : args.within) {
+            std::optional<std::string> out_path = args.out_file;
+            if (!out_path && !args.no_out) out_path = auto_out_file(main_file);
+            if (out_path && file_exists(*out_path)) {
+                if (args.skip_existing ||
+                    ask_consent(args, "Ausgabe Datei \"" + *out_path + "\" existiert bereits, möchtest du skippen"))
+                    continue;
+                if (!ask_consent(args, "soll die existierende Datei überschrieben werden")) out_path.reset();
+            }
+            if (args.verbosity >= (args.within.size() == 1 ? 3 : 1))
+                std::printf("preparing data of '%s'\n", main_file.c_str());
+            const Pcm m = read_wav(main_file);
+            const std::uint32_t m_sr = m.sample_rate;
+            const size_t k = snips.size();
+            std::vector<const am_needle*> handles(k);
+            std::vector<std::uint64_t> overlaps(k);
+            for (size_t j = 0; j < k; ++j) {
+                Snip& sn = snips[j];
+                if (m_sr != sn.sr && !args.resample) {
+                    std::fprintf(stderr, "sample rate of snippet (%u) and main file (%u) don't match\n", sn.sr, m_sr);
+                    release();
+                    return 3;
+                }
+                am_needle* algo = sn.h;
+                overlaps[j] = make_params(args, m_sr, sn.duration).overlap;
+                if (m_sr != sn.sr) {
+                    am_needle*& h = sn.resampled[m_sr];
+                    if (!h) {
+                        if (am_needle_create_resampled(args.device, sn.data.data(), sn.data.size(), AM_FMT_F32_MONO, sn.sr, m_sr, &h) != AM_OK)
+                            throw std::runtime_error(std::string("am_needle_create_resampled: ") + am_last_error_string());
+                        if (args.normalize && am_needle_set_option(h, "score_norm", 1) != AM_OK)
+                            throw std::runtime_error(std::string("--normalize: ") + am_last_error_string());
+                    }
+                    algo = h;
+                    size_t s_len = 0;   // the overlap = the resampled snippet's length
+                    am_needle_len(algo, &s_len);
+                    overlaps[j] = s_len;
+                }
+                handles[j] = algo;
+            }
+            const std::vector<float> m_samples = to_mono_f32(m, args.device);
+            const am_match_params p = make_params(args, m_sr, snips[0].duration);
+            size_t cap = 1024;
+            std::vector<am_peak> peaks(cap * k);
+            std::vector<size_t> n(k, 0);
+            if (!args.normalize) {
+                int rc = am_match_multi_varlen(handles.data(), k, overlaps.data(), m_samples.data(), m_samples.size(), AM_FMT_F32_MONO, &p,
+                                               peaks.data(), cap, n.data());
+                if (rc == AM_ERR_CAPACITY) {
+                    for (size_t j = 0; j < k; ++j) cap = std::max(cap, n[j]);
+                    peaks.assign(cap * k, am_peak{});
+                    rc = am_match_multi_varlen(handles.data(), k, overlaps.data(), m_samples.data(), m_samples.size(), AM_FMT_F32_MONO, &p,
+                                               peaks.data(), cap, n.data());
+                }
+                if (rc != AM_OK) throw std::runtime_error(std::string("am_match_multi_varlen: ") + am_last_error_string());
+            } else {
+                std::vector<std::vector<am_peak>> each(k);
+                for (size_t j = 0; j < k; ++j) {
+                    am_match_params pj = p;
+                    pj.overlap = overlaps[j];
+                    each[j].resize(1024);
+                    int rc = am_match(handles[j], m_samples.data(), m_samples.size(), &pj, each[j].data(), each[j].size(), &n[j]);
+                    if (rc == AM_ERR_CAPACITY) {
+                        each[j].resize(n[j]);
+                        rc = am_match(handles[j], m_samples.data(), m_samples.size(), &pj, each[j].data(), each[j].size(), &n[j]);
+                    }
+                    if (rc != AM_OK) throw std::runtime_error(std::string("am_match: ") + am_last_error_string());
+                    cap = std::max(cap, n[j]);
+                }
+                peaks.assign(cap * k, am_peak{});
+                for (size_t j = 0; j < k; ++j) std::copy(each[j].begin(), each[j].begin() + (std::ptrdiff_t)n[j], peaks.begin() + (std::ptrdiff_t)(j * cap));
+            }
+            for (size_t j = 0; j < k; ++j) {
+                am_peak* pk = peaks.data() + j * cap;
+                if (args.min_confidence && n[j] > 0) {   // each snippet's hits scored with that snippet's handle
+                    std::vector<am_hit_score> sc(n[j]);
+                    if (am_hit_scores(handles[j], m_samples.data(), m_samples.size(), AM_FMT_F32_MONO, pk, n[j], sc.data()) != AM_OK)
+                        throw std::runtime_error(std::string("am_hit_scores: ") + am_last_error_string());
+                    size_t kept = 0;
+                    for (size_t i = 0; i < n[j]; ++i) {
+                        if (args.verbosity >= 2)
+                            std::printf("%s: hit %zu: position %.3f ncc %.6f gain %.6g window %.2f dB%s\n", snips[j].name.c_str(), i + 1,
+                                        sc[i].position, (double)sc[i].ncc, (double)sc[i].gain, (double)sc[i].window_db,
+                                        sc[i].ncc >= *args.min_confidence ? "" : " (dropped)");
+                        if (sc[i].ncc >= *args.min_confidence) pk[kept++] = pk[i];
+                    }
+                    n[j] = kept;
+                }
+                if (args.verbosity >= 1)
+                    for (const auto& line : offset_lines(pk, n[j], m_sr)) std::printf("%s: %s\n", snips[j].name.c_str(), line.c_str());
+            }
+            if (out_path) {
+                std::vector<std::pair<std::uint64_t, size_t>> order;   // (start, slot): sorted by start, then snippet, then position
+                for (size_t j = 0; j < k; ++j)
+                    for (size_t i = 0; i < n[j]; ++i) order.emplace_back(peaks[j * cap + i].start, j * cap + i);
+                std::stable_sort(order.begin(), order.end(), [](const auto& a, const auto& b) { return a.first < b.first; });
+                std::vector<am_peak> merged;
+                for (const auto& o : order) merged.push_back(peaks[o.second]);
+                const std::string text = format_labels(timelabel_from_peaks(merged.data(), merged.size(), m_sr, 7.0, "Segment #"));
+                if (args.dry_run) {
+                    std::printf("would write to '%s':\n%s", out_path->c_str(), text.c_str());
+                } else {
+                    std::ofstream f(*out_path, std::ios::binary | std::ios::trunc);
+                    if (!f) { std::fprintf(stderr, "couldn't find file '%s'\n", out_path->c_str()); rc_all = 4; continue; }
+                    f << text;
+                }
+            }
+        }
+        release();
+        return rc_all;
+    } catch (const std::exception& e) {
+        release();
+        std::fprintf(stderr, "error: %s\n", e.what());
+        return 1;
+    }
+}
+
 int main(int argc, char** argv) {
     Arguments args;
     try {
@@ -44,6 +204,7 @@ int main(int argc, char** argv) {
         std::printf("%s", usage_text());
         return 0;
     }
+    if (args.snippets.size() > 1) return run_multi(args);
     try {
         const Pcm snippet = read_wav(args.snippet);                           // mod.rs:29
         const std::uint32_t sr = snippet.sample_rate;

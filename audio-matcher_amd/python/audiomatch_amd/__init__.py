@@ -152,6 +152,12 @@ _SIGNATURES = {
     "am_pool_match_batch_pcm16_device": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.c_size_t,
                                                    C.POINTER(AmMatchParams), C.POINTER(AmPeak), C.c_size_t,
                                                    C.POINTER(C.c_size_t)]),
+    "am_match_multi_varlen_batch_device": (C.c_int, [C.POINTER(C.c_void_p), C.c_size_t, C.POINTER(C.c_uint64), C.POINTER(C.c_void_p),
+                                                     C.POINTER(C.c_size_t), C.c_size_t, C.c_int, C.POINTER(AmMatchParams),
+                                                     C.POINTER(AmPeak), C.c_size_t, C.POINTER(C.c_size_t)]),
+    "am_match_multi_varlen": (C.c_int, [C.POINTER(C.c_void_p), C.c_size_t, C.POINTER(C.c_uint64), C.c_void_p, C.c_size_t,
+                                        C.c_int, C.POINTER(AmMatchParams), C.POINTER(AmPeak), C.c_size_t,
+                                        C.POINTER(C.c_size_t)]),
     "am_pool_create_multi": (C.c_int, [C.POINTER(C.c_void_p), C.c_size_t, C.c_size_t, C.POINTER(C.c_int), C.c_size_t,
                                        C.POINTER(C.c_void_p)]),
     "am_pool_needle_count": (C.c_int, [C.c_void_p, C.POINTER(C.c_size_t)]),
@@ -814,6 +820,48 @@ def match_multi_batch_device(algos, ptrs, lengths, params: AmMatchParams, fmt: i
     counts = (C.c_size_t * max(1, k * nn))()
     _check(lib().am_match_multi_batch_device(handles, nn, arr_p, arr_l, k, int(fmt), C.byref(params), buf, cap_per_pair, counts))
     return _split_pairs(buf, counts, k, nn, cap_per_pair)
+
+
+def _overlaps(overlaps, nn: int):
+    if overlaps is None:
+        return None
+    if len(overlaps) != nn:
+        raise ValueError(f"{len(overlaps)} overlaps for {nn} needles")
+    return (C.c_uint64 * max(1, nn))(*[int(v) for v in overlaps])
+
+
+def match_multi_varlen_batch_device(algos, ptrs, lengths, params: AmMatchParams, fmt: int = Fmt.F32_MONO, cap_per_pair: int = 64,
+                                    overlaps=None):
+    """Several needles of any lengths against a batch of resident haystacks (am_match_multi_varlen_batch_device):
+    result [k][j] = haystack k against needle j, as am_match_device with overlap overlaps[j] (None: params.overlap)."""
+    nn, k = len(algos), len(ptrs)
+    handles = (C.c_void_p * max(1, nn))(*[a._h for a in algos])
+    arr_p = (C.c_void_p * max(1, k))(*ptrs)
+    arr_l = (C.c_size_t * max(1, k))(*lengths)
+    buf = (AmPeak * max(1, cap_per_pair * k * nn))()
+    counts = (C.c_size_t * max(1, k * nn))()
+    _check(lib().am_match_multi_varlen_batch_device(handles, nn, _overlaps(overlaps, nn), arr_p, arr_l, k, int(fmt), C.byref(params),
+                                                    buf, cap_per_pair, counts))
+    return _split_pairs(buf, counts, k, nn, cap_per_pair)
+
+
+def match_multi_varlen(algos, haystack, params: AmMatchParams, overlaps=None, cap_per_needle: int = 256):
+    """Several needles of any lengths against ONE haystack in host memory (am_match_multi_varlen): a numpy f32 mono
+    array, or an interleaved i16 stereo array (int16 dtype, frames x 2 or flat).  Result [j] = the hits of needle j."""
+    h = np.asarray(haystack)
+    if h.dtype == np.int16:
+        h = np.ascontiguousarray(h, dtype=np.int16).reshape(-1)
+        fmt, length = Fmt.S16_STEREO, h.size // 2
+    else:
+        h = np.ascontiguousarray(h, dtype=np.float32)
+        fmt, length = Fmt.F32_MONO, h.size
+    nn = len(algos)
+    handles = (C.c_void_p * max(1, nn))(*[a._h for a in algos])
+    buf = (AmPeak * max(1, cap_per_needle * nn))()
+    counts = (C.c_size_t * max(1, nn))()
+    _check(lib().am_match_multi_varlen(handles, nn, _overlaps(overlaps, nn), h.ctypes.data, length, int(fmt), C.byref(params),
+                                       buf, cap_per_needle, counts))
+    return [_peaks_at(buf, j * cap_per_needle, counts[j]) for j in range(nn)]
 
 
 def hit_scores_batch_device(algos, ptrs, lengths, peaks_per_pair, fmt: int = Fmt.F32_MONO):

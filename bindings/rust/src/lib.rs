@@ -48,6 +48,7 @@ pub const AM_HIT_BELOW_FLOOR: u32 = 2;
 pub const AM_HIT_NONFINITE: u32 = 4;
 
 pub const AM_OK: c_int = 0;
+pub const AM_ERR_INVALID_ARG: c_int = 1;
 pub const AM_ERR_CAPACITY: c_int = 2;
 
 extern "C" {
@@ -112,6 +113,16 @@ extern "C" {
         needles: *const *const AmNeedle, n_needles: usize, d_haystacks: *const *const std::ffi::c_void,
         lens: *const usize, n_hay: usize, sample_format: c_int, p: *const AmMatchParams,
         out: *mut AmPeak, cap_per_pair: usize, n_out: *mut usize,
+    ) -> c_int;
+    /// several snippets of ANY lengths: one block layout per haystack from the longest, overlaps[j] per needle (null: p.overlap)
+    pub fn am_match_multi_varlen_batch_device(
+        needles: *const *const AmNeedle, n_needles: usize, overlaps: *const u64, d_haystacks: *const *const std::ffi::c_void,
+        lens: *const usize, n_hay: usize, sample_format: c_int, p: *const AmMatchParams,
+        out: *mut AmPeak, cap_per_pair: usize, n_out: *mut usize,
+    ) -> c_int;
+    pub fn am_match_multi_varlen(
+        needles: *const *const AmNeedle, n_needles: usize, overlaps: *const u64, haystack: *const std::ffi::c_void, len: usize,
+        sample_format: c_int, p: *const AmMatchParams, out: *mut AmPeak, cap_per_needle: usize, n_out: *mut usize,
     ) -> c_int;
     pub fn am_pool_create_multi(
         needles: *const *const f32, n_needles: usize, n: usize, devices: *const c_int, n_dev: usize, out: *mut *mut AmPool,
@@ -322,6 +333,37 @@ impl HipConvolve {
         buf.truncate(n);
         Ok(buf)
     }
+}
+
+/// `calc_chunks` for SEVERAL snippets of any lengths against one haystack in one pass (am_match_multi_varlen): result
+/// [j] is what `needles[j].calc_chunks` returns with overlap `overlaps[j]` (None: `p.overlap` for every snippet).
+pub fn calc_chunks_multi(needles: &[&HipConvolve], p: &AmMatchParams, overlaps: Option<&[u64]>, m_samples: &[f32])
+                         -> Result<Vec<Vec<AmPeak>>, Box<dyn std::error::Error>> {
+    let k = needles.len();
+    if let Some(o) = overlaps {
+        if o.len() != k {
+            return Err(am_err(AM_ERR_INVALID_ARG));
+        }
+    }
+    let hs: Vec<*const AmNeedle> = needles.iter().map(|n| n.h as *const AmNeedle).collect();
+    let ov = overlaps.map_or(std::ptr::null(), |o| o.as_ptr());
+    let mut cap = 256usize;
+    let mut buf = vec![AmPeak::default(); k * cap];
+    let mut n = vec![0usize; k];
+    let run = |buf: &mut Vec<AmPeak>, n: &mut Vec<usize>, cap: usize| unsafe {
+        am_match_multi_varlen(hs.as_ptr(), k, ov, m_samples.as_ptr() as *const std::ffi::c_void, m_samples.len(), AM_FMT_F32_MONO, p,
+                              buf.as_mut_ptr(), cap, n.as_mut_ptr())
+    };
+    let mut rc = run(&mut buf, &mut n, cap);
+    if rc == AM_ERR_CAPACITY {
+        cap = n.iter().copied().max().unwrap_or(cap).max(cap);
+        buf = vec![AmPeak::default(); k * cap];
+        rc = run(&mut buf, &mut n, cap);
+    }
+    if rc != AM_OK {
+        return Err(am_err(rc));
+    }
+    Ok((0..k).map(|j| buf[j * cap..j * cap + n[j]].to_vec()).collect())
 }
 
 impl Drop for HipConvolve {

@@ -172,6 +172,27 @@ int am_match_multi_batch_device(const am_needle* const* needles, size_t n_needle
                                 const size_t* lens, size_t n_hay, int sample_format, const am_match_params* p,
                                 am_peak* out, size_t cap_per_pair, size_t* n_out);
 
+/* Several needles of ANY lengths (same device) against a batch of resident haystacks: a radio archive's intro, outro,
+ * stingers and station IDs in one call.  overlaps[j] is the overlap (in samples) of needle j's windows,
+ * chunk + overlaps[j]; overlaps == NULL means p->overlap for every needle.  Pair (haystack k, needle j) returns what
+ * am_match_device(needles[j], haystack k, p') (am_match_pcm16_device for AM_FMT_S16_STEREO) returns, p' = p with
+ * overlap = overlaps[j]: offsets identical, heights and prominences to f32 rounding; non-finite samples cost exactly
+ * the windows of that needle that hold them; a haystack shorter than needle j gives that pair 0 hits.  Layout of out
+ * and n_out, tail_window, the peak rules, scaling (AM_SCALE_NONE / AM_SCALE_LIB) and half_pipeline as in
+ * am_match_multi_batch_device; options come from needles[0].  Every haystack has one block layout, that of the
+ * longest needle: its forward column pass runs once, its forward row transforms once per group of needles (grouped
+ * longest first), each needle's scores end at its own last offset.  Needles of one length with every overlap equal
+ * to p->overlap: am_match_multi_batch_device's results bit for bit. */
+int am_match_multi_varlen_batch_device(const am_needle* const* needles, size_t n_needles, const uint64_t* overlaps,
+                                       const void* const* d_haystacks, const size_t* lens, size_t n_hay,
+                                       int sample_format, const am_match_params* p,
+                                       am_peak* out, size_t cap_per_pair, size_t* n_out);
+/* the same for ONE haystack in host memory (AM_FMT_F32_MONO or AM_FMT_S16_STEREO; len in samples / frames):
+ * out holds cap_per_needle slots per needle, n_out[j] the count for needle j */
+int am_match_multi_varlen(const am_needle* const* needles, size_t n_needles, const uint64_t* overlaps,
+                          const void* haystack, size_t len, int sample_format, const am_match_params* p,
+                          am_peak* out, size_t cap_per_needle, size_t* n_out);
+
 /* The same matcher on interleaved 16-bit stereo PCM, the sample format the
  * reference decodes to (mp3_reader.rs:26 asserts two channels): the down-mix
  * mono = (l as f32 + r as f32) * 0.5 * (1/65535) (mp3_reader.rs:12, 28-37) is
@@ -518,8 +539,8 @@ int am_debug_column_bench(int device, int wide, int npairs, int iters, int dense
  *     Also per needle handle (am_needle_set_option); pools use the process default (their needles are internal).
  *     Supported by am_correlate*, am_match, am_match_device, am_match_batch_device, am_match_pcm16*,
  *     am_pool_match_batch and am_pool_match_batch_pcm16 (and their _device forms).  NOT supported -- AM_ERR_INVALID_ARG,
- *     "score_norm: not supported by this entry point" -- by am_match_multi*, am_pool_match_multi*, am_match_stream_*,
- *     am_match_part_device and am_pool_match_long*.  am_find_peaks is unaffected.
+ *     "score_norm: not supported by this entry point" -- by am_match_multi*, am_match_multi_varlen_batch_device,
+ *     am_match_multi_varlen, am_pool_match_multi*, am_match_stream_*, am_match_part_device and am_pool_match_long*.  am_find_peaks is unaffected.
  *     Non-finite samples cost exactly the windows that hold them (they count as 0 in every other window's energy); a
  *     haystack's result is the same bit pattern alone, in a batch and on any pool; chunking, "tail_window", the peak
  *     rules and the overshadow filter apply to the NCC scores unchanged; "half_pipeline" keeps its offsets and

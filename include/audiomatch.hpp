@@ -168,6 +168,68 @@ inline std::vector<Peak> calc_chunks(std::uint16_t sr, const float* m_samples, s
     return out;
 }
 
+// calc_chunks for SEVERAL snippets of any lengths against one haystack (am_match_multi_varlen): result [j] = what
+// calc_chunks with needles[j] and overlap overlaps[j] returns (overlaps empty: the config's overlap for every needle);
+// the haystack is host memory of `sample_format` (AM_FMT_*), len in samples / frames.
+inline std::vector<std::vector<Peak>> calc_chunks_multi(std::uint16_t sr, const void* m_samples, std::size_t len, int sample_format,
+                                                        const std::vector<const HipConvolve*>& needles, bool scale, const Config& config,
+                                                        const std::vector<std::uint64_t>& overlaps = {}, std::size_t cap_per_needle = 256) {
+    const am_match_params p = config.params(sr, scale);
+    const std::size_t k = needles.size();
+    std::vector<const am_needle*> hs;
+    for (const HipConvolve* h : needles) hs.push_back(h->handle());
+    if (!overlaps.empty() && overlaps.size() != k) check(AM_ERR_INVALID_ARG);
+    const std::uint64_t* ov = overlaps.empty() ? nullptr : overlaps.data();
+    std::vector<am_peak> buf(k * cap_per_needle);
+    std::vector<std::size_t> n(k, 0);
+    int rc = am_match_multi_varlen(hs.data(), k, ov, m_samples, len, sample_format, &p, buf.data(), cap_per_needle, n.data());
+    if (rc == AM_ERR_CAPACITY) {
+        for (std::size_t v : n) cap_per_needle = std::max(cap_per_needle, v);
+        buf.assign(k * cap_per_needle, am_peak{});
+        rc = am_match_multi_varlen(hs.data(), k, ov, m_samples, len, sample_format, &p, buf.data(), cap_per_needle, n.data());
+    }
+    check(rc);
+    std::vector<std::vector<Peak>> out(k);
+    for (std::size_t j = 0; j < k; ++j)
+        for (std::size_t q = 0; q < n[j]; ++q) {
+            const am_peak& v = buf[j * cap_per_needle + q];
+            out[j].push_back(Peak{static_cast<std::size_t>(v.start), static_cast<std::size_t>(v.end), v.height, v.prominence});
+        }
+    return out;
+}
+// ... and against a batch of resident haystacks (am_match_multi_varlen_batch_device): result [k][j]
+inline std::vector<std::vector<std::vector<Peak>>> calc_chunks_multi_device(std::uint16_t sr, const std::vector<const void*>& d_haystacks,
+                                                                           const std::vector<std::size_t>& lens, int sample_format,
+                                                                           const std::vector<const HipConvolve*>& needles, bool scale,
+                                                                           const Config& config, const std::vector<std::uint64_t>& overlaps = {},
+                                                                           std::size_t cap_per_pair = 64) {
+    const am_match_params p = config.params(sr, scale);
+    const std::size_t k = d_haystacks.size(), nn = needles.size();
+    std::vector<const am_needle*> hs;
+    for (const HipConvolve* h : needles) hs.push_back(h->handle());
+    if (!overlaps.empty() && overlaps.size() != nn) check(AM_ERR_INVALID_ARG);
+    const std::uint64_t* ov = overlaps.empty() ? nullptr : overlaps.data();
+    std::vector<am_peak> buf(k * nn * cap_per_pair);
+    std::vector<std::size_t> n(k * nn, 0);
+    int rc = am_match_multi_varlen_batch_device(hs.data(), nn, ov, d_haystacks.data(), lens.data(), k, sample_format, &p, buf.data(),
+                                                cap_per_pair, n.data());
+    if (rc == AM_ERR_CAPACITY) {
+        for (std::size_t v : n) cap_per_pair = std::max(cap_per_pair, v);
+        buf.assign(k * nn * cap_per_pair, am_peak{});
+        rc = am_match_multi_varlen_batch_device(hs.data(), nn, ov, d_haystacks.data(), lens.data(), k, sample_format, &p, buf.data(),
+                                                cap_per_pair, n.data());
+    }
+    check(rc);
+    std::vector<std::vector<std::vector<Peak>>> out(k, std::vector<std::vector<Peak>>(nn));
+    for (std::size_t i = 0; i < k; ++i)
+        for (std::size_t j = 0; j < nn; ++j)
+            for (std::size_t q = 0; q < n[i * nn + j]; ++q) {
+                const am_peak& v = buf[(i * nn + j) * cap_per_pair + q];
+                out[i][j].push_back(Peak{static_cast<std::size_t>(v.start), static_cast<std::size_t>(v.end), v.height, v.prominence});
+            }
+    return out;
+}
+
 // The per-file loop of matcher::run (matcher/mod.rs:42-87) over every GPU of the node: the
 // needle replicated per device, haystack k matched on device k mod n (am_pool_*), one submit
 // thread per device inside the library, results gathered on the host.
