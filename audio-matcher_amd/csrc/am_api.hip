@@ -12,6 +12,8 @@
 // am_peaks.hip; there is no CPU fallback.
 #include "am_internal.h"
 
+#include <climits>
+
 using namespace am;
 
 
@@ -23,8 +25,8 @@ static size_t mode_len(size_t w, size_t s, int mode) {                // audio_m
 
 
 // find_peaks on one host score array (am_find_peaks)
-static int find_peaks_host_array(Ctx* c, const float* d_scores, long long n, float min_prom, long long min_dist,
-                                 std::vector<am_peak>& all) {
+int am::find_peaks_host_array(Ctx* c, const float* d_scores, long long n, float min_prom, long long min_dist,
+                              std::vector<am_peak>& all) {
     int rc;
     const PeakPolicy pol = snapshot_opts(nullptr).peak_policy();
     Segment sg; sg.a = 0; sg.b = n;
@@ -430,6 +432,102 @@ int am_find_peaks(int device, const float* scores, size_t n, float min_prominenc
     for (size_t i = 0; i < all.size() && i < cap; ++i) out[i] = all[i];
     if (all.size() > cap) return fail(AM_ERR_CAPACITY, "peak output buffer too small");
     return AM_OK;
+}
+
+// ---- the k best matches (am_best.hip) ----
+static int best_check(const am_needle* h, int sample_format, const am_best_params* bp) {
+    int rc = check_needle(h);
+    if (rc) return rc;
+    if (!bp) return fail(AM_ERR_INVALID_ARG, "null pointer");
+    if (sample_format != AM_FMT_F32_MONO && sample_format != AM_FMT_S16_STEREO) return fail(AM_ERR_INVALID_ARG, "bad sample format");
+    if (bp->k == 0) return fail(AM_ERR_INVALID_ARG, "k must be at least 1");
+    if (bp->scale != AM_SCALE_NONE && bp->scale != AM_SCALE_LIB)
+        return fail(AM_ERR_INVALID_ARG, "am_match_best: scale must be AM_SCALE_NONE or AM_SCALE_LIB (AM_SCALE_MY depends on a chunk)");
+    return norm_check(norm_spec(h, snapshot_opts(h)), bp->scale);
+}
+
+int am_match_best_device(const am_needle* hc, const void* d_haystack, size_t len, int sample_format,
+                         const am_best_params* bp, am_peak* out, size_t* n_out) {
+    am_needle* h = const_cast<am_needle*>(hc);
+    int rc = best_check(h, sample_format, bp);
+    if (rc) return rc;
+    if (!d_haystack || !out || !n_out) return fail(AM_ERR_INVALID_ARG, "null pointer");
+    std::lock_guard<std::recursive_mutex> lk(h->ctx->mu);
+    return match_best_one(h, d_haystack, len, sample_format, bp, out, n_out);
+}
+
+int am_match_best(const am_needle* hc, const void* haystack, size_t len, int sample_format,
+                  const am_best_params* bp, am_peak* out, size_t* n_out) {
+    am_needle* h = const_cast<am_needle*>(hc);
+    int rc = best_check(h, sample_format, bp);
+    if (rc) return rc;
+    if (!haystack || !out || !n_out) return fail(AM_ERR_INVALID_ARG, "null pointer");
+    *n_out = 0;
+    if (len < h->n) return AM_OK;
+    Ctx* c = h->ctx;
+    std::lock_guard<std::recursive_mutex> lk(c->mu);
+    const size_t bytes = len * (sample_format == AM_FMT_S16_STEREO ? 2 * sizeof(int16_t) : sizeof(float));
+    if ((rc = c->io_in.ensure(bytes))) return rc;
+    AM_HIP(copy_on_stream(c, c->io_in.p, haystack, bytes, hipMemcpyHostToDevice));
+    return match_best_one(h, c->io_in.p, len, sample_format, bp, out, n_out);
+}
+
+int am_match_best_batch_device(const am_needle* hc, const void* const* d_haystacks, const size_t* lens,
+                               size_t n_hay, int sample_format, const am_best_params* bp,
+                               am_peak* out, size_t* n_out) {
+    am_needle* h = const_cast<am_needle*>(hc);
+    int rc = best_check(h, sample_format, bp);
+    if (rc) return rc;
+    if (n_hay == 0) return AM_OK;
+    if (!d_haystacks || !lens || !out || !n_out) return fail(AM_ERR_INVALID_ARG, "null pointer");
+    for (size_t i = 0; i < n_hay; ++i)
+        if (!d_haystacks[i]) return fail(AM_ERR_INVALID_ARG, "haystack " + std::to_string(i) + ": null pointer");
+    Ctx* c = h->ctx;
+    std::lock_guard<std::recursive_mutex> lk(c->mu);
+    // the score array and the down-mix sized once, for the longest haystack
+    size_t longest = 0;
+    for (size_t i = 0; i < n_hay; ++i) longest = std::max(longest, lens[i]);
+    if (longest >= h->n) {
+        if ((rc = c->best_scores.ensure(sizeof(float) * (longest - h->n + 1)))) return rc;
+        if (sample_format == AM_FMT_S16_STEREO && (rc = c->best_mono.ensure(sizeof(float) * longest))) return rc;
+    }
+    for (size_t i = 0; i < n_hay; ++i)
+        if ((rc = match_best_one(h, d_haystacks[i], lens[i], sample_format, bp, out + i * bp->k, n_out + i))) return rc;
+    return AM_OK;
+}
+
+static int find_peaks_top_impl(int device, const float* scores, size_t n, float min_prominence, uint64_t min_distance,
+                               size_t k, am_peak* out, size_t* n_out, bool device_io) {
+    if (!scores || !out || !n_out) return fail(AM_ERR_INVALID_ARG, "null pointer");
+    if (k == 0) return fail(AM_ERR_INVALID_ARG, "k must be at least 1");
+    Ctx* c = nullptr;
+    int rc = get_ctx(device, &c);
+    if (rc) return rc;
+    *n_out = 0;
+    if (n == 0) return AM_OK;
+    std::lock_guard<std::recursive_mutex> lk(c->mu);
+    const float* d_scores = scores;
+    if (!device_io) {
+        if ((rc = c->io_in.ensure(n * sizeof(float)))) return rc;
+        AM_HIP(copy_on_stream(c, c->io_in.p, scores, n * sizeof(float), hipMemcpyHostToDevice));
+        d_scores = (const float*)c->io_in.p;
+    }
+    std::vector<am_peak> res;
+    if ((rc = best_select(c, d_scores, (long long)n, min_prominence, (long long)std::min<uint64_t>(min_distance, (uint64_t)LLONG_MAX),
+                          k, snapshot_opts(nullptr).peak_policy(), res))) return rc;
+    for (size_t i = 0; i < res.size(); ++i) out[i] = res[i];
+    *n_out = res.size();
+    return AM_OK;
+}
+
+int am_find_peaks_top(int device, const float* scores, size_t n, float min_prominence,
+                      uint64_t min_distance, size_t k, am_peak* out, size_t* n_out) {
+    return find_peaks_top_impl(device, scores, n, min_prominence, min_distance, k, out, n_out, false);
+}
+
+int am_find_peaks_top_device(int device, const float* d_scores, size_t n, float min_prominence,
+                             uint64_t min_distance, size_t k, am_peak* out, size_t* n_out) {
+    return find_peaks_top_impl(device, d_scores, n, min_prominence, min_distance, k, out, n_out, true);
 }
 
 int am_pcm_s16_stereo_to_mono_device(int device, const int16_t* d_in, size_t frames, float* d_out) {

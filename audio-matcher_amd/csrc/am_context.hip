@@ -509,6 +509,7 @@ int am_shutdown(void) {
         c->ranges.release(); c->range_flags.release(); c->big.release(); c->norm_blk.release();
         for (DevBuf* b : {&c->hit_tab, &c->hit_parts, &c->hit_flags, &c->hit_out, &c->hit_stage}) b->release();
         c->hit_io.release();
+        for (DevBuf* b : {&c->best_stats, &c->best_lmax, &c->best_ctl, &c->best_trans, &c->best_list, &c->best_scores, &c->best_mono}) b->release();
         for (auto& kv : c->rs_taps) kv.second.release();
         c->rs_taps.clear();
         c->work_tail.release(); c->tail_scores.release(); c->tail_stats.release(); c->work_tail2.release();

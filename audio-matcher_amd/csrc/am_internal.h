@@ -167,6 +167,9 @@ struct Ctx {
     HostBuf badflag; // one word per haystack of a call: "some score was not finite"
     DevBuf ranges, range_flags;   // work area of the non-finite-sample search (rare path)
     DevBuf big;                   // lists, sort keys and bucket table of a chunk with more than AM_MAX_PEAKS_PER_CHUNK peaks (rare path)
+    // the k best matches (am_best.hip): tile summaries, per-tile top keys, histograms and counters, the finite/non-finite
+    // transitions, the candidate list; the score array and the down-mixed haystack of am_match_best
+    DevBuf best_stats, best_lmax, best_ctl, best_trans, best_list, best_scores, best_mono;
     // the chunk list currently resident in `segs` (re-uploaded only when it changes)
     std::vector<Segment> segs_resident;
     // profiling
@@ -408,6 +411,14 @@ int launch_pick(Ctx* c, const float* d_scores, long long n_scores, int seg_off, 
 int pick_chunk_big(Ctx* c, const float* d_scores, long long n_scores, int seg_idx, const Segment& sg,
                    float min_prom, long long min_dist, const ScanRequest* scan, float seg_min,
                    std::vector<am_peak>& all, const PeakPolicy& pol);
+// am_find_peaks on a resident score array: one chunk [0, n) (am_api.hip)
+int find_peaks_host_array(Ctx* c, const float* d_scores, long long n, float min_prom, long long min_dist, std::vector<am_peak>& all);
+// ---- am_best.hip ----
+int best_transitions(Ctx* c, const float* d_x, long long n, std::vector<long long>& trans);
+int best_select(Ctx* c, const float* d_g, long long n, float min_prom, long long min_dist, size_t k, const PeakPolicy& pol,
+                std::vector<am_peak>& res);
+int match_best_one(am_needle* h, const void* d_hay, size_t len, int sample_format, const am_best_params* bp, am_peak* out,
+                   size_t* n_out);
 int merge_peaks(std::vector<am_peak>& all, const am_match_params* p, bool from_filtered, am_peak* out, size_t cap, size_t* n_out);
 void append_header_peaks(const SegHeader& hd, const PeakArena& arena, std::vector<am_peak>& all);
 

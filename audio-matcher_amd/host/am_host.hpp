@@ -76,6 +76,7 @@ struct Arguments {
     std::optional<int> normalize_floor_db;    // extension: --normalize-floor DB (option "score_norm_floor_db", 0..200)
     std::optional<float> min_confidence;      // extension: --min-confidence X, drop hits whose exact NCC is below X (am_hit_scores, 0..1)
     bool resample = false;                    // extension: --resample, bring the snippet to each main file's rate (am_needle_create_resampled)
+    std::optional<std::uint64_t> best;        // extension: --best N, the N best hits per main file, no prominence threshold (am_match_best)
     bool help = false;                        // --help
 
     std::uint64_t chunk_size_ms() const { return chunk_ms.value_or(60ull * 1000); }
@@ -93,6 +94,8 @@ inline const char* usage_text() {
            "                         --min-confidence apply to each snippet, --normalize matches them one by one\n"
            "  -p, --prominence P     minimal prominence of a hit, in percent (default 13)\n"
            "  --distance D           minimal distance between hits (default 8m)\n"
+           "  --best N               the N best hits of each file instead of those above the prominence (whole file\n"
+           "                         in one piece, hits at least --distance apart, in whole seconds)\n"
            "  --chunk-size D         length of one chunk (default 60s)\n"
            "  -o, --out FILE         label file (one input file only); --no-out: none\n"
            "  --dry-run              print the label file instead of writing it\n"
@@ -163,6 +166,14 @@ inline Arguments parse_arguments(int argc, const char* const* argv) {
             a.min_confidence = x;
         }
         else if (s == "--resample") a.resample = true;
+        else if (s == "--best") {
+            const std::string v = need(i);
+            char* end = nullptr;
+            const unsigned long long k = std::strtoull(v.c_str(), &end, 10);
+            if (v.empty() || v[0] == '-' || *end != '\0' || k == 0)
+                throw ArgError("invalid value '" + v + "' for --best (a whole number of hits, at least 1)");
+            a.best = (std::uint64_t)k;
+        }
         else if (s == "-h" || s == "--help") { a.help = true; return a; }
         else if (!s.empty() && s[0] == '-' && s != "-") throw ArgError("unknown option " + s);
         else if (!s.empty()) a.within.push_back(s);
@@ -313,6 +324,23 @@ inline std::uint64_t round_samples_ms(std::uint64_t ms, std::uint32_t sr) {
 }
 
 // Config::from_args (audio_matcher.rs:38-52) + the rounding of :99-100, :228
+// --best N: the N best hits of one main file (am_match_best: no chunks, no prominence threshold; min_distance from
+// --distance as the reference computes it; scale LIB), sorted by start
+inline std::vector<am_peak> best_hits(const Arguments& a, const am_needle* h, const std::vector<float>& samples, std::uint32_t sr) {
+    am_best_params bp{};
+    bp.k = *a.best;
+    bp.min_distance = (a.distance_msec() / 1000) * (std::uint64_t)sr;
+    bp.min_prominence = 0.0f;
+    bp.scale = AM_SCALE_LIB;
+    std::vector<am_peak> out((size_t)bp.k);
+    size_t n = 0;
+    if (am_match_best(h, samples.data(), samples.size(), AM_FMT_F32_MONO, &bp, out.data(), &n) != AM_OK)
+        throw std::runtime_error(std::string("am_match_best: ") + am_last_error_string());
+    out.resize(n);
+    std::stable_sort(out.begin(), out.end(), [](const am_peak& x, const am_peak& y) { return x.start < y.start; });
+    return out;
+}
+
 inline am_match_params make_params(const Arguments& a, std::uint32_t sr, double snippet_duration_s) {
     am_match_params p{};
     p.sr = sr;

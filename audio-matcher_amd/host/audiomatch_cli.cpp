@@ -120,7 +120,16 @@ static int run_multi(const Arguments& args) {
             size_t cap = 1024;
             std::vector<am_peak> peaks(cap * k);
             std::vector<size_t> n(k, 0);
-            if (!args.normalize) {
+            if (args.best) {   // extension: --best N, one am_match_best per snippet
+                std::vector<std::vector<am_peak>> each(k);
+                for (size_t j = 0; j < k; ++j) {
+                    each[j] = best_hits(args, handles[j], m_samples, m_sr);
+                    n[j] = each[j].size();
+                    cap = std::max(cap, n[j]);
+                }
+                peaks.assign(cap * k, am_peak{});
+                for (size_t j = 0; j < k; ++j) std::copy(each[j].begin(), each[j].end(), peaks.begin() + (std::ptrdiff_t)(j * cap));
+            } else if (!args.normalize) {
                 int rc = am_match_multi_varlen(handles.data(), k, overlaps.data(), m_samples.data(), m_samples.size(), AM_FMT_F32_MONO, &p,
                                                peaks.data(), cap, n.data());
                 if (rc == AM_ERR_CAPACITY) {
@@ -258,12 +267,17 @@ int main(int argc, char** argv) {
             }
             std::vector<am_peak> peaks(1024);
             size_t n = 0;
-            int rc = am_match(algo, m_samples.data(), m_samples.size(), &p, peaks.data(), peaks.size(), &n);
-            if (rc == AM_ERR_CAPACITY) {
-                peaks.resize(n);
-                rc = am_match(algo, m_samples.data(), m_samples.size(), &p, peaks.data(), peaks.size(), &n);
+            if (args.best) {                                                  // extension: --best N
+                peaks = best_hits(args, algo, m_samples, m_sr);
+                n = peaks.size();
+            } else {
+                int rc = am_match(algo, m_samples.data(), m_samples.size(), &p, peaks.data(), peaks.size(), &n);
+                if (rc == AM_ERR_CAPACITY) {
+                    peaks.resize(n);
+                    rc = am_match(algo, m_samples.data(), m_samples.size(), &p, peaks.data(), peaks.size(), &n);
+                }
+                if (rc != AM_OK) throw std::runtime_error(std::string("am_match: ") + am_last_error_string());
             }
-            if (rc != AM_OK) throw std::runtime_error(std::string("am_match: ") + am_last_error_string());
             if (args.min_confidence && n > 0) {                               // extension: --min-confidence
                 std::vector<am_hit_score> sc(n);
                 if (am_hit_scores(algo, m_samples.data(), m_samples.size(), AM_FMT_F32_MONO, peaks.data(), n, sc.data()) != AM_OK)

@@ -67,6 +67,10 @@ class AmMatchParams(C.Structure):
                 ("overshadow_distance_s", C.c_double), ("scale", C.c_int)]
 
 
+class AmBestParams(C.Structure):     # am_best_params (include/audiomatch.h, the k best matches)
+    _fields_ = [("k", C.c_uint64), ("min_distance", C.c_uint64), ("min_prominence", C.c_float), ("scale", C.c_int)]
+
+
 class AudioMatchError(RuntimeError):
     def __init__(self, code: int, msg: str):
         super().__init__(f"audiomatch error {code}: {msg}")
@@ -200,6 +204,16 @@ _SIGNATURES = {
     "am_needle_create_resampled": (C.c_int, [C.c_int, C.c_void_p, C.c_size_t, C.c_int, C.c_uint32, C.c_uint32,
                                              C.POINTER(C.c_void_p)]),
     "am_set_option": (C.c_int, [C.c_char_p, C.c_longlong]),
+    "am_match_best": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.POINTER(AmBestParams), C.POINTER(AmPeak),
+                                C.POINTER(C.c_size_t)]),
+    "am_match_best_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.POINTER(AmBestParams),
+                                       C.POINTER(AmPeak), C.POINTER(C.c_size_t)]),
+    "am_match_best_batch_device": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.c_size_t, C.c_int,
+                                             C.POINTER(AmBestParams), C.POINTER(AmPeak), C.POINTER(C.c_size_t)]),
+    "am_find_peaks_top": (C.c_int, [C.c_int, C.c_void_p, C.c_size_t, C.c_float, C.c_uint64, C.c_size_t,
+                                    C.POINTER(AmPeak), C.POINTER(C.c_size_t)]),
+    "am_find_peaks_top_device": (C.c_int, [C.c_int, C.c_void_p, C.c_size_t, C.c_float, C.c_uint64, C.c_size_t,
+                                           C.POINTER(AmPeak), C.POINTER(C.c_size_t)]),
     "am_get_option": (C.c_int, [C.c_char_p, C.POINTER(C.c_longlong)]),
 }
 
@@ -403,6 +417,32 @@ def find_peaks(y_data, min_prominence: float, min_distance: int = 0, device: int
     return [Peak(int(b.start), int(b.end), float(b.height), float(b.prominence)) for b in buf[:n.value]]
 
 
+def find_peaks_top(y_data, k: int, min_prominence: float = 0.0, min_distance: int = 0, device: int = 0):
+    """am_find_peaks_top: the first min(k, count) peaks find_peaks(y_data, min_prominence, min_distance) returns, by
+    descending height, without computing all of them.  A non-finite score splits the array."""
+    a = np.ascontiguousarray(y_data, dtype=np.float32)
+    buf = (AmPeak * max(1, int(k)))()
+    n = C.c_size_t(0)
+    _check(lib().am_find_peaks_top(device, a.ctypes.data, a.size, float(min_prominence), int(min_distance), int(k),
+                                   buf, C.byref(n)))
+    return _peaks(buf, n.value)
+
+
+def find_peaks_top_device(device: int, ptr: int, n: int, k: int, min_prominence: float = 0.0, min_distance: int = 0):
+    """am_find_peaks_top_device: the same on n f32 scores resident on `device`."""
+    buf = (AmPeak * max(1, int(k)))()
+    got = C.c_size_t(0)
+    _check(lib().am_find_peaks_top_device(device, ptr, int(n), float(min_prominence), int(min_distance), int(k),
+                                          buf, C.byref(got)))
+    return _peaks(buf, got.value)
+
+
+def best_params(k: int, min_distance: int = 0, min_prominence: float = 0.0, scale=Scale.LIB) -> AmBestParams:
+    """am_best_params of the k best matches (scale: Scale.NONE or Scale.LIB, or a bool as in correlate_with_sample)."""
+    sc = int(Scale.LIB if scale is True else Scale.NONE if scale is False else scale)
+    return AmBestParams(k=int(k), min_distance=int(min_distance), min_prominence=float(min_prominence), scale=sc)
+
+
 @dataclass
 class HitScore:
     """am_hit_score: exact NCC, least-squares gain, window level and sub-sample position of one hit."""
@@ -596,6 +636,41 @@ class HipConvolve:
                                            cap_per_hay, counts))
         return _split_batch(buf, counts, k, cap_per_hay)
 
+
+    # -- the k best matches --
+    def match_best(self, haystack, k: int, min_distance: int = 0, min_prominence: float = 0.0, scale=Scale.LIB):
+        """am_match_best: the k best peaks of the haystack's Valid scores (one array, no chunks), by descending height.
+        haystack: an f32 array, or an i16 (frames, 2) array of interleaved stereo."""
+        a = np.asarray(haystack)
+        if a.dtype == np.int16:
+            a = np.ascontiguousarray(a)
+            fmt, length = Fmt.S16_STEREO, a.size // 2
+        else:
+            a = np.ascontiguousarray(a, dtype=np.float32)
+            fmt, length = Fmt.F32_MONO, a.size
+        bp = best_params(k, min_distance, min_prominence, scale)
+        buf = (AmPeak * max(1, int(k)))()
+        n = C.c_size_t(0)
+        _check(lib().am_match_best(self._h, a.ctypes.data, length, int(fmt), C.byref(bp), buf, C.byref(n)))
+        return _peaks(buf, n.value)
+
+    def match_best_device(self, ptr: int, length: int, params: AmBestParams, fmt: int = Fmt.F32_MONO):
+        """am_match_best_device on a haystack resident on this needle's device."""
+        buf = (AmPeak * max(1, int(params.k)))()
+        n = C.c_size_t(0)
+        _check(lib().am_match_best_device(self._h, ptr, length, int(fmt), C.byref(params), buf, C.byref(n)))
+        return _peaks(buf, n.value)
+
+    def match_best_batch_device(self, ptrs, lengths, params: AmBestParams, fmt: int = Fmt.F32_MONO):
+        """am_match_best_batch_device: one list of the k best peaks per resident haystack."""
+        nh = len(ptrs)
+        k = int(params.k)
+        arr_p = (C.c_void_p * max(1, nh))(*ptrs)
+        arr_l = (C.c_size_t * max(1, nh))(*lengths)
+        buf = (AmPeak * max(1, k * nh))()
+        counts = (C.c_size_t * max(1, nh))()
+        _check(lib().am_match_best_batch_device(self._h, arr_p, arr_l, nh, int(fmt), C.byref(params), buf, counts))
+        return _split_batch(buf, counts, nh, k)
 
     # -- per-hit scoring --
     def hit_scores(self, haystack, peaks):

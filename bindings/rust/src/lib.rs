@@ -43,6 +43,16 @@ pub struct AmHitScore {
     pub window_db: f32,
     pub flags: u32,
 }
+/// am_best_params: the k best matches (am_match_best*)
+#[repr(C)]
+#[derive(Clone, Copy, Default, Debug)]
+pub struct AmBestParams {
+    pub k: u64,
+    pub min_distance: u64,
+    pub min_prominence: f32,
+    pub scale: c_int,
+}
+
 pub const AM_HIT_UNREFINED: u32 = 1;
 pub const AM_HIT_BELOW_FLOOR: u32 = 2;
 pub const AM_HIT_NONFINITE: u32 = 4;
@@ -157,6 +167,27 @@ extern "C" {
     pub fn am_hit_scores_batch_device(
         needles: *const *const AmNeedle, n_needles: usize, d_haystacks: *const *const std::ffi::c_void, lens: *const usize,
         n_hay: usize, sample_format: c_int, peaks: *const AmPeak, cap_per_pair: usize, n_peaks: *const usize, out: *mut AmHitScore,
+    ) -> c_int;
+    /// the k best matches: the first k peaks of find_peaks over the Valid scores, no prominence threshold (audiomatch.h)
+    pub fn am_match_best(
+        h: *const AmNeedle, haystack: *const std::ffi::c_void, len: usize, sample_format: c_int, bp: *const AmBestParams,
+        out: *mut AmPeak, n_out: *mut usize,
+    ) -> c_int;
+    pub fn am_match_best_device(
+        h: *const AmNeedle, d_haystack: *const std::ffi::c_void, len: usize, sample_format: c_int, bp: *const AmBestParams,
+        out: *mut AmPeak, n_out: *mut usize,
+    ) -> c_int;
+    pub fn am_match_best_batch_device(
+        h: *const AmNeedle, d_haystacks: *const *const std::ffi::c_void, lens: *const usize, n_hay: usize, sample_format: c_int,
+        bp: *const AmBestParams, out: *mut AmPeak, n_out: *mut usize,
+    ) -> c_int;
+    pub fn am_find_peaks_top(
+        device: c_int, scores: *const f32, n: usize, min_prominence: f32, min_distance: u64, k: usize, out: *mut AmPeak,
+        n_out: *mut usize,
+    ) -> c_int;
+    pub fn am_find_peaks_top_device(
+        device: c_int, d_scores: *const f32, n: usize, min_prominence: f32, min_distance: u64, k: usize, out: *mut AmPeak,
+        n_out: *mut usize,
     ) -> c_int;
     /// calc_chunks on the lazy sample iterator (audio_matcher.rs:88-104, mp3_reader.rs:13-41)
     pub fn am_match_stream_begin(
@@ -313,6 +344,24 @@ impl HipConvolve {
         if rc != AM_OK {
             return Err(am_err(rc));
         }
+        Ok(out)
+    }
+
+    /// The `k` best matches in the host haystack `m_samples` (am_match_best): the best peaks of its Valid scores by
+    /// descending height, at least `min_distance` samples apart, no prominence threshold; LIB scale (NCC when the
+    /// handle's "score_norm" is on).  Fewer than `k` when fewer peaks exist.
+    pub fn best_matches(&self, m_samples: &[f32], k: usize, min_distance: u64) -> Result<Vec<AmPeak>, Box<dyn std::error::Error>> {
+        let bp = AmBestParams { k: k as u64, min_distance, min_prominence: 0.0, scale: 1 };
+        let mut out = vec![AmPeak::default(); k.max(1)];
+        let mut n = 0usize;
+        let rc = unsafe {
+            am_match_best(self.h, m_samples.as_ptr() as *const std::ffi::c_void, m_samples.len(), AM_FMT_F32_MONO, &bp,
+                          out.as_mut_ptr(), &mut n)
+        };
+        if rc != AM_OK {
+            return Err(am_err(rc));
+        }
+        out.truncate(n);
         Ok(out)
     }
 

@@ -279,6 +279,49 @@ void am_match_stream_destroy(am_stream* st);
 int am_find_peaks(int device, const float* scores, size_t n, float min_prominence,
                   uint64_t min_distance, am_peak* out, size_t cap, size_t* n_out);
 
+/* ---- the k best matches -------------------------------------------------------------------------------------
+ * "Where are the k places this needle fits best?" without a prominence threshold ("The k best
+ * matches").
+ *
+ * am_find_peaks_top(scores, n, k, p, d) returns the first min(k, count) entries of what
+ * am_find_peaks(scores, n, p, d) returns: the same peaks in the same order (descending height, ties by ascending
+ * start), bit for bit in start, end, height and prominence, under every value of the options "peak_filter_order" and
+ * "distance_rule".  A non-finite score splits the array: every finite stretch is its own find_peaks array (no peak
+ * at its ends; prominence walks and plateaus stop there); the distance rule and k apply to the union.  For an
+ * all-finite array the result is exactly am_find_peaks[:k].  Selection runs on the device without computing the
+ * prominence of every local maximum: a height histogram of the maxima picks a threshold that leaves a few thousand
+ * candidates, whose prominences are walked and filtered; the threshold is lowered while fewer than k survive.
+ * *n_out = the number of peaks written (< k when fewer exist: not an error).  out: k slots.  k == 0 or a null
+ * pointer: AM_ERR_INVALID_ARG.
+ *
+ * am_match_best(h, haystack, len, fmt, bp) = am_find_peaks_top over the haystack's AM_MODE_VALID correlation scores
+ * (one array, no chunks): on a finite f32 haystack exactly the scores am_correlate_device(h, haystack, len,
+ * AM_MODE_VALID, bp->scale) writes, "score_norm" (NCC) included.  AM_FMT_S16_STEREO: the bit-exact down-mix, then as
+ * for f32.  A window that holds a non-finite sample has no score (NaN, which splits the array as above): every
+ * finite stretch of at least S samples is correlated on its own.  A haystack shorter than the needle: 0 hits.
+ * bp->scale must be AM_SCALE_NONE or AM_SCALE_LIB (AM_SCALE_MY depends on a chunk: AM_ERR_INVALID_ARG).
+ * am_match_best_batch_device: n_hay resident haystacks, k slots and one count per haystack; each result is
+ * bit-identical to its single call. */
+typedef struct am_best_params {
+    uint64_t k;              /* hits wanted, >= 1 */
+    uint64_t min_distance;   /* samples, as am_match_params.min_distance (find_peaks' with_min_distance) */
+    float min_prominence;    /* 0 = every local maximum competes */
+    int scale;               /* AM_SCALE_NONE or AM_SCALE_LIB */
+} am_best_params;
+
+int am_match_best(const am_needle* h, const void* haystack, size_t len, int sample_format,
+                  const am_best_params* bp, am_peak* out, size_t* n_out);
+int am_match_best_device(const am_needle* h, const void* d_haystack, size_t len, int sample_format,
+                         const am_best_params* bp, am_peak* out, size_t* n_out);
+int am_match_best_batch_device(const am_needle* h, const void* const* d_haystacks, const size_t* lens,
+                               size_t n_hay, int sample_format, const am_best_params* bp,
+                               am_peak* out, size_t* n_out);
+int am_find_peaks_top(int device, const float* scores, size_t n, float min_prominence,
+                      uint64_t min_distance, size_t k, am_peak* out, size_t* n_out);
+int am_find_peaks_top_device(int device, const float* d_scores, size_t n, float min_prominence,
+                             uint64_t min_distance, size_t k, am_peak* out, size_t* n_out);
+
+
 /* ---- ingest: PCM -> f32 mono -------------------------------------------- */
 /* mp3_reader.rs:12, 28-37: mono = (l as f32 + r as f32) * 0.5 * (1/65535) */
 int am_pcm_s16_stereo_to_mono(int device, const int16_t* interleaved, size_t frames, float* out);
@@ -538,7 +581,8 @@ int am_debug_column_bench(int device, int wide, int npairs, int iters, int dense
  *     ("Normalised scores").  Requires scale == AM_SCALE_LIB (any other scale: AM_ERR_INVALID_ARG).
  *     Also per needle handle (am_needle_set_option); pools use the process default (their needles are internal).
  *     Supported by am_correlate*, am_match, am_match_device, am_match_batch_device, am_match_pcm16*,
- *     am_pool_match_batch and am_pool_match_batch_pcm16 (and their _device forms).  NOT supported -- AM_ERR_INVALID_ARG,
+ *     am_pool_match_batch and am_pool_match_batch_pcm16 (and their _device forms), am_match_best,
+ *     am_match_best_device and am_match_best_batch_device.  NOT supported -- AM_ERR_INVALID_ARG,
  *     "score_norm: not supported by this entry point" -- by am_match_multi*, am_match_multi_varlen_batch_device,
  *     am_match_multi_varlen, am_pool_match_multi*, am_match_stream_*, am_match_part_device and am_pool_match_long*.  am_find_peaks is unaffected.
  *     Non-finite samples cost exactly the windows that hold them (they count as 0 in every other window's energy); a

@@ -141,12 +141,58 @@ public:
         check(am_hit_scores_device(h_, d_haystack, len, sample_format, peaks.data(), peaks.size(), out.data()));
         return out;
     }
+    // the k best matches (am_match_best): the best min(k, count) peaks of the haystack's Valid scores by descending
+    // height, no prominence threshold needed; am_match_best_device / _batch_device for resident haystacks
+    std::vector<am_peak> match_best(const void* haystack, std::size_t len, int sample_format, const am_best_params& bp) const {
+        std::vector<am_peak> out(static_cast<std::size_t>(bp.k));
+        std::size_t n = 0;
+        check(am_match_best(h_, haystack, len, sample_format, &bp, out.data(), &n));
+        out.resize(n);
+        return out;
+    }
+    std::vector<am_peak> match_best_device(const void* d_haystack, std::size_t len, int sample_format, const am_best_params& bp) const {
+        std::vector<am_peak> out(static_cast<std::size_t>(bp.k));
+        std::size_t n = 0;
+        check(am_match_best_device(h_, d_haystack, len, sample_format, &bp, out.data(), &n));
+        out.resize(n);
+        return out;
+    }
+    std::vector<std::vector<am_peak>> match_best_batch_device(const std::vector<const void*>& d_haystacks, const std::vector<std::size_t>& lens,
+                                                              int sample_format, const am_best_params& bp) const {
+        if (d_haystacks.size() != lens.size()) check(AM_ERR_INVALID_ARG);
+        const std::size_t nh = d_haystacks.size(), k = static_cast<std::size_t>(bp.k);
+        std::vector<am_peak> buf(std::max<std::size_t>(1, nh * k));
+        std::vector<std::size_t> n(std::max<std::size_t>(1, nh), 0);
+        check(am_match_best_batch_device(h_, d_haystacks.data(), lens.data(), nh, sample_format, &bp, buf.data(), n.data()));
+        std::vector<std::vector<am_peak>> out(nh);
+        for (std::size_t i = 0; i < nh; ++i) out[i].assign(buf.begin() + (std::ptrdiff_t)(i * k), buf.begin() + (std::ptrdiff_t)(i * k + n[i]));
+        return out;
+    }
     // per-handle "log_n" / "half_pipeline" / "score_norm" (-1 = follow the process default)
     void set_option(const char* key, long long value) { check(am_needle_set_option(h_, key, value)); }
 
 private:
     am_needle* h_ = nullptr;
 };
+
+// am_find_peaks_top: the first min(k, count) peaks find_peaks(scores) returns, by descending height, computed without
+// listing them all; find_peaks_top_device for scores resident on `device`
+inline std::vector<am_peak> find_peaks_top(const float* scores, std::size_t n, std::size_t k, float min_prominence = 0.0f,
+                                           std::uint64_t min_distance = 0, int device = 0) {
+    std::vector<am_peak> out(k);
+    std::size_t got = 0;
+    check(am_find_peaks_top(device, scores, n, min_prominence, min_distance, k, out.data(), &got));
+    out.resize(got);
+    return out;
+}
+inline std::vector<am_peak> find_peaks_top_device(const float* d_scores, std::size_t n, std::size_t k, float min_prominence = 0.0f,
+                                                  std::uint64_t min_distance = 0, int device = 0) {
+    std::vector<am_peak> out(k);
+    std::size_t got = 0;
+    check(am_find_peaks_top_device(device, d_scores, n, min_prominence, min_distance, k, out.data(), &got));
+    out.resize(got);
+    return out;
+}
 
 // calc_chunks(sr, m_samples, &algo, scale, config) (audio_matcher.rs:88-141):
 // peaks sorted by position.start, overshadowed neighbours removed.
