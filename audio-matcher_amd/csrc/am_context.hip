@@ -93,7 +93,9 @@ static Option* find_option(const char* key) {
 }
 
 // every option's value now, with the handle's own "log_n" / "half_pipeline" / "score_norm" (>= 0) over the defaults
+thread_local const Opts* t_opts_pin = nullptr;
 Opts snapshot_opts(const am_needle* h) {
+    if (t_opts_pin) return *t_opts_pin;
     Opts o;
     for (const Option& r : g_options) o.*r.field = r.value.load(std::memory_order_relaxed);
     if (h && h->opt_log_n >= 0) o.log_n = h->opt_log_n;

@@ -531,22 +531,38 @@ void make_segments(size_t len, size_t s, const am_match_params* p, bool drop_tai
 // sequential filter); default: both neighbours come from the sorted, unfiltered sequence.
 int merge_peaks(std::vector<am_peak>& all, const am_match_params* p, bool from_filtered, am_peak* out, size_t cap, size_t* n_out) {
     std::stable_sort(all.begin(), all.end(), [](const am_peak& x, const am_peak& y) { return x.start < y.start; });
-    size_t n = 0;
-    am_peak last_kept{};
-    bool have_kept = false;
-    for (size_t i = 0; i < all.size(); ++i) {
-        const am_peak* before = from_filtered ? (have_kept ? &last_kept : nullptr) : (i > 0 ? &all[i - 1] : nullptr);
-        const am_peak* after = i + 1 < all.size() ? &all[i + 1] : nullptr;
-        if (is_overshadowed(all[i], before, p->sr, p->overshadow_distance_s) ||
-            is_overshadowed(all[i], after, p->sr, p->overshadow_distance_s))
-            continue;
-        last_kept = all[i]; have_kept = true;
-        if (n < cap) out[n] = all[i];
-        ++n;
-    }
+    MergeCursor cur;
+    std::vector<am_peak> kept;
+    merge_settle(p, from_filtered, cur, all.data(), all.size(), 0, true, &kept);
+    const size_t n = kept.size();
+    for (size_t i = 0; i < n && i < cap; ++i) out[i] = kept[i];
     *n_out = n;
     if (n > cap) return fail(AM_ERR_CAPACITY, "peak output buffer too small");
     return AM_OK;
+}
+
+// The filter of merge_peaks over a list that grows at its end (am_monitor).  An element's fate depends on its two
+// neighbours only (audio_matcher.rs:143-160): every element but the last has its successor in the list; the last is
+// settled when its predecessor overshadows it, or when no successor can -- one at `horizon` with +inf prominence is
+// the strongest and nearest any later element can be, and is_overshadowed itself decides.  `ended`: nothing comes.
+size_t merge_settle(const am_match_params* p, bool from_filtered, MergeCursor& cur, const am_peak* sorted, size_t n,
+                    uint64_t horizon, bool ended, std::vector<am_peak>* kept_out) {
+    am_peak strongest{};
+    strongest.start = horizon;
+    strongest.prominence = INFINITY;
+    for (size_t i = 0; i < n; ++i) {
+        const am_peak& x = sorted[i];
+        const am_peak* before = from_filtered ? (cur.has_kept ? &cur.kept : nullptr) : (cur.has_prev ? &cur.prev : nullptr);
+        const am_peak* after = i + 1 < n ? &sorted[i + 1] : nullptr;
+        const bool shadowed_before = is_overshadowed(x, before, p->sr, p->overshadow_distance_s);
+        if (!after && !ended && !shadowed_before && is_overshadowed(x, &strongest, p->sr, p->overshadow_distance_s)) return i;
+        if (!shadowed_before && !is_overshadowed(x, after, p->sr, p->overshadow_distance_s)) {
+            cur.kept = x; cur.has_kept = true;
+            if (kept_out) kept_out->push_back(x);
+        }
+        cur.prev = x; cur.has_prev = true;
+    }
+    return n;
 }
 
 // Appends the peaks of header `hd` (inline, or spilled to the arena) to `all`.
@@ -588,3 +604,16 @@ int nonfinite_flags(Ctx* c, const float* d_src, const Segment* ranges, int n, in
     return AM_OK;
 }
 }  // namespace am
+
+extern "C" int am_merge_ready(const am_match_params* p, const am_peak* sorted, size_t n, uint64_t horizon, int ended, size_t* n_ready) {
+    using namespace am;
+    if (!p || !n_ready || (!sorted && n)) return fail(AM_ERR_INVALID_ARG, "null pointer");
+    if (p->sr == 0) return fail(AM_ERR_INVALID_ARG, "p->sr must be > 0");
+    *n_ready = 0;
+    for (size_t i = 1; i < n; ++i)
+        if (sorted[i].start < sorted[i - 1].start) return fail(AM_ERR_INVALID_ARG, "sorted: peaks not sorted by start");
+    if (!ended && n && sorted[n - 1].start >= horizon) return fail(AM_ERR_INVALID_ARG, "sorted: a peak starts at or after horizon");
+    MergeCursor cur;
+    *n_ready = merge_settle(p, snapshot_opts(nullptr).surrounding_from != 0, cur, sorted, n, horizon, ended != 0, nullptr);
+    return AM_OK;
+}

@@ -352,6 +352,16 @@ inline const void* advance_src(const void* src, size_t elements) {
 
 // ---- am_context.hip ----
 Opts snapshot_opts(const am_needle* h);
+// While an OptsPin lives, snapshot_opts on this thread returns the options it holds (a monitor's calls see the options
+// read at am_monitor_begin, whatever am_set_option did since).
+extern thread_local const Opts* t_opts_pin;
+struct OptsPin {
+    const Opts* prev;
+    explicit OptsPin(const Opts* o) : prev(t_opts_pin) { t_opts_pin = o; }
+    ~OptsPin() { t_opts_pin = prev; }
+    OptsPin(const OptsPin&) = delete;
+    OptsPin& operator=(const OptsPin&) = delete;
+};
 int check_needle(const am_needle* h);
 // a handle over d_needle (n samples, owned by the handle from here on, freed if this fails) with its energy measured
 int create_needle_common(Ctx* c, float* d_needle, size_t n, am_needle** out);
@@ -420,6 +430,12 @@ int best_select(Ctx* c, const float* d_g, long long n, float min_prom, long long
 int match_best_one(am_needle* h, const void* d_hay, size_t len, int sample_format, const am_best_params* bp, am_peak* out,
                    size_t* n_out);
 int merge_peaks(std::vector<am_peak>& all, const am_match_params* p, bool from_filtered, am_peak* out, size_t cap, size_t* n_out);
+// what merge_settle carries from one piece of a sorted list to the next: the element before the next one, the last one kept
+struct MergeCursor { am_peak prev{}, kept{}; bool has_prev = false, has_kept = false; };
+// the longest prefix of sorted[0, n) whose fates under merge_peaks are final (no element still to come starts before
+// `horizon`): settles it into `cur`, appends the kept ones to *kept_out (if given), returns its length
+size_t merge_settle(const am_match_params* p, bool from_filtered, MergeCursor& cur, const am_peak* sorted, size_t n,
+                    uint64_t horizon, bool ended, std::vector<am_peak>* kept_out);
 void append_header_peaks(const SegHeader& hd, const PeakArena& arena, std::vector<am_peak>& all);
 
 // ---- am_engine.hip ----

@@ -77,6 +77,10 @@ struct Arguments {
     std::optional<float> min_confidence;      // extension: --min-confidence X, drop hits whose exact NCC is below X (am_hit_scores, 0..1)
     bool resample = false;                    // extension: --resample, bring the snippet to each main file's rate (am_needle_create_resampled)
     std::optional<std::uint64_t> best;        // extension: --best N, the N best hits per main file, no prominence threshold (am_match_best)
+    bool live = false;                        // extension: --live, raw PCM from stdin through a monitor (am_monitor_*)
+    std::uint32_t rate = 0;                   // --live: --rate R (samples per second of the stream)
+    std::string encoding = "s16le";           // --live: --encoding s16le | f32le
+    int channels = 2;                         // --live: --channels 1 | 2
     bool help = false;                        // --help
 
     std::uint64_t chunk_size_ms() const { return chunk_ms.value_or(60ull * 1000); }
@@ -114,6 +118,15 @@ inline const char* usage_text() {
            "                         hit's position, ncc, gain and window level (default: keep every hit)\n"
            "  --resample             match main files of any sample rate: the snippet is resampled to each file's rate\n"
            "                         (scipy's resample_poly filter); without it, a rate mismatch stops the run\n"
+           "  --live                 read raw PCM from stdin instead of files (no FILE arguments): a live feed, matched\n"
+           "                         as it arrives; each hit's offset line is printed (and flushed) as soon as it is\n"
+           "                         final -- a hit is final once the next hit is found, or once --distance of audio\n"
+           "                         has passed behind it, so use a short --distance for monitoring.  At end of input\n"
+           "                         the label file (-o FILE; none without -o) is written as for a file.  Needs --rate;\n"
+           "                         --best, --normalize and --min-confidence do not apply\n"
+           "  --rate R               --live: sample rate of the stream, in Hz\n"
+           "  --encoding E           --live: s16le (default) or f32le (f32le: one channel only)\n"
+           "  --channels C           --live: 1 or 2 (default 2)\n"
            "  --help                 this text\n";
 }
 
@@ -174,11 +187,36 @@ inline Arguments parse_arguments(int argc, const char* const* argv) {
                 throw ArgError("invalid value '" + v + "' for --best (a whole number of hits, at least 1)");
             a.best = (std::uint64_t)k;
         }
+        else if (s == "--live") a.live = true;
+        else if (s == "--rate") {
+            const std::string v = need(i);
+            char* end = nullptr;
+            const unsigned long r = std::strtoul(v.c_str(), &end, 10);
+            if (v.empty() || v[0] == '-' || *end != '\0' || r == 0 || r > 4000000)
+                throw ArgError("invalid value '" + v + "' for --rate (samples per second, 1..4000000)");
+            a.rate = (std::uint32_t)r;
+        }
+        else if (s == "--encoding") {
+            a.encoding = need(i);
+            if (a.encoding != "s16le" && a.encoding != "f32le") throw ArgError("invalid value '" + a.encoding + "' for --encoding (s16le or f32le)");
+        }
+        else if (s == "--channels") {
+            const std::string v = need(i);
+            if (v != "1" && v != "2") throw ArgError("invalid value '" + v + "' for --channels (1 or 2)");
+            a.channels = v[0] - '0';
+        }
         else if (s == "-h" || s == "--help") { a.help = true; return a; }
         else if (!s.empty() && s[0] == '-' && s != "-") throw ArgError("unknown option " + s);
         else if (!s.empty()) a.within.push_back(s);
     }
     if (a.snippet.empty()) throw ArgError("--snippet <FILE> is required");
+    if (a.live) {
+        if (!a.within.empty()) throw ArgError("--live reads stdin: no FILE arguments");
+        if (a.rate == 0) throw ArgError("--live needs --rate");
+        if (a.encoding == "f32le" && a.channels != 1) throw ArgError("--encoding f32le takes one channel only (--channels 1)");
+        if (a.best || a.normalize || a.min_confidence) throw ArgError("--live: --best, --normalize and --min-confidence do not apply");
+        return a;
+    }
     if (a.no_out && a.out_file) throw ArgError("--no-out and --out are mutually exclusive");      // #[group(multiple = false)]
     if (a.out_file && a.within.size() != 1)
         throw ArgError("providet outfile only compatible with one main file");                     // matcher/mod.rs:20-26
@@ -275,17 +313,18 @@ inline std::string fmt_f32(float v) {
 }
 
 // matcher/mod.rs:110-125: "Offset i: hh:mm:ss with prominence p"
+inline std::string offset_line(const am_peak& peak, std::size_t i, std::uint32_t sr) {   // i counts from 0
+    const double secs = (double)peak.start / (double)sr;     // start_as_duration (:127-129)
+    const std::uint64_t whole = (std::uint64_t)secs;
+    char buf[160];
+    std::snprintf(buf, sizeof buf, "Offset %zu: %02" PRIu64 ":%02" PRIu64 ":%02" PRIu64 " with prominence %s", i + 1,
+                  whole / 3600, (whole / 60) % 60, whole % 60, fmt_f32(peak.prominence).c_str());
+    return buf;
+}
 inline std::vector<std::string> offset_lines(const am_peak* peaks, std::size_t n, std::uint32_t sr) {
     std::vector<std::string> out;
     if (n == 0) { out.push_back("no offsets found"); return out; }
-    for (std::size_t i = 0; i < n; ++i) {
-        const double secs = (double)peaks[i].start / (double)sr;     // start_as_duration (:127-129)
-        const std::uint64_t whole = (std::uint64_t)secs;
-        char buf[160];
-        std::snprintf(buf, sizeof buf, "Offset %zu: %02" PRIu64 ":%02" PRIu64 ":%02" PRIu64 " with prominence %s", i + 1,
-                      whole / 3600, (whole / 60) % 60, whole % 60, fmt_f32(peaks[i].prominence).c_str());
-        out.push_back(buf);
-    }
+    for (std::size_t i = 0; i < n; ++i) out.push_back(offset_line(peaks[i], i, sr));
     return out;
 }
 

@@ -7,6 +7,7 @@
 #include <iostream>
 #include <map>
 #include <sys/stat.h>
+#include <unistd.h>
 
 #include "am_host.hpp"
 
@@ -201,6 +202,143 @@ static int run_multi(const Arguments& args) {
     }
 }
 
+// extension: --live.  Raw PCM from stdin through one monitor (am_monitor_*, all snippets in it): every chunk of input is
+// turned into the f32 mono samples the file mode would have made of the same frames (to_mono_f32), pushed, and the hits
+// that became final are printed at once, numbered per snippet as the file mode numbers them.  At end of input the
+// label file is written exactly as the file mode writes it for that recording (timelabel_from_peaks over the hits of
+// all snippets by start, equal starts in --snippet order: the monitor's own order).
+static int run_live(const Arguments& args) {
+    struct Snip {
+        std::string name;
+        am_needle* h = nullptr;
+        am_needle* resampled = nullptr;
+        am_match_params p{};
+        size_t hits = 0;
+    };
+    const std::uint32_t sr = args.rate;
+    const size_t k = args.snippets.size();
+    std::vector<Snip> snips(k);
+    am_monitor* mon = nullptr;
+    auto release = [&]() {
+        if (mon) am_monitor_destroy(mon);
+        for (Snip& sn : snips) {
+            if (sn.h) am_needle_destroy(sn.h);
+            if (sn.resampled) am_needle_destroy(sn.resampled);
+        }
+    };
+    try {
+        std::vector<const am_needle*> handles(k);
+        std::vector<am_match_params> params(k);
+        for (size_t j = 0; j < k; ++j) {
+            Snip& sn = snips[j];
+            const Pcm pcm = read_wav(args.snippets[j]);
+            sn.name = base_name(args.snippets[j]);
+            const double duration = (double)pcm.frames() / (double)pcm.sample_rate;
+            const std::vector<float> data = to_mono_f32(pcm, args.device);
+            if (am_needle_create(args.device, data.data(), data.size(), &sn.h) != AM_OK)
+                throw std::runtime_error(std::string("am_needle_create: ") + am_last_error_string());
+            sn.p = make_params(args, sr, duration);
+            handles[j] = sn.h;
+            if (pcm.sample_rate != sr) {
+                if (!args.resample) {
+                    std::fprintf(stderr, "sample rate of snippet (%u) and main file (%u) don't match\n", pcm.sample_rate, sr);
+                    release();
+                    return 3;
+                }
+                if (am_needle_create_resampled(args.device, data.data(), data.size(), AM_FMT_F32_MONO, pcm.sample_rate, sr, &sn.resampled) != AM_OK)
+                    throw std::runtime_error(std::string("am_needle_create_resampled: ") + am_last_error_string());
+                size_t s_len = 0;   // the overlap = the resampled snippet's length
+                am_needle_len(sn.resampled, &s_len);
+                sn.p.overlap = s_len;
+                handles[j] = sn.resampled;
+            }
+            params[j] = sn.p;
+        }
+        if (am_monitor_begin(handles.data(), k, params.data(), AM_FMT_F32_MONO, 1, &mon) != AM_OK)
+            throw std::runtime_error(std::string("am_monitor_begin: ") + am_last_error_string());
+        std::vector<am_peak> all;            // every hit, in the monitor's order: (start, snippet)
+        std::vector<am_peak> got(256);
+        std::vector<std::uint32_t> which(256);
+        auto report = [&](size_t n) {
+            for (size_t i = 0; i < n; ++i) {
+                Snip& sn = snips[which[i]];
+                if (args.verbosity >= 1) {
+                    const std::string line = offset_line(got[i], sn.hits, sr);
+                    if (k > 1) std::printf("%s: %s\n", sn.name.c_str(), line.c_str());
+                    else std::printf("%s\n", line.c_str());
+                }
+                ++sn.hits;
+                all.push_back(got[i]);
+            }
+            std::fflush(stdout);
+        };
+        auto take = [&](int (*fn)(am_monitor*, am_peak*, std::uint32_t*, size_t, size_t*), const char* what) {
+            size_t n = 0;
+            int rc = fn(mon, got.data(), which.data(), got.size(), &n);
+            if (rc == AM_ERR_CAPACITY) {
+                got.resize(n); which.resize(n);
+                rc = fn(mon, got.data(), which.data(), got.size(), &n);
+            }
+            if (rc != AM_OK) throw std::runtime_error(std::string(what) + ": " + am_last_error_string());
+            report(n);
+        };
+        // stdin in pieces as they come (read(2): a pipe hands over what it holds), whole frames only
+        const size_t in_frame = (args.encoding == "f32le" ? 4u : 2u) * (size_t)args.channels;
+        std::vector<char> raw((size_t)1 << 16);
+        size_t have = 0;
+        Pcm piece;
+        piece.sample_rate = sr;
+        piece.channels = (std::uint16_t)args.channels;
+        piece.is_float = args.encoding == "f32le";
+        for (;;) {
+            const ssize_t got_bytes = ::read(0, raw.data() + have, raw.size() - have);
+            if (got_bytes < 0) throw std::runtime_error("reading stdin failed");
+            if (got_bytes == 0) break;
+            have += (size_t)got_bytes;
+            const size_t frames = have / in_frame;
+            if (frames == 0) continue;
+            if (piece.is_float) {
+                piece.f32.resize(frames);
+                std::memcpy(piece.f32.data(), raw.data(), frames * 4);
+            } else {
+                piece.s16.resize(frames * (size_t)args.channels);
+                std::memcpy(piece.s16.data(), raw.data(), frames * in_frame);
+            }
+            const std::vector<float> mono = to_mono_f32(piece, args.device);
+            if (am_monitor_push(mon, mono.data(), mono.size()) != AM_OK)
+                throw std::runtime_error(std::string("am_monitor_push: ") + am_last_error_string());
+            take(am_monitor_poll, "am_monitor_poll");
+            std::memmove(raw.data(), raw.data() + frames * in_frame, have - frames * in_frame);
+            have -= frames * in_frame;
+        }
+        take(am_monitor_end, "am_monitor_end");
+        if (args.verbosity >= 1)
+            for (const Snip& sn : snips)
+                if (sn.hits == 0) {
+                    if (k > 1) std::printf("%s: no offsets found\n", sn.name.c_str());
+                    else std::printf("no offsets found\n");
+                }
+        std::fflush(stdout);
+        int rc_all = 0;
+        if (args.out_file && !args.no_out) {
+            const std::string text = format_labels(timelabel_from_peaks(all.data(), all.size(), sr, 7.0, "Segment #"));
+            if (args.dry_run) {
+                std::printf("would write to '%s':\n%s", args.out_file->c_str(), text.c_str());
+            } else {
+                std::ofstream f(*args.out_file, std::ios::binary | std::ios::trunc);
+                if (!f) { std::fprintf(stderr, "couldn't find file '%s'\n", args.out_file->c_str()); rc_all = 4; }
+                else f << text;
+            }
+        }
+        release();
+        return rc_all;
+    } catch (const std::exception& e) {
+        release();
+        std::fprintf(stderr, "error: %s\n", e.what());
+        return 1;
+    }
+}
+
 int main(int argc, char** argv) {
     Arguments args;
     try {
@@ -213,6 +351,7 @@ int main(int argc, char** argv) {
         std::printf("%s", usage_text());
         return 0;
     }
+    if (args.live) return run_live(args);
     if (args.snippets.size() > 1) return run_multi(args);
     try {
         const Pcm snippet = read_wav(args.snippet);                           // mod.rs:29

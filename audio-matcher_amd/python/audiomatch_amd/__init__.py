@@ -71,6 +71,10 @@ class AmBestParams(C.Structure):     # am_best_params (include/audiomatch.h, the
     _fields_ = [("k", C.c_uint64), ("min_distance", C.c_uint64), ("min_prominence", C.c_float), ("scale", C.c_int)]
 
 
+class AmMonitorInfo(C.Structure):  # am_monitor_info (include/audiomatch.h, live monitoring)
+    _fields_ = [("received", C.c_uint64), ("horizon", C.c_uint64), ("resident_bytes", C.c_uint64), ("pending", C.c_uint64)]
+
+
 class AudioMatchError(RuntimeError):
     def __init__(self, code: int, msg: str):
         super().__init__(f"audiomatch error {code}: {msg}")
@@ -181,6 +185,15 @@ _SIGNATURES = {
                                      C.c_size_t, C.POINTER(C.c_size_t)]),
     "am_pool_match_long_device": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.c_size_t, C.c_int, C.POINTER(AmMatchParams),
                                             C.POINTER(AmPeak), C.c_size_t, C.POINTER(C.c_size_t)]),
+    "am_merge_ready": (C.c_int, [C.POINTER(AmMatchParams), C.POINTER(AmPeak), C.c_size_t, C.c_uint64, C.c_int,
+                                 C.POINTER(C.c_size_t)]),
+    "am_monitor_begin": (C.c_int, [C.POINTER(C.c_void_p), C.c_size_t, C.POINTER(AmMatchParams), C.c_int, C.c_size_t,
+                                   C.POINTER(C.c_void_p)]),
+    "am_monitor_push": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
+    "am_monitor_poll": (C.c_int, [C.c_void_p, C.POINTER(AmPeak), C.POINTER(C.c_uint32), C.c_size_t, C.POINTER(C.c_size_t)]),
+    "am_monitor_end": (C.c_int, [C.c_void_p, C.POINTER(AmPeak), C.POINTER(C.c_uint32), C.c_size_t, C.POINTER(C.c_size_t)]),
+    "am_monitor_info_get": (C.c_int, [C.c_void_p, C.POINTER(AmMonitorInfo)]),
+    "am_monitor_destroy": (None, [C.c_void_p]),
     "am_match_stream_begin": (C.c_int, [C.c_void_p, C.c_int, C.c_size_t, C.POINTER(AmMatchParams), C.POINTER(C.c_void_p)]),
     "am_match_stream_push": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
     "am_match_stream_finish": (C.c_int, [C.c_void_p, C.POINTER(AmPeak), C.c_size_t, C.POINTER(C.c_size_t)]),
@@ -772,6 +785,79 @@ def merge_peaks(params: AmMatchParams, peaks, cap: int = 4096):
     n = C.c_size_t(0)
     _check(lib().am_merge_peaks(C.byref(params), src, k, buf, cap, C.byref(n)))
     return _peaks(buf, n.value)
+
+
+def merge_ready(params: AmMatchParams, peaks, horizon: int, ended: bool = False) -> int:
+    """am_merge_ready: how many of `peaks` (unfiltered, sorted by start; none at or after `horizon`) have a fate under
+    merge_peaks that no later peak can change (audio_matcher.rs:143-160)."""
+    n = C.c_size_t(0)
+    _check(lib().am_merge_ready(C.byref(params), _peak_array(peaks), len(peaks), int(horizon), int(bool(ended)), C.byref(n)))
+    return n.value
+
+
+@dataclass
+class MonitorInfo:
+    received: int        # samples / frames pushed so far
+    horizon: int         # every window before this sample has been matched
+    resident_bytes: int  # device bytes of the monitor's sample buffer (fixed at begin)
+    pending: int         # peaks found but not yet final
+
+
+class HipMonitor:
+    """Live monitoring (am_monitor_*): the final hits of one or several needles while the recording arrives, in
+    bounded device memory.  params: one AmMatchParams for all needles, or one per needle.  push() returns the hits
+    that became final, as (needle index, Peak) sorted by (start, needle); end() returns the rest."""
+
+    def __init__(self, algos, params, fmt: int = Fmt.F32_MONO, group_windows: int = 1):
+        algos = list(algos) if isinstance(algos, (list, tuple)) else [algos]
+        self._algos = algos                    # keeps the needle handles alive
+        self.fmt = int(fmt)
+        ps = list(params) if isinstance(params, (list, tuple)) else [params] * len(algos)
+        hs = (C.c_void_p * len(algos))(*[a._h.value for a in algos])
+        pa = (AmMatchParams * len(ps))(*ps)
+        self._m = C.c_void_p()
+        self._cap = 256
+        _check(lib().am_monitor_begin(hs, len(algos), pa, self.fmt, int(group_windows), C.byref(self._m)))
+
+    def _take(self, fn):
+        while True:
+            buf = (AmPeak * self._cap)()
+            idx = (C.c_uint32 * self._cap)()
+            n = C.c_size_t(0)
+            rc = fn(self._m, buf, idx, self._cap, C.byref(n))
+            if rc == AM_ERR_CAPACITY:
+                self._cap = max(2 * self._cap, n.value)
+                continue
+            _check(rc)
+            return list(zip(idx[:n.value], _peaks(buf, n.value)))
+
+    def push(self, samples):
+        a = np.ascontiguousarray(samples, dtype=np.float32 if self.fmt == Fmt.F32_MONO else np.int16)
+        n = a.size if self.fmt == Fmt.F32_MONO else a.size // 2
+        _check(lib().am_monitor_push(self._m, a.ctypes.data, n))
+        return self.poll()
+
+    def poll(self):
+        return self._take(lib().am_monitor_poll)
+
+    def end(self):
+        return self._take(lib().am_monitor_end)
+
+    def info(self) -> MonitorInfo:
+        i = AmMonitorInfo()
+        _check(lib().am_monitor_info_get(self._m, C.byref(i)))
+        return MonitorInfo(i.received, i.horizon, i.resident_bytes, i.pending)
+
+    def close(self):
+        if getattr(self, "_m", None):
+            lib().am_monitor_destroy(self._m)
+            self._m = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 def shard_plan(n_items: int, n_shards: int, shard: int):

@@ -196,6 +196,18 @@ extern "C" {
     pub fn am_match_stream_push(st: *mut AmStream, samples: *const std::ffi::c_void, n: usize) -> c_int;
     pub fn am_match_stream_finish(st: *mut AmStream, out: *mut AmPeak, cap: usize, n_out: *mut usize) -> c_int;
     pub fn am_match_stream_destroy(st: *mut AmStream);
+    /// live monitoring: the finality rule of the overshadow filter (audio_matcher.rs:143-160) and the monitor over an
+    /// unbounded sample source (matcher/mod.rs:42-99)
+    pub fn am_merge_ready(p: *const AmMatchParams, sorted: *const AmPeak, n: usize, horizon: u64, ended: c_int, n_ready: *mut usize) -> c_int;
+    pub fn am_monitor_begin(
+        needles: *const *const AmNeedle, n_needles: usize, params: *const AmMatchParams, sample_format: c_int, group_windows: usize,
+        out: *mut *mut AmMonitor,
+    ) -> c_int;
+    pub fn am_monitor_push(m: *mut AmMonitor, samples: *const std::ffi::c_void, n: usize) -> c_int;
+    pub fn am_monitor_poll(m: *mut AmMonitor, out: *mut AmPeak, needle: *mut u32, cap: usize, n_out: *mut usize) -> c_int;
+    pub fn am_monitor_end(m: *mut AmMonitor, out: *mut AmPeak, needle: *mut u32, cap: usize, n_out: *mut usize) -> c_int;
+    pub fn am_monitor_info_get(m: *const AmMonitor, info: *mut AmMonitorInfo) -> c_int;
+    pub fn am_monitor_destroy(m: *mut AmMonitor);
 }
 
 pub const AM_FMT_F32_MONO: c_int = 0;
@@ -209,6 +221,21 @@ pub const AM_OPT_SCORE_NORM_FLOOR_DB: &str = "score_norm_floor_db";
 #[repr(C)]
 pub struct AmStream {
     _private: [u8; 0],
+}
+
+#[repr(C)]
+pub struct AmMonitor {
+    _private: [u8; 0],
+}
+
+/// am_monitor_info
+#[repr(C)]
+#[derive(Clone, Copy, Default, Debug)]
+pub struct AmMonitorInfo {
+    pub received: u64,
+    pub horizon: u64,
+    pub resident_bytes: u64,
+    pub pending: u64,
 }
 
 #[repr(C)]
@@ -520,5 +547,80 @@ impl HipConvolve {
         if rc != AM_OK { return Err(am_err(rc)); }
         buf.truncate(n);
         Ok(buf)
+    }
+}
+
+/// Live monitoring over a sample source that may never end: `LiveHits` pulls samples from `I` in blocks of `block`,
+/// pushes them through one monitor and yields `(needle, peak)` as soon as each hit is final (by start, then needle);
+/// at the end of `I` it yields the rest.  Each needle's hits, concatenated, equal calc_chunks on the whole recording
+/// (offsets exactly, values to f32 rounding), merged as the reference merges (audio_matcher.rs:132-160).
+pub struct LiveHits<'a, I: Iterator<Item = f32>> {
+    m: *mut AmMonitor,
+    src: I,
+    block: Vec<f32>,
+    ready: std::collections::VecDeque<(u32, AmPeak)>,
+    done: bool,
+    _needles: std::marker::PhantomData<&'a HipConvolve>,
+}
+
+impl<'a, I: Iterator<Item = f32>> LiveHits<'a, I> {
+    pub fn new(needles: &[&'a HipConvolve], params: &[AmMatchParams], group_windows: usize, block: usize, src: I)
+        -> Result<Self, Box<dyn std::error::Error>> {
+        if needles.len() != params.len() { return Err("one AmMatchParams per needle".into()); }
+        let hs: Vec<*const AmNeedle> = needles.iter().map(|n| n.h as *const AmNeedle).collect();
+        let mut m = std::ptr::null_mut();
+        let rc = unsafe { am_monitor_begin(hs.as_ptr(), hs.len(), params.as_ptr(), AM_FMT_F32_MONO, group_windows, &mut m) };
+        if rc != AM_OK { return Err(am_err(rc)); }
+        Ok(Self { m, src, block: Vec::with_capacity(block.max(1)), ready: Default::default(), done: false,
+                  _needles: std::marker::PhantomData })
+    }
+
+    pub fn info(&self) -> Result<AmMonitorInfo, Box<dyn std::error::Error>> {
+        let mut i = AmMonitorInfo::default();
+        let rc = unsafe { am_monitor_info_get(self.m, &mut i) };
+        if rc != AM_OK { return Err(am_err(rc)); }
+        Ok(i)
+    }
+
+    fn take(&mut self, end: bool) -> c_int {
+        let mut cap = 64usize;
+        loop {
+            let mut buf = vec![AmPeak::default(); cap];
+            let mut idx = vec![0u32; cap];
+            let mut n = 0usize;
+            let rc = unsafe {
+                if end { am_monitor_end(self.m, buf.as_mut_ptr(), idx.as_mut_ptr(), cap, &mut n) }
+                else { am_monitor_poll(self.m, buf.as_mut_ptr(), idx.as_mut_ptr(), cap, &mut n) }
+            };
+            if rc == AM_ERR_CAPACITY { cap = n; continue; }
+            if rc == AM_OK { self.ready.extend(idx[..n].iter().copied().zip(buf[..n].iter().copied())); }
+            return rc;
+        }
+    }
+}
+
+impl<'a, I: Iterator<Item = f32>> Iterator for LiveHits<'a, I> {
+    type Item = Result<(u32, AmPeak), Box<dyn std::error::Error>>;
+    fn next(&mut self) -> Option<Self::Item> {
+        loop {
+            if let Some(h) = self.ready.pop_front() { return Some(Ok(h)); }
+            if self.done { return None; }
+            self.block.clear();
+            while self.block.len() < self.block.capacity() {
+                match self.src.next() { Some(x) => self.block.push(x), None => break }
+            }
+            let end = self.block.len() < self.block.capacity();
+            let mut rc = AM_OK;
+            if !self.block.is_empty() { rc = unsafe { am_monitor_push(self.m, self.block.as_ptr().cast(), self.block.len()) }; }
+            if rc == AM_OK { rc = self.take(end); }
+            if end { self.done = true; }
+            if rc != AM_OK { self.done = true; return Some(Err(am_err(rc))); }
+        }
+    }
+}
+
+impl<'a, I: Iterator<Item = f32>> Drop for LiveHits<'a, I> {
+    fn drop(&mut self) {
+        unsafe { am_monitor_destroy(self.m) }
     }
 }

@@ -479,6 +479,60 @@ int am_pool_match_long(am_pool* pool, const void* haystack, size_t len, int samp
 int am_pool_match_long_device(am_pool* pool, const void* const* d_parts, size_t len, int sample_format, const am_match_params* p,
                               am_peak* out, size_t cap, size_t* n_out);
 
+/* ---- live monitoring: final hits while the audio arrives ----------------------------- */
+/* The overshadow filter (is_overshadowed, audio_matcher.rs:143-160) looks at an element's two neighbours in start
+ * order only, so a peak's fate is settled once its successor is known, or once no later peak can come within the
+ * overshadow distance.  am_merge_ready is that rule as a pure host function.  Given the UNFILTERED peaks of a
+ * recording sorted by start (stable, window order on ties) as am_merge_peaks sorts them, of which every peak with
+ * start < horizon is present and none with start >= horizon is, *n_ready = the length of the longest prefix whose
+ * fate under am_merge_peaks (kept or overshadowed) can no longer change, whatever peaks with start >= horizon are
+ * still to come: every peak but the last, and the last too when its predecessor (option "surrounding_from" = 1: the
+ * last peak kept) overshadows it or when a peak at `horizon` with +inf prominence could not.  ended != 0: nothing
+ * more comes, *n_ready = n.  A list not sorted by start, or (ended == 0) a peak at or after horizon: AM_ERR_INVALID_ARG. */
+int am_merge_ready(const am_match_params* p, const am_peak* sorted, size_t n, uint64_t horizon, int ended, size_t* n_ready);
+
+/* A monitor watches an unbounded recording (a live feed) for n_needles >= 1 needles on ONE device, params[j] for
+ * needle j (sr equal for all; chunk and overlap may differ), samples in sample_format (AM_FMT_F32_MONO or
+ * AM_FMT_S16_STEREO).  The windows are those of calc_chunks (chunked(chunk + overlap, hop = chunk),
+ * audio_matcher.rs:104; the lazy sample source of matcher/mod.rs:42-99): group g is windows [g G, g G + G),
+ * G = group_windows (0 means 1), matched as one part (am_match_part_device: n_samples the group's span, first_sample
+ * g G chunk) as soon as its last window's samples have arrived.  What am_monitor_poll and am_monitor_end return for
+ * needle j, concatenated, equals am_merge_peaks over those parts bit for bit, for every way the samples are split
+ * into pushes; offsets and plateau ends equal am_match on the whole recording, heights and prominences agree to f32
+ * rounding (a part's overlap-save blocks start at the part).
+ *
+ * Latency: a peak is returned by the first poll after it is final under am_merge_ready with horizon g G chunk, g the
+ * needle's first group not yet matched -- once the group holding its successor is matched, or the one that takes
+ * the horizon the overshadow distance past it.  A returned peak is never revised.
+ * Memory: the samples live in one device buffer of fixed size, 4 x (2 x the largest group span + 65536) bytes
+ * (span = (G - 1) chunk + chunk + overlap); samples before the earliest horizon are dropped (a device-to-device copy
+ * on the library's stream).  A push of any size is consumed in steps.
+ * Options are read once, at am_monitor_begin (each needle with its handle's overrides): "half_pipeline",
+ * "peak_filter_order", "distance_rule", "tail_window", "surrounding_from", "log_n", the non-finite redo path and
+ * AM_SCALE_MY behave as for am_match_part_device.  "score_norm" is refused (AM_ERR_INVALID_ARG, "score_norm: not
+ * supported by this entry point").  One producer per monitor; monitors of one device share its queue.
+ *
+ * push: n samples / frames from host memory; a piece is copied into a pinned staging slot and push returns without
+ * waiting for the device unless the piece completes a group (which is then matched).  poll: the peaks that became
+ * final since the last poll, of all needles, sorted by (start, needle); needle[i] (may be null) = the needle of
+ * out[i].  end: end of input -- the remaining groups are matched (the windows at the end as make_segments cuts
+ * them, option "tail_window") and every peak not yet returned comes back; after end, push is refused and end / poll
+ * return what is left.  poll / end with cap too small: AM_ERR_CAPACITY, *n_out = the count, nothing is consumed. */
+typedef struct am_monitor am_monitor;
+int am_monitor_begin(const am_needle* const* needles, size_t n_needles, const am_match_params* params, int sample_format,
+                     size_t group_windows, am_monitor** out);
+int am_monitor_push(am_monitor* m, const void* samples, size_t n);
+int am_monitor_poll(am_monitor* m, am_peak* out, uint32_t* needle, size_t cap, size_t* n_out);
+int am_monitor_end(am_monitor* m, am_peak* out, uint32_t* needle, size_t cap, size_t* n_out);
+typedef struct am_monitor_info {
+    uint64_t received;        /* samples / frames pushed so far */
+    uint64_t horizon;         /* every window before this sample has been matched (all needles) */
+    uint64_t resident_bytes;  /* device bytes the monitor owns (its sample buffer); fixed at begin */
+    uint64_t pending;         /* peaks found but not yet final */
+} am_monitor_info;
+int am_monitor_info_get(const am_monitor* m, am_monitor_info* info);
+void am_monitor_destroy(am_monitor* m);
+
 /* ---- progress hooks ---------------------------------------------------------- */
 /* The two-stage progress callbacks of calc_chunks (audio_matcher.rs:102-117, 129:
  * f1 when a chunk is picked up, f2 when it is done).

@@ -410,4 +410,64 @@ private:
     std::size_t nn_ = 0;
 };
 
+// Live monitoring (am_monitor_*): the final hits of one or several needles while an unbounded recording arrives
+// (calc_chunks over a lazy sample source, audio_matcher.rs:88-141 / matcher/mod.rs:42-99), in bounded device memory.
+struct MonitorHit {
+    std::uint32_t needle = 0;
+    Peak peak;
+};
+class HipMonitor {
+public:
+    // params[j] for needles[j]; sample_format AM_FMT_*; group_windows 0 means 1
+    HipMonitor(const std::vector<const HipConvolve*>& needles, const std::vector<am_match_params>& params,
+               int sample_format = AM_FMT_F32_MONO, std::size_t group_windows = 1) {
+        std::vector<const am_needle*> hs;
+        for (const HipConvolve* n : needles) hs.push_back(n->handle());
+        if (params.size() != hs.size()) throw Error(AM_ERR_INVALID_ARG, "audiomatch: one am_match_params per needle");
+        check(am_monitor_begin(hs.data(), hs.size(), params.data(), sample_format, group_windows, &m_));
+    }
+    HipMonitor(const HipMonitor&) = delete;
+    HipMonitor& operator=(const HipMonitor&) = delete;
+    HipMonitor(HipMonitor&& o) noexcept : m_(std::exchange(o.m_, nullptr)) {}
+    ~HipMonitor() { am_monitor_destroy(m_); }
+    // n samples / frames from host memory; returns the hits that became final, by (start, needle)
+    std::vector<MonitorHit> push(const void* samples, std::size_t n) {
+        check(am_monitor_push(m_, samples, n));
+        return take(am_monitor_poll);
+    }
+    std::vector<MonitorHit> poll() { return take(am_monitor_poll); }
+    // end of input: every hit not yet returned
+    std::vector<MonitorHit> end() { return take(am_monitor_end); }
+    am_monitor_info info() const {
+        am_monitor_info i{};
+        check(am_monitor_info_get(m_, &i));
+        return i;
+    }
+    // am_merge_ready: how many of `sorted` are final, whatever peaks at or after `horizon` follow
+    static std::size_t merge_ready(const am_match_params& p, const std::vector<am_peak>& sorted, std::uint64_t horizon, bool ended) {
+        std::size_t n = 0;
+        check(am_merge_ready(&p, sorted.data(), sorted.size(), horizon, ended ? 1 : 0, &n));
+        return n;
+    }
+
+private:
+    std::vector<MonitorHit> take(int (*fn)(am_monitor*, am_peak*, std::uint32_t*, std::size_t, std::size_t*)) {
+        std::size_t n = 0;
+        int rc = fn(m_, buf_.data(), idx_.data(), buf_.size(), &n);
+        if (rc == AM_ERR_CAPACITY) {
+            buf_.resize(n); idx_.resize(n);
+            rc = fn(m_, buf_.data(), idx_.data(), buf_.size(), &n);
+        }
+        check(rc);
+        std::vector<MonitorHit> out;
+        for (std::size_t i = 0; i < n; ++i)
+            out.push_back(MonitorHit{idx_[i], Peak{static_cast<std::size_t>(buf_[i].start), static_cast<std::size_t>(buf_[i].end),
+                                                   buf_[i].height, buf_[i].prominence}});
+        return out;
+    }
+    am_monitor* m_ = nullptr;
+    std::vector<am_peak> buf_ = std::vector<am_peak>(64);
+    std::vector<std::uint32_t> idx_ = std::vector<std::uint32_t>(64);
+};
+
 }  // namespace audiomatch
