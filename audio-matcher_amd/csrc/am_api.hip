@@ -32,9 +32,9 @@ int am::find_peaks_host_array(Ctx* c, const float* d_scores, long long n, float 
     Segment sg; sg.a = 0; sg.b = n;
     PeakArena arena{};
     if ((rc = prepare_results(c, 1, AM_MAX_PEAKS_PER_CHUNK, &arena))) return rc;
-    if ((rc = c->peaks.ensure(sizeof(am_peak) * AM_MAX_PEAKS_PER_CHUNK))) return rc;
+    if ((rc = c->side[0].peaks.ensure(sizeof(am_peak) * AM_MAX_PEAKS_PER_CHUNK))) return rc;
     if ((rc = upload_segments(c, std::vector<Segment>(1, sg)))) return rc;
-    if ((rc = launch_pick(c, d_scores, n, 0, 1, min_prom, min_dist, nullptr, 0, arena, pol))) return rc;
+    if ((rc = launch_pick(c, c->side[0], d_scores, n, 0, 1, min_prom, min_dist, nullptr, nullptr, 0, arena, pol))) return rc;
     AM_HIP(hipStreamSynchronize(c->stream));
     const SegHeader hd = *static_cast<const SegHeader*>(c->hdr.p);
     all.clear();

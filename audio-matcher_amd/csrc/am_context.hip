@@ -328,7 +328,8 @@ static int needle_spectrum(am_needle* h, const Plan* pl, const float2** out) {
     if (it != h->spectra.end()) { *out = it->second; return AM_OK; }
     const size_t N = (size_t)1 << pl->dev.logN;
     if (c->stream2) (void)hipStreamSynchronize(c->stream2);   // (a device-side redo may still read the work matrix)
-    int rc = c->work.ensure(std::max<size_t>(N * sizeof(float2), c->work.cap));
+    DevBuf& work = c->side[0].work;
+    int rc = work.ensure(std::max<size_t>(N * sizeof(float2), work.cap));
     if (rc) return rc;
     float2* hc = nullptr;
     AM_HIP(hipMalloc((void**)&hc, N * sizeof(float2)));
@@ -338,8 +339,8 @@ static int needle_spectrum(am_needle* h, const Plan* pl, const float2** out) {
     hipError_t e;
     {
         ProfScope ps(c, KN_OTHER);
-        e = launch_k1(c->stream, job, 1, (float2*)c->work.p, pl->dev);
-        if (e == hipSuccess) e = launch_k2_spectrum(c->stream, (float2*)c->work.p, hc, pl->dev);
+        e = launch_k1(c->stream, job, 1, (float2*)work.p, pl->dev);
+        if (e == hipSuccess) e = launch_k2_spectrum(c->stream, (float2*)work.p, hc, pl->dev);
     }
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
     if (e != hipSuccess) { (void)hipFree(hc); return hip_fail(e, "needle spectrum"); }
@@ -503,9 +504,10 @@ int am_shutdown(void) {
         (void)hipStreamSynchronize(c->stream);
         if (c->stream2) (void)hipStreamSynchronize(c->stream2);
         if (c->stream_tail) (void)hipStreamSynchronize(c->stream_tail);
-        for (DevBuf* b : {&c->work, &c->work2, &c->scores, &c->stats, &c->stats32, &c->wflags, &c->segs,
-                          &c->scores_b, &c->stats_b, &c->stats32_b, &c->wflags_b, &c->peaks_b, &c->work_b, &c->redo_pairs[0], &c->redo_pairs[1],
-                          &c->peaks, &c->io_in, &c->io_out, &c->sum, &c->arena_cur, &c->wide_ctl, &c->wide_list, &c->wide_tiles})
+        for (ScoreSide& sd : c->side)
+            for (DevBuf* b : {&sd.scores, &sd.stats, &sd.stats32, &sd.wflags, &sd.peaks, &sd.work}) b->release();
+        for (DevBuf* b : {&c->work2, &c->segs, &c->redo_pairs[0], &c->redo_pairs[1],
+                          &c->io_in, &c->io_out, &c->sum, &c->arena_cur, &c->wide_ctl, &c->wide_list, &c->wide_tiles})
             b->release();
         for (HostBuf* b : {&c->pinned, &c->hdr, &c->spill, &c->badflag, &c->failcnt}) b->release();
         c->ranges.release(); c->range_flags.release(); c->big.release(); c->norm_blk.release();
@@ -515,7 +517,8 @@ int am_shutdown(void) {
         for (auto& kv : c->rs_taps) kv.second.release();
         c->rs_taps.clear();
         c->work_tail.release(); c->tail_scores.release(); c->tail_stats.release(); c->work_tail2.release();
-        for (int i = 0; i < 2 * kMaxNeedleGroup; ++i) { c->grp_scores[i].release(); c->grp_stats32[i].release(); c->grp_wflags[i].release(); }
+        for (int set = 0; set < 2; ++set)
+            for (int i = 0; i < kMaxNeedleGroup; ++i) { c->grp_scores[set][i].release(); c->grp_stats32[set][i].release(); c->grp_wflags[set][i].release(); }
         for (int i = 0; i < kMaxNeedleGroup; ++i) c->grp_stats[i].release();
         c->segs_resident.clear();
         for (auto& pk : c->plans) { if (pk.second.tables) (void)hipFree(pk.second.tables); if (pk.second.mf) (void)hipFree(pk.second.mf); }

@@ -1,5 +1,5 @@
-// am_correlate.hip -- the overlap-save pass over one haystack: plan geometry, the odd last block (TailPlan), the
-// passes themselves (run_correlation), what a batch must size for them, and the peak pick's launches and merge.
+// am_correlate.hip -- the overlap-save pass over one haystack: which path it takes (pass_plan: plan geometry, fused scan,
+// the odd last block, what a batch must size), the passes themselves (run_correlation), the peak pick's launches and merge.
 // Host-side mirror of the reference's driver (paths relative to the reference):
 //   calc_chunks            src/matcher/audio_matcher.rs:88-141
 //   is_overshadowed        src/matcher/audio_matcher.rs:143-160
@@ -90,10 +90,10 @@ bool tail_plan(size_t s, long long out_count, const Opts& o, const Geometry& g, 
 // block, column tile and wavefront: which of the tile's runs were written), then the write
 // thresholds K3 used, one float per (block, column tile).
 static size_t sparse_word_bytes(long long nblocks, const PlanDev& pl) {
-    return sizeof(unsigned long long) * (((size_t)nblocks << (pl.logN2 - kColsLog)) << (pl.logN1 - 6));
+    return sizeof(unsigned long long) * (size_t)nblocks * ballot_layout(pl.logN1, pl.logN2).words;
 }
 size_t sparse_bytes(long long nblocks, const PlanDev& pl) {
-    return sparse_word_bytes(nblocks, pl) + sizeof(float) * ((size_t)nblocks << (pl.logN2 - kColsLog));
+    return sparse_word_bytes(nblocks, pl) + sizeof(float) * (size_t)nblocks * ballot_layout(pl.logN1, pl.logN2).tiles;
 }
 void fill_scan_cfg(ScanCfg* cfg, void* stats32, void* side, long long nblocks, const PlanDev& pl, float margin, float hist_min,
                           long long seg_c, long long seg_d) {
@@ -114,8 +114,8 @@ SparseScores sparse_view(const ScanCfg& cfg, long long hop, const PlanDev& pl) {
 bool needle_is_segmented(const am_needle* h, const Opts& o) {
     return (long long)h->n > kSegmentFrom && o.log_n == 0;
 }
-static int needle_segments(am_needle* h) {
-    if (!h->segments.empty()) return AM_OK;
+static void needle_segments(am_needle* h) {
+    if (!h->segments.empty()) return;
     const long long n = (long long)h->n;
     const long long nseg = (n + kSegmentLen - 1) / kSegmentLen;
     for (long long i = 0; i < nseg; ++i) {
@@ -126,139 +126,155 @@ static int needle_segments(am_needle* h) {
         h->segments.push_back(sub);
         h->seg_off.push_back(a);
     }
+}
+
+bool plan_fuses_scan(const PlanDev& pl, const Geometry& g) { return plan_has_scan(pl) && (g.hop % kTile) == 0; }
+
+int pass_plan(am_needle* h, const Opts& o, long long out_count, bool allow_tail, PassPlan* pp) {
+    Ctx* c = h->ctx;
+    *pp = PassPlan{};
+    int rc;
+    if (needle_is_segmented(h, o)) {
+        // one pass per needle segment, K3 adding up the partial sums: plain scores, no summary, no flags, no tail
+        pp->kind = PassKind::Partitioned;
+        needle_segments(h);
+        Opts os = o;
+        os.half = 0;   // (the accumulating K3 exists for the f32 work matrix)
+        pp->parts.resize(h->segments.size());
+        for (size_t i = 0; i < pp->parts.size(); ++i) {
+            if ((rc = pass_plan(h->segments[i], os, out_count, false, &pp->parts[i]))) return rc;
+            pp->need.work = std::max(pp->need.work, pp->parts[i].need.work);
+        }
+        return AM_OK;
+    }
+    if (h->n <= (size_t)kDirectMaxNeedle && o.log_n == 0) return AM_OK;   // tiny needle: direct summation, no blocks, no scratch
+    pp->kind = PassKind::Transform;
+    Geometry& g = pp->g;
+    if ((rc = plan_geometry(h->n, out_count, o, &g))) return rc;
+    if ((rc = get_plan(c, g.logN, &pp->pl))) return rc;
+    if ((rc = needle_k2_spectrum(h, o, pp->pl, &pp->hc, &pp->hs))) return rc;
+    pp->fused = plan_fuses_scan(pp->pl->dev, g);
+    // the tail runs on a stream of its own beside the main pass (or, in a batch, is committed in front of the pick)
+    if (allow_tail && pp->fused && c->stream_tail && c->ev_fork && c->ev_join && tail_plan(h->n, out_count, o, g, &pp->tail)) {
+        if ((rc = get_plan(c, pp->tail.g.logN, &pp->tail_pl))) return rc;
+        if ((rc = needle_k2_spectrum(h, o, pp->tail_pl, &pp->tail_hc, &pp->tail_hs))) return rc;
+        pp->need.work_tail = (size_t)pp->tail.g.N * sizeof(float2);
+    }
+    pp->nblocks = pp->tail.on ? g.nblocks - 1 : g.nblocks;
+    pp->npairs = pp->tail.on ? g.npairs - 1 : g.npairs;
+    pp->main_count = pp->tail.on ? pp->tail.T : out_count;
+    pp->ppg = std::min(std::max<long long>(1, o.pairs_per_group), pp->npairs);
+    pp->need.work = (size_t)pp->ppg * (size_t)g.N * sizeof(float2);
+    pp->need.npairs = g.npairs;
+    if (pp->fused) {
+        pp->need.stats32 = (size_t)((out_count + 31) / 32) * sizeof(float2);
+        pp->need.side = sparse_bytes(g.nblocks, pp->pl->dev);
+    }
     return AM_OK;
 }
 
-static int run_correlation_one(am_needle* h, const Opts& o, const void* d_src, long long src_len, long long lead,
-                               float* d_dst, long long out_count, float factor,
-                               ScanRequest* scan_req, int src_kind, bool accumulate);
-
 // The scores [tail.T, out_count) of a haystack on the smaller plan (TailPlan), queued on the context's tail stream:
 // one block pair through K1 / K2 / K3 with every run written and the level-0 summary at its place in the main
-// pass's stats32; then block `main_nblocks - 1` of the MAIN layout is marked "every run written, threshold -inf".
-static int run_tail_block(am_needle* h, const Opts& o, const TailPlan& tail, const void* d_src, long long src_len,
-                          float* d_dst, long long out_count, float factor, const ScanCfg& main_scan, const PlanDev& main_pl,
-                          long long main_nblocks, int src_kind) {
-    Ctx* c = h->ctx;
+// pass's stats32; then the last block of the MAIN layout is marked "every run written, threshold -inf".
+static int run_tail_block(Ctx* c, const PassPlan& pp, const void* d_src, long long src_len,
+                          float* d_dst, long long out_count, float factor, const ScanCfg& main_scan, int src_kind) {
     hipStream_t st = c->stream_tail;
+    const TailPlan& tail = pp.tail;
+    const PlanDev& pl = pp.tail_pl->dev;
+    const HalfScale& hs = pp.tail_hs;
     int rc;
-    const Plan* pl = nullptr;
-    if ((rc = get_plan(c, tail.g.logN, &pl))) return rc;
-    const float2* hc = nullptr;
-    HalfScale hs;
-    if ((rc = needle_k2_spectrum(h, o, pl, &hc, &hs))) return rc;
-    if ((rc = c->work_tail.ensure((size_t)tail.g.N * sizeof(float2)))) return rc;
+    if ((rc = c->work_tail.ensure(pp.need.work_tail))) return rc;
     Job job = tail_job(tail, d_src, src_len, out_count, src_kind);
     job.dst = d_dst + tail.T;
     ScanCfg scan{};
     scan.stats32 = main_scan.stats32 ? main_scan.stats32 + tail.T / 32 : nullptr;
     scan.margin = -1.0f; scan.hist_min = FLT_MAX;
     // (profiled as "other": the three classes' figures stay those of the main pass's launches)
-    { ProfScope ps(c, KN_OTHER, st); AM_HIP(launch_k1(st, job, 1, (float2*)c->work_tail.p, pl->dev, hs.level)); }
-    { ProfScope ps(c, KN_OTHER, st); AM_HIP(launch_k2(st, 1, (float2*)c->work_tail.p, hc, pl->dev, nullptr, hs.level, hs.hscale, hs.pre, true)); }
-    { ProfScope ps(c, KN_OTHER, st); AM_HIP(launch_k3(st, job, 1, (const float2*)c->work_tail.p, pl->dev, hs.k3(factor), scan, hs.level, false)); }
+    { ProfScope ps(c, KN_OTHER, st); AM_HIP(launch_k1(st, job, 1, (float2*)c->work_tail.p, pl, hs.level)); }
+    { ProfScope ps(c, KN_OTHER, st); AM_HIP(launch_k2(st, 1, (float2*)c->work_tail.p, pp.tail_hc, pl, nullptr, hs.level, hs.hscale, hs.pre, true)); }
+    { ProfScope ps(c, KN_OTHER, st); AM_HIP(launch_k3(st, job, 1, (const float2*)c->work_tail.p, pl, hs.k3(factor), scan, hs.level, false)); }
     if (main_scan.stats32 && main_scan.margin >= 0.0f && main_scan.wbits && main_scan.tile_theta) {
-        const size_t tiles = (size_t)1 << (main_pl.logN2 - kColsLog), words = tiles << (main_pl.logN1 - 6);
-        const size_t blk = (size_t)(main_nblocks - 1);
-        AM_HIP(hipMemsetAsync(main_scan.wbits + blk * words, 0xFF, words * sizeof(unsigned long long), st));
-        AM_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(main_scan.tile_theta + blk * tiles), (int)0xFF7FFFFFu, tiles, st));   // -FLT_MAX
+        const BallotLayout bl = ballot_layout(pp.pl->dev.logN1, pp.pl->dev.logN2);
+        const size_t blk = (size_t)(pp.g.nblocks - 1);
+        AM_HIP(hipMemsetAsync(main_scan.wbits + blk * bl.words, 0xFF, bl.words * sizeof(unsigned long long), st));
+        AM_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(main_scan.tile_theta + blk * bl.tiles), (int)0xFF7FFFFFu, bl.tiles, st));   // -FLT_MAX
     }
     return AM_OK;
 }
+
+static int run_correlation_one(am_needle* h, const PassPlan& pp, const void* d_src, long long src_len, long long lead,
+                               float* d_dst, long long out_count, float factor,
+                               const ScanRequest* scan_req, ScanResult* res, int src_kind, bool accumulate);
 
 // The overlap-save engine for any needle length: one pass, or one pass per needle segment with the
 // source shifted by the segment's offset and K3 adding up the partial sums (plain scores, every one
 // written; the peak pick summarises them with tile_stats instead of the fused scan).
 int run_correlation(am_needle* h, const Opts& o, const void* d_src, long long src_len, long long lead,
                            float* d_dst, long long out_count, float factor,
-                           ScanRequest* scan_req, int src_kind) {
-    if (!needle_is_segmented(h, o)) return run_correlation_one(h, o, d_src, src_len, lead, d_dst, out_count, factor, scan_req, src_kind, false);
-    int rc = needle_segments(h);
-    if (rc) return rc;
+                           const ScanRequest* scan_req, ScanResult* res, int src_kind, const PassPlan* plan) {
+    int rc;
+    PassPlan own;
+    if (!plan) {
+        if ((rc = pass_plan(h, o, out_count, scan_req && !scan_req->no_scan && lead == 0, &own))) return rc;
+        plan = &own;
+    }
+    if (res) { res->fused = false; res->redo_ok = false; res->sparse = plain_scores(); }
+    if (plan->kind != PassKind::Partitioned) return run_correlation_one(h, *plan, d_src, src_len, lead, d_dst, out_count, factor, scan_req, res, src_kind, false);
     if (scan_req && scan_req->skip_launch) return fail(AM_ERR_INVALID_ARG, "internal: streaming ingest does not run early pairs for partitioned needles");
-    Opts os = o;
-    os.half = 0;   // (the accumulating K3 exists for the f32 work matrix)
-    const size_t nseg = h->segments.size();
-    for (size_t i = 0; i < nseg; ++i) {
+    for (size_t i = 0; i < plan->parts.size(); ++i) {
         // every pass writes (i = 0) or adds (i > 0) plain scores; a pass still honours the restriction to the
         // blocks of one chunk, and the first one may not touch the score buffer before the pick that last
         // read it is done
         ScanRequest plain{};
-        ScanRequest* sr = nullptr;
         if (scan_req) {
             plain.margin = -1.0f; plain.range_a = scan_req->range_a; plain.range_b = scan_req->range_b;
             plain.before_k3 = i == 0 ? scan_req->before_k3 : nullptr;
             plain.no_scan = true;
-            sr = &plain;
         }
-        if ((rc = run_correlation_one(h->segments[i], os, d_src, src_len, lead - h->seg_off[i], d_dst, out_count, factor, sr, src_kind, i > 0)))
+        if ((rc = run_correlation_one(h->segments[i], plan->parts[i], d_src, src_len, lead - h->seg_off[i], d_dst, out_count, factor,
+                                      scan_req ? &plain : nullptr, nullptr, src_kind, i > 0)))
             return rc;
-    }
-    if (scan_req) {   // the sums are complete scores without a level-0 summary: the pick summarises them itself (tile_stats)
-        scan_req->fused = false;
-        scan_req->sparse = SparseScores{nullptr, nullptr, nullptr, 1, 5, 5, 1.0};
     }
     return AM_OK;
 }
 
-static int run_correlation_one(am_needle* h, const Opts& o, const void* d_src, long long src_len, long long lead,
+static int run_correlation_one(am_needle* h, const PassPlan& pp, const void* d_src, long long src_len, long long lead,
                                float* d_dst, long long out_count, float factor,
-                               ScanRequest* scan_req, int src_kind, bool accumulate) {
+                               const ScanRequest* scan_req, ScanResult* res, int src_kind, bool accumulate) {
     Ctx* c = h->ctx;
-    if (h->n <= (size_t)kDirectMaxNeedle && o.log_n == 0) {
-        // tiny needle: direct summation, every score written, no fused scan
-        if (scan_req) {
-            scan_req->fused = false;
-            scan_req->sparse = SparseScores{nullptr, nullptr, nullptr, 1, 5, 5, 1.0};
-        }
-        Job job{};
-        job.src = d_src; job.src_len = src_len; job.lead = lead; job.src_kind = src_kind;
-        job.dst = d_dst; job.out_count = out_count;
+    Job job{};
+    job.src = d_src; job.src_len = src_len; job.lead = lead; job.src_kind = src_kind;
+    job.dst = d_dst; job.out_count = out_count;
+    if (pp.kind == PassKind::Direct) {   // every score written, no fused scan
         ProfScope ps(c, KN_OTHER);
         AM_HIP(launch_direct(c->stream, job, h->d_needle, (int)h->n, factor));
         return AM_OK;
     }
-    Geometry g{};
-    int rc = plan_geometry(h->n, out_count, o, &g);
-    if (rc) return rc;
-    const Plan* pl = nullptr;
-    if ((rc = get_plan(c, g.logN, &pl))) return rc;
-    const float2* hc = nullptr;
-    HalfScale hs;
-    if ((rc = needle_k2_spectrum(h, o, pl, &hc, &hs))) return rc;
-    const long long N = g.N, hop = g.hop, nblocks = g.nblocks;
-    // (streaming ingest launches its pairs itself, under the layout of the announced length: no tail there)
-    TailPlan tail{};
-    if (scan_req && !scan_req->no_scan && !accumulate && lead == 0 && !scan_req->ext_stats32 && !scan_req->ext_side &&
-        !scan_req->skip_launch && scan_req->side_nblocks == 0 && plan_has_scan(pl->dev) && c->stream_tail && c->ev_fork && c->ev_join)
-        tail_plan(h->n, out_count, o, g, &tail);
-    const long long npairs = tail.on ? g.npairs - 1 : g.npairs;   // block pairs of the main pass
-    long long ppg = std::max<long long>(1, o.pairs_per_group);
-    if (ppg > npairs) ppg = npairs;
-    DevBuf& wk = (scan_req && scan_req->work_by_set && scan_req->set) ? c->work_b : c->work;
+    int rc;
+    const PlanDev& pl = pp.pl->dev;
+    const HalfScale& hs = pp.hs;
+    const TailPlan& tail = pp.tail;
+    const long long N = pp.g.N, hop = pp.g.hop, npairs = pp.npairs, ppg = pp.ppg;
+    const ScanBuffers out = (scan_req && scan_req->out.work) ? scan_req->out : scan_buffers(c->side[0]);
+    DevBuf& wk = *out.work;
     if ((rc = wk.ensure((size_t)ppg * (size_t)N * sizeof(float2)))) return rc;
-    if (scan_req) scan_req->redo_ok = false;
     ScanCfg scan{};
+    bool fused = false;
     if (scan_req && !scan_req->no_scan) {
-        scan_req->fused = false;
-        scan_req->sparse = SparseScores{nullptr, nullptr, nullptr, (int)hop, pl->dev.logN2, pl->dev.logN1, 1.0 / (double)hop};
-        if (plan_has_scan(pl->dev) && (hop % kTile) == 0) {
-            DevBuf& b32 = scan_req->ext_stats32 ? *scan_req->ext_stats32 : (scan_req->set ? c->stats32_b : c->stats32);
-            DevBuf& bwf = scan_req->ext_side ? *scan_req->ext_side : (scan_req->set ? c->wflags_b : c->wflags);
-            const long long side_blocks = std::max(nblocks, scan_req->side_nblocks);
-            if ((rc = b32.ensure((size_t)((out_count + 31) / 32) * sizeof(float2)))) return rc;
-            if ((rc = bwf.ensure(sparse_bytes(side_blocks, pl->dev)))) return rc;
-            fill_scan_cfg(&scan, b32.p, bwf.p, side_blocks, pl->dev, scan_req->margin, scan_req->hist_min, scan_req->seg_c, scan_req->seg_d);
-            scan_req->fused = true;
-            scan_req->sparse = sparse_view(scan, hop, pl->dev);
+        if (res) res->sparse = SparseScores{nullptr, nullptr, nullptr, (int)hop, pl.logN2, pl.logN1, 1.0 / (double)hop};
+        if (pp.fused) {
+            const long long side_blocks = std::max(pp.g.nblocks, scan_req->side_nblocks);
+            if ((rc = out.stats32->ensure((size_t)((out_count + 31) / 32) * sizeof(float2)))) return rc;
+            if ((rc = out.wflags->ensure(sparse_bytes(side_blocks, pl)))) return rc;
+            fill_scan_cfg(&scan, out.stats32->p, out.wflags->p, side_blocks, pl, scan_req->margin, scan_req->hist_min, scan_req->seg_c, scan_req->seg_d);
+            fused = true;
+            if (res) { res->fused = true; res->sparse = sparse_view(scan, hop, pl); }
         }
     }
     // half-precision storage of the work matrix: K2 normalises by the needle
     // energy (times a fixed gain) so that stored values sit mid-range in f16
     const float k3scale = hs.k3(factor);
-    Job job{};
-    job.src = d_src; job.src_len = src_len; job.lead = lead; job.src_kind = src_kind;
-    job.dst = d_dst; job.out_count = tail.on ? tail.T : out_count; job.hop = (int)hop; job.nblocks = (int)(tail.on ? nblocks - 1 : nblocks);
+    job.out_count = pp.main_count; job.hop = (int)hop; job.nblocks = (int)pp.nblocks;
     if (scan_req && scan_req->skip_launch) return AM_OK;
     long long pair_lo = 0, pair_hi = npairs;
     bool with_tail = tail.on;
@@ -273,65 +289,26 @@ static int run_correlation_one(am_needle* h, const Opts& o, const void* d_src, l
         // holds for the tail's stream too, and the main stream takes the tail back in before anything reads the scores
         AM_HIP(hipEventRecord(c->ev_fork, c->stream));
         AM_HIP(hipStreamWaitEvent(c->stream_tail, c->ev_fork, 0));
-        if ((rc = run_tail_block(h, o, tail, d_src, src_len, d_dst, out_count, factor, scan, pl->dev, nblocks, src_kind))) return rc;
+        if ((rc = run_tail_block(c, pp, d_src, src_len, d_dst, out_count, factor, scan, src_kind))) return rc;
         AM_HIP(hipEventRecord(c->ev_join, c->stream_tail));
     }
     bool waited = false;
     for (long long first = pair_lo; first < pair_hi; first += ppg) {
         const int np = (int)std::min(ppg, pair_hi - first);
         job.first_pair = (int)first;
-        { ProfScope ps(c, KN_K1); AM_HIP(launch_k1(c->stream, job, np, (float2*)wk.p, pl->dev, hs.level)); }
-        { ProfScope ps(c, KN_K2); AM_HIP(launch_k2(c->stream, np, (float2*)wk.p, hc, pl->dev, nullptr, hs.level, hs.hscale, hs.pre)); }
+        { ProfScope ps(c, KN_K1); AM_HIP(launch_k1(c->stream, job, np, (float2*)wk.p, pl, hs.level)); }
+        { ProfScope ps(c, KN_K2); AM_HIP(launch_k2(c->stream, np, (float2*)wk.p, pp.hc, pl, nullptr, hs.level, hs.hscale, hs.pre)); }
         if (!waited && scan_req && scan_req->before_k3) AM_HIP(hipStreamWaitEvent(c->stream, scan_req->before_k3, 0));
         waited = true;
-        { ProfScope ps(c, KN_K3); AM_HIP(launch_k3(c->stream, job, np, (const float2*)wk.p, pl->dev, k3scale, scan, hs.level, accumulate)); }
+        { ProfScope ps(c, KN_K3); AM_HIP(launch_k3(c->stream, job, np, (const float2*)wk.p, pl, k3scale, scan, hs.level, accumulate)); }
     }
     if (with_tail) AM_HIP(hipStreamWaitEvent(c->stream, c->ev_join, 0));
-    if (scan_req && scan_req->fused && !accumulate && pair_lo == 0 && pair_hi == npairs && npairs <= ppg) {
+    if (res && fused && !accumulate && pair_lo == 0 && pair_hi == npairs && npairs <= ppg) {
         // the whole haystack's inverse rows sit in one work matrix: K3 can run again over chosen pairs
-        scan_req->redo_ok = true;
+        res->redo_ok = true;
         job.first_pair = 0;
-        scan_req->redo_job = job; scan_req->redo_pl = pl->dev; scan_req->redo_scale = k3scale; scan_req->redo_half = hs.level;
-        scan_req->redo_npairs = (int)npairs; scan_req->redo_work = (const float2*)wk.p; scan_req->redo_cfg = scan;
-    }
-    return AM_OK;
-}
-
-int correlation_footprint(am_needle* h, const Opts& o, long long out_count, Footprint* f) {
-    if (needle_is_segmented(h, o)) {
-        int rc = needle_segments(h);
-        if (rc) return rc;
-        Opts os = o;
-        os.half = 0;
-        for (am_needle* sub : h->segments) {
-            Footprint one;
-            if ((rc = correlation_footprint(sub, os, out_count, &one))) return rc;
-            f->work = std::max(f->work, one.work);   // (plain scores: no summary, no flags)
-        }
-        return AM_OK;
-    }
-    if (h->n <= (size_t)kDirectMaxNeedle && o.log_n == 0) return AM_OK;
-    Geometry g{};
-    int rc = plan_geometry(h->n, out_count, o, &g);
-    if (rc) return rc;
-    const Plan* pl = nullptr;
-    if ((rc = get_plan(h->ctx, g.logN, &pl))) return rc;
-    const float2* hc = nullptr;
-    HalfScale hs;
-    if ((rc = needle_k2_spectrum(h, o, pl, &hc, &hs))) return rc;
-    const long long ppg = std::min(std::max<long long>(1, o.pairs_per_group), g.npairs);
-    f->work = std::max(f->work, (size_t)ppg * (size_t)g.N * sizeof(float2));
-    f->npairs = std::max(f->npairs, g.npairs);
-    if (plan_has_scan(pl->dev) && (g.hop % kTile) == 0) {
-        f->stats32 = std::max(f->stats32, (size_t)((out_count + 31) / 32) * sizeof(float2));
-        f->side = std::max(f->side, sparse_bytes(g.nblocks, pl->dev));
-        TailPlan tail{};
-        if (tail_plan(h->n, out_count, o, g, &tail)) {   // (plan and spectrum of the odd last block's transform, see run_tail_block)
-            const Plan* plt = nullptr;
-            if ((rc = get_plan(h->ctx, tail.g.logN, &plt))) return rc;
-            if ((rc = needle_k2_spectrum(h, o, plt, &hc, &hs))) return rc;
-            f->work_tail = std::max(f->work_tail, (size_t)tail.g.N * sizeof(float2));
-        }
+        res->redo_job = job; res->redo_pl = pl; res->redo_scale = k3scale; res->redo_half = hs.level;
+        res->redo_npairs = (int)npairs; res->redo_work = (const float2*)wk.p; res->redo_cfg = scan;
     }
     return AM_OK;
 }
@@ -406,47 +383,48 @@ int prepare_results(Ctx* c, size_t nhdr, size_t arena_entries, PeakArena* arena)
     return AM_OK;
 }
 
-// Launches find_peaks (audio_matcher.rs:221-230) for `nsegs` segments of a
-// resident score array; segment descriptors live at [seg_off, seg_off + nsegs) of the
-// context's segment buffer, result headers at [hdr_off, hdr_off + nsegs).
-int launch_pick(Ctx* c, const float* d_scores, long long n_scores, int seg_off, int nsegs,
-                       float min_prom, long long min_dist, const ScanRequest* scan, int hdr_off,
-                       const PeakArena& arena, const PeakPolicy& pol, hipStream_t st, bool only_failed) {
-    if (!st) st = c->stream;
-    const int set = scan ? scan->set : 0;
-    DevBuf& bstats = set ? c->stats_b : c->stats;
-    DevBuf& bpeaks = set ? c->peaks_b : c->peaks;
-    const float2* d_stats32 = (scan && scan->fused) ? scan->sparse.stats32 : nullptr;
-    const SparseScores sp = (scan && scan->fused) ? scan->sparse : SparseScores{nullptr, nullptr, nullptr, 1, 5, 5, 1.0};
-    if (nsegs == 0 || n_scores <= 0) return AM_OK;
+int wide_reserve(Ctx* c, size_t n) {
     int rc;
-    const long long ntiles = (n_scores + kTile - 1) / kTile;
-    if ((rc = bstats.ensure((size_t)ntiles * sizeof(float2)))) return rc;
-    if (!only_failed) {   // (a second pick after a device-side redo of K3 finds the summaries it left: the scores are the same)
-        ProfScope ps(c, KN_STATS, st);
-        int* bad = scan ? scan->bad : nullptr;
-        if (d_stats32) AM_HIP(launch_stats_reduce(st, d_stats32, n_scores, (float2*)bstats.p, bad));
-        else AM_HIP(launch_tile_stats(st, d_scores, n_scores, (float2*)bstats.p, bad));
-    }
-    // hand-over area for chunks with many candidate tiles (per chunk of this launch; the picks
-    // of one call run in stream order, so one area serves them all)
-    if ((rc = c->wide_ctl.ensure((size_t)nsegs * 24))) return rc;
-    if ((rc = c->wide_list.ensure((size_t)nsegs * AM_MAX_PEAKS_PER_CHUNK * sizeof(am_peak)))) return rc;
+    if ((rc = c->wide_ctl.ensure(n * kWideCtlBytes))) return rc;
+    if ((rc = c->wide_list.ensure(n * AM_MAX_PEAKS_PER_CHUNK * sizeof(am_peak)))) return rc;
+    return c->wide_tiles.ensure(n * kWideTileList * sizeof(int));
+}
+WideState wide_carve(Ctx* c, size_t n) {
     WideState wide{};
     wide.best = static_cast<unsigned long long*>(c->wide_ctl.p);
-    wide.state = reinterpret_cast<int*>(wide.best + nsegs);
-    wide.count = reinterpret_cast<unsigned*>(wide.state + nsegs);
-    wide.seg_min = reinterpret_cast<float*>(wide.state + 2 * nsegs);
-    wide.ntiles = wide.state + 3 * nsegs;
-    if ((rc = c->wide_tiles.ensure((size_t)nsegs * kWideTileList * sizeof(int)))) return rc;
+    wide.state = reinterpret_cast<int*>(wide.best + n);
+    wide.count = reinterpret_cast<unsigned*>(wide.state + n);
+    wide.seg_min = reinterpret_cast<float*>(wide.state + 2 * n);
+    wide.ntiles = wide.state + 3 * n;
     wide.tiles = static_cast<int*>(c->wide_tiles.p);
     wide.list = static_cast<am_peak*>(c->wide_list.p);
     wide.cap = AM_MAX_PEAKS_PER_CHUNK;
+    return wide;
+}
+
+// Launches find_peaks (audio_matcher.rs:221-230) for `nsegs` segments of a
+// resident score array; segment descriptors live at [seg_off, seg_off + nsegs) of the
+// context's segment buffer, result headers at [hdr_off, hdr_off + nsegs).
+int launch_pick(Ctx* c, ScoreSide& side, const float* d_scores, long long n_scores, int seg_off, int nsegs,
+                       float min_prom, long long min_dist, int* bad, const ScanResult* res, int hdr_off,
+                       const PeakArena& arena, const PeakPolicy& pol, hipStream_t st, bool only_failed) {
+    if (!st) st = c->stream;
+    const SparseScores sp = (res && res->fused) ? res->sparse : plain_scores();
+    if (nsegs == 0 || n_scores <= 0) return AM_OK;
+    int rc;
+    const long long ntiles = (n_scores + kTile - 1) / kTile;
+    if ((rc = side.stats.ensure((size_t)ntiles * sizeof(float2)))) return rc;
+    if (!only_failed) {   // (a second pick after a device-side redo of K3 finds the summaries it left: the scores are the same)
+        ProfScope ps(c, KN_STATS, st);
+        if (sp.stats32) AM_HIP(launch_stats_reduce(st, sp.stats32, n_scores, (float2*)side.stats.p, bad));
+        else AM_HIP(launch_tile_stats(st, d_scores, n_scores, (float2*)side.stats.p, bad));
+    }
+    if ((rc = wide_reserve(c, (size_t)nsegs))) return rc;
     {
         ProfScope ps(c, KN_PEAKS, st);
-        AM_HIP(launch_peaks(st, d_scores, n_scores, (const float2*)bstats.p,
+        AM_HIP(launch_peaks(st, d_scores, n_scores, (const float2*)side.stats.p,
                             (const Segment*)c->segs.p + seg_off, nsegs, min_prom, min_dist,
-                            (am_peak*)bpeaks.p, (SegHeader*)c->hdr.p + hdr_off, sp, arena, wide, only_failed, pol));
+                            (am_peak*)side.peaks.p, (SegHeader*)c->hdr.p + hdr_off, sp, arena, wide_carve(c, (size_t)nsegs), only_failed, pol));
     }
     return AM_OK;
 }
@@ -457,26 +435,23 @@ int launch_pick(Ctx* c, const float* d_scores, long long n_scores, int seg_off, 
 // Count the qualifying peaks, build the list in global memory, sort and filter it on the device
 // (am_peaks.hip, peaks_big_finish), fetch the survivors.  Synchronous; appends to `all`.
 int pick_chunk_big(Ctx* c, const float* d_scores, long long n_scores, int seg_idx, const Segment& sg,
-                          float min_prom, long long min_dist, const ScanRequest* scan, float seg_min,
+                          float min_prom, long long min_dist, const ScanResult* res, float seg_min,
                           std::vector<am_peak>& all, const PeakPolicy& pol) {
     const long long a = sg.a, b = std::min(sg.b, n_scores);
     if (b - a >= 0xFFFFFFFFll) return fail(AM_ERR_PEAK_OVERFLOW, "chunk of 2^32 scores or more with more than AM_MAX_PEAKS_PER_CHUNK peaks");
-    const SparseScores sp = (scan && scan->fused) ? scan->sparse : SparseScores{nullptr, nullptr, nullptr, 1, 5, 5, 1.0};
+    const SparseScores sp = (res && res->fused) ? res->sparse : plain_scores();
+    const DevBuf& stats = c->side[0].stats;
     int rc;
-    if ((rc = c->wide_ctl.ensure(24))) return rc;
+    if ((rc = c->wide_ctl.ensure(kWideCtlBytes))) return rc;
     struct Ctl { unsigned long long best; int state; unsigned count; float seg_min; int ntiles; } ctl{0ull, 7, 0u, seg_min, -1};   // (state: handed over, head and tail pieces to be scanned)
-    WideState wide{};
-    wide.best = static_cast<unsigned long long*>(c->wide_ctl.p);
-    wide.state = reinterpret_cast<int*>(wide.best + 1);
-    wide.count = reinterpret_cast<unsigned*>(wide.state + 1);
-    wide.seg_min = reinterpret_cast<float*>(wide.state + 2);
-    wide.ntiles = wide.state + 3;
+    static_assert(sizeof(Ctl) == kWideCtlBytes, "one chunk's control words, in wide_carve's order");
+    WideState wide = wide_carve(c, 1);
     wide.tiles = nullptr;
     const Segment* d_seg = (const Segment*)c->segs.p + seg_idx;
     // pass 1: count
     wide.list = nullptr; wide.cap = 0;
-    AM_HIP(hipMemcpyAsync(c->wide_ctl.p, &ctl, 24, hipMemcpyHostToDevice, c->stream));
-    AM_HIP(launch_peaks_wide_one(c->stream, d_scores, n_scores, (const float2*)c->stats.p, d_seg, min_prom, min_dist, sp, wide, pol));
+    AM_HIP(hipMemcpyAsync(c->wide_ctl.p, &ctl, sizeof(ctl), hipMemcpyHostToDevice, c->stream));
+    AM_HIP(launch_peaks_wide_one(c->stream, d_scores, n_scores, (const float2*)stats.p, d_seg, min_prom, min_dist, sp, wide, pol));
     unsigned n = 0;
     AM_HIP(hipMemcpyAsync(&n, wide.count, sizeof(unsigned), hipMemcpyDeviceToHost, c->stream));
     AM_HIP(hipStreamSynchronize(c->stream));
@@ -490,8 +465,8 @@ int pick_chunk_big(Ctx* c, const float* d_scores, long long n_scores, int seg_id
     char* base = static_cast<char*>(c->big.p);
     // pass 2: fill the list (in any order)
     wide.list = reinterpret_cast<am_peak*>(base); wide.cap = n;
-    AM_HIP(hipMemcpyAsync(c->wide_ctl.p, &ctl, 24, hipMemcpyHostToDevice, c->stream));
-    AM_HIP(launch_peaks_wide_one(c->stream, d_scores, n_scores, (const float2*)c->stats.p, d_seg, min_prom, min_dist, sp, wide, pol));
+    AM_HIP(hipMemcpyAsync(c->wide_ctl.p, &ctl, sizeof(ctl), hipMemcpyHostToDevice, c->stream));
+    AM_HIP(launch_peaks_wide_one(c->stream, d_scores, n_scores, (const float2*)stats.p, d_seg, min_prom, min_dist, sp, wide, pol));
     AM_HIP(hipMemsetAsync(base + off_table, 0xFF, 8 * nb, c->stream));
     AM_HIP(launch_peaks_big_finish(c->stream, wide.list, n, a, min_dist, reinterpret_cast<unsigned long long*>(base + off_keys),
                                    reinterpret_cast<unsigned*>(base + off_idx), reinterpret_cast<long long*>(base + off_table),

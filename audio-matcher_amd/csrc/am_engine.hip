@@ -31,23 +31,12 @@ static int launch_pick_group(Ctx* c, const K3Group& kg, long long n_scores, int 
     }
     { ProfScope ps(c, KN_STATS, st);
       AM_HIP(launch_stats_reduce(st, pg.stats32[0], n_scores, pg.stats[0], bad, &pg)); }
-    if ((rc = c->wide_ctl.ensure(total * 24))) return rc;
-    if ((rc = c->wide_list.ensure(total * AM_MAX_PEAKS_PER_CHUNK * sizeof(am_peak)))) return rc;
-    if ((rc = c->wide_tiles.ensure(total * kWideTileList * sizeof(int)))) return rc;
-    if ((rc = c->peaks.ensure(total * AM_MAX_PEAKS_PER_CHUNK * sizeof(am_peak)))) return rc;
-    WideState wide{};
-    wide.best = static_cast<unsigned long long*>(c->wide_ctl.p);
-    wide.state = reinterpret_cast<int*>(wide.best + total);
-    wide.count = reinterpret_cast<unsigned*>(wide.state + total);
-    wide.seg_min = reinterpret_cast<float*>(wide.state + 2 * total);
-    wide.ntiles = wide.state + 3 * total;
-    wide.tiles = static_cast<int*>(c->wide_tiles.p);
-    wide.list = static_cast<am_peak*>(c->wide_list.p);
-    wide.cap = AM_MAX_PEAKS_PER_CHUNK;
+    if ((rc = wide_reserve(c, total))) return rc;
+    if ((rc = c->side[0].peaks.ensure(total * AM_MAX_PEAKS_PER_CHUNK * sizeof(am_peak)))) return rc;
     {
         ProfScope ps(c, KN_PEAKS, st);
         AM_HIP(launch_peaks(st, pg.g[0], n_scores, pg.stats[0], (const Segment*)c->segs.p + seg_off, nsegs, min_prom, min_dist,
-                            (am_peak*)c->peaks.p, (SegHeader*)c->hdr.p, sp_common, arena, wide, false, pol, &pg));
+                            (am_peak*)c->side[0].peaks.p, (SegHeader*)c->hdr.p, sp_common, arena, wide_carve(c, total), false, pol, &pg));
     }
     return AM_OK;
 }
@@ -105,20 +94,20 @@ struct ScoreSets {
         : c(c_), overlap(o.batch_overlap && n_items > 1 && c_->stream2 && c_->ev_k3[0] && c_->ev_k3[1] && c_->ev_pick[0] && c_->ev_pick[1]) {}
     int count() const { return overlap ? 2 : 1; }
     int set() const { return overlap ? (int)(seq & 1) : 0; }
-    float* scores() const { return (float*)(set() ? c->scores_b.p : c->scores.p); }
+    ScoreSide& side() const { return c->side[set()]; }
+    float* scores() const { return (float*)side().scores.p; }
     hipStream_t pick_stream() const { return overlap ? c->stream2 : c->stream; }
     // scores, tile summaries and peak lists of every set, and the pick's hand-over area, for the largest item: sized
     // before anything is queued, so that no pick has to grow them while the previous one still runs on the other stream
     int size(size_t max_scores, size_t max_segs) {
         int rc;
         for (int set = 0; set < count(); ++set) {
-            if ((rc = (set ? c->scores_b : c->scores).ensure(max_scores * sizeof(float)))) return rc;
-            if ((rc = (set ? c->peaks_b : c->peaks).ensure(sizeof(am_peak) * max_segs * AM_MAX_PEAKS_PER_CHUNK))) return rc;
-            if ((rc = (set ? c->stats_b : c->stats).ensure((max_scores + kTile - 1) / kTile * sizeof(float2)))) return rc;
+            ScoreSide& sd = c->side[set];
+            if ((rc = sd.scores.ensure(max_scores * sizeof(float)))) return rc;
+            if ((rc = sd.peaks.ensure(sizeof(am_peak) * max_segs * AM_MAX_PEAKS_PER_CHUNK))) return rc;
+            if ((rc = sd.stats.ensure((max_scores + kTile - 1) / kTile * sizeof(float2)))) return rc;
         }
-        if ((rc = c->wide_ctl.ensure(max_segs * 24))) return rc;
-        if ((rc = c->wide_list.ensure(max_segs * AM_MAX_PEAKS_PER_CHUNK * sizeof(am_peak)))) return rc;
-        return c->wide_tiles.ensure(max_segs * kWideTileList * sizeof(int));
+        return wide_reserve(c, max_segs);
     }
     // before K3 overwrites the current set: the pick that last read it is done (on_host: this thread waits for it,
     // otherwise the main stream does)
@@ -163,7 +152,7 @@ static int match_alone(am_needle* h, const void* d_hay, size_t len, const am_mat
 // header with a spill arena of its own, its peaks appended to `all`, shifted by `shift` samples.
 // With score_norm on (`nrm`), the chunk's scores are normalised before the pick, which then summarises them itself.
 static int pick_alone(am_needle* h, const Opts& o, const am_match_params* p, const void* src, long long src_len, float factor,
-                      ScanRequest& req, long long n_scores, int seg_idx, const Segment& sg, int spare_hdr, uint64_t shift, int src_kind,
+                      const ScanRequest& req, long long n_scores, int seg_idx, const Segment& sg, int spare_hdr, uint64_t shift, int src_kind,
                       const NormSpec& nrm, std::vector<am_peak>& all) {
     Ctx* c = h->ctx;
     const PeakPolicy pol = o.peak_policy();
@@ -173,20 +162,22 @@ static int pick_alone(am_needle* h, const Opts& o, const am_match_params* p, con
     AM_HIP(hipMemsetAsync(c->arena_cur.p, 0, sizeof(unsigned), c->stream));
     own.base = static_cast<am_peak*>(c->spill.p); own.cursor = static_cast<unsigned*>(c->arena_cur.p);
     own.cap = AM_MAX_PEAKS_PER_CHUNK;
-    if ((rc = c->scores.ensure((size_t)n_scores * sizeof(float)))) return rc;
-    float* d_scores = (float*)c->scores.p;
-    if ((rc = run_correlation(h, o, src, src_len, 0, d_scores, n_scores, factor, &req, src_kind))) return rc;
+    ScoreSide& side = c->side[0];
+    if ((rc = side.scores.ensure((size_t)n_scores * sizeof(float)))) return rc;
+    float* d_scores = (float*)side.scores.p;
+    ScanResult res{};
+    if ((rc = run_correlation(h, o, src, src_len, 0, d_scores, n_scores, factor, &req, &res, src_kind))) return rc;
     if (nrm.on) {
         if ((rc = normalise_scores(c, c->stream, nrm, src, src_len, src_kind, 0, (long long)h->n, d_scores, sg.a, std::min(sg.b, n_scores))))
             return rc;
-        req.fused = false;
+        res.fused = false;
     }
-    if ((rc = launch_pick(c, d_scores, n_scores, seg_idx, 1, p->min_prominence, (long long)p->min_distance, &req, spare_hdr, own, pol))) return rc;
+    if ((rc = launch_pick(c, side, d_scores, n_scores, seg_idx, 1, p->min_prominence, (long long)p->min_distance, nullptr, &res, spare_hdr, own, pol))) return rc;
     AM_HIP(hipStreamSynchronize(c->stream));
     const SegHeader& hd = static_cast<const SegHeader*>(c->hdr.p)[spare_hdr];
     const size_t old = all.size();
     if (hd.overflow & 1) {
-        if ((rc = pick_chunk_big(c, d_scores, n_scores, seg_idx, sg, p->min_prominence, (long long)p->min_distance, &req, hd.seg_min, all, pol)))
+        if ((rc = pick_chunk_big(c, d_scores, n_scores, seg_idx, sg, p->min_prominence, (long long)p->min_distance, &res, hd.seg_min, all, pol)))
             return rc;
     } else append_header_peaks(hd, own, all);
     for (size_t j = old; j < all.size(); ++j) { all[j].start += shift; all[j].end += shift; }
@@ -194,17 +185,6 @@ static int pick_alone(am_needle* h, const Opts& o, const am_match_params* p, con
 }
 
 // ---- the odd last blocks of a batch -------------------------------------------------------------------------------
-// Whether the main pass of a haystack with out_count scores leaves its odd last block to a TailPlan -- the conditions
-// run_correlation_one applies, for a caller that computes the tails of several haystacks per launch (match_many).
-static bool haystack_tail(am_needle* h, const Opts& o, long long out_count, TailPlan* t) {
-    t->on = false;
-    Ctx* c = h->ctx;
-    if (needle_is_segmented(h, o) || (h->n <= (size_t)kDirectMaxNeedle && o.log_n == 0)) return false;
-    if (!c->stream_tail || !c->ev_fork || !c->ev_join) return false;
-    Geometry g{};
-    if (plan_geometry(h->n, out_count, o, &g)) return false;
-    return tail_plan(h->n, out_count, o, g, t);   // (main plans of 2^22 points and more: all carry the fused scan)
-}
 // The tails of up to kMaxTailBatch haystacks of a batch (all on one smaller plan) as ONE launch each of K1 / K2 / K3 on
 // the main stream: full grids instead of one under-filled launch triple per haystack beside the main pass (which costs
 // about as much as the dropped pair saves, profiles/r04/tail_block_ab.txt).  The scores and their summary go to slots
@@ -215,22 +195,20 @@ struct TailSlots { size_t scores, stats; };   // elements per slot (floats, floa
 // (the several-per-launch kernels exist for the 256-row plan, 2^21 points: the tail of a 2^23 main pass that needs the
 // 2^22 plan is computed beside its main pass, like a single haystack's)
 static bool tail_batchable(const TailPlan& t) { return t.on && t.g.logN == 21; }
-static int launch_tail_batch(am_needle* h, const Opts& o, const std::vector<TailPlan>& tails, const std::vector<size_t>& members, int half_idx,
+static int launch_tail_batch(am_needle* h, const std::vector<PassPlan>& plans, const std::vector<size_t>& members, int half_idx,
                              const TailSlots& sl, const void* const* d_hays, const size_t* lens, float factor, int src_kind) {
     Ctx* c = h->ctx;
-    int rc;
-    const TailPlan& first = tails[members[0]];
-    const Plan* pl = nullptr;
-    if ((rc = get_plan(c, first.g.logN, &pl))) return rc;
-    const float2* hc = nullptr;
-    HalfScale hs;
-    if ((rc = needle_k2_spectrum(h, o, pl, &hc, &hs))) return rc;
+    const PassPlan& lead = plans[members[0]];   // (one plan, one spectrum: the members share the needle and the tail's transform size)
+    const TailPlan& first = lead.tail;
+    const Plan* pl = lead.tail_pl;
+    const float2* hc = lead.tail_hc;
+    const HalfScale& hs = lead.tail_hs;
     TailBatch tb{};
     tb.n = (int)members.size();
     for (int j = 0; j < tb.n; ++j) {
         const size_t k = members[j];
         const size_t slot = (size_t)half_idx * kMaxTailBatch + (size_t)j;
-        const Job job = tail_job(tails[k], d_hays[k], (long long)lens[k], (long long)(lens[k] - h->n + 1), src_kind);
+        const Job job = tail_job(plans[k].tail, d_hays[k], (long long)lens[k], (long long)(lens[k] - h->n + 1), src_kind);
         tb.src[j] = job.src;
         tb.src_len[j] = job.src_len;
         tb.out_count[j] = job.out_count;
@@ -248,9 +226,9 @@ static int launch_tail_batch(am_needle* h, const Opts& o, const std::vector<Tail
 // holds one (the reference's scores for it are NaN throughout: no peak); again[i] = its window is
 // clean but some of its scores came from a block pair that holds one.  One search kernel over the
 // sample ranges of all block pairs and all windows; rare path, synchronous.
-static int classify_nonfinite(am_needle* h, const Opts& o, const float* d_hay, size_t len, long long out_count,
+static int classify_nonfinite(am_needle* h, const PassPlan& pp, const float* d_hay, size_t len,
                               const std::vector<Segment>& segs, int s0, int s1,
-                              std::vector<char>* drop, std::vector<char>* again, bool with_tail) {
+                              std::vector<char>* drop, std::vector<char>* again) {
     Ctx* c = h->ctx;
     const long long s = (long long)h->n;
     const int nch = s1 - s0;
@@ -258,36 +236,20 @@ static int classify_nonfinite(am_needle* h, const Opts& o, const float* d_hay, s
     std::vector<Segment> ranges;
     for (int i = s0; i < s1; ++i)       // the samples behind scores [a, b): a .. b + s - 2
         ranges.push_back(Segment{segs[i].a, std::min<long long>((long long)len, segs[i].b + s - 1)});
-    Geometry g{};
-    TailPlan tail{};
-    long long npairs = 0;
-    const bool segmented = needle_is_segmented(h, o);   // (every segment pass has block pairs of its own: all clean windows again)
-    if (!segmented && !(h->n <= (size_t)kDirectMaxNeedle && o.log_n == 0)) {   // (direct summation spreads nothing)
-        int rc = plan_geometry(h->n, out_count, o, &g);
-        if (rc) return rc;
-        npairs = g.npairs;
-        // K1 loads a full N samples per block, starting at block * hop (am_fft.hip, k1_cols_fwd_*), and hop
-        // may have been rounded down to a multiple of kTile: pair q reads [2q hop, (2q + 1) hop + N), or
-        // [2q hop, 2q hop + N) when its second block does not exist -- up to kTile - 1 samples more than
-        // the scores it yields depend on, and a NaN there still poisons the whole pair
-        if (with_tail) tail_plan(h->n, out_count, o, g, &tail);
-        if (tail.on) --npairs;   // (the main pass ends at tail.T; the scores behind it come from one pair of the smaller plan)
-        for (long long q = 0; q < npairs; ++q) {
-            const long long last_block = (2 * q + 1 < g.nblocks) ? 2 * q + 1 : 2 * q;
-            ranges.push_back(Segment{2 * q * g.hop, std::min<long long>((long long)len, last_block * g.hop + g.N)});
-        }
-        if (tail.on) ranges.push_back(Segment{tail.T, std::min<long long>((long long)len, tail.T + (tail.g.nblocks - 1) * tail.g.hop + tail.g.N)});
-    }
+    // (direct summation spreads nothing; every segment pass of a partitioned needle has block pairs of its own: all clean windows again)
+    const long long npairs = pp.kind == PassKind::Transform ? pp.npairs : 0;
+    for (long long q = 0; q < npairs; ++q) ranges.push_back(pp.pair_reads(q, (long long)len));
+    if (pp.tail.on) ranges.push_back(pp.tail_reads((long long)len));
     std::vector<int> flags(ranges.size(), 0);
     int rc = nonfinite_flags(c, d_hay, ranges.data(), (int)ranges.size(), flags.data());
     if (rc) return rc;
     for (int i = 0; i < nch; ++i) {
         if (flags[i]) { (*drop)[i] = 1; continue; }
-        if (segmented) { (*again)[i] = 1; continue; }
+        if (pp.kind == PassKind::Partitioned) { (*again)[i] = 1; continue; }
         const Segment sg = segs[s0 + i];
         for (long long q = 0; q < npairs && !(*again)[i]; ++q)
-            if (flags[nch + q] && 2 * q * g.hop < sg.b && (2 * q + 2) * g.hop > sg.a) (*again)[i] = 1;
-        if (tail.on && flags[nch + npairs] && tail.T < sg.b) (*again)[i] = 1;
+            if (flags[nch + q] && 2 * q * pp.g.hop < sg.b && (2 * q + 2) * pp.g.hop > sg.a) (*again)[i] = 1;
+        if (pp.tail.on && flags[nch + npairs] && pp.tail.T < sg.b) (*again)[i] = 1;
     }
     return AM_OK;
 }
@@ -331,12 +293,12 @@ int match_many(am_needle* h, const void* const* d_hays, const size_t* lens, size
     // (a dip deeper than half a prominence that most tiles' samples missed) is redone with every
     // run written.
     const int sm = p->scale == AM_SCALE_LIB ? 1 : 0;
-    ScanRequest scan{};
-    scan.margin = nrm.on ? -1.0f : write_margin(o, p);
-    const bool sparse_ok = scan.margin >= 0.0f;
-    scan.hist_min = nrm.on ? FLT_MAX : h->hist_min(sm);   // (of the haystacks before this call: the whole batch is queued before any result is back)
-    scan.seg_c = (long long)p->chunk;
-    scan.seg_d = (long long)(p->chunk + p->overlap) - (long long)s;
+    ScanRequest base{};   // what every pass of this call asks for; each pass adds its buffers and restrictions to a copy
+    base.margin = nrm.on ? -1.0f : write_margin(o, p);
+    const bool sparse_ok = base.margin >= 0.0f;
+    base.hist_min = nrm.on ? FLT_MAX : h->hist_min(sm);   // (of the haystacks before this call: the whole batch is queued before any result is back)
+    base.seg_c = (long long)p->chunk;
+    base.seg_d = (long long)(p->chunk + p->overlap) - (long long)s;
     for (size_t k = 0; k < n_hay; ++k) n_out[G(k)] = 0;
     ChunkPlan cp;
     plan_chunks(s, d_hays, lens, n_hay, p, o, my, part ? part->max_windows : (size_t)-1, &cp);
@@ -352,30 +314,28 @@ int match_many(am_needle* h, const void* const* d_hays, const size_t* lens, size
     // ... and the transforms' own buffers -- work matrix, level-0 summary, ballots and thresholds -- for the
     // haystack that needs the most of each: a ragged batch whose later haystacks are longer must not free
     // and re-allocate them under the kernels of the earlier ones (plans and needle spectra are built here too)
+    // (streaming ingest launched its early pairs under the layout of the announced length: no tail there)
+    std::vector<PassPlan> plans(n_hay);
     Footprint need;
     for (size_t k = 0; k < n_hay; ++k) {
         if (cp.n_chunks[k] == 0 || cp.ns(k) == 0) continue;
-        Footprint one;
-        if ((rc = correlation_footprint(h, o, (long long)(lens[k] - s + 1), &one))) return rc;
-        need.take(one);
+        if ((rc = pass_plan(h, o, (long long)(lens[k] - s + 1), pre == nullptr, &plans[k]))) return rc;
+        need.take(plans[k].need);
     }
     // The odd last blocks (TailPlan).  A single haystack computes its tail beside its main pass (run_tail_block); a
     // batch that overlaps picks and transforms computes the tails of up to kMaxTailBatch haystacks per launch, into
     // slots of two alternating halves (a half is written again two batches later: every commit out of it is long done,
     // the main stream has waited for the pick of the haystack before the previous one by then).
-    std::vector<TailPlan> tails(n_hay);
     std::vector<int> tail_slot(n_hay, -1);
     TailSlots tslots{0, 0};
     bool batch_tails = false;
-    if (!pre && need.work_tail) {
+    if (need.work_tail) {
         size_t n_tails = 0;
-        for (size_t k = 0; k < n_hay; ++k) {
-            if (cp.n_chunks[k] == 0 || cp.ns(k) == 0) continue;
-            if (haystack_tail(h, o, (long long)(lens[k] - s + 1), &tails[k]) && tail_batchable(tails[k])) {
+        for (size_t k = 0; k < n_hay; ++k)
+            if (tail_batchable(plans[k].tail)) {
                 ++n_tails;
-                tslots.scores = std::max(tslots.scores, (size_t)(2 * tails[k].g.hop));
+                tslots.scores = std::max(tslots.scores, (size_t)(2 * plans[k].tail.g.hop));
             }
-        }
         tslots.stats = tslots.scores / 32;
         batch_tails = sets.overlap && n_tails > 1;
         const size_t nslot = batch_tails ? kMaxTailBatch : 1;
@@ -387,10 +347,10 @@ int match_many(am_needle* h, const void* const* d_hays, const size_t* lens, size
     }
     int tail_batches = 0;
     for (int set = 0; set < sets.count(); ++set) {
-        if (need.work && (rc = (set ? c->work_b : c->work).ensure(need.work))) return rc;
+        if (need.work && (rc = c->side[set].work.ensure(need.work))) return rc;
         if (pre) continue;   // (streaming ingest brings its own summary and flag buffers)
-        if (need.stats32 && (rc = (set ? c->stats32_b : c->stats32).ensure(need.stats32))) return rc;
-        if (need.side && (rc = (set ? c->wflags_b : c->wflags).ensure(need.side))) return rc;
+        if (need.stats32 && (rc = c->side[set].stats32.ensure(need.stats32))) return rc;
+        if (need.side && (rc = c->side[set].wflags.ensure(need.side))) return rc;
     }
     // one spare header behind the main ones serves the single-chunk passes below; the arena
     // holds every list of one haystack in the worst case plus a few entries per chunk
@@ -405,7 +365,7 @@ int match_many(am_needle* h, const void* const* d_hays, const size_t* lens, size
     // own window (non-finite samples nearby, below); the pick clamps it to the scores there are
     const int local_seg = (int)resident.size();
     // (seg_d is the index of a full window's LAST score: chunk + overlap - s + 1 scores in all)
-    resident.push_back(Segment{0, std::max<long long>(scan.seg_d + 1, 1)});
+    resident.push_back(Segment{0, std::max<long long>(base.seg_d + 1, 1)});
     if ((rc = upload_segments(c, resident))) return rc;
     if ((rc = c->badflag.ensure(sizeof(int) * n_hay))) return rc;
     int* h_bad = static_cast<int*>(c->badflag.p);
@@ -455,101 +415,89 @@ int match_many(am_needle* h, const void* const* d_hays, const size_t* lens, size
         if (ns == 0) continue;
         const long long out_count = (long long)(lens[k] - s + 1);
         const int set = sets.set();
+        const PassPlan& pp = plans[k];
+        ScoreSide& side = sets.side();
         float* d_scores = sets.scores();
-        scan.set = set;
+        ScanRequest req = base;
+        req.out = scan_buffers(side);
         // this set's work matrix, scores and summaries are overwritten: the pick (and redo) that last used them must be done
         // (On the host: this thread runs far ahead of the GPU -- it queues a haystack in 35 us, the GPU takes 700 -- so
         // waiting here for the pick of the haystack before the previous one leaves more than a haystack's work queued,
         // and the main stream is spared a barrier packet between K3 and the next K1: that boundary measured 6.5 us
         // instead of 11 - 27, profiles/r04/event_gaps.txt.  Option host_pick_wait = 0: the stream waits.)
         if ((rc = sets.wait_pick(o.host_pick_wait != 0))) return rc;
-        scan.before_k3 = nullptr;
-        scan.work_by_set = sets.overlap;
         int* d_redo = nullptr;
         if (redo_armed) {
-            Geometry g{};
-            if ((rc = plan_geometry(s, out_count, o, &g))) return rc;
-            AM_HIP(hipMemsetAsync(c->redo_pairs[set].p, 0, sizeof(int) * (size_t)g.npairs, c->stream));
+            AM_HIP(hipMemsetAsync(c->redo_pairs[set].p, 0, sizeof(int) * (size_t)std::max<long long>(pp.g.npairs, 1), c->stream));
             d_redo = static_cast<int*>(c->redo_pairs[set].p);
         }
         // (i16 frames are always finite -- but a half-precision transform can overflow on them)
-        scan.bad = ((src_kind == 0 || o.half) && std::isfinite(factor)) ? &h_bad[k] : nullptr;
+        int* bad = ((src_kind == 0 || o.half) && std::isfinite(factor)) ? &h_bad[k] : nullptr;
         if (pre) {
             // the pairs that were computed while the samples arrived are in the stream's own buffers:
             // only the rest is launched now, into the same buffers
-            Geometry g{};
-            if ((rc = plan_geometry(s, out_count, o, &g))) return rc;
             d_scores = pre->scores;
-            scan.ext_stats32 = pre->stats32; scan.ext_side = pre->side;
-            scan.side_nblocks = pre->layout_nblocks;
-            scan.range_a = std::min(pre->pairs_done, g.npairs) * 2 * g.hop;
-            scan.range_b = out_count;
-            scan.skip_launch = scan.range_a >= out_count;
+            req.out.stats32 = pre->stats32; req.out.wflags = pre->side;
+            req.side_nblocks = pre->layout_nblocks;
+            req.range_a = std::min(pre->pairs_done, pp.g.npairs) * 2 * pp.g.hop;
+            req.range_b = out_count;
+            req.skip_launch = req.range_a >= out_count;
         }
-        scan.tail_by_caller = false;
-        if (batch_tails && tail_batchable(tails[k])) {
+        if (batch_tails && tail_batchable(pp.tail)) {
             if (tail_slot[k] < 0) {   // the next batch: this haystack and the following ones with such a tail
                 std::vector<size_t> members;
                 for (size_t k2 = k; k2 < n_hay && members.size() < (size_t)kMaxTailBatch; ++k2)
-                    if (tail_batchable(tails[k2]) && tail_slot[k2] < 0) {
+                    if (tail_batchable(plans[k2].tail) && tail_slot[k2] < 0) {
                         tail_slot[k2] = (tail_batches & 1) * kMaxTailBatch + (int)members.size();
                         members.push_back(k2);
                     }
-                if ((rc = launch_tail_batch(h, o, tails, members, tail_batches & 1, tslots, d_hays, lens, factor, src_kind))) return rc;
+                if ((rc = launch_tail_batch(h, plans, members, tail_batches & 1, tslots, d_hays, lens, factor, src_kind))) return rc;
                 ++tail_batches;
             }
-            scan.tail_by_caller = true;
+            req.tail_by_caller = true;
         }
-        if ((rc = run_correlation(h, o, d_hays[k], (long long)lens[k], 0, d_scores, out_count, factor,
-                                  &scan, src_kind))) return rc;
+        ScanResult res{};
+        if ((rc = run_correlation(h, o, d_hays[k], (long long)lens[k], 0, d_scores, out_count, factor, &req, &res, src_kind, &pp))) return rc;
         if ((rc = sets.k3_done())) return rc;
-        if (scan.tail_by_caller && scan.fused) {
+        if (req.tail_by_caller && res.fused) {
             // (behind the main pass in stream order, hence behind the batch that filled the slot; in front of the pick)
-            const TailPlan& t = tails[k];
-            const size_t tiles = (size_t)1 << (scan.sparse.log_n2 - kColsLog), words = tiles << (scan.sparse.log_n1 - 6);
-            const size_t blk = (size_t)(t.T / scan.sparse.hop);
+            const TailPlan& t = pp.tail;
+            const BallotLayout bl = ballot_layout(res.sparse.log_n1, res.sparse.log_n2);
+            const size_t blk = (size_t)(t.T / res.sparse.hop);
             ProfScope ps(c, KN_OTHER, c->stream2);
             AM_HIP(launch_tail_commit(c->stream2, static_cast<const float*>(c->tail_scores.p) + (size_t)tail_slot[k] * tslots.scores, d_scores + t.T,
                                       out_count - t.T, static_cast<const float2*>(c->tail_stats.p) + (size_t)tail_slot[k] * tslots.stats,
-                                      const_cast<float2*>(scan.sparse.stats32) + t.T / 32,
-                                      scan.sparse.wbits ? const_cast<unsigned long long*>(scan.sparse.wbits) + blk * words : nullptr, (long long)words,
-                                      scan.sparse.tile_theta ? const_cast<float*>(scan.sparse.tile_theta) + blk * tiles : nullptr, (int)tiles));
+                                      const_cast<float2*>(res.sparse.stats32) + t.T / 32,
+                                      res.sparse.wbits ? const_cast<unsigned long long*>(res.sparse.wbits) + blk * bl.words : nullptr, (long long)bl.words,
+                                      res.sparse.tile_theta ? const_cast<float*>(res.sparse.tile_theta) + blk * bl.tiles : nullptr, (int)bl.tiles));
         }
-        if (scan.fused && scan.sparse.wbits) {
-            scan.sparse.fail_flags = h_fail + seg_off[k];
-            scan.sparse.redo_pairs = (redo_armed && scan.redo_ok) ? d_redo : nullptr;
+        if (res.fused && res.sparse.wbits) {
+            res.sparse.fail_flags = h_fail + seg_off[k];
+            res.sparse.redo_pairs = (redo_armed && res.redo_ok) ? d_redo : nullptr;
         }
-        ScanRequest pick_req = scan;
         if (nrm.on) {
-            // behind K3 and the tail's commit (both ordered before the pick's stream by now), in front of the pick; the
-            // samples are the caller's (or io_in, which nothing overwrites before this call has drained)
+            // behind K3 and the tail's commit (both ordered before the pick's stream by now), in front of the pick, which
+            // then summarises the scores itself; the samples are the caller's (or io_in, which nothing overwrites before
+            // this call has drained)
             if ((rc = normalise_scores(c, sets.pick_stream(), nrm, d_hays[k], (long long)lens[k], src_kind, 0, (long long)s, d_scores, 0, out_count)))
                 return rc;
-            pick_req.fused = false;
         }
-        if ((rc = launch_pick(c, d_scores, out_count, seg_off[k], ns, p->min_prominence,
-                              (long long)p->min_distance, &pick_req, seg_off[k], arena, pol, sets.pick_stream()))) return rc;
-        if (scan.fused && scan.sparse.redo_pairs) {
-            ScanCfg cfg = scan.redo_cfg;
+        if ((rc = launch_pick(c, side, d_scores, out_count, seg_off[k], ns, p->min_prominence,
+                              (long long)p->min_distance, bad, nrm.on ? nullptr : &res, seg_off[k], arena, pol, sets.pick_stream()))) return rc;
+        if (res.fused && res.sparse.redo_pairs) {
+            ScanCfg cfg = res.redo_cfg;
             cfg.margin = -1.0f;
             cfg.only_pairs = d_redo;
             { ProfScope ps(c, KN_OTHER, c->stream2);   // (not under "k3_cols_inv": an all-but-empty launch that queues behind the next haystack's kernels)
-              AM_HIP(launch_k3(c->stream2, scan.redo_job, scan.redo_npairs, scan.redo_work, scan.redo_pl, scan.redo_scale, cfg, scan.redo_half)); }
-            ScanRequest again = scan;
-            again.sparse.redo_pairs = nullptr; again.sparse.fail_flags = nullptr; again.bad = nullptr;
-            if ((rc = launch_pick(c, d_scores, out_count, seg_off[k], ns, p->min_prominence, (long long)p->min_distance,
-                                  &again, seg_off[k], arena, pol, c->stream2, true))) return rc;
+              AM_HIP(launch_k3(c->stream2, res.redo_job, res.redo_npairs, res.redo_work, res.redo_pl, res.redo_scale, cfg, res.redo_half)); }
+            res.sparse.redo_pairs = nullptr; res.sparse.fail_flags = nullptr;
+            if ((rc = launch_pick(c, side, d_scores, out_count, seg_off[k], ns, p->min_prominence, (long long)p->min_distance,
+                                  nullptr, &res, seg_off[k], arena, pol, c->stream2, true))) return rc;
         }
         if ((rc = sets.pick_done())) return rc;
     }
     queueing.end();
     if ((rc = sets.drain())) return rc;   // the headers are in host memory once the peak kernels have finished
-    scan.set = 0;
-    scan.before_k3 = nullptr;
-    scan.bad = nullptr;
-    scan.ext_stats32 = nullptr; scan.ext_side = nullptr; scan.side_nblocks = 0; scan.skip_launch = false;   // (the single-chunk passes below work in the context's own buffers)
-    scan.tail_by_caller = false;   // (... and compute a tail they need themselves)
-    scan.range_a = 0; scan.range_b = 0;
     int worst = AM_OK;
     std::vector<am_peak> all;
     std::vector<size_t> retry_f32;
@@ -588,7 +536,7 @@ int match_many(am_needle* h, const void* const* d_hays, const size_t* lens, size
         // own samples (as the reference does it) and picked from that.
         std::vector<char> drop, again;
         if (h_bad[k]) {
-            if ((rc = classify_nonfinite(h, o, (const float*)d_hays[k], lens[k], out_count, segs, s0, s1, &drop, &again, pre == nullptr))) return rc;
+            if ((rc = classify_nonfinite(h, plans[k], (const float*)d_hays[k], lens[k], segs, s0, s1, &drop, &again))) return rc;
         }
         // collect in window order (audio_matcher.rs:132-133)
         for (int i = s0; i < s1; ++i) {
@@ -608,7 +556,7 @@ int match_many(am_needle* h, const void* const* d_hays, const size_t* lens, size
             // score buffers have moved on to later haystacks by now).  Redo the blocks that produce this
             // chunk's scores with every run written, in place in set 0 (same block layout, hence
             // bit-identical scores), and pick the chunk again with a spill arena of its own.
-            ScanRequest full = scan;
+            ScanRequest full = base;   // (in set 0 of the context, with a tail of its own if the layout has one)
             full.margin = -1.0f;
             full.range_a = sg.a; full.range_b = sg.b;
             if ((rc = pick_alone(h, o, p, d_hays[k], (long long)lens[k], factor, full, out_count, i, sg, spare_hdr, 0, src_kind, nrm, all))) return rc;
@@ -787,29 +735,28 @@ int match_multi_many(am_needle* const* needles, size_t nn, const void* const* d_
     size_t n_pairs_active = 0;
     for (size_t k = 0; k < n_hay; ++k) n_pairs_active += ns_max(k) > 0 ? m : 0;
     ScoreSets sets(c, o, n_pairs_active);
-    if ((rc = c->work.ensure(max_matrix * sizeof(float2)))) return rc;
+    DevBuf& fwd = c->side[0].work;   // the haystack's forward columns (K1), shared by every needle
+    if ((rc = fwd.ensure(max_matrix * sizeof(float2)))) return rc;
     if ((rc = c->work2.ensure(std::min(group_opt, m) * max_matrix * sizeof(float2)))) return rc;
     if ((rc = sets.size(max_scores, max_segs))) return rc;
     for (int set = 0; set < sets.count(); ++set) {
-        if ((rc = (set ? c->stats32_b : c->stats32).ensure((max_scores + 31) / 32 * sizeof(float2)))) return rc;
-        if ((rc = (set ? c->wflags_b : c->wflags).ensure(max_wflags))) return rc;
+        if ((rc = c->side[set].stats32.ensure((max_scores + 31) / 32 * sizeof(float2)))) return rc;
+        if ((rc = c->side[set].wflags.ensure(max_wflags))) return rc;
     }
     // one K3 launch per needle group: every needle of a group (two groups in flight) has its own score-side buffers
     const size_t k3_group = (o.k3_group && group_opt > 1 && m > 1 && !o.half && max_wflags > 0) ? std::min(group_opt, m) : 0;
-    for (size_t i = 0; i < k3_group * (size_t)sets.count(); ++i) {
-        const size_t slot = i < k3_group ? i : kMaxNeedleGroup + (i - k3_group);
-        if ((rc = c->grp_scores[slot].ensure(max_scores * sizeof(float)))) return rc;
-        if ((rc = c->grp_stats32[slot].ensure((max_scores + 31) / 32 * sizeof(float2)))) return rc;
-        if ((rc = c->grp_wflags[slot].ensure(max_wflags))) return rc;
-    }
+    for (int set = 0; set < sets.count(); ++set)
+        for (size_t q = 0; q < k3_group; ++q) {
+            if ((rc = c->grp_scores[set][q].ensure(max_scores * sizeof(float)))) return rc;
+            if ((rc = c->grp_stats32[set][q].ensure((max_scores + 31) / 32 * sizeof(float2)))) return rc;
+            if ((rc = c->grp_wflags[set][q].ensure(max_wflags))) return rc;
+        }
     if (k3_group && o.pick_group) {   // ... and the scratch of the group's picks, which run as one set of launches
         const size_t total = k3_group * max_segs;
         for (size_t z = 0; z < k3_group; ++z)
             if ((rc = c->grp_stats[z].ensure((max_scores + kTile - 1) / kTile * sizeof(float2)))) return rc;
-        if ((rc = c->wide_ctl.ensure(total * 24))) return rc;
-        if ((rc = c->wide_list.ensure(total * AM_MAX_PEAKS_PER_CHUNK * sizeof(am_peak)))) return rc;
-        if ((rc = c->wide_tiles.ensure(total * kWideTileList * sizeof(int)))) return rc;
-        if ((rc = c->peaks.ensure(total * AM_MAX_PEAKS_PER_CHUNK * sizeof(am_peak)))) return rc;
+        if ((rc = wide_reserve(c, total))) return rc;
+        if ((rc = c->side[0].peaks.ensure(total * AM_MAX_PEAKS_PER_CHUNK * sizeof(am_peak)))) return rc;
     }
     PeakArena arena{};
     if ((rc = prepare_results(c, nhdr, nhdr * 8 + 4096, &arena))) return rc;
@@ -831,7 +778,7 @@ int match_multi_many(am_needle* const* needles, size_t nn, const void* const* d_
         const int half = (o.half && (plan_is_r16(pl->dev) || plan_is_c512(pl->dev))) ? (o.half >= 2 ? 2 : 1) : 0;
         const size_t group = (!half && plan_k2_has_group(pl->dev)) ? group_opt : 1;
         const size_t matrix = (size_t)g.npairs * (size_t)g.N;
-        const bool fused = plan_has_scan(pl->dev) && (g.hop % kTile) == 0;
+        const bool fused = plan_fuses_scan(pl->dev, g);
         // The odd last block (TailPlan): the main pass -- K1 here, every group's K2 and K3 below -- stops at the even
         // block boundary, the scores behind it come from one pair of the 2^21 plan: K1 once, then per needle group one
         // row-kernel launch and one K3 launch (every run written) behind the group's own, and the main layout's
@@ -842,7 +789,7 @@ int match_multi_many(am_needle* const* needles, size_t nn, const void* const* d_
         Job job{}, job_t{};
         job.src = d_hays[k]; job.src_len = (long long)lens[k]; job.lead = 0; job.src_kind = src_kind;
         job.out_count = tail.on ? tail.T : out_count; job.hop = (int)g.hop; job.nblocks = (int)(tail.on ? g.nblocks - 1 : g.nblocks); job.first_pair = 0;
-        { ProfScope ps(c, KN_K1); AM_HIP(launch_k1(c->stream, job, main_pairs, (float2*)c->work.p, pl->dev, half)); }
+        { ProfScope ps(c, KN_K1); AM_HIP(launch_k1(c->stream, job, main_pairs, (float2*)fwd.p, pl->dev, half)); }
         if (tail.on) {
             if ((rc = get_plan(c, tail.g.logN, &plt))) return rc;
             job_t = tail_job(tail, d_hays[k], (long long)lens[k], out_count, src_kind);
@@ -858,7 +805,7 @@ int match_multi_many(am_needle* const* needles, size_t nn, const void* const* d_
                 K2Group grp{};
                 grp.n = (int)gn;
                 for (int q = 0; q < grp.n; ++q) { grp.hc[q] = hc[i + q]; grp.dst[q] = (float2*)c->work2.p + (size_t)q * matrix; }
-                { ProfScope ps(c, KN_K2); AM_HIP(launch_k2_group(c->stream, main_pairs, (const float2*)c->work.p, grp, pl->dev)); }
+                { ProfScope ps(c, KN_K2); AM_HIP(launch_k2_group(c->stream, main_pairs, (const float2*)fwd.p, grp, pl->dev)); }
                 if (tail.on) {
                     K2Group gt{};
                     gt.n = (int)gn;
@@ -875,27 +822,23 @@ int match_multi_many(am_needle* const* needles, size_t nn, const void* const* d_
             if (grouped_k3) {
                 K3Group kg{};
                 kg.n = (int)gn;
-                ScanRequest scans[kMaxNeedleGroup];
+                ScanResult scans[kMaxNeedleGroup];   // what each member's pick reads
+                int* const bad = (src_kind == 0 || o.half) ? &h_bad[k] : nullptr;
                 ScanCfg common{};
                 bool same_plan = true, same_edges = true;
                 for (size_t q = 0; q < gn; ++q) {
                     am_needle* hq = needles[ord[i + q]];
-                    const size_t slot = (size_t)set * kMaxNeedleGroup + q;
-                    ScanRequest& sc = scans[q];
-                    sc = ScanRequest{};
-                    sc.set = 0;          // (the picks of a call run one after the other: they share the pick's own scratch)
-                    sc.margin = margin; sc.hist_min = hq->hist_min(sm);
-                    sc.seg_c = (long long)p->chunk; sc.seg_d = (long long)(p->chunk + pj[ord[i + q]].overlap) - (long long)hq->n;
-                    sc.bad = (src_kind == 0 || o.half) ? &h_bad[k] : nullptr;
-                    sc.fused = true;
                     ScanCfg cfg{};
-                    fill_scan_cfg(&cfg, c->grp_stats32[slot].p, c->grp_wflags[slot].p, g.nblocks, pl->dev, margin, sc.hist_min, sc.seg_c, sc.seg_d);
-                    sc.sparse = sparse_view(cfg, g.hop, pl->dev);
+                    fill_scan_cfg(&cfg, c->grp_stats32[set][q].p, c->grp_wflags[set][q].p, g.nblocks, pl->dev, margin, hq->hist_min(sm),
+                                  (long long)p->chunk, (long long)(p->chunk + pj[ord[i + q]].overlap) - (long long)hq->n);
+                    scans[q] = ScanResult{};
+                    scans[q].fused = true;
+                    scans[q].sparse = sparse_view(cfg, g.hop, pl->dev);
                     if (q == 0) common = cfg;
                     same_plan = same_plan && plan_of[i + q] == plan_of[i];
                     same_edges = same_edges && cfg.seg_d == common.seg_d;
                     kg.work[q] = (const float2*)c->work2.p + q * matrix;
-                    kg.dst[q] = (float*)c->grp_scores[slot].p;
+                    kg.dst[q] = (float*)c->grp_scores[set][q].p;
                     kg.stats32[q] = cfg.stats32; kg.wbits[q] = cfg.wbits; kg.tile_theta[q] = cfg.tile_theta;
                     kg.hist_min[q] = cfg.hist_min;
                     kg.out_scale[q] = half_scale(hq, o, pl->dev).k3(scale_factor(hq, p->scale, 1));
@@ -930,12 +873,13 @@ int match_multi_many(am_needle* const* needles, size_t nn, const void* const* d_
                     int hoff[kMaxNeedleGroup];
                     for (size_t q = 0; q < gn; ++q) hoff[q] = hdr_of(k, i + q);
                     if ((rc = launch_pick_group(c, kg, count_of(k, i), seg_of(k, i), plan_i(i).ns(k), p->min_prominence, (long long)p->min_distance,
-                                                scans[0].sparse, scans[0].bad, hoff, arena, pol, sets.pick_stream()))) return rc;
+                                                scans[0].sparse, bad, hoff, arena, pol, sets.pick_stream()))) return rc;
                 } else
                 for (size_t q = 0; q < gn; ++q)
                     if (plan_i(i + q).ns(k) > 0 &&
-                        (rc = launch_pick(c, kg.dst[q], count_of(k, i + q), seg_of(k, i + q), plan_i(i + q).ns(k), p->min_prominence,
-                                          (long long)p->min_distance, &scans[q], hdr_of(k, i + q), arena, pol, sets.pick_stream()))) return rc;
+                        // (the picks of a call run one after the other: they share set 0's tile summaries and peak lists)
+                        (rc = launch_pick(c, c->side[0], kg.dst[q], count_of(k, i + q), seg_of(k, i + q), plan_i(i + q).ns(k), p->min_prominence,
+                                          (long long)p->min_distance, bad, &scans[q], hdr_of(k, i + q), arena, pol, sets.pick_stream()))) return rc;
                 if ((rc = sets.pick_done())) return rc;
                 continue;
             }
@@ -945,33 +889,29 @@ int match_multi_many(am_needle* const* needles, size_t nn, const void* const* d_
             Job jn = job;   // (this needle's scores end before the layout's: tails only run on the grouped path)
             jn.dst = d_scores;
             jn.out_count = std::min(count_of(k, i), job.out_count);
-            ScanRequest scan{};
-            scan.set = set;
-            scan.margin = margin;
-            scan.hist_min = h->hist_min(sm);
-            scan.seg_c = (long long)p->chunk;
-            scan.seg_d = (long long)(p->chunk + pj[ord[i]].overlap) - (long long)h->n;
-            scan.bad = (src_kind == 0 || o.half) ? &h_bad[k] : nullptr;   // (i16 frames are always finite; an f16 transform can overflow)
+            ScoreSide& side = sets.side();
+            int* const bad = (src_kind == 0 || o.half) ? &h_bad[k] : nullptr;   // (i16 frames are always finite; an f16 transform can overflow)
+            ScanResult scan{};
             scan.fused = fused;
             scan.sparse = SparseScores{nullptr, nullptr, nullptr, (int)g.hop, pl->dev.logN2, pl->dev.logN1, 1.0 / (double)g.hop};
             ScanCfg cfg{};
             if (fused) {
-                fill_scan_cfg(&cfg, set ? c->stats32_b.p : c->stats32.p, set ? c->wflags_b.p : c->wflags.p, g.nblocks, pl->dev, scan.margin,
-                              scan.hist_min, scan.seg_c, scan.seg_d);
+                fill_scan_cfg(&cfg, side.stats32.p, side.wflags.p, g.nblocks, pl->dev, margin, h->hist_min(sm), (long long)p->chunk,
+                              (long long)(p->chunk + pj[ord[i]].overlap) - (long long)h->n);
                 scan.sparse = sparse_view(cfg, g.hop, pl->dev);
             }
             const float factor = scale_factor(h, p->scale, 1);
             const HalfScale hs = half_scale(h, o, pl->dev);
             if (group == 1) {
                 ProfScope ps(c, KN_K2);
-                AM_HIP(launch_k2(c->stream, (int)g.npairs, (float2*)c->work.p, hc[i], pl->dev, (float2*)c->work2.p, hs.level, hs.hscale, hs.pre));
+                AM_HIP(launch_k2(c->stream, (int)g.npairs, (float2*)fwd.p, hc[i], pl->dev, (float2*)c->work2.p, hs.level, hs.hscale, hs.pre));
             }
             // K3 overwrites this set's scores and summaries: the pick that last read them must be done
             if ((rc = sets.wait_pick(false))) return rc;
             { ProfScope ps(c, KN_K3); AM_HIP(launch_k3(c->stream, jn, (int)g.npairs, inv_rows, pl->dev, hs.k3(factor), cfg, half)); }
             if ((rc = sets.k3_done())) return rc;
-            if ((rc = launch_pick(c, d_scores, count_of(k, i), seg_of(k, i), ns, p->min_prominence, (long long)p->min_distance,
-                                  &scan, hdr_of(k, i), arena, pol, sets.pick_stream()))) return rc;
+            if ((rc = launch_pick(c, side, d_scores, count_of(k, i), seg_of(k, i), ns, p->min_prominence, (long long)p->min_distance,
+                                  bad, &scan, hdr_of(k, i), arena, pol, sets.pick_stream()))) return rc;
             if ((rc = sets.pick_done())) return rc;
         }
     }

@@ -128,6 +128,10 @@ struct Plan {
     unsigned* mf = nullptr;    // constant tables of the matrix-core row kernel (N2 = 8192 only)
 };
 
+// One set of score-side buffers: the scores, their tile summaries (level 1) and peak lists for the pick; K3's level-0
+// summary and its ballots / thresholds; the work matrix the scores come from.
+struct ScoreSide { DevBuf scores, stats, stats32, wflags, peaks, work; };
+
 struct ProfRec { int name; hipEvent_t e0, e1; };
 enum { KN_K1 = 0, KN_K2, KN_K3, KN_STATS, KN_PEAKS, KN_OTHER, KN_COUNT };
 
@@ -141,20 +145,20 @@ struct Ctx {
     DevBuf work_tail2;                           // several needles: the tail's inverse rows, one matrix per needle of a group
     std::recursive_mutex mu;
     std::map<int, Plan> plans;
-    DevBuf work, work2, scores, stats, stats32, wflags, segs, peaks, io_in, io_out, sum, arena_cur, wide_ctl, wide_list, wide_tiles;
+    // The score-side buffers, two sets: in a batch the peak pick of haystack k runs on stream2 beside the transforms of
+    // haystack k+1, which then need their own set.  The second work matrix serves the device-side redo (batches): the
+    // inverse rows of haystack k are still there when its pick has found chunks whose certificate failed.  Everything
+    // outside an overlapped batch works in side[0].
+    ScoreSide side[2];
+    DevBuf work2, segs, io_in, io_out, sum, arena_cur, wide_ctl, wide_list, wide_tiles;
     DevBuf norm_blk;   // block energies of the haystack being normalised (option score_norm; used on one stream at a time)
     DevBuf hit_tab, hit_parts, hit_flags, hit_out, hit_stage;   // per-hit scoring (am_hits.hip): hit table, partials, results, staged spans
     HostBuf hit_io;                                              // ... and the pinned host side of the table and the results
     std::map<std::pair<int, int>, DevBuf> rs_taps;               // sample-rate conversion: the polyphase table of each (L, M)
-    // second set of the score-side buffers: in a batch the peak pick of haystack k runs on
-    // stream2 beside the transforms of haystack k+1, which then need their own set
-    DevBuf scores_b, stats_b, stats32_b, wflags_b, peaks_b;
-    // device-side redo (batches): a second work matrix, so that the inverse rows of haystack k are still there
-    // when its pick has found chunks whose certificate failed, and the per-pair "run again" flags of both sets
-    DevBuf work_b, redo_pairs[2];
+    DevBuf redo_pairs[2];   // device-side redo (batches): the per-pair "run again" flags of both sets
     // several needles: the K3s of a needle group run as ONE launch, every needle of the group with score-side
     // buffers of its own; two such sets alternate (the picks of group g beside the transforms of group g + 1)
-    DevBuf grp_scores[2 * kMaxNeedleGroup], grp_stats32[2 * kMaxNeedleGroup], grp_wflags[2 * kMaxNeedleGroup];
+    DevBuf grp_scores[2][kMaxNeedleGroup], grp_stats32[2][kMaxNeedleGroup], grp_wflags[2][kMaxNeedleGroup];
     DevBuf grp_stats[kMaxNeedleGroup];   // tile summaries of the group's picks (one set: picks run one group after the other)
     HostBuf failcnt;   // host-visible: one byte per chunk of a call, set when the chunk failed its certificate
     hipEvent_t ev_k3[2] = {nullptr, nullptr}, ev_pick[2] = {nullptr, nullptr};
@@ -257,35 +261,40 @@ namespace am {
 
 // The overlap-save engine: scores[j] = factor * sum_n X[j + n - lead] needle[n]
 // When a ScanRequest is given and the plan supports it, K3 also writes the level-0
-// (min,max) summary into the chosen set's stats32 and `fused` becomes true.
+// (min,max) summary into the request's stats32 and ScanResult::fused becomes true.
+// Where a pass works: the work matrix, K3's level-0 summary and its ballots / thresholds.  A score-side set of the
+// context (scan_buffers), or -- streaming ingest -- summary and flag buffers the caller owns.
+struct ScanBuffers { DevBuf* work; DevBuf* stats32; DevBuf* wflags; };
+inline ScanBuffers scan_buffers(ScoreSide& sd) { return ScanBuffers{&sd.work, &sd.stats32, &sd.wflags}; }
+// What the caller asks of a pass (the callee does not change it)
 struct ScanRequest {
-    float margin;            // in: a run's raw scores are written when its maximum reaches min(its K3 tile's minimum, hist_min) + margin; < 0: all
-    float hist_min;          // in: lowest chunk minimum of the needle's recent haystacks (FLT_MAX: none)
-    long long seg_c, seg_d;  // in: chunk geometry (scores i*seg_c .. i*seg_c + seg_d)
-    int set;                 // in: which set of score-side buffers (0, or 1 in an overlapped batch)
-    hipEvent_t before_k3;    // in: K3 must not overwrite that set before this event (or null)
-    // in: restrict the launch to the blocks that produce scores [range_a, range_b) (range_b = 0:
+    float margin;            // a run's raw scores are written when its maximum reaches min(its K3 tile's minimum, hist_min) + margin; < 0: all
+    float hist_min;          // lowest chunk minimum of the needle's recent haystacks (FLT_MAX: none)
+    long long seg_c, seg_d;  // chunk geometry (scores i*seg_c .. i*seg_c + seg_d)
+    ScanBuffers out;         // where the pass works (all null: set 0 of the context)
+    hipEvent_t before_k3;    // K3 must not overwrite those buffers before this event (or null)
+    // restrict the launch to the blocks that produce scores [range_a, range_b) (range_b = 0:
     // everything).  Used to redo single chunks with theta = -inf in place.
     long long range_a, range_b;
-    int* bad;                // in: host-visible word the summary kernels of the pick set when a score is not finite, or null
-    // in (streaming ingest): summary / flag buffers owned by the caller instead of the context's sets, and
-    // "launch nothing" (every pair was computed while the samples arrived; only describe what is there)
-    DevBuf* ext_stats32; DevBuf* ext_side;
-    // in (streaming ingest): the block count the side buffer is laid out for (0: this launch's own).  The
+    // (streaming ingest): the block count the flag buffer is laid out for (0: this launch's own).  The
     // thresholds sit behind the ballots, i.e. at an offset that depends on the block count: early pairs are
     // launched under the layout of the announced length and the final pass must keep that layout even
     // when the real length gives fewer blocks.
     long long side_nblocks;
-    bool skip_launch;
-    bool tail_by_caller;     // in: the caller computes a TailPlan's scores itself (match_many, several haystacks per launch): main pass only
-    bool no_scan;            // in: only the block restriction (range_a, range_b) applies; K3 writes plain scores
-    bool work_by_set;        // in: the work matrix of set 1 is the context's second one (kept for a device-side redo)
-    // out: what a second K3 launch over the same work matrix needs (valid when redo_ok)
+    bool skip_launch;        // (streaming ingest) launch nothing: every pair was computed while the samples arrived; only describe what is there
+    bool tail_by_caller;     // the caller computes a TailPlan's scores itself (match_many, several haystacks per launch): main pass only
+    bool no_scan;            // only the block restriction (range_a, range_b) applies; K3 writes plain scores
+};
+// What a pass reports back
+struct ScanResult {
+    bool fused;              // K3 produced stats32 / wflags
+    SparseScores sparse;     // description of what was written
+    // what a second K3 launch over the same work matrix needs (valid when redo_ok)
     bool redo_ok;
     Job redo_job; PlanDev redo_pl; float redo_scale; int redo_half; int redo_npairs; const float2* redo_work; ScanCfg redo_cfg;
-    bool fused;              // out: K3 produced stats32 / wflags
-    SparseScores sparse;     // out: description of what was written
 };
+// plain scores, every one written, no level-0 summary: the pick summarises them itself (tile_stats)
+inline SparseScores plain_scores() { return SparseScores{nullptr, nullptr, nullptr, 1, 5, 5, 1.0}; }
 struct Geometry {
     int logN;
     long long N, hop, nblocks, npairs;
@@ -314,9 +323,8 @@ struct HalfScale {
     float pre, hscale;
     float k3(float factor) const { return level ? factor / (hscale * pre) : factor; }
 };
-// What the transforms of one haystack need of the context's scratch buffers, so that a batch can size them
-// once, for its largest haystack, before anything is queued (see QueueingScope).  Also builds the plan and
-// the needle spectrum the haystack will use (building one runs kernels and waits for them).
+// What the transforms of one haystack need of the context's scratch buffers (PassPlan::need), so that a batch can
+// size them once, for its largest haystack, before anything is queued (see QueueingScope).
 struct Footprint {
     size_t work = 0, stats32 = 0, side = 0, work_tail = 0;
     long long npairs = 0;
@@ -325,6 +333,37 @@ struct Footprint {
         work_tail = std::max(work_tail, f.work_tail);
         npairs = std::max(npairs, f.npairs);
     }
+};
+// Which path one haystack takes for (needle, options, score count) -- THE place that decides it (pass_plan,
+// am_correlate.hip); run_correlation, the batch engine and streaming ingest all read the answer here.
+enum class PassKind { Direct, Partitioned, Transform };   // direct summation (tiny needle) / one pass per needle segment / one pass
+struct PassPlan {
+    PassKind kind = PassKind::Direct;
+    // Transform:
+    Geometry g{};                      // the whole haystack's block layout
+    const Plan* pl = nullptr;          // ... its plan, the needle's spectrum on it and the half-precision scales
+    const float2* hc = nullptr;
+    HalfScale hs{};
+    bool fused = false;                // K3 carries the score scan (level-0 summary, ballots, thresholds)
+    TailPlan tail{};                   // the odd last block on a smaller plan (tail.on), with its plan and spectrum
+    const Plan* tail_pl = nullptr;
+    const float2* tail_hc = nullptr;
+    HalfScale tail_hs{};
+    long long nblocks = 0, npairs = 0; // of the main pass (without the tail's block)
+    long long ppg = 0;                 // block pairs per launch
+    long long main_count = 0;          // scores of the main pass (tail.T, or all)
+    // Partitioned: one plan per needle segment (am_needle::segments)
+    std::vector<PassPlan> parts;
+    Footprint need;                    // what the pass needs of the scratch buffers
+    // The samples block pair q of the main pass reads, and the tail's pair.  K1 loads a full N samples per block,
+    // starting at block * hop (am_fft.hip, k1_cols_fwd_*), and hop may have been rounded down to a multiple of kTile:
+    // pair q reads [2q hop, (2q + 1) hop + N), or [2q hop, 2q hop + N) when its second block does not exist -- up to
+    // kTile - 1 samples more than the scores it yields depend on, and a NaN there still poisons the whole pair.
+    Segment pair_reads(long long q, long long len) const {
+        const long long last_block = (2 * q + 1 < nblocks) ? 2 * q + 1 : 2 * q;
+        return Segment{2 * q * g.hop, std::min(len, last_block * g.hop + g.N)};
+    }
+    Segment tail_reads(long long len) const { return Segment{tail.T, std::min(len, tail.T + (tail.g.nblocks - 1) * tail.g.hop + tail.g.N)}; }
 };
 // One part of a haystack that is split over several devices (am_match_part_device, am_pool_match_long*): the
 // buffer holds the samples from window `first_window` on, only its first `max_windows` windows belong to
@@ -342,7 +381,7 @@ struct StreamPre {
     float* scores;
     DevBuf* stats32; DevBuf* side;
     long long pairs_done;
-    long long layout_nblocks;   // the block count the early pairs laid the side buffer out for (ScanRequest::side_nblocks)
+    long long layout_nblocks;   // the block count the early pairs laid the flag buffer out for (ScanRequest::side_nblocks)
 };
 
 inline const void* advance_src(const void* src, size_t elements) {
@@ -398,28 +437,49 @@ int score_hits(Ctx* c, std::vector<HitDesc>& hits, am_hit_score* const* out);
 
 // ---- am_correlate.hip ----
 int plan_geometry(size_t s, long long out_count, const Opts& o, Geometry* g);
+bool plan_fuses_scan(const PlanDev& pl, const Geometry& g);   // K3 of this plan, at this hop, carries the score scan
 bool tail_plan(size_t s, long long out_count, const Opts& o, const Geometry& g, TailPlan* t);
+// allow_tail: the caller's passes may leave the odd last block to a TailPlan (not streaming ingest, whose early pairs
+// fix the layout; not an accumulating segment pass; not with lead != 0).  Builds the plans and the needle spectra the
+// haystack will use (building one runs kernels and waits for them): call it before anything is queued.
+int pass_plan(am_needle* h, const Opts& o, long long out_count, bool allow_tail, PassPlan* pp);
 Job tail_job(const TailPlan& t, const void* d_src, long long src_len, long long out_count, int src_kind);
+// a plan's ballot layout: column tiles per block (one threshold each), 64-bit ballot words per block
+struct BallotLayout { size_t tiles, words; };
+inline BallotLayout ballot_layout(int log_n1, int log_n2) {
+    const size_t tiles = (size_t)1 << (log_n2 - kColsLog);
+    return BallotLayout{tiles, tiles << (log_n1 - 6)};
+}
 size_t sparse_bytes(long long nblocks, const PlanDev& pl);
 void fill_scan_cfg(ScanCfg* cfg, void* stats32, void* side, long long nblocks, const PlanDev& pl, float margin, float hist_min,
                    long long seg_c, long long seg_d);
 SparseScores sparse_view(const ScanCfg& cfg, long long hop, const PlanDev& pl);
 bool needle_is_segmented(const am_needle* h, const Opts& o);
 float write_margin(const Opts& o, const am_match_params* p);
+// plan: the haystack's pass_plan when the caller has it (a batch plans before it queues); otherwise planned here, with
+// a tail allowed when a scan is requested and lead == 0
 int run_correlation(am_needle* h, const Opts& o, const void* d_src, long long src_len, long long lead,
-                    float* d_dst, long long out_count, float factor, ScanRequest* scan_req = nullptr, int src_kind = 0);
-int correlation_footprint(am_needle* h, const Opts& o, long long out_count, Footprint* f);
+                    float* d_dst, long long out_count, float factor, const ScanRequest* scan_req = nullptr, ScanResult* res = nullptr,
+                    int src_kind = 0, const PassPlan* plan = nullptr);
 int nonfinite_flags(Ctx* c, const float* d_src, const Segment* ranges, int n, int* flags);
 float scale_factor(const am_needle* h, int scale, size_t w);
 void make_segments(size_t len, size_t s, const am_match_params* p, bool drop_tail, std::vector<Segment>& segs,
                    std::vector<size_t>* widths = nullptr, size_t max_windows = (size_t)-1);
 int upload_segments(Ctx* c, const std::vector<Segment>& segs);
 int prepare_results(Ctx* c, size_t nhdr, size_t arena_entries, PeakArena* arena);
-int launch_pick(Ctx* c, const float* d_scores, long long n_scores, int seg_off, int nsegs,
-                float min_prom, long long min_dist, const ScanRequest* scan, int hdr_off,
+// The pick's hand-over area for chunks with many candidate tiles (WideState, am_kernels.h), one entry per chunk of a
+// launch; the picks of one call run in stream order, so one area serves them all.  wide_ctl holds the control words as
+// five arrays of n entries, one after the other: best (8 bytes), then state, count, seg_min, ntiles (4 bytes each).
+constexpr size_t kWideCtlBytes = sizeof(unsigned long long) + sizeof(int) + sizeof(unsigned) + sizeof(float) + sizeof(int);
+int wide_reserve(Ctx* c, size_t n);         // sizes the area for n chunks
+WideState wide_carve(Ctx* c, size_t n);     // the area as it is, laid out for n chunks
+// side: the set whose tile summaries and peak lists the pick uses; bad: host-visible word the summary kernels set when a
+// score is not finite, or null; res: what the pass that wrote the scores reported (null: plain scores)
+int launch_pick(Ctx* c, ScoreSide& side, const float* d_scores, long long n_scores, int seg_off, int nsegs,
+                float min_prom, long long min_dist, int* bad, const ScanResult* res, int hdr_off,
                 const PeakArena& arena, const PeakPolicy& pol, hipStream_t st = nullptr, bool only_failed = false);
 int pick_chunk_big(Ctx* c, const float* d_scores, long long n_scores, int seg_idx, const Segment& sg,
-                   float min_prom, long long min_dist, const ScanRequest* scan, float seg_min,
+                   float min_prom, long long min_dist, const ScanResult* res, float seg_min,
                    std::vector<am_peak>& all, const PeakPolicy& pol);
 // am_find_peaks on a resident score array: one chunk [0, n) (am_api.hip)
 int find_peaks_host_array(Ctx* c, const float* d_scores, long long n, float min_prom, long long min_dist, std::vector<am_peak>& all);

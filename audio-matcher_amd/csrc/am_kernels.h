@@ -60,7 +60,7 @@ struct Segment {
 // (K2 and K1 whole; K3's first pass -- its second pass and the score scan stay f32)
 hipError_t launch_k1(hipStream_t st, const Job& job, int npairs, float2* work, const PlanDev& pl, int half = 0);
 // dst == nullptr: in place; otherwise the result goes to a second work matrix
-// tail: the launch belongs to a haystack's odd last block (am_api.hip, run_tail_block) -- the same row kernels under
+// tail: the launch belongs to a haystack's odd last block (am_correlate.hip, run_tail_block) -- the same row kernels under
 // names of their own (tail_rows_*), so that a profile's per-kernel averages stay those of the main pass
 hipError_t launch_k2(hipStream_t st, int npairs, float2* work, const float2* hc, const PlanDev& pl, float2* dst = nullptr,
                      int half = 0, float hscale = 1.0f, float pre = 1.0f, bool tail = false);
@@ -135,7 +135,7 @@ struct K3Group {
     double inv_c;
 };
 bool plan_k3_has_group(const PlanDev& pl);
-// The odd last blocks of several haystacks of a batch (am_api.hip, TailPlan) as ONE launch each of K1 / K2 / K3 on the
+// The odd last blocks of several haystacks of a batch (am_engine.hip, launch_tail_batch; TailPlan in am_internal.h) as ONE launch each of K1 / K2 / K3 on the
 // 256-row plan: entry z = blockIdx.y is one block pair of a job of its own (source, scores, summary), work slot z.
 // Every run of raw scores is written (no ballots, no thresholds).
 constexpr int kMaxTailBatch = 8;

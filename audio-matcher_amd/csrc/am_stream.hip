@@ -43,17 +43,17 @@ static int stream_layout(am_stream* st) {
     st->early = false;
     st->pairs_done = 0;
     if (st->cap < h->n || st->p.scale == AM_SCALE_MY || st->p.chunk == 0) return AM_OK;
-    if (h->n <= (size_t)kDirectMaxNeedle && o.log_n == 0) return AM_OK;               // direct summation: no blocks
     if (o.log_n == 0 && (long long)h->n > kWidestFromSamples) return AM_OK;    // the plan depends on the final length / the needle is partitioned
     const long long out_cap = (long long)(st->cap - h->n + 1);
-    int rc = plan_geometry(h->n, out_cap, o, &st->geo);
+    PassPlan pp;   // (no tail: the early pairs fix the layout before the length is known)
+    int rc = pass_plan(h, o, out_cap, false, &pp);
     if (rc) return rc;
-    const Plan* pl = nullptr;
-    if ((rc = get_plan(h->ctx, st->geo.logN, &pl))) return rc;
-    if (!(plan_has_scan(pl->dev) && (st->geo.hop % kTile) == 0)) return AM_OK;           // (small generic plans: nothing to overlap)
+    // direct summation has no blocks; small generic plans without the fused scan: nothing to overlap
+    if (pp.kind != PassKind::Transform || !pp.fused) return AM_OK;
+    st->geo = pp.g;
     if ((rc = st->scores.ensure((size_t)out_cap * sizeof(float)))) return rc;
-    if ((rc = st->stats32.ensure((size_t)((out_cap + 31) / 32) * sizeof(float2)))) return rc;
-    if ((rc = st->side.ensure(sparse_bytes(st->geo.nblocks, pl->dev)))) return rc;
+    if ((rc = st->stats32.ensure(pp.need.stats32))) return rc;
+    if ((rc = st->side.ensure(pp.need.side))) return rc;
     st->early = true;
     return AM_OK;
 }
@@ -122,10 +122,10 @@ static int stream_launch_ready_pairs(am_stream* st) {
     ready = std::min(ready, g.npairs);
     if (ready - st->pairs_done < 1) return AM_OK;
     const Opts o = snapshot_opts(h);
-    Geometry now{};
-    int rc = plan_geometry(h->n, (long long)(st->cap - h->n + 1), o, &now);
+    PassPlan now;
+    int rc = pass_plan(h, o, (long long)(st->cap - h->n + 1), false, &now);
     if (rc) return rc;
-    if (now.logN != g.logN || now.hop != g.hop) {   // an option changed under the stream: start over at finish
+    if (now.kind != PassKind::Transform || now.g.logN != g.logN || now.g.hop != g.hop) {   // an option changed under the stream: start over at finish
         st->early = false; st->pairs_done = 0;
         return AM_OK;
     }
@@ -141,13 +141,13 @@ static int stream_launch_ready_pairs(am_stream* st) {
         return AM_OK;
     }
     st->margin = scan.margin;
-    scan.ext_stats32 = &st->stats32; scan.ext_side = &st->side;
+    scan.out = ScanBuffers{&c->side[0].work, &st->stats32, &st->side};
     scan.side_nblocks = g.nblocks;
     scan.range_a = st->pairs_done * 2 * g.hop;
     scan.range_b = ready * 2 * g.hop;
     AM_HIP(hipStreamWaitEvent(c->stream, st->copied, 0));   // the kernels read what has been copied so far
     rc = run_correlation(h, o, st->hay.p, (long long)st->cap, 0, (float*)st->scores.p, (long long)(st->cap - h->n + 1),
-                         scale_factor(h, st->p.scale, 1), &scan, st->fmt);
+                         scale_factor(h, st->p.scale, 1), &scan, nullptr, st->fmt, &now);
     if (rc) { st->failed = true; return rc; }
     st->pairs_done = ready;
     return AM_OK;
