@@ -154,6 +154,7 @@ struct Ctx {
     DevBuf norm_blk;   // block energies of the haystack being normalised (option score_norm; used on one stream at a time)
     DevBuf hit_tab, hit_parts, hit_flags, hit_out, hit_stage;   // per-hit scoring (am_hits.hip): hit table, partials, results, staged spans
     HostBuf hit_io;                                              // ... and the pinned host side of the table and the results
+    DevBuf seg_tab, seg_parts, seg_flags, seg_out;               // per-segment hit scoring (am_segments.hip); spans and pinned side: hit_stage, hit_io
     std::map<std::pair<int, int>, DevBuf> rs_taps;               // sample-rate conversion: the polyphase table of each (L, M)
     DevBuf redo_pairs[2];   // device-side redo (batches): the per-pair "run again" flags of both sets
     // several needles: the K3s of a needle group run as ONE launch, every needle of the group with score-side
@@ -434,6 +435,13 @@ int hit_desc(const am_needle* h, const void* hay, size_t len, int sample_format,
              const HitWhere& where, HitDesc* d);
 // scores every hit of `hits` in one launch sequence on c's stream; out[i]: host destination of hit i
 int score_hits(Ctx* c, std::vector<HitDesc>& hits, am_hit_score* const* out);
+
+// ---- am_segments.hip ----
+// the table entry of hit pk for radius r (checks as hit_desc does, same messages)
+int seg_desc(const am_needle* h, const void* hay, size_t len, int sample_format, const am_peak& pk, int r, double floor_ratio,
+             const HitWhere& where, SegDesc* d);
+// scores every hit of `hits` in one launch sequence on c's stream; out[i]: host destination of hit i's sp.segments records
+int score_segments(Ctx* c, std::vector<SegDesc>& hits, const am_segment_params& sp, am_hit_segment* const* out);
 
 // ---- am_correlate.hip ----
 int plan_geometry(size_t s, long long out_count, const Opts& o, Geometry* g);

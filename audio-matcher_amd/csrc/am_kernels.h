@@ -310,6 +310,27 @@ struct HitDesc {
 hipError_t launch_hit_scores(hipStream_t st, const HitDesc* d_hits, long long n, long long max_slices, int kind, double* parts,
                              unsigned* pflags, am_hit_score* d_out);
 
+// ---- am_segments.hip: per-segment hit scoring (am_hit_segments*) ----
+// The slice kernel exists for three radii; a call runs the smallest that holds its R (kSegRadii) and reads the lags
+// -R .. R of its records.  A record: c(-RT .. RT), E_w(-RT .. RT), E_n.
+constexpr int kSegRadii[3] = {1, 4, 16};
+inline int seg_kernel_radius(int r) { return r <= kSegRadii[0] ? kSegRadii[0] : r <= kSegRadii[1] ? kSegRadii[1] : kSegRadii[2]; }
+inline int seg_record_len(int rt) { return 2 * (2 * rt + 1) + 1; }   // doubles per partial record
+// One hit of a call, as the kernels read it (the call's table, uploaded once); m and R are the call's
+struct SegDesc {
+    const void* win;      // device: sample t of the haystack (f32 mono, or an i16 stereo frame for kind 1)
+    const float* needle;  // device: the whole needle
+    long long s;          // needle length
+    long long ulo, uhi;   // x[t + u] exists (and is read) for ulo <= u < uhi only: [-R, s + R) clipped to the haystack
+    long long part0;      // first partial record of the hit: segment j, slice k at part0 + j * nsl + k
+    double floor_ratio;   // 10^(-score_norm_floor_db / 10)
+    int kind;             // 0 = f32 mono, 1 = i16 stereo (one kind per launch)
+    int nsl;              // slices reserved per segment: ceil(ceil(s / m) / kHitSlice)
+};
+// parts: seg_record_len(seg_kernel_radius(r)) doubles per slice, pflags: one word per slice; d_out: n * m records
+hipError_t launch_hit_segments(hipStream_t st, const SegDesc* d_hits, long long n, int m, int r, int max_nsl, int kind,
+                               double* parts, unsigned* pflags, am_hit_segment* d_out);
+
 // ---- am_resample.hip: sample-rate conversion (am_resample*) ----
 constexpr int kRsThreads = 256;
 constexpr int kRsJ = 8;          // outputs per work item: k, k + W, ..., k + 7 W (one phase, its taps read once)

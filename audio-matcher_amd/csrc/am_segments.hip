@@ -1,0 +1,479 @@
+// am_segments.hip -- per-segment hit scoring (am_hit_segments*, include/audiomatch.h): the pass of am_hits.hip resolved
+// along the needle.  For a hit at t, the needle cut into m segments [a_j, a_{j+1}), a_j = floor(j S / m), and the lags
+// l = -R .. R, in f64:
+//   c_j(l) = sum_{i in seg j} x[t + l + i] n[i],   E_w,j(l) = sum_{i in seg j} x[t + l + i]^2,   E_n,j = sum_{i in seg j} n[i]^2
+// (x = 0 outside the haystack) and from those, per segment, the best lag with its parabola vertex and the NCC, gain and
+// level there.
+//
+// Two kernels on the context's stream:
+//   seg_slices    one workgroup per slice of kHitSlice needle samples counted from the segment's start (blockIdx.x =
+//                 slice within the segment, blockIdx.y = hit * m + segment): stages x over the slice plus RT samples each
+//                 side in LDS once, keeps the thread's needle samples in registers, accumulates the 2 RT + 1 pairs
+//                 (c, E_w) and E_n from that one read and writes one partial record, one 64-bit store per lane.  RT is
+//                 the smallest of kSegRadii that holds R: three instances per sample format, the accumulators in registers.
+//   seg_combine   one wave per (hit, segment): adds the segment's partials in slice order, picks l*, the vertex and the
+//                 flags and writes the am_hit_segment.
+// The kernels read x[t + u] for u in [-R, S + R) inside the haystack only (SegDesc::ulo, uhi), whatever RT is: that is
+// what the host form stages, and lags beyond R never reach a result.  A segment's result depends on the needle, the
+// samples it reads, m, R and the floor only (slices start at multiples of kHitSlice from a_j, every reduction runs in
+// a fixed order): the single, batch and host forms agree bit for bit.
+#include "am_internal.h"
+
+namespace am {
+
+namespace {
+
+constexpr int kSegThreads = 256;
+constexpr int kSegPer = kHitSlice / kSegThreads;   // needle samples per thread and slice
+constexpr int kSegMaxRecord = 2 * (2 * AM_SEG_MAX_RADIUS + 1) + 1;
+static_assert(kHitSlice % kSegThreads == 0, "slice must split evenly over the workgroup");
+static_assert(kSegRadii[2] == AM_SEG_MAX_RADIUS, "the widest kernel holds every radius");
+static_assert(2 * AM_SEG_MAX_RADIUS <= kSegThreads && kSegMaxRecord < kSegThreads, "one staged tail sample and one record value per thread");
+
+typedef __attribute__((address_space(1))) const float gfloat;
+typedef __attribute__((address_space(1))) const unsigned guint;   // (one i16 stereo frame)
+template <int KIND>
+__device__ __forceinline__ float seg_sample(const void* win, long long u) {
+    return KIND ? norm_downmix(__builtin_bit_cast(short2, ((guint*)win)[u])) : ((gfloat*)win)[u];
+}
+
+__device__ __forceinline__ long long seg_start(long long j, long long s, int m) { return j * s / m; }   // a_j (j <= 1024, s < 2^52)
+
+template <int KIND, int RT>
+__global__ __launch_bounds__(kSegThreads) void seg_slices_kernel(const SegDesc* __restrict__ hits, long long g0, int m, int r,
+                                                                 double* __restrict__ parts, unsigned* __restrict__ pflags) {
+    constexpr int NL = 2 * RT + 1, NV = 2 * NL + 1;
+    __shared__ float xs[kHitSlice + 2 * RT];
+    __shared__ double ws[NV][kSegThreads / 64];
+    const long long g = g0 + blockIdx.y, h = g / m;
+    const int j = (int)(g - h * m);
+    const SegDesc d = hits[h];
+    const long long a0 = seg_start(j, d.s, m), a1 = seg_start(j + 1, d.s, m);
+    const long long i0 = (long long)blockIdx.x * kHitSlice;
+    if (i0 >= a1 - a0) return;   // (a shorter segment than the launch's longest: whole workgroups leave together)
+    const int tid = threadIdx.x;
+    const int cnt = (int)min((long long)kHitSlice, a1 - a0 - i0);
+    // every load of the slice in flight at once: xs[q] = x[t + a0 + i0 - RT + q] (q < cnt + 2 RT, 0 where the hit reads
+    // no sample) and the thread's needle samples n[a0 + i0 + q]; a staged sample counts for the segment's non-finite
+    // flag when one of the lags -r .. r reads it
+    gfloat* nd = (gfloat*)d.needle + (a0 + i0);
+    const long long u0 = a0 + i0 - RT;
+    const int qlo = RT - r, qhi = cnt + RT + r;
+    float xv[kSegPer], nv[kSegPer];
+#pragma unroll
+    for (int k = 0; k < kSegPer; ++k) {
+        const int q = tid + k * kSegThreads;
+        const long long u = u0 + q;
+        xv[k] = q < cnt + 2 * RT && u >= d.ulo && u < d.uhi ? seg_sample<KIND>(d.win, u) : 0.0f;
+        nv[k] = q < cnt ? nd[q] : 0.0f;
+    }
+    float xt = 0.0f;
+    if (tid < 2 * RT) {
+        const int q = kHitSlice + tid;
+        const long long u = u0 + q;
+        xt = q < cnt + 2 * RT && u >= d.ulo && u < d.uhi ? seg_sample<KIND>(d.win, u) : 0.0f;
+    }
+    bool bad = false;
+#pragma unroll
+    for (int k = 0; k < kSegPer; ++k) {
+        const int q = tid + k * kSegThreads;
+        xs[q] = xv[k];
+        bad |= (q >= qlo && q < qhi && !__builtin_isfinite(xv[k])) || !__builtin_isfinite(nv[k]);
+    }
+    if (tid < 2 * RT) {
+        const int q = kHitSlice + tid;
+        xs[q] = xt;
+        bad |= q >= qlo && q < qhi && !__builtin_isfinite(xt);
+    }
+    __syncthreads();
+    double acc[NV];   // the record: c(-RT .. RT), E_w(-RT .. RT), E_n
+#pragma unroll
+    for (int k = 0; k < NV; ++k) acc[k] = 0.0;
+#pragma unroll
+    for (int k = 0; k < kSegPer; ++k) {
+        const int q = tid + k * kSegThreads;
+        if (q < cnt) {
+            const double dn = (double)nv[k];
+            acc[2 * NL] += dn * dn;
+#pragma unroll
+            for (int l = 0; l < NL; ++l) {
+                const double dx = (double)xs[q + l];
+                acc[l] += dx * dn;   // (a product of two f32 values is exact in f64)
+                acc[NL + l] += dx * dx;
+            }
+        }
+    }
+    // the sums of the workgroup in the order of hit_block_sum4: a butterfly over the wave, then the waves in order
+    const int lane = tid & 63, w = tid >> 6;
+#pragma unroll
+    for (int k = 0; k < NV; ++k) {
+        double v = acc[k];
+        for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+        if (lane == 0) ws[k][w] = v;
+    }
+    const int any_bad = __syncthreads_or(bad ? 1 : 0);
+    // one 64-bit store per lane: no record leaves as one wide store (tools/check_store_hazard.py)
+    const long long p = d.part0 + (long long)j * d.nsl + blockIdx.x;
+    if (tid < NV) {
+        double t = 0.0;
+        for (int i = 0; i < kSegThreads / 64; ++i) t += ws[tid][i];
+        parts[NV * p + tid] = t;
+    } else if (tid == NV) {
+        pflags[p] = (unsigned)any_bad;
+    }
+}
+
+// One wave per (hit, segment): lane k adds value k (and k + 64) of the segment's partial records in slice order, lane 0
+// turns the sums into the record.
+__global__ __launch_bounds__(64) void seg_combine_kernel(const SegDesc* __restrict__ hits, int m, int r, int rt,
+                                                         const double* __restrict__ parts, const unsigned* __restrict__ pflags,
+                                                         am_hit_segment* __restrict__ out) {
+    __shared__ double sh[kSegMaxRecord];
+    const long long g = blockIdx.x, h = g / m;
+    const int j = (int)(g - h * m);
+    const int lane = threadIdx.x;
+    const SegDesc d = hits[h];
+    const long long a0 = seg_start(j, d.s, m), a1 = seg_start(j + 1, d.s, m);
+    const long long ns = (a1 - a0 + kHitSlice - 1) / kHitSlice, p0 = d.part0 + (long long)j * d.nsl;
+    const int nl = 2 * rt + 1, nv = 2 * nl + 1;
+    for (int k = lane; k < nv; k += 64) {
+        double t = 0.0;
+        for (long long i = 0; i < ns; ++i) t += parts[nv * (p0 + i) + k];
+        sh[k] = t;
+    }
+    unsigned b = 0;
+    for (long long i = lane; i < ns; i += 64) b |= pflags[p0 + i];
+    const int bad = __syncthreads_or(b != 0 ? 1 : 0);
+    if (lane != 0) return;
+    const double* cc = sh + rt;        // cc[l] = c_j(l), ee[l] = E_w,j(l) for -rt <= l <= rt
+    const double* ee = sh + nl + rt;
+    const double en = sh[2 * nl];
+    const double nan = __builtin_nan("");
+    double lag = 0.0;
+    float ncc, gain, ldb;
+    unsigned flags = 0;
+    if (bad) {
+        flags = AM_HIT_NONFINITE;
+        ncc = gain = ldb = (float)nan;
+    } else if (en == 0.0) {
+        flags = AM_HIT_EMPTY_SEGMENT;
+        ncc = gain = 0.0f;
+        ldb = ee[0] > 0.0 ? __builtin_inff() : (float)nan;
+    } else {
+        int ls = 0;   // ties: the smaller |l|, then the negative lag
+        for (int k = 1; k <= r; ++k) {
+            if (cc[-k] > cc[ls]) ls = -k;
+            if (cc[k] > cc[ls]) ls = k;
+        }
+        lag = (double)ls;
+        const double bb = cc[ls], ew = ee[ls];
+        if (r == 0 || ls == r || ls == -r) {
+            flags |= AM_HIT_UNREFINED;
+        } else {
+            const double a = cc[ls - 1], c = cc[ls + 1], den = a - 2.0 * bb + c;
+            if (!(den < 0.0)) flags |= AM_HIT_UNREFINED;
+            else lag += fmin(fmax(0.5 * (a - c) / den, -0.5), 0.5);
+        }
+        if (ew == 0.0 || ew < en * d.floor_ratio) {
+            flags |= AM_HIT_BELOW_FLOOR;
+            ncc = 0.0f;
+        } else {
+            ncc = (float)(bb / sqrt(en * ew));
+        }
+        gain = (float)(bb / en);
+        ldb = ew == 0.0 ? -__builtin_inff() : (float)(10.0 * log10(ew / en));
+    }
+    am_hit_segment* o = out + g;
+    o->lag = lag;
+    o->ncc = ncc;
+    o->gain = gain;
+    o->level_db = ldb;
+    o->flags = flags;
+}
+
+template <int KIND, int RT>
+void launch_seg_slices(hipStream_t st, dim3 grid, const SegDesc* d_hits, long long g0, int m, int r, double* parts, unsigned* pflags) {
+    hipLaunchKernelGGL((seg_slices_kernel<KIND, RT>), grid, dim3(kSegThreads), 0, st, d_hits, g0, m, r, parts, pflags);
+}
+
+template <int KIND>
+void launch_seg_slices_rt(hipStream_t st, int rt, dim3 grid, const SegDesc* d_hits, long long g0, int m, int r, double* parts,
+                          unsigned* pflags) {
+    if (rt == kSegRadii[0]) launch_seg_slices<KIND, kSegRadii[0]>(st, grid, d_hits, g0, m, r, parts, pflags);
+    else if (rt == kSegRadii[1]) launch_seg_slices<KIND, kSegRadii[1]>(st, grid, d_hits, g0, m, r, parts, pflags);
+    else launch_seg_slices<KIND, kSegRadii[2]>(st, grid, d_hits, g0, m, r, parts, pflags);
+}
+
+}  // namespace
+
+hipError_t launch_hit_segments(hipStream_t st, const SegDesc* d_hits, long long n, int m, int r, int max_nsl, int kind,
+                               double* parts, unsigned* pflags, am_hit_segment* d_out) {
+    if (n <= 0) return hipSuccess;
+    const int rt = seg_kernel_radius(r);
+    const long long total = n * m;
+    for (long long g0 = 0; g0 < total; g0 += kHitMaxGridY) {   // (more segments than one grid column holds: a few launches)
+        const dim3 grid((unsigned)max_nsl, (unsigned)std::min<long long>(kHitMaxGridY, total - g0));
+        if (kind) launch_seg_slices_rt<1>(st, rt, grid, d_hits, g0, m, r, parts, pflags);
+        else launch_seg_slices_rt<0>(st, rt, grid, d_hits, g0, m, r, parts, pflags);
+        hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return e;
+    }
+    hipLaunchKernelGGL(seg_combine_kernel, dim3((unsigned)total), dim3(64), 0, st, d_hits, m, r, rt, (const double*)parts,
+                       (const unsigned*)pflags, d_out);
+    return hipGetLastError();
+}
+
+// ---- host side -------------------------------------------------------------------------------------------------------
+
+int seg_desc(const am_needle* h, const void* hay, size_t len, int sample_format, const am_peak& pk, int r, double floor_ratio,
+             const HitWhere& where, SegDesc* d) {
+    HitDesc hd{};
+    int rc;
+    if ((rc = hit_desc(h, hay, len, sample_format, pk, 0.0, where, &hd))) return rc;
+    d->win = hd.win;
+    d->needle = hd.needle;
+    d->s = hd.s;
+    d->ulo = -std::min<long long>(r, hd.t);
+    d->uhi = std::min<long long>(hd.s + r, (long long)len - hd.t);
+    d->part0 = 0;
+    d->floor_ratio = floor_ratio;
+    d->kind = hd.kind;
+    d->nsl = 0;
+    return AM_OK;
+}
+
+int score_segments(Ctx* c, std::vector<SegDesc>& hits, const am_segment_params& sp, am_hit_segment* const* out) {
+    const long long n = (long long)hits.size(), m = sp.segments;
+    if (n == 0) return AM_OK;
+    const size_t rec = sizeof(double) * (size_t)seg_record_len(seg_kernel_radius((int)sp.radius));
+    long long total = 0;
+    int max_nsl = 0;
+    for (SegDesc& d : hits) {
+        const long long longest = (d.s + m - 1) / m;   // (the longest segment of a needle: ceil(s / m))
+        d.nsl = (int)((longest + kHitSlice - 1) / kHitSlice);
+        d.part0 = total;
+        total += m * d.nsl;
+        max_nsl = std::max(max_nsl, d.nsl);
+    }
+    const size_t n_out = (size_t)(n * m);
+    int rc;
+    if ((rc = c->seg_tab.ensure(sizeof(SegDesc) * (size_t)n)) || (rc = c->seg_parts.ensure(rec * (size_t)total)) ||
+        (rc = c->seg_flags.ensure(sizeof(unsigned) * (size_t)total)) || (rc = c->seg_out.ensure(sizeof(am_hit_segment) * n_out)) ||
+        (rc = c->hit_io.ensure(std::max(sizeof(SegDesc) * (size_t)n, sizeof(am_hit_segment) * n_out))))
+        return rc;
+    // (the copies go through pinned memory, as in score_hits)
+    std::memcpy(c->hit_io.p, hits.data(), sizeof(SegDesc) * (size_t)n);
+    AM_HIP(hipMemcpyAsync(c->seg_tab.p, c->hit_io.p, sizeof(SegDesc) * (size_t)n, hipMemcpyHostToDevice, c->stream));
+    {
+        ProfScope ps(c, KN_OTHER, c->stream);
+        AM_HIP(launch_hit_segments(c->stream, static_cast<const SegDesc*>(c->seg_tab.p), n, (int)m, (int)sp.radius, max_nsl, hits[0].kind,
+                                   static_cast<double*>(c->seg_parts.p), static_cast<unsigned*>(c->seg_flags.p),
+                                   static_cast<am_hit_segment*>(c->seg_out.p)));
+    }
+    AM_HIP(hipMemcpyAsync(c->hit_io.p, c->seg_out.p, sizeof(am_hit_segment) * n_out, hipMemcpyDeviceToHost, c->stream));
+    AM_HIP(hipStreamSynchronize(c->stream));
+    const am_hit_segment* res = static_cast<const am_hit_segment*>(c->hit_io.p);
+    for (long long i = 0; i < n; ++i) std::memcpy(out[i], res + i * m, sizeof(am_hit_segment) * (size_t)m);
+    return AM_OK;
+}
+
+namespace {
+
+// AM_ERR_INVALID_ARG unless sp is a valid request for a needle of s samples (`who`: "" or "needle j: ")
+int seg_check_params(const am_segment_params* sp, size_t s, const std::string& who) {
+    if (sp->radius > AM_SEG_MAX_RADIUS)
+        return fail(AM_ERR_INVALID_ARG, "radius " + std::to_string(sp->radius) + " > AM_SEG_MAX_RADIUS (" + std::to_string(AM_SEG_MAX_RADIUS) + ")");
+    if (sp->segments == 0) return fail(AM_ERR_INVALID_ARG, "segments = 0");
+    if (sp->segments > s)
+        return fail(AM_ERR_INVALID_ARG, who + "segments " + std::to_string(sp->segments) + " > needle length " + std::to_string(s));
+    if (sp->segments > AM_SEG_MAX_SEGMENTS)
+        return fail(AM_ERR_INVALID_ARG, "segments " + std::to_string(sp->segments) + " > AM_SEG_MAX_SEGMENTS (" + std::to_string(AM_SEG_MAX_SEGMENTS) + ")");
+    return AM_OK;
+}
+
+double seg_floor_ratio(const am_needle* h) {
+    return std::pow(10.0, -(double)snapshot_opts(h).score_norm_floor_db / 10.0);
+}
+
+}  // namespace
+
+}  // namespace am
+
+using namespace am;
+
+extern "C" {
+
+// ---- per-segment hit scoring: the hit table of a call is built here, scored in one launch sequence ----
+int am_hit_segments_device(const am_needle* h, const void* d_haystack, size_t len, int sample_format,
+                           const am_peak* peaks, size_t n, const am_segment_params* sp, am_hit_segment* out) {
+    int rc = check_needle(h);
+    if (rc) return rc;
+    if ((rc = hit_check_format(sample_format))) return rc;
+    if (n == 0) return AM_OK;
+    if (!d_haystack || !peaks || !out || !sp) return fail(AM_ERR_INVALID_ARG, "null pointer");
+    if ((rc = seg_check_params(sp, h->n, ""))) return rc;
+    Ctx* c = h->ctx;
+    std::lock_guard<std::recursive_mutex> lk(c->mu);
+    if ((rc = hit_check_device(d_haystack, c->device, HitWhere{-1, 0, 0, 0}))) return rc;
+    const double ratio = seg_floor_ratio(h);
+    std::vector<SegDesc> hits(n);
+    std::vector<am_hit_segment*> dst(n);
+    for (size_t i = 0; i < n; ++i) {
+        if ((rc = seg_desc(h, d_haystack, len, sample_format, peaks[i], (int)sp->radius, ratio, HitWhere{-1, 0, 0, i}, &hits[i]))) return rc;
+        dst[i] = out + i * sp->segments;
+    }
+    return score_segments(c, hits, *sp, dst.data());
+}
+
+int am_hit_segments(const am_needle* h, const void* haystack, size_t len, int sample_format,
+                    const am_peak* peaks, size_t n, const am_segment_params* sp, am_hit_segment* out) {
+    int rc = check_needle(h);
+    if (rc) return rc;
+    if ((rc = hit_check_format(sample_format))) return rc;
+    if (n == 0) return AM_OK;
+    if (!haystack || !peaks || !out || !sp) return fail(AM_ERR_INVALID_ARG, "null pointer");
+    if ((rc = seg_check_params(sp, h->n, ""))) return rc;
+    Ctx* c = h->ctx;
+    std::lock_guard<std::recursive_mutex> lk(c->mu);
+    const double ratio = seg_floor_ratio(h);
+    const size_t s = h->n, r = sp->radius;
+    std::vector<SegDesc> hits(n);
+    std::vector<am_hit_segment*> dst(n);
+    for (size_t i = 0; i < n; ++i) {
+        if ((rc = seg_desc(h, haystack, len, sample_format, peaks[i], (int)r, ratio, HitWhere{-1, 0, 0, i}, &hits[i]))) return rc;
+        dst[i] = out + i * sp->segments;
+    }
+    // the spans [t - R, t + S + R) of the hits, clipped to the haystack and merged where they overlap or touch, copied
+    // one after the other into the staging buffer; every hit's window pointer then points into its span's copy
+    std::vector<size_t> order(n);
+    for (size_t i = 0; i < n; ++i) order[i] = i;
+    std::sort(order.begin(), order.end(), [&](size_t a, size_t b) { return peaks[a].start < peaks[b].start; });
+    struct Span { size_t lo, hi, off; };
+    std::vector<Span> spans;
+    std::vector<size_t> span_of(n);
+    size_t staged = 0;
+    for (size_t i : order) {
+        const size_t t = (size_t)peaks[i].start, lo = t > r ? t - r : 0, hi = std::min(len, t + s + r);
+        if (!spans.empty() && lo <= spans.back().hi) {
+            staged += std::max(hi, spans.back().hi) - spans.back().hi;
+            spans.back().hi = std::max(hi, spans.back().hi);
+        } else {
+            spans.push_back({lo, hi, staged});
+            staged += hi - lo;
+        }
+        span_of[i] = spans.size() - 1;
+    }
+    if ((rc = c->hit_stage.ensure(4 * staged))) return rc;   // (4 bytes per f32 sample and per i16 stereo frame)
+    for (const Span& sp_ : spans)
+        AM_HIP(hipMemcpyAsync(const_cast<void*>(advance_src(c->hit_stage.p, sp_.off)), advance_src(haystack, sp_.lo), 4 * (sp_.hi - sp_.lo),
+                              hipMemcpyHostToDevice, c->stream));
+    for (size_t i = 0; i < n; ++i) {
+        const Span& sp_ = spans[span_of[i]];
+        hits[i].win = advance_src(c->hit_stage.p, sp_.off + ((size_t)peaks[i].start - sp_.lo));
+    }
+    return score_segments(c, hits, *sp, dst.data());
+}
+
+int am_hit_segments_batch_device(const am_needle* const* needles, size_t n_needles,
+                                 const void* const* d_haystacks, const size_t* lens, size_t n_hay, int sample_format,
+                                 const am_peak* peaks, size_t cap_per_pair, const size_t* n_peaks,
+                                 const am_segment_params* sp, am_hit_segment* out) {
+    int rc;
+    if ((rc = hit_check_format(sample_format))) return rc;
+    if (n_needles == 0 || n_hay == 0) return AM_OK;
+    if (!needles || !d_haystacks || !lens || !n_peaks) return fail(AM_ERR_INVALID_ARG, "null pointer");
+    size_t total = 0;
+    for (size_t q = 0; q < n_needles * n_hay; ++q) total += std::min(n_peaks[q], cap_per_pair);
+    if (total == 0) return AM_OK;
+    if (!peaks || !out || !sp) return fail(AM_ERR_INVALID_ARG, "null pointer");
+    for (size_t j = 0; j < n_needles; ++j)
+        if (!needles[j] || !needles[j]->ctx) return fail(AM_ERR_INVALID_ARG, "needle " + std::to_string(j) + ": null needle handle");
+    if ((rc = check_needle(needles[0]))) return rc;
+    Ctx* c = needles[0]->ctx;
+    for (size_t j = 1; j < n_needles; ++j)
+        if (needles[j]->ctx->device != c->device)
+            return fail(AM_ERR_INVALID_ARG, "needle " + std::to_string(j) + ": on device " + std::to_string(needles[j]->ctx->device) +
+                                                ", needle 0 on device " + std::to_string(c->device));
+    for (size_t j = 0; j < n_needles; ++j)
+        if ((rc = seg_check_params(sp, needles[j]->n, "needle " + std::to_string(j) + ": "))) return rc;
+    std::lock_guard<std::recursive_mutex> lk(c->mu);
+    std::vector<double> ratio(n_needles);
+    for (size_t j = 0; j < n_needles; ++j) ratio[j] = seg_floor_ratio(needles[j]);
+    std::vector<SegDesc> hits;
+    std::vector<am_hit_segment*> dst;
+    hits.reserve(total);
+    dst.reserve(total);
+    for (size_t k = 0; k < n_hay; ++k) {
+        bool checked = false;
+        for (size_t j = 0; j < n_needles; ++j) {
+            const size_t pair = k * n_needles + j, np = std::min(n_peaks[pair], cap_per_pair);
+            if (np == 0) continue;
+            if (!checked) {   // (once per haystack; messages are spelled out only for a refusal)
+                const HitWhere w{(long long)pair, k, j, 0};
+                if (!d_haystacks[k]) return fail(AM_ERR_INVALID_ARG, hit_pair_name(w) + "null haystack");
+                if ((rc = hit_check_device(d_haystacks[k], c->device, w))) return rc;
+                checked = true;
+            }
+            for (size_t i = 0; i < np; ++i) {
+                SegDesc d{};
+                const size_t slot = pair * cap_per_pair + i;
+                if ((rc = seg_desc(needles[j], d_haystacks[k], lens[k], sample_format, peaks[slot], (int)sp->radius, ratio[j],
+                                   HitWhere{(long long)pair, k, j, i}, &d)))
+                    return rc;
+                hits.push_back(d);
+                dst.push_back(out + slot * sp->segments);
+            }
+        }
+    }
+    return score_segments(c, hits, *sp, dst.data());
+}
+
+int am_hit_segments_summary(const am_hit_segment* seg, uint32_t segments, size_t needle_len, float min_ncc,
+                            am_segment_summary* out) {
+    if (!seg || !out) return fail(AM_ERR_INVALID_ARG, "null pointer");
+    if (segments == 0 || segments > needle_len) return fail(AM_ERR_INVALID_ARG, "segments = 0 or > needle length");
+    const double nan = std::nan("");
+    const uint64_t m = segments, s = needle_len;
+    auto start = [&](uint64_t j) { return (double)(j * s / m); };   // a_j (exact: below 2^53)
+    const unsigned absent = AM_HIT_NONFINITE | AM_HIT_BELOW_FLOOR | AM_HIT_EMPTY_SEGMENT;
+    am_segment_summary r{};
+    r.first_present = r.last_present = -1;
+    double covered = 0.0, sx = 0.0, sy = 0.0;
+    std::vector<double> xs, ys;   // centres and lags of the usable segments, in index order
+    for (uint64_t j = 0; j < m; ++j) {
+        const am_hit_segment& q = seg[j];
+        if ((q.flags & absent) || !(q.ncc >= min_ncc)) continue;
+        if (r.first_present < 0) r.first_present = (int32_t)j;
+        r.last_present = (int32_t)j;
+        ++r.n_present;
+        covered += start(j + 1) - start(j);
+        if (q.flags & AM_HIT_UNREFINED) continue;
+        ++r.n_usable;
+        xs.push_back(0.5 * (start(j) + start(j + 1)));
+        ys.push_back(q.lag);
+        sx += xs.back();
+        sy += ys.back();
+    }
+    r.coverage = covered / (double)s;
+    r.drift_ppm = r.start_lag = r.residual_rms = nan;
+    if (r.n_usable >= 2) {
+        const double k = (double)r.n_usable, mx = sx / k, my = sy / k;
+        double sxx = 0.0, sxy = 0.0, res = 0.0;
+        for (size_t i = 0; i < xs.size(); ++i) {
+            sxx += (xs[i] - mx) * (xs[i] - mx);
+            sxy += (xs[i] - mx) * (ys[i] - my);
+        }
+        const double slope = sxy / sxx;
+        r.drift_ppm = 1e6 * slope;
+        r.start_lag = my - slope * mx;
+        for (size_t i = 0; i < xs.size(); ++i) {
+            const double dv = ys[i] - (r.start_lag + slope * xs[i]);
+            res += dv * dv;
+        }
+        r.residual_rms = std::sqrt(res / k);
+    }
+    *out = r;
+    return AM_OK;
+}
+
+}  // extern "C"

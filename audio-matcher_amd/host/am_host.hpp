@@ -75,6 +75,8 @@ struct Arguments {
     bool normalize = false;                   // extension: --normalize, window-energy normalised scores (option "score_norm")
     std::optional<int> normalize_floor_db;    // extension: --normalize-floor DB (option "score_norm_floor_db", 0..200)
     std::optional<float> min_confidence;      // extension: --min-confidence X, drop hits whose exact NCC is below X (am_hit_scores, 0..1)
+    std::uint32_t segments = 0;               // extension: --segments M[:R], per-segment scoring of every printed hit (am_hit_segments), 0 = off
+    std::uint32_t segment_radius = 4;         // ... the lags -R .. R examined per segment
     bool resample = false;                    // extension: --resample, bring the snippet to each main file's rate (am_needle_create_resampled)
     std::optional<std::uint64_t> best;        // extension: --best N, the N best hits per main file, no prominence threshold (am_match_best)
     bool live = false;                        // extension: --live, raw PCM from stdin through a monitor (am_monitor_*)
@@ -116,6 +118,10 @@ inline const char* usage_text() {
            "  --min-confidence X     drop every hit whose normalised cross-correlation with the snippet, computed\n"
            "                         exactly for the hit's own window, is below X (0..1); with --debug, print each\n"
            "                         hit's position, ncc, gain and window level (default: keep every hit)\n"
+           "  --segments M[:R]       after each hit's offset line, print which of M equal parts of the snippet the hit\n"
+           "                         holds ('#' present, '.' absent: the part's NCC against --min-confidence if given,\n"
+           "                         else 0.5), the covered fraction, the drift in ppm and the refined start's lag;\n"
+           "                         each part is matched within R samples (0..16, default 4); M in 1..1024\n"
            "  --resample             match main files of any sample rate: the snippet is resampled to each file's rate\n"
            "                         (scipy's resample_poly filter); without it, a rate mismatch stops the run\n"
            "  --live                 read raw PCM from stdin instead of files (no FILE arguments): a live feed, matched\n"
@@ -123,7 +129,7 @@ inline const char* usage_text() {
            "                         final -- a hit is final once the next hit is found, or once --distance of audio\n"
            "                         has passed behind it, so use a short --distance for monitoring.  At end of input\n"
            "                         the label file (-o FILE; none without -o) is written as for a file.  Needs --rate;\n"
-           "                         --best, --normalize and --min-confidence do not apply\n"
+           "                         --best, --normalize, --min-confidence and --segments do not apply\n"
            "  --rate R               --live: sample rate of the stream, in Hz\n"
            "  --encoding E           --live: s16le (default) or f32le (f32le: one channel only)\n"
            "  --channels C           --live: 1 or 2 (default 2)\n"
@@ -178,6 +184,21 @@ inline Arguments parse_arguments(int argc, const char* const* argv) {
                 throw ArgError("invalid value '" + v + "' for --min-confidence (a number in 0..1)");
             a.min_confidence = x;
         }
+        else if (s == "--segments") {
+            const std::string v = need(i);
+            const std::size_t colon = v.find(':');
+            const std::string vm = v.substr(0, colon), vr = colon == std::string::npos ? "4" : v.substr(colon + 1);
+            auto whole = [](const std::string& t, unsigned long& x) {
+                char* end = nullptr;
+                x = std::strtoul(t.c_str(), &end, 10);
+                return !t.empty() && t[0] >= '0' && t[0] <= '9' && *end == '\0';
+            };
+            unsigned long m = 0, r = 0;
+            if (!whole(vm, m) || !whole(vr, r) || m == 0 || m > 1024 || r > 16)
+                throw ArgError("invalid value '" + v + "' for --segments (M[:R], M in 1..1024 parts, R in 0..16 samples)");
+            a.segments = (std::uint32_t)m;
+            a.segment_radius = (std::uint32_t)r;
+        }
         else if (s == "--resample") a.resample = true;
         else if (s == "--best") {
             const std::string v = need(i);
@@ -215,6 +236,7 @@ inline Arguments parse_arguments(int argc, const char* const* argv) {
         if (a.rate == 0) throw ArgError("--live needs --rate");
         if (a.encoding == "f32le" && a.channels != 1) throw ArgError("--encoding f32le takes one channel only (--channels 1)");
         if (a.best || a.normalize || a.min_confidence) throw ArgError("--live: --best, --normalize and --min-confidence do not apply");
+        if (a.segments) throw ArgError("--live: --segments does not apply");
         return a;
     }
     if (a.no_out && a.out_file) throw ArgError("--no-out and --out are mutually exclusive");      // #[group(multiple = false)]

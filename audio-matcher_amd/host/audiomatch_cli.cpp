@@ -39,6 +39,36 @@ static std::string base_name(const std::string& path) {
     return slash == std::string::npos ? path : path.substr(slash + 1);
 }
 
+// extension: --segments M[:R].  One line per hit, to follow the hit's offset line: the presence mask of the snippet's M
+// parts ('#' present, '.' absent, at min_ncc = --min-confidence if given, else 0.5), coverage, drift and start lag
+// (am_hit_segments + am_hit_segments_summary).
+static std::vector<std::string> segment_lines(const Arguments& args, const am_needle* algo, const std::vector<float>& samples,
+                                              const am_peak* peaks, size_t n) {
+    std::vector<std::string> out;
+    if (n == 0) return out;
+    const am_segment_params sp{args.segments, args.segment_radius};
+    const float min_ncc = args.min_confidence.value_or(0.5f);
+    size_t s_len = 0;
+    am_needle_len(algo, &s_len);
+    std::vector<am_hit_segment> seg(n * sp.segments);
+    if (am_hit_segments(algo, samples.data(), samples.size(), AM_FMT_F32_MONO, peaks, n, &sp, seg.data()) != AM_OK)
+        throw std::runtime_error(std::string("am_hit_segments: ") + am_last_error_string());
+    const unsigned absent = AM_HIT_NONFINITE | AM_HIT_BELOW_FLOOR | AM_HIT_EMPTY_SEGMENT;
+    for (size_t i = 0; i < n; ++i) {
+        const am_hit_segment* q = seg.data() + i * sp.segments;
+        am_segment_summary sm{};
+        if (am_hit_segments_summary(q, sp.segments, s_len, min_ncc, &sm) != AM_OK)
+            throw std::runtime_error(std::string("am_hit_segments_summary: ") + am_last_error_string());
+        std::string mask(sp.segments, '.');
+        for (std::uint32_t j = 0; j < sp.segments; ++j)
+            if (!(q[j].flags & absent) && q[j].ncc >= min_ncc) mask[j] = '#';
+        char tail[128];
+        std::snprintf(tail, sizeof tail, " coverage %.3f drift_ppm %.1f start_lag %.3f", sm.coverage, sm.drift_ppm, sm.start_lag);
+        out.push_back("  segments " + mask + tail);
+    }
+    return out;
+}
+
 // extension: several --snippet files.  Each main file is matched by ONE am_match_multi_varlen call (the snippets may
 // differ in length: each uses an overlap of its own length at the main file's rate, as make_params does for one);
 // with --normalize, which that call refuses, snippet by snippet with am_match.  The label file is timelabel_from_peaks
@@ -173,8 +203,15 @@ static int run_multi(const Arguments& args) {
                     }
                     n[j] = kept;
                 }
-                if (args.verbosity >= 1)
-                    for (const auto& line : offset_lines(pk, n[j], m_sr)) std::printf("%s: %s\n", snips[j].name.c_str(), line.c_str());
+                if (args.verbosity >= 1) {
+                    const std::vector<std::string> lines = offset_lines(pk, n[j], m_sr);
+                    const std::vector<std::string> segs =
+                        args.segments ? segment_lines(args, handles[j], m_samples, pk, n[j]) : std::vector<std::string>();
+                    for (size_t i = 0; i < lines.size(); ++i) {
+                        std::printf("%s: %s\n", snips[j].name.c_str(), lines[i].c_str());
+                        if (i < segs.size()) std::printf("%s: %s\n", snips[j].name.c_str(), segs[i].c_str());
+                    }
+                }
             }
             if (out_path) {
                 std::vector<std::pair<std::uint64_t, size_t>> order;   // (start, slot): sorted by start, then snippet, then position
@@ -431,8 +468,15 @@ int main(int argc, char** argv) {
                 }
                 n = kept;
             }
-            if (args.verbosity >= 1)
-                for (const auto& line : offset_lines(peaks.data(), n, m_sr)) std::printf("%s\n", line.c_str());   // mod.rs:89
+            if (args.verbosity >= 1) {
+                const std::vector<std::string> lines = offset_lines(peaks.data(), n, m_sr);                       // mod.rs:89
+                const std::vector<std::string> segs =
+                    args.segments ? segment_lines(args, algo, m_samples, peaks.data(), n) : std::vector<std::string>();   // extension: --segments
+                for (size_t i = 0; i < lines.size(); ++i) {
+                    std::printf("%s\n", lines[i].c_str());
+                    if (i < segs.size()) std::printf("%s\n", segs[i].c_str());
+                }
+            }
             if (out_path) {                                                   // mod.rs:92-99
                 const std::string text = format_labels(timelabel_from_peaks(peaks.data(), n, m_sr, 7.0, "Segment #"));
                 if (args.dry_run) {

@@ -61,6 +61,28 @@ class AmHitScore(C.Structure):     # am_hit_score (include/audiomatch.h, per-hit
 AM_HIT_UNREFINED, AM_HIT_BELOW_FLOOR, AM_HIT_NONFINITE = 1, 2, 4
 
 
+class AmSegmentParams(C.Structure):   # am_segment_params (include/audiomatch.h, per-segment hit scoring)
+    _fields_ = [("segments", C.c_uint32), ("radius", C.c_uint32)]
+
+
+class HitSegment(C.Structure):        # am_hit_segment: one segment of one hit
+    _fields_ = [("lag", C.c_double), ("ncc", C.c_float), ("gain", C.c_float),
+                ("level_db", C.c_float), ("flags", C.c_uint32)]
+
+    def __repr__(self):
+        return f"HitSegment(lag={self.lag!r}, ncc={self.ncc!r}, gain={self.gain!r}, level_db={self.level_db!r}, flags={self.flags})"
+
+
+class AmSegmentSummary(C.Structure):  # am_segment_summary
+    _fields_ = [("coverage", C.c_double), ("drift_ppm", C.c_double), ("start_lag", C.c_double),
+                ("residual_rms", C.c_double), ("first_present", C.c_int32), ("last_present", C.c_int32),
+                ("n_present", C.c_uint32), ("n_usable", C.c_uint32)]
+
+
+AM_HIT_EMPTY_SEGMENT = 8
+AM_SEG_MAX_SEGMENTS, AM_SEG_MAX_RADIUS = 1024, 16
+
+
 class AmMatchParams(C.Structure):
     _fields_ = [("sr", C.c_uint32), ("chunk", C.c_uint64), ("overlap", C.c_uint64),
                 ("min_prominence", C.c_float), ("min_distance", C.c_uint64),
@@ -209,6 +231,15 @@ _SIGNATURES = {
     "am_hit_scores_batch_device": (C.c_int, [C.POINTER(C.c_void_p), C.c_size_t, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t),
                                              C.c_size_t, C.c_int, C.POINTER(AmPeak), C.c_size_t, C.POINTER(C.c_size_t),
                                              C.POINTER(AmHitScore)]),
+    "am_hit_segments_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.POINTER(AmPeak), C.c_size_t,
+                                         C.POINTER(AmSegmentParams), C.POINTER(HitSegment)]),
+    "am_hit_segments": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.POINTER(AmPeak), C.c_size_t,
+                                  C.POINTER(AmSegmentParams), C.POINTER(HitSegment)]),
+    "am_hit_segments_batch_device": (C.c_int, [C.POINTER(C.c_void_p), C.c_size_t, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t),
+                                               C.c_size_t, C.c_int, C.POINTER(AmPeak), C.c_size_t, C.POINTER(C.c_size_t),
+                                               C.POINTER(AmSegmentParams), C.POINTER(HitSegment)]),
+    "am_hit_segments_summary": (C.c_int, [C.POINTER(HitSegment), C.c_uint32, C.c_size_t, C.c_float,
+                                          C.POINTER(AmSegmentSummary)]),
     "am_resample_len": (C.c_int, [C.c_size_t, C.c_uint32, C.c_uint32, C.POINTER(C.c_size_t)]),
     "am_resample": (C.c_int, [C.c_int, C.c_void_p, C.c_size_t, C.c_int, C.c_uint32, C.c_uint32, C.c_void_p, C.c_size_t,
                               C.POINTER(C.c_size_t)]),
@@ -475,6 +506,35 @@ def _hit_scores(buf, idx):
     return [HitScore(buf[i].position, buf[i].ncc, buf[i].gain, buf[i].window_db, int(buf[i].flags)) for i in idx]
 
 
+def _hit_segments(buf, first, m):
+    """The m records of one hit as a list of HitSegment (copies: they outlive the call's buffer)."""
+    return [HitSegment(buf[first + j].lag, buf[first + j].ncc, buf[first + j].gain, buf[first + j].level_db,
+                       buf[first + j].flags) for j in range(m)]
+
+
+@dataclass
+class SegmentSummary:
+    """am_segment_summary: coverage, drift and refined start of one hit, from its segment records."""
+    coverage: float
+    drift_ppm: float
+    start_lag: float
+    residual_rms: float
+    first_present: int
+    last_present: int
+    n_present: int
+    n_usable: int
+
+
+def hit_segments_summary(segments, needle_len: int, min_ncc: float = 0.5) -> SegmentSummary:
+    """am_hit_segments_summary (pure host code): `segments` = one hit's HitSegment records."""
+    m = len(segments)
+    buf = (HitSegment * max(1, m))(*[HitSegment(q.lag, q.ncc, q.gain, q.level_db, q.flags) for q in segments])
+    out = AmSegmentSummary()
+    _check(lib().am_hit_segments_summary(buf, m, int(needle_len), float(min_ncc), C.byref(out)))
+    return SegmentSummary(out.coverage, out.drift_ppm, out.start_lag, out.residual_rms, out.first_present,
+                          out.last_present, out.n_present, out.n_usable)
+
+
 # ---------------------------------------------------------------------------
 @dataclass
 class Peak:
@@ -707,6 +767,31 @@ class HipConvolve:
         out = (AmHitScore * max(1, k))()
         _check(lib().am_hit_scores_device(self._h, ptr, length, int(fmt), _peak_array(peaks), k, out))
         return _hit_scores(out, range(k))
+
+    # -- per-segment hit scoring --
+    def hit_segments(self, haystack, peaks, segments: int, radius: int = 4):
+        """am_hit_segments: for each of `peaks` of a host haystack (as in hit_scores) the list of its `segments`
+        HitSegment records, lags -radius .. radius examined."""
+        a = np.asarray(haystack)
+        if a.dtype == np.int16:
+            a = np.ascontiguousarray(a)
+            fmt, length = Fmt.S16_STEREO, a.size // 2
+        else:
+            a = np.ascontiguousarray(a, dtype=np.float32)
+            fmt, length = Fmt.F32_MONO, a.size
+        k, m = len(peaks), int(segments)
+        out = (HitSegment * max(1, k * max(m, 0)))()
+        sp = AmSegmentParams(m, int(radius))
+        _check(lib().am_hit_segments(self._h, a.ctypes.data, length, int(fmt), _peak_array(peaks), k, C.byref(sp), out))
+        return [_hit_segments(out, i * m, m) for i in range(k)]
+
+    def hit_segments_device(self, ptr: int, length: int, peaks, segments: int, radius: int = 4, fmt: int = Fmt.F32_MONO):
+        """am_hit_segments_device: the same for a haystack resident on this needle's device."""
+        k, m = len(peaks), int(segments)
+        out = (HitSegment * max(1, k * max(m, 0)))()
+        sp = AmSegmentParams(m, int(radius))
+        _check(lib().am_hit_segments_device(self._h, ptr, length, int(fmt), _peak_array(peaks), k, C.byref(sp), out))
+        return [_hit_segments(out, i * m, m) for i in range(k)]
 
 
 class MatchStream:
@@ -1044,6 +1129,29 @@ def hit_scores_batch_device(algos, ptrs, lengths, peaks_per_pair, fmt: int = Fmt
     out = (AmHitScore * max(1, cap * k * nn))()
     _check(lib().am_hit_scores_batch_device(handles, nn, arr_p, arr_l, k, int(fmt), buf, cap, counts, out))
     return [[_hit_scores(out, range((h * nn + j) * cap, (h * nn + j) * cap + counts[h * nn + j])) for j in range(nn)]
+            for h in range(k)]
+
+
+def hit_segments_batch_device(algos, ptrs, lengths, peaks_per_pair, segments: int, radius: int = 4, fmt: int = Fmt.F32_MONO):
+    """am_hit_segments_batch_device: peaks_per_pair[k][j] as in hit_scores_batch_device; result [k][j][i] = the
+    `segments` HitSegment records of hit i of haystack k against needle j."""
+    nn, k, m = len(algos), len(ptrs), int(segments)
+    cap = max([1] + [len(peaks_per_pair[h][j]) for h in range(k) for j in range(nn)])
+    handles = (C.c_void_p * max(1, nn))(*[a._h for a in algos])
+    arr_p = (C.c_void_p * max(1, k))(*ptrs)
+    arr_l = (C.c_size_t * max(1, k))(*lengths)
+    buf = (AmPeak * max(1, cap * k * nn))()
+    counts = (C.c_size_t * max(1, k * nn))()
+    for h in range(k):
+        for j in range(nn):
+            q = h * nn + j
+            counts[q] = len(peaks_per_pair[h][j])
+            for i, p in enumerate(peaks_per_pair[h][j]):
+                buf[q * cap + i] = AmPeak(int(p.start), int(p.end), float(p.height), float(p.prominence))
+    out = (HitSegment * max(1, cap * k * nn * max(m, 0)))()
+    sp = AmSegmentParams(m, int(radius))
+    _check(lib().am_hit_segments_batch_device(handles, nn, arr_p, arr_l, k, int(fmt), buf, cap, counts, C.byref(sp), out))
+    return [[[_hit_segments(out, ((h * nn + j) * cap + i) * m, m) for i in range(counts[h * nn + j])] for j in range(nn)]
             for h in range(k)]
 
 

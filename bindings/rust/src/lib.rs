@@ -43,6 +43,36 @@ pub struct AmHitScore {
     pub window_db: f32,
     pub flags: u32,
 }
+/// am_segment_params: per-segment hit scoring (am_hit_segments*)
+#[repr(C)]
+#[derive(Clone, Copy, Default, Debug)]
+pub struct AmSegmentParams {
+    pub segments: u32,
+    pub radius: u32,
+}
+/// am_hit_segment: one segment of one hit (24 bytes)
+#[repr(C)]
+#[derive(Clone, Copy, Default, Debug)]
+pub struct AmHitSegment {
+    pub lag: f64,
+    pub ncc: f32,
+    pub gain: f32,
+    pub level_db: f32,
+    pub flags: u32,
+}
+/// am_segment_summary: coverage, drift and refined start of one hit
+#[repr(C)]
+#[derive(Clone, Copy, Default, Debug)]
+pub struct AmSegmentSummary {
+    pub coverage: f64,
+    pub drift_ppm: f64,
+    pub start_lag: f64,
+    pub residual_rms: f64,
+    pub first_present: i32,
+    pub last_present: i32,
+    pub n_present: u32,
+    pub n_usable: u32,
+}
 /// am_best_params: the k best matches (am_match_best*)
 #[repr(C)]
 #[derive(Clone, Copy, Default, Debug)]
@@ -168,6 +198,23 @@ extern "C" {
         needles: *const *const AmNeedle, n_needles: usize, d_haystacks: *const *const std::ffi::c_void, lens: *const usize,
         n_hay: usize, sample_format: c_int, peaks: *const AmPeak, cap_per_pair: usize, n_peaks: *const usize, out: *mut AmHitScore,
     ) -> c_int;
+    /// per-segment hit scoring: which part of the needle a hit holds, and its drift (audiomatch.h)
+    pub fn am_hit_segments(
+        h: *const AmNeedle, haystack: *const std::ffi::c_void, len: usize, sample_format: c_int, peaks: *const AmPeak, n: usize,
+        sp: *const AmSegmentParams, out: *mut AmHitSegment,
+    ) -> c_int;
+    pub fn am_hit_segments_device(
+        h: *const AmNeedle, d_haystack: *const std::ffi::c_void, len: usize, sample_format: c_int, peaks: *const AmPeak, n: usize,
+        sp: *const AmSegmentParams, out: *mut AmHitSegment,
+    ) -> c_int;
+    pub fn am_hit_segments_batch_device(
+        needles: *const *const AmNeedle, n_needles: usize, d_haystacks: *const *const std::ffi::c_void, lens: *const usize,
+        n_hay: usize, sample_format: c_int, peaks: *const AmPeak, cap_per_pair: usize, n_peaks: *const usize,
+        sp: *const AmSegmentParams, out: *mut AmHitSegment,
+    ) -> c_int;
+    pub fn am_hit_segments_summary(
+        seg: *const AmHitSegment, segments: u32, needle_len: usize, min_ncc: f32, out: *mut AmSegmentSummary,
+    ) -> c_int;
     /// the k best matches: the first k peaks of find_peaks over the Valid scores, no prominence threshold (audiomatch.h)
     pub fn am_match_best(
         h: *const AmNeedle, haystack: *const std::ffi::c_void, len: usize, sample_format: c_int, bp: *const AmBestParams,
@@ -264,6 +311,16 @@ pub struct HipConvolve {
 }
 unsafe impl Send for HipConvolve {}
 unsafe impl Sync for HipConvolve {}
+
+/// Coverage, drift and refined start of one hit from its segment records (am_hit_segments_summary; no device needed).
+pub fn segment_summary(seg: &[AmHitSegment], needle_len: usize, min_ncc: f32) -> Result<AmSegmentSummary, Box<dyn std::error::Error>> {
+    let mut out = AmSegmentSummary::default();
+    let rc = unsafe { am_hit_segments_summary(seg.as_ptr(), seg.len() as u32, needle_len, min_ncc, &mut out) };
+    if rc != AM_OK {
+        return Err(am_err(rc));
+    }
+    Ok(out)
+}
 
 impl HipConvolve {
     pub fn new(sample_data: Box<[f32]>) -> Result<Self, Box<dyn std::error::Error>> {
@@ -367,6 +424,22 @@ impl HipConvolve {
         let rc = unsafe {
             am_hit_scores(self.h, m_samples.as_ptr() as *const std::ffi::c_void, m_samples.len(), AM_FMT_F32_MONO, peaks.as_ptr(),
                           peaks.len(), out.as_mut_ptr())
+        };
+        if rc != AM_OK {
+            return Err(am_err(rc));
+        }
+        Ok(out)
+    }
+
+    /// Per-segment hit scoring (am_hit_segments) of `peaks` found in the host haystack `m_samples`: `segments` records
+    /// per peak (peak i at [i * segments, (i + 1) * segments)), lags -radius ..= radius examined per segment.
+    pub fn hit_segments(&self, m_samples: &[f32], peaks: &[AmPeak], segments: u32, radius: u32)
+                        -> Result<Vec<AmHitSegment>, Box<dyn std::error::Error>> {
+        let sp = AmSegmentParams { segments, radius };
+        let mut out = vec![AmHitSegment::default(); peaks.len() * segments as usize];
+        let rc = unsafe {
+            am_hit_segments(self.h, m_samples.as_ptr() as *const std::ffi::c_void, m_samples.len(), AM_FMT_F32_MONO, peaks.as_ptr(),
+                            peaks.len(), &sp, out.as_mut_ptr())
         };
         if rc != AM_OK {
             return Err(am_err(rc));

@@ -251,6 +251,73 @@ int am_hit_scores_batch_device(const am_needle* const* needles, size_t n_needles
                                const void* const* d_haystacks, const size_t* lens, size_t n_hay, int sample_format,
                                const am_peak* peaks, size_t cap_per_pair, const size_t* n_peaks, am_hit_score* out);
 
+/* ---- per-segment hit scoring ----------------------------------------------------- */
+/* Which part of the needle a hit holds, and how its position drifts along the needle: the pass of am_hit_scores
+ * resolved along the needle (the reference reports one offset and one height per hit, matcher/mod.rs:110-125).  The
+ * needle n[0 .. S) is cut into m segments, segment j = needle samples [a_j, a_{j+1}) with a_j = floor(j S / m) (lengths
+ * differ by at most one).  With t = peak.start and x the haystack's samples (f32 mono, or the bit-exact down-mix for
+ * AM_FMT_S16_STEREO as above), x COUNTING AS 0 OUTSIDE [0, len), for every lag l in [-R, R], in f64:
+ *     c_j(l) = sum_{i in seg j} x[t + l + i] n[i],   E_w,j(l) = sum_{i in seg j} x[t + l + i]^2,   E_n,j = sum_{i in seg j} n[i]^2
+ *   l*         the lag with the largest c_j(l); ties go to the smaller |l|, then to the negative lag.
+ *   lag        l* + d,  d = 0.5 (a - c) / (a - 2b + c) clamped to [-0.5, 0.5], a, b, c = c_j(l* - 1), c_j(l*), c_j(l* + 1).
+ *              d = 0 and flag AM_HIT_UNREFINED when R = 0, when |l*| = R or when a - 2b + c >= 0.
+ *   ncc        c_j(l*) / sqrt(E_n,j E_w,j(l*)); 0 with flag AM_HIT_BELOW_FLOOR when E_w,j(l*) = 0 or
+ *              E_w,j(l*) < E_n,j 10^(-score_norm_floor_db / 10) -- the process option am_hit_scores reads at call time,
+ *              applied per segment.
+ *   gain       c_j(l*) / E_n,j.
+ *   level_db   10 log10(E_w,j(l*) / E_n,j); -inf for a silent window.
+ *   flags      AM_HIT_*.  AM_HIT_EMPTY_SEGMENT: E_n,j = 0 (a silent stretch of the needle); lag = 0, ncc = gain = 0,
+ *              level_db = +inf for E_w,j(0) > 0 and NaN for E_w,j(0) = 0, no other flag.  AM_HIT_NONFINITE: a sample of the
+ *              needle's segment, or of x[t - R + a_j .. t + R + a_{j+1}) inside [0, len), is not finite; that segment only
+ *              has lag = 0 and ncc, gain, level_db NaN, no other flag.
+ * A segment's result depends on the needle, the samples it reads, m, R and the floor only: the three forms below agree
+ * bit for bit, whatever else the call holds.  The cost is proportional to hits x S x (2R + 1), not to the haystack.
+ * out holds m records per hit, hit i at out[i m .. (i + 1) m); in the batch form hit slot q of pair p is at
+ * (p cap_per_pair + q) m -- the layout of am_hit_scores_batch_device times m; other slots stay untouched.
+ * AM_ERR_INVALID_ARG, naming the hit (and pair): a null pointer with n > 0, sp == NULL, segments == 0, segments > S or
+ * > AM_SEG_MAX_SEGMENTS, radius > AM_SEG_MAX_RADIUS, an unknown sample format, peak.start + S > len, a haystack on
+ * another device than the needle.  n = 0: AM_OK, nothing launched. */
+enum { AM_HIT_EMPTY_SEGMENT = 8 };
+#define AM_SEG_MAX_SEGMENTS 1024
+#define AM_SEG_MAX_RADIUS   16
+typedef struct am_segment_params {
+    uint32_t segments;   /* m, 1 .. min(S, AM_SEG_MAX_SEGMENTS) */
+    uint32_t radius;     /* R, 0 .. AM_SEG_MAX_RADIUS: lags -R .. R are examined */
+} am_segment_params;
+typedef struct am_hit_segment {
+    double lag;        /* l* + d: where this segment fits best, in samples relative to the hit's start */
+    float ncc;         /* at l* */
+    float gain;        /* at l* */
+    float level_db;    /* 10 log10(E_w / E_n) of the segment at l*; -inf for silence */
+    uint32_t flags;    /* AM_HIT_* */
+} am_hit_segment;      /* 24 bytes, no padding */
+/* the haystack resident on the needle's device */
+int am_hit_segments_device(const am_needle* h, const void* d_haystack, size_t len, int sample_format,
+                           const am_peak* peaks, size_t n, const am_segment_params* sp, am_hit_segment* out);
+/* the haystack in host memory: only the spans [t - R, t + S + R) of the hits are copied (clipped, merged where they overlap) */
+int am_hit_segments(const am_needle* h, const void* haystack, size_t len, int sample_format,
+                    const am_peak* peaks, size_t n, const am_segment_params* sp, am_hit_segment* out);
+/* the pair layout of am_hit_scores_batch_device; every hit of the call in one launch sequence, needles of any lengths */
+int am_hit_segments_batch_device(const am_needle* const* needles, size_t n_needles,
+                                 const void* const* d_haystacks, const size_t* lens, size_t n_hay, int sample_format,
+                                 const am_peak* peaks, size_t cap_per_pair, const size_t* n_peaks,
+                                 const am_segment_params* sp, am_hit_segment* out);
+/* What callers want from one hit's m records (pure host code, no device): a segment is PRESENT when its flags hold none
+ * of NONFINITE | BELOW_FLOOR | EMPTY_SEGMENT and ncc >= min_ncc, USABLE when present and not UNREFINED.  The line is the
+ * ordinary least-squares fit of lag_j against the segment centre (a_j + a_{j+1}) / 2 over the usable segments (sums in
+ * f64, in index order); with fewer than two usable segments drift_ppm, start_lag and residual_rms are NaN.
+ * AM_ERR_INVALID_ARG: a null pointer, segments == 0 or > needle_len. */
+typedef struct am_segment_summary {
+    double coverage;       /* needle samples in present segments / S */
+    double drift_ppm;      /* 1e6 * slope of lag over needle position; NaN with fewer than 2 usable segments */
+    double start_lag;      /* the fitted line at needle position 0: refined start = peak.start + start_lag */
+    double residual_rms;   /* rms of lag - line over the usable segments, samples */
+    int32_t first_present, last_present;   /* segment indices, -1 when none */
+    uint32_t n_present, n_usable;
+} am_segment_summary;
+int am_hit_segments_summary(const am_hit_segment* seg, uint32_t segments, size_t needle_len, float min_ncc,
+                            am_segment_summary* out);
+
 /* ---- streaming ingest ---------------------------------------------------------- */
 /* calc_chunks consumes a lazy ExactSizeIterator<Item = f32> (audio_matcher.rs:88-97): the decoder
  * yields frames (mp3_reader.rs:13-41) and the windows are cut as they arrive (:104).  The same

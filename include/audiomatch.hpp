@@ -141,6 +141,25 @@ public:
         check(am_hit_scores_device(h_, d_haystack, len, sample_format, peaks.data(), peaks.size(), out.data()));
         return out;
     }
+    // per-segment hit scoring (am_hit_segments): sp.segments records per peak, peak i at [i * segments, (i + 1) * segments)
+    std::vector<am_hit_segment> hit_segments(const void* haystack, std::size_t len, int sample_format, const std::vector<am_peak>& peaks,
+                                             const am_segment_params& sp) const {
+        std::vector<am_hit_segment> out(peaks.size() * sp.segments);
+        check(am_hit_segments(h_, haystack, len, sample_format, peaks.data(), peaks.size(), &sp, out.data()));
+        return out;
+    }
+    std::vector<am_hit_segment> hit_segments_device(const void* d_haystack, std::size_t len, int sample_format,
+                                                    const std::vector<am_peak>& peaks, const am_segment_params& sp) const {
+        std::vector<am_hit_segment> out(peaks.size() * sp.segments);
+        check(am_hit_segments_device(h_, d_haystack, len, sample_format, peaks.data(), peaks.size(), &sp, out.data()));
+        return out;
+    }
+    // coverage, drift and refined start of one hit from its records (am_hit_segments_summary; no device needed)
+    static am_segment_summary segment_summary(const am_hit_segment* seg, std::uint32_t segments, std::size_t needle_len, float min_ncc) {
+        am_segment_summary out{};
+        check(am_hit_segments_summary(seg, segments, needle_len, min_ncc, &out));
+        return out;
+    }
     // the k best matches (am_match_best): the best min(k, count) peaks of the haystack's Valid scores by descending
     // height, no prominence threshold needed; am_match_best_device / _batch_device for resident haystacks
     std::vector<am_peak> match_best(const void* haystack, std::size_t len, int sample_format, const am_best_params& bp) const {
