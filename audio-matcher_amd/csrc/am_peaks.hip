@@ -664,11 +664,14 @@ peaks_kernel(const float* g, long long g_len, const float2* stats,
                 __syncthreads();
                 if (wv == 0) {
                     for (int k = 0; k < kWaves; ++k) { lm = fminf(lm, side_s[0][k]); rm = fminf(rm, side_s[1][k]); }
-                    const float prom = M - fmaxf(lm, rm);
+                    // the height as the score array holds it at the peak's start (a tile summary's maximum does not tell
+                    // -0.0 from +0.0, as in finish_best)
+                    const float hM = score_for_cmp(g, sp, pi);
+                    const float prom = hM - fmaxf(lm, rm);
                     const bool keep = prom >= min_prom;
                     if (lane == 0) {
                         if (keep) {
-                            am_peak pk; pk.start = (uint64_t)pi; pk.end = (uint64_t)peak_k_s; pk.height = M; pk.prominence = prom;
+                            am_peak pk; pk.start = (uint64_t)pi; pk.end = (uint64_t)peak_k_s; pk.height = hM; pk.prominence = prom;
                             hdr[blockIdx.x].first[0] = pk;
                             my_out[0] = pk;
                             hdr[blockIdx.x].n = 1; hdr[blockIdx.x].overflow = 0; hdr[blockIdx.x].seg_min = seg_min; hdr[blockIdx.x].arena_off = -1;
