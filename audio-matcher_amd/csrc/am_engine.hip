@@ -595,7 +595,7 @@ int match_many(am_needle* h, const void* const* d_hays, const size_t* lens, size
 // BASELINE config 4: several needles against a batch of resident haystacks = the per-file loop of
 // matcher::run (matcher/mod.rs:42-87) around N snippets.  Per haystack the forward column pass (K1)
 // runs once; needles are then taken in groups that share the forward row transforms of K2
-// (k2_rows_r16_group), each needle with its own inverse rows, K3 (fused scan) and peak pick.  The
+// (k2_rows_r16_group_planes), each needle with its own inverse rows, K3 (fused scan) and peak pick.  The
 // pick of (haystack, needle) runs on the second stream beside the next needle's K3 / the next
 // haystack's K1 and K2; the score-side buffers alternate between two sets, as in match_many.
 // Needles must share one length, unless `varlen` (am_match_multi_varlen*): then every haystack has ONE block layout,

@@ -31,20 +31,26 @@
 //            coalesced HBM accesses.
 //   *_c1024: K1/K3 for N = 2^23 = 1024 x 8192 (needles above 34 s; needle partitioning above 2^22 samples).
 //   *_gen  : any N = 2^10 .. 2^23 (small inputs, forced plans): in-LDS radix-4 passes.
-// K2 of the register plans is k2_rows_r16_planes (the row crosses LDS one 32 KB plane at a time: four
-// workgroups per CU -- the row kernel is bound by VALU issue), k2_rows_r16_group_planes
-// for several needles, k2_rows_h16 with packed-f16 butterflies.  Twiddle powers come from TWO table entries
-// per pass boundary (w and w^4, twiddle_apply / twiddle_chain below): a power e of one rounded entry carries
-// e times its rounding error.
-// The needle spectrum is produced by the same K1/K2 code of the same flavour
-// and therefore always lives in the layout the multiply expects.
+//   512 x 16384 (N = 2^23) runs the *_c512 column kernels on longer rows (am_debug_column_bench; no row kernel).
+// K2 of every plan with 8192-point rows:
+//   k2_rows_r16_planes       f32 butterflies, f32 or f16 storage; the row crosses LDS one 32 KB plane at a time: four
+//                            workgroups per CU -- the row kernel is bound by VALU issue
+//   k2_rows_r16_group_planes the same for a group of needles: one forward transform, one inverse per needle
+//   k2_rows_h16              packed-f16 butterflies (half_pipeline = 2); k2_rows_m16: the same on the matrix cores (opt-in)
+//   k2_rows_r16_spectrum     the needle's spectrum: forward passes only
+//   tail_*                   the 256-row kernels under names of their own, for a haystack's odd last block
+// Twiddle powers come from TWO table entries per pass boundary (w and w^4, twiddle_apply / twiddle_chain below): a
+// power e of one rounded entry carries e times its rounding error.
+// The needle spectrum is produced by the same K1 / forward-K2 code and therefore always lives in the layout the
+// multiply expects.
+// Every variant of these kernels (sample kind, half level, accumulate / redo, tail) is one row of a table in the launch
+// layer at the end of the file; nothing in this file is switched by the preprocessor.
 #include "am_kernels.h"
 
 #include <float.h>
 #include <stdlib.h>
 #include <algorithm>
 #include <atomic>
-#include <type_traits>
 #include <hip/hip_fp16.h>
 
 namespace am {
@@ -133,35 +139,9 @@ __device__ __forceinline__ h2 mul_w32(h2 d, int idx) {
     return __builtin_elementwise_fma(d.yx, (h2){s, -s}, t);
 }
 
-// Packed single precision: a complex point as one 64-bit register pair, so that a complex add is
-// one v_pk_add_f32 and a complex multiply one v_pk_mul_f32 + one v_pk_fma_f32 (the swap and the
-// signs ride on op_sel / neg modifiers) -- half the VALU instructions of the scalar form.  Measured,
-// not adopted (AM_K3_PK): a packed instruction takes about 1.75x the issue time of a scalar one.
-typedef float p2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ p2 cadd(p2 a, p2 b) { return a + b; }
-__device__ __forceinline__ p2 csub(p2 a, p2 b) { return a - b; }
-__device__ __forceinline__ p2 cmul(p2 a, p2 b) {
-    const p2 t = a * b.xx;
-    return __builtin_elementwise_fma(a.yx, (p2){-b.y, b.y}, t);
-}
-__device__ __forceinline__ p2 mul_neg_i(p2 a) { return (p2){a.y, -a.x}; }
-__device__ __forceinline__ p2 mul_pos_i(p2 a) { return (p2){-a.y, a.x}; }
-__device__ __forceinline__ p2 to_p2(float2 v) { return (p2){v.x, v.y}; }
 // u + sgn * v (the radix-2 stage of the 512-point column transform)
-__device__ __forceinline__ p2 add_signed(float2 u, float2 v, float sgn, p2) {
-    return __builtin_elementwise_fma(to_p2(v), (p2){sgn, sgn}, to_p2(u));
-}
-__device__ __forceinline__ float2 add_signed(float2 u, float2 v, float sgn, float2) {
+__device__ __forceinline__ float2 add_signed(float2 u, float2 v, float sgn) {
     return make_float2(fmaf(sgn, v.x, u.x), fmaf(sgn, v.y, u.y));
-}
-template <bool INV>
-__device__ __forceinline__ p2 mul_w32(p2 d, int idx) {
-    if (idx == 0) return d;
-    if (idx == 8) return INV ? mul_pos_i(d) : mul_neg_i(d);
-    const float c = kCos32[idx], s = kSin32[idx];
-    const p2 t = d * (p2){c, c};
-    if (INV) return __builtin_elementwise_fma(d.yx, (p2){-s, s}, t);
-    return __builtin_elementwise_fma(d.yx, (p2){s, -s}, t);
 }
 
 template <int R, bool INV, typename T>
@@ -208,32 +188,6 @@ __device__ __forceinline__ void twiddle_apply(h2* x, float2 w) {
         const float2 v = cmul(pw[(e + 1) / 2], pw[e / 2]);
         if (e <= R / 2) pw[e] = v;
         x[BREV ? brev<R>(e) : e] = cmul(x[BREV ? brev<R>(e) : e], to_h2(v));
-    }
-}
-// packed single precision: powers and products in packed form
-template <int R, bool CONJ, bool BREV>
-__device__ __forceinline__ void twiddle_apply(p2* x, float2 w) {
-    p2 pw[R / 2 + 1];
-    if (CONJ) w.y = -w.y;
-    pw[1] = to_p2(w);
-    x[BREV ? brev<R>(1) : 1] = cmul(x[BREV ? brev<R>(1) : 1], pw[1]);
-#pragma unroll
-    for (int e = 2; e < R; ++e) {
-        const p2 v = cmul(pw[(e + 1) / 2], pw[e / 2]);
-        if (e <= R / 2) pw[e] = v;
-        x[BREV ? brev<R>(e) : e] = cmul(x[BREV ? brev<R>(e) : e], v);
-    }
-}
-template <int R, bool CONJ, bool BREV>
-__device__ __forceinline__ void twiddle_chain(p2* x, float2 base, float2 step) {
-    if (CONJ) { base.y = -base.y; step.y = -step.y; }
-    p2 c = to_p2(base);
-    const p2 st = to_p2(step);
-    x[0] = cmul(x[0], c);
-#pragma unroll
-    for (int e = 1; e < R; ++e) {
-        c = cmul(c, st);
-        x[BREV ? brev<R>(e) : e] = cmul(x[BREV ? brev<R>(e) : e], c);
     }
 }
 // two half-precision columns that take the same twiddles (the column passes: the pass twiddle does
@@ -293,7 +247,6 @@ __device__ __forceinline__ void twiddle_nat(T* x, float2 w) { twiddle_apply<R, C
 // the reference's correlation KAT).  13 products instead of 14, four live powers instead of eight.
 __device__ __forceinline__ float2 tw_as(float2 v, float2) { return v; }
 __device__ __forceinline__ h2 tw_as(float2 v, h2) { return to_h2(v); }
-__device__ __forceinline__ p2 tw_as(float2 v, p2) { return to_p2(v); }
 template <int R, bool CONJ, bool BREV, typename T>
 __device__ __forceinline__ void twiddle_apply(T* x, float2 w, float2 w4) {
     static_assert(R == 16, "powers 1..15 from w and w^4");
@@ -341,48 +294,12 @@ __device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const void* p, unsig
 }
 // Cache policy of the work-matrix stream (aux of the raw buffer builtins on gfx940+: bit 0 =
 // sc0, bit 1 = nt, bit 4 = sc1).  The work matrix is read once and written once per kernel; the
-// needle-spectrum rows and the twiddle tables are what should stay in L2.  The defaults are the
-// measured best (tools/ntbench.hip); the macros exist for A/B builds.
-#ifndef AM_K2_LOAD_AUX
-#define AM_K2_LOAD_AUX 0
-#endif
-#ifndef AM_K2_STORE_AUX
-#define AM_K2_STORE_AUX 0
-#endif
-#ifndef AM_K1_STORE_NT
-#define AM_K1_STORE_NT 0
-#endif
-#ifndef AM_K3_LOAD_NT
-#define AM_K3_LOAD_NT 1   // K3's once-read column loads: 0.180 -> 0.156 ms per 1 h haystack (profiles/r02/nt_ab.txt)
-#endif
-#ifndef AM_K3H_LOAD_AUX
-#define AM_K3H_LOAD_AUX 2   // K3's column loads from a half-storage work matrix: nt, as the f32 form's
-#endif
-#ifndef AM_K1_LOAD_NT
-#define AM_K1_LOAD_NT 1   // K1's sample loads: 0.269 -> 0.261 ms with the 512-row kernel (profiles/r02/nt_ab_c512.txt)
-#endif
+// needle-spectrum rows and the twiddle tables are what should stay in L2.  Each kernel's policy is a
+// constant beside it, with the measurement that chose it (tools/ntbench.hip).
 template <int AUX = 0>
 __device__ __forceinline__ float4 buf_load4(__amdgpu_buffer_rsrc_t r, unsigned voff, unsigned soff) {
     const f32x4 v = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r, voff, soff, AUX));
     return make_float4(v.x, v.y, v.z, v.w);
-}
-// 16-byte global accesses with an optional nt bit (column passes: K1's stores, K3's loads)
-template <int NT>
-__device__ __forceinline__ float4 load_f4(const float4* p) {
-    if (NT) {
-        const f32x4 v = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(p));
-        return make_float4(v.x, v.y, v.z, v.w);
-    }
-    return *p;
-}
-template <int NT>
-__device__ __forceinline__ void store_f4(float4* p, float4 v) {
-    if (NT) {
-        f32x4 o; o.x = v.x; o.y = v.y; o.z = v.z; o.w = v.w;
-        __builtin_nontemporal_store(o, reinterpret_cast<f32x4*>(p));
-    } else {
-        *p = v;
-    }
 }
 // A 16-byte store reads its four data VGPRs over several cycles after issue.  hipcc (ROCm 7.2)
 // keeps the documented wait state before a VALU write of one of them only when the store has no
@@ -455,10 +372,12 @@ __device__ __forceinline__ float2 decode_sample2(uint2 raw) {
     return make_float2(downmix_s16(a), downmix_s16(b));
 }
 // two consecutive samples from an 8-byte aligned position
+// K1's sample loads are read once: nt, 0.269 -> 0.261 ms with the 512-row kernel (profiles/r02/nt_ab_c512.txt)
+constexpr bool kK1LoadNt = true;
 template <int KIND>
 __device__ __forceinline__ float2 load_sample2(const void* __restrict__ src, long long i) {
     if (KIND == 0) {
-        if (AM_K1_LOAD_NT) {
+        if (kK1LoadNt) {
             const f32x2 v = __builtin_nontemporal_load(reinterpret_cast<const f32x2*>(static_cast<const float*>(src) + i));
             return make_float2(v.x, v.y);
         }
@@ -466,7 +385,7 @@ __device__ __forceinline__ float2 load_sample2(const void* __restrict__ src, lon
     }
     typedef int i32x2 __attribute__((ext_vector_type(2)));
     const i32x2* p = reinterpret_cast<const i32x2*>(static_cast<const short2*>(src) + i);
-    const i32x2 raw = AM_K1_LOAD_NT ? __builtin_nontemporal_load(p) : *p;   // (read once, like the f32 samples)
+    const i32x2 raw = kK1LoadNt ? __builtin_nontemporal_load(p) : *p;   // (read once, like the f32 samples)
     const int lo = raw.x, hi = raw.y;
     return make_float2(downmix_s16(__builtin_bit_cast(short2, lo)), downmix_s16(__builtin_bit_cast(short2, hi)));
 }
@@ -623,8 +542,8 @@ __device__ __forceinline__ void k1_cols_fwd_r16_tile(const Job& job, float2* __r
 #pragma unroll
     for (int bp = 0; bp < 16; ++bp) {
         const size_t k1 = (size_t)(hi + 16 * bp);
-        store_f4<AM_K1_STORE_NT>(out4 + k1 * (kN2 / 2), make_float4(x0[brev<16>(bp)].x, x0[brev<16>(bp)].y,
-                                                                    x1[brev<16>(bp)].x, x1[brev<16>(bp)].y));
+        out4[k1 * (kN2 / 2)] = make_float4(x0[brev<16>(bp)].x, x0[brev<16>(bp)].y,
+                                             x1[brev<16>(bp)].x, x1[brev<16>(bp)].y);
     }
 }
 template <int KIND, int HALF>
@@ -676,21 +595,14 @@ __device__ __forceinline__ K2Lane k2_lane(const PlanDev& pl, int t = threadIdx.x
 }
 
 // row load + forward passes 1 and 2; leaves the row in LDS in the layout pass 3 reads
-template <bool HALF>
 __device__ __forceinline__ void k2_forward12(const K2Lane& k, __amdgpu_buffer_rsrc_t rrow, float4* lds4) {
     const int t = k.t, hi = k.hi, cp = k.cp;
     float2 x0[16], x1[16];
 #pragma unroll
     for (int a = 0; a < 16; ++a) {   // elements a*512 + 2t, +1
-        if (HALF) {
-            const uint2 v = buf_load_u2(rrow, k.voff / 2, a * 2048);
-            x0[a] = unpack_h2(v.x);
-            x1[a] = unpack_h2(v.y);
-        } else {
-            const float4 v = buf_load4<AM_K2_LOAD_AUX>(rrow, k.voff, a * 4096);
-            x0[a] = make_float2(v.x, v.y);
-            x1[a] = make_float2(v.z, v.w);
-        }
+        const float4 v = buf_load4(rrow, k.voff, a * 4096);
+        x0[a] = make_float2(v.x, v.y);
+        x1[a] = make_float2(v.z, v.w);
     }
     // ---- pass 1 over a (stride 512), twiddle W_8192^(j*a'), j = 2t, 2t+1 ----
     dif<16, false>(x0);
@@ -732,23 +644,10 @@ __device__ __forceinline__ void k2_forward3(const K2Lane& k, const float4* lds4,
     dif<32, false>(z);
 }
 
-// pointwise multiply (pairwise_mult_in_place, audio_matcher.rs:432-438)
-// q = z * h in the order the inverse wants (z[r] holds frequency brev(r); the inverse takes natural order)
-template <bool HALF>
-__device__ __forceinline__ void k2_multiply(const float2 (&z)[32], const float4 (&h)[16], float hscale, float2 (&q)[32]) {
-#pragma unroll
-    for (int i = 0; i < 16; ++i) {
-        // hscale: half storage only (it keeps the stored values well inside f16's range); the f32 form
-        // does not spend 64 multiplications by one on it
-        const float s = HALF ? hscale : 1.0f;
-        q[brev<32>(2 * i)] = cmul(z[2 * i], HALF ? make_float2(h[i].x * s, h[i].y * s) : make_float2(h[i].x, h[i].y));
-        q[brev<32>(2 * i + 1)] = cmul(z[2 * i + 1], HALF ? make_float2(h[i].z * s, h[i].w * s) : make_float2(h[i].z, h[i].w));
-    }
-}
-// The same with the spectrum row fetched a quarter at a time (needle-group kernel: z
-// stays live across needles, so z, q and a whole spectrum row do not fit the register
-// file together).  The fetch of a quarter is in flight while the previous one is used;
-// `first` is quarter 0, requested by the caller ahead of time.
+// pointwise multiply (pairwise_mult_in_place, audio_matcher.rs:432-438): q = z * h in the order the inverse wants
+// (z[r] holds frequency brev(r); the inverse takes natural order), with the spectrum row fetched a quarter at a
+// time: z, q and a whole spectrum row do not fit the register file together.  The fetch of a quarter is in flight
+// while the previous one is used; `first` is quarter 0, requested by the caller ahead of time.
 __device__ __forceinline__ void k2_fetch_quarter(__amdgpu_buffer_rsrc_t rh, unsigned voff, int part, float4 (&h)[4]) {
 #pragma unroll
     for (int i = 0; i < 4; ++i) h[i] = buf_load4(rh, voff, (part * 4 + i) * 4096);
@@ -776,58 +675,6 @@ __device__ __forceinline__ void k2_multiply_fetch(const float2 (&z)[32], __amdgp
     k2_multiply_quarter(z, ha, 3, q);
 }
 
-// inverse passes 3, 2, 1 of the product q and the row store
-template <bool HALF, int SAUX = AM_K2_STORE_AUX>
-__device__ __forceinline__ void k2_inverse(const K2Lane& k, float2 (&q)[32], float4* lds4, __amdgpu_buffer_rsrc_t rdst) {
-    const int t = k.t, hi = k.hi, cp = k.cp;
-    // ---- inverse pass 3 over c' ----
-    dif<32, true>(q);   // time index c at q[brev(c)]
-#pragma unroll
-    for (int i = 0; i < 16; ++i)   // own row again, no barrier needed before
-        lds4[t * 16 + (i ^ cp)] = make_float4(q[brev<32>(2 * i)].x, q[brev<32>(2 * i)].y,
-                                              q[brev<32>(2 * i + 1)].x, q[brev<32>(2 * i + 1)].y);
-    wave_sync_lds();   // this exchange stays inside one wavefront (rows 64w .. 64w+63 <-> threads of wave w)
-    // ---- inverse pass 2 over b': conj twiddle first, then butterflies ----
-    float2 x0[16], x1[16];
-#pragma unroll
-    for (int bp = 0; bp < 16; ++bp) {
-        const float4 v = lds4[(hi * 16 + bp) * 16 + (cp ^ bp)];
-        x0[bp] = make_float2(v.x, v.y);
-        x1[bp] = make_float2(v.z, v.w);
-    }
-    twiddle_nat<16, true>(x0, k.wc0, k.qc0);
-    twiddle_nat<16, true>(x1, k.wc1, k.qc1);
-    dif<16, true>(x0);
-    dif<16, true>(x1);
-    wave_sync_lds();   // this exchange stays inside one wavefront (rows 64w .. 64w+63 <-> threads of wave w)
-#pragma unroll
-    for (int b = 0; b < 16; ++b)
-        lds4[hi * 256 + b * 16 + cp] = make_float4(x0[brev<16>(b)].x, x0[brev<16>(b)].y,
-                                                   x1[brev<16>(b)].x, x1[brev<16>(b)].y);
-    __syncthreads();
-    // ---- inverse pass 1 over a' ----
-#pragma unroll
-    for (int ap = 0; ap < 16; ++ap) {
-        const float4 v = lds4[ap * 256 + t];
-        x0[ap] = make_float2(v.x, v.y);
-        x1[ap] = make_float2(v.z, v.w);
-    }
-    twiddle_nat<16, true>(x0, k.wj0, k.qj0);
-    twiddle_nat<16, true>(x1, k.wj1, k.qj1);
-    dif<16, true>(x0);
-    dif<16, true>(x1);
-    if (HALF) {
-#pragma unroll
-        for (int a = 0; a < 16; ++a)
-            buf_store_u2(rdst, k.voff / 2, a * 2048, make_uint2(pack_h2(x0[brev<16>(a)]), pack_h2(x1[brev<16>(a)])));
-        return;
-    }
-#pragma unroll
-    for (int a = 0; a < 16; ++a)
-        buf_store4<SAUX>(rdst, k.voff, a * 4096, make_float4(x0[brev<16>(a)].x, x0[brev<16>(a)].y,
-                                                       x1[brev<16>(a)].x, x1[brev<16>(a)].y));
-}
-
 // Workgroups are dealt round-robin over the 8 XCDs (speed only, never
 // correctness): give every XCD whole rows, so that the needle-spectrum row
 // shared by all pairs is fetched into that XCD's L2 once.
@@ -837,50 +684,29 @@ __device__ __forceinline__ void k2_place(unsigned npairs, unsigned& row, unsigne
     slot = seq % npairs;
 }
 
-// SPECTRUM = true stores conj(FFT)/N of the needle instead (fft_b, the conj of
-// pairwise_mult_in_place and the 1/len of audio_matcher.rs:430-442 folded into
-// one table).
-template <bool SPECTRUM, bool HALF>
+// The needle's spectrum: forward row transform only, stored as conj(FFT)/N (fft_b, the conj of
+// pairwise_mult_in_place and the 1/len of audio_matcher.rs:430-442 folded into one table) in the register order of
+// pass 3, which is the order every row kernel multiplies in.  The whole row crosses LDS at once (64 KB): this kernel
+// runs once per needle.  (The parameter list is the row kernels'; hc and hscale are not read.)
 __global__ void __launch_bounds__(256, 2)
-k2_rows_r16(float2* __restrict__ work, const float2* __restrict__ hc, float2* __restrict__ hc_out, PlanDev pl,
-            unsigned npairs, float hscale) {
+k2_rows_r16_spectrum(float2* __restrict__ work, const float2* __restrict__ hc, float2* __restrict__ hc_out, PlanDev pl,
+                     unsigned npairs, float hscale) {
     extern __shared__ float4 lds4[];
     unsigned row, slot;
     k2_place(npairs, row, slot);
     const size_t row_off = ((size_t)slot << pl.logN) + (size_t)row * kN2;
-    // one point is 8 bytes (float2) or, with half storage, 4 bytes (__half2)
-    const __amdgpu_buffer_rsrc_t rrow = HALF ? make_rsrc(reinterpret_cast<unsigned*>(work) + row_off, kN2 * 4)
-                                             : make_rsrc(work + row_off, kN2 * 8);
+    const __amdgpu_buffer_rsrc_t rrow = make_rsrc(work + row_off, kN2 * 8);
     const size_t hoff4 = (size_t)row * (kN2 / 2);
     const K2Lane k = k2_lane(pl);
-    k2_forward12<HALF>(k, rrow, lds4);
-    // the needle-spectrum row (L2-resident) is requested here, where only the 32
-    // points of pass 3 are live, so that its latency hides behind that pass
-    float4 h[16];
-    if (!SPECTRUM) {
-        __builtin_amdgcn_sched_barrier(0);
-        const __amdgpu_buffer_rsrc_t rh = make_rsrc(reinterpret_cast<const float4*>(hc) + hoff4, kN2 * 8);
-#pragma unroll
-        for (int i = 0; i < 16; ++i) h[i] = buf_load4(rh, k.voff, i * 4096);
-        __builtin_amdgcn_sched_barrier(0);
-    }
+    k2_forward12(k, rrow, lds4);
     float2 z[32];
     k2_forward3(k, lds4, z);
-    if (SPECTRUM) {
-        const float invN = 1.0f / (float)(1u << pl.logN);
-        const __amdgpu_buffer_rsrc_t rho = make_rsrc(reinterpret_cast<float4*>(hc_out) + hoff4, kN2 * 8);
+    const float invN = 1.0f / (float)(1u << pl.logN);
+    const __amdgpu_buffer_rsrc_t rho = make_rsrc(reinterpret_cast<float4*>(hc_out) + hoff4, kN2 * 8);
 #pragma unroll
-        for (int i = 0; i < 16; ++i)
-            buf_store4(rho, k.voff, i * 4096, make_float4(z[2 * i].x * invN, -z[2 * i].y * invN,
-                                                         z[2 * i + 1].x * invN, -z[2 * i + 1].y * invN));
-        return;
-    }
-    // in place, or into a second work matrix (hc_out doubles as that destination)
-    const __amdgpu_buffer_rsrc_t rdst = !hc_out ? rrow
-        : HALF ? make_rsrc(reinterpret_cast<unsigned*>(hc_out) + row_off, kN2 * 4) : make_rsrc(hc_out + row_off, kN2 * 8);
-    float2 q[32];
-    k2_multiply<HALF>(z, h, hscale, q);
-    k2_inverse<HALF>(k, q, lds4, rdst);
+    for (int i = 0; i < 16; ++i)
+        buf_store4(rho, k.voff, i * 4096, make_float4(z[2 * i].x * invN, -z[2 * i].y * invN,
+                                                     z[2 * i + 1].x * invN, -z[2 * i + 1].y * invN));
 }
 
 // K2 with half-precision butterflies (option half_pipeline = 2, BASELINE config 5's "f16 FFT
@@ -893,9 +719,7 @@ k2_rows_r16(float2* __restrict__ work, const float2* __restrict__ hc, float2* __
 constexpr int kK2hSlab = 272;                  // 8-byte elements per a' (256 + 16)
 constexpr int kK2hLds = 16 * kK2hSlab * 8;     // 34 816 bytes
 
-#ifndef AM_K2H_WGS
-#define AM_K2H_WGS 3   // waves per SIMD the register allocation has to allow (3 and 4 measure the same; 4 spills)
-#endif
+constexpr int kK2hWaves = 3;   // waves per SIMD the register allocation has to allow (3 and 4 measure the same; 4 spills)
 __device__ __forceinline__ void k2_rows_h16_row(unsigned* __restrict__ work, const unsigned* __restrict__ hc16, unsigned* __restrict__ dst,
                                                 const PlanDev& pl, unsigned npairs, float pre) {
     extern __shared__ float4 lds4[];
@@ -1004,33 +828,29 @@ __device__ __forceinline__ void k2_rows_h16_row(unsigned* __restrict__ work, con
     for (int a = 0; a < 16; ++a)
         buf_store_u2(rdst, k.voff / 2, a * 2048, make_uint2(h2_bits(x0[brev<16>(a)]), h2_bits(x1[brev<16>(a)])));
 }
-__global__ void __launch_bounds__(256, AM_K2H_WGS)
+__global__ void __launch_bounds__(256, kK2hWaves)
 k2_rows_h16(unsigned* __restrict__ work, const unsigned* __restrict__ hc16, unsigned* __restrict__ dst, PlanDev pl, unsigned npairs,
             float pre) {
     k2_rows_h16_row(work, hc16, dst, pl, npairs, pre);
 }
 // (the same kernel for a haystack's odd last block on the smaller plan -- launch_k2(..., tail) -- under a name of its
 // own: a profile's average for k2_rows_h16 stays that of the main pass's launches)
-__global__ void __launch_bounds__(256, AM_K2H_WGS)
+__global__ void __launch_bounds__(256, kK2hWaves)
 tail_rows_h16(unsigned* __restrict__ work, const unsigned* __restrict__ hc16, unsigned* __restrict__ dst, PlanDev pl, unsigned npairs,
               float pre) {
     k2_rows_h16_row(work, hc16, dst, pl, npairs, pre);
 }
 
 // K2 in f32 with the row exchanged one PLANE at a time (the points a thread holds as x0, then those it
-// holds as x1: every exchange of the kernel keeps the two apart, see k2_forward12 / k2_inverse), in the
+// holds as x1: every exchange of the kernel keeps the two apart, see k2p_forward / k2p_inverse), in the
 // 8-byte layout of k2_rows_h16: 34 KB of LDS instead of 64 and, with the needle-spectrum row fetched by
 // halves, at most 168 registers -- three workgroups per CU instead of two.  Why that matters: K2 is bound
 // by VALU issue, not by its stream (SQ counters, DESIGN.md section 5: 3292 VALU instructions per wave, the
 // SIMDs' VALU busy in 90 % of the kernel's cycles at one instruction per four cycles); one wave issues a
 // VALU instruction at most every eight cycles, two waves per SIMD reach one per four, three and more one
 // per 3.2 - 3.5 (tools/pkbench).  The two cross-wave exchanges cost three barriers each instead of one.
-#ifndef AM_K2_PLANES
-#define AM_K2_PLANES 1
-#endif
-#ifndef AM_K2P_WAVES
-#define AM_K2P_WAVES 4   // (both forms fit 124 registers: four workgroups per CU, 136 KB of LDS)
-#endif
+// (The form that exchanged the whole row at once was removed: profiles/r03/k2_planes_k3_diet_ab.txt.)
+constexpr int kK2pWaves = 4;   // (both storage forms fit 124 registers: four workgroups per CU, 136 KB of LDS)
 // row load, forward passes 1 and 2 and the exchange into pass 3's layout: z[r] = point r of the thread's row u = t
 template <bool HALF>
 __device__ __forceinline__ void k2p_forward(const K2Lane& k, __amdgpu_buffer_rsrc_t rrow, float2* lds2, float2 (&z)[32]) {
@@ -1043,7 +863,7 @@ __device__ __forceinline__ void k2p_forward(const K2Lane& k, __amdgpu_buffer_rsr
             x0[a] = unpack_h2(v.x);
             x1[a] = unpack_h2(v.y);
         } else {
-            const float4 v = buf_load4<AM_K2_LOAD_AUX>(rrow, k.voff, a * 4096);
+            const float4 v = buf_load4(rrow, k.voff, a * 4096);
             x0[a] = make_float2(v.x, v.y);
             x1[a] = make_float2(v.z, v.w);
         }
@@ -1090,7 +910,7 @@ __device__ __forceinline__ void k2p_forward(const K2Lane& k, __amdgpu_buffer_rsr
 // boundary's at the start: the needle-group kernel, which carries the forward spectrum through this function, gets
 // from 12 spilled registers to 5 with it (1.46 -> 1.37 ms per launch); the single-needle kernel has the registers
 // and measures 2 % slower with the later fetch.
-template <bool HALF, int SAUX = AM_K2_STORE_AUX, bool LATE_J = false>
+template <bool HALF, int SAUX = 0, bool LATE_J = false>
 __device__ __forceinline__ void k2p_inverse(const PlanDev& pl, float2 (&q)[32], float2* lds2, __amdgpu_buffer_rsrc_t rdst) {
     // the lane's twiddle seeds are fetched again (L1 / L2 hits, in flight behind pass 3) instead of kept alive
     // across the product: sixteen registers the multiply, the kernel's widest point, does not have
@@ -1217,32 +1037,29 @@ __device__ __forceinline__ void k2_rows_r16_planes_row(float2* __restrict__ work
     k2p_inverse<HALF>(pl, q, lds2, rdst);
 }
 template <bool HALF>
-__global__ void __launch_bounds__(256, AM_K2P_WAVES)
+__global__ void __launch_bounds__(256, kK2pWaves)
 k2_rows_r16_planes(float2* __restrict__ work, const float2* __restrict__ hc, float2* __restrict__ dst, PlanDev pl, unsigned npairs,
                    float hscale) {
     k2_rows_r16_planes_row<HALF>(work, hc, dst, pl, npairs, hscale);
 }
 template <bool HALF>   // (a haystack's odd last block: see tail_rows_h16)
-__global__ void __launch_bounds__(256, AM_K2P_WAVES)
+__global__ void __launch_bounds__(256, kK2pWaves)
 tail_rows_r16_planes(float2* __restrict__ work, const float2* __restrict__ hc, float2* __restrict__ dst, PlanDev pl, unsigned npairs,
                      float hscale) {
     k2_rows_r16_planes_row<HALF>(work, hc, dst, pl, npairs, hscale);
 }
 
-// The needle-group kernel (below) on the same plane-by-plane exchanges.
-#ifndef AM_K2G_PLANES
-#define AM_K2G_PLANES 1
-#endif
-#ifndef AM_K2GP_WAVES
-#define AM_K2GP_WAVES 3
-#endif
-#ifndef AM_K2G_STORE_AUX
-// cache policy of the group kernels' eight write streams: 2 = nt.  With the plane-wise kernel at three waves per
-// SIMD nt stores take 6.05 ms per call of 32 needles x 22 pairs against 6.6 (and against 6.5 for the 64 KB form at
-// two waves per SIMD, where nt made no difference: profiles/r03/k2_group_ab.txt)
-#define AM_K2G_STORE_AUX 2
-#endif
-__global__ void __launch_bounds__(256, AM_K2GP_WAVES)
+// K2 for a group of needles against one haystack (am_match_multi_device, BASELINE
+// config 4): the row is read and transformed ONCE; every needle of the group then
+// multiplies that spectrum with its own and runs its own inverse transform into its
+// own work matrix.  Per needle the row costs 8/n + 8 bytes of HBM traffic instead of
+// 16 and the forward half of the arithmetic is shared.  The exchanges are the plane-by-plane ones above.
+constexpr int kK2gpWaves = 3;
+// cache policy of the group kernel's eight write streams: 2 = nt.  At three waves per SIMD nt stores take 6.05 ms
+// per call of 32 needles x 22 pairs against 6.6 (and against 6.5 for the removed 64 KB form at two waves per SIMD,
+// where nt made no difference: profiles/r03/k2_group_ab.txt)
+constexpr int kK2gStoreAux = 2;
+__global__ void __launch_bounds__(256, kK2gpWaves)
 k2_rows_r16_group_planes(const float2* __restrict__ work, K2Group grp, PlanDev pl, unsigned npairs) {
     extern __shared__ float4 lds4[];
     float2* lds2 = reinterpret_cast<float2*>(lds4);
@@ -1262,7 +1079,7 @@ k2_rows_r16_group_planes(const float2* __restrict__ work, K2Group grp, PlanDev p
         k2_fetch_quarter(rh, k.voff, 0, hq);
         float2 q[32];
         k2_multiply_fetch(z, rh, k.voff, hq, q);
-        k2p_inverse<false, AM_K2G_STORE_AUX, true>(pl, q, lds2, make_rsrc(grp.dst[j] + row_off, kN2 * 8));
+        k2p_inverse<false, kK2gStoreAux, true>(pl, q, lds2, make_rsrc(grp.dst[j] + row_off, kN2 * 8));
         __syncthreads();   // the last pass read slabs of every wave: finish before the next needle's exchanges overwrite them
     }
 }
@@ -1344,10 +1161,8 @@ __device__ __forceinline__ int swap_bits02(int c) { return (c & ~5) | ((c & 1) <
 // and still slower -- 0.241 ms per launch against 0.210: the six passes of a row are one dependent chain with five
 // workgroup barriers, the kernel needs 216 registers (two waves per SIMD), and forms with fewer registers (the pass-1
 // twiddles fetched twice per row: 128 / 168 registers) or with prefetches ran at 0.28 - 0.36 ms.  Kept as an opt-in.
-#ifndef AM_K2M_WAVES
-#define AM_K2M_WAVES 2
-#endif
-__global__ void __launch_bounds__(256, AM_K2M_WAVES)
+constexpr int kK2mWaves = 2;
+__global__ void __launch_bounds__(256, kK2mWaves)
 k2_rows_m16(unsigned* __restrict__ work, const unsigned* __restrict__ hcm, unsigned* __restrict__ dst, PlanDev pl, unsigned npairs,
             float pre) {
     extern __shared__ float4 lds4[];
@@ -1545,7 +1360,7 @@ k2_rows_m16(unsigned* __restrict__ work, const unsigned* __restrict__ hcm, unsig
 }
 
 // the needle spectrum for k2_rows_m16: conjugated, scaled, as h2 points in [row][a'][b'][c'] order (hc: the f32
-// spectrum in the register order of k2_rows_r16: float2 index 2t + 512 i + e of a row holds frequency
+// spectrum in the register order of k2_rows_r16_spectrum: float2 index 2t + 512 i + e of a row holds frequency
 // (a' = t >> 4, b' = t & 15, c' = brev32(2i + e)))
 __global__ void __launch_bounds__(256) spectrum_to_half_mfma_kernel(const float2* __restrict__ hc, long long n, float scale, unsigned* __restrict__ out) {
     for (long long o = (long long)blockIdx.x * 256 + threadIdx.x; o < n; o += (long long)gridDim.x * 256) {
@@ -1559,56 +1374,6 @@ __global__ void __launch_bounds__(256) spectrum_to_half_mfma_kernel(const float2
 hipError_t launch_spectrum_to_half_mfma(hipStream_t st, const float2* hc, long long n, float scale, unsigned* out) {
     hipLaunchKernelGGL(spectrum_to_half_mfma_kernel, dim3(2048), dim3(256), 0, st, hc, n, scale, out);
     return hipGetLastError();
-}
-
-// K2 for a group of needles against one haystack (am_match_multi_device, BASELINE
-// config 4): the row is read and transformed ONCE; every needle of the group then
-// multiplies that spectrum with its own and runs its own inverse transform into its
-// own work matrix.  Per needle the row costs 8/n + 8 bytes of HBM traffic instead of
-// 16 and the forward half of the arithmetic is shared.
-#ifndef AM_K2G_PREFETCH
-// 1 = request the first quarter of the next needle's spectrum row one needle ahead.  Measured and dropped
-// (profiles/r03/k2_group_ab.txt): the 16 registers it holds across the inverse passes push the kernel
-// from 230 to 256 VGPRs plus 15 spilled ones (64 bytes of scratch per lane, reloaded inside the needle
-// loop): 2.16 ms per launch of 8 needles x 22 pairs with it, 1.60 ms without.
-#define AM_K2G_PREFETCH 0
-#endif
-__global__ void __launch_bounds__(256, 2)
-k2_rows_r16_group(const float2* __restrict__ work, K2Group grp, PlanDev pl, unsigned npairs) {
-    extern __shared__ float4 lds4[];
-    unsigned row, slot;
-    k2_place(npairs, row, slot);
-    const size_t row_off = ((size_t)slot << pl.logN) + (size_t)row * kN2;
-    const __amdgpu_buffer_rsrc_t rrow = make_rsrc(work + row_off, kN2 * 8);
-    const size_t hoff4 = (size_t)row * (kN2 / 2);
-    const K2Lane k = k2_lane(pl);
-    k2_forward12<false>(k, rrow, lds4);
-    float2 z[32];
-    k2_forward3(k, lds4, z);
-    float4 hq[4];
-    if (AM_K2G_PREFETCH) k2_fetch_quarter(make_rsrc(reinterpret_cast<const float4*>(grp.hc[0]) + hoff4, kN2 * 8), k.voff, 0, hq);
-#pragma unroll 1
-    for (int j = 0; j < grp.n; ++j) {
-        const __amdgpu_buffer_rsrc_t rh = make_rsrc(reinterpret_cast<const float4*>(grp.hc[j]) + hoff4, kN2 * 8);
-        if (!AM_K2G_PREFETCH) k2_fetch_quarter(rh, k.voff, 0, hq);
-        // The twiddle powers of the inverse passes depend on the lane only; left alone
-        // the compiler computes them once before the loop and keeps ~120 values alive
-        // across it (in scratch).  Recomputing them per needle is far cheaper.
-        K2Lane kj = k;
-        asm volatile("" : "+v"(kj.wj0.x), "+v"(kj.wj0.y), "+v"(kj.wj1.x), "+v"(kj.wj1.y),
-                          "+v"(kj.wc0.x), "+v"(kj.wc0.y), "+v"(kj.wc1.x), "+v"(kj.wc1.y));
-        asm volatile("" : "+v"(kj.qj0.x), "+v"(kj.qj0.y), "+v"(kj.qj1.x), "+v"(kj.qj1.y),
-                          "+v"(kj.qc0.x), "+v"(kj.qc0.y), "+v"(kj.qc1.x), "+v"(kj.qc1.y));
-        float2 q[32];
-        k2_multiply_fetch(z, rh, k.voff, hq, q);
-        if (AM_K2G_PREFETCH) {
-            const int jn = j + 1 < grp.n ? j + 1 : j;   // (the last needle refetches its own quarter: harmless)
-            k2_fetch_quarter(make_rsrc(reinterpret_cast<const float4*>(grp.hc[jn]) + hoff4, kN2 * 8), k.voff, 0, hq);
-            __builtin_amdgcn_sched_barrier(0);
-        }
-        k2_inverse<false, AM_K2G_STORE_AUX>(kj, q, lds4, make_rsrc(grp.dst[j] + row_off, kN2 * 8));
-        __syncthreads();   // the last pass read rows of every wave: finish before the next needle overwrites them
-    }
 }
 
 // v_min3 / v_max3 without the input canonicalisation the compiler puts in front of
@@ -1775,10 +1540,10 @@ __device__ __forceinline__ K3Edges k3_edges(const Job& job, const ScanCfg& scan,
 // and the fused scan is left out -- scan and accumulation together do not fit the 128 registers of the
 // 1024-thread kernel (over a thousand spilled values); the sums get their summary from tile_stats instead.
 // SCALED: the caller has folded out_scale into the transform (its first twiddle), the values are scores already.
-template <int HB, typename T, bool ACC = false, bool SCALED = false>
+template <int HB, bool ACC = false, bool SCALED = false>
 __device__ __forceinline__ void k3_finish(const Job& job, const ScanCfg& scan, const K3Edges& ed, float2* lds2,
                                           int n2_0, int out_stride, int t, long long blkA, long long blkB,
-                                          float out_scale, const T (&x0)[16], const T (&x1)[16]) {
+                                          float out_scale, const float2 (&x0)[16], const float2 (&x1)[16]) {
     const int hi = t >> 4, cp = t & 15;
     const long long col = n2_0 + 2 * cp;
     const long long outA = ed.outA, outB = ed.outB;
@@ -1790,7 +1555,7 @@ __device__ __forceinline__ void k3_finish(const Job& job, const ScanCfg& scan, c
     float sa0[16], sa1[16], sb0[16], sb1[16];
 #pragma unroll
     for (int a = 0; a < 16; ++a) {
-        const T v0 = x0[brev<16>(a)], v1 = x1[brev<16>(a)];
+        const float2 v0 = x0[brev<16>(a)], v1 = x1[brev<16>(a)];
         if (SCALED) {
             sa0[a] = v0.x; sa1[a] = v1.x;
             sb0[a] = v0.y; sb1[a] = v1.y;
@@ -1965,7 +1730,7 @@ __device__ __forceinline__ void k3_tile(const Job& job, const PlanDev& pl, const
     for (int ap = 0; ap < 16; ++ap) x1[ap] = lds2[(ap * 16 + hi) * 16 + cp];
     twiddle_nat<16, true>(x1, w256, w256q);
     dif<16, true>(x1);
-    k3_finish<4, float2, ACC, true>(job, scan, ed, lds2, n2_0, out_stride, t, blkA, blkB, out_scale, x0, x1);
+    k3_finish<4, ACC, true>(job, scan, ed, lds2, n2_0, out_stride, t, blkA, blkB, out_scale, x0, x1);
 }
 
 // The same with the first pass (pipeline twiddle, 16-point transform over b') and the exchange on
@@ -2009,9 +1774,11 @@ __device__ __forceinline__ void k3_tile_h16(const Job& job, const PlanDev& pl, c
     k3_finish<4>(job, scan, ed, lds2, n2_0, out_stride, t, blkA, blkB, out_scale, x0, x1);
 }
 
-#ifndef AM_K3_WGS
-#define AM_K3_WGS 3   // waves per SIMD the register allocation has to allow (= workgroups per CU for 256 threads; it uses 118 VGPRs: four fit)
-#endif
+constexpr int kK3Waves = 3;   // waves per SIMD the register allocation has to allow (= workgroups per CU for 256 threads; it uses 118 VGPRs: four fit)
+// Cache policy of K3's column loads (aux of the buffer loads: 2 = nt), the 512- and 1024-row kernels' too.  The work
+// matrix is read once: nt takes K3 from 0.180 to 0.156 ms per 1 h haystack (profiles/r02/nt_ab.txt); the loads from
+// a half-storage work matrix follow the f32 form's.
+constexpr int kK3LoadAux = 2, kK3hLoadAux = 2;
 // One column tile of the 256-row K3; lin = the tile's number in the launch (blockIdx.x in the pipeline's launches).
 template <int HALF, bool ACC>   // 0 = f32 work matrix, 1 = f16 storage, 2 = f16 storage and an f16 first pass
 __device__ __forceinline__ void k3_cols_inv_r16_tile(unsigned lin, float4* lds4, const Job& job, const float2* __restrict__ work,
@@ -2054,7 +1821,7 @@ __device__ __forceinline__ void k3_cols_inv_r16_tile(unsigned lin, float4* lds4,
         const unsigned voff = (unsigned)hi * (kN2 * 8u) + (unsigned)cp * 16u;
 #pragma unroll
         for (int bp = 0; bp < 16; ++bp) {   // rows k1 = a' + 16*b', a' = hi
-            const float4 v = buf_load4<AM_K3_LOAD_NT ? 2 : 0>(rin, voff, (unsigned)bp * (16u * kN2 * 8u));
+            const float4 v = buf_load4<kK3LoadAux>(rin, voff, (unsigned)bp * (16u * kN2 * 8u));
             x0[bp] = make_float2(v.x, v.y);
             x1[bp] = make_float2(v.z, v.w);
         }
@@ -2066,7 +1833,7 @@ __device__ __forceinline__ void k3_cols_inv_r16_tile(unsigned lin, float4* lds4,
 // launches of it find nothing to do, and 512 workgroups that look at 22 flags are gone sooner than 5632 that each
 // need a workgroup's worth of LDS and registers to find out.
 template <int HALF, bool ACC = false, int REDO = 0>
-__global__ void __launch_bounds__(256, REDO ? 4 : AM_K3_WGS)
+__global__ void __launch_bounds__(256, REDO ? 4 : kK3Waves)
 k3_cols_inv_r16(Job job, const float2* __restrict__ work, PlanDev pl, float out_scale, ScanCfg scan) {
     extern __shared__ float4 lds4[];
     if constexpr (REDO != 0) {
@@ -2080,7 +1847,7 @@ k3_cols_inv_r16(Job job, const float2* __restrict__ work, PlanDev pl, float out_
 }
 
 // the same for the 256-row plan (see k3_cols_inv_c512_group)
-__global__ void __launch_bounds__(256, AM_K3_WGS)
+__global__ void __launch_bounds__(256, kK3Waves)
 k3_cols_inv_r16_group(Job job, PlanDev pl, ScanCfg scan, K3Group grp) {
     extern __shared__ float4 lds4[];
     const unsigned z = blockIdx.y;
@@ -2095,7 +1862,7 @@ k3_cols_inv_r16_group(Job job, PlanDev pl, ScanCfg scan, K3Group grp) {
 // ... and for the odd last blocks of several haystacks (TailBatch): entry z is one pair of a job of its own, every run
 // written, the summary at the place the entry names.
 template <int HALF>
-__global__ void __launch_bounds__(256, AM_K3_WGS)
+__global__ void __launch_bounds__(256, kK3Waves)
 tail_cols_inv_r16(TailBatch tb, int hop, const float2* __restrict__ work, PlanDev pl, float out_scale) {
     extern __shared__ float4 lds4[];
     const unsigned z = blockIdx.y;
@@ -2212,8 +1979,8 @@ k1_cols_fwd_c512(Job job, float2* __restrict__ work, PlanDev pl) {
         const unsigned voff = 4u * ((unsigned)hi * kN2 + (unsigned)col), offB = 4u * (unsigned)job.hop;
 #pragma unroll
         for (int a = 0; a < 16; ++a) {
-            const float2 va = decode_sample2<KIND>(buf_load_u2<AM_K1_LOAD_NT ? 2 : 0>(rsrc, voff, (unsigned)a * (4u * 32u * kN2)));
-            const float2 vb = decode_sample2<KIND>(buf_load_u2<AM_K1_LOAD_NT ? 2 : 0>(rsrc, voff, (unsigned)a * (4u * 32u * kN2) + offB));
+            const float2 va = decode_sample2<KIND>(buf_load_u2<kK1LoadNt ? 2 : 0>(rsrc, voff, (unsigned)a * (4u * 32u * kN2)));
+            const float2 vb = decode_sample2<KIND>(buf_load_u2<kK1LoadNt ? 2 : 0>(rsrc, voff, (unsigned)a * (4u * 32u * kN2) + offB));
             x0[a] = make_float2(va.x, vb.x);
             x1[a] = make_float2(va.y, vb.y);
         }
@@ -2312,8 +2079,8 @@ k1_cols_fwd_c512(Job job, float2* __restrict__ work, PlanDev pl) {
 #pragma unroll
     for (int bt = 0; bt < 16; ++bt) {
         const size_t k1 = (size_t)(k10 + 32 * bt);
-        store_f4<AM_K1_STORE_NT>(out4 + k1 * (kN2 / 2), make_float4(y0[brev<16>(bt)].x, y0[brev<16>(bt)].y,
-                                                                    y1[brev<16>(bt)].x, y1[brev<16>(bt)].y));
+        out4[k1 * (kN2 / 2)] = make_float4(y0[brev<16>(bt)].x, y0[brev<16>(bt)].y,
+                                             y1[brev<16>(bt)].x, y1[brev<16>(bt)].y);
     }
 }
 
@@ -2337,15 +2104,7 @@ __device__ __forceinline__ void k3_cols_inv_c512_tile(unsigned lin, float4* lds4
     const long long N = 1ll << pl.logN;
     const unsigned maskN = (unsigned)(N - 1);
     const unsigned n2 = (unsigned)n2_0 + 2u * (unsigned)cp;
-#ifndef AM_K3_INTERLEAVE
-#define AM_K3_INTERLEAVE 1
-#endif
-#ifndef AM_K3_PK
-#define AM_K3_PK 0   // 1 = the 512-row K3's butterflies in packed f32: 40 % fewer VALU instructions, the same 0.170 ms
-                     // (tools/pkbench: v_pk_fma_f32 delivers 1.14x the flops of v_fma_f32 at 4 waves per SIMD, not 2x)
-#endif
-    using T = typename std::conditional<AM_K3_PK != 0, p2, float2>::type;
-    T x0[16], x1[16];
+    float2 x0[16], x1[16];
     if constexpr (HALF == 2) {
         // first pass (pipeline twiddle, 16-point transform over beta, the W_32 branch factors) and the
         // exchange on packed half-precision points, both columns in one exchange; the second pass and
@@ -2357,7 +2116,7 @@ __device__ __forceinline__ void k3_cols_inv_c512_tile(unsigned lin, float4* lds4
         h2 hx0[16], hx1[16];
 #pragma unroll
         for (int bt = 0; bt < 16; ++bt) {
-            const uint2 v = buf_load_u2<AM_K3H_LOAD_AUX>(rin, voff, (unsigned)bt * (32u * kN2 * 4u));
+            const uint2 v = buf_load_u2<kK3hLoadAux>(rin, voff, (unsigned)bt * (32u * kN2 * 4u));
             hx0[bt] = bits_h2(v.x);
             hx1[bt] = bits_h2(v.y);
         }
@@ -2390,8 +2149,8 @@ __device__ __forceinline__ void k3_cols_inv_c512_tile(unsigned lin, float4* lds4
         for (int a2 = 0; a2 < 16; ++a2) {
             const uint2 u = ldsu[c512_idx3(a2, bb, cp)], v = ldsu[c512_idx3(a2, bb + 16, cp)];
             const float2 u0 = to_f2(bits_h2(u.x)), v0 = to_f2(bits_h2(v.x)), u1 = to_f2(bits_h2(u.y)), v1 = to_f2(bits_h2(v.y));
-            x0[a2] = T{fmaf(sgn, v0.x, u0.x), fmaf(sgn, v0.y, u0.y)};
-            x1[a2] = T{fmaf(sgn, v1.x, u1.x), fmaf(sgn, v1.y, u1.y)};
+            x0[a2] = make_float2(fmaf(sgn, v0.x, u0.x), fmaf(sgn, v0.y, u0.y));
+            x1[a2] = make_float2(fmaf(sgn, v1.x, u1.x), fmaf(sgn, v1.y, u1.y));
         }
         twiddle_nat<16, true>(x0, w512);
         twiddle_nat<16, true>(x1, w512);
@@ -2406,10 +2165,9 @@ __device__ __forceinline__ void k3_cols_inv_c512_tile(unsigned lin, float4* lds4
         const unsigned voff = (unsigned)k10 * (kN2 * 4u) + (unsigned)cp * 8u;
 #pragma unroll
         for (int bt = 0; bt < 16; ++bt) {
-            const uint2 v = buf_load_u2<AM_K3H_LOAD_AUX>(rin, voff, (unsigned)bt * (32u * kN2 * 4u));
-            const float2 f0 = unpack_h2(v.x), f1 = unpack_h2(v.y);
-            x0[bt] = T{f0.x, f0.y};
-            x1[bt] = T{f1.x, f1.y};
+            const uint2 v = buf_load_u2<kK3hLoadAux>(rin, voff, (unsigned)bt * (32u * kN2 * 4u));
+            x0[bt] = unpack_h2(v.x);
+            x1[bt] = unpack_h2(v.y);
         }
     } else {
         // buffer loads: one VGPR of address for all 16 (the row offsets, multiples of 2 MB, ride in SGPRs), so
@@ -2418,9 +2176,9 @@ __device__ __forceinline__ void k3_cols_inv_c512_tile(unsigned lin, float4* lds4
         const unsigned voff = (unsigned)k10 * (kN2 * 8u) + (unsigned)cp * 16u;
 #pragma unroll
         for (int bt = 0; bt < 16; ++bt) {   // rows k1 = k10 + 32*beta
-            const float4 v = buf_load4<AM_K3_LOAD_NT ? 2 : 0>(rin, voff, (unsigned)bt * (32u * kN2 * 8u));
-            x0[bt] = T{v.x, v.y};
-            x1[bt] = T{v.z, v.w};
+            const float4 v = buf_load4<kK3LoadAux>(rin, voff, (unsigned)bt * (32u * kN2 * 8u));
+            x0[bt] = make_float2(v.x, v.y);
+            x1[bt] = make_float2(v.z, v.w);
         }
     }
     const K3Edges ed = k3_edges(job, geo ? *geo : scan, blkA, blkB);
@@ -2434,7 +2192,6 @@ __device__ __forceinline__ void k3_cols_inv_c512_tile(unsigned lin, float4* lds4
         float2 step0, step1, step0q, step1q;
         tw_big_pair(pl, (n2 * 32u) & maskN, step0, step0q);
         tw_big_pair(pl, ((n2 + 1u) * 32u) & maskN, step1, step1q);
-#if AM_K3_INTERLEAVE
         // column 0 goes through its first pass and into LDS before column 1 is touched, and comes out into its
         // second pass while column 1 is on its way: arithmetic between every two barriers
         twiddle_chain<16, true, false>(x0, base0, step0, step0q);
@@ -2444,7 +2201,7 @@ __device__ __forceinline__ void k3_cols_inv_c512_tile(unsigned lin, float4* lds4
             for (int b = 1; b < 16; ++b) x0[brev<16>(b)] = mul_w32<true>(x0[brev<16>(b)], b);
         }
 #pragma unroll
-        for (int b = 0; b < 16; ++b) lds2[c512_idx3(ap, b + 16 * half, cp)] = make_float2(x0[brev<16>(b)].x, x0[brev<16>(b)].y);
+        for (int b = 0; b < 16; ++b) lds2[c512_idx3(ap, b + 16 * half, cp)] = x0[brev<16>(b)];
         twiddle_chain<16, true, false>(x1, base1, step1, step1q);
     }
     dif<16, true>(x1);
@@ -2460,61 +2217,22 @@ __device__ __forceinline__ void k3_cols_inv_c512_tile(unsigned lin, float4* lds4
 #pragma unroll
     for (int a2 = 0; a2 < 16; ++a2) {
         const float2 u = lds2[c512_idx3(a2, bb, cp)], v = lds2[c512_idx3(a2, bb + 16, cp)];
-        x0[a2] = add_signed(u, v, sgn, T{});
+        x0[a2] = add_signed(u, v, sgn);
     }
     __syncthreads();
 #pragma unroll
-    for (int b = 0; b < 16; ++b) lds2[c512_idx3(ap, b + 16 * half, cp)] = make_float2(x1[brev<16>(b)].x, x1[brev<16>(b)].y);
+    for (int b = 0; b < 16; ++b) lds2[c512_idx3(ap, b + 16 * half, cp)] = x1[brev<16>(b)];
     twiddle_nat<16, true>(x0, w512, w512q);   // conj(W_512^(b*a'))
     dif<16, true>(x0);   // a at x[brev(a)], n1 = a*32 + b
     __syncthreads();
 #pragma unroll
     for (int a2 = 0; a2 < 16; ++a2) {
         const float2 u = lds2[c512_idx3(a2, bb, cp)], v = lds2[c512_idx3(a2, bb + 16, cp)];
-        x1[a2] = add_signed(u, v, sgn, T{});
+        x1[a2] = add_signed(u, v, sgn);
     }
     twiddle_nat<16, true>(x1, w512, w512q);
     dif<16, true>(x1);
-#else
-        twiddle_chain<16, true, false>(x0, base0, step0, step0q);
-        twiddle_chain<16, true, false>(x1, base1, step1, step1q);
-    }
-    dif<16, true>(x0);   // inverse over beta: branch value b at x[brev(b)], b = 0..15
-    dif<16, true>(x1);
-    if (half) {          // the odd-b' branch carries conj(W_32^b)
-#pragma unroll
-        for (int b = 1; b < 16; ++b) {
-            x0[brev<16>(b)] = mul_w32<true>(x0[brev<16>(b)], b);
-            x1[brev<16>(b)] = mul_w32<true>(x1[brev<16>(b)], b);
-        }
-    }
-    // exchange, one column of the pair at a time: afterwards thread b = hi (0..31) holds
-    // z[a'] = u[a'][b & 15] +- v[a'][b & 15]
-    const float sgn = hi >= 16 ? -1.0f : 1.0f;
-    const int bb = hi & 15;
-#pragma unroll
-    for (int b = 0; b < 16; ++b) lds2[c512_idx3(ap, b + 16 * half, cp)] = make_float2(x0[brev<16>(b)].x, x0[brev<16>(b)].y);
-    __syncthreads();
-#pragma unroll
-    for (int a2 = 0; a2 < 16; ++a2) {
-        const float2 u = lds2[c512_idx3(a2, bb, cp)], v = lds2[c512_idx3(a2, bb + 16, cp)];
-        x0[a2] = add_signed(u, v, sgn, T{});
-    }
-    __syncthreads();
-#pragma unroll
-    for (int b = 0; b < 16; ++b) lds2[c512_idx3(ap, b + 16 * half, cp)] = make_float2(x1[brev<16>(b)].x, x1[brev<16>(b)].y);
-    __syncthreads();
-#pragma unroll
-    for (int a2 = 0; a2 < 16; ++a2) {
-        const float2 u = lds2[c512_idx3(a2, bb, cp)], v = lds2[c512_idx3(a2, bb + 16, cp)];
-        x1[a2] = add_signed(u, v, sgn, T{});
-    }
-    twiddle_nat<16, true>(x0, w512, w512q);   // conj(W_512^(b*a'))
-    twiddle_nat<16, true>(x1, w512, w512q);
-    dif<16, true>(x0);   // a at x[brev(a)], n1 = a*32 + b
-    dif<16, true>(x1);
-#endif
-    k3_finish<5, T, ACC, true>(job, scan, ed, lds2, n2_0, kN2, t, blkA, blkB, out_scale, x0, x1);
+    k3_finish<5, ACC, true>(job, scan, ed, lds2, n2_0, kN2, t, blkA, blkB, out_scale, x0, x1);
 }
 template <int HALF, bool ACC = false, int REDO = 0>   // (REDO: see k3_cols_inv_r16)
 __global__ void __launch_bounds__(512, REDO ? 4 : 2)   // (113 - 119 VGPRs, two workgroups per CU, without being told; the loop of the REDO form has to be held to 128)
@@ -2670,8 +2388,8 @@ k1_cols_fwd_c1024(Job job, float2* __restrict__ work, PlanDev pl) {
 #pragma unroll
     for (int bt = 0; bt < 16; ++bt) {
         const size_t k1 = (size_t)(k10 + 64 * bt);
-        store_f4<AM_K1_STORE_NT>(out4 + k1 * (kN2 / 2), make_float4(y0[brev<16>(bt)].x, y0[brev<16>(bt)].y,
-                                                                    y1[brev<16>(bt)].x, y1[brev<16>(bt)].y));
+        out4[k1 * (kN2 / 2)] = make_float4(y0[brev<16>(bt)].x, y0[brev<16>(bt)].y,
+                                             y1[brev<16>(bt)].x, y1[brev<16>(bt)].y);
     }
 }
 
@@ -2699,7 +2417,7 @@ __device__ __forceinline__ void k3_cols_inv_c1024_tile(unsigned lin, float4* lds
         const unsigned voff = (unsigned)k10 * (kN2 * 8u) + (unsigned)cp * 16u;
 #pragma unroll
         for (int bt = 0; bt < 16; ++bt) {   // rows k1 = k10 + 64*beta
-            const float4 v = buf_load4<AM_K3_LOAD_NT ? 2 : 0>(rin, voff, (unsigned)bt * (64u * kN2 * 8u));
+            const float4 v = buf_load4<kK3LoadAux>(rin, voff, (unsigned)bt * (64u * kN2 * 8u));
             x0[bt] = make_float2(v.x, v.y);
             x1[bt] = make_float2(v.z, v.w);
         }
@@ -2745,7 +2463,7 @@ __device__ __forceinline__ void k3_cols_inv_c1024_tile(unsigned lin, float4* lds
                                      lds2[c1024_idx3(a2, bb + 32, cp)], lds2[c1024_idx3(a2, bb + 48, cp)], m);
     twiddle_nat<16, true>(x1, w1024);
     dif<16, true>(x1);
-    k3_finish<6, float2, ACC, true>(job, scan, ed, lds2, n2_0, kN2, t, blkA, blkB, out_scale, x0, x1);
+    k3_finish<6, ACC, true>(job, scan, ed, lds2, n2_0, kN2, t, blkA, blkB, out_scale, x0, x1);
 }
 template <bool ACC, int REDO = 0>   // (REDO: see k3_cols_inv_r16)
 __global__ void __launch_bounds__(1024)
@@ -2982,11 +2700,26 @@ hipError_t launch_direct(hipStream_t st, const Job& job, const float* needle, in
     return hipGetLastError();
 }
 
-// ---------------------------------------------------------------------------
-static constexpr int kMaxLds = 160 * 1024;
-static constexpr int kR16Lds = 64 * 1024;       // K2: one 8192-point row
-static constexpr int kR16LdsK1 = 256 * 17 * 8;   // K1: one column of the pair at a time, padded rows
-static constexpr int kR16LdsK3 = 256 * 16 * 8;
+// ===========================================================================
+// The launch layer.  Every kernel variant that takes dynamic LDS is described ONCE, as a row of its family's
+// table: the kernel, its block size and its dynamic LDS bytes.  fft_kernels_init walks the tables, every launcher
+// picks a row and launches it; a combination that does not exist is an empty row, and asking for it is an invalid
+// argument.  A new variant is one more row.
+// ===========================================================================
+template <typename Fn>
+struct Variant { Fn fn; int threads; int lds; };
+
+// (args: the kernel's own parameter types, checked by the call through the typed pointer)
+template <typename Fn, typename... Args>
+static hipError_t launch_row_lds(const Variant<Fn>& v, dim3 grid, size_t lds, hipStream_t st, const Args&... args) {
+    if (v.fn == nullptr) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(v.fn, grid, dim3(v.threads), lds, st, args...);
+    return hipGetLastError();
+}
+template <typename Fn, typename... Args>
+static hipError_t launch_row(const Variant<Fn>& v, dim3 grid, hipStream_t st, const Args&... args) {
+    return launch_row_lds(v, grid, (size_t)v.lds, st, args...);
+}
 
 bool plan_is_r16(const PlanDev& pl) { return pl.logN1 == kR16LogN1 && pl.logN2 == kR16LogN2; }
 bool plan_is_c512(const PlanDev& pl) { return pl.logN1 == 9 && pl.logN2 == kR16LogN2; }
@@ -2996,109 +2729,116 @@ bool plan_has_scan(const PlanDev& pl) { return plan_is_r16(pl) || plan_is_c512(p
 // the row kernel only needs 8192-point rows; it serves any N1 (its rows are independent)
 bool plan_k2_is_r16(const PlanDev& pl) { return pl.logN2 == kR16LogN2 && pl.logN1 >= 3; }
 
-hipError_t fft_kernels_init() {
-    hipError_t e;
-#define AM_SET_LDS(fn, bytes)                                                                     \
-    e = hipFuncSetAttribute((const void*)(fn), hipFuncAttributeMaxDynamicSharedMemorySize, bytes); \
-    if (e != hipSuccess) return e;
-    AM_SET_LDS((k1_cols_fwd_gen<kColsLog, 0>), kMaxLds)
-    AM_SET_LDS((k1_cols_fwd_gen<kColsLog, 1>), kMaxLds)
-    AM_SET_LDS(k3_cols_inv_gen<kColsLog>, kMaxLds)
-    AM_SET_LDS(k2_rows_gen<false>, kMaxLds)
-    AM_SET_LDS(k2_rows_gen<true>, kMaxLds)
-    AM_SET_LDS((k1_cols_fwd_r16<0, 0>), kR16LdsK1)
-    AM_SET_LDS((k1_cols_fwd_r16<1, 0>), kR16LdsK1)
-    AM_SET_LDS((k1_cols_fwd_r16<0, 1>), kR16LdsK1)
-    AM_SET_LDS((k1_cols_fwd_r16<1, 1>), kR16LdsK1)
-    AM_SET_LDS((k1_cols_fwd_r16<0, 2>), kR16LdsK1)
-    AM_SET_LDS((k1_cols_fwd_r16<1, 2>), kR16LdsK1)
-    AM_SET_LDS((k1_cols_fwd_c512<0, 0>), kC512Lds)
-    AM_SET_LDS((k1_cols_fwd_c512<1, 0>), kC512Lds)
-    AM_SET_LDS((k1_cols_fwd_c512<0, 1>), kC512Lds)
-    AM_SET_LDS((k1_cols_fwd_c512<1, 1>), kC512Lds)
-    AM_SET_LDS((k1_cols_fwd_c512<0, 2>), kC512Lds)
-    AM_SET_LDS((k1_cols_fwd_c512<1, 2>), kC512Lds)
-    AM_SET_LDS(k1_cols_fwd_c1024<0>, kC1024Lds)
-    AM_SET_LDS(k1_cols_fwd_c1024<1>, kC1024Lds)
-    AM_SET_LDS(k3_cols_inv_c1024<false>, kC1024Lds)
-    AM_SET_LDS((k3_cols_inv_c1024<false, 1>), kC1024Lds)
-    AM_SET_LDS((k3_cols_inv_c512<0, false, 1>), kC512Lds)
-    AM_SET_LDS((k3_cols_inv_c512<1, false, 1>), kC512Lds)
-    AM_SET_LDS((k3_cols_inv_c512<2, false, 1>), kC512Lds)
-    AM_SET_LDS((k3_cols_inv_r16<0, false, 1>), kR16LdsK3)
-    AM_SET_LDS((k3_cols_inv_r16<1, false, 1>), kR16LdsK3)
-    AM_SET_LDS((k3_cols_inv_r16<2, false, 1>), kR16LdsK3)
-    AM_SET_LDS(k3_cols_inv_c1024<true>, kC1024Lds)
-    AM_SET_LDS(k3_cols_inv_c512_group, kC512Lds)
-    AM_SET_LDS(k3_cols_inv_c512w, kC512Lds)
-    AM_SET_LDS((k1_cols_fwd_c512<0, 0, 14>), kC512Lds)
-    AM_SET_LDS(k3_cols_inv_r16_group, kR16LdsK3)
-    AM_SET_LDS(tail_cols_inv_r16<0>, kR16LdsK3)
-    AM_SET_LDS(tail_cols_inv_r16<1>, kR16LdsK3)
-    AM_SET_LDS(tail_cols_inv_r16<2>, kR16LdsK3)
-    AM_SET_LDS((tail_cols_fwd_r16<0, 0>), kR16LdsK1)
-    AM_SET_LDS((tail_cols_fwd_r16<1, 0>), kR16LdsK1)
-    AM_SET_LDS((tail_cols_fwd_r16<0, 1>), kR16LdsK1)
-    AM_SET_LDS((tail_cols_fwd_r16<1, 1>), kR16LdsK1)
-    AM_SET_LDS((tail_cols_fwd_r16<0, 2>), kR16LdsK1)
-    AM_SET_LDS((tail_cols_fwd_r16<1, 2>), kR16LdsK1)
-    AM_SET_LDS(k3_cols_inv_c512<0>, kC512Lds)
-    AM_SET_LDS((k3_cols_inv_c512<0, true>), kC512Lds)
-    AM_SET_LDS((k3_cols_inv_r16<0, true>), kR16LdsK3)
-    AM_SET_LDS(k3_cols_inv_c512<1>, kC512Lds)
-    AM_SET_LDS(k3_cols_inv_c512<2>, kC512Lds)
-    AM_SET_LDS(k3_cols_inv_r16<0>, kR16LdsK3)
-    AM_SET_LDS(k3_cols_inv_r16<1>, kR16LdsK3)
-    AM_SET_LDS(k3_cols_inv_r16<2>, kR16LdsK3)
-    AM_SET_LDS((k2_rows_r16<false, false>), kR16Lds)
-    AM_SET_LDS((k2_rows_r16<false, true>), kR16Lds)
-    AM_SET_LDS((k2_rows_r16<true, false>), kR16Lds)
-    AM_SET_LDS(k2_rows_r16_group, kR16Lds)
-    AM_SET_LDS(k2_rows_h16, kK2hLds)
-    AM_SET_LDS(tail_rows_h16, kK2hLds)
-    AM_SET_LDS(k2_rows_m16, kK2mLds)
-#undef AM_SET_LDS
+// first index of the column kernels' tables
+enum ColPlan { kColR16, kColC512, kColC1024, kColC512w, kColGen, kColPlans };
+static ColPlan col_plan(const PlanDev& pl) {
+    return plan_is_r16(pl) ? kColR16 : plan_is_c512(pl) ? kColC512 : plan_is_c1024(pl) ? kColC1024 : plan_is_c512w(pl) ? kColC512w : kColGen;
+}
+static int half_level(int half) { return half == 2 ? 2 : half ? 1 : 0; }
+
+static constexpr int kMaxLds = 160 * 1024;       // the generic kernels: the most a plan may ask for (a launch asks for what its plan needs)
+static constexpr int kR16Lds = 64 * 1024;        // the spectrum kernel: one 8192-point row
+static constexpr int kR16LdsK1 = 256 * 17 * 8;   // K1: one column of the pair at a time, padded rows
+static constexpr int kR16LdsK3 = 256 * 16 * 8;
+
+// K1: [plan][sample kind: f32 mono, i16 stereo][half level].  Half storage exists for the 256- and 512-row plans; the
+// 512 x 16384 plan takes f32 samples only; the generic kernel has no half form and ignores the level (row 0).
+using K1Fn = void (*)(Job, float2*, PlanDev);
+static constexpr Variant<K1Fn> kK1[kColPlans][2][3] = {
+    /* r16   */ {{{k1_cols_fwd_r16<0, 0>, 256, kR16LdsK1}, {k1_cols_fwd_r16<0, 1>, 256, kR16LdsK1}, {k1_cols_fwd_r16<0, 2>, 256, kR16LdsK1}},
+                 {{k1_cols_fwd_r16<1, 0>, 256, kR16LdsK1}, {k1_cols_fwd_r16<1, 1>, 256, kR16LdsK1}, {k1_cols_fwd_r16<1, 2>, 256, kR16LdsK1}}},
+    /* c512  */ {{{k1_cols_fwd_c512<0, 0>, 512, kC512Lds}, {k1_cols_fwd_c512<0, 1>, 512, kC512Lds}, {k1_cols_fwd_c512<0, 2>, 512, kC512Lds}},
+                 {{k1_cols_fwd_c512<1, 0>, 512, kC512Lds}, {k1_cols_fwd_c512<1, 1>, 512, kC512Lds}, {k1_cols_fwd_c512<1, 2>, 512, kC512Lds}}},
+    /* c1024 */ {{{k1_cols_fwd_c1024<0>, 1024, kC1024Lds}}, {{k1_cols_fwd_c1024<1>, 1024, kC1024Lds}}},
+    /* c512w */ {{{k1_cols_fwd_c512<0, 0, 14>, 512, kC512Lds}}},
+    /* gen   */ {{{k1_cols_fwd_gen<kColsLog, 0>, kFftThreads, kMaxLds}}, {{k1_cols_fwd_gen<kColsLog, 1>, kFftThreads, kMaxLds}}},
+};
+// the odd last blocks of a batch (256-row plan): [sample kind][half level]
+using TailK1Fn = void (*)(TailBatch, int, float2*, PlanDev);
+static constexpr Variant<TailK1Fn> kTailK1[2][3] = {
+    {{tail_cols_fwd_r16<0, 0>, 256, kR16LdsK1}, {tail_cols_fwd_r16<0, 1>, 256, kR16LdsK1}, {tail_cols_fwd_r16<0, 2>, 256, kR16LdsK1}},
+    {{tail_cols_fwd_r16<1, 0>, 256, kR16LdsK1}, {tail_cols_fwd_r16<1, 1>, 256, kR16LdsK1}, {tail_cols_fwd_r16<1, 2>, 256, kR16LdsK1}},
+};
+
+// K2 on 8192-point rows, f32 butterflies: [half storage][tail]; the needle-spectrum kernel shares the signature
+using K2Fn = void (*)(float2*, const float2*, float2*, PlanDev, unsigned, float);
+static constexpr Variant<K2Fn> kK2[2][2] = {
+    {{k2_rows_r16_planes<false>, 256, kK2hLds}, {tail_rows_r16_planes<false>, 256, kK2hLds}},
+    {{k2_rows_r16_planes<true>, 256, kK2hLds}, {tail_rows_r16_planes<true>, 256, kK2hLds}},
+};
+static constexpr Variant<K2Fn> kK2Spectrum = {k2_rows_r16_spectrum, 256, kR16Lds};
+// ... with f16 butterflies (half level 2): [tail], and the matrix-core form (option k2_mfma; it has no tail form)
+using K2hFn = void (*)(unsigned*, const unsigned*, unsigned*, PlanDev, unsigned, float);
+static constexpr Variant<K2hFn> kK2h[2] = {{k2_rows_h16, 256, kK2hLds}, {tail_rows_h16, 256, kK2hLds}};
+static constexpr Variant<K2hFn> kK2Mfma = {k2_rows_m16, 256, kK2mLds};
+using K2GroupFn = void (*)(const float2*, K2Group, PlanDev, unsigned);
+static constexpr Variant<K2GroupFn> kK2Group = {k2_rows_r16_group_planes, 256, kK2hLds};
+// rows of any other length: [spectrum]
+using K2GenFn = void (*)(float2*, const float2*, float2*, PlanDev);
+static constexpr Variant<K2GenFn> kK2Gen[2] = {{k2_rows_gen<false>, kFftThreads, kMaxLds}, {k2_rows_gen<true>, kFftThreads, kMaxLds}};
+
+// K3: [plan][half level][form].  The accumulating forms exist for the f32 work matrix only, and not on the 256-row
+// plan (they add up the segments of a partitioned needle, and a segment is longer than 2^21 samples); the 1024-row
+// plan has no half storage, the 512 x 16384 plan has the plain f32 form alone; the generic kernel has a signature
+// of its own.
+enum K3Form { kK3Plain, kK3Acc, kK3Redo, kK3Forms };
+using K3Fn = void (*)(Job, const float2*, PlanDev, float, ScanCfg);
+static constexpr Variant<K3Fn> kK3[kColGen][3][kK3Forms] = {
+    /* r16   */ {{{k3_cols_inv_r16<0>, 256, kR16LdsK3}, {}, {k3_cols_inv_r16<0, false, 1>, 256, kR16LdsK3}},
+                 {{k3_cols_inv_r16<1>, 256, kR16LdsK3}, {}, {k3_cols_inv_r16<1, false, 1>, 256, kR16LdsK3}},
+                 {{k3_cols_inv_r16<2>, 256, kR16LdsK3}, {}, {k3_cols_inv_r16<2, false, 1>, 256, kR16LdsK3}}},
+    /* c512  */ {{{k3_cols_inv_c512<0>, 512, kC512Lds}, {k3_cols_inv_c512<0, true>, 512, kC512Lds}, {k3_cols_inv_c512<0, false, 1>, 512, kC512Lds}},
+                 {{k3_cols_inv_c512<1>, 512, kC512Lds}, {}, {k3_cols_inv_c512<1, false, 1>, 512, kC512Lds}},
+                 {{k3_cols_inv_c512<2>, 512, kC512Lds}, {}, {k3_cols_inv_c512<2, false, 1>, 512, kC512Lds}}},
+    /* c1024 */ {{{k3_cols_inv_c1024<false>, 1024, kC1024Lds}, {k3_cols_inv_c1024<true>, 1024, kC1024Lds}, {k3_cols_inv_c1024<false, 1>, 1024, kC1024Lds}}},
+    /* c512w */ {{{k3_cols_inv_c512w, 512, kC512Lds}}},
+};
+using K3GenFn = void (*)(Job, const float2*, PlanDev, float, int);
+static constexpr Variant<K3GenFn> kK3Gen = {k3_cols_inv_gen<kColsLog>, kFftThreads, kMaxLds};
+// the needles of a group in one launch: [plan] (f32 work matrices of the 256- and 512-row plans)
+using K3GroupFn = void (*)(Job, PlanDev, ScanCfg, K3Group);
+static constexpr Variant<K3GroupFn> kK3Group[kColGen] = {{k3_cols_inv_r16_group, 256, kR16LdsK3}, {k3_cols_inv_c512_group, 512, kC512Lds}};
+// the odd last blocks of a batch (256-row plan): [half level]
+using TailK3Fn = void (*)(TailBatch, int, const float2*, PlanDev, float);
+static constexpr Variant<TailK3Fn> kTailK3[3] = {
+    {tail_cols_inv_r16<0>, 256, kR16LdsK3}, {tail_cols_inv_r16<1>, 256, kR16LdsK3}, {tail_cols_inv_r16<2>, 256, kR16LdsK3}};
+
+// A kernel may ask for more than 64 KB of dynamic LDS only once it has been allowed to.  Every row of every table is
+// given its size (a table is a row or an array of tables), the rows below 64 KB included: one call each at start-up.
+template <typename Fn>
+static hipError_t allow_lds(const Variant<Fn>& v) {
+    return v.fn == nullptr ? hipSuccess : hipFuncSetAttribute((const void*)v.fn, hipFuncAttributeMaxDynamicSharedMemorySize, v.lds);
+}
+template <typename T, size_t N>
+static hipError_t allow_lds(const T (&table)[N]) {
+    for (const T& t : table) {
+        const hipError_t e = allow_lds(t);
+        if (e != hipSuccess) return e;
+    }
     return hipSuccess;
+}
+hipError_t fft_kernels_init() {
+    hipError_t e = allow_lds(kK1);
+    if (e == hipSuccess) e = allow_lds(kTailK1);
+    if (e == hipSuccess) e = allow_lds(kK2);
+    if (e == hipSuccess) e = allow_lds(kK2Spectrum);
+    if (e == hipSuccess) e = allow_lds(kK2h);
+    if (e == hipSuccess) e = allow_lds(kK2Mfma);
+    if (e == hipSuccess) e = allow_lds(kK2Group);
+    if (e == hipSuccess) e = allow_lds(kK2Gen);
+    if (e == hipSuccess) e = allow_lds(kK3);
+    if (e == hipSuccess) e = allow_lds(kK3Gen);
+    if (e == hipSuccess) e = allow_lds(kK3Group);
+    if (e == hipSuccess) e = allow_lds(kTailK3);
+    return e;
 }
 
 hipError_t launch_k1(hipStream_t st, const Job& job, int npairs, float2* work, const PlanDev& pl, int half) {
     const dim3 grid((1u << pl.logN2) >> kColsLog, npairs);
-    const bool pcm = job.src_kind == 1;
-    if (plan_is_c512w(pl)) {
-        if (half || pcm) return hipErrorInvalidValue;
-        hipLaunchKernelGGL((k1_cols_fwd_c512<0, 0, 14>), grid, dim3(512), kC512Lds, st, job, work, pl);
-    } else if (plan_is_c1024(pl)) {
-        if (half) return hipErrorInvalidValue;   // (f32 work matrix only)
-        if (pcm) hipLaunchKernelGGL(k1_cols_fwd_c1024<1>, grid, dim3(1024), kC1024Lds, st, job, work, pl);
-        else hipLaunchKernelGGL(k1_cols_fwd_c1024<0>, grid, dim3(1024), kC1024Lds, st, job, work, pl);
-    } else if (plan_is_c512(pl)) {
-        if (half == 2) {
-            if (pcm) hipLaunchKernelGGL((k1_cols_fwd_c512<1, 2>), grid, dim3(512), kC512Lds, st, job, work, pl);
-            else hipLaunchKernelGGL((k1_cols_fwd_c512<0, 2>), grid, dim3(512), kC512Lds, st, job, work, pl);
-        } else if (half) {
-            if (pcm) hipLaunchKernelGGL((k1_cols_fwd_c512<1, 1>), grid, dim3(512), kC512Lds, st, job, work, pl);
-            else hipLaunchKernelGGL((k1_cols_fwd_c512<0, 1>), grid, dim3(512), kC512Lds, st, job, work, pl);
-        } else {
-            if (pcm) hipLaunchKernelGGL((k1_cols_fwd_c512<1, 0>), grid, dim3(512), kC512Lds, st, job, work, pl);
-            else hipLaunchKernelGGL((k1_cols_fwd_c512<0, 0>), grid, dim3(512), kC512Lds, st, job, work, pl);
-        }
-    } else if (plan_is_r16(pl)) {
-        if (half == 2) {
-            if (pcm) hipLaunchKernelGGL((k1_cols_fwd_r16<1, 2>), grid, dim3(256), kR16LdsK1, st, job, work, pl);
-            else hipLaunchKernelGGL((k1_cols_fwd_r16<0, 2>), grid, dim3(256), kR16LdsK1, st, job, work, pl);
-        } else if (half) {
-            if (pcm) hipLaunchKernelGGL((k1_cols_fwd_r16<1, 1>), grid, dim3(256), kR16LdsK1, st, job, work, pl);
-            else hipLaunchKernelGGL((k1_cols_fwd_r16<0, 1>), grid, dim3(256), kR16LdsK1, st, job, work, pl);
-        } else {
-            if (pcm) hipLaunchKernelGGL((k1_cols_fwd_r16<1, 0>), grid, dim3(256), kR16LdsK1, st, job, work, pl);
-            else hipLaunchKernelGGL((k1_cols_fwd_r16<0, 0>), grid, dim3(256), kR16LdsK1, st, job, work, pl);
-        }
-    } else {
-        const size_t lds = (sizeof(float2) << pl.logN1) << kColsLog;
-        if (pcm) hipLaunchKernelGGL((k1_cols_fwd_gen<kColsLog, 1>), grid, dim3(kFftThreads), lds, st, job, work, pl);
-        else hipLaunchKernelGGL((k1_cols_fwd_gen<kColsLog, 0>), grid, dim3(kFftThreads), lds, st, job, work, pl);
-    }
-    return hipGetLastError();
+    const ColPlan p = col_plan(pl);
+    const int kind = job.src_kind == 1 ? 1 : 0;
+    if (p == kColGen) return launch_row_lds(kK1[p][kind][0], grid, (sizeof(float2) << pl.logN1) << kColsLog, st, job, work, pl);
+    return launch_row(kK1[p][kind][half_level(half)], grid, st, job, work, pl);
 }
 
 // (the environment variable AM_K2_MFMA sets the initial value, so that whole test runs can be repeated with it)
@@ -3110,63 +2850,33 @@ int k2_mfma_table_dwords() { return kMfTotal; }
 
 hipError_t launch_k2(hipStream_t st, int npairs, float2* work, const float2* hc, const PlanDev& pl, float2* dst,
                      int half, float hscale, float pre, bool tail) {
-    const dim3 grid(1u << pl.logN1, npairs);
-    if (tail && plan_k2_is_r16(pl) && AM_K2_PLANES) {
-        const dim3 rows((unsigned)npairs << pl.logN1);
-        if (half == 2) hipLaunchKernelGGL(tail_rows_h16, rows, dim3(256), kK2hLds, st, reinterpret_cast<unsigned*>(work),
-                                          reinterpret_cast<const unsigned*>(hc), reinterpret_cast<unsigned*>(dst), pl, (unsigned)npairs, pre);
-        else if (half) hipLaunchKernelGGL(tail_rows_r16_planes<true>, rows, dim3(256), kK2hLds, st, work, hc, dst, pl, (unsigned)npairs, hscale);
-        else hipLaunchKernelGGL(tail_rows_r16_planes<false>, rows, dim3(256), kK2hLds, st, work, hc, dst, pl, (unsigned)npairs, 1.0f);
-        return hipGetLastError();
-    }
-    if (plan_k2_is_r16(pl)) {
-        if (half == 2 && k2_mfma_enabled() && pl.mf != nullptr) {
+    if (!plan_k2_is_r16(pl))
+        return launch_row_lds(kK2Gen[0], dim3(1u << pl.logN1, npairs), sizeof(float2) << pl.logN2, st, work, hc, dst, pl);
+    const unsigned rows = (unsigned)npairs << pl.logN1;   // one workgroup per row, dealt over the XCDs (k2_place)
+    if (half == 2) {
+        unsigned* const w = reinterpret_cast<unsigned*>(work);
+        const unsigned* const h = reinterpret_cast<const unsigned*>(hc);
+        unsigned* const d = reinterpret_cast<unsigned*>(dst);
+        if (!tail && k2_mfma_enabled() && pl.mf != nullptr) {
             // persistent workgroups: four per CU walk the rows (the grid stays a multiple of the 8 XCDs)
-            const unsigned rows = (unsigned)npairs << pl.logN1;
             const unsigned grid = std::min<unsigned>(rows, 256u * 4u) & ~7u;
-            hipLaunchKernelGGL(k2_rows_m16, dim3(grid ? grid : 8u), dim3(256), kK2mLds, st,
-                               reinterpret_cast<unsigned*>(work), reinterpret_cast<const unsigned*>(hc), reinterpret_cast<unsigned*>(dst),
-                               pl, (unsigned)npairs, pre);
-        } else if (half == 2) {
-            hipLaunchKernelGGL(k2_rows_h16, dim3((unsigned)npairs << pl.logN1), dim3(256), kK2hLds, st,
-                               reinterpret_cast<unsigned*>(work), reinterpret_cast<const unsigned*>(hc), reinterpret_cast<unsigned*>(dst),
-                               pl, (unsigned)npairs, pre);
-        } else if (half && AM_K2_PLANES) hipLaunchKernelGGL(k2_rows_r16_planes<true>, dim3((unsigned)npairs << pl.logN1), dim3(256), kK2hLds, st, work, hc,
-                                                          dst, pl, (unsigned)npairs, hscale);
-        else if (half) hipLaunchKernelGGL((k2_rows_r16<false, true>), dim3((unsigned)npairs << pl.logN1), dim3(256), kR16Lds, st, work, hc,
-                                     dst, pl, (unsigned)npairs, hscale);
-        else if (AM_K2_PLANES) hipLaunchKernelGGL(k2_rows_r16_planes<false>, dim3((unsigned)npairs << pl.logN1), dim3(256), kK2hLds, st, work, hc,
-                                                  dst, pl, (unsigned)npairs, 1.0f);
-        else hipLaunchKernelGGL((k2_rows_r16<false, false>), dim3((unsigned)npairs << pl.logN1), dim3(256), kR16Lds, st, work, hc,
-                                dst, pl, (unsigned)npairs, 1.0f);
-    } else {
-        const size_t lds = sizeof(float2) << pl.logN2;
-        hipLaunchKernelGGL(k2_rows_gen<false>, grid, dim3(kFftThreads), lds, st, work, hc, dst, pl);
+            return launch_row(kK2Mfma, dim3(grid ? grid : 8u), st, w, h, d, pl, (unsigned)npairs, pre);
+        }
+        return launch_row(kK2h[tail], dim3(rows), st, w, h, d, pl, (unsigned)npairs, pre);
     }
-    return hipGetLastError();
+    return launch_row(kK2[half ? 1 : 0][tail], dim3(rows), st, work, hc, dst, pl, (unsigned)npairs, half ? hscale : 1.0f);
 }
 
 bool plan_k2_has_group(const PlanDev& pl) { return plan_k2_is_r16(pl); }
 
 hipError_t launch_k2_group(hipStream_t st, int npairs, const float2* work, const K2Group& grp, const PlanDev& pl) {
     if (!plan_k2_has_group(pl) || grp.n < 1 || grp.n > kMaxNeedleGroup) return hipErrorInvalidValue;
-    if (AM_K2G_PLANES) hipLaunchKernelGGL(k2_rows_r16_group_planes, dim3((unsigned)npairs << pl.logN1), dim3(256), kK2hLds, st, work, grp, pl,
-                                          (unsigned)npairs);
-    else hipLaunchKernelGGL(k2_rows_r16_group, dim3((unsigned)npairs << pl.logN1), dim3(256), kR16Lds, st, work, grp, pl,
-                            (unsigned)npairs);
-    return hipGetLastError();
+    return launch_row(kK2Group, dim3((unsigned)npairs << pl.logN1), st, work, grp, pl, (unsigned)npairs);
 }
 
 hipError_t launch_k2_spectrum(hipStream_t st, float2* work, float2* hc_out, const PlanDev& pl) {
-    const dim3 grid(1u << pl.logN1, 1);
-    if (plan_k2_is_r16(pl)) {
-        hipLaunchKernelGGL((k2_rows_r16<true, false>), dim3(1u << pl.logN1), dim3(256), kR16Lds, st, work, (const float2*)nullptr,
-                           hc_out, pl, 1u, 1.0f);
-    } else {
-        const size_t lds = sizeof(float2) << pl.logN2;
-        hipLaunchKernelGGL(k2_rows_gen<true>, grid, dim3(kFftThreads), lds, st, work, (const float2*)nullptr, hc_out, pl);
-    }
-    return hipGetLastError();
+    if (plan_k2_is_r16(pl)) return launch_row(kK2Spectrum, dim3(1u << pl.logN1), st, work, (const float2*)nullptr, hc_out, pl, 1u, 1.0f);
+    return launch_row_lds(kK2Gen[1], dim3(1u << pl.logN1, 1), sizeof(float2) << pl.logN2, st, work, (const float2*)nullptr, hc_out, pl);
 }
 
 // scan.stats32 != nullptr only for the plans with a fused scan (plan_has_scan) and a 1024-aligned hop
@@ -3197,19 +2907,11 @@ bool plan_k3_has_group(const PlanDev& pl) { return plan_is_c512(pl) || plan_is_r
 hipError_t launch_tail_batch_k1(hipStream_t st, const TailBatch& tb, int hop, int src_kind, float2* work, const PlanDev& pl, int half) {
     if (!plan_is_r16(pl) || tb.n < 1 || tb.n > kMaxTailBatch) return hipErrorInvalidValue;
     const dim3 grid((1u << pl.logN2) >> kColsLog, (unsigned)tb.n);
-#define AM_TAIL_K1(K, H) hipLaunchKernelGGL((tail_cols_fwd_r16<K, H>), grid, dim3(256), kR16LdsK1, st, tb, hop, work, pl)
-    if (src_kind == 1) { if (half == 2) AM_TAIL_K1(1, 2); else if (half) AM_TAIL_K1(1, 1); else AM_TAIL_K1(1, 0); }
-    else { if (half == 2) AM_TAIL_K1(0, 2); else if (half) AM_TAIL_K1(0, 1); else AM_TAIL_K1(0, 0); }
-#undef AM_TAIL_K1
-    return hipGetLastError();
+    return launch_row(kTailK1[src_kind == 1 ? 1 : 0][half_level(half)], grid, st, tb, hop, work, pl);
 }
 hipError_t launch_tail_batch_k3(hipStream_t st, const TailBatch& tb, int hop, const float2* work, const PlanDev& pl, float out_scale, int half) {
     if (!plan_is_r16(pl) || tb.n < 1 || tb.n > kMaxTailBatch) return hipErrorInvalidValue;
-    const dim3 grid(kN2 >> kColsLog, (unsigned)tb.n);
-    if (half == 2) hipLaunchKernelGGL(tail_cols_inv_r16<2>, grid, dim3(256), kR16LdsK3, st, tb, hop, work, pl, out_scale);
-    else if (half) hipLaunchKernelGGL(tail_cols_inv_r16<1>, grid, dim3(256), kR16LdsK3, st, tb, hop, work, pl, out_scale);
-    else hipLaunchKernelGGL(tail_cols_inv_r16<0>, grid, dim3(256), kR16LdsK3, st, tb, hop, work, pl, out_scale);
-    return hipGetLastError();
+    return launch_row(kTailK3[half_level(half)], dim3(kN2 >> kColsLog, (unsigned)tb.n), st, tb, hop, work, pl, out_scale);
 }
 hipError_t launch_tail_preset_group(hipStream_t st, const K3Group& grp, long long blk, int log_n1, int log_n2) {
     if (grp.n < 1 || grp.n > kMaxNeedleGroup) return hipErrorInvalidValue;
@@ -3231,75 +2933,33 @@ hipError_t launch_k3_group(hipStream_t st, const Job& job, int npairs, const K3G
     scan.only_pairs = nullptr;
     fill_edges(job, npairs, scan);
     const dim3 grid((unsigned)npairs * (kN2 >> kColsLog), (unsigned)grp.n);
-    if (plan_is_c512(pl)) hipLaunchKernelGGL(k3_cols_inv_c512_group, grid, dim3(512), kC512Lds, st, job, pl, scan, grp);
-    else hipLaunchKernelGGL(k3_cols_inv_r16_group, grid, dim3(256), kR16LdsK3, st, job, pl, scan, grp);
-    return hipGetLastError();
+    return launch_row(kK3Group[col_plan(pl)], grid, st, job, pl, scan, grp);
 }
 
 hipError_t launch_k3(hipStream_t st, const Job& job, int npairs, const float2* work,
                      const PlanDev& pl, float out_scale, const ScanCfg& scan_in, int half, bool accumulate) {
-    const dim3 grid((1u << pl.logN2) >> kColsLog, npairs);
     ScanCfg scan = scan_in;
     fill_edges(job, npairs, scan);
-    if (scan.only_pairs != nullptr && !accumulate && plan_has_scan(pl)) {
-        // the device-side redo: the same kernels under names of their own
-        // (a grid of one round of resident workgroups -- 1, 2, 4 per CU -- walks the tiles)
-        scan.redo_tiles = npairs * (kN2 >> kColsLog);
-        const unsigned per_cu = plan_is_c1024(pl) ? 1u : plan_is_c512(pl) ? 2u : 4u;
-        const dim3 g1(std::min<unsigned>((unsigned)scan.redo_tiles, 256u * per_cu));
-        if (plan_is_c1024(pl)) {
-            if (half) return hipErrorInvalidValue;
-            hipLaunchKernelGGL((k3_cols_inv_c1024<false, 1>), g1, dim3(1024), kC1024Lds, st, job, work, pl, out_scale, scan);
-        } else if (plan_is_c512(pl)) {
-            if (half == 2) hipLaunchKernelGGL((k3_cols_inv_c512<2, false, 1>), g1, dim3(512), kC512Lds, st, job, work, pl, out_scale, scan);
-            else if (half) hipLaunchKernelGGL((k3_cols_inv_c512<1, false, 1>), g1, dim3(512), kC512Lds, st, job, work, pl, out_scale, scan);
-            else hipLaunchKernelGGL((k3_cols_inv_c512<0, false, 1>), g1, dim3(512), kC512Lds, st, job, work, pl, out_scale, scan);
-        } else {
-            if (half == 2) hipLaunchKernelGGL((k3_cols_inv_r16<2, false, 1>), g1, dim3(256), kR16LdsK3, st, job, work, pl, out_scale, scan);
-            else if (half) hipLaunchKernelGGL((k3_cols_inv_r16<1, false, 1>), g1, dim3(256), kR16LdsK3, st, job, work, pl, out_scale, scan);
-            else hipLaunchKernelGGL((k3_cols_inv_r16<0, false, 1>), g1, dim3(256), kR16LdsK3, st, job, work, pl, out_scale, scan);
-        }
-        return hipGetLastError();
+    const ColPlan p = col_plan(pl);
+    if (p == kColGen) {
+        if (accumulate && half) return hipErrorInvalidValue;   // (the accumulating forms exist for the f32 work matrix only)
+        const dim3 grid((1u << pl.logN2) >> kColsLog, npairs);
+        return launch_row_lds(kK3Gen, grid, (sizeof(float2) << pl.logN1) << kColsLog, st, job, work, pl, out_scale, accumulate ? 1 : 0);
     }
-    if (plan_is_c512w(pl)) {
-        if (half || accumulate || scan.only_pairs != nullptr) return hipErrorInvalidValue;
-        hipLaunchKernelGGL(k3_cols_inv_c512w, dim3((unsigned)npairs * ((1u << pl.logN2) >> kColsLog)), dim3(512), kC512Lds, st, job, work, pl, out_scale, scan);
-        return hipGetLastError();
-    }
-    if (accumulate && half) return hipErrorInvalidValue;   // (the accumulating forms exist for the f32 work matrix only)
     // (a score pointer that is only 4-byte aligned, or an odd hop, takes k3_finish's scalar read-modify-writes: every
     // score belongs to one thread, so the accumulating form needs no alignment either)
-    if (plan_is_c1024(pl)) {
-        if (half) return hipErrorInvalidValue;
-        if (accumulate) hipLaunchKernelGGL(k3_cols_inv_c1024<true>, dim3((unsigned)npairs * (kN2 >> kColsLog)), dim3(1024), kC1024Lds, st, job, work,
-                                           pl, out_scale, scan);
-        else hipLaunchKernelGGL(k3_cols_inv_c1024<false>, dim3((unsigned)npairs * (kN2 >> kColsLog)), dim3(1024), kC1024Lds, st, job, work,
-                                pl, out_scale, scan);
-    } else if (accumulate && plan_is_c512(pl)) {
-        hipLaunchKernelGGL((k3_cols_inv_c512<0, true>), dim3((unsigned)npairs * (kN2 >> kColsLog)), dim3(512), kC512Lds, st, job, work,
-                           pl, out_scale, scan);
-    } else if (accumulate && plan_is_r16(pl)) {
-        hipLaunchKernelGGL((k3_cols_inv_r16<0, true>), dim3((unsigned)npairs * (kN2 >> kColsLog)), dim3(256), kR16LdsK3, st, job, work,
-                           pl, out_scale, scan);
-    } else if (plan_is_c512(pl)) {
-        if (half == 2) hipLaunchKernelGGL(k3_cols_inv_c512<2>, dim3((unsigned)npairs * (kN2 >> kColsLog)), dim3(512), kC512Lds, st, job, work,
-                                          pl, out_scale, scan);
-        else if (half) hipLaunchKernelGGL(k3_cols_inv_c512<1>, dim3((unsigned)npairs * (kN2 >> kColsLog)), dim3(512), kC512Lds, st, job, work,
-                                          pl, out_scale, scan);
-        else hipLaunchKernelGGL(k3_cols_inv_c512<0>, dim3((unsigned)npairs * (kN2 >> kColsLog)), dim3(512), kC512Lds, st, job, work,
-                                pl, out_scale, scan);
-    } else if (plan_is_r16(pl)) {
-        if (half == 2) hipLaunchKernelGGL(k3_cols_inv_r16<2>, dim3((unsigned)npairs * (kN2 >> kColsLog)), dim3(256), kR16LdsK3, st, job, work,
-                                          pl, out_scale, scan);
-        else if (half) hipLaunchKernelGGL(k3_cols_inv_r16<1>, dim3((unsigned)npairs * (kN2 >> kColsLog)), dim3(256), kR16LdsK3, st, job, work,
-                                          pl, out_scale, scan);
-        else hipLaunchKernelGGL(k3_cols_inv_r16<0>, dim3((unsigned)npairs * (kN2 >> kColsLog)), dim3(256), kR16LdsK3, st, job, work,
-                                pl, out_scale, scan);
-    } else {
-        const size_t lds = (sizeof(float2) << pl.logN1) << kColsLog;
-        hipLaunchKernelGGL(k3_cols_inv_gen<kColsLog>, grid, dim3(kFftThreads), lds, st, job, work, pl, out_scale, accumulate ? 1 : 0);
+    K3Form form = accumulate ? kK3Acc : kK3Plain;
+    unsigned grid = (unsigned)npairs * ((1u << pl.logN2) >> kColsLog);   // one workgroup per column tile
+    if (scan.only_pairs != nullptr && !accumulate) {
+        // the device-side redo: the same kernels under names of their own
+        // (a grid of one round of resident workgroups -- 1, 2, 4 per CU -- walks the tiles)
+        if (!plan_has_scan(pl)) return hipErrorInvalidValue;
+        form = kK3Redo;
+        scan.redo_tiles = (int)grid;
+        const unsigned per_cu = p == kColC1024 ? 1u : p == kColC512 ? 2u : 4u;
+        grid = std::min<unsigned>(grid, 256u * per_cu);
     }
-    return hipGetLastError();
+    return launch_row(kK3[p][half_level(half)][form], dim3(grid), st, job, work, pl, out_scale, scan);
 }
 
 }  // namespace am

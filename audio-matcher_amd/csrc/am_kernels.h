@@ -58,6 +58,10 @@ struct Segment {
 
 // half: 0 = f32 work matrix; 1 = one __half2 per point, f32 butterflies; 2 = packed f16 butterflies too
 // (K2 and K1 whole; K3's first pass -- its second pass and the score scan stay f32)
+// Every launcher returns hipErrorInvalidValue, and launches nothing, for a combination of plan, sample kind, half level
+// and form that has no kernel (the empty rows of am_fft.hip's tables): a half level on the 1024-row plan, i16 samples or
+// a half level on the 512 x 16384 plan, accumulate with a half level or on the 256-row plan.  The generic kernels
+// (N below 2^21) have no half form and ignore the level.
 hipError_t launch_k1(hipStream_t st, const Job& job, int npairs, float2* work, const PlanDev& pl, int half = 0);
 // dst == nullptr: in place; otherwise the result goes to a second work matrix
 // tail: the launch belongs to a haystack's odd last block (am_correlate.hip, run_tail_block) -- the same row kernels under
@@ -83,7 +87,7 @@ struct K2Group {
 };
 bool plan_k2_has_group(const PlanDev& pl);
 hipError_t launch_k2_group(hipStream_t st, int npairs, const float2* work, const K2Group& grp, const PlanDev& pl);
-// The score scan fused into K3 (r16 plan only).  stats32 == nullptr disables it
+// The score scan fused into K3 (the plans of plan_has_scan).  stats32 == nullptr disables it
 // (plain correlation: every score is written).
 struct ScanCfg {
     float2* stats32;          // (min,max) per 32 consecutive scores, always written
@@ -109,7 +113,8 @@ struct ScanCfg {
     int edges_n;
     int edge_rel[kMaxEdgeSlots][4];
 };
-// accumulate: the scores are added to what job.dst holds (every run written; f32 work matrix only)
+// accumulate: the scores are added to what job.dst holds (every run written; f32 work matrix only; the 512- and
+// 1024-row plans and the generic ones -- the segments of a partitioned needle never run on the 256-row plan)
 hipError_t launch_k3(hipStream_t st, const Job& job, int npairs, const float2* work,
                      const PlanDev& pl, float out_scale, const ScanCfg& scan, int half = 0, bool accumulate = false);
 // K3 for the needles of a group in ONE launch (BASELINE configs[3]): needle z = blockIdx.y reads its own inverse rows

@@ -1,6 +1,8 @@
 #!/bin/bash
 # Builds a variant of the library for tools/ab.sh: am_fft.hip recompiled with extra -D flags, the other
 # objects taken from the last regular build.  Usage: tools/build_variant.sh <name> [-DAM_...=...]...
+# The flags are for macros that an experiment introduces in am_fft.hip for as long as it lasts: the file ships with
+# none (a measured choice becomes a constant beside its kernel, the rejected form is removed).
 set -e
 name=$1; shift
 root=$(cd "$(dirname "$0")/.." && pwd)

@@ -1,5 +1,5 @@
 #!/bin/bash
-# Evidence for the needle-group row kernel (k2_rows_r16_group, BASELINE configs[3]): rocprofv3
+# Evidence for the needle-group row kernel (k2_rows_r16_group_planes, BASELINE configs[3]): rocprofv3
 # kernel-trace stats, FETCH_SIZE / WRITE_SIZE and SQ counters of tools/multi_bench.py (separate --pmc
 # passes, no trace domains).  Run on the GPU box from the repo root: tools/profile_group.sh gpurun_out/<tag>
 set -o pipefail
