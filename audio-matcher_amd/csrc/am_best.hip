@@ -452,7 +452,7 @@ int best_select(Ctx* c, const float* d_g, long long n, float min_prom, long long
 
 // The AM_MODE_VALID scores of samples x[0, w) into d_out[0, w - S + 1), as correlate_impl (am_api.hip) computes them
 // for a finite input: the same run_correlation, the same half-precision redo check, normalise_scores under score_norm.
-static int valid_scores(am_needle* h, const Opts& o0, const NormSpec& nrm, float factor, const float* d_x, long long w, float* d_out) {
+int valid_scores(am_needle* h, const Opts& o0, const NormSpec& nrm, float factor, const float* d_x, long long w, float* d_out) {
     Ctx* c = h->ctx;
     const long long s = (long long)h->n, len = w - s + 1;
     Opts o = o0;

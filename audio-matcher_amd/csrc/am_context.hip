@@ -515,6 +515,7 @@ int am_shutdown(void) {
                            &c->seg_out})
             b->release();
         c->hit_io.release();
+        for (DevBuf* b : {&c->sig_span, &c->sig_scores, &c->sig_tab, &c->sig_psum, &c->sig_pmax, &c->sig_mean, &c->sig_hmax, &c->sig_out}) b->release();
         for (DevBuf* b : {&c->best_stats, &c->best_lmax, &c->best_ctl, &c->best_trans, &c->best_list, &c->best_scores, &c->best_mono}) b->release();
         for (auto& kv : c->rs_taps) kv.second.release();
         c->rs_taps.clear();

@@ -155,7 +155,10 @@ struct Ctx {
     DevBuf hit_tab, hit_parts, hit_flags, hit_out, hit_stage;   // per-hit scoring (am_hits.hip): hit table, partials, results, staged spans
     HostBuf hit_io;                                              // ... and the pinned host side of the table and the results
     DevBuf seg_tab, seg_parts, seg_flags, seg_out;               // per-segment hit scoring (am_segments.hip); spans and pinned side: hit_stage, hit_io
-    std::map<std::pair<int, int>, DevBuf> rs_taps;               // sample-rate conversion: the polyphase table of each (L, M)
+    // per-hit significance (am_significance.hip): the spans and score zones of one group of hits, the table, the slice
+    // partials, the per-hit state between the two passes and the results; pinned side: hit_io, host spans: hit_stage
+    DevBuf sig_span, sig_scores, sig_tab, sig_psum, sig_pmax, sig_mean, sig_hmax, sig_out;
+    std::map<std::pair<int, int>, DevBuf> rs_taps;              // sample-rate conversion: the polyphase table of each (L, M)
     DevBuf redo_pairs[2];   // device-side redo (batches): the per-pair "run again" flags of both sets
     // several needles: the K3s of a needle group run as ONE launch, every needle of the group with score-side
     // buffers of its own; two such sets alternate (the picks of group g beside the transforms of group g + 1)
@@ -492,6 +495,9 @@ int pick_chunk_big(Ctx* c, const float* d_scores, long long n_scores, int seg_id
 // am_find_peaks on a resident score array: one chunk [0, n) (am_api.hip)
 int find_peaks_host_array(Ctx* c, const float* d_scores, long long n, float min_prom, long long min_dist, std::vector<am_peak>& all);
 // ---- am_best.hip ----
+// The AM_MODE_VALID scores of samples x[0, w) into d_out[0, w - S + 1), as am_correlate computes them for a finite
+// input: the same run_correlation with lead 0, the same half-precision redo, normalise_scores under score_norm.
+int valid_scores(am_needle* h, const Opts& o0, const NormSpec& nrm, float factor, const float* d_x, long long w, float* d_out);
 int best_transitions(Ctx* c, const float* d_x, long long n, std::vector<long long>& trans);
 int best_select(Ctx* c, const float* d_g, long long n, float min_prom, long long min_dist, size_t k, const PeakPolicy& pol,
                 std::vector<am_peak>& res);

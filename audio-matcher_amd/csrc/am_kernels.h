@@ -336,6 +336,23 @@ struct SegDesc {
 hipError_t launch_hit_segments(hipStream_t st, const SegDesc* d_hits, long long n, int m, int r, int max_nsl, int kind,
                                double* parts, unsigned* pflags, am_hit_segment* d_out);
 
+// ---- am_significance.hip: per-hit significance (am_hit_significance*) ----
+constexpr int kSigSlice = 4096;   // scores of a hit's zone per workgroup of the slice kernels, counted from the zone's start
+// One hit of a launch sequence, as the kernels read it.  The zone's scores r(lo .. hi) lie at scores[z0 .. z0 + nz).
+struct SigDesc {
+    long long z0;      // first score of the zone in the score buffer
+    long long nz;      // hi - lo + 1
+    long long c;       // t - lo: the hit's own score
+    long long g;       // guard: zone index k is background when |k - c| > g
+    long long part0;   // first partial record of the hit
+    unsigned flags;    // AM_HIT_CLIPPED, AM_HIT_NONFINITE as the host found them
+    unsigned pad;
+};
+// psum: one double per slice (pass 1: the sum, pass 2: the sum of squared deviations), pmax: three words per slice
+// (count, largest background score, its lag), mean / hmax: the same per hit; d_out: n records
+hipError_t launch_hit_significance(hipStream_t st, const SigDesc* d_hits, long long n, long long max_slices, const float* scores,
+                                   double* psum, unsigned* pmax, double* mean, unsigned* hmax, am_significance* d_out);
+
 // ---- am_resample.hip: sample-rate conversion (am_resample*) ----
 constexpr int kRsThreads = 256;
 constexpr int kRsJ = 8;          // outputs per work item: k, k + W, ..., k + 7 W (one phase, its taps read once)

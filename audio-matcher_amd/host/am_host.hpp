@@ -77,6 +77,8 @@ struct Arguments {
     std::optional<float> min_confidence;      // extension: --min-confidence X, drop hits whose exact NCC is below X (am_hit_scores, 0..1)
     std::uint32_t segments = 0;               // extension: --segments M[:R], per-segment scoring of every printed hit (am_hit_segments), 0 = off
     std::uint32_t segment_radius = 4;         // ... the lags -R .. R examined per segment
+    std::optional<float> min_significance;    // extension: --min-significance Z, drop hits whose z against the local background is below Z (am_hit_significance)
+    std::optional<std::uint64_t> significance_zone_ms;   // ... --significance-zone D: the background reaches D each side of a hit (default: three snippet lengths)
     bool resample = false;                    // extension: --resample, bring the snippet to each main file's rate (am_needle_create_resampled)
     std::optional<std::uint64_t> best;        // extension: --best N, the N best hits per main file, no prominence threshold (am_match_best)
     bool live = false;                        // extension: --live, raw PCM from stdin through a monitor (am_monitor_*)
@@ -122,6 +124,15 @@ inline const char* usage_text() {
            "                         holds ('#' present, '.' absent: the part's NCC against --min-confidence if given,\n"
            "                         else 0.5), the covered fraction, the drift in ppm and the refined start's lag;\n"
            "                         each part is matched within R samples (0..16, default 4); M in 1..1024\n"
+           "  --min-significance Z   drop every hit that stands less than Z standard deviations above the scores around\n"
+           "                         it (its z: the hit's score minus the mean of the background scores, over their\n"
+           "                         standard deviation; the background is every offset within --significance-zone of\n"
+           "                         the hit and at least one snippet length away from it).  Applies to files, to\n"
+           "                         several --snippet and with --best, not with --live; with --debug, print each\n"
+           "                         hit's score, background mean and std, z and the largest background score with\n"
+           "                         its lag (default: keep every hit)\n"
+           "  --significance-zone D  how far the background reaches each side of a hit, a duration (default: three\n"
+           "                         snippet lengths; at most 4194304 samples)\n"
            "  --resample             match main files of any sample rate: the snippet is resampled to each file's rate\n"
            "                         (scipy's resample_poly filter); without it, a rate mismatch stops the run\n"
            "  --live                 read raw PCM from stdin instead of files (no FILE arguments): a live feed, matched\n"
@@ -129,7 +140,8 @@ inline const char* usage_text() {
            "                         final -- a hit is final once the next hit is found, or once --distance of audio\n"
            "                         has passed behind it, so use a short --distance for monitoring.  At end of input\n"
            "                         the label file (-o FILE; none without -o) is written as for a file.  Needs --rate;\n"
-           "                         --best, --normalize, --min-confidence and --segments do not apply\n"
+           "                         --best, --normalize, --min-confidence and --segments do not apply, nor do\n"
+           "                         --min-significance and --significance-zone\n"
            "  --rate R               --live: sample rate of the stream, in Hz\n"
            "  --encoding E           --live: s16le (default) or f32le (f32le: one channel only)\n"
            "  --channels C           --live: 1 or 2 (default 2)\n"
@@ -184,6 +196,19 @@ inline Arguments parse_arguments(int argc, const char* const* argv) {
                 throw ArgError("invalid value '" + v + "' for --min-confidence (a number in 0..1)");
             a.min_confidence = x;
         }
+        else if (s == "--min-significance") {
+            const std::string v = need(i);
+            char* end = nullptr;
+            const float z = std::strtof(v.c_str(), &end);
+            if (v.empty() || *end != '\0' || !(z == z) || z > 3.0e38f || z < -3.0e38f)
+                throw ArgError("invalid value '" + v + "' for --min-significance (a number of standard deviations)");
+            a.min_significance = z;
+        }
+        else if (s == "--significance-zone") {
+            const std::uint64_t d = dur(need(i), "--significance-zone");
+            if (d == 0) throw ArgError("invalid duration '0' for --significance-zone (must be longer than 0)");
+            a.significance_zone_ms = d;
+        }
         else if (s == "--segments") {
             const std::string v = need(i);
             const std::size_t colon = v.find(':');
@@ -237,6 +262,7 @@ inline Arguments parse_arguments(int argc, const char* const* argv) {
         if (a.encoding == "f32le" && a.channels != 1) throw ArgError("--encoding f32le takes one channel only (--channels 1)");
         if (a.best || a.normalize || a.min_confidence) throw ArgError("--live: --best, --normalize and --min-confidence do not apply");
         if (a.segments) throw ArgError("--live: --segments does not apply");
+        if (a.min_significance || a.significance_zone_ms) throw ArgError("--live: --min-significance and --significance-zone do not apply");
         return a;
     }
     if (a.no_out && a.out_file) throw ArgError("--no-out and --out are mutually exclusive");      // #[group(multiple = false)]

@@ -69,6 +69,33 @@ static std::vector<std::string> segment_lines(const Arguments& args, const am_ne
     return out;
 }
 
+// extension: --min-significance Z [--significance-zone D].  Keeps the hits whose z against their local background
+// (am_hit_significance: guard = the snippet's length - 1, radius = D at the file's rate, by default three snippet
+// lengths) is at least Z, in place; returns how many are left.  With --debug one line per hit (`prefix` in front).
+static size_t significance_filter(const Arguments& args, const am_needle* algo, const std::vector<float>& samples, std::uint32_t sr,
+                                  am_peak* peaks, size_t n, const std::string& prefix) {
+    if (n == 0) return 0;
+    size_t s_len = 0;
+    am_needle_len(algo, &s_len);
+    am_significance_params sp{};
+    sp.guard = s_len - 1;
+    sp.radius = args.significance_zone_ms ? (*args.significance_zone_ms * sr + 999) / 1000
+                                          : std::min<std::uint64_t>(3 * (std::uint64_t)s_len, AM_SIG_MAX_RADIUS);
+    std::vector<am_significance> sg(n);
+    if (am_hit_significance(algo, samples.data(), samples.size(), AM_FMT_F32_MONO, peaks, n, &sp, sg.data()) != AM_OK)
+        throw std::runtime_error(std::string("am_hit_significance: ") + am_last_error_string());
+    size_t kept = 0;
+    for (size_t i = 0; i < n; ++i) {
+        const bool keep = sg[i].z >= *args.min_significance;   // (a NaN z -- no background, a non-finite sample -- is dropped too)
+        if (args.verbosity >= 2)
+            std::printf("%shit %zu: score %.6f mean %.6f std %.6f z %.2f side_max %.6f lag %d%s\n", prefix.c_str(), i + 1,
+                        (double)sg[i].score, (double)sg[i].bg_mean, (double)sg[i].bg_std, (double)sg[i].z, (double)sg[i].side_max,
+                        (int)sg[i].side_lag, keep ? "" : " (dropped)");
+        if (keep) peaks[kept++] = peaks[i];
+    }
+    return kept;
+}
+
 // extension: several --snippet files.  Each main file is matched by ONE am_match_multi_varlen call (the snippets may
 // differ in length: each uses an overlap of its own length at the main file's rate, as make_params does for one);
 // with --normalize, which that call refuses, snippet by snippet with am_match.  The label file is timelabel_from_peaks
@@ -203,6 +230,7 @@ static int run_multi(const Arguments& args) {
                     }
                     n[j] = kept;
                 }
+                if (args.min_significance) n[j] = significance_filter(args, handles[j], m_samples, m_sr, pk, n[j], snips[j].name + ": ");
                 if (args.verbosity >= 1) {
                     const std::vector<std::string> lines = offset_lines(pk, n[j], m_sr);
                     const std::vector<std::string> segs =
@@ -468,6 +496,7 @@ int main(int argc, char** argv) {
                 }
                 n = kept;
             }
+            if (args.min_significance) n = significance_filter(args, algo, m_samples, m_sr, peaks.data(), n, "");   // extension: --min-significance
             if (args.verbosity >= 1) {
                 const std::vector<std::string> lines = offset_lines(peaks.data(), n, m_sr);                       // mod.rs:89
                 const std::vector<std::string> segs =

@@ -83,6 +83,27 @@ AM_HIT_EMPTY_SEGMENT = 8
 AM_SEG_MAX_SEGMENTS, AM_SEG_MAX_RADIUS = 1024, 16
 
 
+class AmSignificanceParams(C.Structure):   # am_significance_params (include/audiomatch.h, per-hit significance)
+    _fields_ = [("guard", C.c_uint64), ("radius", C.c_uint64)]
+
+
+class HitSignificance(C.Structure):        # am_significance: one hit against its local background
+    _fields_ = [("score", C.c_float), ("bg_mean", C.c_float), ("bg_std", C.c_float), ("z", C.c_float),
+                ("side_max", C.c_float), ("side_lag", C.c_int32), ("n_bg", C.c_uint32), ("flags", C.c_uint32)]
+
+    def __repr__(self):
+        return (f"HitSignificance(score={self.score!r}, bg_mean={self.bg_mean!r}, bg_std={self.bg_std!r}, z={self.z!r}, "
+                f"side_max={self.side_max!r}, side_lag={self.side_lag}, n_bg={self.n_bg}, flags={self.flags})")
+
+    def pack(self) -> bytes:
+        """The record's 32 bytes (for bit-for-bit comparisons)."""
+        return bytes(self)
+
+
+AM_HIT_NO_BACKGROUND, AM_HIT_FLAT_BACKGROUND, AM_HIT_CLIPPED = 16, 32, 64
+AM_SIG_MAX_RADIUS = 1 << 22
+
+
 class AmMatchParams(C.Structure):
     _fields_ = [("sr", C.c_uint32), ("chunk", C.c_uint64), ("overlap", C.c_uint64),
                 ("min_prominence", C.c_float), ("min_distance", C.c_uint64),
@@ -240,6 +261,13 @@ _SIGNATURES = {
                                                C.POINTER(AmSegmentParams), C.POINTER(HitSegment)]),
     "am_hit_segments_summary": (C.c_int, [C.POINTER(HitSegment), C.c_uint32, C.c_size_t, C.c_float,
                                           C.POINTER(AmSegmentSummary)]),
+    "am_hit_significance_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.POINTER(AmPeak), C.c_size_t,
+                                             C.POINTER(AmSignificanceParams), C.POINTER(HitSignificance)]),
+    "am_hit_significance": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.POINTER(AmPeak), C.c_size_t,
+                                      C.POINTER(AmSignificanceParams), C.POINTER(HitSignificance)]),
+    "am_hit_significance_batch_device": (C.c_int, [C.POINTER(C.c_void_p), C.c_size_t, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t),
+                                                   C.c_size_t, C.c_int, C.POINTER(AmPeak), C.c_size_t, C.POINTER(C.c_size_t),
+                                                   C.POINTER(AmSignificanceParams), C.POINTER(HitSignificance)]),
     "am_resample_len": (C.c_int, [C.c_size_t, C.c_uint32, C.c_uint32, C.POINTER(C.c_size_t)]),
     "am_resample": (C.c_int, [C.c_int, C.c_void_p, C.c_size_t, C.c_int, C.c_uint32, C.c_uint32, C.c_void_p, C.c_size_t,
                               C.POINTER(C.c_size_t)]),
@@ -504,6 +532,11 @@ def _peak_array(peaks):
 
 def _hit_scores(buf, idx):
     return [HitScore(buf[i].position, buf[i].ncc, buf[i].gain, buf[i].window_db, int(buf[i].flags)) for i in idx]
+
+
+def _hit_significance(buf, idx):
+    """Copies of the records at `idx` (they outlive the call's buffer)."""
+    return [HitSignificance.from_buffer_copy(buf[i]) for i in idx]
 
 
 def _hit_segments(buf, first, m):
@@ -792,6 +825,31 @@ class HipConvolve:
         sp = AmSegmentParams(m, int(radius))
         _check(lib().am_hit_segments_device(self._h, ptr, length, int(fmt), _peak_array(peaks), k, C.byref(sp), out))
         return [_hit_segments(out, i * m, m) for i in range(k)]
+
+    # -- per-hit significance --
+    def hit_significance(self, haystack, peaks, guard: int, radius: int):
+        """am_hit_significance: for each of `peaks` of a host haystack (as in hit_scores) its HitSignificance -- the
+        hit's score against the scores at lags guard < |lag| <= radius around it."""
+        a = np.asarray(haystack)
+        if a.dtype == np.int16:
+            a = np.ascontiguousarray(a)
+            fmt, length = Fmt.S16_STEREO, a.size // 2
+        else:
+            a = np.ascontiguousarray(a, dtype=np.float32)
+            fmt, length = Fmt.F32_MONO, a.size
+        k = len(peaks)
+        out = (HitSignificance * max(1, k))()
+        sp = AmSignificanceParams(int(guard), int(radius))
+        _check(lib().am_hit_significance(self._h, a.ctypes.data, length, int(fmt), _peak_array(peaks), k, C.byref(sp), out))
+        return _hit_significance(out, range(k))
+
+    def hit_significance_device(self, ptr: int, length: int, peaks, guard: int, radius: int, fmt: int = Fmt.F32_MONO):
+        """am_hit_significance_device: the same for a haystack resident on this needle's device."""
+        k = len(peaks)
+        out = (HitSignificance * max(1, k))()
+        sp = AmSignificanceParams(int(guard), int(radius))
+        _check(lib().am_hit_significance_device(self._h, ptr, length, int(fmt), _peak_array(peaks), k, C.byref(sp), out))
+        return _hit_significance(out, range(k))
 
 
 class MatchStream:
@@ -1152,6 +1210,29 @@ def hit_segments_batch_device(algos, ptrs, lengths, peaks_per_pair, segments: in
     sp = AmSegmentParams(m, int(radius))
     _check(lib().am_hit_segments_batch_device(handles, nn, arr_p, arr_l, k, int(fmt), buf, cap, counts, C.byref(sp), out))
     return [[[_hit_segments(out, ((h * nn + j) * cap + i) * m, m) for i in range(counts[h * nn + j])] for j in range(nn)]
+            for h in range(k)]
+
+
+def hit_significance_batch_device(algos, ptrs, lengths, peaks_per_pair, guard: int, radius: int, fmt: int = Fmt.F32_MONO):
+    """am_hit_significance_batch_device: peaks_per_pair[k][j] as in hit_scores_batch_device; result [k][j][i] = the
+    HitSignificance of hit i of haystack k against needle j."""
+    nn, k = len(algos), len(ptrs)
+    cap = max([1] + [len(peaks_per_pair[h][j]) for h in range(k) for j in range(nn)])
+    handles = (C.c_void_p * max(1, nn))(*[a._h for a in algos])
+    arr_p = (C.c_void_p * max(1, k))(*ptrs)
+    arr_l = (C.c_size_t * max(1, k))(*lengths)
+    buf = (AmPeak * max(1, cap * k * nn))()
+    counts = (C.c_size_t * max(1, k * nn))()
+    for h in range(k):
+        for j in range(nn):
+            q = h * nn + j
+            counts[q] = len(peaks_per_pair[h][j])
+            for i, p in enumerate(peaks_per_pair[h][j]):
+                buf[q * cap + i] = AmPeak(int(p.start), int(p.end), float(p.height), float(p.prominence))
+    out = (HitSignificance * max(1, cap * k * nn))()
+    sp = AmSignificanceParams(int(guard), int(radius))
+    _check(lib().am_hit_significance_batch_device(handles, nn, arr_p, arr_l, k, int(fmt), buf, cap, counts, C.byref(sp), out))
+    return [[_hit_significance(out, range((h * nn + j) * cap, (h * nn + j) * cap + counts[h * nn + j])) for j in range(nn)]
             for h in range(k)]
 
 

@@ -60,6 +60,30 @@ pub struct AmHitSegment {
     pub level_db: f32,
     pub flags: u32,
 }
+/// am_significance_params: per-hit significance (am_hit_significance*)
+#[repr(C)]
+#[derive(Clone, Copy, Default, Debug)]
+pub struct AmSignificanceParams {
+    pub guard: u64,
+    pub radius: u64,
+}
+/// am_significance: one hit against its local background (32 bytes)
+#[repr(C)]
+#[derive(Clone, Copy, Default, Debug)]
+pub struct AmSignificance {
+    pub score: f32,
+    pub bg_mean: f32,
+    pub bg_std: f32,
+    pub z: f32,
+    pub side_max: f32,
+    pub side_lag: i32,
+    pub n_bg: u32,
+    pub flags: u32,
+}
+pub const AM_HIT_NO_BACKGROUND: u32 = 16;
+pub const AM_HIT_FLAT_BACKGROUND: u32 = 32;
+pub const AM_HIT_CLIPPED: u32 = 64;
+pub const AM_SIG_MAX_RADIUS: u64 = 1 << 22;
 /// am_segment_summary: coverage, drift and refined start of one hit
 #[repr(C)]
 #[derive(Clone, Copy, Default, Debug)]
@@ -214,6 +238,20 @@ extern "C" {
     ) -> c_int;
     pub fn am_hit_segments_summary(
         seg: *const AmHitSegment, segments: u32, needle_len: usize, min_ncc: f32, out: *mut AmSegmentSummary,
+    ) -> c_int;
+    /// per-hit significance: each hit's score against its local background (audiomatch.h)
+    pub fn am_hit_significance(
+        h: *const AmNeedle, haystack: *const std::ffi::c_void, len: usize, sample_format: c_int, peaks: *const AmPeak, n: usize,
+        sp: *const AmSignificanceParams, out: *mut AmSignificance,
+    ) -> c_int;
+    pub fn am_hit_significance_device(
+        h: *const AmNeedle, d_haystack: *const std::ffi::c_void, len: usize, sample_format: c_int, peaks: *const AmPeak, n: usize,
+        sp: *const AmSignificanceParams, out: *mut AmSignificance,
+    ) -> c_int;
+    pub fn am_hit_significance_batch_device(
+        needles: *const *const AmNeedle, n_needles: usize, d_haystacks: *const *const std::ffi::c_void, lens: *const usize,
+        n_hay: usize, sample_format: c_int, peaks: *const AmPeak, cap_per_pair: usize, n_peaks: *const usize,
+        sp: *const AmSignificanceParams, out: *mut AmSignificance,
     ) -> c_int;
     /// the k best matches: the first k peaks of find_peaks over the Valid scores, no prominence threshold (audiomatch.h)
     pub fn am_match_best(

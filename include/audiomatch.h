@@ -318,6 +318,68 @@ typedef struct am_segment_summary {
 int am_hit_segments_summary(const am_hit_segment* seg, uint32_t segments, size_t needle_len, float min_ncc,
                             am_segment_summary* out);
 
+/* ---- per-hit significance --------------------------------------------------------- */
+/* How far a hit stands out from the scores around it: the peak-to-sidelobe measure of matched filtering.  NCC
+ * (am_hit_scores) says how well the window matches the needle; it cannot tell a certain hit under a loud voice-over
+ * (NCC 0.3, 100 sigma above its surroundings) from an ambiguous one in tonal material (NCC 0.8, 4 sigma).
+ * With t = peak.start, S the needle's length, G = sp->guard, B = sp->radius, lo = max(0, t - B) and
+ * hi = min(len - S, t + B):
+ *   span        the samples x[lo, hi + S); for AM_FMT_S16_STEREO the bit-exact down-mix of those frames, as above.
+ *   scores      r(u), u in [lo, hi]: exactly the f32 scores am_correlate returns for the span as a buffer of its own with
+ *               AM_MODE_VALID and AM_SCALE_LIB under the options in force at call time -- the same transform pass with
+ *               lead 0, the same half-precision redo and, under "score_norm", the same normalisation with the same
+ *               floor (the scores are then NCC).
+ *   background  U = { u in [lo, hi] : |u - t| > G },  n_bg = |U|.  Lags within G of the hit are its own autocorrelation
+ *               lobes; G = S - 1 clears them all.
+ *   reductions  in f64 over the f32 scores, in one fixed order that depends on this hit's zone only, each result
+ *               rounded to f32 once, at the end:
+ *                 bg_mean  = sum_U r / n_bg
+ *                 bg_std   = sqrt( sum_U (r - mean)^2 / n_bg )     (two passes, not E[r^2] - mean^2)
+ *                 z        = (r(t) - mean) / std
+ *                 side_max = max_U r, side_lag = u - t of that score; ties go to the smaller |u - t|, then to the
+ *                            negative lag.
+ *   flags       AM_HIT_NONFINITE: a sample of the span, or of the needle, is not finite; the five float fields are NaN,
+ *               side_lag = 0, n_bg as counted; no flag but AM_HIT_CLIPPED beside it.
+ *               AM_HIT_NO_BACKGROUND: n_bg < 2; score is given, bg_mean, bg_std, z and side_max are NaN, side_lag = 0.
+ *               AM_HIT_FLAT_BACKGROUND: std == 0; z is +inf, -inf or 0 by the sign of score - mean.
+ *               AM_HIT_CLIPPED: lo > t - B or hi < t + B (the zone is cut by an end of the haystack); informational,
+ *               combines with any other flag.
+ * A hit's record depends on the needle, the samples of its span, G, B and the options only -- not on the other hits, the
+ * batch or the entry point: every hit's span is correlated on its own even where spans overlap, and the three forms
+ * below agree bit for bit.  A hit costs the transforms of one am_correlate_device call of its span's length plus a reduction
+ * of about a quarter of their time (tools/hit_significance_bench.py, profiles/r13/).  A second occurrence of the needle inside the zone raises bg_std and side_max: by design.
+ * peaks and out are host memory, out[i] scores peaks[i]; len counts samples (frames for AM_FMT_S16_STEREO).
+ * AM_ERR_INVALID_ARG, naming the hit (and pair): a null pointer with n > 0, sp == NULL, guard >= radius,
+ * radius > AM_SIG_MAX_RADIUS, an unknown sample format, peak.start + S > len, a haystack on another device than the
+ * needle.  n = 0: AM_OK, nothing launched. */
+enum { AM_HIT_NO_BACKGROUND = 16, AM_HIT_FLAT_BACKGROUND = 32, AM_HIT_CLIPPED = 64 };
+#define AM_SIG_MAX_RADIUS (1u << 22)
+typedef struct am_significance_params {
+    uint64_t guard;    /* G: lags with |u - t| <= G are not background (the hit's own autocorrelation lobes; S - 1 clears them) */
+    uint64_t radius;   /* B: lags with G < |u - t| <= B are background; G < B <= AM_SIG_MAX_RADIUS */
+} am_significance_params;
+typedef struct am_significance {
+    float score;       /* r(t) */
+    float bg_mean;     /* mean of the background scores */
+    float bg_std;      /* their population standard deviation */
+    float z;           /* (r(t) - mean) / std */
+    float side_max;    /* largest background score */
+    int32_t side_lag;  /* its lag relative to t */
+    uint32_t n_bg;     /* background lags counted */
+    uint32_t flags;    /* AM_HIT_* */
+} am_significance;      /* 32 bytes, no padding */
+/* the haystack resident on the needle's device */
+int am_hit_significance_device(const am_needle* h, const void* d_haystack, size_t len, int sample_format,
+                               const am_peak* peaks, size_t n, const am_significance_params* sp, am_significance* out);
+/* the haystack in host memory: only the spans [lo, hi + S) of the hits are copied (merged where they overlap) */
+int am_hit_significance(const am_needle* h, const void* haystack, size_t len, int sample_format,
+                        const am_peak* peaks, size_t n, const am_significance_params* sp, am_significance* out);
+/* the pair layout of am_hit_scores_batch_device (other slots stay untouched), needles of any lengths */
+int am_hit_significance_batch_device(const am_needle* const* needles, size_t n_needles,
+                                     const void* const* d_haystacks, const size_t* lens, size_t n_hay, int sample_format,
+                                     const am_peak* peaks, size_t cap_per_pair, const size_t* n_peaks,
+                                     const am_significance_params* sp, am_significance* out);
+
 /* ---- streaming ingest ---------------------------------------------------------- */
 /* calc_chunks consumes a lazy ExactSizeIterator<Item = f32> (audio_matcher.rs:88-97): the decoder
  * yields frames (mp3_reader.rs:13-41) and the windows are cut as they arrive (:104).  The same

@@ -154,6 +154,20 @@ public:
         check(am_hit_segments_device(h_, d_haystack, len, sample_format, peaks.data(), peaks.size(), &sp, out.data()));
         return out;
     }
+    // per-hit significance (am_hit_significance): each peak's score against the scores at lags guard < |lag| <= radius
+    // around it (mean, standard deviation, z and the largest background score), one record per peak
+    std::vector<am_significance> hit_significance(const void* haystack, std::size_t len, int sample_format, const std::vector<am_peak>& peaks,
+                                                  const am_significance_params& sp) const {
+        std::vector<am_significance> out(peaks.size());
+        check(am_hit_significance(h_, haystack, len, sample_format, peaks.data(), peaks.size(), &sp, out.data()));
+        return out;
+    }
+    std::vector<am_significance> hit_significance_device(const void* d_haystack, std::size_t len, int sample_format,
+                                                         const std::vector<am_peak>& peaks, const am_significance_params& sp) const {
+        std::vector<am_significance> out(peaks.size());
+        check(am_hit_significance_device(h_, d_haystack, len, sample_format, peaks.data(), peaks.size(), &sp, out.data()));
+        return out;
+    }
     // coverage, drift and refined start of one hit from its records (am_hit_segments_summary; no device needed)
     static am_segment_summary segment_summary(const am_hit_segment* seg, std::uint32_t segments, std::size_t needle_len, float min_ncc) {
         am_segment_summary out{};
