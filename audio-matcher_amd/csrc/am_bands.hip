@@ -1,0 +1,520 @@
+// am_bands.hip -- per-band hit scoring (am_hit_bands*, include/audiomatch.h): the pass of am_hits.hip resolved along
+// frequency.  For a hit at t, frames of F = 2^frame_log2 samples at hop H = F / 2 (J = floor((S - F) / H) + 1 of them),
+// the Hann window w and the spectra X_j, N_j of the windowed haystack and needle frames, in f64:
+//   P_xn[k] = sum_j X_j[k] conj(N_j[k]),   P_xx[k] = sum_j |X_j[k]|^2,   P_nn[k] = sum_j |N_j[k]|^2      (k = 0 .. F/2)
+// summed over the bins of each band, and from those per band the NCC at lag 0, the coherence, the gain, the level and the
+// band's share of the needle's energy.
+//
+// Two kernels on the context's stream:
+//   band_frames   one workgroup per (hit, group of kBandGroup consecutive frames): per frame it loads F samples of x and
+//                 of n, widens and windows them, packs z = x + i n and runs ONE F-point complex f64 FFT in LDS (radix 2,
+//                 decimation in time: the samples are stored bit-reversed, the spectrum comes out in order; both
+//                 parities of frame_log2 alike), untangles X[k] = (Z[k] + conj Z[F-k]) / 2, N[k] = (Z[k] - conj Z[F-k]) / 2i
+//                 and adds the three products to the thread's bins (registers).  After the group's frames the bins go
+//                 through LDS to one sum per band and value, in a fixed order, and the workgroup writes one partial
+//                 record: (Re C, Im C, E_x, E_n) per band and E_n over every bin, one 64-bit store per lane.
+//   band_combine  one wave per hit: adds the hit's partials in group order, forms the B records and sets the flags.
+// Window and twiddles come from a table built on the host in f64, once per (device, F): the kernels compute no
+// transcendental but the final log10.  A frame whose haystack samples are all zero counts as X_j = 0 exactly (and a
+// frame of needle zeros as N_j = 0): what the packed transform would leak from the other signal, 1e-32 of its power,
+// never turns digital silence into a level.
+// The kernels read x[t + u] for u in [0, (J - 1) H + F) and n[0 .. (J - 1) H + F) only.  A hit's records depend on the
+// needle, the samples it reads, the parameters and the floor only (groups start at multiples of kBandGroup frames, every
+// reduction runs in a fixed order; one kernel serves both sample formats): the single, batch and host forms agree
+// bit for bit.
+#include "am_internal.h"
+
+namespace am {
+
+namespace {
+
+constexpr int kBandThreads = 256;
+constexpr int kBandMaxF = 1 << 12;
+constexpr int kBandLds = kBandMaxF + (kBandMaxF >> 5) + (kBandMaxF >> 10);   // one padded array of F doubles
+constexpr int kBandBins = (kBandMaxF / 2) / kBandThreads + 1;                // bins per thread: k = tid + m * kBandThreads <= F / 2
+static_assert(AM_BAND_MAX_BANDS <= 64, "band_combine forms one record per lane");
+
+typedef __attribute__((address_space(1))) const float gfloat;
+typedef __attribute__((address_space(1))) const unsigned guint;   // (one i16 stereo frame)
+
+// Element i of an LDS array of 8-byte values, one pad per 32 and per 1024: the bit-reversed store of a frame (stride
+// F / 2, F / 4, ...) and the butterflies of the first stages (stride 2, 4, ...) then spread over the banks.
+__device__ __forceinline__ int lpad(int i) { return i + (i >> 5) + (i >> 10); }
+
+struct BandArgs {
+    am_band_params bp;
+    int nrec;   // doubles per partial record: 4 B + 1
+};
+
+__global__ __launch_bounds__(kBandThreads) void band_frames_kernel(const BandDesc* __restrict__ hits, long long h0, BandArgs a,
+                                                                   const double* __restrict__ tab, double* __restrict__ parts,
+                                                                   unsigned* __restrict__ pflags) {
+    __shared__ double sh[2 * kBandLds];
+    __shared__ unsigned wbits[kBandThreads / 64];
+    const BandDesc d = hits[h0 + blockIdx.y];
+    if ((int)blockIdx.x >= d.ngroups) return;   // (a hit of fewer groups than the launch's largest: whole workgroups leave together)
+    const int lf = (int)a.bp.frame_log2, F = 1 << lf, H = F >> 1;
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    double* re = sh;
+    double* im = sh + kBandLds;
+    const double2* tw = reinterpret_cast<const double2*>(tab + F);   // tw[k] = (cos, -sin)(2 pi k / F), k < F / 2
+    const long long j0 = (long long)blockIdx.x * kBandGroup;
+    const int nfr = (int)min((long long)kBandGroup, d.nframes - j0);
+    double acc[kBandBins][4];   // the thread's bins: Re P_xn, Im P_xn, P_xx, P_nn
+#pragma unroll
+    for (int m = 0; m < kBandBins; ++m) acc[m][0] = acc[m][1] = acc[m][2] = acc[m][3] = 0.0;
+    bool bad = false;
+    for (int f = 0; f < nfr; ++f) {
+        const long long u0 = (j0 + f) * H;   // the frame's first sample: u0 + F <= (J - 1) H + F <= S
+        unsigned nz = 0;
+        for (int i = tid; i < F; i += kBandThreads) {
+            const float xv = d.kind ? norm_downmix(__builtin_bit_cast(short2, ((guint*)d.win)[u0 + i])) : ((gfloat*)d.win)[u0 + i];
+            const float nv = ((gfloat*)d.needle)[u0 + i];
+            bad |= !__builtin_isfinite(xv) || !__builtin_isfinite(nv);
+            nz |= (xv != 0.0f ? 1u : 0u) | (nv != 0.0f ? 2u : 0u);
+            const double w = tab[i];
+            const int p = lpad((int)(__brev((unsigned)i) >> (32 - lf)));
+            re[p] = (double)xv * w;
+            im[p] = (double)nv * w;
+        }
+        for (int off = 32; off > 0; off >>= 1) nz |= __shfl_xor(nz, off, 64);
+        if (lane == 0) wbits[wv] = nz;
+        __syncthreads();
+        for (int s = 1; s <= lf; ++s) {
+            const int h = 1 << (s - 1);
+            for (int b = tid; b < H; b += kBandThreads) {
+                const int pos = b & (h - 1);
+                const int i = lpad(((b >> (s - 1)) << s) + pos), j = lpad(((b >> (s - 1)) << s) + pos + h);
+                const double2 w = tw[pos << (lf - s)];
+                const double ar = re[i], ai = im[i], br = re[j], bi = im[j];
+                const double tr = w.x * br - w.y * bi, ti = w.x * bi + w.y * br;
+                re[i] = ar + tr;
+                im[i] = ai + ti;
+                re[j] = ar - tr;
+                im[j] = ai - ti;
+            }
+            __syncthreads();
+        }
+        unsigned any = 0;
+#pragma unroll
+        for (int i = 0; i < kBandThreads / 64; ++i) any |= wbits[i];
+        const bool has_x = any & 1u, has_n = any & 2u;
+#pragma unroll
+        for (int m = 0; m < kBandBins; ++m) {
+            const int k = tid + m * kBandThreads;
+            if (k <= H) {
+                const int p = lpad(k), q = lpad((F - k) & (F - 1));
+                const double zr = re[p], zi = im[p], mr = re[q], mi = im[q];
+                const double xr = has_x ? 0.5 * (zr + mr) : 0.0, xi = has_x ? 0.5 * (zi - mi) : 0.0;
+                const double nr = has_n ? 0.5 * (zi + mi) : 0.0, ni = has_n ? 0.5 * (mr - zr) : 0.0;
+                acc[m][0] += xr * nr + xi * ni;
+                acc[m][1] += xi * nr - xr * ni;
+                acc[m][2] += xr * xr + xi * xi;
+                acc[m][3] += nr * nr + ni * ni;
+            }
+        }
+        __syncthreads();   // (the next frame's samples go where these were read)
+    }
+    // bins to bands, two values at a time through LDS: wave w sums quantity w, w + 4, ... (lane l the bins lo + l, lo + l + 64,
+    // ..., then a butterfly over the wave) and its lane 0 stores the sum: one 64-bit store per lane and quantity
+    const int nb = (int)a.bp.n_bands;
+    double* out = parts + (d.part0 + blockIdx.x) * (long long)a.nrec;
+    for (int pass = 0; pass < 2; ++pass) {
+#pragma unroll
+        for (int m = 0; m < kBandBins; ++m) {
+            const int k = tid + m * kBandThreads;
+            if (k <= H) {
+                re[k] = acc[m][2 * pass];
+                im[k] = acc[m][2 * pass + 1];
+            }
+        }
+        __syncthreads();
+        const int nq = 2 * nb + pass;   // (the second pass also sums E_n over every bin)
+        for (int q = wv; q < nq; q += kBandThreads / 64) {
+            const int b = q >> 1;
+            const int lo = b < nb ? (int)a.bp.edges[b] : 0, hi = b < nb ? (int)a.bp.edges[b + 1] : H + 1;
+            const double* src = (q & 1) || b == nb ? im : re;
+            double v = 0.0;
+            for (int k = lo + lane; k < hi; k += 64) v += src[k];
+            for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+            if (lane == 0) out[b < nb ? 4 * b + 2 * pass + (q & 1) : 4 * nb] = v;
+        }
+        __syncthreads();
+    }
+    const int any_bad = __syncthreads_or(bad ? 1 : 0);
+    if (tid == 0) pflags[d.part0 + blockIdx.x] = (unsigned)any_bad;
+}
+
+// One wave per hit: lane k adds value k (k + 64, ...) of the hit's partial records in group order, lane b forms band b's record.
+__global__ __launch_bounds__(64) void band_combine_kernel(const BandDesc* __restrict__ hits, int nb, double empty_ratio,
+                                                          const double* __restrict__ parts, const unsigned* __restrict__ pflags,
+                                                          am_hit_band* __restrict__ out) {
+    __shared__ double sh[4 * AM_BAND_MAX_BANDS + 1];
+    const long long h = blockIdx.x;
+    const int lane = threadIdx.x;
+    const BandDesc d = hits[h];
+    const int nrec = 4 * nb + 1;
+    for (int k = lane; k < nrec; k += 64) {
+        double t = 0.0;
+        for (long long g = 0; g < d.ngroups; ++g) t += parts[(d.part0 + g) * nrec + k];
+        sh[k] = t;
+    }
+    unsigned bf = 0;
+    for (long long g = lane; g < d.ngroups; g += 64) bf |= pflags[d.part0 + g];
+    const int bad = __syncthreads_or(bf != 0 ? 1 : 0);
+    if (lane >= nb) return;
+    const double cr = sh[4 * lane], ci = sh[4 * lane + 1], ex = sh[4 * lane + 2], en = sh[4 * lane + 3], ent = sh[4 * nb];
+    const float nan = __builtin_nanf("");
+    float ncc, coh, gain, ldb, share;
+    unsigned flags = 0;
+    if (bad) {
+        flags = AM_HIT_NONFINITE;
+        ncc = coh = gain = ldb = share = nan;
+    } else {
+        const double sv = ent > 0.0 ? en / ent : 0.0;   // (a silent needle: every band is empty)
+        share = (float)sv;
+        if (sv < empty_ratio) {
+            flags = AM_HIT_EMPTY_BAND;
+            ncc = coh = gain = 0.0f;
+            ldb = ex > 0.0 ? __builtin_inff() : nan;
+        } else {
+            if (ex == 0.0 || ex < en * d.floor_ratio) {
+                flags = AM_HIT_BELOW_FLOOR;
+                ncc = coh = 0.0f;
+            } else {
+                const double den = sqrt(ex * en);
+                ncc = (float)(cr / den);
+                coh = (float)(sqrt(cr * cr + ci * ci) / den);
+            }
+            gain = (float)(cr / en);
+            ldb = ex == 0.0 ? -__builtin_inff() : (float)(10.0 * log10(ex / en));
+        }
+    }
+    // three 64-bit stores per lane (volatile: the compiler does not merge them): no record leaves as one wide store
+    // (tools/check_store_hazard.py)
+    volatile unsigned long long* o = reinterpret_cast<volatile unsigned long long*>(out + h * nb + lane);
+    o[0] = (unsigned long long)__float_as_uint(ncc) | ((unsigned long long)__float_as_uint(coh) << 32);
+    o[1] = (unsigned long long)__float_as_uint(gain) | ((unsigned long long)__float_as_uint(ldb) << 32);
+    o[2] = (unsigned long long)__float_as_uint(share) | ((unsigned long long)flags << 32);
+}
+
+}  // namespace
+
+hipError_t launch_hit_bands(hipStream_t st, const BandDesc* d_hits, long long n, const am_band_params& bp, int max_groups,
+                            double empty_ratio, const double* tab, double* parts, unsigned* pflags, am_hit_band* d_out) {
+    if (n <= 0) return hipSuccess;
+    BandArgs a{};
+    a.bp = bp;
+    a.nrec = band_record_len((int)bp.n_bands);
+    for (long long h0 = 0; h0 < n; h0 += kHitMaxGridY) {   // (more hits than one grid column holds: a few launches)
+        const dim3 grid((unsigned)max_groups, (unsigned)std::min<long long>(kHitMaxGridY, n - h0));
+        hipLaunchKernelGGL(band_frames_kernel, grid, dim3(kBandThreads), 0, st, d_hits, h0, a, tab, parts, pflags);
+        hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return e;
+    }
+    hipLaunchKernelGGL(band_combine_kernel, dim3((unsigned)n), dim3(64), 0, st, d_hits, (int)bp.n_bands, empty_ratio, (const double*)parts,
+                       (const unsigned*)pflags, d_out);
+    return hipGetLastError();
+}
+
+// ---- host side -------------------------------------------------------------------------------------------------------
+
+namespace {
+
+constexpr double kPi = 3.14159265358979323846;
+
+long long band_frames(long long s, int lf) { return (s - (1ll << lf)) / (1ll << (lf - 1)) + 1; }   // J (s >= F)
+// the samples a hit reads, counted from its start: (J - 1) H + F
+size_t band_span(size_t s, int lf) { return (size_t)((band_frames((long long)s, lf) - 1) * (1ll << (lf - 1)) + (1ll << lf)); }
+
+// the table of F on c's device, built on first use and kept until am_shutdown: w[0 .. F), then (cos, -sin)(2 pi k / F), k < F / 2
+int band_table(Ctx* c, int lf, const double** d_tab) {
+    DevBuf& b = c->band_tabs[lf];
+    if (b.p) { *d_tab = static_cast<const double*>(b.p); return AM_OK; }
+    const size_t f = (size_t)1 << lf;
+    std::vector<double> t(2 * f);
+    for (size_t i = 0; i < f; ++i) t[i] = 0.5 - 0.5 * std::cos(2.0 * kPi * (double)i / (double)f);
+    for (size_t k = 0; k < f / 2; ++k) {
+        t[f + 2 * k] = std::cos(2.0 * kPi * (double)k / (double)f);
+        t[f + 2 * k + 1] = -std::sin(2.0 * kPi * (double)k / (double)f);
+    }
+    int rc;
+    if ((rc = b.ensure(sizeof(double) * t.size()))) return rc;
+    hipError_t e = hipMemcpyAsync(b.p, t.data(), sizeof(double) * t.size(), hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);   // (t leaves scope)
+    if (e != hipSuccess) { b.release(); return hip_fail(e, "hipMemcpy(band table)"); }
+    *d_tab = static_cast<const double*>(b.p);
+    return AM_OK;
+}
+
+// AM_ERR_INVALID_ARG unless bp is a valid request
+int band_check_params(const am_band_params* bp) {
+    if (bp->frame_log2 < 8 || bp->frame_log2 > 12)
+        return fail(AM_ERR_INVALID_ARG, "frame_log2 " + std::to_string(bp->frame_log2) + " outside 8 .. 12");
+    if (bp->n_bands == 0) return fail(AM_ERR_INVALID_ARG, "n_bands = 0");
+    if (bp->n_bands > AM_BAND_MAX_BANDS)
+        return fail(AM_ERR_INVALID_ARG, "n_bands " + std::to_string(bp->n_bands) + " > AM_BAND_MAX_BANDS (" + std::to_string(AM_BAND_MAX_BANDS) + ")");
+    for (uint32_t b = 0; b < bp->n_bands; ++b)
+        if (bp->edges[b] >= bp->edges[b + 1])
+            return fail(AM_ERR_INVALID_ARG, "edges[" + std::to_string(b + 1) + "] = " + std::to_string(bp->edges[b + 1]) + ": edges not strictly ascending");
+    const uint32_t top = (1u << bp->frame_log2) / 2 + 1;
+    if (bp->edges[bp->n_bands] > top)
+        return fail(AM_ERR_INVALID_ARG, "edges[" + std::to_string(bp->n_bands) + "] = " + std::to_string(bp->edges[bp->n_bands]) + " > F / 2 + 1 (" +
+                                            std::to_string(top) + ")");
+    return AM_OK;
+}
+
+// ... and unless a needle of s samples holds one frame (`who`: "" or "needle j: ")
+int band_check_needle(const am_band_params* bp, size_t s, const std::string& who) {
+    if (s < ((size_t)1 << bp->frame_log2))
+        return fail(AM_ERR_INVALID_ARG, who + "needle length " + std::to_string(s) + " < frame length " + std::to_string((size_t)1 << bp->frame_log2));
+    return AM_OK;
+}
+
+double band_floor_ratio(const am_needle* h) {
+    return std::pow(10.0, -(double)snapshot_opts(h).score_norm_floor_db / 10.0);
+}
+
+// the table entry of hit pk (checks as hit_desc does, same messages)
+int band_desc(const am_needle* h, const void* hay, size_t len, int sample_format, const am_peak& pk, int lf, double floor_ratio,
+              const HitWhere& where, BandDesc* d) {
+    HitDesc hd{};
+    int rc;
+    if ((rc = hit_desc(h, hay, len, sample_format, pk, 0.0, where, &hd))) return rc;
+    d->win = hd.win;
+    d->needle = hd.needle;
+    d->nframes = band_frames(hd.s, lf);
+    d->part0 = 0;
+    d->floor_ratio = floor_ratio;
+    d->kind = hd.kind;
+    d->ngroups = (int)((d->nframes + kBandGroup - 1) / kBandGroup);
+    return AM_OK;
+}
+
+// scores every hit of `hits` in one launch sequence on c's stream; out[i]: host destination of hit i's bp.n_bands records
+int score_bands(Ctx* c, std::vector<BandDesc>& hits, const am_band_params& bp, am_hit_band* const* out) {
+    const long long n = (long long)hits.size(), nb = bp.n_bands;
+    if (n == 0) return AM_OK;
+    const size_t rec = sizeof(double) * (size_t)band_record_len((int)nb);
+    long long total = 0;
+    int max_groups = 0;
+    for (BandDesc& d : hits) {
+        d.part0 = total;
+        total += d.ngroups;
+        max_groups = std::max(max_groups, d.ngroups);
+    }
+    const size_t n_out = (size_t)(n * nb);
+    const double* tab = nullptr;
+    int rc;
+    if ((rc = band_table(c, (int)bp.frame_log2, &tab))) return rc;
+    if ((rc = c->band_tab.ensure(sizeof(BandDesc) * (size_t)n)) || (rc = c->band_parts.ensure(rec * (size_t)total)) ||
+        (rc = c->band_flags.ensure(sizeof(unsigned) * (size_t)total)) || (rc = c->band_out.ensure(sizeof(am_hit_band) * n_out)) ||
+        (rc = c->hit_io.ensure(std::max(sizeof(BandDesc) * (size_t)n, sizeof(am_hit_band) * n_out))))
+        return rc;
+    // (the copies go through pinned memory, as in score_hits)
+    std::memcpy(c->hit_io.p, hits.data(), sizeof(BandDesc) * (size_t)n);
+    AM_HIP(hipMemcpyAsync(c->band_tab.p, c->hit_io.p, sizeof(BandDesc) * (size_t)n, hipMemcpyHostToDevice, c->stream));
+    {
+        ProfScope ps(c, KN_OTHER, c->stream);
+        AM_HIP(launch_hit_bands(c->stream, static_cast<const BandDesc*>(c->band_tab.p), n, bp, max_groups,
+                                std::pow(10.0, -(double)AM_BAND_EMPTY_DB / 10.0), tab, static_cast<double*>(c->band_parts.p),
+                                static_cast<unsigned*>(c->band_flags.p), static_cast<am_hit_band*>(c->band_out.p)));
+    }
+    AM_HIP(hipMemcpyAsync(c->hit_io.p, c->band_out.p, sizeof(am_hit_band) * n_out, hipMemcpyDeviceToHost, c->stream));
+    AM_HIP(hipStreamSynchronize(c->stream));
+    const am_hit_band* res = static_cast<const am_hit_band*>(c->hit_io.p);
+    for (long long i = 0; i < n; ++i) std::memcpy(out[i], res + i * nb, sizeof(am_hit_band) * (size_t)nb);
+    return AM_OK;
+}
+
+}  // namespace
+
+}  // namespace am
+
+using namespace am;
+
+extern "C" {
+
+// ---- per-band hit scoring: the hit table of a call is built here, scored in one launch sequence ----
+int am_hit_bands_device(const am_needle* h, const void* d_haystack, size_t len, int sample_format,
+                        const am_peak* peaks, size_t n, const am_band_params* bp, am_hit_band* out) {
+    int rc = check_needle(h);
+    if (rc) return rc;
+    if ((rc = hit_check_format(sample_format))) return rc;
+    if (n == 0) return AM_OK;
+    if (!d_haystack || !peaks || !out || !bp) return fail(AM_ERR_INVALID_ARG, "null pointer");
+    if ((rc = band_check_params(bp)) || (rc = band_check_needle(bp, h->n, ""))) return rc;
+    Ctx* c = h->ctx;
+    std::lock_guard<std::recursive_mutex> lk(c->mu);
+    if ((rc = hit_check_device(d_haystack, c->device, HitWhere{-1, 0, 0, 0}))) return rc;
+    const double ratio = band_floor_ratio(h);
+    std::vector<BandDesc> hits(n);
+    std::vector<am_hit_band*> dst(n);
+    for (size_t i = 0; i < n; ++i) {
+        if ((rc = band_desc(h, d_haystack, len, sample_format, peaks[i], (int)bp->frame_log2, ratio, HitWhere{-1, 0, 0, i}, &hits[i]))) return rc;
+        dst[i] = out + i * bp->n_bands;
+    }
+    return score_bands(c, hits, *bp, dst.data());
+}
+
+int am_hit_bands(const am_needle* h, const void* haystack, size_t len, int sample_format,
+                 const am_peak* peaks, size_t n, const am_band_params* bp, am_hit_band* out) {
+    int rc = check_needle(h);
+    if (rc) return rc;
+    if ((rc = hit_check_format(sample_format))) return rc;
+    if (n == 0) return AM_OK;
+    if (!haystack || !peaks || !out || !bp) return fail(AM_ERR_INVALID_ARG, "null pointer");
+    if ((rc = band_check_params(bp)) || (rc = band_check_needle(bp, h->n, ""))) return rc;
+    Ctx* c = h->ctx;
+    std::lock_guard<std::recursive_mutex> lk(c->mu);
+    const double ratio = band_floor_ratio(h);
+    const size_t span = band_span(h->n, (int)bp->frame_log2);
+    std::vector<BandDesc> hits(n);
+    std::vector<am_hit_band*> dst(n);
+    for (size_t i = 0; i < n; ++i) {
+        if ((rc = band_desc(h, haystack, len, sample_format, peaks[i], (int)bp->frame_log2, ratio, HitWhere{-1, 0, 0, i}, &hits[i]))) return rc;
+        dst[i] = out + i * bp->n_bands;
+    }
+    // the spans [t, t + (J - 1) H + F) of the hits, merged where they overlap or touch, copied one after the other into
+    // the staging buffer; every hit's window pointer then points into its span's copy
+    std::vector<size_t> order(n);
+    for (size_t i = 0; i < n; ++i) order[i] = i;
+    std::sort(order.begin(), order.end(), [&](size_t a, size_t b) { return peaks[a].start < peaks[b].start; });
+    struct Span { size_t lo, hi, off; };
+    std::vector<Span> spans;
+    std::vector<size_t> span_of(n);
+    size_t staged = 0;
+    for (size_t i : order) {
+        const size_t lo = (size_t)peaks[i].start, hi = lo + span;
+        if (!spans.empty() && lo <= spans.back().hi) {
+            staged += std::max(hi, spans.back().hi) - spans.back().hi;
+            spans.back().hi = std::max(hi, spans.back().hi);
+        } else {
+            spans.push_back({lo, hi, staged});
+            staged += hi - lo;
+        }
+        span_of[i] = spans.size() - 1;
+    }
+    if ((rc = c->hit_stage.ensure(4 * staged))) return rc;   // (4 bytes per f32 sample and per i16 stereo frame)
+    for (const Span& sp_ : spans)
+        AM_HIP(hipMemcpyAsync(const_cast<void*>(advance_src(c->hit_stage.p, sp_.off)), advance_src(haystack, sp_.lo), 4 * (sp_.hi - sp_.lo),
+                              hipMemcpyHostToDevice, c->stream));
+    for (size_t i = 0; i < n; ++i) {
+        const Span& sp_ = spans[span_of[i]];
+        hits[i].win = advance_src(c->hit_stage.p, sp_.off + ((size_t)peaks[i].start - sp_.lo));
+    }
+    return score_bands(c, hits, *bp, dst.data());
+}
+
+int am_hit_bands_batch_device(const am_needle* const* needles, size_t n_needles,
+                              const void* const* d_haystacks, const size_t* lens, size_t n_hay, int sample_format,
+                              const am_peak* peaks, size_t cap_per_pair, const size_t* n_peaks,
+                              const am_band_params* bp, am_hit_band* out) {
+    int rc;
+    if ((rc = hit_check_format(sample_format))) return rc;
+    if (n_needles == 0 || n_hay == 0) return AM_OK;
+    if (!needles || !d_haystacks || !lens || !n_peaks) return fail(AM_ERR_INVALID_ARG, "null pointer");
+    size_t total = 0;
+    for (size_t q = 0; q < n_needles * n_hay; ++q) total += std::min(n_peaks[q], cap_per_pair);
+    if (total == 0) return AM_OK;
+    if (!peaks || !out || !bp) return fail(AM_ERR_INVALID_ARG, "null pointer");
+    for (size_t j = 0; j < n_needles; ++j)
+        if (!needles[j] || !needles[j]->ctx) return fail(AM_ERR_INVALID_ARG, "needle " + std::to_string(j) + ": null needle handle");
+    if ((rc = check_needle(needles[0]))) return rc;
+    Ctx* c = needles[0]->ctx;
+    for (size_t j = 1; j < n_needles; ++j)
+        if (needles[j]->ctx->device != c->device)
+            return fail(AM_ERR_INVALID_ARG, "needle " + std::to_string(j) + ": on device " + std::to_string(needles[j]->ctx->device) +
+                                                ", needle 0 on device " + std::to_string(c->device));
+    if ((rc = band_check_params(bp))) return rc;
+    for (size_t j = 0; j < n_needles; ++j)
+        if ((rc = band_check_needle(bp, needles[j]->n, "needle " + std::to_string(j) + ": "))) return rc;
+    std::lock_guard<std::recursive_mutex> lk(c->mu);
+    std::vector<double> ratio(n_needles);
+    for (size_t j = 0; j < n_needles; ++j) ratio[j] = band_floor_ratio(needles[j]);
+    std::vector<BandDesc> hits;
+    std::vector<am_hit_band*> dst;
+    hits.reserve(total);
+    dst.reserve(total);
+    for (size_t k = 0; k < n_hay; ++k) {
+        bool checked = false;
+        for (size_t j = 0; j < n_needles; ++j) {
+            const size_t pair = k * n_needles + j, np = std::min(n_peaks[pair], cap_per_pair);
+            if (np == 0) continue;
+            if (!checked) {   // (once per haystack; messages are spelled out only for a refusal)
+                const HitWhere w{(long long)pair, k, j, 0};
+                if (!d_haystacks[k]) return fail(AM_ERR_INVALID_ARG, hit_pair_name(w) + "null haystack");
+                if ((rc = hit_check_device(d_haystacks[k], c->device, w))) return rc;
+                checked = true;
+            }
+            for (size_t i = 0; i < np; ++i) {
+                BandDesc d{};
+                const size_t slot = pair * cap_per_pair + i;
+                if ((rc = band_desc(needles[j], d_haystacks[k], lens[k], sample_format, peaks[slot], (int)bp->frame_log2, ratio[j],
+                                    HitWhere{(long long)pair, k, j, i}, &d)))
+                    return rc;
+                hits.push_back(d);
+                dst.push_back(out + slot * bp->n_bands);
+            }
+        }
+    }
+    return score_bands(c, hits, *bp, dst.data());
+}
+
+int am_hit_bands_summary(const am_hit_band* rec, uint32_t n_bands, float min_coherence, am_band_summary* out) {
+    if (!rec || !out) return fail(AM_ERR_INVALID_ARG, "null pointer");
+    if (n_bands == 0 || n_bands > AM_BAND_MAX_BANDS) return fail(AM_ERR_INVALID_ARG, "n_bands = 0 or > AM_BAND_MAX_BANDS");
+    am_band_summary r{};
+    r.first_present = r.last_present = -1;
+    double all = 0.0, held = 0.0, coh = 0.0, gmin = 0.0, gmax = 0.0;
+    uint32_t n_gain = 0;
+    for (uint32_t b = 0; b < n_bands; ++b) {
+        const am_hit_band& q = rec[b];
+        if (q.flags & (AM_HIT_NONFINITE | AM_HIT_EMPTY_BAND)) continue;
+        ++r.n_countable;
+        all += (double)q.needle_share;
+        coh += (double)q.needle_share * (double)q.coherence;
+        if ((q.flags & AM_HIT_BELOW_FLOOR) || !(q.coherence >= min_coherence)) continue;
+        if (r.first_present < 0) r.first_present = (int32_t)b;
+        r.last_present = (int32_t)b;
+        ++r.n_present;
+        held += (double)q.needle_share;
+        if (q.gain > 0.0f) {
+            const double g = 20.0 * std::log10((double)q.gain);
+            gmin = n_gain ? std::min(gmin, g) : g;
+            gmax = n_gain ? std::max(gmax, g) : g;
+            ++n_gain;
+        }
+    }
+    r.coverage = held / all;              // (NaN without a countable band)
+    r.weighted_coherence = coh / all;
+    r.gain_db_spread = n_gain >= 2 ? gmax - gmin : std::nan("");
+    *out = r;
+    return AM_OK;
+}
+
+int am_band_edges_log(uint32_t sr, uint32_t frame_log2, double lo_hz, double hi_hz, uint32_t n_bands, am_band_params* out) {
+    if (!out) return fail(AM_ERR_INVALID_ARG, "null pointer");
+    if (sr == 0) return fail(AM_ERR_INVALID_ARG, "sr = 0");
+    if (frame_log2 < 8 || frame_log2 > 12) return fail(AM_ERR_INVALID_ARG, "frame_log2 " + std::to_string(frame_log2) + " outside 8 .. 12");
+    if (n_bands == 0 || n_bands > AM_BAND_MAX_BANDS) return fail(AM_ERR_INVALID_ARG, "n_bands = 0 or > AM_BAND_MAX_BANDS");
+    if (!(lo_hz > 0.0) || !(hi_hz > lo_hz) || !(hi_hz <= 0.5 * (double)sr))
+        return fail(AM_ERR_INVALID_ARG, "band edges: need 0 < lo_hz < hi_hz <= sr / 2");
+    const double f = (double)(1u << frame_log2);
+    am_band_params p{};
+    p.frame_log2 = frame_log2;
+    p.n_bands = n_bands;
+    long long prev = -1;
+    for (uint32_t b = 0; b <= n_bands; ++b) {
+        long long e = std::llround(lo_hz * std::pow(hi_hz / lo_hz, (double)b / (double)n_bands) * f / (double)sr);
+        e = std::max(e, prev + 1);
+        p.edges[b] = (uint32_t)e;
+        prev = e;
+    }
+    if (prev > (long long)(1u << frame_log2) / 2 + 1)
+        return fail(AM_ERR_INVALID_ARG, "band edges: " + std::to_string(n_bands) + " bands do not fit below F / 2 + 1");
+    *out = p;
+    return AM_OK;
+}
+
+}  // extern "C"

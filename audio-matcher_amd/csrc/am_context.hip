@@ -519,6 +519,9 @@ int am_shutdown(void) {
         for (DevBuf* b : {&c->best_stats, &c->best_lmax, &c->best_ctl, &c->best_trans, &c->best_list, &c->best_scores, &c->best_mono}) b->release();
         for (auto& kv : c->rs_taps) kv.second.release();
         c->rs_taps.clear();
+        for (DevBuf* b : {&c->band_tab, &c->band_parts, &c->band_flags, &c->band_out}) b->release();
+        for (auto& kv : c->band_tabs) kv.second.release();
+        c->band_tabs.clear();
         c->work_tail.release(); c->tail_scores.release(); c->tail_stats.release(); c->work_tail2.release();
         for (int set = 0; set < 2; ++set)
             for (int i = 0; i < kMaxNeedleGroup; ++i) { c->grp_scores[set][i].release(); c->grp_stats32[set][i].release(); c->grp_wflags[set][i].release(); }

@@ -155,6 +155,8 @@ struct Ctx {
     DevBuf hit_tab, hit_parts, hit_flags, hit_out, hit_stage;   // per-hit scoring (am_hits.hip): hit table, partials, results, staged spans
     HostBuf hit_io;                                              // ... and the pinned host side of the table and the results
     DevBuf seg_tab, seg_parts, seg_flags, seg_out;               // per-segment hit scoring (am_segments.hip); spans and pinned side: hit_stage, hit_io
+    DevBuf band_tab, band_parts, band_flags, band_out;           // per-band hit scoring (am_bands.hip); spans and pinned side: hit_stage, hit_io
+    std::map<int, DevBuf> band_tabs;                             // ... and the window and twiddle table of each frame_log2
     // per-hit significance (am_significance.hip): the spans and score zones of one group of hits, the table, the slice
     // partials, the per-hit state between the two passes and the results; pinned side: hit_io, host spans: hit_stage
     DevBuf sig_span, sig_scores, sig_tab, sig_psum, sig_pmax, sig_mean, sig_hmax, sig_out;

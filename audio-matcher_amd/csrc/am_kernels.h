@@ -336,6 +336,23 @@ struct SegDesc {
 hipError_t launch_hit_segments(hipStream_t st, const SegDesc* d_hits, long long n, int m, int r, int max_nsl, int kind,
                                double* parts, unsigned* pflags, am_hit_segment* d_out);
 
+// ---- am_bands.hip: per-band hit scoring (am_hit_bands*) ----
+constexpr int kBandGroup = 8;   // consecutive frames per workgroup of the frame kernel, counted from the hit's first frame
+inline int band_record_len(int n_bands) { return 4 * n_bands + 1; }   // doubles per partial record: (Re C, Im C, E_x, E_n) per band, E_n over every bin
+// One hit of a call, as the kernels read it (the call's table, uploaded once); F and the bands are the call's
+struct BandDesc {
+    const void* win;      // device: sample t of the haystack (f32 mono, or an i16 stereo frame for kind 1)
+    const float* needle;  // device: the whole needle
+    long long nframes;    // J: frame j reads samples [j F / 2, j F / 2 + F) of both
+    long long part0;      // first partial record of the hit: group g at part0 + g
+    double floor_ratio;   // 10^(-score_norm_floor_db / 10)
+    int kind;             // 0 = f32 mono, 1 = i16 stereo
+    int ngroups;          // ceil(J / kBandGroup)
+};
+// tab: the table of F (window, twiddles); parts: band_record_len(B) doubles per group, pflags: one word per group; d_out: n * B records
+hipError_t launch_hit_bands(hipStream_t st, const BandDesc* d_hits, long long n, const am_band_params& bp, int max_groups,
+                            double empty_ratio, const double* tab, double* parts, unsigned* pflags, am_hit_band* d_out);
+
 // ---- am_significance.hip: per-hit significance (am_hit_significance*) ----
 constexpr int kSigSlice = 4096;   // scores of a hit's zone per workgroup of the slice kernels, counted from the zone's start
 // One hit of a launch sequence, as the kernels read it.  The zone's scores r(lo .. hi) lie at scores[z0 .. z0 + nz).

@@ -77,6 +77,8 @@ struct Arguments {
     std::optional<float> min_confidence;      // extension: --min-confidence X, drop hits whose exact NCC is below X (am_hit_scores, 0..1)
     std::uint32_t segments = 0;               // extension: --segments M[:R], per-segment scoring of every printed hit (am_hit_segments), 0 = off
     std::uint32_t segment_radius = 4;         // ... the lags -R .. R examined per segment
+    std::uint32_t bands = 0;                  // extension: --bands B[:LOG2F], per-band scoring of every printed hit (am_hit_bands), 0 = off
+    std::uint32_t band_frame_log2 = 11;       // ... in frames of 2^LOG2F samples
     std::optional<float> min_significance;    // extension: --min-significance Z, drop hits whose z against the local background is below Z (am_hit_significance)
     std::optional<std::uint64_t> significance_zone_ms;   // ... --significance-zone D: the background reaches D each side of a hit (default: three snippet lengths)
     bool resample = false;                    // extension: --resample, bring the snippet to each main file's rate (am_needle_create_resampled)
@@ -124,6 +126,12 @@ inline const char* usage_text() {
            "                         holds ('#' present, '.' absent: the part's NCC against --min-confidence if given,\n"
            "                         else 0.5), the covered fraction, the drift in ppm and the refined start's lag;\n"
            "                         each part is matched within R samples (0..16, default 4); M in 1..1024\n"
+           "  --bands B[:LOG2F]      after each hit's offset line, print which of B log-spaced frequency bands of the\n"
+           "                         snippet (50 Hz up to 16 kHz or half the sample rate) the hit holds ('#' present,\n"
+           "                         '.' absent: the band's coherence against --min-confidence if given, else 0.5),\n"
+           "                         the share of the snippet's energy in the bands held, the share-weighted coherence\n"
+           "                         and the spread of the bands' gains in dB; spectra of 2^LOG2F samples (8..12,\n"
+           "                         default 11); B in 1..32.  Does not apply with --live\n"
            "  --min-significance Z   drop every hit that stands less than Z standard deviations above the scores around\n"
            "                         it (its z: the hit's score minus the mean of the background scores, over their\n"
            "                         standard deviation; the background is every offset within --significance-zone of\n"
@@ -224,6 +232,21 @@ inline Arguments parse_arguments(int argc, const char* const* argv) {
             a.segments = (std::uint32_t)m;
             a.segment_radius = (std::uint32_t)r;
         }
+        else if (s == "--bands") {
+            const std::string v = need(i);
+            const std::size_t colon = v.find(':');
+            const std::string vb = v.substr(0, colon), vf = colon == std::string::npos ? "11" : v.substr(colon + 1);
+            auto whole = [](const std::string& t, unsigned long& x) {
+                char* end = nullptr;
+                x = std::strtoul(t.c_str(), &end, 10);
+                return !t.empty() && t[0] >= '0' && t[0] <= '9' && *end == '\0';
+            };
+            unsigned long b = 0, lf = 0;
+            if (!whole(vb, b) || !whole(vf, lf) || b == 0 || b > 32 || lf < 8 || lf > 12)
+                throw ArgError("invalid value '" + v + "' for --bands (B[:LOG2F], B in 1..32 bands, LOG2F in 8..12)");
+            a.bands = (std::uint32_t)b;
+            a.band_frame_log2 = (std::uint32_t)lf;
+        }
         else if (s == "--resample") a.resample = true;
         else if (s == "--best") {
             const std::string v = need(i);
@@ -262,6 +285,7 @@ inline Arguments parse_arguments(int argc, const char* const* argv) {
         if (a.encoding == "f32le" && a.channels != 1) throw ArgError("--encoding f32le takes one channel only (--channels 1)");
         if (a.best || a.normalize || a.min_confidence) throw ArgError("--live: --best, --normalize and --min-confidence do not apply");
         if (a.segments) throw ArgError("--live: --segments does not apply");
+        if (a.bands) throw ArgError("--live: --bands does not apply");
         if (a.min_significance || a.significance_zone_ms) throw ArgError("--live: --min-significance and --significance-zone do not apply");
         return a;
     }

@@ -39,6 +39,36 @@ static std::string base_name(const std::string& path) {
     return slash == std::string::npos ? path : path.substr(slash + 1);
 }
 
+// extension: --bands B[:LOG2F].  One line per hit, to follow the hit's offset line (and its --segments line): the presence
+// mask of B log-spaced bands from 50 Hz to min(sr / 2, 16 kHz) ('#' present, '.' absent, at min_coherence =
+// --min-confidence if given, else 0.5), coverage, weighted coherence and gain spread (am_hit_bands + am_hit_bands_summary).
+static std::vector<std::string> band_lines(const Arguments& args, const am_needle* algo, const std::vector<float>& samples,
+                                           std::uint32_t sr, const am_peak* peaks, size_t n) {
+    std::vector<std::string> out;
+    if (n == 0) return out;
+    am_band_params bp{};
+    if (am_band_edges_log(sr, args.band_frame_log2, 50.0, std::min(0.5 * (double)sr, 16000.0), args.bands, &bp) != AM_OK)
+        throw std::runtime_error(std::string("--bands: ") + am_last_error_string());
+    const float min_coh = args.min_confidence.value_or(0.5f);
+    std::vector<am_hit_band> rec(n * bp.n_bands);
+    if (am_hit_bands(algo, samples.data(), samples.size(), AM_FMT_F32_MONO, peaks, n, &bp, rec.data()) != AM_OK)
+        throw std::runtime_error(std::string("am_hit_bands: ") + am_last_error_string());
+    const unsigned absent = AM_HIT_NONFINITE | AM_HIT_BELOW_FLOOR | AM_HIT_EMPTY_BAND;
+    for (size_t i = 0; i < n; ++i) {
+        const am_hit_band* q = rec.data() + i * bp.n_bands;
+        am_band_summary sm{};
+        if (am_hit_bands_summary(q, bp.n_bands, min_coh, &sm) != AM_OK)
+            throw std::runtime_error(std::string("am_hit_bands_summary: ") + am_last_error_string());
+        std::string mask(bp.n_bands, '.');
+        for (std::uint32_t b = 0; b < bp.n_bands; ++b)
+            if (!(q[b].flags & absent) && q[b].coherence >= min_coh) mask[b] = '#';
+        char tail[128];
+        std::snprintf(tail, sizeof tail, " coverage %.3f coherence %.3f gain_db_spread %.1f", sm.coverage, sm.weighted_coherence, sm.gain_db_spread);
+        out.push_back("  bands " + mask + tail);
+    }
+    return out;
+}
+
 // extension: --segments M[:R].  One line per hit, to follow the hit's offset line: the presence mask of the snippet's M
 // parts ('#' present, '.' absent, at min_ncc = --min-confidence if given, else 0.5), coverage, drift and start lag
 // (am_hit_segments + am_hit_segments_summary).
@@ -235,9 +265,12 @@ static int run_multi(const Arguments& args) {
                     const std::vector<std::string> lines = offset_lines(pk, n[j], m_sr);
                     const std::vector<std::string> segs =
                         args.segments ? segment_lines(args, handles[j], m_samples, pk, n[j]) : std::vector<std::string>();
+                    const std::vector<std::string> bands =
+                        args.bands ? band_lines(args, handles[j], m_samples, m_sr, pk, n[j]) : std::vector<std::string>();
                     for (size_t i = 0; i < lines.size(); ++i) {
                         std::printf("%s: %s\n", snips[j].name.c_str(), lines[i].c_str());
                         if (i < segs.size()) std::printf("%s: %s\n", snips[j].name.c_str(), segs[i].c_str());
+                        if (i < bands.size()) std::printf("%s: %s\n", snips[j].name.c_str(), bands[i].c_str());
                     }
                 }
             }
@@ -501,9 +534,12 @@ int main(int argc, char** argv) {
                 const std::vector<std::string> lines = offset_lines(peaks.data(), n, m_sr);                       // mod.rs:89
                 const std::vector<std::string> segs =
                     args.segments ? segment_lines(args, algo, m_samples, peaks.data(), n) : std::vector<std::string>();   // extension: --segments
+                const std::vector<std::string> bands =
+                    args.bands ? band_lines(args, algo, m_samples, m_sr, peaks.data(), n) : std::vector<std::string>();   // extension: --bands
                 for (size_t i = 0; i < lines.size(); ++i) {
                     std::printf("%s\n", lines[i].c_str());
                     if (i < segs.size()) std::printf("%s\n", segs[i].c_str());
+                    if (i < bands.size()) std::printf("%s\n", bands[i].c_str());
                 }
             }
             if (out_path) {                                                   // mod.rs:92-99

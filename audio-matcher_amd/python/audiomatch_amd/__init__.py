@@ -83,6 +83,33 @@ AM_HIT_EMPTY_SEGMENT = 8
 AM_SEG_MAX_SEGMENTS, AM_SEG_MAX_RADIUS = 1024, 16
 
 
+class AmBandParams(C.Structure):      # am_band_params (include/audiomatch.h, per-band hit scoring)
+    _fields_ = [("frame_log2", C.c_uint32), ("n_bands", C.c_uint32), ("edges", C.c_uint32 * 33)]
+
+
+class HitBand(C.Structure):           # am_hit_band: one band of one hit
+    _fields_ = [("ncc", C.c_float), ("coherence", C.c_float), ("gain", C.c_float), ("level_db", C.c_float),
+                ("needle_share", C.c_float), ("flags", C.c_uint32)]
+
+    def __repr__(self):
+        return (f"HitBand(ncc={self.ncc!r}, coherence={self.coherence!r}, gain={self.gain!r}, level_db={self.level_db!r}, "
+                f"needle_share={self.needle_share!r}, flags={self.flags})")
+
+    def pack(self) -> bytes:
+        """The record's 24 bytes (for bit-for-bit comparisons)."""
+        return bytes(self)
+
+
+class AmBandSummary(C.Structure):     # am_band_summary
+    _fields_ = [("coverage", C.c_double), ("weighted_coherence", C.c_double), ("gain_db_spread", C.c_double),
+                ("first_present", C.c_int32), ("last_present", C.c_int32), ("n_present", C.c_uint32),
+                ("n_countable", C.c_uint32)]
+
+
+AM_HIT_EMPTY_BAND = 128
+AM_BAND_MAX_BANDS, AM_BAND_EMPTY_DB = 32, 90
+
+
 class AmSignificanceParams(C.Structure):   # am_significance_params (include/audiomatch.h, per-hit significance)
     _fields_ = [("guard", C.c_uint64), ("radius", C.c_uint64)]
 
@@ -261,6 +288,15 @@ _SIGNATURES = {
                                                C.POINTER(AmSegmentParams), C.POINTER(HitSegment)]),
     "am_hit_segments_summary": (C.c_int, [C.POINTER(HitSegment), C.c_uint32, C.c_size_t, C.c_float,
                                           C.POINTER(AmSegmentSummary)]),
+    "am_hit_bands_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.POINTER(AmPeak), C.c_size_t,
+                                      C.POINTER(AmBandParams), C.POINTER(HitBand)]),
+    "am_hit_bands": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.POINTER(AmPeak), C.c_size_t,
+                               C.POINTER(AmBandParams), C.POINTER(HitBand)]),
+    "am_hit_bands_batch_device": (C.c_int, [C.POINTER(C.c_void_p), C.c_size_t, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t),
+                                            C.c_size_t, C.c_int, C.POINTER(AmPeak), C.c_size_t, C.POINTER(C.c_size_t),
+                                            C.POINTER(AmBandParams), C.POINTER(HitBand)]),
+    "am_hit_bands_summary": (C.c_int, [C.POINTER(HitBand), C.c_uint32, C.c_float, C.POINTER(AmBandSummary)]),
+    "am_band_edges_log": (C.c_int, [C.c_uint32, C.c_uint32, C.c_double, C.c_double, C.c_uint32, C.POINTER(AmBandParams)]),
     "am_hit_significance_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.POINTER(AmPeak), C.c_size_t,
                                              C.POINTER(AmSignificanceParams), C.POINTER(HitSignificance)]),
     "am_hit_significance": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.POINTER(AmPeak), C.c_size_t,
@@ -568,6 +604,49 @@ def hit_segments_summary(segments, needle_len: int, min_ncc: float = 0.5) -> Seg
                           out.last_present, out.n_present, out.n_usable)
 
 
+def band_params(frame_log2: int, edges) -> AmBandParams:
+    """am_band_params for F = 2^frame_log2 and the bands [edges[b], edges[b + 1]) (bin indices)."""
+    edges = [int(e) for e in edges]
+    bp = AmBandParams(int(frame_log2), max(len(edges) - 1, 0))
+    for b, e in enumerate(edges[:AM_BAND_MAX_BANDS + 1]):
+        bp.edges[b] = e
+    return bp
+
+
+def band_edges_log(sr: int, frame_log2: int, lo_hz: float, hi_hz: float, n_bands: int) -> AmBandParams:
+    """am_band_edges_log (pure host code): n_bands log-spaced bands from lo_hz to hi_hz at sample rate sr."""
+    out = AmBandParams()
+    _check(lib().am_band_edges_log(int(sr), int(frame_log2), float(lo_hz), float(hi_hz), int(n_bands), C.byref(out)))
+    return out
+
+
+def _hit_bands(buf, first, nb):
+    """The nb records of one hit as a list of HitBand (copies: they outlive the call's buffer)."""
+    return [HitBand.from_buffer_copy(buf[first + b]) for b in range(nb)]
+
+
+@dataclass
+class BandSummary:
+    """am_band_summary: how much of the needle's spectrum one hit holds, from its band records."""
+    coverage: float
+    weighted_coherence: float
+    gain_db_spread: float
+    first_present: int
+    last_present: int
+    n_present: int
+    n_countable: int
+
+
+def hit_bands_summary(bands, min_coherence: float = 0.5) -> BandSummary:
+    """am_hit_bands_summary (pure host code): `bands` = one hit's HitBand records."""
+    nb = len(bands)
+    buf = (HitBand * max(1, nb))(*[HitBand(q.ncc, q.coherence, q.gain, q.level_db, q.needle_share, q.flags) for q in bands])
+    out = AmBandSummary()
+    _check(lib().am_hit_bands_summary(buf, nb, float(min_coherence), C.byref(out)))
+    return BandSummary(out.coverage, out.weighted_coherence, out.gain_db_spread, out.first_present, out.last_present,
+                       out.n_present, out.n_countable)
+
+
 # ---------------------------------------------------------------------------
 @dataclass
 class Peak:
@@ -825,6 +904,29 @@ class HipConvolve:
         sp = AmSegmentParams(m, int(radius))
         _check(lib().am_hit_segments_device(self._h, ptr, length, int(fmt), _peak_array(peaks), k, C.byref(sp), out))
         return [_hit_segments(out, i * m, m) for i in range(k)]
+
+    # -- per-band hit scoring --
+    def hit_bands(self, haystack, peaks, bp: AmBandParams):
+        """am_hit_bands: for each of `peaks` of a host haystack (as in hit_scores) the list of its bp.n_bands HitBand
+        records (bp: band_params or band_edges_log)."""
+        a = np.asarray(haystack)
+        if a.dtype == np.int16:
+            a = np.ascontiguousarray(a)
+            fmt, length = Fmt.S16_STEREO, a.size // 2
+        else:
+            a = np.ascontiguousarray(a, dtype=np.float32)
+            fmt, length = Fmt.F32_MONO, a.size
+        k, nb = len(peaks), int(bp.n_bands)
+        out = (HitBand * max(1, k * nb))()
+        _check(lib().am_hit_bands(self._h, a.ctypes.data, length, int(fmt), _peak_array(peaks), k, C.byref(bp), out))
+        return [_hit_bands(out, i * nb, nb) for i in range(k)]
+
+    def hit_bands_device(self, ptr: int, length: int, peaks, bp: AmBandParams, fmt: int = Fmt.F32_MONO):
+        """am_hit_bands_device: the same for a haystack resident on this needle's device."""
+        k, nb = len(peaks), int(bp.n_bands)
+        out = (HitBand * max(1, k * nb))()
+        _check(lib().am_hit_bands_device(self._h, ptr, length, int(fmt), _peak_array(peaks), k, C.byref(bp), out))
+        return [_hit_bands(out, i * nb, nb) for i in range(k)]
 
     # -- per-hit significance --
     def hit_significance(self, haystack, peaks, guard: int, radius: int):
@@ -1210,6 +1312,28 @@ def hit_segments_batch_device(algos, ptrs, lengths, peaks_per_pair, segments: in
     sp = AmSegmentParams(m, int(radius))
     _check(lib().am_hit_segments_batch_device(handles, nn, arr_p, arr_l, k, int(fmt), buf, cap, counts, C.byref(sp), out))
     return [[[_hit_segments(out, ((h * nn + j) * cap + i) * m, m) for i in range(counts[h * nn + j])] for j in range(nn)]
+            for h in range(k)]
+
+
+def hit_bands_batch_device(algos, ptrs, lengths, peaks_per_pair, bp: AmBandParams, fmt: int = Fmt.F32_MONO):
+    """am_hit_bands_batch_device: peaks_per_pair[k][j] as in hit_scores_batch_device; result [k][j][i] = the bp.n_bands
+    HitBand records of hit i of haystack k against needle j."""
+    nn, k, nb = len(algos), len(ptrs), int(bp.n_bands)
+    cap = max([1] + [len(peaks_per_pair[h][j]) for h in range(k) for j in range(nn)])
+    handles = (C.c_void_p * max(1, nn))(*[a._h for a in algos])
+    arr_p = (C.c_void_p * max(1, k))(*ptrs)
+    arr_l = (C.c_size_t * max(1, k))(*lengths)
+    buf = (AmPeak * max(1, cap * k * nn))()
+    counts = (C.c_size_t * max(1, k * nn))()
+    for h in range(k):
+        for j in range(nn):
+            q = h * nn + j
+            counts[q] = len(peaks_per_pair[h][j])
+            for i, p in enumerate(peaks_per_pair[h][j]):
+                buf[q * cap + i] = AmPeak(int(p.start), int(p.end), float(p.height), float(p.prominence))
+    out = (HitBand * max(1, cap * k * nn * nb))()
+    _check(lib().am_hit_bands_batch_device(handles, nn, arr_p, arr_l, k, int(fmt), buf, cap, counts, C.byref(bp), out))
+    return [[[_hit_bands(out, ((h * nn + j) * cap + i) * nb, nb) for i in range(counts[h * nn + j])] for j in range(nn)]
             for h in range(k)]
 
 

@@ -60,6 +60,43 @@ pub struct AmHitSegment {
     pub level_db: f32,
     pub flags: u32,
 }
+/// am_band_params: per-band hit scoring (am_hit_bands*)
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct AmBandParams {
+    pub frame_log2: u32,
+    pub n_bands: u32,
+    pub edges: [u32; AM_BAND_MAX_BANDS + 1],
+}
+impl Default for AmBandParams {
+    fn default() -> Self { AmBandParams { frame_log2: 0, n_bands: 0, edges: [0; AM_BAND_MAX_BANDS + 1] } }
+}
+/// am_hit_band: one band of one hit (24 bytes)
+#[repr(C)]
+#[derive(Clone, Copy, Default, Debug)]
+pub struct AmHitBand {
+    pub ncc: f32,
+    pub coherence: f32,
+    pub gain: f32,
+    pub level_db: f32,
+    pub needle_share: f32,
+    pub flags: u32,
+}
+/// am_band_summary: how much of the needle's spectrum one hit holds
+#[repr(C)]
+#[derive(Clone, Copy, Default, Debug)]
+pub struct AmBandSummary {
+    pub coverage: f64,
+    pub weighted_coherence: f64,
+    pub gain_db_spread: f64,
+    pub first_present: i32,
+    pub last_present: i32,
+    pub n_present: u32,
+    pub n_countable: u32,
+}
+pub const AM_HIT_EMPTY_BAND: u32 = 128;
+pub const AM_BAND_MAX_BANDS: usize = 32;
+pub const AM_BAND_EMPTY_DB: u32 = 90;
 /// am_significance_params: per-hit significance (am_hit_significance*)
 #[repr(C)]
 #[derive(Clone, Copy, Default, Debug)]
@@ -239,6 +276,22 @@ extern "C" {
     pub fn am_hit_segments_summary(
         seg: *const AmHitSegment, segments: u32, needle_len: usize, min_ncc: f32, out: *mut AmSegmentSummary,
     ) -> c_int;
+    /// per-band hit scoring: which frequencies of the needle a hit holds (audiomatch.h)
+    pub fn am_hit_bands(
+        h: *const AmNeedle, haystack: *const std::ffi::c_void, len: usize, sample_format: c_int, peaks: *const AmPeak, n: usize,
+        bp: *const AmBandParams, out: *mut AmHitBand,
+    ) -> c_int;
+    pub fn am_hit_bands_device(
+        h: *const AmNeedle, d_haystack: *const std::ffi::c_void, len: usize, sample_format: c_int, peaks: *const AmPeak, n: usize,
+        bp: *const AmBandParams, out: *mut AmHitBand,
+    ) -> c_int;
+    pub fn am_hit_bands_batch_device(
+        needles: *const *const AmNeedle, n_needles: usize, d_haystacks: *const *const std::ffi::c_void, lens: *const usize,
+        n_hay: usize, sample_format: c_int, peaks: *const AmPeak, cap_per_pair: usize, n_peaks: *const usize,
+        bp: *const AmBandParams, out: *mut AmHitBand,
+    ) -> c_int;
+    pub fn am_hit_bands_summary(rec: *const AmHitBand, n_bands: u32, min_coherence: f32, out: *mut AmBandSummary) -> c_int;
+    pub fn am_band_edges_log(sr: u32, frame_log2: u32, lo_hz: f64, hi_hz: f64, n_bands: u32, out: *mut AmBandParams) -> c_int;
     /// per-hit significance: each hit's score against its local background (audiomatch.h)
     pub fn am_hit_significance(
         h: *const AmNeedle, haystack: *const std::ffi::c_void, len: usize, sample_format: c_int, peaks: *const AmPeak, n: usize,
@@ -349,6 +402,26 @@ pub struct HipConvolve {
 }
 unsafe impl Send for HipConvolve {}
 unsafe impl Sync for HipConvolve {}
+
+/// How much of the needle's spectrum one hit holds, from its band records (am_hit_bands_summary; no device needed).
+pub fn band_summary(rec: &[AmHitBand], min_coherence: f32) -> Result<AmBandSummary, Box<dyn std::error::Error>> {
+    let mut out = AmBandSummary::default();
+    let rc = unsafe { am_hit_bands_summary(rec.as_ptr(), rec.len() as u32, min_coherence, &mut out) };
+    if rc != AM_OK {
+        return Err(am_err(rc));
+    }
+    Ok(out)
+}
+
+/// `n_bands` log-spaced bands from `lo_hz` to `hi_hz` for frames of 2^`frame_log2` samples (am_band_edges_log; no device needed).
+pub fn band_edges_log(sr: u32, frame_log2: u32, lo_hz: f64, hi_hz: f64, n_bands: u32) -> Result<AmBandParams, Box<dyn std::error::Error>> {
+    let mut out = AmBandParams::default();
+    let rc = unsafe { am_band_edges_log(sr, frame_log2, lo_hz, hi_hz, n_bands, &mut out) };
+    if rc != AM_OK {
+        return Err(am_err(rc));
+    }
+    Ok(out)
+}
 
 /// Coverage, drift and refined start of one hit from its segment records (am_hit_segments_summary; no device needed).
 pub fn segment_summary(seg: &[AmHitSegment], needle_len: usize, min_ncc: f32) -> Result<AmSegmentSummary, Box<dyn std::error::Error>> {
@@ -478,6 +551,20 @@ impl HipConvolve {
         let rc = unsafe {
             am_hit_segments(self.h, m_samples.as_ptr() as *const std::ffi::c_void, m_samples.len(), AM_FMT_F32_MONO, peaks.as_ptr(),
                             peaks.len(), &sp, out.as_mut_ptr())
+        };
+        if rc != AM_OK {
+            return Err(am_err(rc));
+        }
+        Ok(out)
+    }
+
+    /// Per-band hit scoring (am_hit_bands) of `peaks` found in the host haystack `m_samples`: `bp.n_bands` records per
+    /// peak (peak i, band b at i * n_bands + b).
+    pub fn hit_bands(&self, m_samples: &[f32], peaks: &[AmPeak], bp: &AmBandParams) -> Result<Vec<AmHitBand>, Box<dyn std::error::Error>> {
+        let mut out = vec![AmHitBand::default(); peaks.len() * bp.n_bands as usize];
+        let rc = unsafe {
+            am_hit_bands(self.h, m_samples.as_ptr() as *const std::ffi::c_void, m_samples.len(), AM_FMT_F32_MONO, peaks.as_ptr(),
+                         peaks.len(), bp, out.as_mut_ptr())
         };
         if rc != AM_OK {
             return Err(am_err(rc));

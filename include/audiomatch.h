@@ -318,6 +318,86 @@ typedef struct am_segment_summary {
 int am_hit_segments_summary(const am_hit_segment* seg, uint32_t segments, size_t needle_len, float min_ncc,
                             am_segment_summary* out);
 
+/* ---- per-band hit scoring --------------------------------------------------------- */
+/* Which frequencies of the needle a hit holds: the pass of am_hit_scores resolved along frequency (the reference reports
+ * one offset and one height per hit, matcher/mod.rs:110-125).  A copy from a low-rate MP3, a telephone insert or a
+ * transfer with a tilted EQ matches in some bands and not in others; one broadband NCC mixes that into one number.
+ * With t = peak.start, the needle n[0 .. S) (the handle's whole needle, partitioned handles included) and x the
+ * haystack's samples (f32 mono, or the bit-exact down-mix for AM_FMT_S16_STEREO as above), everything in f64:
+ *   frames     F = 2^frame_log2 samples at hop H = F / 2, J = floor((S - F) / H) + 1 of them; frame j reads
+ *              x[t + jH .. t + jH + F) and n[jH .. jH + F).  The fewer than H needle samples behind the last frame are
+ *              not read, nor the haystack samples under them.  Window w[i] = 0.5 - 0.5 cos(2 pi i / F).
+ *   spectra    X_j[k] = sum_i w[i] x[t + jH + i] e^(-2 pi i ik / F), N_j[k] likewise from the needle, k = 0 .. F / 2.
+ *   sums       P_xn[k] = sum_j X_j[k] conj(N_j[k]),   P_xx[k] = sum_j |X_j[k]|^2,   P_nn[k] = sum_j |N_j[k]|^2
+ *   bands      band b = the bins [edges[b], edges[b + 1]):  C_b = sum_k P_xn[k],  E_x,b = sum_k P_xx[k],
+ *              E_n,b = sum_k P_nn[k];  E_n = sum_{k = 0 .. F/2} P_nn[k] over every bin, in a band or not.
+ *   ncc          Re C_b / sqrt(E_x,b E_n,b): the band's NCC at lag 0, in [-1, 1].
+ *   coherence    |C_b| / sqrt(E_x,b E_n,b) in [0, 1]: survives a misalignment of a few samples, where ncc falls.
+ *   gain         Re C_b / E_n,b: the least-squares gain of the needle in this band (over the bands: the copy's EQ curve).
+ *   level_db     10 log10(E_x,b / E_n,b); -inf for a silent band.
+ *   needle_share E_n,b / E_n: how much of the needle lives in this band (0 for a needle of zeros).
+ *   flags      AM_HIT_*.  AM_HIT_NONFINITE: a sample the hit reads, x[t .. t + (J - 1) H + F) or n[0 .. (J - 1) H + F), is
+ *              not finite; every band of the hit then has the five floats NaN and no other flag.
+ *              AM_HIT_EMPTY_BAND: needle_share < 10^(-AM_BAND_EMPTY_DB / 10) -- a computed spectrum is never exactly 0,
+ *              hence a fixed relative bound; ncc = coherence = gain = 0, level_db = +inf for E_x,b > 0 and NaN
+ *              otherwise, no other flag.
+ *              AM_HIT_BELOW_FLOOR: E_x,b = 0 or E_x,b < E_n,b 10^(-score_norm_floor_db / 10) -- the process option
+ *              am_hit_scores reads at call time, applied per band; ncc = coherence = 0, gain and level_db are given.
+ * A hit's records depend on the needle, the samples it reads, the parameters and the floor only: the three forms below
+ * agree bit for bit, whatever else the call holds.  The cost is proportional to hits x J transforms of F points, not to
+ * the haystack: 15 us per hit for a 10 s needle at 44.1 kHz with F = 1024 and 16 bands, 14 us with F = 4096 (64 hits in one
+ * call), beside 2.0 us for am_hit_segments with m = 8, R = 4 on the same hits (tools/hit_bands_bench.py, profiles/r14/).
+ * out holds B = n_bands records per hit, hit i band b at out[i B + b]; in the batch form hit slot q of pair p is at
+ * (p cap_per_pair + q) B -- the layout of am_hit_scores_batch_device times B; other slots stay untouched.
+ * AM_ERR_INVALID_ARG, naming the hit (and pair): a null pointer with n > 0, bp == NULL, frame_log2 outside 8 .. 12,
+ * n_bands == 0 or > AM_BAND_MAX_BANDS, edges not strictly ascending or edges[B] > F / 2 + 1, S < F, an unknown sample
+ * format, peak.start + S > len, a haystack on another device than the needle.  n = 0: AM_OK, nothing launched. */
+enum { AM_HIT_EMPTY_BAND = 128 };
+#define AM_BAND_MAX_BANDS 32
+#define AM_BAND_EMPTY_DB  90
+typedef struct am_band_params {
+    uint32_t frame_log2;                    /* 8 .. 12 */
+    uint32_t n_bands;                       /* B, 1 .. AM_BAND_MAX_BANDS */
+    uint32_t edges[AM_BAND_MAX_BANDS + 1];  /* B + 1 bin indices, strictly ascending, edges[B] <= F / 2 + 1 */
+} am_band_params;
+typedef struct am_hit_band {
+    float ncc;          /* Re C_b / sqrt(E_x,b E_n,b): the band's NCC at lag 0, in [-1, 1] */
+    float coherence;    /* |C_b| / sqrt(E_x,b E_n,b), in [0, 1]: survives a few samples of misalignment */
+    float gain;         /* Re C_b / E_n,b: least-squares gain of the needle in this band (the copy's EQ curve) */
+    float level_db;     /* 10 log10(E_x,b / E_n,b); -inf for a silent band */
+    float needle_share; /* E_n,b / E_n: how much of the needle lives in this band */
+    uint32_t flags;     /* AM_HIT_* */
+} am_hit_band;          /* 24 bytes, no padding */
+/* the haystack resident on the needle's device */
+int am_hit_bands_device(const am_needle* h, const void* d_haystack, size_t len, int sample_format,
+                        const am_peak* peaks, size_t n, const am_band_params* bp, am_hit_band* out);
+/* the haystack in host memory: only the spans [t, t + (J - 1) H + F) of the hits are copied (merged where they overlap) */
+int am_hit_bands(const am_needle* h, const void* haystack, size_t len, int sample_format,
+                 const am_peak* peaks, size_t n, const am_band_params* bp, am_hit_band* out);
+/* the pair layout of am_hit_scores_batch_device; every hit of the call in one launch sequence, needles of any lengths
+ * (each at least F).  Pool results: score each slot's hits with that slot's needle (am_pool_slot). */
+int am_hit_bands_batch_device(const am_needle* const* needles, size_t n_needles,
+                              const void* const* d_haystacks, const size_t* lens, size_t n_hay, int sample_format,
+                              const am_peak* peaks, size_t cap_per_pair, const size_t* n_peaks,
+                              const am_band_params* bp, am_hit_band* out);
+/* What callers want from one hit's B records (pure host code, no device): a band is COUNTABLE when its flags hold neither
+ * NONFINITE nor EMPTY_BAND, PRESENT when countable, not BELOW_FLOOR and coherence >= min_coherence.  Sums run in f64, in
+ * index order; coverage and weighted_coherence are NaN without a countable band.
+ * AM_ERR_INVALID_ARG: a null pointer, n_bands == 0 or > AM_BAND_MAX_BANDS. */
+typedef struct am_band_summary {
+    double coverage;             /* sum of needle_share over present bands / sum over countable bands */
+    double weighted_coherence;   /* sum of needle_share * coherence / sum of needle_share, over countable bands */
+    double gain_db_spread;       /* max - min of 20 log10(gain) over present bands with gain > 0; NaN with fewer than 2 */
+    int32_t first_present, last_present;   /* band indices, -1 when none */
+    uint32_t n_present, n_countable;
+} am_band_summary;
+int am_hit_bands_summary(const am_hit_band* rec, uint32_t n_bands, float min_coherence, am_band_summary* out);
+/* B log-spaced bands from lo_hz to hi_hz at sample rate sr (pure host code): edges[b] = llround(lo (hi / lo)^(b / B) F / sr),
+ * b = 0 .. B, each then raised to at least its predecessor + 1; the rest of *out is zeroed.
+ * AM_ERR_INVALID_ARG: out == NULL, sr == 0, frame_log2 outside 8 .. 12, n_bands == 0 or > AM_BAND_MAX_BANDS, lo_hz <= 0,
+ * hi_hz <= lo_hz, hi_hz > sr / 2, or edges that do not fit below F / 2 + 1. */
+int am_band_edges_log(uint32_t sr, uint32_t frame_log2, double lo_hz, double hi_hz, uint32_t n_bands, am_band_params* out);
+
 /* ---- per-hit significance --------------------------------------------------------- */
 /* How far a hit stands out from the scores around it: the peak-to-sidelobe measure of matched filtering.  NCC
  * (am_hit_scores) says how well the window matches the needle; it cannot tell a certain hit under a loud voice-over

@@ -154,6 +154,19 @@ public:
         check(am_hit_segments_device(h_, d_haystack, len, sample_format, peaks.data(), peaks.size(), &sp, out.data()));
         return out;
     }
+    // per-band hit scoring (am_hit_bands): bp.n_bands records per peak, peak i band b at i * n_bands + b
+    std::vector<am_hit_band> hit_bands(const void* haystack, std::size_t len, int sample_format, const std::vector<am_peak>& peaks,
+                                       const am_band_params& bp) const {
+        std::vector<am_hit_band> out(peaks.size() * bp.n_bands);
+        check(am_hit_bands(h_, haystack, len, sample_format, peaks.data(), peaks.size(), &bp, out.data()));
+        return out;
+    }
+    std::vector<am_hit_band> hit_bands_device(const void* d_haystack, std::size_t len, int sample_format,
+                                              const std::vector<am_peak>& peaks, const am_band_params& bp) const {
+        std::vector<am_hit_band> out(peaks.size() * bp.n_bands);
+        check(am_hit_bands_device(h_, d_haystack, len, sample_format, peaks.data(), peaks.size(), &bp, out.data()));
+        return out;
+    }
     // per-hit significance (am_hit_significance): each peak's score against the scores at lags guard < |lag| <= radius
     // around it (mean, standard deviation, z and the largest background score), one record per peak
     std::vector<am_significance> hit_significance(const void* haystack, std::size_t len, int sample_format, const std::vector<am_peak>& peaks,
@@ -172,6 +185,18 @@ public:
     static am_segment_summary segment_summary(const am_hit_segment* seg, std::uint32_t segments, std::size_t needle_len, float min_ncc) {
         am_segment_summary out{};
         check(am_hit_segments_summary(seg, segments, needle_len, min_ncc, &out));
+        return out;
+    }
+    // how much of the needle's spectrum one hit holds, from its band records (am_hit_bands_summary; no device needed)
+    static am_band_summary band_summary(const am_hit_band* rec, std::uint32_t n_bands, float min_coherence) {
+        am_band_summary out{};
+        check(am_hit_bands_summary(rec, n_bands, min_coherence, &out));
+        return out;
+    }
+    // n_bands log-spaced bands from lo_hz to hi_hz for frames of 2^frame_log2 samples (am_band_edges_log; no device needed)
+    static am_band_params band_edges_log(std::uint32_t sr, std::uint32_t frame_log2, double lo_hz, double hi_hz, std::uint32_t n_bands) {
+        am_band_params out{};
+        check(am_band_edges_log(sr, frame_log2, lo_hz, hi_hz, n_bands, &out));
         return out;
     }
     // the k best matches (am_match_best): the best min(k, count) peaks of the haystack's Valid scores by descending
