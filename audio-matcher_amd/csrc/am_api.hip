@@ -295,125 +295,6 @@ int am_match_pcm16_batch_device(const am_needle* hc, const int16_t* const* d_int
 }
 
 
-// ---- per-hit scoring (am_hits.hip): the hit table of a call is built here, scored in one launch sequence ----
-int am_hit_scores_device(const am_needle* h, const void* d_haystack, size_t len, int sample_format,
-                         const am_peak* peaks, size_t n, am_hit_score* out) {
-    int rc = check_needle(h);
-    if (rc) return rc;
-    if ((rc = hit_check_format(sample_format))) return rc;
-    if (n == 0) return AM_OK;
-    if (!d_haystack || !peaks || !out) return fail(AM_ERR_INVALID_ARG, "null pointer");
-    Ctx* c = h->ctx;
-    std::lock_guard<std::recursive_mutex> lk(c->mu);
-    if ((rc = hit_check_device(d_haystack, c->device, HitWhere{-1, 0, 0, 0}))) return rc;
-    const double thr = hit_floor(h);
-    std::vector<HitDesc> hits(n);
-    std::vector<am_hit_score*> dst(n);
-    for (size_t i = 0; i < n; ++i) {
-        if ((rc = hit_desc(h, d_haystack, len, sample_format, peaks[i], thr, HitWhere{-1, 0, 0, i}, &hits[i]))) return rc;
-        dst[i] = out + i;
-    }
-    return score_hits(c, hits, dst.data());
-}
-
-int am_hit_scores(const am_needle* h, const void* haystack, size_t len, int sample_format,
-                  const am_peak* peaks, size_t n, am_hit_score* out) {
-    int rc = check_needle(h);
-    if (rc) return rc;
-    if ((rc = hit_check_format(sample_format))) return rc;
-    if (n == 0) return AM_OK;
-    if (!haystack || !peaks || !out) return fail(AM_ERR_INVALID_ARG, "null pointer");
-    Ctx* c = h->ctx;
-    std::lock_guard<std::recursive_mutex> lk(c->mu);
-    const double thr = hit_floor(h);
-    std::vector<HitDesc> hits(n);
-    std::vector<am_hit_score*> dst(n);
-    for (size_t i = 0; i < n; ++i) {
-        if ((rc = hit_desc(h, haystack, len, sample_format, peaks[i], thr, HitWhere{-1, 0, 0, i}, &hits[i]))) return rc;
-        dst[i] = out + i;
-    }
-    // the spans [t - 1, t + S + 1) of the hits, clipped to the haystack and merged where they overlap or touch, copied
-    // one after the other into the staging buffer; every hit's window pointer then points into its span's copy
-    const size_t s = h->n;
-    std::vector<size_t> order(n);
-    for (size_t i = 0; i < n; ++i) order[i] = i;
-    std::sort(order.begin(), order.end(), [&](size_t a, size_t b) { return peaks[a].start < peaks[b].start; });
-    struct Span { size_t lo, hi, off; };
-    std::vector<Span> spans;
-    std::vector<size_t> span_of(n);
-    size_t staged = 0;
-    for (size_t i : order) {
-        const size_t lo = peaks[i].start > 0 ? (size_t)peaks[i].start - 1 : 0, hi = std::min(len, (size_t)peaks[i].start + s + 1);
-        if (!spans.empty() && lo <= spans.back().hi) {
-            staged += std::max(hi, spans.back().hi) - spans.back().hi;
-            spans.back().hi = std::max(hi, spans.back().hi);
-        } else {
-            spans.push_back({lo, hi, staged});
-            staged += hi - lo;
-        }
-        span_of[i] = spans.size() - 1;
-    }
-    if ((rc = c->hit_stage.ensure(4 * staged))) return rc;   // (4 bytes per f32 sample and per i16 stereo frame)
-    for (const Span& sp : spans)
-        AM_HIP(hipMemcpyAsync(const_cast<void*>(advance_src(c->hit_stage.p, sp.off)), advance_src(haystack, sp.lo), 4 * (sp.hi - sp.lo),
-                              hipMemcpyHostToDevice, c->stream));
-    for (size_t i = 0; i < n; ++i) {
-        const Span& sp = spans[span_of[i]];
-        hits[i].win = advance_src(c->hit_stage.p, sp.off + ((size_t)peaks[i].start - sp.lo));
-    }
-    return score_hits(c, hits, dst.data());
-}
-
-int am_hit_scores_batch_device(const am_needle* const* needles, size_t n_needles,
-                               const void* const* d_haystacks, const size_t* lens, size_t n_hay, int sample_format,
-                               const am_peak* peaks, size_t cap_per_pair, const size_t* n_peaks, am_hit_score* out) {
-    int rc;
-    if ((rc = hit_check_format(sample_format))) return rc;
-    if (n_needles == 0 || n_hay == 0) return AM_OK;
-    if (!needles || !d_haystacks || !lens || !n_peaks) return fail(AM_ERR_INVALID_ARG, "null pointer");
-    size_t total = 0;
-    for (size_t q = 0; q < n_needles * n_hay; ++q) total += std::min(n_peaks[q], cap_per_pair);
-    if (total == 0) return AM_OK;
-    if (!peaks || !out) return fail(AM_ERR_INVALID_ARG, "null pointer");
-    for (size_t j = 0; j < n_needles; ++j)
-        if (!needles[j] || !needles[j]->ctx) return fail(AM_ERR_INVALID_ARG, "needle " + std::to_string(j) + ": null needle handle");
-    if ((rc = check_needle(needles[0]))) return rc;
-    Ctx* c = needles[0]->ctx;
-    for (size_t j = 1; j < n_needles; ++j)
-        if (needles[j]->ctx->device != c->device)
-            return fail(AM_ERR_INVALID_ARG, "needle " + std::to_string(j) + ": on device " + std::to_string(needles[j]->ctx->device) +
-                                                ", needle 0 on device " + std::to_string(c->device));
-    std::lock_guard<std::recursive_mutex> lk(c->mu);
-    std::vector<double> thr(n_needles);
-    for (size_t j = 0; j < n_needles; ++j) thr[j] = hit_floor(needles[j]);
-    std::vector<HitDesc> hits;
-    std::vector<am_hit_score*> dst;
-    hits.reserve(total);
-    dst.reserve(total);
-    for (size_t k = 0; k < n_hay; ++k) {
-        bool checked = false;
-        for (size_t j = 0; j < n_needles; ++j) {
-            const size_t pair = k * n_needles + j, np = std::min(n_peaks[pair], cap_per_pair);
-            if (np == 0) continue;
-            if (!checked) {   // (once per haystack; messages are spelled out only for a refusal)
-                const HitWhere w{(long long)pair, k, j, 0};
-                if (!d_haystacks[k]) return fail(AM_ERR_INVALID_ARG, hit_pair_name(w) + "null haystack");
-                if ((rc = hit_check_device(d_haystacks[k], c->device, w))) return rc;
-                checked = true;
-            }
-            for (size_t i = 0; i < np; ++i) {
-                HitDesc d{};
-                const size_t slot = pair * cap_per_pair + i;
-                if ((rc = hit_desc(needles[j], d_haystacks[k], lens[k], sample_format, peaks[slot], thr[j], HitWhere{(long long)pair, k, j, i}, &d)))
-                    return rc;
-                hits.push_back(d);
-                dst.push_back(out + slot);
-            }
-        }
-    }
-    return score_hits(c, hits, dst.data());
-}
-
 int am_find_peaks(int device, const float* scores, size_t n, float min_prominence,
                   uint64_t min_distance, am_peak* out, size_t cap, size_t* n_out) {
     if (!scores || !n_out || (!out && cap)) return fail(AM_ERR_INVALID_ARG, "null pointer");

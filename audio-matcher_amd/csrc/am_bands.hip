@@ -21,7 +21,8 @@
 // The kernels read x[t + u] for u in [0, (J - 1) H + F) and n[0 .. (J - 1) H + F) only.  A hit's records depend on the
 // needle, the samples it reads, the parameters and the floor only (groups start at multiples of kBandGroup frames, every
 // reduction runs in a fixed order; one kernel serves both sample formats): the single, batch and host forms agree
-// bit for bit.
+// bit for bit.  The three forms run in the frame of am_hits.hip (am_internal.h: hit_call, hit_call_batch,
+// hit_round_trip); BandFamily below is what this family adds to it.
 #include "am_internal.h"
 
 namespace am {
@@ -33,9 +34,6 @@ constexpr int kBandMaxF = 1 << 12;
 constexpr int kBandLds = kBandMaxF + (kBandMaxF >> 5) + (kBandMaxF >> 10);   // one padded array of F doubles
 constexpr int kBandBins = (kBandMaxF / 2) / kBandThreads + 1;                // bins per thread: k = tid + m * kBandThreads <= F / 2
 static_assert(AM_BAND_MAX_BANDS <= 64, "band_combine forms one record per lane");
-
-typedef __attribute__((address_space(1))) const float gfloat;
-typedef __attribute__((address_space(1))) const unsigned guint;   // (one i16 stereo frame)
 
 // Element i of an LDS array of 8-byte values, one pad per 32 and per 1024: the bit-reversed store of a frame (stride
 // F / 2, F / 4, ...) and the butterflies of the first stages (stride 2, 4, ...) then spread over the banks.
@@ -271,31 +269,8 @@ int band_check_needle(const am_band_params* bp, size_t s, const std::string& who
     return AM_OK;
 }
 
-double band_floor_ratio(const am_needle* h) {
-    return std::pow(10.0, -(double)snapshot_opts(h).score_norm_floor_db / 10.0);
-}
-
-// the table entry of hit pk (checks as hit_desc does, same messages)
-int band_desc(const am_needle* h, const void* hay, size_t len, int sample_format, const am_peak& pk, int lf, double floor_ratio,
-              const HitWhere& where, BandDesc* d) {
-    HitDesc hd{};
-    int rc;
-    if ((rc = hit_desc(h, hay, len, sample_format, pk, 0.0, where, &hd))) return rc;
-    d->win = hd.win;
-    d->needle = hd.needle;
-    d->nframes = band_frames(hd.s, lf);
-    d->part0 = 0;
-    d->floor_ratio = floor_ratio;
-    d->kind = hd.kind;
-    d->ngroups = (int)((d->nframes + kBandGroup - 1) / kBandGroup);
-    return AM_OK;
-}
-
 // scores every hit of `hits` in one launch sequence on c's stream; out[i]: host destination of hit i's bp.n_bands records
 int score_bands(Ctx* c, std::vector<BandDesc>& hits, const am_band_params& bp, am_hit_band* const* out) {
-    const long long n = (long long)hits.size(), nb = bp.n_bands;
-    if (n == 0) return AM_OK;
-    const size_t rec = sizeof(double) * (size_t)band_record_len((int)nb);
     long long total = 0;
     int max_groups = 0;
     for (BandDesc& d : hits) {
@@ -303,29 +278,42 @@ int score_bands(Ctx* c, std::vector<BandDesc>& hits, const am_band_params& bp, a
         total += d.ngroups;
         max_groups = std::max(max_groups, d.ngroups);
     }
-    const size_t n_out = (size_t)(n * nb);
     const double* tab = nullptr;
     int rc;
     if ((rc = band_table(c, (int)bp.frame_log2, &tab))) return rc;
-    if ((rc = c->band_tab.ensure(sizeof(BandDesc) * (size_t)n)) || (rc = c->band_parts.ensure(rec * (size_t)total)) ||
-        (rc = c->band_flags.ensure(sizeof(unsigned) * (size_t)total)) || (rc = c->band_out.ensure(sizeof(am_hit_band) * n_out)) ||
-        (rc = c->hit_io.ensure(std::max(sizeof(BandDesc) * (size_t)n, sizeof(am_hit_band) * n_out))))
-        return rc;
-    // (the copies go through pinned memory, as in score_hits)
-    std::memcpy(c->hit_io.p, hits.data(), sizeof(BandDesc) * (size_t)n);
-    AM_HIP(hipMemcpyAsync(c->band_tab.p, c->hit_io.p, sizeof(BandDesc) * (size_t)n, hipMemcpyHostToDevice, c->stream));
-    {
-        ProfScope ps(c, KN_OTHER, c->stream);
-        AM_HIP(launch_hit_bands(c->stream, static_cast<const BandDesc*>(c->band_tab.p), n, bp, max_groups,
-                                std::pow(10.0, -(double)AM_BAND_EMPTY_DB / 10.0), tab, static_cast<double*>(c->band_parts.p),
-                                static_cast<unsigned*>(c->band_flags.p), static_cast<am_hit_band*>(c->band_out.p)));
-    }
-    AM_HIP(hipMemcpyAsync(c->hit_io.p, c->band_out.p, sizeof(am_hit_band) * n_out, hipMemcpyDeviceToHost, c->stream));
-    AM_HIP(hipStreamSynchronize(c->stream));
-    const am_hit_band* res = static_cast<const am_hit_band*>(c->hit_io.p);
-    for (long long i = 0; i < n; ++i) std::memcpy(out[i], res + i * nb, sizeof(am_hit_band) * (size_t)nb);
-    return AM_OK;
+    return hit_round_trip(c, hits, sizeof(double) * (size_t)band_record_len((int)bp.n_bands), (size_t)total, (size_t)bp.n_bands, out,
+                          [&](const BandDesc* d_hits, double* parts, unsigned* pflags, am_hit_band* d_out) {
+                              return launch_hit_bands(c->stream, d_hits, (long long)hits.size(), bp, max_groups,
+                                                      std::pow(10.0, -(double)AM_BAND_EMPTY_DB / 10.0), tab, parts, pflags, d_out);
+                          });
 }
+
+// am_hit_bands*: a hit at t reads [t, t + (J - 1) H + F)
+struct BandFamily {
+    typedef BandDesc Desc;
+    typedef am_hit_band Rec;
+    const am_band_params* bp;
+    const void* params() const { return bp; }
+    size_t recs() const { return bp->n_bands; }
+    int check_call() const { return AM_OK; }
+    int check(const am_needle* h, long long j) const {
+        const int rc = band_check_params(bp);
+        return rc ? rc : band_check_needle(bp, h->n, hit_needle_name(j));
+    }
+    double floor(const am_needle* h) const { return hit_floor_ratio(h); }
+    // (checks as hit_desc does, same messages)
+    int desc(const am_needle* h, const void* hay, size_t len, int sample_format, const am_peak& pk, double ratio, const HitWhere& where,
+             BandDesc* d) const {
+        HitDesc hd{};
+        int rc;
+        if ((rc = hit_desc(h, hay, len, sample_format, pk, 0.0, where, &hd))) return rc;
+        const long long nframes = band_frames(hd.s, (int)bp->frame_log2);
+        *d = BandDesc{hd.win, hd.needle, nframes, 0, ratio, hd.kind, (int)((nframes + kBandGroup - 1) / kBandGroup)};
+        return AM_OK;
+    }
+    HitRange span(const am_needle* h, size_t t, size_t) const { return HitRange{t, t + band_span(h->n, (int)bp->frame_log2)}; }
+    int score(Ctx* c, std::vector<BandDesc>& hits, am_hit_band* const* out) const { return score_bands(c, hits, *bp, out); }
+};
 
 }  // namespace
 
@@ -335,130 +323,21 @@ using namespace am;
 
 extern "C" {
 
-// ---- per-band hit scoring: the hit table of a call is built here, scored in one launch sequence ----
-int am_hit_bands_device(const am_needle* h, const void* d_haystack, size_t len, int sample_format,
-                        const am_peak* peaks, size_t n, const am_band_params* bp, am_hit_band* out) {
-    int rc = check_needle(h);
-    if (rc) return rc;
-    if ((rc = hit_check_format(sample_format))) return rc;
-    if (n == 0) return AM_OK;
-    if (!d_haystack || !peaks || !out || !bp) return fail(AM_ERR_INVALID_ARG, "null pointer");
-    if ((rc = band_check_params(bp)) || (rc = band_check_needle(bp, h->n, ""))) return rc;
-    Ctx* c = h->ctx;
-    std::lock_guard<std::recursive_mutex> lk(c->mu);
-    if ((rc = hit_check_device(d_haystack, c->device, HitWhere{-1, 0, 0, 0}))) return rc;
-    const double ratio = band_floor_ratio(h);
-    std::vector<BandDesc> hits(n);
-    std::vector<am_hit_band*> dst(n);
-    for (size_t i = 0; i < n; ++i) {
-        if ((rc = band_desc(h, d_haystack, len, sample_format, peaks[i], (int)bp->frame_log2, ratio, HitWhere{-1, 0, 0, i}, &hits[i]))) return rc;
-        dst[i] = out + i * bp->n_bands;
-    }
-    return score_bands(c, hits, *bp, dst.data());
-}
-
 int am_hit_bands(const am_needle* h, const void* haystack, size_t len, int sample_format,
                  const am_peak* peaks, size_t n, const am_band_params* bp, am_hit_band* out) {
-    int rc = check_needle(h);
-    if (rc) return rc;
-    if ((rc = hit_check_format(sample_format))) return rc;
-    if (n == 0) return AM_OK;
-    if (!haystack || !peaks || !out || !bp) return fail(AM_ERR_INVALID_ARG, "null pointer");
-    if ((rc = band_check_params(bp)) || (rc = band_check_needle(bp, h->n, ""))) return rc;
-    Ctx* c = h->ctx;
-    std::lock_guard<std::recursive_mutex> lk(c->mu);
-    const double ratio = band_floor_ratio(h);
-    const size_t span = band_span(h->n, (int)bp->frame_log2);
-    std::vector<BandDesc> hits(n);
-    std::vector<am_hit_band*> dst(n);
-    for (size_t i = 0; i < n; ++i) {
-        if ((rc = band_desc(h, haystack, len, sample_format, peaks[i], (int)bp->frame_log2, ratio, HitWhere{-1, 0, 0, i}, &hits[i]))) return rc;
-        dst[i] = out + i * bp->n_bands;
-    }
-    // the spans [t, t + (J - 1) H + F) of the hits, merged where they overlap or touch, copied one after the other into
-    // the staging buffer; every hit's window pointer then points into its span's copy
-    std::vector<size_t> order(n);
-    for (size_t i = 0; i < n; ++i) order[i] = i;
-    std::sort(order.begin(), order.end(), [&](size_t a, size_t b) { return peaks[a].start < peaks[b].start; });
-    struct Span { size_t lo, hi, off; };
-    std::vector<Span> spans;
-    std::vector<size_t> span_of(n);
-    size_t staged = 0;
-    for (size_t i : order) {
-        const size_t lo = (size_t)peaks[i].start, hi = lo + span;
-        if (!spans.empty() && lo <= spans.back().hi) {
-            staged += std::max(hi, spans.back().hi) - spans.back().hi;
-            spans.back().hi = std::max(hi, spans.back().hi);
-        } else {
-            spans.push_back({lo, hi, staged});
-            staged += hi - lo;
-        }
-        span_of[i] = spans.size() - 1;
-    }
-    if ((rc = c->hit_stage.ensure(4 * staged))) return rc;   // (4 bytes per f32 sample and per i16 stereo frame)
-    for (const Span& sp_ : spans)
-        AM_HIP(hipMemcpyAsync(const_cast<void*>(advance_src(c->hit_stage.p, sp_.off)), advance_src(haystack, sp_.lo), 4 * (sp_.hi - sp_.lo),
-                              hipMemcpyHostToDevice, c->stream));
-    for (size_t i = 0; i < n; ++i) {
-        const Span& sp_ = spans[span_of[i]];
-        hits[i].win = advance_src(c->hit_stage.p, sp_.off + ((size_t)peaks[i].start - sp_.lo));
-    }
-    return score_bands(c, hits, *bp, dst.data());
+    return hit_call(BandFamily{bp}, true, h, haystack, len, sample_format, peaks, n, out);
+}
+
+int am_hit_bands_device(const am_needle* h, const void* d_haystack, size_t len, int sample_format,
+                        const am_peak* peaks, size_t n, const am_band_params* bp, am_hit_band* out) {
+    return hit_call(BandFamily{bp}, false, h, d_haystack, len, sample_format, peaks, n, out);
 }
 
 int am_hit_bands_batch_device(const am_needle* const* needles, size_t n_needles,
                               const void* const* d_haystacks, const size_t* lens, size_t n_hay, int sample_format,
                               const am_peak* peaks, size_t cap_per_pair, const size_t* n_peaks,
                               const am_band_params* bp, am_hit_band* out) {
-    int rc;
-    if ((rc = hit_check_format(sample_format))) return rc;
-    if (n_needles == 0 || n_hay == 0) return AM_OK;
-    if (!needles || !d_haystacks || !lens || !n_peaks) return fail(AM_ERR_INVALID_ARG, "null pointer");
-    size_t total = 0;
-    for (size_t q = 0; q < n_needles * n_hay; ++q) total += std::min(n_peaks[q], cap_per_pair);
-    if (total == 0) return AM_OK;
-    if (!peaks || !out || !bp) return fail(AM_ERR_INVALID_ARG, "null pointer");
-    for (size_t j = 0; j < n_needles; ++j)
-        if (!needles[j] || !needles[j]->ctx) return fail(AM_ERR_INVALID_ARG, "needle " + std::to_string(j) + ": null needle handle");
-    if ((rc = check_needle(needles[0]))) return rc;
-    Ctx* c = needles[0]->ctx;
-    for (size_t j = 1; j < n_needles; ++j)
-        if (needles[j]->ctx->device != c->device)
-            return fail(AM_ERR_INVALID_ARG, "needle " + std::to_string(j) + ": on device " + std::to_string(needles[j]->ctx->device) +
-                                                ", needle 0 on device " + std::to_string(c->device));
-    if ((rc = band_check_params(bp))) return rc;
-    for (size_t j = 0; j < n_needles; ++j)
-        if ((rc = band_check_needle(bp, needles[j]->n, "needle " + std::to_string(j) + ": "))) return rc;
-    std::lock_guard<std::recursive_mutex> lk(c->mu);
-    std::vector<double> ratio(n_needles);
-    for (size_t j = 0; j < n_needles; ++j) ratio[j] = band_floor_ratio(needles[j]);
-    std::vector<BandDesc> hits;
-    std::vector<am_hit_band*> dst;
-    hits.reserve(total);
-    dst.reserve(total);
-    for (size_t k = 0; k < n_hay; ++k) {
-        bool checked = false;
-        for (size_t j = 0; j < n_needles; ++j) {
-            const size_t pair = k * n_needles + j, np = std::min(n_peaks[pair], cap_per_pair);
-            if (np == 0) continue;
-            if (!checked) {   // (once per haystack; messages are spelled out only for a refusal)
-                const HitWhere w{(long long)pair, k, j, 0};
-                if (!d_haystacks[k]) return fail(AM_ERR_INVALID_ARG, hit_pair_name(w) + "null haystack");
-                if ((rc = hit_check_device(d_haystacks[k], c->device, w))) return rc;
-                checked = true;
-            }
-            for (size_t i = 0; i < np; ++i) {
-                BandDesc d{};
-                const size_t slot = pair * cap_per_pair + i;
-                if ((rc = band_desc(needles[j], d_haystacks[k], lens[k], sample_format, peaks[slot], (int)bp->frame_log2, ratio[j],
-                                    HitWhere{(long long)pair, k, j, i}, &d)))
-                    return rc;
-                hits.push_back(d);
-                dst.push_back(out + slot * bp->n_bands);
-            }
-        }
-    }
-    return score_bands(c, hits, *bp, dst.data());
+    return hit_call_batch(BandFamily{bp}, needles, n_needles, d_haystacks, lens, n_hay, sample_format, peaks, cap_per_pair, n_peaks, out);
 }
 
 int am_hit_bands_summary(const am_hit_band* rec, uint32_t n_bands, float min_coherence, am_band_summary* out) {

@@ -511,15 +511,12 @@ int am_shutdown(void) {
             b->release();
         for (HostBuf* b : {&c->pinned, &c->hdr, &c->spill, &c->badflag, &c->failcnt}) b->release();
         c->ranges.release(); c->range_flags.release(); c->big.release(); c->norm_blk.release();
-        for (DevBuf* b : {&c->hit_tab, &c->hit_parts, &c->hit_flags, &c->hit_out, &c->hit_stage, &c->seg_tab, &c->seg_parts, &c->seg_flags,
-                           &c->seg_out})
-            b->release();
+        for (DevBuf* b : {&c->hit_tab, &c->hit_parts, &c->hit_flags, &c->hit_out, &c->hit_stage}) b->release();
         c->hit_io.release();
-        for (DevBuf* b : {&c->sig_span, &c->sig_scores, &c->sig_tab, &c->sig_psum, &c->sig_pmax, &c->sig_mean, &c->sig_hmax, &c->sig_out}) b->release();
+        for (DevBuf* b : {&c->sig_span, &c->sig_scores, &c->sig_psum, &c->sig_pmax, &c->sig_mean, &c->sig_hmax}) b->release();
         for (DevBuf* b : {&c->best_stats, &c->best_lmax, &c->best_ctl, &c->best_trans, &c->best_list, &c->best_scores, &c->best_mono}) b->release();
         for (auto& kv : c->rs_taps) kv.second.release();
         c->rs_taps.clear();
-        for (DevBuf* b : {&c->band_tab, &c->band_parts, &c->band_flags, &c->band_out}) b->release();
         for (auto& kv : c->band_tabs) kv.second.release();
         c->band_tabs.clear();
         c->work_tail.release(); c->tail_scores.release(); c->tail_stats.release(); c->work_tail2.release();

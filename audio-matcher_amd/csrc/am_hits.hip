@@ -11,6 +11,11 @@
 // A hit's result depends on its needle, the samples it reads and the floor only (the slices of a hit start at
 // multiples of kHitSlice of the needle, every reduction runs in a fixed order): the single, batch and host forms agree
 // bit for bit, whatever else a call holds.
+//
+// Below the kernels: the host side every per-hit family shares (this file, am_segments.hip, am_bands.hip,
+// am_significance.hip) -- the preludes of the three call forms, span staging for the host forms and the table's trip to
+// the device and back; the templates that tie them together (hit_call, hit_call_batch, hit_round_trip) are in
+// am_internal.h, which also says what a family supplies.  Then am_hit_scores* itself, as the first such family.
 #include "am_internal.h"
 
 namespace am {
@@ -35,14 +40,6 @@ __device__ void hit_block_sum4(double v[4]) {
         for (int i = 0; i < kHitThreads / 64; ++i) t += ws[k][i];
         v[k] = t;
     }
-}
-
-// x[t + u] of a hit's window pointer, read through the global address space (u may be -1)
-typedef __attribute__((address_space(1))) const float gfloat;
-typedef __attribute__((address_space(1))) const unsigned guint;   // (one i16 stereo frame)
-template <int KIND>
-__device__ __forceinline__ float hit_sample(const void* win, long long u) {
-    return KIND ? norm_downmix(__builtin_bit_cast(short2, ((guint*)win)[u])) : ((gfloat*)win)[u];
 }
 
 template <int KIND>
@@ -228,9 +225,94 @@ double hit_floor(const am_needle* h) {
     return norm_spec(h, snapshot_opts(h)).thr;
 }
 
+double hit_floor_ratio(const am_needle* h) {
+    return std::pow(10.0, -(double)snapshot_opts(h).score_norm_floor_db / 10.0);
+}
+
+// ---- the frame of the per-hit families (am_internal.h) ---------------------------------------------------------------
+
+std::string hit_needle_name(long long j) {
+    return j < 0 ? "" : "needle " + std::to_string(j) + ": ";
+}
+
+int hit_single_prelude(const am_needle* h, int sample_format, size_t n, const void* hay, const am_peak* peaks, const void* out,
+                       const void* params, bool* done) {
+    int rc = check_needle(h);
+    if (rc) return rc;
+    if ((rc = hit_check_format(sample_format))) return rc;
+    *done = n == 0;
+    if (*done) return AM_OK;
+    if (!hay || !peaks || !out || !params) return fail(AM_ERR_INVALID_ARG, "null pointer");
+    return AM_OK;
+}
+
+int hit_batch_counts(size_t n_needles, size_t n_hay, int sample_format, const void* needles, const void* d_haystacks, const void* lens,
+                     const am_peak* peaks, size_t cap_per_pair, const size_t* n_peaks, const void* out, const void* params, size_t* total) {
+    int rc;
+    *total = 0;
+    if ((rc = hit_check_format(sample_format))) return rc;
+    if (n_needles == 0 || n_hay == 0) return AM_OK;
+    if (!needles || !d_haystacks || !lens || !n_peaks) return fail(AM_ERR_INVALID_ARG, "null pointer");
+    size_t sum = 0;
+    for (size_t q = 0; q < n_needles * n_hay; ++q) sum += std::min(n_peaks[q], cap_per_pair);
+    if (sum && (!peaks || !out || !params)) return fail(AM_ERR_INVALID_ARG, "null pointer");
+    *total = sum;
+    return AM_OK;
+}
+
+int hit_batch_needles(const am_needle* const* needles, size_t n_needles) {
+    int rc;
+    for (size_t j = 0; j < n_needles; ++j)
+        if (!needles[j] || !needles[j]->ctx) return fail(AM_ERR_INVALID_ARG, hit_needle_name((long long)j) + "null needle handle");
+    if ((rc = check_needle(needles[0]))) return rc;
+    const int device = needles[0]->ctx->device;
+    for (size_t j = 1; j < n_needles; ++j)
+        if (needles[j]->ctx->device != device)
+            return fail(AM_ERR_INVALID_ARG, hit_needle_name((long long)j) + "on device " + std::to_string(needles[j]->ctx->device) +
+                                                ", needle 0 on device " + std::to_string(device));
+    return AM_OK;
+}
+
+int stage_spans(Ctx* c, const void* haystack, const HitRange* r, size_t n, const void** at) {
+    std::vector<Span> spans;
+    std::vector<size_t> span_of;
+    const size_t staged = merge_spans(r, n, spans, span_of);
+    int rc;
+    if ((rc = c->hit_stage.ensure(4 * staged))) return rc;   // (4 bytes per f32 sample and per i16 stereo frame)
+    for (const Span& sp : spans)
+        AM_HIP(hipMemcpyAsync(const_cast<void*>(advance_src(c->hit_stage.p, sp.off)), advance_src(haystack, sp.lo), 4 * (sp.hi - sp.lo),
+                              hipMemcpyHostToDevice, c->stream));
+    for (size_t i = 0; i < n; ++i) {
+        const Span& sp = spans[span_of[i]];
+        at[i] = advance_src(c->hit_stage.p, sp.off + (r[i].lo - sp.lo));
+    }
+    return AM_OK;
+}
+
+int hit_io_reserve(Ctx* c, size_t tab_bytes, size_t out_bytes) {
+    int rc;
+    if ((rc = c->hit_tab.ensure(tab_bytes)) || (rc = c->hit_out.ensure(out_bytes))) return rc;
+    return c->hit_io.ensure(tab_bytes + out_bytes);
+}
+
+int hit_table_put(Ctx* c, const void* rows, size_t off, size_t bytes) {
+    char* pinned = static_cast<char*>(c->hit_io.p) + off;
+    std::memcpy(pinned, rows, bytes);
+    AM_HIP(hipMemcpyAsync(static_cast<char*>(c->hit_tab.p) + off, pinned, bytes, hipMemcpyHostToDevice, c->stream));
+    return AM_OK;
+}
+
+int hit_results_get(Ctx* c, size_t tab_bytes, size_t out_bytes, const void** res) {
+    void* pinned = static_cast<char*>(c->hit_io.p) + tab_bytes;
+    AM_HIP(hipMemcpyAsync(pinned, c->hit_out.p, out_bytes, hipMemcpyDeviceToHost, c->stream));
+    AM_HIP(hipStreamSynchronize(c->stream));
+    *res = pinned;
+    return AM_OK;
+}
+
+namespace {
+
 int score_hits(Ctx* c, std::vector<HitDesc>& hits, am_hit_score* const* out) {
-    const long long n = (long long)hits.size();
-    if (n == 0) return AM_OK;
     long long total = 0, max_slices = 0;
     for (HitDesc& d : hits) {
         const long long ns = (d.s + kHitSlice - 1) / kHitSlice;
@@ -238,24 +320,51 @@ int score_hits(Ctx* c, std::vector<HitDesc>& hits, am_hit_score* const* out) {
         total += ns;
         max_slices = std::max(max_slices, ns);
     }
-    int rc;
-    if ((rc = c->hit_tab.ensure(sizeof(HitDesc) * (size_t)n)) || (rc = c->hit_parts.ensure(4 * sizeof(double) * (size_t)total)) ||
-        (rc = c->hit_flags.ensure(sizeof(unsigned) * (size_t)total)) || (rc = c->hit_out.ensure(sizeof(am_hit_score) * (size_t)n)) ||
-        (rc = c->hit_io.ensure(std::max(sizeof(HitDesc), sizeof(am_hit_score)) * (size_t)n)))
-        return rc;
-    // (the copies go through pinned memory: no staging in the runtime, which is most of a small call's time)
-    std::memcpy(c->hit_io.p, hits.data(), sizeof(HitDesc) * (size_t)n);
-    AM_HIP(hipMemcpyAsync(c->hit_tab.p, c->hit_io.p, sizeof(HitDesc) * (size_t)n, hipMemcpyHostToDevice, c->stream));
-    {
-        ProfScope ps(c, KN_OTHER, c->stream);
-        AM_HIP(launch_hit_scores(c->stream, static_cast<const HitDesc*>(c->hit_tab.p), n, max_slices, hits[0].kind, static_cast<double*>(c->hit_parts.p),
-                                 static_cast<unsigned*>(c->hit_flags.p), static_cast<am_hit_score*>(c->hit_out.p)));
-    }
-    AM_HIP(hipMemcpyAsync(c->hit_io.p, c->hit_out.p, sizeof(am_hit_score) * (size_t)n, hipMemcpyDeviceToHost, c->stream));
-    AM_HIP(hipStreamSynchronize(c->stream));
-    const am_hit_score* res = static_cast<const am_hit_score*>(c->hit_io.p);
-    for (long long i = 0; i < n; ++i) *out[i] = res[i];
-    return AM_OK;
+    return hit_round_trip(c, hits, 4 * sizeof(double), (size_t)total, 1, out,
+                          [&](const HitDesc* tab, double* parts, unsigned* pflags, am_hit_score* d_out) {
+                              return launch_hit_scores(c->stream, tab, (long long)hits.size(), max_slices, hits[0].kind, parts, pflags, d_out);
+                          });
 }
 
+// am_hit_scores*: no parameters; a hit at t reads [t - 1, t + S + 1), clipped to the haystack
+struct ScoreFamily {
+    typedef HitDesc Desc;
+    typedef am_hit_score Rec;
+    const void* params() const { return this; }
+    size_t recs() const { return 1; }
+    int check_call() const { return AM_OK; }
+    int check(const am_needle*, long long) const { return AM_OK; }
+    double floor(const am_needle* h) const { return hit_floor(h); }
+    int desc(const am_needle* h, const void* hay, size_t len, int sample_format, const am_peak& pk, double thr, const HitWhere& where,
+             HitDesc* d) const {
+        return hit_desc(h, hay, len, sample_format, pk, thr, where, d);
+    }
+    HitRange span(const am_needle* h, size_t t, size_t len) const { return HitRange{t > 0 ? t - 1 : 0, std::min(len, t + h->n + 1)}; }
+    int score(Ctx* c, std::vector<HitDesc>& hits, am_hit_score* const* out) const { return score_hits(c, hits, out); }
+};
+
+}  // namespace
+
 }  // namespace am
+
+using namespace am;
+
+extern "C" {
+
+int am_hit_scores(const am_needle* h, const void* haystack, size_t len, int sample_format,
+                  const am_peak* peaks, size_t n, am_hit_score* out) {
+    return hit_call(ScoreFamily{}, true, h, haystack, len, sample_format, peaks, n, out);
+}
+
+int am_hit_scores_device(const am_needle* h, const void* d_haystack, size_t len, int sample_format,
+                         const am_peak* peaks, size_t n, am_hit_score* out) {
+    return hit_call(ScoreFamily{}, false, h, d_haystack, len, sample_format, peaks, n, out);
+}
+
+int am_hit_scores_batch_device(const am_needle* const* needles, size_t n_needles,
+                               const void* const* d_haystacks, const size_t* lens, size_t n_hay, int sample_format,
+                               const am_peak* peaks, size_t cap_per_pair, const size_t* n_peaks, am_hit_score* out) {
+    return hit_call_batch(ScoreFamily{}, needles, n_needles, d_haystacks, lens, n_hay, sample_format, peaks, cap_per_pair, n_peaks, out);
+}
+
+}  // extern "C"

@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "am_kernels.h"
+#include "am_spans.h"
 
 namespace am {
 
@@ -152,14 +153,15 @@ struct Ctx {
     ScoreSide side[2];
     DevBuf work2, segs, io_in, io_out, sum, arena_cur, wide_ctl, wide_list, wide_tiles;
     DevBuf norm_blk;   // block energies of the haystack being normalised (option score_norm; used on one stream at a time)
-    DevBuf hit_tab, hit_parts, hit_flags, hit_out, hit_stage;   // per-hit scoring (am_hits.hip): hit table, partials, results, staged spans
-    HostBuf hit_io;                                              // ... and the pinned host side of the table and the results
-    DevBuf seg_tab, seg_parts, seg_flags, seg_out;               // per-segment hit scoring (am_segments.hip); spans and pinned side: hit_stage, hit_io
-    DevBuf band_tab, band_parts, band_flags, band_out;           // per-band hit scoring (am_bands.hip); spans and pinned side: hit_stage, hit_io
-    std::map<int, DevBuf> band_tabs;                             // ... and the window and twiddle table of each frame_log2
-    // per-hit significance (am_significance.hip): the spans and score zones of one group of hits, the table, the slice
-    // partials, the per-hit state between the two passes and the results; pinned side: hit_io, host spans: hit_stage
-    DevBuf sig_span, sig_scores, sig_tab, sig_psum, sig_pmax, sig_mean, sig_hmax, sig_out;
+    // per-hit scoring, every family (the frame in am_hits.hip): the call's hit table, its partial records and their flag
+    // words, the results and the spans a host form stages, each sized in bytes by the call at hand; a call holds `mu`
+    // and waits for its results, so one set serves the families in turn
+    DevBuf hit_tab, hit_parts, hit_flags, hit_out, hit_stage;
+    HostBuf hit_io;                         // ... and the pinned host side: the table, the results behind it
+    std::map<int, DevBuf> band_tabs;        // per-band hit scoring (am_bands.hip): the window and twiddle table of each frame_log2
+    // per-hit significance (am_significance.hip): the spans and score zones of one group of hits, the slice partials and
+    // the per-hit state between the two passes
+    DevBuf sig_span, sig_scores, sig_psum, sig_pmax, sig_mean, sig_hmax;
     std::map<std::pair<int, int>, DevBuf> rs_taps;              // sample-rate conversion: the polyphase table of each (L, M)
     DevBuf redo_pairs[2];   // device-side redo (batches): the per-pair "run again" flags of both sets
     // several needles: the K3s of a needle group run as ONE launch, every needle of the group with score-side
@@ -425,28 +427,152 @@ int normalise_scores(Ctx* c, hipStream_t st, const NormSpec& ns, const void* src
                      long long s, float* scores, long long a, long long b);
 #define AM_NORM_UNSUPPORTED "score_norm: not supported by this entry point"
 
-// ---- am_hits.hip ----
+// ---- am_hits.hip: per-hit scoring, and the frame every per-hit family's three call forms run in ----
 int hit_check_format(int sample_format);
-double hit_floor(const am_needle* h);   // the floor on E_w the NCC path applies (process option score_norm_floor_db)
+double hit_floor(const am_needle* h);         // the floor on E_w the NCC path applies (process option score_norm_floor_db)
+double hit_floor_ratio(const am_needle* h);   // ... as a ratio to the needle's energy: 10^(-score_norm_floor_db / 10)
 // Which hit of a call (for error messages): hit `hit` of pair `pair` = (haystack `hay`, needle `needle`), pair < 0: a
 // single-haystack call
 struct HitWhere { long long pair; size_t hay, needle, hit; };
 std::string hit_pair_name(const HitWhere& w);   // "pair p (haystack k, needle j): ", or "" for a single-haystack call
+std::string hit_needle_name(long long j);       // "needle j: ", or "" for j < 0 (a single-haystack call)
 // AM_ERR_INVALID_ARG (message: names the pair of `where`) unless p is device memory of `device`
 int hit_check_device(const void* p, int device, const HitWhere& where);
 // the table entry of hit pk of haystack `hay` (its samples from element 0; `len` elements), or AM_ERR_INVALID_ARG
 // (message: names `where`) when the needle does not fit behind pk.start
 int hit_desc(const am_needle* h, const void* hay, size_t len, int sample_format, const am_peak& pk, double thr,
              const HitWhere& where, HitDesc* d);
-// scores every hit of `hits` in one launch sequence on c's stream; out[i]: host destination of hit i
-int score_hits(Ctx* c, std::vector<HitDesc>& hits, am_hit_score* const* out);
 
-// ---- am_segments.hip ----
-// the table entry of hit pk for radius r (checks as hit_desc does, same messages)
-int seg_desc(const am_needle* h, const void* hay, size_t len, int sample_format, const am_peak& pk, int r, double floor_ratio,
-             const HitWhere& where, SegDesc* d);
-// scores every hit of `hits` in one launch sequence on c's stream; out[i]: host destination of hit i's sp.segments records
-int score_segments(Ctx* c, std::vector<SegDesc>& hits, const am_segment_params& sp, am_hit_segment* const* out);
+// What the host and _device forms check before they look at a hit, in this order: the needle handle, the sample format,
+// n == 0 (*done: nothing to do), the pointers (`params`: the family's parameter block)
+int hit_single_prelude(const am_needle* h, int sample_format, size_t n, const void* hay, const am_peak* peaks, const void* out,
+                       const void* params, bool* done);
+// ... and the _batch_device form: the sample format, an empty call, the pointers, *total = sum(min(n_peaks, cap)) (0:
+// nothing to do); then the needle handles and that they share a device
+int hit_batch_counts(size_t n_needles, size_t n_hay, int sample_format, const void* needles, const void* d_haystacks, const void* lens,
+                     const am_peak* peaks, size_t cap_per_pair, const size_t* n_peaks, const void* out, const void* params, size_t* total);
+int hit_batch_needles(const am_needle* const* needles, size_t n_needles);
+// r[i]: the elements of the host haystack hit i reads.  Merges them (am_spans.h), copies the merged spans one after the
+// other into c->hit_stage on c's stream; at[i]: where element r[i].lo lies on the device
+int stage_spans(Ctx* c, const void* haystack, const HitRange* r, size_t n, const void** at);
+// The table and the results of a call: sizes c->hit_tab / hit_out and the pinned hit_io (the table, the results behind
+// it); rows [off, off + bytes) of the table through the pinned side to the device; the results back, waited for
+int hit_io_reserve(Ctx* c, size_t tab_bytes, size_t out_bytes);
+int hit_table_put(Ctx* c, const void* rows, size_t off, size_t bytes);
+int hit_results_get(Ctx* c, size_t tab_bytes, size_t out_bytes, const void** res);
+
+// A family F names its table entry (Desc; its member `win` points at the samples), its record (Rec) and
+//   params()                  its parameter block, for the null check
+//   recs()                    records per hit
+//   check_call()              the parameters by themselves: a batch call checks them before it looks at a needle handle
+//   check(h, j)               the parameters against needle h (hit_needle_name(j) for messages)
+//   floor(h)                  what it reads of h's options, once per call and needle
+//   desc(h, hay, len, fmt, pk, floor, where, &d)   the table entry of one hit, or its refusal
+//   span(h, t, len)           the elements of the haystack a hit at t reads
+//   score(c, hits, out)       the kernels: every hit of the table, out[i] the host destination of hit i's records
+
+// the host form's staging: every hit's `win` moves from the host haystack into its span's copy on the device
+template <class F>
+int stage_host_spans(const F& f, Ctx* c, const am_needle* h, const void* haystack, size_t len, const am_peak* peaks,
+                     std::vector<typename F::Desc>& hits) {
+    const size_t n = hits.size();
+    std::vector<HitRange> r(n);
+    std::vector<const void*> at(n);
+    for (size_t i = 0; i < n; ++i) r[i] = f.span(h, (size_t)peaks[i].start, len);
+    int rc;
+    if ((rc = stage_spans(c, haystack, r.data(), n, at.data()))) return rc;
+    for (size_t i = 0; i < n; ++i) {
+        const size_t e = (size_t)(static_cast<const char*>(hits[i].win) - static_cast<const char*>(haystack)) / 4;
+        hits[i].win = advance_src(at[i], e - r[i].lo);
+    }
+    return AM_OK;
+}
+
+// the host form (on_host) and the _device form
+template <class F>
+int hit_call(const F& f, bool on_host, const am_needle* h, const void* hay, size_t len, int sample_format, const am_peak* peaks,
+             size_t n, typename F::Rec* out) {
+    bool done = false;
+    int rc = hit_single_prelude(h, sample_format, n, hay, peaks, out, f.params(), &done);
+    if (rc || done) return rc;
+    if ((rc = f.check_call()) || (rc = f.check(h, -1))) return rc;
+    Ctx* c = h->ctx;
+    std::lock_guard<std::recursive_mutex> lk(c->mu);
+    if (!on_host && (rc = hit_check_device(hay, c->device, HitWhere{-1, 0, 0, 0}))) return rc;
+    const double floor = f.floor(h);
+    std::vector<typename F::Desc> hits(n);
+    std::vector<typename F::Rec*> dst(n);
+    for (size_t i = 0; i < n; ++i) {
+        if ((rc = f.desc(h, hay, len, sample_format, peaks[i], floor, HitWhere{-1, 0, 0, i}, &hits[i]))) return rc;
+        dst[i] = out + i * f.recs();
+    }
+    if (on_host && (rc = stage_host_spans(f, c, h, hay, len, peaks, hits))) return rc;
+    return f.score(c, hits, dst.data());
+}
+
+// the _batch_device form: pair (k, j) = haystack k against needle j, its hits in slots [pair * cap, pair * cap + n_peaks[pair])
+template <class F>
+int hit_call_batch(const F& f, const am_needle* const* needles, size_t n_needles, const void* const* d_haystacks, const size_t* lens,
+                   size_t n_hay, int sample_format, const am_peak* peaks, size_t cap_per_pair, const size_t* n_peaks,
+                   typename F::Rec* out) {
+    size_t total = 0;
+    int rc = hit_batch_counts(n_needles, n_hay, sample_format, needles, d_haystacks, lens, peaks, cap_per_pair, n_peaks, out, f.params(), &total);
+    if (rc || total == 0) return rc;
+    if ((rc = f.check_call()) || (rc = hit_batch_needles(needles, n_needles))) return rc;
+    for (size_t j = 0; j < n_needles; ++j)
+        if ((rc = f.check(needles[j], (long long)j))) return rc;
+    Ctx* c = needles[0]->ctx;
+    std::lock_guard<std::recursive_mutex> lk(c->mu);
+    std::vector<double> floor(n_needles);
+    for (size_t j = 0; j < n_needles; ++j) floor[j] = f.floor(needles[j]);
+    std::vector<typename F::Desc> hits;
+    std::vector<typename F::Rec*> dst;
+    hits.reserve(total);
+    dst.reserve(total);
+    for (size_t k = 0; k < n_hay; ++k) {
+        bool checked = false;
+        for (size_t j = 0; j < n_needles; ++j) {
+            const size_t pair = k * n_needles + j, np = std::min(n_peaks[pair], cap_per_pair);
+            if (np == 0) continue;
+            if (!checked) {   // (once per haystack; messages are spelled out only for a refusal)
+                const HitWhere w{(long long)pair, k, j, 0};
+                if (!d_haystacks[k]) return fail(AM_ERR_INVALID_ARG, hit_pair_name(w) + "null haystack");
+                if ((rc = hit_check_device(d_haystacks[k], c->device, w))) return rc;
+                checked = true;
+            }
+            for (size_t i = 0; i < np; ++i) {
+                typename F::Desc d{};
+                const size_t slot = pair * cap_per_pair + i;
+                if ((rc = f.desc(needles[j], d_haystacks[k], lens[k], sample_format, peaks[slot], floor[j], HitWhere{(long long)pair, k, j, i}, &d)))
+                    return rc;
+                hits.push_back(d);
+                dst.push_back(out + slot * f.recs());
+            }
+        }
+    }
+    return f.score(c, hits, dst.data());
+}
+
+// The round trip of a table whose kernels write n_parts partial records of part_bytes (and one flag word each) and
+// `recs` records per hit: the table up through pinned memory (no staging in the runtime, which is most of a small
+// call's time), launch(table, parts, flags, results) on c's stream, the results back and out to out[i]
+template <class Desc, class Rec, class Launch>
+int hit_round_trip(Ctx* c, const std::vector<Desc>& hits, size_t part_bytes, size_t n_parts, size_t recs, Rec* const* out, Launch launch) {
+    const size_t n = hits.size(), tab_bytes = sizeof(Desc) * n, out_bytes = sizeof(Rec) * recs * n;
+    int rc;
+    if ((rc = hit_io_reserve(c, tab_bytes, out_bytes)) || (rc = c->hit_parts.ensure(part_bytes * n_parts)) ||
+        (rc = c->hit_flags.ensure(sizeof(unsigned) * n_parts)) || (rc = hit_table_put(c, hits.data(), 0, tab_bytes)))
+        return rc;
+    {
+        ProfScope ps(c, KN_OTHER, c->stream);
+        AM_HIP(launch(static_cast<const Desc*>(c->hit_tab.p), static_cast<double*>(c->hit_parts.p), static_cast<unsigned*>(c->hit_flags.p),
+                      static_cast<Rec*>(c->hit_out.p)));
+    }
+    const void* res = nullptr;
+    if ((rc = hit_results_get(c, tab_bytes, out_bytes, &res))) return rc;
+    for (size_t i = 0; i < n; ++i) std::memcpy(out[i], static_cast<const Rec*>(res) + i * recs, sizeof(Rec) * recs);
+    return AM_OK;
+}
 
 // ---- am_correlate.hip ----
 int plan_geometry(size_t s, long long out_count, const Opts& o, Geometry* g);

@@ -275,6 +275,14 @@ hipError_t launch_pcm_downmix(hipStream_t st, const int16_t* in, long long frame
 __device__ __forceinline__ float norm_downmix(short2 lr) {
     return __fmul_rn((float)((int)lr.x + (int)lr.y), 0.5f * (1.0f / 65535.0f));
 }
+// x[u] of a hit's sample pointer (u may be negative) in either sample format, read through the global address space:
+// what the per-hit kernels (am_hits.hip, am_segments.hip, am_bands.hip) load; am_resample.hip reads through the same types
+typedef __attribute__((address_space(1))) const float gfloat;
+typedef __attribute__((address_space(1))) const unsigned guint;   // (one i16 stereo frame)
+template <int KIND>
+__device__ __forceinline__ float hit_sample(const void* win, long long u) {
+    return KIND ? norm_downmix(__builtin_bit_cast(short2, ((guint*)win)[u])) : ((gfloat*)win)[u];
+}
 
 // ---- am_norm.hip: window-energy normalisation (option "score_norm") ----
 constexpr int kNormBlock = 1024;   // samples per block energy

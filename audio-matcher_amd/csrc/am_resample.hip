@@ -24,8 +24,6 @@ constexpr int kRsWMax = 2048;     // work items per workgroup (unless L alone is
 constexpr uint32_t kResampleMaxRate = 768000;   // rates in 1 .. this, Hz
 constexpr long long kResampleMaxR = 8192;       // R = max(L, M) up to this (11025 <-> 384000 Hz: 5120)
 
-typedef __attribute__((address_space(1))) const float gfloat;
-typedef __attribute__((address_space(1))) const unsigned guint;   // (one i16 stereo frame)
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 typedef __attribute__((address_space(1))) const f32x4 gf32x4;

@@ -16,7 +16,8 @@
 // The kernels read x[t + u] for u in [-R, S + R) inside the haystack only (SegDesc::ulo, uhi), whatever RT is: that is
 // what the host form stages, and lags beyond R never reach a result.  A segment's result depends on the needle, the
 // samples it reads, m, R and the floor only (slices start at multiples of kHitSlice from a_j, every reduction runs in
-// a fixed order): the single, batch and host forms agree bit for bit.
+// a fixed order): the single, batch and host forms agree bit for bit.  The three forms run in the frame of am_hits.hip
+// (am_internal.h: hit_call, hit_call_batch, hit_round_trip); SegFamily below is what this family adds to it.
 #include "am_internal.h"
 
 namespace am {
@@ -29,13 +30,6 @@ constexpr int kSegMaxRecord = 2 * (2 * AM_SEG_MAX_RADIUS + 1) + 1;
 static_assert(kHitSlice % kSegThreads == 0, "slice must split evenly over the workgroup");
 static_assert(kSegRadii[2] == AM_SEG_MAX_RADIUS, "the widest kernel holds every radius");
 static_assert(2 * AM_SEG_MAX_RADIUS <= kSegThreads && kSegMaxRecord < kSegThreads, "one staged tail sample and one record value per thread");
-
-typedef __attribute__((address_space(1))) const float gfloat;
-typedef __attribute__((address_space(1))) const unsigned guint;   // (one i16 stereo frame)
-template <int KIND>
-__device__ __forceinline__ float seg_sample(const void* win, long long u) {
-    return KIND ? norm_downmix(__builtin_bit_cast(short2, ((guint*)win)[u])) : ((gfloat*)win)[u];
-}
 
 __device__ __forceinline__ long long seg_start(long long j, long long s, int m) { return j * s / m; }   // a_j (j <= 1024, s < 2^52)
 
@@ -64,14 +58,14 @@ __global__ __launch_bounds__(kSegThreads) void seg_slices_kernel(const SegDesc* 
     for (int k = 0; k < kSegPer; ++k) {
         const int q = tid + k * kSegThreads;
         const long long u = u0 + q;
-        xv[k] = q < cnt + 2 * RT && u >= d.ulo && u < d.uhi ? seg_sample<KIND>(d.win, u) : 0.0f;
+        xv[k] = q < cnt + 2 * RT && u >= d.ulo && u < d.uhi ? hit_sample<KIND>(d.win, u) : 0.0f;
         nv[k] = q < cnt ? nd[q] : 0.0f;
     }
     float xt = 0.0f;
     if (tid < 2 * RT) {
         const int q = kHitSlice + tid;
         const long long u = u0 + q;
-        xt = q < cnt + 2 * RT && u >= d.ulo && u < d.uhi ? seg_sample<KIND>(d.win, u) : 0.0f;
+        xt = q < cnt + 2 * RT && u >= d.ulo && u < d.uhi ? hit_sample<KIND>(d.win, u) : 0.0f;
     }
     bool bad = false;
 #pragma unroll
@@ -225,27 +219,11 @@ hipError_t launch_hit_segments(hipStream_t st, const SegDesc* d_hits, long long 
 
 // ---- host side -------------------------------------------------------------------------------------------------------
 
-int seg_desc(const am_needle* h, const void* hay, size_t len, int sample_format, const am_peak& pk, int r, double floor_ratio,
-             const HitWhere& where, SegDesc* d) {
-    HitDesc hd{};
-    int rc;
-    if ((rc = hit_desc(h, hay, len, sample_format, pk, 0.0, where, &hd))) return rc;
-    d->win = hd.win;
-    d->needle = hd.needle;
-    d->s = hd.s;
-    d->ulo = -std::min<long long>(r, hd.t);
-    d->uhi = std::min<long long>(hd.s + r, (long long)len - hd.t);
-    d->part0 = 0;
-    d->floor_ratio = floor_ratio;
-    d->kind = hd.kind;
-    d->nsl = 0;
-    return AM_OK;
-}
+namespace {
 
+// scores every hit of `hits` in one launch sequence on c's stream; out[i]: host destination of hit i's sp.segments records
 int score_segments(Ctx* c, std::vector<SegDesc>& hits, const am_segment_params& sp, am_hit_segment* const* out) {
-    const long long n = (long long)hits.size(), m = sp.segments;
-    if (n == 0) return AM_OK;
-    const size_t rec = sizeof(double) * (size_t)seg_record_len(seg_kernel_radius((int)sp.radius));
+    const long long m = sp.segments;
     long long total = 0;
     int max_nsl = 0;
     for (SegDesc& d : hits) {
@@ -255,29 +233,12 @@ int score_segments(Ctx* c, std::vector<SegDesc>& hits, const am_segment_params& 
         total += m * d.nsl;
         max_nsl = std::max(max_nsl, d.nsl);
     }
-    const size_t n_out = (size_t)(n * m);
-    int rc;
-    if ((rc = c->seg_tab.ensure(sizeof(SegDesc) * (size_t)n)) || (rc = c->seg_parts.ensure(rec * (size_t)total)) ||
-        (rc = c->seg_flags.ensure(sizeof(unsigned) * (size_t)total)) || (rc = c->seg_out.ensure(sizeof(am_hit_segment) * n_out)) ||
-        (rc = c->hit_io.ensure(std::max(sizeof(SegDesc) * (size_t)n, sizeof(am_hit_segment) * n_out))))
-        return rc;
-    // (the copies go through pinned memory, as in score_hits)
-    std::memcpy(c->hit_io.p, hits.data(), sizeof(SegDesc) * (size_t)n);
-    AM_HIP(hipMemcpyAsync(c->seg_tab.p, c->hit_io.p, sizeof(SegDesc) * (size_t)n, hipMemcpyHostToDevice, c->stream));
-    {
-        ProfScope ps(c, KN_OTHER, c->stream);
-        AM_HIP(launch_hit_segments(c->stream, static_cast<const SegDesc*>(c->seg_tab.p), n, (int)m, (int)sp.radius, max_nsl, hits[0].kind,
-                                   static_cast<double*>(c->seg_parts.p), static_cast<unsigned*>(c->seg_flags.p),
-                                   static_cast<am_hit_segment*>(c->seg_out.p)));
-    }
-    AM_HIP(hipMemcpyAsync(c->hit_io.p, c->seg_out.p, sizeof(am_hit_segment) * n_out, hipMemcpyDeviceToHost, c->stream));
-    AM_HIP(hipStreamSynchronize(c->stream));
-    const am_hit_segment* res = static_cast<const am_hit_segment*>(c->hit_io.p);
-    for (long long i = 0; i < n; ++i) std::memcpy(out[i], res + i * m, sizeof(am_hit_segment) * (size_t)m);
-    return AM_OK;
+    return hit_round_trip(c, hits, sizeof(double) * (size_t)seg_record_len(seg_kernel_radius((int)sp.radius)), (size_t)total, (size_t)m, out,
+                          [&](const SegDesc* tab, double* parts, unsigned* pflags, am_hit_segment* d_out) {
+                              return launch_hit_segments(c->stream, tab, (long long)hits.size(), (int)m, (int)sp.radius, max_nsl, hits[0].kind,
+                                                         parts, pflags, d_out);
+                          });
 }
-
-namespace {
 
 // AM_ERR_INVALID_ARG unless sp is a valid request for a needle of s samples (`who`: "" or "needle j: ")
 int seg_check_params(const am_segment_params* sp, size_t s, const std::string& who) {
@@ -291,9 +252,32 @@ int seg_check_params(const am_segment_params* sp, size_t s, const std::string& w
     return AM_OK;
 }
 
-double seg_floor_ratio(const am_needle* h) {
-    return std::pow(10.0, -(double)snapshot_opts(h).score_norm_floor_db / 10.0);
-}
+// am_hit_segments*: a hit at t reads [t - R, t + S + R), clipped to the haystack
+struct SegFamily {
+    typedef SegDesc Desc;
+    typedef am_hit_segment Rec;
+    const am_segment_params* sp;
+    const void* params() const { return sp; }
+    size_t recs() const { return sp->segments; }
+    int check_call() const { return AM_OK; }
+    int check(const am_needle* h, long long j) const { return seg_check_params(sp, h->n, hit_needle_name(j)); }
+    double floor(const am_needle* h) const { return hit_floor_ratio(h); }
+    // (checks as hit_desc does, same messages)
+    int desc(const am_needle* h, const void* hay, size_t len, int sample_format, const am_peak& pk, double ratio, const HitWhere& where,
+             SegDesc* d) const {
+        HitDesc hd{};
+        const long long r = sp->radius;
+        int rc;
+        if ((rc = hit_desc(h, hay, len, sample_format, pk, 0.0, where, &hd))) return rc;
+        *d = SegDesc{hd.win, hd.needle, hd.s, -std::min(r, hd.t), std::min(hd.s + r, (long long)len - hd.t), 0, ratio, hd.kind, 0};
+        return AM_OK;
+    }
+    HitRange span(const am_needle* h, size_t t, size_t len) const {
+        const size_t r = sp->radius;
+        return HitRange{t > r ? t - r : 0, std::min(len, t + h->n + r)};
+    }
+    int score(Ctx* c, std::vector<SegDesc>& hits, am_hit_segment* const* out) const { return score_segments(c, hits, *sp, out); }
+};
 
 }  // namespace
 
@@ -303,129 +287,21 @@ using namespace am;
 
 extern "C" {
 
-// ---- per-segment hit scoring: the hit table of a call is built here, scored in one launch sequence ----
-int am_hit_segments_device(const am_needle* h, const void* d_haystack, size_t len, int sample_format,
-                           const am_peak* peaks, size_t n, const am_segment_params* sp, am_hit_segment* out) {
-    int rc = check_needle(h);
-    if (rc) return rc;
-    if ((rc = hit_check_format(sample_format))) return rc;
-    if (n == 0) return AM_OK;
-    if (!d_haystack || !peaks || !out || !sp) return fail(AM_ERR_INVALID_ARG, "null pointer");
-    if ((rc = seg_check_params(sp, h->n, ""))) return rc;
-    Ctx* c = h->ctx;
-    std::lock_guard<std::recursive_mutex> lk(c->mu);
-    if ((rc = hit_check_device(d_haystack, c->device, HitWhere{-1, 0, 0, 0}))) return rc;
-    const double ratio = seg_floor_ratio(h);
-    std::vector<SegDesc> hits(n);
-    std::vector<am_hit_segment*> dst(n);
-    for (size_t i = 0; i < n; ++i) {
-        if ((rc = seg_desc(h, d_haystack, len, sample_format, peaks[i], (int)sp->radius, ratio, HitWhere{-1, 0, 0, i}, &hits[i]))) return rc;
-        dst[i] = out + i * sp->segments;
-    }
-    return score_segments(c, hits, *sp, dst.data());
-}
-
 int am_hit_segments(const am_needle* h, const void* haystack, size_t len, int sample_format,
                     const am_peak* peaks, size_t n, const am_segment_params* sp, am_hit_segment* out) {
-    int rc = check_needle(h);
-    if (rc) return rc;
-    if ((rc = hit_check_format(sample_format))) return rc;
-    if (n == 0) return AM_OK;
-    if (!haystack || !peaks || !out || !sp) return fail(AM_ERR_INVALID_ARG, "null pointer");
-    if ((rc = seg_check_params(sp, h->n, ""))) return rc;
-    Ctx* c = h->ctx;
-    std::lock_guard<std::recursive_mutex> lk(c->mu);
-    const double ratio = seg_floor_ratio(h);
-    const size_t s = h->n, r = sp->radius;
-    std::vector<SegDesc> hits(n);
-    std::vector<am_hit_segment*> dst(n);
-    for (size_t i = 0; i < n; ++i) {
-        if ((rc = seg_desc(h, haystack, len, sample_format, peaks[i], (int)r, ratio, HitWhere{-1, 0, 0, i}, &hits[i]))) return rc;
-        dst[i] = out + i * sp->segments;
-    }
-    // the spans [t - R, t + S + R) of the hits, clipped to the haystack and merged where they overlap or touch, copied
-    // one after the other into the staging buffer; every hit's window pointer then points into its span's copy
-    std::vector<size_t> order(n);
-    for (size_t i = 0; i < n; ++i) order[i] = i;
-    std::sort(order.begin(), order.end(), [&](size_t a, size_t b) { return peaks[a].start < peaks[b].start; });
-    struct Span { size_t lo, hi, off; };
-    std::vector<Span> spans;
-    std::vector<size_t> span_of(n);
-    size_t staged = 0;
-    for (size_t i : order) {
-        const size_t t = (size_t)peaks[i].start, lo = t > r ? t - r : 0, hi = std::min(len, t + s + r);
-        if (!spans.empty() && lo <= spans.back().hi) {
-            staged += std::max(hi, spans.back().hi) - spans.back().hi;
-            spans.back().hi = std::max(hi, spans.back().hi);
-        } else {
-            spans.push_back({lo, hi, staged});
-            staged += hi - lo;
-        }
-        span_of[i] = spans.size() - 1;
-    }
-    if ((rc = c->hit_stage.ensure(4 * staged))) return rc;   // (4 bytes per f32 sample and per i16 stereo frame)
-    for (const Span& sp_ : spans)
-        AM_HIP(hipMemcpyAsync(const_cast<void*>(advance_src(c->hit_stage.p, sp_.off)), advance_src(haystack, sp_.lo), 4 * (sp_.hi - sp_.lo),
-                              hipMemcpyHostToDevice, c->stream));
-    for (size_t i = 0; i < n; ++i) {
-        const Span& sp_ = spans[span_of[i]];
-        hits[i].win = advance_src(c->hit_stage.p, sp_.off + ((size_t)peaks[i].start - sp_.lo));
-    }
-    return score_segments(c, hits, *sp, dst.data());
+    return hit_call(SegFamily{sp}, true, h, haystack, len, sample_format, peaks, n, out);
+}
+
+int am_hit_segments_device(const am_needle* h, const void* d_haystack, size_t len, int sample_format,
+                           const am_peak* peaks, size_t n, const am_segment_params* sp, am_hit_segment* out) {
+    return hit_call(SegFamily{sp}, false, h, d_haystack, len, sample_format, peaks, n, out);
 }
 
 int am_hit_segments_batch_device(const am_needle* const* needles, size_t n_needles,
                                  const void* const* d_haystacks, const size_t* lens, size_t n_hay, int sample_format,
                                  const am_peak* peaks, size_t cap_per_pair, const size_t* n_peaks,
                                  const am_segment_params* sp, am_hit_segment* out) {
-    int rc;
-    if ((rc = hit_check_format(sample_format))) return rc;
-    if (n_needles == 0 || n_hay == 0) return AM_OK;
-    if (!needles || !d_haystacks || !lens || !n_peaks) return fail(AM_ERR_INVALID_ARG, "null pointer");
-    size_t total = 0;
-    for (size_t q = 0; q < n_needles * n_hay; ++q) total += std::min(n_peaks[q], cap_per_pair);
-    if (total == 0) return AM_OK;
-    if (!peaks || !out || !sp) return fail(AM_ERR_INVALID_ARG, "null pointer");
-    for (size_t j = 0; j < n_needles; ++j)
-        if (!needles[j] || !needles[j]->ctx) return fail(AM_ERR_INVALID_ARG, "needle " + std::to_string(j) + ": null needle handle");
-    if ((rc = check_needle(needles[0]))) return rc;
-    Ctx* c = needles[0]->ctx;
-    for (size_t j = 1; j < n_needles; ++j)
-        if (needles[j]->ctx->device != c->device)
-            return fail(AM_ERR_INVALID_ARG, "needle " + std::to_string(j) + ": on device " + std::to_string(needles[j]->ctx->device) +
-                                                ", needle 0 on device " + std::to_string(c->device));
-    for (size_t j = 0; j < n_needles; ++j)
-        if ((rc = seg_check_params(sp, needles[j]->n, "needle " + std::to_string(j) + ": "))) return rc;
-    std::lock_guard<std::recursive_mutex> lk(c->mu);
-    std::vector<double> ratio(n_needles);
-    for (size_t j = 0; j < n_needles; ++j) ratio[j] = seg_floor_ratio(needles[j]);
-    std::vector<SegDesc> hits;
-    std::vector<am_hit_segment*> dst;
-    hits.reserve(total);
-    dst.reserve(total);
-    for (size_t k = 0; k < n_hay; ++k) {
-        bool checked = false;
-        for (size_t j = 0; j < n_needles; ++j) {
-            const size_t pair = k * n_needles + j, np = std::min(n_peaks[pair], cap_per_pair);
-            if (np == 0) continue;
-            if (!checked) {   // (once per haystack; messages are spelled out only for a refusal)
-                const HitWhere w{(long long)pair, k, j, 0};
-                if (!d_haystacks[k]) return fail(AM_ERR_INVALID_ARG, hit_pair_name(w) + "null haystack");
-                if ((rc = hit_check_device(d_haystacks[k], c->device, w))) return rc;
-                checked = true;
-            }
-            for (size_t i = 0; i < np; ++i) {
-                SegDesc d{};
-                const size_t slot = pair * cap_per_pair + i;
-                if ((rc = seg_desc(needles[j], d_haystacks[k], lens[k], sample_format, peaks[slot], (int)sp->radius, ratio[j],
-                                   HitWhere{(long long)pair, k, j, i}, &d)))
-                    return rc;
-                hits.push_back(d);
-                dst.push_back(out + slot * sp->segments);
-            }
-        }
-    }
-    return score_segments(c, hits, *sp, dst.data());
+    return hit_call_batch(SegFamily{sp}, needles, n_needles, d_haystacks, lens, n_hay, sample_format, peaks, cap_per_pair, n_peaks, out);
 }
 
 int am_hit_segments_summary(const am_hit_segment* seg, uint32_t segments, size_t needle_len, float min_ncc,

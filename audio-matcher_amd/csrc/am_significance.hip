@@ -12,7 +12,9 @@
 //   sig_finish    one wave per hit: adds those partials in slice order and writes the am_significance record.
 // No atomics: a thread adds its scores in index order, a wave by a butterfly, the waves and the slices in index order.
 // Slices start at multiples of kSigSlice from the zone's first lag, so a hit's record depends on its own zone only --
-// not on the group, the call or the entry point.
+// not on the group, the call or the entry point.  The three call forms run in the frame of am_hits.hip (am_internal.h:
+// hit_call, hit_call_batch); SigFamily below is what this family adds to it, and score_significance uses the frame's
+// table and result halves per group.
 #include "am_internal.h"
 
 #include <climits>
@@ -259,12 +261,11 @@ namespace {
 // One hit of a call, as the host sees it
 struct SigHit {
     am_needle* h;
-    const void* span;        // device: element lo of the haystack (f32 mono, or i16 stereo frames for kind 1)
+    const void* win;         // device: element lo of the haystack (f32 mono, or i16 stereo frames for kind 1)
     int kind;
     long long span_len;      // hi + S - lo
     long long nz, c;         // hi - lo + 1, t - lo
     unsigned flags;          // AM_HIT_CLIPPED
-    am_significance* out;
 };
 
 // What a call reads of one needle, once: the options in force, the normalisation, the factor, "a sample is not finite"
@@ -278,29 +279,9 @@ int sig_check_params(const am_significance_params* sp) {
     return AM_OK;
 }
 
-// the host's view of hit pk of haystack `hay` (its samples from element 0; `len` elements), or AM_ERR_INVALID_ARG
-// (message: names `where`) when the needle does not fit behind pk.start
-int sig_hit(const am_needle* h, const void* hay, size_t len, int sample_format, const am_peak& pk, const am_significance_params& sp,
-            const HitWhere& where, am_significance* out, SigHit* d) {
-    HitDesc hd{};
-    int rc;
-    if ((rc = hit_desc(h, hay, len, sample_format, pk, 0.0, where, &hd))) return rc;
-    const long long t = hd.t, s = hd.s, b = (long long)sp.radius;
-    const long long lo = std::max(0ll, t - b), hi = std::min((long long)len - s, t + b);
-    d->h = const_cast<am_needle*>(h);
-    d->span = advance_src(hay, (size_t)lo);
-    d->kind = hd.kind;
-    d->span_len = hi + s - lo;
-    d->nz = hi - lo + 1;
-    d->c = t - lo;
-    d->flags = (lo > t - b || hi < t + b) ? AM_HIT_CLIPPED : 0u;
-    d->out = out;
-    return AM_OK;
-}
-
-int score_significance(Ctx* c, std::vector<SigHit>& hits, const am_significance_params& sp) {
+// scores every hit of `hits` on c's stream, group by group; out[i]: host destination of hit i's record
+int score_significance(Ctx* c, std::vector<SigHit>& hits, const am_significance_params& sp, am_significance* const* out) {
     const size_t n = hits.size();
-    if (n == 0) return AM_OK;
     int rc;
     // every needle of the call once: its options as they are now, and whether it holds a non-finite sample
     std::map<am_needle*, SigNeedle> needles;
@@ -331,14 +312,10 @@ int score_significance(Ctx* c, std::vector<SigHit>& hits, const am_significance_
         total += (d.nz + kSigSlice - 1) / kSigSlice;
     }
     const size_t tab_bytes = sizeof(SigDesc) * n, out_bytes = sizeof(am_significance) * n;
-    if ((rc = c->sig_tab.ensure(tab_bytes)) || (rc = c->sig_psum.ensure(sizeof(double) * (size_t)total)) ||
+    if ((rc = hit_io_reserve(c, tab_bytes, out_bytes)) || (rc = c->sig_psum.ensure(sizeof(double) * (size_t)total)) ||
         (rc = c->sig_pmax.ensure(3 * sizeof(unsigned) * (size_t)total)) || (rc = c->sig_mean.ensure(sizeof(double) * n)) ||
-        (rc = c->sig_hmax.ensure(3 * sizeof(unsigned) * n)) || (rc = c->sig_out.ensure(out_bytes)) ||
-        (rc = c->hit_io.ensure(tab_bytes + out_bytes)))
+        (rc = c->sig_hmax.ensure(3 * sizeof(unsigned) * n)))
         return rc;
-    // (the copies go through pinned memory, as in score_hits; every group has its own part of the table)
-    SigDesc* h_tab = static_cast<SigDesc*>(c->hit_io.p);
-    am_significance* h_out = reinterpret_cast<am_significance*>(static_cast<char*>(c->hit_io.p) + tab_bytes);
     std::vector<Segment> ranges;
     std::vector<int> bad;
     for (size_t g0 = 0; g0 < n;) {
@@ -361,8 +338,8 @@ int score_significance(Ctx* c, std::vector<SigHit>& hits, const am_significance_
         float* d_scores = static_cast<float*>(c->sig_scores.p);
         for (size_t i = g0; i < g1; ++i) {
             float* dst = d_span + ranges[i - g0].a;
-            if (hits[i].kind) AM_HIP(launch_pcm_downmix(c->stream, static_cast<const int16_t*>(hits[i].span), hits[i].span_len, dst));
-            else AM_HIP(hipMemcpyAsync(dst, hits[i].span, sizeof(float) * (size_t)hits[i].span_len, hipMemcpyDeviceToDevice, c->stream));
+            if (hits[i].kind) AM_HIP(launch_pcm_downmix(c->stream, static_cast<const int16_t*>(hits[i].win), hits[i].span_len, dst));
+            else AM_HIP(hipMemcpyAsync(dst, hits[i].win, sizeof(float) * (size_t)hits[i].span_len, hipMemcpyDeviceToDevice, c->stream));
         }
         bad.assign(ng, 0);
         if ((rc = nonfinite_flags(c, d_span, ranges.data(), (int)ng, bad.data()))) return rc;
@@ -377,23 +354,52 @@ int score_significance(Ctx* c, std::vector<SigHit>& hits, const am_significance_
                 return rc;
             }
         }
-        std::memcpy(h_tab + g0, descs.data() + g0, sizeof(SigDesc) * ng);
-        SigDesc* d_tab = static_cast<SigDesc*>(c->sig_tab.p) + g0;
-        AM_HIP(hipMemcpyAsync(d_tab, h_tab + g0, sizeof(SigDesc) * ng, hipMemcpyHostToDevice, c->stream));
+        // (every group has its own rows of the table)
+        if ((rc = hit_table_put(c, descs.data() + g0, sizeof(SigDesc) * g0, sizeof(SigDesc) * ng))) return rc;
+        const SigDesc* d_tab = static_cast<const SigDesc*>(c->hit_tab.p) + g0;
         {
             ProfScope ps(c, KN_OTHER, c->stream);
             AM_HIP(launch_hit_significance(c->stream, d_tab, (long long)ng, max_slices, d_scores, static_cast<double*>(c->sig_psum.p),
                                            static_cast<unsigned*>(c->sig_pmax.p), static_cast<double*>(c->sig_mean.p) + g0,
                                            static_cast<unsigned*>(c->sig_hmax.p) + 3 * g0,
-                                           static_cast<am_significance*>(c->sig_out.p) + g0));
+                                           static_cast<am_significance*>(c->hit_out.p) + g0));
         }
         g0 = g1;
     }
-    AM_HIP(hipMemcpyAsync(h_out, c->sig_out.p, out_bytes, hipMemcpyDeviceToHost, c->stream));
-    AM_HIP(hipStreamSynchronize(c->stream));
-    for (size_t i = 0; i < n; ++i) *hits[i].out = h_out[i];
+    const void* res = nullptr;
+    if ((rc = hit_results_get(c, tab_bytes, out_bytes, &res))) return rc;
+    for (size_t i = 0; i < n; ++i) *out[i] = static_cast<const am_significance*>(res)[i];
     return AM_OK;
 }
+
+// am_hit_significance*: a hit at t reads its zone's span [max(0, t - B), min(len - S, t + B) + S)
+struct SigFamily {
+    typedef SigHit Desc;
+    typedef am_significance Rec;
+    const am_significance_params* sp;
+    const void* params() const { return sp; }
+    size_t recs() const { return 1; }
+    int check_call() const { return sig_check_params(sp); }
+    int check(const am_needle*, long long) const { return AM_OK; }
+    double floor(const am_needle*) const { return 0.0; }   // (the zone's scores are am_correlate's: nothing of its own)
+    // (checks as hit_desc does, same messages)
+    int desc(const am_needle* h, const void* hay, size_t len, int sample_format, const am_peak& pk, double, const HitWhere& where,
+             SigHit* d) const {
+        HitDesc hd{};
+        int rc;
+        if ((rc = hit_desc(h, hay, len, sample_format, pk, 0.0, where, &hd))) return rc;
+        const long long t = hd.t, s = hd.s, b = (long long)sp->radius;
+        const long long lo = std::max(0ll, t - b), hi = std::min((long long)len - s, t + b);
+        *d = SigHit{const_cast<am_needle*>(h), advance_src(hay, (size_t)lo), hd.kind, hi + s - lo, hi - lo + 1, t - lo,
+                    (lo > t - b || hi < t + b) ? AM_HIT_CLIPPED : 0u};
+        return AM_OK;
+    }
+    HitRange span(const am_needle* h, size_t t, size_t len) const {
+        const size_t b = (size_t)sp->radius;
+        return HitRange{t > b ? t - b : 0, std::min(len - h->n, t + b) + h->n};
+    }
+    int score(Ctx* c, std::vector<SigHit>& hits, am_significance* const* out) const { return score_significance(c, hits, *sp, out); }
+};
 
 }  // namespace
 
@@ -403,115 +409,21 @@ using namespace am;
 
 extern "C" {
 
-int am_hit_significance_device(const am_needle* h, const void* d_haystack, size_t len, int sample_format,
-                               const am_peak* peaks, size_t n, const am_significance_params* sp, am_significance* out) {
-    int rc = check_needle(h);
-    if (rc) return rc;
-    if ((rc = hit_check_format(sample_format))) return rc;
-    if (n == 0) return AM_OK;
-    if (!d_haystack || !peaks || !out || !sp) return fail(AM_ERR_INVALID_ARG, "null pointer");
-    if ((rc = sig_check_params(sp))) return rc;
-    Ctx* c = h->ctx;
-    std::lock_guard<std::recursive_mutex> lk(c->mu);
-    if ((rc = hit_check_device(d_haystack, c->device, HitWhere{-1, 0, 0, 0}))) return rc;
-    std::vector<SigHit> hits(n);
-    for (size_t i = 0; i < n; ++i)
-        if ((rc = sig_hit(h, d_haystack, len, sample_format, peaks[i], *sp, HitWhere{-1, 0, 0, i}, out + i, &hits[i]))) return rc;
-    return score_significance(c, hits, *sp);
-}
-
 int am_hit_significance(const am_needle* h, const void* haystack, size_t len, int sample_format,
                         const am_peak* peaks, size_t n, const am_significance_params* sp, am_significance* out) {
-    int rc = check_needle(h);
-    if (rc) return rc;
-    if ((rc = hit_check_format(sample_format))) return rc;
-    if (n == 0) return AM_OK;
-    if (!haystack || !peaks || !out || !sp) return fail(AM_ERR_INVALID_ARG, "null pointer");
-    if ((rc = sig_check_params(sp))) return rc;
-    Ctx* c = h->ctx;
-    std::lock_guard<std::recursive_mutex> lk(c->mu);
-    std::vector<SigHit> hits(n);
-    for (size_t i = 0; i < n; ++i)
-        if ((rc = sig_hit(h, haystack, len, sample_format, peaks[i], *sp, HitWhere{-1, 0, 0, i}, out + i, &hits[i]))) return rc;
-    // the spans [lo, hi + S) of the hits, merged where they overlap or touch, copied one after the other into the
-    // staging buffer; every hit's span pointer then points into its span's copy
-    const size_t s = h->n, b = (size_t)sp->radius;
-    std::vector<size_t> order(n);
-    for (size_t i = 0; i < n; ++i) order[i] = i;
-    std::sort(order.begin(), order.end(), [&](size_t x, size_t y) { return peaks[x].start < peaks[y].start; });
-    struct Span { size_t lo, hi, off; };
-    std::vector<Span> spans;
-    std::vector<size_t> span_of(n), lo_of(n);
-    size_t staged = 0;
-    for (size_t i : order) {
-        const size_t t = (size_t)peaks[i].start, lo = t > b ? t - b : 0, hi = std::min(len - s, t + b) + s;
-        lo_of[i] = lo;
-        if (!spans.empty() && lo <= spans.back().hi) {
-            staged += std::max(hi, spans.back().hi) - spans.back().hi;
-            spans.back().hi = std::max(hi, spans.back().hi);
-        } else {
-            spans.push_back({lo, hi, staged});
-            staged += hi - lo;
-        }
-        span_of[i] = spans.size() - 1;
-    }
-    if ((rc = c->hit_stage.ensure(4 * staged))) return rc;   // (4 bytes per f32 sample and per i16 stereo frame)
-    for (const Span& q : spans)
-        AM_HIP(hipMemcpyAsync(const_cast<void*>(advance_src(c->hit_stage.p, q.off)), advance_src(haystack, q.lo), 4 * (q.hi - q.lo),
-                              hipMemcpyHostToDevice, c->stream));
-    for (size_t i = 0; i < n; ++i) {
-        const Span& q = spans[span_of[i]];
-        hits[i].span = advance_src(c->hit_stage.p, q.off + (lo_of[i] - q.lo));
-    }
-    return score_significance(c, hits, *sp);
+    return hit_call(SigFamily{sp}, true, h, haystack, len, sample_format, peaks, n, out);
+}
+
+int am_hit_significance_device(const am_needle* h, const void* d_haystack, size_t len, int sample_format,
+                               const am_peak* peaks, size_t n, const am_significance_params* sp, am_significance* out) {
+    return hit_call(SigFamily{sp}, false, h, d_haystack, len, sample_format, peaks, n, out);
 }
 
 int am_hit_significance_batch_device(const am_needle* const* needles, size_t n_needles,
                                      const void* const* d_haystacks, const size_t* lens, size_t n_hay, int sample_format,
                                      const am_peak* peaks, size_t cap_per_pair, const size_t* n_peaks,
                                      const am_significance_params* sp, am_significance* out) {
-    int rc;
-    if ((rc = hit_check_format(sample_format))) return rc;
-    if (n_needles == 0 || n_hay == 0) return AM_OK;
-    if (!needles || !d_haystacks || !lens || !n_peaks) return fail(AM_ERR_INVALID_ARG, "null pointer");
-    size_t total = 0;
-    for (size_t q = 0; q < n_needles * n_hay; ++q) total += std::min(n_peaks[q], cap_per_pair);
-    if (total == 0) return AM_OK;
-    if (!peaks || !out || !sp) return fail(AM_ERR_INVALID_ARG, "null pointer");
-    if ((rc = sig_check_params(sp))) return rc;
-    for (size_t j = 0; j < n_needles; ++j)
-        if (!needles[j] || !needles[j]->ctx) return fail(AM_ERR_INVALID_ARG, "needle " + std::to_string(j) + ": null needle handle");
-    if ((rc = check_needle(needles[0]))) return rc;
-    Ctx* c = needles[0]->ctx;
-    for (size_t j = 1; j < n_needles; ++j)
-        if (needles[j]->ctx->device != c->device)
-            return fail(AM_ERR_INVALID_ARG, "needle " + std::to_string(j) + ": on device " + std::to_string(needles[j]->ctx->device) +
-                                                ", needle 0 on device " + std::to_string(c->device));
-    std::lock_guard<std::recursive_mutex> lk(c->mu);
-    std::vector<SigHit> hits;
-    hits.reserve(total);
-    for (size_t k = 0; k < n_hay; ++k) {
-        bool checked = false;
-        for (size_t j = 0; j < n_needles; ++j) {
-            const size_t pair = k * n_needles + j, np = std::min(n_peaks[pair], cap_per_pair);
-            if (np == 0) continue;
-            if (!checked) {   // (once per haystack; messages are spelled out only for a refusal)
-                const HitWhere w{(long long)pair, k, j, 0};
-                if (!d_haystacks[k]) return fail(AM_ERR_INVALID_ARG, hit_pair_name(w) + "null haystack");
-                if ((rc = hit_check_device(d_haystacks[k], c->device, w))) return rc;
-                checked = true;
-            }
-            for (size_t i = 0; i < np; ++i) {
-                SigHit d{};
-                const size_t slot = pair * cap_per_pair + i;
-                if ((rc = sig_hit(needles[j], d_haystacks[k], lens[k], sample_format, peaks[slot], *sp, HitWhere{(long long)pair, k, j, i},
-                                  out + slot, &d)))
-                    return rc;
-                hits.push_back(d);
-            }
-        }
-    }
-    return score_significance(c, hits, *sp);
+    return hit_call_batch(SigFamily{sp}, needles, n_needles, d_haystacks, lens, n_hay, sample_format, peaks, cap_per_pair, n_peaks, out);
 }
 
 }  // extern "C"
