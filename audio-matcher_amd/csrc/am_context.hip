@@ -517,6 +517,7 @@ int am_shutdown(void) {
         for (DevBuf* b : {&c->best_stats, &c->best_lmax, &c->best_ctl, &c->best_trans, &c->best_list, &c->best_scores, &c->best_mono}) b->release();
         for (auto& kv : c->rs_taps) kv.second.release();
         c->rs_taps.clear();
+        c->lag_parts.release(); c->lag_r.release();
         for (auto& kv : c->band_tabs) kv.second.release();
         c->band_tabs.clear();
         c->work_tail.release(); c->tail_scores.release(); c->tail_stats.release(); c->work_tail2.release();

@@ -163,6 +163,7 @@ struct Ctx {
     // the per-hit state between the two passes
     DevBuf sig_span, sig_scores, sig_psum, sig_pmax, sig_mean, sig_hmax;
     std::map<std::pair<int, int>, DevBuf> rs_taps;              // sample-rate conversion: the polyphase table of each (L, M)
+    DevBuf lag_parts, lag_r;   // spectral whitening (am_whiten.hip): the per-(lag, block) partial lag products and their sums
     DevBuf redo_pairs[2];   // device-side redo (batches): the per-pair "run again" flags of both sets
     // several needles: the K3s of a needle group run as ONE launch, every needle of the group with score-side
     // buffers of its own; two such sets alternate (the picks of group g beside the transforms of group g + 1)

@@ -398,4 +398,34 @@ struct ResampleJob {
 };
 hipError_t launch_resample(hipStream_t st, const ResampleJob& j, int kind);
 
+// ---- am_whiten.hip: spectral whitening (am_lag_products*, am_fir*) ----
+constexpr int kLagBlock = 8192;     // samples per block of the lag products: one f64 partial per (lag, block)
+constexpr int kLagThreads = 256;
+constexpr int kLagChunk = 8;        // lags accumulated at a time (8 f64 accumulators per work item)
+constexpr int kLagHist = AM_WHITEN_MAX_ORDER + kLagChunk;   // samples staged in front of a block / a tile: what the aligned
+                                                            // register windows of the last chunk reach back to
+inline long long lag_blocks(long long n) { return (n + kLagBlock - 1) / kLagBlock; }
+// parts[k * nblk + b] = sum over the samples i of block b of x~[i] x~[i - k], k <= order (x~: 0 before sample 0 and for a
+// non-finite sample); r[k] = the partials of lag k added in block order.  vec: src is 16-byte aligned.
+hipError_t launch_lag_products(hipStream_t st, const void* src, long long n, int kind, int vec, int order, double* parts, double* r);
+constexpr int kFirThreads = 256;
+constexpr int kFirPer = 4;          // consecutive outputs per work item and pass
+constexpr int kFirPasses = 2;
+constexpr int kFirTile = kFirThreads * kFirPer * kFirPasses;   // outputs per workgroup
+constexpr int kFirChunk = 8;        // taps per register window
+constexpr int kFirHist = AM_FIR_MAX_TAPS - 1 + kFirChunk;   // samples staged in front of a tile (the last window's reach)
+// One launch: y[k] = sum_{j < n_taps} taps[j] x[lead + k - j], k < n_out = n_in - lead; x = src (f32 mono, or the down-mix
+// of i16 stereo frames for kind 1), 0 before src[0].  The taps travel in the kernel argument.
+struct FirJob {
+    const void* src;
+    long long n_in, lead;
+    float* dst;
+    long long n_out;
+    int n_taps;
+    int vec;             // 1: src + lead is 16-byte aligned (the staging loads read 4 samples / frames at a time)
+    int vec_out;         // 1: dst is 16-byte aligned (four samples per store)
+    float taps[AM_FIR_MAX_TAPS + kFirChunk - 1];   // taps[j >= n_taps] = 0, never multiplied
+};
+hipError_t launch_fir(hipStream_t st, const FirJob& j, int kind);
+
 }  // namespace am

@@ -82,6 +82,8 @@ struct Arguments {
     std::optional<float> min_significance;    // extension: --min-significance Z, drop hits whose z against the local background is below Z (am_hit_significance)
     std::optional<std::uint64_t> significance_zone_ms;   // ... --significance-zone D: the background reaches D each side of a hit (default: three snippet lengths)
     bool resample = false;                    // extension: --resample, bring the snippet to each main file's rate (am_needle_create_resampled)
+    std::uint32_t whiten = 0;                 // extension: --whiten P, one order-P whitening filter designed from all main files (am_lag_products, am_whiten_taps), 0 = off
+    std::optional<float> preemphasis;         // extension: --preemphasis A, the fixed filter {1, -A} on snippets and main files (am_fir)
     std::optional<std::uint64_t> best;        // extension: --best N, the N best hits per main file, no prominence threshold (am_match_best)
     bool live = false;                        // extension: --live, raw PCM from stdin through a monitor (am_monitor_*)
     std::uint32_t rate = 0;                   // --live: --rate R (samples per second of the stream)
@@ -143,6 +145,12 @@ inline const char* usage_text() {
            "                         snippet lengths; at most 4194304 samples)\n"
            "  --resample             match main files of any sample rate: the snippet is resampled to each file's rate\n"
            "                         (scipy's resample_poly filter); without it, a rate mismatch stops the run\n"
+           "  --whiten P             match in coloured material (speech, music): one prediction-error filter of order P\n"
+           "                         (1..64) is designed from all main files of the run and applied to the snippets\n"
+           "                         (after --resample) and to every main file before matching; offsets do not move,\n"
+           "                         scores are those of the whitened signals.  Does not apply with --live\n"
+           "  --preemphasis A        the fixed filter y[i] = x[i] - A x[i-1] (0 < A < 1) on the snippets and on every main\n"
+           "                         file instead; not together with --whiten.  Does not apply with --live\n"
            "  --live                 read raw PCM from stdin instead of files (no FILE arguments): a live feed, matched\n"
            "                         as it arrives; each hit's offset line is printed (and flushed) as soon as it is\n"
            "                         final -- a hit is final once the next hit is found, or once --distance of audio\n"
@@ -248,6 +256,22 @@ inline Arguments parse_arguments(int argc, const char* const* argv) {
             a.band_frame_log2 = (std::uint32_t)lf;
         }
         else if (s == "--resample") a.resample = true;
+        else if (s == "--whiten") {
+            const std::string v = need(i);
+            char* end = nullptr;
+            const unsigned long p = std::strtoul(v.c_str(), &end, 10);
+            if (v.empty() || v[0] < '0' || v[0] > '9' || *end != '\0' || p < 1 || p > AM_WHITEN_MAX_ORDER)
+                throw ArgError("invalid value '" + v + "' for --whiten (the filter's order, 1..64)");
+            a.whiten = (std::uint32_t)p;
+        }
+        else if (s == "--preemphasis") {
+            const std::string v = need(i);
+            char* end = nullptr;
+            const float x = std::strtof(v.c_str(), &end);
+            if (v.empty() || *end != '\0' || !(x > 0.0f && x < 1.0f))
+                throw ArgError("invalid value '" + v + "' for --preemphasis (a number with 0 < A < 1)");
+            a.preemphasis = x;
+        }
         else if (s == "--best") {
             const std::string v = need(i);
             char* end = nullptr;
@@ -279,6 +303,7 @@ inline Arguments parse_arguments(int argc, const char* const* argv) {
         else if (!s.empty()) a.within.push_back(s);
     }
     if (a.snippet.empty()) throw ArgError("--snippet <FILE> is required");
+    if (a.whiten && a.preemphasis) throw ArgError("--whiten and --preemphasis are mutually exclusive");
     if (a.live) {
         if (!a.within.empty()) throw ArgError("--live reads stdin: no FILE arguments");
         if (a.rate == 0) throw ArgError("--live needs --rate");
@@ -286,6 +311,7 @@ inline Arguments parse_arguments(int argc, const char* const* argv) {
         if (a.best || a.normalize || a.min_confidence) throw ArgError("--live: --best, --normalize and --min-confidence do not apply");
         if (a.segments) throw ArgError("--live: --segments does not apply");
         if (a.bands) throw ArgError("--live: --bands does not apply");
+        if (a.whiten || a.preemphasis) throw ArgError("--live: --whiten and --preemphasis do not apply (not supported on a live feed yet)");
         if (a.min_significance || a.significance_zone_ms) throw ArgError("--live: --min-significance and --significance-zone do not apply");
         return a;
     }

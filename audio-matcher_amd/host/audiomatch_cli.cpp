@@ -126,6 +126,68 @@ static size_t significance_filter(const Arguments& args, const am_needle* algo, 
     return kept;
 }
 
+// extension: --whiten P / --preemphasis A.  The taps of the ONE filter every snippet and every main file of the run passes
+// through before matching (empty: none).  --whiten: the lag products of all main files are added (am_lag_products), the
+// filter is their prediction-error filter of order P with noise_db 60 (am_whiten_taps); --preemphasis: {1, -A}.
+static std::vector<float> filter_taps(const Arguments& args) {
+    if (args.preemphasis) return {1.0f, -*args.preemphasis};
+    if (!args.whiten) return {};
+    std::vector<double> r(args.whiten + 1, 0.0), part(args.whiten + 1);
+    for (const std::string& main_file : args.within) {
+        const std::vector<float> x = to_mono_f32(read_wav(main_file), args.device);
+        if (am_lag_products(args.device, x.data(), x.size(), AM_FMT_F32_MONO, args.whiten, part.data()) != AM_OK)
+            throw std::runtime_error(std::string("am_lag_products: ") + am_last_error_string());
+        for (size_t k = 0; k < r.size(); ++k) r[k] += part[k];
+    }
+    std::vector<float> taps(args.whiten + 1);
+    if (am_whiten_taps(r.data(), args.whiten, 60.0, taps.data()) != AM_OK)
+        throw std::runtime_error(std::string("am_whiten_taps: ") + am_last_error_string());
+    if (args.verbosity >= 2) {
+        std::printf("whitening filter:");
+        for (float t : taps) std::printf(" %.6g", (double)t);
+        std::printf("\n");
+    }
+    return taps;
+}
+
+// x through the run's filter (am_fir); without one, x itself
+static std::vector<float> filtered(const Arguments& args, std::vector<float> x, const std::vector<float>& taps) {
+    if (taps.empty() || x.empty()) return x;
+    std::vector<float> y(x.size());
+    size_t n = 0;
+    if (am_fir(args.device, x.data(), x.size(), AM_FMT_F32_MONO, taps.data(), (std::uint32_t)taps.size(), 0, y.data(), y.size(), &n) != AM_OK)
+        throw std::runtime_error(std::string("am_fir: ") + am_last_error_string());
+    return y;
+}
+
+// The handle of a snippet (rate sr) for main files of rate m_sr: resampled when the rates differ (--resample), then
+// passed through the run's filter, if any.
+static am_needle* make_needle(const Arguments& args, const std::vector<float>& data, std::uint32_t sr, std::uint32_t m_sr,
+                              const std::vector<float>& taps) {
+    am_needle* h = nullptr;
+    if (taps.empty()) {
+        if (sr == m_sr) {
+            if (am_needle_create(args.device, data.data(), data.size(), &h) != AM_OK)
+                throw std::runtime_error(std::string("am_needle_create: ") + am_last_error_string());
+        } else if (am_needle_create_resampled(args.device, data.data(), data.size(), AM_FMT_F32_MONO, sr, m_sr, &h) != AM_OK) {
+            throw std::runtime_error(std::string("am_needle_create_resampled: ") + am_last_error_string());
+        }
+        return h;
+    }
+    std::vector<float> at_rate;
+    if (sr != m_sr) {
+        size_t n = 0;
+        if (am_resample_len(data.size(), sr, m_sr, &n) != AM_OK) throw std::runtime_error(std::string("am_resample_len: ") + am_last_error_string());
+        at_rate.resize(n);
+        if (am_resample(args.device, data.data(), data.size(), AM_FMT_F32_MONO, sr, m_sr, at_rate.data(), at_rate.size(), &n) != AM_OK)
+            throw std::runtime_error(std::string("am_resample: ") + am_last_error_string());
+    }
+    const std::vector<float>& x = sr != m_sr ? at_rate : data;
+    if (am_needle_create_filtered(args.device, x.data(), x.size(), AM_FMT_F32_MONO, taps.data(), (std::uint32_t)taps.size(), &h) != AM_OK)
+        throw std::runtime_error(std::string("am_needle_create_filtered: ") + am_last_error_string());
+    return h;
+}
+
 // extension: several --snippet files.  Each main file is matched by ONE am_match_multi_varlen call (the snippets may
 // differ in length: each uses an overlap of its own length at the main file's rate, as make_params does for one);
 // with --normalize, which that call refuses, snippet by snippet with am_match.  The label file is timelabel_from_peaks
@@ -149,6 +211,7 @@ static int run_multi(const Arguments& args) {
     try {
         if (args.normalize_floor_db && am_set_option("score_norm_floor_db", *args.normalize_floor_db) != AM_OK)
             throw std::runtime_error(std::string("--normalize-floor: ") + am_last_error_string());
+        const std::vector<float> taps = filter_taps(args);   // extension: --whiten / --preemphasis
         for (size_t j = 0; j < snips.size(); ++j) {
             Snip& sn = snips[j];
             const Pcm pcm = read_wav(args.snippets[j]);
@@ -156,8 +219,7 @@ static int run_multi(const Arguments& args) {
             sn.sr = pcm.sample_rate;
             sn.duration = (double)pcm.frames() / (double)sn.sr;
             sn.data = to_mono_f32(pcm, args.device);
-            if (am_needle_create(args.device, sn.data.data(), sn.data.size(), &sn.h) != AM_OK)
-                throw std::runtime_error(std::string("am_needle_create: ") + am_last_error_string());
+            sn.h = make_needle(args, sn.data, sn.sr, sn.sr, taps);
             if (args.normalize && am_needle_set_option(sn.h, "score_norm", 1) != AM_OK)
                 throw std::runtime_error(std::string("--normalize: ") + am_last_error_string());
         }
@@ -191,8 +253,7 @@ static int run_multi(const Arguments& args) {
                 if (m_sr != sn.sr) {
                     am_needle*& h = sn.resampled[m_sr];
                     if (!h) {
-                        if (am_needle_create_resampled(args.device, sn.data.data(), sn.data.size(), AM_FMT_F32_MONO, sn.sr, m_sr, &h) != AM_OK)
-                            throw std::runtime_error(std::string("am_needle_create_resampled: ") + am_last_error_string());
+                        h = make_needle(args, sn.data, sn.sr, m_sr, taps);
                         if (args.normalize && am_needle_set_option(h, "score_norm", 1) != AM_OK)
                             throw std::runtime_error(std::string("--normalize: ") + am_last_error_string());
                     }
@@ -203,7 +264,7 @@ static int run_multi(const Arguments& args) {
                 }
                 handles[j] = algo;
             }
-            const std::vector<float> m_samples = to_mono_f32(m, args.device);
+            const std::vector<float> m_samples = filtered(args, to_mono_f32(m, args.device), taps);
             const am_match_params p = make_params(args, m_sr, snips[0].duration);
             size_t cap = 1024;
             std::vector<am_peak> peaks(cap * k);
@@ -456,9 +517,8 @@ int main(int argc, char** argv) {
         const std::uint32_t sr = snippet.sample_rate;
         const double s_duration = (double)snippet.frames() / (double)sr;      // mod.rs:30 (mp3_duration)
         const std::vector<float> sample_data = to_mono_f32(snippet, args.device);   // mod.rs:32
-        am_needle* snippet_algo = nullptr;                                    // mod.rs:34: LibConvolve::new
-        if (am_needle_create(args.device, sample_data.data(), sample_data.size(), &snippet_algo) != AM_OK)
-            throw std::runtime_error(std::string("am_needle_create: ") + am_last_error_string());
+        const std::vector<float> taps = filter_taps(args);                    // extension: --whiten / --preemphasis
+        am_needle* snippet_algo = make_needle(args, sample_data, sr, sr, taps);   // mod.rs:34: LibConvolve::new
         if (args.normalize_floor_db && am_set_option("score_norm_floor_db", *args.normalize_floor_db) != AM_OK)
             throw std::runtime_error(std::string("--normalize-floor: ") + am_last_error_string());
         if (args.normalize && am_needle_set_option(snippet_algo, "score_norm", 1) != AM_OK)
@@ -487,15 +547,14 @@ int main(int argc, char** argv) {
             if (m.sample_rate != sr) {                                        // extension: --resample
                 am_needle*& h = resampled[m.sample_rate];
                 if (!h) {
-                    if (am_needle_create_resampled(args.device, sample_data.data(), sample_data.size(), AM_FMT_F32_MONO, sr, m.sample_rate, &h) != AM_OK)
-                        throw std::runtime_error(std::string("am_needle_create_resampled: ") + am_last_error_string());
+                    h = make_needle(args, sample_data, sr, m.sample_rate, taps);
                     if (args.normalize && am_needle_set_option(h, "score_norm", 1) != AM_OK)
                         throw std::runtime_error(std::string("--normalize: ") + am_last_error_string());
                 }
                 algo = h;
             }
             const std::uint32_t m_sr = m.sample_rate;
-            const std::vector<float> m_samples = to_mono_f32(m, args.device);
+            const std::vector<float> m_samples = filtered(args, to_mono_f32(m, args.device), taps);
             am_match_params p = make_params(args, m_sr, s_duration);          // mod.rs:81-87
             if (m_sr != sr) {                                                 // the overlap = the resampled snippet's length
                 size_t s_len = 0;

@@ -311,6 +311,15 @@ _SIGNATURES = {
                                      C.c_size_t, C.POINTER(C.c_size_t)]),
     "am_needle_create_resampled": (C.c_int, [C.c_int, C.c_void_p, C.c_size_t, C.c_int, C.c_uint32, C.c_uint32,
                                              C.POINTER(C.c_void_p)]),
+    "am_lag_products": (C.c_int, [C.c_int, C.c_void_p, C.c_size_t, C.c_int, C.c_uint32, C.POINTER(C.c_double)]),
+    "am_lag_products_device": (C.c_int, [C.c_int, C.c_void_p, C.c_size_t, C.c_int, C.c_uint32, C.POINTER(C.c_double)]),
+    "am_whiten_taps": (C.c_int, [C.POINTER(C.c_double), C.c_uint32, C.c_double, C.POINTER(C.c_float)]),
+    "am_fir": (C.c_int, [C.c_int, C.c_void_p, C.c_size_t, C.c_int, C.POINTER(C.c_float), C.c_uint32, C.c_size_t, C.c_void_p,
+                         C.c_size_t, C.POINTER(C.c_size_t)]),
+    "am_fir_device": (C.c_int, [C.c_int, C.c_void_p, C.c_size_t, C.c_int, C.POINTER(C.c_float), C.c_uint32, C.c_size_t,
+                                C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "am_needle_create_filtered": (C.c_int, [C.c_int, C.c_void_p, C.c_size_t, C.c_int, C.POINTER(C.c_float), C.c_uint32,
+                                            C.POINTER(C.c_void_p)]),
     "am_set_option": (C.c_int, [C.c_char_p, C.c_longlong]),
     "am_match_best": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.POINTER(AmBestParams), C.POINTER(AmPeak),
                                 C.POINTER(C.c_size_t)]),
@@ -512,6 +521,64 @@ def resample_device(device: int, src_ptr: int, n_in: int, src_rate: int, dst_rat
     got = C.c_size_t(0)
     _check(lib().am_resample_device(device, src_ptr, int(n_in), int(fmt), int(src_rate), int(dst_rate), dst_ptr, int(cap),
                                     C.byref(got)))
+    return got.value
+
+
+WHITEN_MAX_ORDER = 64                 # AM_WHITEN_MAX_ORDER
+FIR_MAX_TAPS = WHITEN_MAX_ORDER + 1   # AM_FIR_MAX_TAPS
+LAG_BLOCK = 8192                      # samples per block of the lag products (kLagBlock, csrc/am_kernels.h)
+FIR_TILE = 2048                       # outputs per workgroup of the FIR kernel (kFirTile, csrc/am_kernels.h)
+
+
+def lag_products(x, order: int, device: int = 0) -> np.ndarray:
+    """am_lag_products: r[k] = sum_i x~[i] x~[i - k], k = 0 .. order, in f64 (x: f32 mono, or int16 interleaved stereo;
+    non-finite samples count as 0).  Additive over files: add the r of an archive's files to design one filter."""
+    a, fmt, length = _samples(x)
+    r = np.zeros(int(order) + 1, dtype=np.float64)
+    _check(lib().am_lag_products(device, a.ctypes.data, length, int(fmt), int(order), r.ctypes.data_as(C.POINTER(C.c_double))))
+    return r
+
+
+def lag_products_device(device: int, src_ptr: int, n: int, order: int, fmt: int = Fmt.F32_MONO) -> np.ndarray:
+    """am_lag_products_device on a resident buffer; r comes back in host memory."""
+    r = np.zeros(int(order) + 1, dtype=np.float64)
+    _check(lib().am_lag_products_device(device, src_ptr, int(n), int(fmt), int(order), r.ctypes.data_as(C.POINTER(C.c_double))))
+    return r
+
+
+def whiten_taps(r, noise_db: float = 60.0) -> np.ndarray:
+    """am_whiten_taps (pure host function): the prediction-error filter a[0 .. order], a[0] = 1, of the lag products
+    r[0 .. order] (Levinson-Durbin in f64, r[0] raised by -noise_db of white noise), rounded to f32."""
+    r = np.ascontiguousarray(r, dtype=np.float64)
+    taps = np.zeros(max(r.size, 1), dtype=np.float32)
+    _check(lib().am_whiten_taps(r.ctypes.data_as(C.POINTER(C.c_double)), r.size - 1, float(noise_db),
+                                taps.ctypes.data_as(C.POINTER(C.c_float))))
+    return taps
+
+
+def _taps(taps):
+    t = np.ascontiguousarray(taps, dtype=np.float32)
+    return t, t.ctypes.data_as(C.POINTER(C.c_float))
+
+
+def fir(x, taps, lead: int = 0, device: int = 0) -> np.ndarray:
+    """am_fir: y[k] = sum_j taps[j] x[lead + k - j], k < len(x) - lead (x: f32 mono, or int16 interleaved stereo; x = 0
+    before its first sample); f32 mono out.  Filtering x[a - l:b] with lead = l = min(a, len(taps) - 1) gives
+    fir(x, taps)[a:b] bit for bit."""
+    a, fmt, length = _samples(x)
+    t, tp = _taps(taps)
+    out = np.empty(max(length - int(lead), 0), dtype=np.float32)
+    got = C.c_size_t(0)
+    _check(lib().am_fir(device, a.ctypes.data, length, int(fmt), tp, t.size, int(lead), out.ctypes.data, out.size, C.byref(got)))
+    return out
+
+
+def fir_device(device: int, src_ptr: int, n_in: int, taps, dst_ptr: int, cap: int, lead: int = 0,
+               fmt: int = Fmt.F32_MONO) -> int:
+    """am_fir_device on resident buffers; returns the output length."""
+    t, tp = _taps(taps)
+    got = C.c_size_t(0)
+    _check(lib().am_fir_device(device, src_ptr, int(n_in), int(fmt), tp, t.size, int(lead), dst_ptr, int(cap), C.byref(got)))
     return got.value
 
 
@@ -734,6 +801,22 @@ class HipConvolve:
         n = C.c_size_t(0)
         _check(lib().am_needle_len(self._h, C.byref(n)))
         self.sample_len = int(n.value)
+        if score_norm is not None:
+            self.set_option(OPT_SCORE_NORM, int(bool(score_norm)))
+        return self
+
+    @classmethod
+    def filtered(cls, needle, taps, device: int = 0, score_norm=None) -> "HipConvolve":
+        """am_needle_create_filtered: the needle (f32, or int16 interleaved stereo) passed through the FIR filter `taps`
+        (whiten_taps of the haystacks' lag_products, or a pre-emphasis [1, -alpha]); the same handle as
+        HipConvolve(fir(needle, taps)).  Every haystack it is matched against must pass through the same taps."""
+        a, fmt, length = _samples(needle)
+        t, tp = _taps(taps)
+        self = cls.__new__(cls)
+        self.device = device
+        self._h = C.c_void_p()
+        _check(lib().am_needle_create_filtered(device, a.ctypes.data, length, int(fmt), tp, t.size, C.byref(self._h)))
+        self.sample_len = int(length)
         if score_norm is not None:
             self.set_option(OPT_SCORE_NORM, int(bool(score_norm)))
         return self

@@ -246,6 +246,27 @@ extern "C" {
         device: c_int, needle: *const std::ffi::c_void, n: usize, sample_format: c_int, src_rate: u32, dst_rate: u32,
         out: *mut *mut AmNeedle,
     ) -> c_int;
+    /// spectral whitening (audiomatch.h): lag products, the prediction-error filter they give, a short FIR filter for
+    /// the needle and every haystack it is matched against (the reference has no such stage, audio_matcher.rs:297-343)
+    pub fn am_lag_products(
+        device: c_int, input: *const std::ffi::c_void, n: usize, sample_format: c_int, order: u32, r: *mut f64,
+    ) -> c_int;
+    pub fn am_lag_products_device(
+        device: c_int, d_in: *const std::ffi::c_void, n: usize, sample_format: c_int, order: u32, r: *mut f64,
+    ) -> c_int;
+    pub fn am_whiten_taps(r: *const f64, order: u32, noise_db: f64, taps: *mut f32) -> c_int;
+    pub fn am_fir(
+        device: c_int, input: *const std::ffi::c_void, n_in: usize, sample_format: c_int, taps: *const f32, n_taps: u32,
+        lead: usize, out: *mut f32, cap: usize, n_out: *mut usize,
+    ) -> c_int;
+    pub fn am_fir_device(
+        device: c_int, d_in: *const std::ffi::c_void, n_in: usize, sample_format: c_int, taps: *const f32, n_taps: u32,
+        lead: usize, d_out: *mut f32, cap: usize, n_out: *mut usize,
+    ) -> c_int;
+    pub fn am_needle_create_filtered(
+        device: c_int, needle: *const std::ffi::c_void, n: usize, sample_format: c_int, taps: *const f32, n_taps: u32,
+        out: *mut *mut AmNeedle,
+    ) -> c_int;
     /// per-hit scoring: exact NCC, gain, window level and sub-sample position of each hit (audiomatch.h)
     pub fn am_hit_scores(
         h: *const AmNeedle, haystack: *const std::ffi::c_void, len: usize, sample_format: c_int, peaks: *const AmPeak, n: usize,
@@ -462,6 +483,21 @@ impl HipConvolve {
             return Err(am_err(rc));
         }
         Ok(Self { h, len })
+    }
+
+    /// `LibConvolve::new` on a snippet passed through the FIR filter `taps` (am_needle_create_filtered): the whitening
+    /// filter designed from the haystacks (am_lag_products, am_whiten_taps) or a pre-emphasis `[1, -alpha]`.  Every
+    /// haystack it is matched against must pass through the same taps (am_fir); offsets do not move.
+    pub fn new_filtered(sample_data: &[f32], taps: &[f32]) -> Result<Self, Box<dyn std::error::Error>> {
+        let mut h = std::ptr::null_mut();
+        let rc = unsafe {
+            am_needle_create_filtered(0, sample_data.as_ptr() as *const std::ffi::c_void, sample_data.len(), AM_FMT_F32_MONO,
+                                      taps.as_ptr(), taps.len() as u32, &mut h)
+        };
+        if rc != AM_OK {
+            return Err(am_err(rc));
+        }
+        Ok(Self { h, len: sample_data.len() })
     }
 
     /// The same from decoded stereo PCM (`frame.data`, mp3_reader.rs:28): no CPU down-mix pass.

@@ -575,6 +575,75 @@ int am_resample_device(int device, const void* d_in, size_t n_in, int sample_for
 int am_needle_create_resampled(int device, const void* needle, size_t n, int sample_format, uint32_t src_rate,
                                uint32_t dst_rate, am_needle** out);
 
+/* ---- spectral whitening --------------------------------------------------- */
+/* The reference correlates the decoded samples as they are (audio_matcher.rs:297-343) and has no such stage.  Speech and
+ * music are low-pass material: a plain cross-correlation of such signals is dominated by their few loudest low
+ * frequencies, its peak is wide and unrelated programme scores a large fraction of a true hit.  The remedy is to pass
+ * the needle AND every haystack through one short prediction-error (whitening) filter before they are correlated.
+ * These entry points prepare the signals; every match, pool, streaming, monitor and per-hit entry point then works on
+ * the prepared signals unchanged.
+ *
+ * In all of them `in` is f32 mono, or for AM_FMT_S16_STEREO interleaved i16 stereo frames, down-mixed
+ * (l + r) * 0.5 * (1/65535) bit for bit as everywhere else; n counts samples, or frames for AM_FMT_S16_STEREO.
+ *
+ * What a caller must know:
+ *   One filter for all.  The needle and every haystack it is matched against must pass through the SAME taps.  Design
+ *     the filter from the haystacks (the programme), not from the needle: add the lag products of the files.
+ *   Offsets do not move: the filter is causal and applied to both sides.
+ *   Needle start.  The needle's first n_taps - 1 filtered samples see zero history, where its occurrence in a haystack
+ *     sees the programme before it.  That affects (n_taps - 1) / S of the needle (S = its length); at S = 4096 and
+ *     order 32 no loss was measured.
+ *   Scores.  Heights, NCC and per-hit records are those of the whitened signals.
+ *   Pre-emphasis.  A fixed pre-emphasis is just taps = {1, -alpha}. */
+#define AM_WHITEN_MAX_ORDER 64
+#define AM_FIR_MAX_TAPS     (AM_WHITEN_MAX_ORDER + 1)
+
+/* Lag products:  r[k] = sum_{i=k}^{n-1} x~[i] * x~[i-k],  k = 0 .. order;  x~ = x, with 0 for a non-finite sample.
+ * r: order + 1 doubles in host memory (both forms).
+ *   Every product is formed in f64, where a product of two f32 values is exact.  The sums run in one fixed order that
+ *   depends on n only: blocks of 8192 samples give one partial per lag each (a block reads the samples its lags reach
+ *   in front of its first one: the previous block's, nothing before index 0), and the partials are added in block order.
+ *   The host and the device form give the same bits, a device pointer of any 4-byte alignment gives the same bits, and
+ *   r[k] does not depend on the `order` asked for.
+ *   The products are additive: a caller designs one filter for a whole archive by adding the r of its files.
+ *   n = 0: all zeros, AM_OK, nothing launched.
+ *   AM_ERR_INVALID_ARG: order 0 or above AM_WHITEN_MAX_ORDER, an unknown sample format, a null pointer (in: with n > 0). */
+int am_lag_products(int device, const void* in, size_t n, int sample_format, uint32_t order, double* r);
+/* the same on a device pointer (resident on `device`); complete when the call returns */
+int am_lag_products_device(int device, const void* d_in, size_t n, int sample_format, uint32_t order, double* r);
+
+/* Pure host function (no device): the prediction-error filter a[0 .. order], a[0] = 1, of the lag products r[0 .. order]
+ * by the Levinson-Durbin recursion in f64, with r[0] replaced by r[0] * (1 + 10^(-noise_db / 10)) (the usual white-noise
+ * correction; noise_db in [0, 200], 60 is a good choice).  taps: order + 1 floats, each rounded to f32 once.
+ *   The recursion stops before step m when the prediction error has reached <= 0, and at step m when the reflection
+ *   coefficient has |k| >= 1 (or is not a number); the taps m .. order are then 0.  r[0] <= 0 (silence): the identity
+ *   {1, 0, ...}.  On white input the filter is (nearly) the identity.
+ *   AM_ERR_INVALID_ARG: a null pointer, order 0 or above AM_WHITEN_MAX_ORDER, a non-finite r[k], noise_db out of range. */
+int am_whiten_taps(const double* r, uint32_t order, double noise_db, float* taps);
+
+/* FIR filter:  y[k] = sum_{j < n_taps} taps[j] * x[lead + k - j],  k in [0, n_in - lead);  x = 0 before in[0].
+ * Host memory in and out.  *n_out receives the output length n_in - lead; on AM_ERR_CAPACITY (cap < n_out) nothing is
+ * written but *n_out.  n_in == lead: AM_OK, *n_out = 0, nothing launched.
+ *   Each output is accumulated in f32 from 0 with one fma per tap, in the order j = 0, 1, ...; every entry point gives
+ *   the same bits for the same input.  Non-finite samples spread, by IEEE arithmetic, to the n_taps outputs whose support
+ *   holds them and to no others; the matcher then drops exactly those windows, as for any haystack.
+ *   Pieces.  For any cut a < b, am_fir on x[a - l .. b) with lead = l = min(a, n_taps - 1) equals
+ *   am_fir(x, lead = 0)[a .. b) bit for bit (the launch geometry depends on n_taps and on the output index relative to
+ *   `lead` only): a streaming caller keeps n_taps - 1 samples of history and pushes the filtered pieces.
+ *   AM_ERR_INVALID_ARG: n_taps 0 or above AM_FIR_MAX_TAPS, a non-finite tap, lead > n_in, an unknown sample format, a
+ *   null pointer. */
+int am_fir(int device, const void* in, size_t n_in, int sample_format, const float* taps, uint32_t n_taps,
+           size_t lead, float* out, size_t cap, size_t* n_out);
+/* the same on device pointers (resident on `device`, not overlapping; taps in host memory); complete when the call
+ * returns */
+int am_fir_device(int device, const void* d_in, size_t n_in, int sample_format, const float* taps, uint32_t n_taps,
+                  size_t lead, float* d_out, size_t cap, size_t* n_out);
+/* LibConvolve::new(sample_data) (audio_matcher.rs:289) on a filtered needle: the handle am_needle_create gives on
+ * am_fir(needle, lead = 0)'s output, bit for bit (am_needle_len reports n).  Pools keep their own am_pool_create*: pass
+ * them am_fir's output. */
+int am_needle_create_filtered(int device, const void* needle, size_t n, int sample_format,
+                              const float* taps, uint32_t n_taps, am_needle** out);
+
 /* ---- device memory plumbing (for hosts without their own HIP allocator) -- */
 int am_device_malloc(int device, size_t bytes, void** out);
 int am_device_free(int device, void* p);

@@ -77,6 +77,30 @@ inline std::vector<float> resample(const void* x, std::size_t n, int sample_form
     return out;
 }
 
+// spectral whitening (audiomatch.h, "spectral whitening"): x is f32 mono, or interleaved i16 stereo with
+// AM_FMT_S16_STEREO; n samples / frames.  The needle and every haystack it is matched against pass through the SAME taps.
+// am_lag_products: r[k] = sum_i x[i] x[i - k], k = 0 .. order, in f64 (additive over the files of an archive)
+inline std::vector<double> lag_products(const void* x, std::size_t n, int sample_format, std::uint32_t order, int device = 0) {
+    std::vector<double> r(static_cast<std::size_t>(order) + 1);
+    check(am_lag_products(device, x, n, sample_format, order, r.data()));
+    return r;
+}
+// am_whiten_taps (pure host): the prediction-error filter a[0 .. order], a[0] = 1, of the lag products r[0 .. order]
+inline std::vector<float> whiten_taps(const std::vector<double>& r, double noise_db = 60.0) {
+    std::vector<float> taps(r.empty() ? 1 : r.size());
+    check(am_whiten_taps(r.data(), static_cast<std::uint32_t>(taps.size() - 1), noise_db, taps.data()));
+    return taps;
+}
+// am_fir: y[k] = sum_j taps[j] x[lead + k - j], k < n - lead; a signal filtered in pieces (lead = the history kept, up to
+// taps.size() - 1 samples) gives the bits of the signal filtered whole
+inline std::vector<float> fir(const void* x, std::size_t n, int sample_format, const std::vector<float>& taps, std::size_t lead = 0,
+                              int device = 0) {
+    std::vector<float> out(n >= lead ? n - lead : 0);
+    std::size_t len = 0;
+    check(am_fir(device, x, n, sample_format, taps.data(), static_cast<std::uint32_t>(taps.size()), lead, out.data(), out.size(), &len));
+    return out;
+}
+
 // trait CorrelateAlgo<f32> (audio_matcher.rs:65-76)
 // option keys of window-energy normalised scores (audiomatch.h): HipConvolve::set_option(kOptScoreNorm, 1) for NCC
 // on one handle, am_set_option for the process default and the floor
@@ -106,6 +130,11 @@ public:
     // frames) brought from src_rate to the haystack's dst_rate
     HipConvolve(const void* needle, std::size_t n, int sample_format, std::uint32_t src_rate, std::uint32_t dst_rate, int device = 0) {
         check(am_needle_create_resampled(device, needle, n, sample_format, src_rate, dst_rate, &h_));
+    }
+    // am_needle_create_filtered: the needle passed through the FIR filter `taps` (whiten_taps of the haystacks' lag
+    // products, or a pre-emphasis {1, -alpha}); the haystacks pass through the same taps (fir)
+    HipConvolve(const void* needle, std::size_t n, int sample_format, const std::vector<float>& taps, int device = 0) {
+        check(am_needle_create_filtered(device, needle, n, sample_format, taps.data(), static_cast<std::uint32_t>(taps.size()), &h_));
     }
     HipConvolve(const HipConvolve&) = delete;
     HipConvolve& operator=(const HipConvolve&) = delete;
