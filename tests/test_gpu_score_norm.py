@@ -5,81 +5,12 @@ import ctypes as C
 import numpy as np
 import pytest
 
+from score_norm_ref import assert_peaks, bits, chunks, match_ref, ncc_ref, overshadow_filter  # noqa: F401
+
 pytestmark = pytest.mark.gpu
 
 SR = 8000
 UNSUPPORTED = "score_norm: not supported by this entry point"
-
-
-# ---- the checker ---------------------------------------------------------------------------------------------------
-def ncc_ref(oracle, within, needle, mode, floor_db=60):
-    """Level 1: NCC of every output of `mode`, zero padding as the correlation's."""
-    w, s = len(within), len(needle)
-    x = np.asarray(within, dtype=np.float32)
-    xc = np.where(np.isfinite(x), x, 0).astype(np.float32)
-    raw = oracle.correlate(xc, needle, mode, oracle.SCALE_NONE, prec=oracle.PREC_F64).astype(np.float64)
-    n = len(raw)
-    full = w + s - 1
-    lead = (s - 1) - (full - n) // 2
-    x2 = np.concatenate([np.zeros(max(lead, 0)), xc.astype(np.float64) ** 2, np.zeros(s + n)])
-    c = np.concatenate([[0.0], np.cumsum(x2)])
-    t = np.arange(n) + (max(lead, 0) - lead)
-    ew = c[t + s] - c[t]
-    en = float(np.sum(np.asarray(needle, dtype=np.float64) ** 2))
-    thr = en * 10.0 ** (-floor_db / 10.0)
-    ok = ew >= thr
-    out = np.zeros(n)
-    out[ok] = raw[ok] / np.sqrt(en * ew[ok])
-    return out, ew, thr
-
-
-def chunks(length, s, chunk, overlap, tail_window=0):
-    window = chunk + overlap
-    off = 0
-    while off < length:
-        w = min(window, length - off)
-        if w >= s and not (tail_window and w < window):
-            yield off, w
-        off += chunk
-
-
-def overshadow_filter(oracle, peaks, sr, dist_s):
-    peaks = sorted(peaks, key=lambda q: q[0])
-    out = []
-    for i, q in enumerate(peaks):
-        before = peaks[i - 1] if i > 0 else None
-        after = peaks[i + 1] if i + 1 < len(peaks) else None
-        if oracle.is_overshadowed(q, before, sr, dist_s) or oracle.is_overshadowed(q, after, sr, dist_s):
-            continue
-        out.append(q)
-    return out
-
-
-def match_ref(oracle, hay, needle, p, floor_db=60, tail_window=0, only=None):
-    """Level 2: per chunk as calc_chunks, on NCC scores; chunks whose window holds a non-finite sample are dropped.
-    only: restrict the check to chunks whose offset is in this set (the rest are assumed peak-free)."""
-    s = len(needle)
-    bad = np.flatnonzero(~np.isfinite(hay))
-    peaks = []
-    for off, w in chunks(len(hay), s, p.chunk, p.overlap, tail_window):
-        if only is not None and off not in only:
-            continue
-        if np.any((bad >= off) & (bad < off + w)):
-            continue
-        y, _, _ = ncc_ref(oracle, hay[off:off + w], needle, oracle.MODE_VALID, floor_db)
-        for a, b, h, pr in oracle.find_peaks(y.astype(np.float32), p.min_prominence, p.min_distance):
-            peaks.append((a + off, b + off, h, pr))
-    return overshadow_filter(oracle, peaks, p.sr, p.overshadow_distance_s)
-
-
-def assert_peaks(got, exp, tol=1e-4):
-    assert [(g.start, g.end) for g in got] == [(e[0], e[1]) for e in exp], (got, exp)
-    for g, e in zip(got, exp):
-        assert abs(g.height - e[2]) <= tol and abs(g.prominence - e[3]) <= tol, (g, e)
-
-
-def bits(peaks):
-    return [(q.start, q.end, np.float32(q.height).tobytes(), np.float32(q.prominence).tobytes()) for q in peaks]
 
 
 @pytest.fixture
