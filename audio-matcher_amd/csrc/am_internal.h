@@ -575,6 +575,10 @@ int hit_round_trip(Ctx* c, const std::vector<Desc>& hits, size_t part_bytes, siz
     return AM_OK;
 }
 
+// ---- am_estimate.hip ----
+// slots of the sorting network a call with n rows runs: 0 for AM_EST_MEAN (no sort), else 8, 16, 32 or 64; -1: too many rows
+int estimate_slots(int method, int n);
+
 // ---- am_correlate.hip ----
 int plan_geometry(size_t s, long long out_count, const Opts& o, Geometry* g);
 bool plan_fuses_scan(const PlanDev& pl, const Geometry& g);   // K3 of this plan, at this hop, carries the score scan

@@ -428,4 +428,29 @@ struct FirJob {
 };
 hipError_t launch_fir(hipStream_t st, const FirJob& j, int kind);
 
+// ---- am_estimate.hip: needle estimation (am_needle_estimate_*) ----
+// One row of the gather form, as the kernel reads it (the call's table, uploaded once): element n of the row is
+// fl32(x[off + n] * scale), absent where off + n lies outside [0, len)
+struct EstHit {
+    const void* src;      // device: element 0 of the hit's haystack (f32 mono, or i16 stereo frames); readable even where len = 0
+    long long len;        // its length in samples / frames
+    long long off;        // start - lead (may be negative)
+    float scale;
+    int pad;
+};
+// One launch: output sample n < length from rows 0 .. n - 1, in this order
+struct EstJob {
+    const void* src;      // device: n x length f32, row-major (source 0), or the table of n EstHit (sources 1, 2)
+    long long length;
+    int n;
+    int method;           // AM_EST_*
+    unsigned trim_permille;
+    float* est;           // device, length entries each; dev and count may be null
+    float* dev;
+    unsigned* count;
+};
+// src: 0 = rows, 1 = hit table over f32 mono haystacks, 2 = over i16 stereo haystacks.  Runs the mean kernel, or the
+// smallest sorting network (8, 16, 32, 64 slots) that holds j.n rows; hipErrorInvalidValue where there is none
+hipError_t launch_estimate(hipStream_t st, const EstJob& j, int src);
+
 }  // namespace am

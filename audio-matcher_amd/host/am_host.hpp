@@ -84,6 +84,10 @@ struct Arguments {
     bool resample = false;                    // extension: --resample, bring the snippet to each main file's rate (am_needle_create_resampled)
     std::uint32_t whiten = 0;                 // extension: --whiten P, one order-P whitening filter designed from all main files (am_lag_products, am_whiten_taps), 0 = off
     std::optional<float> preemphasis;         // extension: --preemphasis A, the fixed filter {1, -A} on snippets and main files (am_fir)
+    std::string learn_needle;                 // extension: --learn-needle OUT.wav[:METHOD], a cleaner snippet estimated from the run's hits (am_needle_estimate_rows); empty = off
+    std::uint32_t learn_method = AM_EST_MEDIAN;   // ... :mean | :median | :trimmed=P
+    std::uint32_t learn_trim = 0;             // ... P of trimmed=P, in 1/1000 (0..500)
+    std::optional<std::uint64_t> learn_margin_ms;   // ... --learn-margin D: read D in front of and behind the snippet as well (default 0)
     std::optional<std::uint64_t> best;        // extension: --best N, the N best hits per main file, no prominence threshold (am_match_best)
     bool live = false;                        // extension: --live, raw PCM from stdin through a monitor (am_monitor_*)
     std::uint32_t rate = 0;                   // --live: --rate R (samples per second of the stream)
@@ -151,6 +155,18 @@ inline const char* usage_text() {
            "                         scores are those of the whitened signals.  Does not apply with --live\n"
            "  --preemphasis A        the fixed filter y[i] = x[i] - A x[i-1] (0 < A < 1) on the snippets and on every main\n"
            "                         file instead; not together with --whiten.  Does not apply with --live\n"
+           "  --learn-needle OUT.wav[:mean|median|trimmed=P]\n"
+           "                         after the run, write a cleaner snippet estimated from its hits: every reported hit of\n"
+           "                         every main file is brought to the snippet's level (1 / gain of its exact score),\n"
+           "                         the hits are stacked and each sample becomes their median (default), their mean, or\n"
+           "                         their mean without the P permille (0..500) largest and smallest values; what lies over\n"
+           "                         fewer than half of the hits is gone from a median.  OUT.wav is mono 32-bit float at\n"
+           "                         the main files' rate (one rate for all) and can be the next run's --snippet.  Median\n"
+           "                         and trimmed use the 64 hits of highest NCC.  One line per second of the result shows\n"
+           "                         the spread between the hits relative to the result's peak: where they agree.  One\n"
+           "                         --snippet only; not with --live, --best, --whiten or --preemphasis\n"
+           "  --learn-margin D       with --learn-needle: also read D (a duration, default 0) in front of and behind the\n"
+           "                         snippet; the spread shows where the jingle really begins and ends\n"
            "  --live                 read raw PCM from stdin instead of files (no FILE arguments): a live feed, matched\n"
            "                         as it arrives; each hit's offset line is printed (and flushed) as soon as it is\n"
            "                         final -- a hit is final once the next hit is found, or once --distance of audio\n"
@@ -272,6 +288,26 @@ inline Arguments parse_arguments(int argc, const char* const* argv) {
                 throw ArgError("invalid value '" + v + "' for --preemphasis (a number with 0 < A < 1)");
             a.preemphasis = x;
         }
+        else if (s == "--learn-needle") {
+            const std::string v = need(i);
+            const std::size_t colon = v.rfind(':');
+            a.learn_needle = v.substr(0, colon);
+            const std::string m = colon == std::string::npos ? "median" : v.substr(colon + 1);
+            bool ok = !a.learn_needle.empty();
+            if (m == "median") a.learn_method = AM_EST_MEDIAN;
+            else if (m == "mean") a.learn_method = AM_EST_MEAN;
+            else if (m.rfind("trimmed=", 0) == 0) {
+                const std::string t = m.substr(8);
+                char* end = nullptr;
+                const unsigned long pm = std::strtoul(t.c_str(), &end, 10);
+                ok = ok && !t.empty() && t[0] >= '0' && t[0] <= '9' && *end == '\0' && pm <= 500;
+                a.learn_method = AM_EST_TRIMMED;
+                a.learn_trim = (std::uint32_t)pm;
+            }
+            else ok = false;
+            if (!ok) throw ArgError("invalid value '" + v + "' for --learn-needle (OUT.wav[:mean|median|trimmed=P], P in 0..500 permille)");
+        }
+        else if (s == "--learn-margin") a.learn_margin_ms = dur(need(i), "--learn-margin");
         else if (s == "--best") {
             const std::string v = need(i);
             char* end = nullptr;
@@ -304,6 +340,13 @@ inline Arguments parse_arguments(int argc, const char* const* argv) {
     }
     if (a.snippet.empty()) throw ArgError("--snippet <FILE> is required");
     if (a.whiten && a.preemphasis) throw ArgError("--whiten and --preemphasis are mutually exclusive");
+    if (a.learn_margin_ms && a.learn_needle.empty()) throw ArgError("--learn-margin needs --learn-needle");
+    if (!a.learn_needle.empty()) {
+        if (a.live) throw ArgError("--live: --learn-needle does not apply");
+        if (a.best) throw ArgError("--learn-needle and --best are mutually exclusive");
+        if (a.snippets.size() > 1) throw ArgError("--learn-needle takes one --snippet only");
+        if (a.whiten || a.preemphasis) throw ArgError("--learn-needle does not apply with --whiten or --preemphasis (the hits would be those of the filtered signal)");
+    }
     if (a.live) {
         if (!a.within.empty()) throw ArgError("--live reads stdin: no FILE arguments");
         if (a.rate == 0) throw ArgError("--live needs --rate");
@@ -369,6 +412,21 @@ inline Pcm read_wav(const std::string& path) {
         }
     }
     throw std::runtime_error("'" + path + "' has no data chunk");
+}
+
+// mono 32-bit float WAV (format 3, with the fact chunk non-PCM formats carry): what read_wav reads back as is_float
+inline void write_wav_f32(const std::string& path, const std::vector<float>& x, std::uint32_t sample_rate) {
+    std::ofstream f(path, std::ios::binary | std::ios::trunc);
+    if (!f) throw std::runtime_error("couldn't write file '" + path + "'");
+    const std::uint32_t data = (std::uint32_t)(x.size() * 4), n = (std::uint32_t)x.size(), riff = 4 + (8 + 16) + (8 + 4) + (8 + data);
+    const std::uint32_t fmt_size = 16, fact_size = 4, byte_rate = sample_rate * 4;
+    const std::uint16_t format = 3, channels = 1, block = 4, bits = 32;
+    auto put = [&](const void* p, std::size_t k) { f.write(static_cast<const char*>(p), (std::streamsize)k); };
+    put("RIFF", 4); put(&riff, 4); put("WAVE", 4);
+    put("fmt ", 4); put(&fmt_size, 4); put(&format, 2); put(&channels, 2); put(&sample_rate, 4); put(&byte_rate, 4); put(&block, 2); put(&bits, 2);
+    put("fact", 4); put(&fact_size, 4); put(&n, 4);
+    put("data", 4); put(&data, 4); put(x.data(), data);
+    if (!f) throw std::runtime_error("couldn't write file '" + path + "'");
 }
 
 // f32 mono samples as the matcher sees them: stereo i16 goes through the GPU

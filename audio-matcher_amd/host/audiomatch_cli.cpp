@@ -126,6 +126,73 @@ static size_t significance_filter(const Arguments& args, const am_needle* algo, 
     return kept;
 }
 
+// extension: --learn-needle OUT.wav[:METHOD] [--learn-margin D].  The reported hits of every main file, each as one row
+// cut while its file is in memory (am_hit_window: scale = 1 / gain of am_hit_scores, the margin in front and behind);
+// at the end of the run one am_needle_estimate_rows over the rows, the estimate written as a mono float WAV and one line
+// per second of it with the mean of dev / max|est|.
+struct Learner {
+    struct Row { float ncc; std::vector<float> v; };
+    std::vector<Row> rows;          // in the order the hits were reported; once over the cap, the best by NCC, best first
+    std::uint32_t sr = 0;           // the main files' rate
+    std::uint64_t length = 0;       // elements per row
+    bool capped = false;
+
+    size_t cap(const Arguments& args) const { return args.learn_method == AM_EST_MEAN ? 65535 : AM_EST_MAX_HITS; }
+
+    void take(const Arguments& args, const am_needle* algo, const std::vector<float>& samples, std::uint32_t m_sr, const am_peak* peaks, size_t n) {
+        if (n == 0) return;
+        size_t s_len = 0;
+        am_needle_len(algo, &s_len);
+        const std::uint64_t lead = round_samples_ms(args.learn_margin_ms.value_or(0), m_sr), len = s_len + 2 * lead;
+        if (rows.empty() && !capped) { sr = m_sr; length = len; }
+        if (m_sr != sr || len != length) throw std::runtime_error("--learn-needle: the main files must share one sample rate");
+        std::vector<am_hit_score> sc(n);
+        if (am_hit_scores(algo, samples.data(), samples.size(), AM_FMT_F32_MONO, peaks, n, sc.data()) != AM_OK)
+            throw std::runtime_error(std::string("am_hit_scores: ") + am_last_error_string());
+        for (size_t i = 0; i < n; ++i) {
+            if ((sc[i].flags & (AM_HIT_NONFINITE | AM_HIT_BELOW_FLOOR)) || !(sc[i].gain > 0.0f)) continue;
+            const float scale = 1.0f / sc[i].gain;
+            if (!std::isfinite(scale)) continue;
+            Row r{sc[i].ncc, std::vector<float>((size_t)length)};
+            if (am_hit_window(samples.data(), samples.size(), AM_FMT_F32_MONO, peaks[i].start, scale, lead, length, r.v.data()) != AM_OK)
+                throw std::runtime_error(std::string("am_hit_window: ") + am_last_error_string());
+            rows.push_back(std::move(r));
+        }
+        if (rows.size() > cap(args)) {
+            std::stable_sort(rows.begin(), rows.end(), [](const Row& a, const Row& b) { return a.ncc > b.ncc; });
+            rows.resize(cap(args));
+            capped = true;
+        }
+    }
+
+    int finish(const Arguments& args) const {
+        if (rows.empty()) {
+            std::fprintf(stderr, "--learn-needle: no usable hit, '%s' not written\n", args.learn_needle.c_str());
+            return 5;
+        }
+        if (capped)
+            std::fprintf(stderr, "--learn-needle: more than %zu usable hits, the %zu of highest NCC are used\n", cap(args), cap(args));
+        std::vector<float> flat(rows.size() * (size_t)length), est((size_t)length), dev((size_t)length);
+        for (size_t i = 0; i < rows.size(); ++i) std::copy(rows[i].v.begin(), rows[i].v.end(), flat.begin() + (std::ptrdiff_t)(i * (size_t)length));
+        const am_estimate_params ep{args.learn_method, args.learn_trim, 0, length};
+        if (am_needle_estimate_rows(args.device, flat.data(), rows.size(), &ep, est.data(), dev.data(), nullptr) != AM_OK)
+            throw std::runtime_error(std::string("am_needle_estimate_rows: ") + am_last_error_string());
+        write_wav_f32(args.learn_needle, est, sr);
+        if (args.verbosity >= 1) {
+            float peak = 0.0f;
+            for (float v : est) peak = std::max(peak, std::fabs(v));
+            std::printf("learned needle: %zu hits, %" PRIu64 " samples at %u Hz -> '%s'\n", rows.size(), length, sr, args.learn_needle.c_str());
+            for (std::uint64_t t0 = 0, k = 0; t0 < length; t0 += sr, ++k) {
+                const std::uint64_t t1 = std::min<std::uint64_t>(length, t0 + sr);
+                double sum = 0.0;
+                for (std::uint64_t t = t0; t < t1; ++t) sum += dev[(size_t)t];
+                std::printf("  second %" PRIu64 ": spread %.4f\n", k, peak > 0.0f ? sum / (double)(t1 - t0) / (double)peak : 0.0);
+            }
+        }
+        return 0;
+    }
+};
+
 // extension: --whiten P / --preemphasis A.  The taps of the ONE filter every snippet and every main file of the run passes
 // through before matching (empty: none).  --whiten: the lag products of all main files are added (am_lag_products), the
 // filter is their prediction-error filter of order P with noise_db 60 (am_whiten_taps); --preemphasis: {1, -A}.
@@ -527,6 +594,7 @@ int main(int argc, char** argv) {
         std::map<std::uint32_t, am_needle*> resampled;
         if (args.verbosity >= 2) am_set_progress_callback(progress, nullptr);
         int rc_all = 0;
+        Learner learner;                                                      // extension: --learn-needle
         for (const std::string& main_file : args.within) {                    // mod.rs:42
             std::optional<std::string> out_path = args.out_file;
             if (!out_path && !args.no_out) out_path = auto_out_file(main_file);
@@ -589,6 +657,7 @@ int main(int argc, char** argv) {
                 n = kept;
             }
             if (args.min_significance) n = significance_filter(args, algo, m_samples, m_sr, peaks.data(), n, "");   // extension: --min-significance
+            if (!args.learn_needle.empty()) learner.take(args, algo, m_samples, m_sr, peaks.data(), n);           // extension: --learn-needle
             if (args.verbosity >= 1) {
                 const std::vector<std::string> lines = offset_lines(peaks.data(), n, m_sr);                       // mod.rs:89
                 const std::vector<std::string> segs =
@@ -611,6 +680,10 @@ int main(int argc, char** argv) {
                     f << text;
                 }
             }
+        }
+        if (!args.learn_needle.empty()) {
+            const int rc = learner.finish(args);
+            if (rc) rc_all = rc;
         }
         am_needle_destroy(snippet_algo);
         for (auto& kv : resampled) am_needle_destroy(kv.second);

@@ -131,6 +131,23 @@ AM_HIT_NO_BACKGROUND, AM_HIT_FLAT_BACKGROUND, AM_HIT_CLIPPED = 16, 32, 64
 AM_SIG_MAX_RADIUS = 1 << 22
 
 
+class AmEstimateParams(C.Structure):   # am_estimate_params (include/audiomatch.h, needle estimation)
+    _fields_ = [("method", C.c_uint32), ("trim_permille", C.c_uint32), ("lead", C.c_uint64), ("length", C.c_uint64)]
+
+
+class AmEstHit(C.Structure):           # am_est_hit: one occurrence in a resident haystack
+    _fields_ = [("start", C.c_uint64), ("haystack", C.c_uint32), ("scale", C.c_float)]
+
+
+class Est(enum.IntEnum):               # AM_EST_*
+    MEAN = 0
+    MEDIAN = 1
+    TRIMMED = 2
+
+
+EST_MAX_HITS = 64                      # AM_EST_MAX_HITS
+
+
 class AmMatchParams(C.Structure):
     _fields_ = [("sr", C.c_uint32), ("chunk", C.c_uint64), ("overlap", C.c_uint64),
                 ("min_prominence", C.c_float), ("min_distance", C.c_uint64),
@@ -320,6 +337,12 @@ _SIGNATURES = {
                                 C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]),
     "am_needle_create_filtered": (C.c_int, [C.c_int, C.c_void_p, C.c_size_t, C.c_int, C.POINTER(C.c_float), C.c_uint32,
                                             C.POINTER(C.c_void_p)]),
+    "am_hit_window": (C.c_int, [C.c_void_p, C.c_size_t, C.c_int, C.c_uint64, C.c_float, C.c_uint64, C.c_uint64, C.c_void_p]),
+    "am_needle_estimate_rows": (C.c_int, [C.c_int, C.c_void_p, C.c_size_t, C.POINTER(AmEstimateParams), C.c_void_p, C.c_void_p,
+                                          C.c_void_p]),
+    "am_needle_estimate_device": (C.c_int, [C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.c_size_t, C.c_int,
+                                            C.POINTER(AmEstHit), C.c_size_t, C.POINTER(AmEstimateParams), C.c_void_p, C.c_void_p,
+                                            C.c_void_p]),
     "am_set_option": (C.c_int, [C.c_char_p, C.c_longlong]),
     "am_match_best": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.POINTER(AmBestParams), C.POINTER(AmPeak),
                                 C.POINTER(C.c_size_t)]),
@@ -580,6 +603,47 @@ def fir_device(device: int, src_ptr: int, n_in: int, taps, dst_ptr: int, cap: in
     got = C.c_size_t(0)
     _check(lib().am_fir_device(device, src_ptr, int(n_in), int(fmt), tp, t.size, int(lead), dst_ptr, int(cap), C.byref(got)))
     return got.value
+
+
+def hit_window(haystack, start: int, scale: float, lead: int, length: int) -> np.ndarray:
+    """am_hit_window (pure host function): the row of one occurrence, element n = fl32(x[start - lead + n] * scale) of the
+    host haystack x (f32 mono, or int16 interleaved stereo); NaN where that element lies outside x or is not finite."""
+    a, fmt, n = _samples(haystack)
+    row = np.empty(int(length), dtype=np.float32)
+    _check(lib().am_hit_window(a.ctypes.data, n, int(fmt), int(start), float(scale), int(lead), int(length), row.ctypes.data))
+    return row
+
+
+def _estimate_out(length: int):
+    return np.empty(length, dtype=np.float32), np.empty(length, dtype=np.float32), np.empty(length, dtype=np.uint32)
+
+
+def estimate_needle(rows, method: int = Est.MEDIAN, trim_permille: int = 0, device: int = 0):
+    """am_needle_estimate_rows: (est, dev, count) of the stacked occurrences rows[i] (n x length f32, a non-finite element
+    is absent): the per-sample mean, median or trimmed mean, the spread around it and the number of values it rests on."""
+    r = np.ascontiguousarray(rows, dtype=np.float32)
+    if r.ndim != 2:
+        raise ValueError("rows must be a 2-d array (n x length)")
+    ep = AmEstimateParams(int(method), int(trim_permille), 0, r.shape[1])
+    est, dev, count = _estimate_out(r.shape[1])
+    _check(lib().am_needle_estimate_rows(device, r.ctypes.data, r.shape[0], C.byref(ep), est.ctypes.data, dev.ctypes.data,
+                                         count.ctypes.data))
+    return est, dev, count
+
+
+def estimate_needle_device(device: int, ptrs, lengths, hits, lead: int, length: int, method: int = Est.MEDIAN,
+                           trim_permille: int = 0, fmt: int = Fmt.F32_MONO):
+    """am_needle_estimate_device: the same from hits = [(haystack index, start, scale), ...] in the resident haystacks
+    ptrs[k] (lengths[k] samples / frames); element n of a hit's row reads haystack element start - lead + n."""
+    n_hay = len(ptrs)
+    pp = (C.c_void_p * max(n_hay, 1))(*ptrs)
+    ll = (C.c_size_t * max(n_hay, 1))(*[int(v) for v in lengths])
+    hh = (AmEstHit * max(len(hits), 1))(*[AmEstHit(int(start), int(k), float(scale)) for k, start, scale in hits])
+    ep = AmEstimateParams(int(method), int(trim_permille), int(lead), int(length))
+    est, dev, count = _estimate_out(int(length))
+    _check(lib().am_needle_estimate_device(device, pp, ll, n_hay, int(fmt), hh, len(hits), C.byref(ep), est.ctypes.data,
+                                           dev.ctypes.data, count.ctypes.data))
+    return est, dev, count
 
 
 def find_peaks(y_data, min_prominence: float, min_distance: int = 0, device: int = 0, cap: int = 65536):

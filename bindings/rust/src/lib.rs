@@ -44,6 +44,29 @@ pub struct AmHitScore {
     pub flags: u32,
 }
 /// am_segment_params: per-segment hit scoring (am_hit_segments*)
+/// am_estimate_params (needle estimation, 24 bytes): method AM_EST_*, trim_permille 0..500, the margin read in front of
+/// each hit and the row length
+#[repr(C)]
+#[derive(Clone, Copy, Default, Debug)]
+pub struct AmEstimateParams {
+    pub method: u32,
+    pub trim_permille: u32,
+    pub lead: u64,
+    pub length: u64,
+}
+/// am_est_hit: one occurrence in a resident haystack (16 bytes); scale = 1 / gain of am_hit_scores
+#[repr(C)]
+#[derive(Clone, Copy, Default, Debug)]
+pub struct AmEstHit {
+    pub start: u64,
+    pub haystack: u32,
+    pub scale: f32,
+}
+pub const AM_EST_MEAN: u32 = 0;
+pub const AM_EST_MEDIAN: u32 = 1;
+pub const AM_EST_TRIMMED: u32 = 2;
+pub const AM_EST_MAX_HITS: usize = 64;
+
 #[repr(C)]
 #[derive(Clone, Copy, Default, Debug)]
 pub struct AmSegmentParams {
@@ -266,6 +289,19 @@ extern "C" {
     pub fn am_needle_create_filtered(
         device: c_int, needle: *const std::ffi::c_void, n: usize, sample_format: c_int, taps: *const f32, n_taps: u32,
         out: *mut *mut AmNeedle,
+    ) -> c_int;
+    /// needle estimation (audiomatch.h): a clean needle from the hits of a rough one -- rows of aligned occurrences, their
+    /// per-sample mean, median or trimmed mean, the spread around it (the reference has no such stage, audio_matcher.rs:289)
+    pub fn am_hit_window(
+        haystack: *const std::ffi::c_void, len: usize, sample_format: c_int, start: u64, scale: f32, lead: u64, length: u64,
+        row: *mut f32,
+    ) -> c_int;
+    pub fn am_needle_estimate_rows(
+        device: c_int, rows: *const f32, n: usize, ep: *const AmEstimateParams, est: *mut f32, dev: *mut f32, count: *mut u32,
+    ) -> c_int;
+    pub fn am_needle_estimate_device(
+        device: c_int, d_haystacks: *const *const std::ffi::c_void, lens: *const usize, n_hay: usize, sample_format: c_int,
+        hits: *const AmEstHit, n: usize, ep: *const AmEstimateParams, est: *mut f32, dev: *mut f32, count: *mut u32,
     ) -> c_int;
     /// per-hit scoring: exact NCC, gain, window level and sub-sample position of each hit (audiomatch.h)
     pub fn am_hit_scores(

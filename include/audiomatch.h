@@ -644,6 +644,73 @@ int am_fir_device(int device, const void* d_in, size_t n_in, int sample_format, 
 int am_needle_create_filtered(int device, const void* needle, size_t n, int sample_format,
                               const float* taps, uint32_t n_taps, am_needle** out);
 
+/* ---- needle estimation: a clean needle from the hits of a rough one ---------- */
+/* The reference matches with the snippet as it was cut (LibConvolve::new, audio_matcher.rs:289) and has no such stage.
+ * A needle cut by hand out of one broadcast carries what lay over the jingle that day.  After a first archive run the
+ * caller holds a few dozen occurrences of the same jingle, each under different material, each with a known offset
+ * (am_match*) and a known gain (am_hit_scores): stacked and aligned, a robust per-sample estimate of them is the jingle
+ * itself.  A median over nine occurrences removes whatever lies over fewer than half of them; a mean only dilutes it.
+ *
+ * Rows.  A row is `length` f32 values for one occurrence.  For a hit with `start` and `scale` and the call's `lead`, row
+ *   element n (0 <= n < length) reads haystack element e = start - lead + n:  v = fl32(x[e] * scale), one f32 multiply,
+ *   x the f32 sample (for AM_FMT_S16_STEREO the down-mix (l + r) * 0.5 * (1/65535), bit for bit as everywhere else).
+ *   The element is ABSENT when e lies outside [0, len) or x[e] is not finite.  In a row buffer an absent element is any
+ *   non-finite value (a product that overflows is therefore absent as well); NaN is what the library writes.
+ *   scale = 1 / gain of am_hit_scores brings every occurrence to the needle's level.
+ * For output sample n: P_n = the present values over the hits, in hit order; c_n = |P_n|.
+ * Total order.  Where values are ordered, the order is that of the monotone integer key of the f32 bits:
+ *   bits ^ 0x80000000 for a non-negative sign, ~bits otherwise, compared unsigned: -0 before +0, every tie pinned.
+ * Methods:
+ *   AM_EST_MEAN     m = the f64 sum of P_n in hit order, divided by c_n.
+ *   AM_EST_MEDIAN   odd c_n: m = the middle value of the sorted P_n; even: m = ((double)a + (double)b) / 2 of the two
+ *                   middle values.
+ *   AM_EST_TRIMMED  d = min(floor(c_n * trim_permille / 1000), (c_n - 1) / 2) values are dropped at each end of the sorted
+ *                   P_n; m = the f64 sum of the rest in ascending order, divided by c_n - 2d.  trim_permille in [0, 500].
+ * Outputs (host memory, `length` entries each; dev and count may be null):
+ *   est[n]   = fl32(m), rounded once.
+ *   dev[n]   = fl32(sqrt(sum over P_n in hit order of (v - m)^2 / c_n)), in f64 around the unrounded m: small where the
+ *              occurrences agree.  Read with a margin (lead, and length beyond the rough needle) it shows where the jingle
+ *              really begins and ends: the spread collapses exactly there.
+ *   count[n] = c_n.
+ *   Where c_n = 0: est = 0, dev = 0, count = 0; the result is always usable as a needle.
+ * Limits.  AM_EST_MAX_HITS hits for MEDIAN and TRIMMED, 65535 for MEAN; length >= 1 and n >= 1; every scale finite and
+ *   not zero; lead, length < 2^62.
+ * Invariant.  A result depends on the rows' values, their order and the parameters only: all entry points give the same
+ *   bits.  Exactness: where more than half of the present values of a sample are the same number, the median IS that
+ *   number -- occurrences g_i * c with power-of-two gains under overlays that cover fewer than half of them give c back
+ *   bit for bit.
+ * Out of scope.  Alignment is to whole samples: occurrences whose clocks differ by a fraction of a sample lose some
+ *   treble in a mean (am_hit_segments reports such drift); the rows are not resampled here.
+ * AM_ERR_INVALID_ARG (the message names the hit where one is at fault): a null pointer, an unknown method or sample
+ *   format, trim_permille > 500, n = 0 or length = 0, n above the method's limit (the message states the limit),
+ *   hits[i].haystack >= n_hay, a scale that is zero or not finite, a haystack that is not memory of `device`. */
+#define AM_EST_MAX_HITS 64
+enum { AM_EST_MEAN = 0, AM_EST_MEDIAN = 1, AM_EST_TRIMMED = 2 };
+typedef struct am_estimate_params {
+    uint32_t method;          /* AM_EST_* */
+    uint32_t trim_permille;   /* AM_EST_TRIMMED: share dropped at each end, in 1/1000 (0..500); checked for every method */
+    uint64_t lead;            /* elements read in front of each hit's start (the margin in front of the needle) */
+    uint64_t length;          /* elements per row and per output */
+} am_estimate_params;         /* 24 bytes, no padding */
+typedef struct am_est_hit {
+    uint64_t start;           /* the hit's start in its haystack (am_peak.start) */
+    uint32_t haystack;        /* index into d_haystacks */
+    float scale;              /* 1 / gain */
+} am_est_hit;                 /* 16 bytes */
+/* Pure host function (no device): one row cut out of a host haystack, as defined above (NaN for absent).  len counts
+ * samples (frames for AM_FMT_S16_STEREO); row: length floats.  A caller that holds one file at a time cuts each hit's
+ * row while the file is in memory and estimates at the end. */
+int am_hit_window(const void* haystack, size_t len, int sample_format, uint64_t start, float scale,
+                  uint64_t lead, uint64_t length, float* row);
+/* rows: n x length f32 in host memory, row-major (row i = hit i).  ep->lead is ignored. */
+int am_needle_estimate_rows(int device, const float* rows, size_t n, const am_estimate_params* ep,
+                            float* est, float* dev, uint32_t* count);
+/* The hits in haystacks resident on `device` (an archive in device memory; one hit per file, or many): nothing but the
+ * hit table travels up, the rows are gathered by the kernel.  hits, lens, est, dev, count: host memory. */
+int am_needle_estimate_device(int device, const void* const* d_haystacks, const size_t* lens, size_t n_hay,
+                              int sample_format, const am_est_hit* hits, size_t n, const am_estimate_params* ep,
+                              float* est, float* dev, uint32_t* count);
+
 /* ---- device memory plumbing (for hosts without their own HIP allocator) -- */
 int am_device_malloc(int device, size_t bytes, void** out);
 int am_device_free(int device, void* p);

@@ -101,6 +101,35 @@ inline std::vector<float> fir(const void* x, std::size_t n, int sample_format, c
     return out;
 }
 
+// needle estimation (audiomatch.h, "needle estimation"): a clean needle from the hits of a rough one
+struct NeedleEstimate {
+    std::vector<float> est, dev;          // the estimate and the spread of the occurrences around it, per sample
+    std::vector<std::uint32_t> count;     // the values each sample rests on
+};
+// am_hit_window (pure host): the row of one occurrence, fl32(x[start - lead + n] * scale), NaN where absent
+inline std::vector<float> hit_window(const void* x, std::size_t n, int sample_format, std::uint64_t start, float scale, std::uint64_t lead,
+                                     std::uint64_t length) {
+    std::vector<float> row(static_cast<std::size_t>(length));
+    check(am_hit_window(x, n, sample_format, start, scale, lead, length, row.data()));
+    return row;
+}
+// am_needle_estimate_rows: rows holds n rows of `length` values, one occurrence after the other
+inline NeedleEstimate estimate_needle(const std::vector<float>& rows, std::size_t n, std::uint32_t method = AM_EST_MEDIAN,
+                                      std::uint32_t trim_permille = 0, int device = 0) {
+    const am_estimate_params ep{method, trim_permille, 0, n ? rows.size() / n : 0};
+    NeedleEstimate r{std::vector<float>(ep.length), std::vector<float>(ep.length), std::vector<std::uint32_t>(ep.length)};
+    check(am_needle_estimate_rows(device, rows.data(), n, &ep, r.est.data(), r.dev.data(), r.count.data()));
+    return r;
+}
+// am_needle_estimate_device: the hits in haystacks resident on `device`
+inline NeedleEstimate estimate_needle_device(int device, const std::vector<const void*>& d_haystacks, const std::vector<std::size_t>& lens,
+                                             int sample_format, const std::vector<am_est_hit>& hits, const am_estimate_params& ep) {
+    NeedleEstimate r{std::vector<float>(ep.length), std::vector<float>(ep.length), std::vector<std::uint32_t>(ep.length)};
+    check(am_needle_estimate_device(device, d_haystacks.data(), lens.data(), d_haystacks.size(), sample_format, hits.data(), hits.size(), &ep,
+                                    r.est.data(), r.dev.data(), r.count.data()));
+    return r;
+}
+
 // trait CorrelateAlgo<f32> (audio_matcher.rs:65-76)
 // option keys of window-energy normalised scores (audiomatch.h): HipConvolve::set_option(kOptScoreNorm, 1) for NCC
 // on one handle, am_set_option for the process default and the floor
