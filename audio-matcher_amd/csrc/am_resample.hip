@@ -10,8 +10,12 @@
 // of L, so all of them share one phase, whose taps are read once per chunk of kRsTc into registers and used kRsJ times.
 // Consecutive lanes write consecutive outputs.  Every output adds its taps in the order t = 0, 1, ... with one f32 fma
 // each; taps past cnt(p) are skipped (their x position lies outside the support), so a non-finite sample reaches
-// exactly the outputs whose support holds it.  The launch geometry depends on (L, M) only: every entry point gives the
-// same bits for the same input.
+// exactly the outputs whose support holds it.  Rows of up to kRsSeqTaps taps are one such chain.  Longer rows are added
+// chunk by chunk: the kRsTc taps of a chunk in f32 from zero, in that order, and the chunk sums into an f64 sum that is
+// rounded to f32 once, at the store.  A chain of n taps is off by up to n 2^-24 sum |h x|: with sum |h| < 3 that holds
+// the header's 1e-5 max |x| up to kRsSeqTaps taps and breaks it from some 50 000 taps on (8192 -> 1 Hz has 163 841),
+// while the chunked form stays below (kRsTc + 2) 2^-24 sum |h x| < 2e-6 max |x| for every row length.  The launch
+// geometry and the form of the sum depend on (L, M) only: every entry point gives the same bits for the same input.
 #include "am_internal.h"
 
 namespace am {
@@ -21,6 +25,7 @@ namespace {
 constexpr int kRsXsMax = 8192;    // floats of staged input per workgroup (32 KB)
 constexpr int kRsTabMax = 8192;   // floats of staged table per workgroup (32 KB; with the input 64 KB of LDS at most)
 constexpr int kRsWMax = 2048;     // work items per workgroup (unless L alone is larger)
+constexpr int kRsSeqTaps = 48;    // rows up to this long (ts) are summed as one f32 chain, longer ones through f64
 constexpr uint32_t kResampleMaxRate = 768000;   // rates in 1 .. this, Hz
 constexpr long long kResampleMaxR = 8192;       // R = max(L, M) up to this (11025 <-> 384000 Hz: 5120)
 
@@ -40,7 +45,7 @@ __device__ __forceinline__ float rs_sample(const void* src, long long n) {
     return KIND ? rs_mix(((guint*)src)[n]) : ((gfloat*)src)[n];
 }
 
-template <int KIND, bool XLDS, bool TLDS>
+template <int KIND, bool XLDS, bool TLDS, bool WIDE>
 __global__ __launch_bounds__(kRsThreads) void resample_kernel(ResampleJob j, long long blk0) {
     extern __shared__ float4 rs_lds4[];
     float* rs_lds = reinterpret_cast<float*>(rs_lds4);
@@ -99,9 +104,11 @@ __global__ __launch_bounds__(kRsThreads) void resample_kernel(ResampleJob j, lon
         const int p = (int)(v % (unsigned)L);
         const int cnt = (2 * j.H - p) / L + 1;
         const float* tp = (TLDS ? (const float*)tab : j.taps) + (long long)p * tsl;
+        // acc: the f32 chain of a short row, of one chunk of a long row (WIDE); accw: the f64 sum of the chunk sums
         float acc[kRsJ];
+        double accw[kRsJ];
 #pragma unroll
-        for (int jj = 0; jj < kRsJ; ++jj) acc[jj] = 0.0f;
+        for (int jj = 0; jj < kRsJ; ++jj) { acc[jj] = 0.0f; accw[jj] = 0.0; }
         for (int t0 = 0; t0 < cnt; t0 += kRsTc) {
             float tv[kRsTc];
 #pragma unroll
@@ -130,22 +137,26 @@ __global__ __launch_bounds__(kRsThreads) void resample_kernel(ResampleJob j, lon
                     }
                 }
             }
+            if (WIDE) {
+#pragma unroll
+                for (int jj = 0; jj < kRsJ; ++jj) { accw[jj] += (double)acc[jj]; acc[jj] = 0.0f; }
+            }
         }
 #pragma unroll
         for (int jj = 0; jj < kRsJ; ++jj) {
             const long long kk = k + (long long)jj * j.W;
-            if (kk < j.n_out) j.dst[kk] = acc[jj];
+            if (kk < j.n_out) j.dst[kk] = WIDE ? (float)accw[jj] : acc[jj];
         }
     }
 }
 
-template <int KIND>
+template <int KIND, bool WIDE>
 hipError_t launch_kind(hipStream_t st, const ResampleJob& j, unsigned nblk, long long blk0, size_t lds) {
     const dim3 g(nblk), b(kRsThreads);
-    if (j.xs_cap && j.tab_lds) hipLaunchKernelGGL((resample_kernel<KIND, true, true>), g, b, lds, st, j, blk0);
-    else if (j.xs_cap) hipLaunchKernelGGL((resample_kernel<KIND, true, false>), g, b, lds, st, j, blk0);
-    else if (j.tab_lds) hipLaunchKernelGGL((resample_kernel<KIND, false, true>), g, b, lds, st, j, blk0);
-    else hipLaunchKernelGGL((resample_kernel<KIND, false, false>), g, b, lds, st, j, blk0);
+    if (j.xs_cap && j.tab_lds) hipLaunchKernelGGL((resample_kernel<KIND, true, true, WIDE>), g, b, lds, st, j, blk0);
+    else if (j.xs_cap) hipLaunchKernelGGL((resample_kernel<KIND, true, false, WIDE>), g, b, lds, st, j, blk0);
+    else if (j.tab_lds) hipLaunchKernelGGL((resample_kernel<KIND, false, true, WIDE>), g, b, lds, st, j, blk0);
+    else hipLaunchKernelGGL((resample_kernel<KIND, false, false, WIDE>), g, b, lds, st, j, blk0);
     return hipGetLastError();
 }
 
@@ -157,9 +168,11 @@ hipError_t launch_resample(hipStream_t st, const ResampleJob& j, int kind) {
     const long long nblk = (j.n_out + bo - 1) / bo;
     const size_t lds = sizeof(float) * ((size_t)j.xs_cap + (j.tab_lds ? (size_t)j.L * (size_t)(j.ts + 1) : 0));
     constexpr long long kMaxGrid = 1ll << 30;
+    const bool wide = j.ts > kRsSeqTaps;   // (a function of (L, M) alone, like the geometry)
     for (long long b0 = 0; b0 < nblk; b0 += kMaxGrid) {
         const unsigned n = (unsigned)std::min(kMaxGrid, nblk - b0);
-        const hipError_t e = kind ? launch_kind<1>(st, j, n, b0, lds) : launch_kind<0>(st, j, n, b0, lds);
+        const hipError_t e = wide ? (kind ? launch_kind<1, true>(st, j, n, b0, lds) : launch_kind<0, true>(st, j, n, b0, lds))
+                                  : (kind ? launch_kind<1, false>(st, j, n, b0, lds) : launch_kind<0, false>(st, j, n, b0, lds));
         if (e != hipSuccess) return e;
     }
     return hipSuccess;

@@ -554,8 +554,9 @@ int am_pcm_s16_stereo_to_mono_device(int device, const int16_t* d_interleaved, s
  *   src_rate == dst_rate: y = x, the input's bits (f32) or the down-mix's bits (i16).
  *   Non-finite samples spread, by IEEE arithmetic, to the outputs whose support holds them and to no others; the
  *   matcher then drops exactly those windows, as for any haystack.
- *   Accumulation is f32 in one fixed order: every entry point gives the same bits for the same input, and
- *   max |y - y_f64| <= 1e-5 max |x|.  Index arithmetic is 64-bit.
+ *   Accumulation is in one fixed order that depends on (L, M) alone -- phases of up to 48 taps as one f32 chain, longer
+ *   ones as f32 sums of 8 taps added up in f64 -- so every entry point gives the same bits for the same input, and
+ *   max |y - y_f64| <= 1e-5 max |x| for every accepted pair.  Index arithmetic is 64-bit.
  *   AM_ERR_INVALID_ARG: a rate outside [1, 768000], R > 8192 (every pair of 8, 11.025, 12, 16, 22.05, 24, 32, 44.1, 48,
  *   64, 88.2, 96, 176.4, 192 and 384 kHz is within it; the worst, 11025 <-> 384000, has R = 5120), an unknown sample
  *   format, a null pointer.  The filter table of each (L, M) is built once per device and kept until am_shutdown. */
