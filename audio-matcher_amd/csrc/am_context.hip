@@ -520,6 +520,7 @@ int am_shutdown(void) {
         c->lag_parts.release(); c->lag_r.release();
         for (auto& kv : c->band_tabs) kv.second.release();
         c->band_tabs.clear();
+        c->warp_tab.release(); c->warp_needles.release();
         c->work_tail.release(); c->tail_scores.release(); c->tail_stats.release(); c->work_tail2.release();
         for (int set = 0; set < 2; ++set)
             for (int i = 0; i < kMaxNeedleGroup; ++i) { c->grp_scores[set][i].release(); c->grp_stats32[set][i].release(); c->grp_wflags[set][i].release(); }

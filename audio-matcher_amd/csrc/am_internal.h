@@ -159,6 +159,7 @@ struct Ctx {
     DevBuf hit_tab, hit_parts, hit_flags, hit_out, hit_stage;
     HostBuf hit_io;                         // ... and the pinned host side: the table, the results behind it
     std::map<int, DevBuf> band_tabs;        // per-band hit scoring (am_bands.hip): the window and twiddle table of each frame_log2
+    DevBuf warp_tab, warp_needles;          // per-hit drift scoring (am_warp.hip): the interpolator's table (kept), a call's warped needles
     // per-hit significance (am_significance.hip): the spans and score zones of one group of hits, the slice partials and
     // the per-hit state between the two passes
     DevBuf sig_span, sig_scores, sig_psum, sig_pmax, sig_mean, sig_hmax;

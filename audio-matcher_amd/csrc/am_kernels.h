@@ -344,6 +344,36 @@ struct SegDesc {
 hipError_t launch_hit_segments(hipStream_t st, const SegDesc* d_hits, long long n, int m, int r, int max_nsl, int kind,
                                double* parts, unsigned* pflags, am_hit_segment* d_out);
 
+// the slice launches alone, over n table entries read with m = 1: what am_warp.hip runs over its (hit, rate) entries
+hipError_t launch_seg_slices(hipStream_t st, const SegDesc* d_hits, long long n, int m, int r, int max_nsl, int kind, double* parts,
+                             unsigned* pflags);
+
+// ---- am_warp.hip: per-hit drift scoring (am_hit_warp*) ----
+constexpr int kWarpThreads = 256;          // warped needle samples per workgroup of warp_needle
+constexpr int kWarpCombineThreads = 256;   // threads of the workgroup that turns one hit's partials into its record
+constexpr int kWarpMaxRates = 2 * AM_WARP_MAX_STEPS + 1;
+constexpr size_t kWarpRoundBytes = (size_t)64 << 20;   // a round of hits: its partial records, and its warped needles, at most this much each (one hit at the least)
+// One warped needle of a call: out[j], j < s_q, from needle[0, s) at the step inc (32.32 fixed point)
+struct WarpJob {
+    const float* needle;
+    float* out;
+    long long s, s_q;
+    unsigned long long inc;
+};
+// The call's grid as the combine kernel reads it (a kernel argument)
+struct WarpGrid {
+    double centre_ppm, step_ppm;   // step_ppm = max_ppm / K (0 for K = 0)
+    double d[kWarpMaxRates];       // d_q
+    int k, r;
+};
+// table: h[phase][tap] (AM_WARP_PHASES x AM_WARP_TAPS f32)
+hipError_t launch_warp_needles(hipStream_t st, const WarpJob* d_jobs, int n_jobs, long long max_len, const float* table);
+// tab: 2 k + 1 entries per hit (hit i, rate q at i * (2 k + 1) + q, filled as for launch_seg_slices with m = 1); parts /
+// pflags as launch_seg_slices wrote them; d_out: n records (the `length` of an AM_HIT_NONFINITE record is left to the host,
+// which knows the unwarped needle)
+hipError_t launch_warp_combine(hipStream_t st, const SegDesc* tab, long long n, const WarpGrid& grid, const double* parts,
+                               const unsigned* pflags, am_warp_hit* d_out);
+
 // ---- am_bands.hip: per-band hit scoring (am_hit_bands*) ----
 constexpr int kBandGroup = 8;   // consecutive frames per workgroup of the frame kernel, counted from the hit's first frame
 inline int band_record_len(int n_bands) { return 4 * n_bands + 1; }   // doubles per partial record: (Re C, Im C, E_x, E_n) per band, E_n over every bin

@@ -18,6 +18,7 @@
 // samples it reads, m, R and the floor only (slices start at multiples of kHitSlice from a_j, every reduction runs in
 // a fixed order): the single, batch and host forms agree bit for bit.  The three forms run in the frame of am_hits.hip
 // (am_internal.h: hit_call, hit_call_batch, hit_round_trip); SegFamily below is what this family adds to it.
+// am_warp.hip runs seg_slices alone (launch_seg_slices, m = 1) over a table of its own and combines the records itself.
 #include "am_internal.h"
 
 namespace am {
@@ -200,9 +201,8 @@ void launch_seg_slices_rt(hipStream_t st, int rt, dim3 grid, const SegDesc* d_hi
 
 }  // namespace
 
-hipError_t launch_hit_segments(hipStream_t st, const SegDesc* d_hits, long long n, int m, int r, int max_nsl, int kind,
-                               double* parts, unsigned* pflags, am_hit_segment* d_out) {
-    if (n <= 0) return hipSuccess;
+hipError_t launch_seg_slices(hipStream_t st, const SegDesc* d_hits, long long n, int m, int r, int max_nsl, int kind, double* parts,
+                             unsigned* pflags) {
     const int rt = seg_kernel_radius(r);
     const long long total = n * m;
     for (long long g0 = 0; g0 < total; g0 += kHitMaxGridY) {   // (more segments than one grid column holds: a few launches)
@@ -212,8 +212,16 @@ hipError_t launch_hit_segments(hipStream_t st, const SegDesc* d_hits, long long 
         hipError_t e = hipGetLastError();
         if (e != hipSuccess) return e;
     }
-    hipLaunchKernelGGL(seg_combine_kernel, dim3((unsigned)total), dim3(64), 0, st, d_hits, m, r, rt, (const double*)parts,
-                       (const unsigned*)pflags, d_out);
+    return hipSuccess;
+}
+
+hipError_t launch_hit_segments(hipStream_t st, const SegDesc* d_hits, long long n, int m, int r, int max_nsl, int kind,
+                               double* parts, unsigned* pflags, am_hit_segment* d_out) {
+    if (n <= 0) return hipSuccess;
+    const hipError_t e = launch_seg_slices(st, d_hits, n, m, r, max_nsl, kind, parts, pflags);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(seg_combine_kernel, dim3((unsigned)(n * m)), dim3(64), 0, st, d_hits, m, r, seg_kernel_radius(r),
+                       (const double*)parts, (const unsigned*)pflags, d_out);
     return hipGetLastError();
 }
 

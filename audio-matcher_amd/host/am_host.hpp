@@ -77,6 +77,9 @@ struct Arguments {
     std::optional<float> min_confidence;      // extension: --min-confidence X, drop hits whose exact NCC is below X (am_hit_scores, 0..1)
     std::uint32_t segments = 0;               // extension: --segments M[:R], per-segment scoring of every printed hit (am_hit_segments), 0 = off
     std::uint32_t segment_radius = 4;         // ... the lags -R .. R examined per segment
+    std::optional<double> warp_ppm;           // extension: --warp PPM[:STEPS[:RADIUS]], drift and corrected NCC of every hit (am_hit_warp)
+    std::uint32_t warp_steps = 8;             // ... drifts -PPM .. PPM in 2 STEPS + 1 steps
+    std::uint32_t warp_radius = 4;            // ... the lags -RADIUS .. RADIUS
     std::uint32_t bands = 0;                  // extension: --bands B[:LOG2F], per-band scoring of every printed hit (am_hit_bands), 0 = off
     std::uint32_t band_frame_log2 = 11;       // ... in frames of 2^LOG2F samples
     std::optional<float> min_significance;    // extension: --min-significance Z, drop hits whose z against the local background is below Z (am_hit_significance)
@@ -132,6 +135,12 @@ inline const char* usage_text() {
            "                         holds ('#' present, '.' absent: the part's NCC against --min-confidence if given,\n"
            "                         else 0.5), the covered fraction, the drift in ppm and the refined start's lag;\n"
            "                         each part is matched within R samples (0..16, default 4); M in 1..1024\n"
+           "  --warp PPM[:STEPS[:RADIUS]]  for hits that run on another clock: after each hit's offset line, print its\n"
+           "                         clock drift in ppm (positive: the occurrence is longer than the snippet), its refined\n"
+           "                         lag in samples, the NCC with the drift taken out and the NCC as found; drifts -PPM ..\n"
+           "                         PPM in 2 STEPS + 1 steps (STEPS in 1..32, default 8), lags -RADIUS .. RADIUS (0..16,\n"
+           "                         default 4); PPM up to 50000.  --min-confidence then applies to the corrected NCC and\n"
+           "                         --learn-needle cuts its rows on the snippet's clock.  Does not apply with --live\n"
            "  --bands B[:LOG2F]      after each hit's offset line, print which of B log-spaced frequency bands of the\n"
            "                         snippet (50 Hz up to 16 kHz or half the sample rate) the hit holds ('#' present,\n"
            "                         '.' absent: the band's coherence against --min-confidence if given, else 0.5),\n"
@@ -256,6 +265,27 @@ inline Arguments parse_arguments(int argc, const char* const* argv) {
             a.segments = (std::uint32_t)m;
             a.segment_radius = (std::uint32_t)r;
         }
+        else if (s == "--warp") {
+            const std::string v = need(i);
+            const std::size_t c1 = v.find(':'), c2 = c1 == std::string::npos ? c1 : v.find(':', c1 + 1);
+            const std::string vp = v.substr(0, c1);
+            const std::string vs = c1 == std::string::npos ? "8" : v.substr(c1 + 1, c2 == std::string::npos ? c2 : c2 - c1 - 1);
+            const std::string vr = c2 == std::string::npos ? "4" : v.substr(c2 + 1);
+            auto whole = [](const std::string& t, unsigned long& x) {
+                char* end = nullptr;
+                x = std::strtoul(t.c_str(), &end, 10);
+                return !t.empty() && t[0] >= '0' && t[0] <= '9' && *end == '\0';
+            };
+            char* end = nullptr;
+            const double ppm = std::strtod(vp.c_str(), &end);
+            unsigned long k = 0, r = 0;
+            if (vp.empty() || *end != '\0' || !(ppm > 0.0) || ppm > AM_WARP_MAX_PPM || !whole(vs, k) || !whole(vr, r) || k == 0 ||
+                k > AM_WARP_MAX_STEPS || r > AM_SEG_MAX_RADIUS)
+                throw ArgError("invalid value '" + v + "' for --warp (PPM[:STEPS[:RADIUS]], PPM above 0 up to 50000, STEPS in 1..32, RADIUS in 0..16)");
+            a.warp_ppm = ppm;
+            a.warp_steps = (std::uint32_t)k;
+            a.warp_radius = (std::uint32_t)r;
+        }
         else if (s == "--bands") {
             const std::string v = need(i);
             const std::size_t colon = v.find(':');
@@ -354,6 +384,7 @@ inline Arguments parse_arguments(int argc, const char* const* argv) {
         if (a.best || a.normalize || a.min_confidence) throw ArgError("--live: --best, --normalize and --min-confidence do not apply");
         if (a.segments) throw ArgError("--live: --segments does not apply");
         if (a.bands) throw ArgError("--live: --bands does not apply");
+        if (a.warp_ppm) throw ArgError("--live: --warp does not apply");
         if (a.whiten || a.preemphasis) throw ArgError("--live: --whiten and --preemphasis do not apply (not supported on a live feed yet)");
         if (a.min_significance || a.significance_zone_ms) throw ArgError("--live: --min-significance and --significance-zone do not apply");
         return a;

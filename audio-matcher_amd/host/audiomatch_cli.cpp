@@ -99,6 +99,58 @@ static std::vector<std::string> segment_lines(const Arguments& args, const am_ne
     return out;
 }
 
+// extension: --warp PPM[:STEPS[:RADIUS]].  The drift records of a file's hits (am_hit_warp over the grid -PPM .. PPM),
+// computed once, right after the match; of(): the records of the hits that are left after the filters (a subset in the
+// same order, told apart by their starts).
+struct WarpSet {
+    std::vector<std::uint64_t> starts;
+    std::vector<am_warp_hit> recs;
+
+    static WarpSet compute(const Arguments& args, const am_needle* algo, const std::vector<float>& samples, const am_peak* peaks, size_t n) {
+        WarpSet ws;
+        if (!args.warp_ppm || n == 0) return ws;
+        ws.recs.resize(n);
+        for (size_t i = 0; i < n; ++i) ws.starts.push_back(peaks[i].start);
+        const am_warp_params wp{0.0, *args.warp_ppm, args.warp_steps, args.warp_radius};
+        if (am_hit_warp(algo, samples.data(), samples.size(), AM_FMT_F32_MONO, peaks, n, &wp, ws.recs.data()) != AM_OK)
+            throw std::runtime_error(std::string("am_hit_warp: ") + am_last_error_string());
+        return ws;
+    }
+    std::vector<am_warp_hit> of(const am_peak* peaks, size_t n) const {
+        std::vector<am_warp_hit> out;
+        for (size_t i = 0, k = 0; i < n && k < starts.size(); ++k)
+            if (starts[k] == peaks[i].start) { out.push_back(recs[k]); ++i; }
+        return out;
+    }
+};
+
+// ... one line per hit, to follow the hit's offset line: drift, refined lag, the corrected NCC and the NCC as found
+static std::vector<std::string> warp_lines(const std::vector<am_warp_hit>& recs) {
+    std::vector<std::string> out;
+    for (const am_warp_hit& w : recs) {
+        char line[192];
+        std::snprintf(line, sizeof line, "  warp drift_ppm %.1f lag %.3f ncc %.6f ncc_as_found %.6f%s", w.drift_ppm, w.lag, (double)w.ncc,
+                      (double)w.ncc_centre, (w.flags & AM_HIT_DRIFT_UNREFINED) ? " (drift at the grid's end or unrefined)" : "");
+        out.push_back(line);
+    }
+    return out;
+}
+
+// ... with --min-confidence: keeps the hits whose corrected NCC is at least X, in place (ws holds the records of exactly
+// these n hits); returns how many are left.  With --debug one line per hit (`prefix` in front).
+static size_t warp_confidence_filter(const Arguments& args, const WarpSet& ws, am_peak* peaks, size_t n, const std::string& prefix) {
+    const std::vector<am_warp_hit>& w = ws.recs;
+    size_t kept = 0;
+    for (size_t i = 0; i < n; ++i) {
+        const bool keep = w[i].ncc >= *args.min_confidence;   // (a NaN ncc is dropped too)
+        if (args.verbosity >= 2)
+            std::printf("%shit %zu: drift_ppm %.1f lag %.3f ncc %.6f ncc_as_found %.6f gain %.6g%s\n", prefix.c_str(), i + 1, w[i].drift_ppm,
+                        w[i].lag, (double)w[i].ncc, (double)w[i].ncc_centre, (double)w[i].gain, keep ? "" : " (dropped)");
+        if (keep) peaks[kept++] = peaks[i];
+    }
+    return kept;
+}
+
 // extension: --min-significance Z [--significance-zone D].  Keeps the hits whose z against their local background
 // (am_hit_significance: guard = the snippet's length - 1, radius = D at the file's rate, by default three snippet
 // lengths) is at least Z, in place; returns how many are left.  With --debug one line per hit (`prefix` in front).
@@ -139,23 +191,33 @@ struct Learner {
 
     size_t cap(const Arguments& args) const { return args.learn_method == AM_EST_MEAN ? 65535 : AM_EST_MAX_HITS; }
 
-    void take(const Arguments& args, const am_needle* algo, const std::vector<float>& samples, std::uint32_t m_sr, const am_peak* peaks, size_t n) {
+    // w: with --warp, the drift records of these n hits
+    void take(const Arguments& args, const am_needle* algo, const std::vector<float>& samples, std::uint32_t m_sr, const am_peak* peaks, size_t n,
+              const std::vector<am_warp_hit>& w) {
         if (n == 0) return;
         size_t s_len = 0;
         am_needle_len(algo, &s_len);
         const std::uint64_t lead = round_samples_ms(args.learn_margin_ms.value_or(0), m_sr), len = s_len + 2 * lead;
         if (rows.empty() && !capped) { sr = m_sr; length = len; }
         if (m_sr != sr || len != length) throw std::runtime_error("--learn-needle: the main files must share one sample rate");
-        std::vector<am_hit_score> sc(n);
-        if (am_hit_scores(algo, samples.data(), samples.size(), AM_FMT_F32_MONO, peaks, n, sc.data()) != AM_OK)
+        // with --warp: gain, NCC, lag and drift of am_hit_warp, the row cut on the snippet's clock (am_hit_window_warped)
+        std::vector<am_hit_score> sc(args.warp_ppm ? 0 : n);
+        if (!args.warp_ppm && am_hit_scores(algo, samples.data(), samples.size(), AM_FMT_F32_MONO, peaks, n, sc.data()) != AM_OK)
             throw std::runtime_error(std::string("am_hit_scores: ") + am_last_error_string());
         for (size_t i = 0; i < n; ++i) {
-            if ((sc[i].flags & (AM_HIT_NONFINITE | AM_HIT_BELOW_FLOOR)) || !(sc[i].gain > 0.0f)) continue;
-            const float scale = 1.0f / sc[i].gain;
+            const std::uint32_t flags = args.warp_ppm ? w[i].flags : sc[i].flags;
+            const float gain = args.warp_ppm ? w[i].gain : sc[i].gain;
+            if ((flags & (AM_HIT_NONFINITE | AM_HIT_BELOW_FLOOR | AM_HIT_EMPTY_SEGMENT)) || !(gain > 0.0f)) continue;
+            const float scale = 1.0f / gain;
             if (!std::isfinite(scale)) continue;
-            Row r{sc[i].ncc, std::vector<float>((size_t)length)};
-            if (am_hit_window(samples.data(), samples.size(), AM_FMT_F32_MONO, peaks[i].start, scale, lead, length, r.v.data()) != AM_OK)
+            Row r{args.warp_ppm ? w[i].ncc : sc[i].ncc, std::vector<float>((size_t)length)};
+            if (args.warp_ppm) {
+                if (am_hit_window_warped(samples.data(), samples.size(), AM_FMT_F32_MONO, peaks[i].start, scale, w[i].lag, w[i].drift_ppm, lead,
+                                         length, r.v.data()) != AM_OK)
+                    throw std::runtime_error(std::string("am_hit_window_warped: ") + am_last_error_string());
+            } else if (am_hit_window(samples.data(), samples.size(), AM_FMT_F32_MONO, peaks[i].start, scale, lead, length, r.v.data()) != AM_OK) {
                 throw std::runtime_error(std::string("am_hit_window: ") + am_last_error_string());
+            }
             rows.push_back(std::move(r));
         }
         if (rows.size() > cap(args)) {
@@ -374,7 +436,10 @@ static int run_multi(const Arguments& args) {
             }
             for (size_t j = 0; j < k; ++j) {
                 am_peak* pk = peaks.data() + j * cap;
-                if (args.min_confidence && n[j] > 0) {   // each snippet's hits scored with that snippet's handle
+                const WarpSet warp = WarpSet::compute(args, handles[j], m_samples, pk, n[j]);   // extension: --warp
+                if (args.min_confidence && args.warp_ppm && n[j] > 0) {   // ... the corrected NCC decides
+                    n[j] = warp_confidence_filter(args, warp, pk, n[j], snips[j].name + ": ");
+                } else if (args.min_confidence && n[j] > 0) {   // each snippet's hits scored with that snippet's handle
                     std::vector<am_hit_score> sc(n[j]);
                     if (am_hit_scores(handles[j], m_samples.data(), m_samples.size(), AM_FMT_F32_MONO, pk, n[j], sc.data()) != AM_OK)
                         throw std::runtime_error(std::string("am_hit_scores: ") + am_last_error_string());
@@ -395,8 +460,11 @@ static int run_multi(const Arguments& args) {
                         args.segments ? segment_lines(args, handles[j], m_samples, pk, n[j]) : std::vector<std::string>();
                     const std::vector<std::string> bands =
                         args.bands ? band_lines(args, handles[j], m_samples, m_sr, pk, n[j]) : std::vector<std::string>();
+                    const std::vector<std::string> warps =
+                        args.warp_ppm ? warp_lines(warp.of(pk, n[j])) : std::vector<std::string>();   // extension: --warp
                     for (size_t i = 0; i < lines.size(); ++i) {
                         std::printf("%s: %s\n", snips[j].name.c_str(), lines[i].c_str());
+                        if (i < warps.size()) std::printf("%s: %s\n", snips[j].name.c_str(), warps[i].c_str());
                         if (i < segs.size()) std::printf("%s: %s\n", snips[j].name.c_str(), segs[i].c_str());
                         if (i < bands.size()) std::printf("%s: %s\n", snips[j].name.c_str(), bands[i].c_str());
                     }
@@ -642,7 +710,10 @@ int main(int argc, char** argv) {
                 }
                 if (rc != AM_OK) throw std::runtime_error(std::string("am_match: ") + am_last_error_string());
             }
-            if (args.min_confidence && n > 0) {                               // extension: --min-confidence
+            const WarpSet warp = WarpSet::compute(args, algo, m_samples, peaks.data(), n);   // extension: --warp
+            if (args.min_confidence && args.warp_ppm && n > 0) {              // ... the corrected NCC decides
+                n = warp_confidence_filter(args, warp, peaks.data(), n, "");
+            } else if (args.min_confidence && n > 0) {                        // extension: --min-confidence
                 std::vector<am_hit_score> sc(n);
                 if (am_hit_scores(algo, m_samples.data(), m_samples.size(), AM_FMT_F32_MONO, peaks.data(), n, sc.data()) != AM_OK)
                     throw std::runtime_error(std::string("am_hit_scores: ") + am_last_error_string());
@@ -657,15 +728,18 @@ int main(int argc, char** argv) {
                 n = kept;
             }
             if (args.min_significance) n = significance_filter(args, algo, m_samples, m_sr, peaks.data(), n, "");   // extension: --min-significance
-            if (!args.learn_needle.empty()) learner.take(args, algo, m_samples, m_sr, peaks.data(), n);           // extension: --learn-needle
+            if (!args.learn_needle.empty()) learner.take(args, algo, m_samples, m_sr, peaks.data(), n, warp.of(peaks.data(), n));           // extension: --learn-needle
             if (args.verbosity >= 1) {
                 const std::vector<std::string> lines = offset_lines(peaks.data(), n, m_sr);                       // mod.rs:89
                 const std::vector<std::string> segs =
                     args.segments ? segment_lines(args, algo, m_samples, peaks.data(), n) : std::vector<std::string>();   // extension: --segments
                 const std::vector<std::string> bands =
                     args.bands ? band_lines(args, algo, m_samples, m_sr, peaks.data(), n) : std::vector<std::string>();   // extension: --bands
+                const std::vector<std::string> warps =
+                    args.warp_ppm ? warp_lines(warp.of(peaks.data(), n)) : std::vector<std::string>();   // extension: --warp
                 for (size_t i = 0; i < lines.size(); ++i) {
                     std::printf("%s\n", lines[i].c_str());
+                    if (i < warps.size()) std::printf("%s\n", warps[i].c_str());
                     if (i < segs.size()) std::printf("%s\n", segs[i].c_str());
                     if (i < bands.size()) std::printf("%s\n", bands[i].c_str());
                 }

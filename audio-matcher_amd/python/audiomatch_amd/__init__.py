@@ -83,6 +83,27 @@ AM_HIT_EMPTY_SEGMENT = 8
 AM_SEG_MAX_SEGMENTS, AM_SEG_MAX_RADIUS = 1024, 16
 
 
+class AmWarpParams(C.Structure):      # am_warp_params (include/audiomatch.h, per-hit drift scoring)
+    _fields_ = [("centre_ppm", C.c_double), ("max_ppm", C.c_double), ("steps", C.c_uint32), ("radius", C.c_uint32)]
+
+
+class HitWarp(C.Structure):           # am_warp_hit: one hit's drift, lag and corrected NCC
+    _fields_ = [("drift_ppm", C.c_double), ("lag", C.c_double), ("ncc", C.c_float), ("gain", C.c_float),
+                ("level_db", C.c_float), ("ncc_centre", C.c_float), ("length", C.c_uint32), ("flags", C.c_uint32)]
+
+    def __repr__(self):
+        return (f"HitWarp(drift_ppm={self.drift_ppm!r}, lag={self.lag!r}, ncc={self.ncc!r}, gain={self.gain!r}, "
+                f"level_db={self.level_db!r}, ncc_centre={self.ncc_centre!r}, length={self.length}, flags={self.flags})")
+
+    def pack(self) -> bytes:
+        """The record's 40 bytes (for bit-for-bit comparisons)."""
+        return bytes(self)
+
+
+AM_HIT_DRIFT_UNREFINED = 256
+AM_WARP_PHASES, AM_WARP_TAPS, AM_WARP_MAX_STEPS, AM_WARP_MAX_PPM = 4096, 32, 32, 50000
+
+
 class AmBandParams(C.Structure):      # am_band_params (include/audiomatch.h, per-band hit scoring)
     _fields_ = [("frame_log2", C.c_uint32), ("n_bands", C.c_uint32), ("edges", C.c_uint32 * 33)]
 
@@ -338,6 +359,16 @@ _SIGNATURES = {
     "am_needle_create_filtered": (C.c_int, [C.c_int, C.c_void_p, C.c_size_t, C.c_int, C.POINTER(C.c_float), C.c_uint32,
                                             C.POINTER(C.c_void_p)]),
     "am_hit_window": (C.c_int, [C.c_void_p, C.c_size_t, C.c_int, C.c_uint64, C.c_float, C.c_uint64, C.c_uint64, C.c_void_p]),
+    "am_warp_table": (C.c_int, [C.c_void_p]),
+    "am_hit_warp_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.POINTER(AmPeak), C.c_size_t,
+                                     C.POINTER(AmWarpParams), C.POINTER(HitWarp)]),
+    "am_hit_warp": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.POINTER(AmPeak), C.c_size_t,
+                              C.POINTER(AmWarpParams), C.POINTER(HitWarp)]),
+    "am_hit_warp_batch_device": (C.c_int, [C.POINTER(C.c_void_p), C.c_size_t, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t),
+                                           C.c_size_t, C.c_int, C.POINTER(AmPeak), C.c_size_t, C.POINTER(C.c_size_t),
+                                           C.POINTER(AmWarpParams), C.POINTER(HitWarp)]),
+    "am_hit_window_warped": (C.c_int, [C.c_void_p, C.c_size_t, C.c_int, C.c_uint64, C.c_float, C.c_double, C.c_double,
+                                       C.c_uint64, C.c_uint64, C.c_void_p]),
     "am_needle_estimate_rows": (C.c_int, [C.c_int, C.c_void_p, C.c_size_t, C.POINTER(AmEstimateParams), C.c_void_p, C.c_void_p,
                                           C.c_void_p]),
     "am_needle_estimate_device": (C.c_int, [C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.c_size_t, C.c_int,
@@ -612,6 +643,32 @@ def hit_window(haystack, start: int, scale: float, lead: int, length: int) -> np
     row = np.empty(int(length), dtype=np.float32)
     _check(lib().am_hit_window(a.ctypes.data, n, int(fmt), int(start), float(scale), int(lead), int(length), row.ctypes.data))
     return row
+
+
+def hit_window_warped(haystack, start: int, scale: float, lag: float, drift_ppm: float, lead: int, length: int) -> np.ndarray:
+    """am_hit_window_warped (pure host function): hit_window's row on the needle's clock, for an occurrence whose `lag`
+    and `drift_ppm` hit_warp reported.  NaN where an element is absent."""
+    a, fmt, n = _samples(haystack)
+    row = np.empty(int(length), dtype=np.float32)
+    _check(lib().am_hit_window_warped(a.ctypes.data, n, int(fmt), int(start), float(scale), float(lag), float(drift_ppm),
+                                      int(lead), int(length), row.ctypes.data))
+    return row
+
+
+def warp_table() -> np.ndarray:
+    """am_warp_table (pure host function): the interpolator's table, (AM_WARP_PHASES, AM_WARP_TAPS) f32."""
+    t = np.empty((AM_WARP_PHASES, AM_WARP_TAPS), dtype=np.float32)
+    _check(lib().am_warp_table(t.ctypes.data))
+    return t
+
+
+def warp_params(max_ppm: float, steps: int = 8, radius: int = 4, centre_ppm: float = 0.0) -> AmWarpParams:
+    return AmWarpParams(float(centre_ppm), float(max_ppm), int(steps), int(radius))
+
+
+def _hit_warps(buf, idx):
+    """Copies of the records (they outlive the call's buffer)."""
+    return [HitWarp.from_buffer_copy(bytes(buf[i])) for i in idx]
 
 
 def _estimate_out(length: int):
@@ -1052,6 +1109,29 @@ class HipConvolve:
         _check(lib().am_hit_segments_device(self._h, ptr, length, int(fmt), _peak_array(peaks), k, C.byref(sp), out))
         return [_hit_segments(out, i * m, m) for i in range(k)]
 
+    # -- per-hit drift scoring --
+    def hit_warp(self, haystack, peaks, wp: AmWarpParams):
+        """am_hit_warp: for each of `peaks` of a host haystack (as in hit_scores) its HitWarp record over the grid `wp`
+        (warp_params)."""
+        a = np.asarray(haystack)
+        if a.dtype == np.int16:
+            a = np.ascontiguousarray(a)
+            fmt, length = Fmt.S16_STEREO, a.size // 2
+        else:
+            a = np.ascontiguousarray(a, dtype=np.float32)
+            fmt, length = Fmt.F32_MONO, a.size
+        k = len(peaks)
+        out = (HitWarp * max(1, k))()
+        _check(lib().am_hit_warp(self._h, a.ctypes.data, length, int(fmt), _peak_array(peaks), k, C.byref(wp), out))
+        return _hit_warps(out, range(k))
+
+    def hit_warp_device(self, ptr: int, length: int, peaks, wp: AmWarpParams, fmt: int = Fmt.F32_MONO):
+        """am_hit_warp_device: the same for a haystack resident on this needle's device."""
+        k = len(peaks)
+        out = (HitWarp * max(1, k))()
+        _check(lib().am_hit_warp_device(self._h, ptr, length, int(fmt), _peak_array(peaks), k, C.byref(wp), out))
+        return _hit_warps(out, range(k))
+
     # -- per-band hit scoring --
     def hit_bands(self, haystack, peaks, bp: AmBandParams):
         """am_hit_bands: for each of `peaks` of a host haystack (as in hit_scores) the list of its bp.n_bands HitBand
@@ -1459,6 +1539,28 @@ def hit_segments_batch_device(algos, ptrs, lengths, peaks_per_pair, segments: in
     sp = AmSegmentParams(m, int(radius))
     _check(lib().am_hit_segments_batch_device(handles, nn, arr_p, arr_l, k, int(fmt), buf, cap, counts, C.byref(sp), out))
     return [[[_hit_segments(out, ((h * nn + j) * cap + i) * m, m) for i in range(counts[h * nn + j])] for j in range(nn)]
+            for h in range(k)]
+
+
+def hit_warp_batch_device(algos, ptrs, lengths, peaks_per_pair, wp: AmWarpParams, fmt: int = Fmt.F32_MONO):
+    """am_hit_warp_batch_device: peaks_per_pair[k][j] as in hit_scores_batch_device; result [k][j] = the HitWarp records
+    of haystack k against needle j."""
+    nn, k = len(algos), len(ptrs)
+    cap = max([1] + [len(peaks_per_pair[h][j]) for h in range(k) for j in range(nn)])
+    handles = (C.c_void_p * max(1, nn))(*[a._h for a in algos])
+    arr_p = (C.c_void_p * max(1, k))(*ptrs)
+    arr_l = (C.c_size_t * max(1, k))(*lengths)
+    buf = (AmPeak * max(1, cap * k * nn))()
+    counts = (C.c_size_t * max(1, k * nn))()
+    for h in range(k):
+        for j in range(nn):
+            q = h * nn + j
+            counts[q] = len(peaks_per_pair[h][j])
+            for i, p in enumerate(peaks_per_pair[h][j]):
+                buf[q * cap + i] = AmPeak(int(p.start), int(p.end), float(p.height), float(p.prominence))
+    out = (HitWarp * max(1, cap * k * nn))()
+    _check(lib().am_hit_warp_batch_device(handles, nn, arr_p, arr_l, k, int(fmt), buf, cap, counts, C.byref(wp), out))
+    return [[_hit_warps(out, range((h * nn + j) * cap, (h * nn + j) * cap + counts[h * nn + j])) for j in range(nn)]
             for h in range(k)]
 
 

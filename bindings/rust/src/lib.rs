@@ -83,6 +83,33 @@ pub struct AmHitSegment {
     pub level_db: f32,
     pub flags: u32,
 }
+/// am_warp_params: per-hit drift scoring (am_hit_warp*), 24 bytes
+#[repr(C)]
+#[derive(Clone, Copy, Default, Debug)]
+pub struct AmWarpParams {
+    pub centre_ppm: f64,
+    pub max_ppm: f64,
+    pub steps: u32,
+    pub radius: u32,
+}
+/// am_warp_hit: one hit's drift, refined lag and corrected NCC (40 bytes)
+#[repr(C)]
+#[derive(Clone, Copy, Default, Debug)]
+pub struct AmWarpHit {
+    pub drift_ppm: f64,
+    pub lag: f64,
+    pub ncc: f32,
+    pub gain: f32,
+    pub level_db: f32,
+    pub ncc_centre: f32,
+    pub length: u32,
+    pub flags: u32,
+}
+pub const AM_HIT_DRIFT_UNREFINED: u32 = 256;
+pub const AM_WARP_PHASES: usize = 4096;
+pub const AM_WARP_TAPS: usize = 32;
+pub const AM_WARP_MAX_STEPS: u32 = 32;
+pub const AM_WARP_MAX_PPM: f64 = 50000.0;
 /// am_band_params: per-band hit scoring (am_hit_bands*)
 #[repr(C)]
 #[derive(Clone, Copy, Debug)]
@@ -332,6 +359,25 @@ extern "C" {
     ) -> c_int;
     pub fn am_hit_segments_summary(
         seg: *const AmHitSegment, segments: u32, needle_len: usize, min_ncc: f32, out: *mut AmSegmentSummary,
+    ) -> c_int;
+    /// per-hit drift scoring: a hit's clock drift and its corrected NCC; rows on the needle's clock (audiomatch.h)
+    pub fn am_warp_table(out: *mut f32) -> c_int;
+    pub fn am_hit_warp(
+        h: *const AmNeedle, haystack: *const std::ffi::c_void, len: usize, sample_format: c_int, peaks: *const AmPeak, n: usize,
+        wp: *const AmWarpParams, out: *mut AmWarpHit,
+    ) -> c_int;
+    pub fn am_hit_warp_device(
+        h: *const AmNeedle, d_haystack: *const std::ffi::c_void, len: usize, sample_format: c_int, peaks: *const AmPeak, n: usize,
+        wp: *const AmWarpParams, out: *mut AmWarpHit,
+    ) -> c_int;
+    pub fn am_hit_warp_batch_device(
+        needles: *const *const AmNeedle, n_needles: usize, d_haystacks: *const *const std::ffi::c_void, lens: *const usize,
+        n_hay: usize, sample_format: c_int, peaks: *const AmPeak, cap_per_pair: usize, n_peaks: *const usize,
+        wp: *const AmWarpParams, out: *mut AmWarpHit,
+    ) -> c_int;
+    pub fn am_hit_window_warped(
+        haystack: *const std::ffi::c_void, len: usize, sample_format: c_int, start: u64, scale: f32, lag: f64, drift_ppm: f64,
+        lead: u64, length: u64, row: *mut f32,
     ) -> c_int;
     /// per-band hit scoring: which frequencies of the needle a hit holds (audiomatch.h)
     pub fn am_hit_bands(

@@ -680,8 +680,9 @@ int am_needle_create_filtered(int device, const void* needle, size_t n, int samp
  *   bits.  Exactness: where more than half of the present values of a sample are the same number, the median IS that
  *   number -- occurrences g_i * c with power-of-two gains under overlays that cover fewer than half of them give c back
  *   bit for bit.
- * Out of scope.  Alignment is to whole samples: occurrences whose clocks differ by a fraction of a sample lose some
- *   treble in a mean (am_hit_segments reports such drift); the rows are not resampled here.
+ * Other clocks.  am_hit_window aligns to whole samples on the haystack's clock.  For occurrences whose clocks differ
+ *   from the needle's, am_hit_window_warped (below) cuts the row on the needle's clock from am_hit_warp's `lag` and
+ *   `drift_ppm`; its rows go into am_needle_estimate_rows like any others.
  * AM_ERR_INVALID_ARG (the message names the hit where one is at fault): a null pointer, an unknown method or sample
  *   format, trim_permille > 500, n = 0 or length = 0, n above the method's limit (the message states the limit),
  *   hits[i].haystack >= n_hay, a scale that is zero or not finite, a haystack that is not memory of `device`. */
@@ -711,6 +712,105 @@ int am_needle_estimate_rows(int device, const float* rows, size_t n, const am_es
 int am_needle_estimate_device(int device, const void* const* d_haystacks, const size_t* lens, size_t n_hay,
                               int sample_format, const am_est_hit* hits, size_t n, const am_estimate_params* ep,
                               float* est, float* dev, uint32_t* count);
+
+/* ---- per-hit drift scoring: a hit's clock drift and its corrected NCC ------------ */
+/* The reference has no such stage.  Every per-hit family above assumes that an occurrence runs on the needle's clock;
+ * two digitisation chains differ by tens to hundreds of ppm, a tape or a playout machine by more, and the one NCC of
+ * am_hit_scores collapses long before am_hit_segments runs off its +-16 lags.  For each hit this family correlates the
+ * needle, resampled to each drift of a grid, against the haystack at the lags -R .. R and reports the best cell.
+ *
+ * The interpolator.  One table h[p][k], p = 0 .. AM_WARP_PHASES - 1 (4096), k = 0 .. AM_WARP_TAPS - 1 (32), computed once
+ *   on the host in f64 and stored as f32:  h[p][k] = v[k] / sum_k v[k],  v[k] = sinc(x) I0(8 sqrt(1 - (x / 16)^2)) / I0(8),
+ *   x = k - 15 - p / 4096, sinc(x) = sin(pi x) / (pi x).  Row p = 0 is exactly the delta (h[0][15] = 1, zeros elsewhere),
+ *   by definition and not by computation; where a result is taken at p = 0 it is the sample itself, no sum is formed.
+ *   Measured on the CPU, for sines: the error is 1.1e-4 of the amplitude up to 0.4 of the sample rate, 3.8e-4 with the
+ *   phase rounding included; above 0.45 of the sample rate it falls off.  am_warp_table returns the table (pure host
+ *   function; out: AM_WARP_PHASES x AM_WARP_TAPS floats, the same bits on every call).
+ * The warped needle.  For a drift d in ppm: inc = llround(2^32 / (1 + d 1e-6)) in f64 on the host, its length
+ *   S_d = floor((S - 1) 2^32 / inc) + 1, and for j in [0, S_d):  u = j inc + 2^19 (u64), m = u >> 32, p = (u >> 20) & 4095,
+ *     n_d[j] = fl32( sum_{k = 0 .. 31} (double)h[p][k] (double)n~[m - 15 + k] ),
+ *   n~ the needle with 0 outside [0, S), the sum in f64 in the order k = 0, 1, ..., rounded to f32 once (a product of two
+ *   f32 values is exact in f64: fused and unfused multiply-adds give the same bits).  d = 0 gives n_0 = n bit for bit,
+ *   S_0 = S.  The sign is that of am_segment_summary.drift_ppm: positive d, the occurrence is longer than the needle and
+ *   its lag grows along the needle.
+ * The grid.  K = steps, Q = 2 K + 1 drifts d_q = centre_ppm + max_ppm (q - K) / K (K = 0: the one drift d_0 = centre_ppm),
+ *   lags l = -R .. R.  K <= AM_WARP_MAX_STEPS, R <= AM_SEG_MAX_RADIUS, |centre_ppm| + max_ppm <= AM_WARP_MAX_PPM,
+ *   max_ppm >= 0, and max_ppm > 0 when K > 0.
+ * Cells.  t = peak.start, x the haystack (the bit-exact down-mix for AM_FMT_S16_STEREO), 0 outside [0, len), in f64:
+ *     c(q,l) = sum_{j < S_q} x[t + l + j] n_q[j],   E_w(q,l) = sum_{j < S_q} x[t + l + j]^2,   E_n(q) = sum_j n_q[j]^2,
+ *     ncc(q,l) = c / sqrt(E_n E_w),  0 when E_n(q) = 0, E_w = 0 or E_w < E_n 10^(-score_norm_floor_db / 10).
+ *   The sums run in one fixed order that depends on S_q alone (slices of 4096 samples, the partials added in slice order).
+ * The record of a hit:
+ *   best cell  (q*, l*) = the cell with the largest ncc; ties go to the smaller |q - K|, then the smaller q, then the
+ *              smaller |l|, then the negative l.
+ *   drift_ppm  d_q* + e max_ppm / K, e the vertex of the parabola through ncc(q* - 1, l*), ncc(q*, l*), ncc(q* + 1, l*),
+ *              clamped to +-0.5.  e = 0 and flag AM_HIT_DRIFT_UNREFINED when K = 0, when q* is 0 or 2 K (widen or move the
+ *              grid) or when there is no maximum (a - 2b + c >= 0).
+ *   lag        l* + the vertex through c(q*, l* - 1), c(q*, l*), c(q*, l* + 1), as am_hit_segments refines a lag;
+ *              AM_HIT_UNREFINED when R = 0, |l*| = R or there is no maximum.
+ *   ncc, gain, level_db   at (q*, l*): ncc(q*, l*) (AM_HIT_BELOW_FLOOR by the floor rule), c / E_n, 10 log10(E_w / E_n)
+ *              (-inf for E_w = 0).
+ *   ncc_centre ncc(K, 0): the value at the call's centre drift and lag 0; with centre_ppm = 0, the NCC of am_hit_scores.
+ *   length     S_q*: the occurrence's length in haystack samples.
+ *   flags      AM_HIT_NONFINITE: a needle sample, or a haystack sample in [t - R, t + R + max_q S_q) inside [0, len), is not
+ *              finite; drift_ppm = centre_ppm, lag = 0, the four floats NaN, length = S, no other flag.
+ *              AM_HIT_EMPTY_SEGMENT (the flag of am_hit_segments, reused): E_n(q*) = 0 -- a needle of zeros, every cell 0,
+ *              q* = K and l* = 0 by the tie rule; drift_ppm = d_q*, lag = 0, ncc = gain = 0, level_db = +inf for
+ *              E_w(q*, l*) > 0 and NaN for 0, no other flag.
+ * A hit's record depends on the needle, the samples it reads, the parameters and the floor only: the three forms below
+ * agree bit for bit.  Precondition: peak.start + S <= len; a warped needle longer than what is left reads zeros.  The
+ * host form stages [t - R, t + R + max_q S_q) of each hit only, clipped and merged.  The cost is proportional to
+ * hits x Q x (lags of the kernel) x S, not to the haystack; a large call runs its hits in rounds of bounded scratch memory.
+ * Measured on an MI355X (64 hits of a 10 s needle at 44.1 kHz in a resident 1 h haystack, +-400 ppm): 35.0 us per hit with
+ * K = 8, R = 4 (Q = 17) and 409 us per hit with K = 32, R = 16 (Q = 65), beside 2.03 us for am_hit_segments with m = 8, R = 4
+ * on the same hits; the kernels take 0.999 and 1.002 of Q am_hit_segments calls with m = 1 at the same R
+ * (tools/hit_warp_bench.py, profiles/r19/).
+ * AM_ERR_INVALID_ARG, naming the hit (and pair) or the field: an unknown sample format; wp's steps > AM_WARP_MAX_STEPS,
+ * radius > AM_SEG_MAX_RADIUS, max_ppm < 0 or not finite, max_ppm = 0 with steps > 0, |centre_ppm| + max_ppm >
+ * AM_WARP_MAX_PPM (the parameters are checked first, whatever n is); a null pointer with n > 0; peak.start + S > len; a
+ * haystack on another device.  n = 0 returns AM_OK and launches nothing. */
+enum { AM_HIT_DRIFT_UNREFINED = 256 };
+#define AM_WARP_PHASES    4096
+#define AM_WARP_TAPS      32
+#define AM_WARP_MAX_STEPS 32
+#define AM_WARP_MAX_PPM   50000
+typedef struct am_warp_params {
+    double centre_ppm;   /* the middle of the drift grid */
+    double max_ppm;      /* its half width: drifts centre_ppm - max_ppm .. centre_ppm + max_ppm */
+    uint32_t steps;      /* K, 0 .. AM_WARP_MAX_STEPS: 2 K + 1 drifts */
+    uint32_t radius;     /* R, 0 .. AM_SEG_MAX_RADIUS: lags -R .. R */
+} am_warp_params;        /* 24 bytes, no padding */
+typedef struct am_warp_hit {
+    double drift_ppm;    /* the refined drift of the occurrence against the needle, ppm */
+    double lag;          /* l* + vertex: where the warped needle fits best, samples relative to the hit's start */
+    float ncc;           /* at the best cell */
+    float gain;          /* c / E_n there */
+    float level_db;      /* 10 log10(E_w / E_n) there */
+    float ncc_centre;    /* ncc(K, 0): before the correction */
+    uint32_t length;     /* S_q*: the occurrence's length in haystack samples */
+    uint32_t flags;      /* AM_HIT_* */
+} am_warp_hit;           /* 40 bytes, no padding */
+int am_warp_table(float* out /* AM_WARP_PHASES x AM_WARP_TAPS */);
+int am_hit_warp_device(const am_needle* h, const void* d_haystack, size_t len, int sample_format,
+                       const am_peak* peaks, size_t n, const am_warp_params* wp, am_warp_hit* out);
+int am_hit_warp(const am_needle* h, const void* haystack, size_t len, int sample_format,
+                const am_peak* peaks, size_t n, const am_warp_params* wp, am_warp_hit* out);
+/* pair (k, j) = haystack k against needle j, slots as in am_hit_scores_batch_device; untouched slots stay untouched */
+int am_hit_warp_batch_device(const am_needle* const* needles, size_t n_needles,
+                             const void* const* d_haystacks, const size_t* lens, size_t n_hay, int sample_format,
+                             const am_peak* peaks, size_t cap_per_pair, const size_t* n_peaks,
+                             const am_warp_params* wp, am_warp_hit* out);
+/* Rows on the needle's clock (pure host function, no device): am_hit_window for an occurrence at `start` whose refined
+ * lag and drift am_hit_warp reported.  Row element n (0 <= n < length) sits at needle index i = n - lead; its position in
+ * the haystack is u = (start << 32) + llround(lag 2^32) + i inc' + 2^19, inc' = llround(2^32 (1 + drift_ppm 1e-6)), in
+ * signed 128-bit arithmetic; m = u >> 32 (floor), p = (u >> 20) & 4095, and
+ *   v = fl32( fl32( sum_k (double)h[p][k] (double)x[m - 15 + k] ) * scale ),  the sum over the taps with h[p][k] != 0 in the
+ *   order k = 0, 1, ... (p = 0: the sample x[m] itself).
+ * The element is ABSENT (NaN) when a tap with h[p][k] != 0 would read outside [0, len) or a non-finite sample, or when the
+ * product is not finite.  lag = 0 and drift_ppm = 0 give am_hit_window's row bit for bit.  AM_ERR_INVALID_ARG: as
+ * am_hit_window; lag not finite or |lag| >= 2^30; |drift_ppm| > AM_WARP_MAX_PPM or not finite; start, lead, length >= 2^62. */
+int am_hit_window_warped(const void* haystack, size_t len, int sample_format, uint64_t start, float scale,
+                         double lag, double drift_ppm, uint64_t lead, uint64_t length, float* row);
 
 /* ---- device memory plumbing (for hosts without their own HIP allocator) -- */
 int am_device_malloc(int device, size_t bytes, void** out);

@@ -212,6 +212,33 @@ public:
         check(am_hit_segments_device(h_, d_haystack, len, sample_format, peaks.data(), peaks.size(), &sp, out.data()));
         return out;
     }
+    // per-hit drift scoring (am_hit_warp): each peak's clock drift, refined lag and corrected NCC over the grid wp, one
+    // record per peak
+    std::vector<am_warp_hit> hit_warp(const void* haystack, std::size_t len, int sample_format, const std::vector<am_peak>& peaks,
+                                      const am_warp_params& wp) const {
+        std::vector<am_warp_hit> out(peaks.size());
+        check(am_hit_warp(h_, haystack, len, sample_format, peaks.data(), peaks.size(), &wp, out.data()));
+        return out;
+    }
+    std::vector<am_warp_hit> hit_warp_device(const void* d_haystack, std::size_t len, int sample_format,
+                                             const std::vector<am_peak>& peaks, const am_warp_params& wp) const {
+        std::vector<am_warp_hit> out(peaks.size());
+        check(am_hit_warp_device(h_, d_haystack, len, sample_format, peaks.data(), peaks.size(), &wp, out.data()));
+        return out;
+    }
+    // the interpolator's table (am_warp_table) and one occurrence's row on the needle's clock (am_hit_window_warped); no
+    // device needed.  The batch form is am_hit_warp_batch_device of the C interface.
+    static std::vector<float> warp_table() {
+        std::vector<float> t(static_cast<std::size_t>(AM_WARP_PHASES) * AM_WARP_TAPS);
+        check(am_warp_table(t.data()));
+        return t;
+    }
+    static std::vector<float> hit_window_warped(const void* haystack, std::size_t len, int sample_format, std::uint64_t start, float scale,
+                                                double lag, double drift_ppm, std::uint64_t lead, std::uint64_t length) {
+        std::vector<float> row(length);
+        check(am_hit_window_warped(haystack, len, sample_format, start, scale, lag, drift_ppm, lead, length, row.data()));
+        return row;
+    }
     // per-band hit scoring (am_hit_bands): bp.n_bands records per peak, peak i band b at i * n_bands + b
     std::vector<am_hit_band> hit_bands(const void* haystack, std::size_t len, int sample_format, const std::vector<am_peak>& peaks,
                                        const am_band_params& bp) const {
