@@ -6,6 +6,7 @@
 #include <cstdio>
 #include <iostream>
 #include <map>
+#include <memory>
 #include <sys/stat.h>
 #include <unistd.h>
 
@@ -37,6 +38,20 @@ static void progress(void*, size_t k, int stage, size_t n_chunks) {          // 
 static std::string base_name(const std::string& path) {
     const auto slash = path.find_last_of('/');
     return slash == std::string::npos ? path : path.substr(slash + 1);
+}
+
+// Owners of the library's handles: however a scope is left (return, continue, exception), its handles are destroyed.
+struct NeedleDeleter { void operator()(am_needle* h) const { am_needle_destroy(h); } };
+struct MonitorDeleter { void operator()(am_monitor* m) const { am_monitor_destroy(m); } };
+using Needle = std::unique_ptr<am_needle, NeedleDeleter>;
+using Monitor = std::unique_ptr<am_monitor, MonitorDeleter>;
+
+// exact NCC, gain and position of n hits of a main file (--min-confidence, --learn-needle)
+static std::vector<am_hit_score> hit_scores(const am_needle* algo, const std::vector<float>& samples, const am_peak* peaks, size_t n) {
+    std::vector<am_hit_score> sc(n);
+    if (am_hit_scores(algo, samples.data(), samples.size(), AM_FMT_F32_MONO, peaks, n, sc.data()) != AM_OK)
+        throw std::runtime_error(std::string("am_hit_scores: ") + am_last_error_string());
+    return sc;
 }
 
 // extension: --bands B[:LOG2F].  One line per hit, to follow the hit's offset line (and its --segments line): the presence
@@ -151,6 +166,22 @@ static size_t warp_confidence_filter(const Arguments& args, const WarpSet& ws, a
     return kept;
 }
 
+// extension: --min-confidence X without --warp.  Keeps the hits whose exact NCC is at least X, in place; returns how many
+// are left.  With --debug one line per hit (`prefix` in front).
+static size_t confidence_filter(const Arguments& args, const am_needle* algo, const std::vector<float>& samples, am_peak* peaks, size_t n,
+                                const std::string& prefix) {
+    const std::vector<am_hit_score> sc = hit_scores(algo, samples, peaks, n);
+    size_t kept = 0;
+    for (size_t i = 0; i < n; ++i) {
+        const bool keep = sc[i].ncc >= *args.min_confidence;   // (a NaN ncc is dropped too)
+        if (args.verbosity >= 2)
+            std::printf("%shit %zu: position %.3f ncc %.6f gain %.6g window %.2f dB%s\n", prefix.c_str(), i + 1, sc[i].position,
+                        (double)sc[i].ncc, (double)sc[i].gain, (double)sc[i].window_db, keep ? "" : " (dropped)");
+        if (keep) peaks[kept++] = peaks[i];
+    }
+    return kept;
+}
+
 // extension: --min-significance Z [--significance-zone D].  Keeps the hits whose z against their local background
 // (am_hit_significance: guard = the snippet's length - 1, radius = D at the file's rate, by default three snippet
 // lengths) is at least Z, in place; returns how many are left.  With --debug one line per hit (`prefix` in front).
@@ -201,9 +232,7 @@ struct Learner {
         if (rows.empty() && !capped) { sr = m_sr; length = len; }
         if (m_sr != sr || len != length) throw std::runtime_error("--learn-needle: the main files must share one sample rate");
         // with --warp: gain, NCC, lag and drift of am_hit_warp, the row cut on the snippet's clock (am_hit_window_warped)
-        std::vector<am_hit_score> sc(args.warp_ppm ? 0 : n);
-        if (!args.warp_ppm && am_hit_scores(algo, samples.data(), samples.size(), AM_FMT_F32_MONO, peaks, n, sc.data()) != AM_OK)
-            throw std::runtime_error(std::string("am_hit_scores: ") + am_last_error_string());
+        const std::vector<am_hit_score> sc = args.warp_ppm ? std::vector<am_hit_score>() : hit_scores(algo, samples, peaks, n);
         for (size_t i = 0; i < n; ++i) {
             const std::uint32_t flags = args.warp_ppm ? w[i].flags : sc[i].flags;
             const float gain = args.warp_ppm ? w[i].gain : sc[i].gain;
@@ -291,8 +320,8 @@ static std::vector<float> filtered(const Arguments& args, std::vector<float> x, 
 
 // The handle of a snippet (rate sr) for main files of rate m_sr: resampled when the rates differ (--resample), then
 // passed through the run's filter, if any.
-static am_needle* make_needle(const Arguments& args, const std::vector<float>& data, std::uint32_t sr, std::uint32_t m_sr,
-                              const std::vector<float>& taps) {
+static am_needle* create_needle(const Arguments& args, const std::vector<float>& data, std::uint32_t sr, std::uint32_t m_sr,
+                                const std::vector<float>& taps) {
     am_needle* h = nullptr;
     if (taps.empty()) {
         if (sr == m_sr) {
@@ -317,320 +346,312 @@ static am_needle* make_needle(const Arguments& args, const std::vector<float>& d
     return h;
 }
 
-// extension: several --snippet files.  Each main file is matched by ONE am_match_multi_varlen call (the snippets may
-// differ in length: each uses an overlap of its own length at the main file's rate, as make_params does for one);
-// with --normalize, which that call refuses, snippet by snippet with am_match.  The label file is timelabel_from_peaks
-// over the hits of all snippets, sorted by start (equal starts in --snippet order).
-static int run_multi(const Arguments& args) {
-    struct Snip {
-        std::string name;
-        std::uint32_t sr = 0;
-        double duration = 0.0;
-        std::vector<float> data;
-        am_needle* h = nullptr;
-        std::map<std::uint32_t, am_needle*> resampled;
-    };
-    std::vector<Snip> snips(args.snippets.size());
-    auto release = [&]() {
-        for (Snip& sn : snips) {
-            if (sn.h) am_needle_destroy(sn.h);
-            for (auto& kv : sn.resampled) am_needle_destroy(kv.second);
-        }
-    };
-    try {
-        if (args.normalize_floor_db && am_set_option("score_norm_floor_db", *args.normalize_floor_db) != AM_OK)
-            throw std::runtime_error(std::string("--normalize-floor: ") + am_last_error_string());
-        const std::vector<float> taps = filter_taps(args);   // extension: --whiten / --preemphasis
-        for (size_t j = 0; j < snips.size(); ++j) {
-            Snip& sn = snips[j];
-            const Pcm pcm = read_wav(args.snippets[j]);
-            sn.name = base_name(args.snippets[j]);
-            sn.sr = pcm.sample_rate;
-            sn.duration = (double)pcm.frames() / (double)sn.sr;
-            sn.data = to_mono_f32(pcm, args.device);
-            sn.h = make_needle(args, sn.data, sn.sr, sn.sr, taps);
-            if (args.normalize && am_needle_set_option(sn.h, "score_norm", 1) != AM_OK)
-                throw std::runtime_error(std::string("--normalize: ") + am_last_error_string());
-        }
-        if (args.verbosity >= 2) am_set_progress_callback(progress, nullptr);
-        int rc_all = 0;
-        for (const std::string& main_file : args.within) {
-            std::optional<std::string> out_path = args.out_file;
-            if (!out_path && !args.no_out) out_path = auto_out_file(main_file);
-            if (out_path && file_exists(*out_path)) {
-                if (args.skip_existing ||
-                    ask_consent(args, "Ausgabe Datei \"" + *out_path + "\" existiert bereits, möchtest du skippen"))
-                    continue;
-                if (!ask_consent(args, "soll die existierende Datei überschrieben werden")) out_path.reset();
-            }
-            if (args.verbosity >= (args.within.size() == 1 ? 3 : 1))
-                std::printf("preparing data of '%s'\n", main_file.c_str());
-            const Pcm m = read_wav(main_file);
-            const std::uint32_t m_sr = m.sample_rate;
-            const size_t k = snips.size();
-            std::vector<const am_needle*> handles(k);
-            std::vector<std::uint64_t> overlaps(k);
-            for (size_t j = 0; j < k; ++j) {
-                Snip& sn = snips[j];
-                if (m_sr != sn.sr && !args.resample) {
-                    std::fprintf(stderr, "sample rate of snippet (%u) and main file (%u) don't match\n", sn.sr, m_sr);
-                    release();
-                    return 3;
-                }
-                am_needle* algo = sn.h;
-                overlaps[j] = make_params(args, m_sr, sn.duration).overlap;
-                if (m_sr != sn.sr) {
-                    am_needle*& h = sn.resampled[m_sr];
-                    if (!h) {
-                        h = make_needle(args, sn.data, sn.sr, m_sr, taps);
-                        if (args.normalize && am_needle_set_option(h, "score_norm", 1) != AM_OK)
-                            throw std::runtime_error(std::string("--normalize: ") + am_last_error_string());
-                    }
-                    algo = h;
-                    size_t s_len = 0;   // the overlap = the resampled snippet's length
-                    am_needle_len(algo, &s_len);
-                    overlaps[j] = s_len;
-                }
-                handles[j] = algo;
-            }
-            const std::vector<float> m_samples = filtered(args, to_mono_f32(m, args.device), taps);
-            const am_match_params p = make_params(args, m_sr, snips[0].duration);
-            size_t cap = 1024;
-            std::vector<am_peak> peaks(cap * k);
-            std::vector<size_t> n(k, 0);
-            if (args.best) {   // extension: --best N, one am_match_best per snippet
-                std::vector<std::vector<am_peak>> each(k);
-                for (size_t j = 0; j < k; ++j) {
-                    each[j] = best_hits(args, handles[j], m_samples, m_sr);
-                    n[j] = each[j].size();
-                    cap = std::max(cap, n[j]);
-                }
-                peaks.assign(cap * k, am_peak{});
-                for (size_t j = 0; j < k; ++j) std::copy(each[j].begin(), each[j].end(), peaks.begin() + (std::ptrdiff_t)(j * cap));
-            } else if (!args.normalize) {
-                int rc = am_match_multi_varlen(handles.data(), k, overlaps.data(), m_samples.data(), m_samples.size(), AM_FMT_F32_MONO, &p,
-                                               peaks.data(), cap, n.data());
-                if (rc == AM_ERR_CAPACITY) {
-                    for (size_t j = 0; j < k; ++j) cap = std::max(cap, n[j]);
-                    peaks.assign(cap * k, am_peak{});
-                    rc = am_match_multi_varlen(handles.data(), k, overlaps.data(), m_samples.data(), m_samples.size(), AM_FMT_F32_MONO, &p,
-                                               peaks.data(), cap, n.data());
-                }
-                if (rc != AM_OK) throw std::runtime_error(std::string("am_match_multi_varlen: ") + am_last_error_string());
-            } else {
-                std::vector<std::vector<am_peak>> each(k);
-                for (size_t j = 0; j < k; ++j) {
-                    am_match_params pj = p;
-                    pj.overlap = overlaps[j];
-                    each[j].resize(1024);
-                    int rc = am_match(handles[j], m_samples.data(), m_samples.size(), &pj, each[j].data(), each[j].size(), &n[j]);
-                    if (rc == AM_ERR_CAPACITY) {
-                        each[j].resize(n[j]);
-                        rc = am_match(handles[j], m_samples.data(), m_samples.size(), &pj, each[j].data(), each[j].size(), &n[j]);
-                    }
-                    if (rc != AM_OK) throw std::runtime_error(std::string("am_match: ") + am_last_error_string());
-                    cap = std::max(cap, n[j]);
-                }
-                peaks.assign(cap * k, am_peak{});
-                for (size_t j = 0; j < k; ++j) std::copy(each[j].begin(), each[j].begin() + (std::ptrdiff_t)n[j], peaks.begin() + (std::ptrdiff_t)(j * cap));
-            }
-            for (size_t j = 0; j < k; ++j) {
-                am_peak* pk = peaks.data() + j * cap;
-                const WarpSet warp = WarpSet::compute(args, handles[j], m_samples, pk, n[j]);   // extension: --warp
-                if (args.min_confidence && args.warp_ppm && n[j] > 0) {   // ... the corrected NCC decides
-                    n[j] = warp_confidence_filter(args, warp, pk, n[j], snips[j].name + ": ");
-                } else if (args.min_confidence && n[j] > 0) {   // each snippet's hits scored with that snippet's handle
-                    std::vector<am_hit_score> sc(n[j]);
-                    if (am_hit_scores(handles[j], m_samples.data(), m_samples.size(), AM_FMT_F32_MONO, pk, n[j], sc.data()) != AM_OK)
-                        throw std::runtime_error(std::string("am_hit_scores: ") + am_last_error_string());
-                    size_t kept = 0;
-                    for (size_t i = 0; i < n[j]; ++i) {
-                        if (args.verbosity >= 2)
-                            std::printf("%s: hit %zu: position %.3f ncc %.6f gain %.6g window %.2f dB%s\n", snips[j].name.c_str(), i + 1,
-                                        sc[i].position, (double)sc[i].ncc, (double)sc[i].gain, (double)sc[i].window_db,
-                                        sc[i].ncc >= *args.min_confidence ? "" : " (dropped)");
-                        if (sc[i].ncc >= *args.min_confidence) pk[kept++] = pk[i];
-                    }
-                    n[j] = kept;
-                }
-                if (args.min_significance) n[j] = significance_filter(args, handles[j], m_samples, m_sr, pk, n[j], snips[j].name + ": ");
-                if (args.verbosity >= 1) {
-                    const std::vector<std::string> lines = offset_lines(pk, n[j], m_sr);
-                    const std::vector<std::string> segs =
-                        args.segments ? segment_lines(args, handles[j], m_samples, pk, n[j]) : std::vector<std::string>();
-                    const std::vector<std::string> bands =
-                        args.bands ? band_lines(args, handles[j], m_samples, m_sr, pk, n[j]) : std::vector<std::string>();
-                    const std::vector<std::string> warps =
-                        args.warp_ppm ? warp_lines(warp.of(pk, n[j])) : std::vector<std::string>();   // extension: --warp
-                    for (size_t i = 0; i < lines.size(); ++i) {
-                        std::printf("%s: %s\n", snips[j].name.c_str(), lines[i].c_str());
-                        if (i < warps.size()) std::printf("%s: %s\n", snips[j].name.c_str(), warps[i].c_str());
-                        if (i < segs.size()) std::printf("%s: %s\n", snips[j].name.c_str(), segs[i].c_str());
-                        if (i < bands.size()) std::printf("%s: %s\n", snips[j].name.c_str(), bands[i].c_str());
-                    }
-                }
-            }
-            if (out_path) {
-                std::vector<std::pair<std::uint64_t, size_t>> order;   // (start, slot): sorted by start, then snippet, then position
-                for (size_t j = 0; j < k; ++j)
-                    for (size_t i = 0; i < n[j]; ++i) order.emplace_back(peaks[j * cap + i].start, j * cap + i);
-                std::stable_sort(order.begin(), order.end(), [](const auto& a, const auto& b) { return a.first < b.first; });
-                std::vector<am_peak> merged;
-                for (const auto& o : order) merged.push_back(peaks[o.second]);
-                const std::string text = format_labels(timelabel_from_peaks(merged.data(), merged.size(), m_sr, 7.0, "Segment #"));
-                if (args.dry_run) {
-                    std::printf("would write to '%s':\n%s", out_path->c_str(), text.c_str());
-                } else {
-                    std::ofstream f(*out_path, std::ios::binary | std::ios::trunc);
-                    if (!f) { std::fprintf(stderr, "couldn't find file '%s'\n", out_path->c_str()); rc_all = 4; continue; }
-                    f << text;
-                }
-            }
-        }
-        release();
-        return rc_all;
-    } catch (const std::exception& e) {
-        release();
-        std::fprintf(stderr, "error: %s\n", e.what());
-        return 1;
+// ... owned, and with --normalize on it
+static Needle make_needle(const Arguments& args, const std::vector<float>& data, std::uint32_t sr, std::uint32_t m_sr,
+                          const std::vector<float>& taps) {
+    Needle h(create_needle(args, data, sr, m_sr, taps));
+    if (args.normalize && am_needle_set_option(h.get(), "score_norm", 1) != AM_OK)
+        throw std::runtime_error(std::string("--normalize: ") + am_last_error_string());
+    return h;
+}
+
+// One --snippet file of the file mode: its samples, its handle at its own rate (mod.rs:29-34) and, with --resample, one
+// handle per main-file rate other than its own, made on first use and kept.
+struct Snippet {
+    std::string name;
+    std::uint32_t sr = 0;
+    double duration = 0.0;             // mod.rs:30 (mp3_duration)
+    std::vector<float> data;
+    Needle h;
+    std::map<std::uint32_t, Needle> resampled;
+};
+
+// taps: the run's filter; where it is not designed yet, it is designed between reading the snippet and creating its handle
+static Snippet load_snippet(const Arguments& args, const std::string& path, std::optional<std::vector<float>>& taps) {
+    Snippet sn;
+    const Pcm pcm = read_wav(path);
+    sn.name = base_name(path);
+    sn.sr = pcm.sample_rate;
+    sn.duration = (double)pcm.frames() / (double)sn.sr;
+    sn.data = to_mono_f32(pcm, args.device);
+    if (!taps) taps = filter_taps(args);
+    sn.h = make_needle(args, sn.data, sn.sr, sn.sr, *taps);
+    return sn;
+}
+
+// The handle of sn for a main file of rate m_sr, and the overlap it is matched with: the snippet's length at that rate
+// (as make_params rounds it; the resampled handle's own length where the rates differ).
+static const am_needle* needle_at(const Arguments& args, Snippet& sn, std::uint32_t m_sr, const std::vector<float>& taps, std::uint64_t& overlap) {
+    overlap = make_params(args, m_sr, sn.duration).overlap;
+    if (m_sr == sn.sr) return sn.h.get();
+    Needle& h = sn.resampled[m_sr];
+    if (!h) h = make_needle(args, sn.data, sn.sr, m_sr, taps);
+    size_t s_len = 0;
+    am_needle_len(h.get(), &s_len);
+    overlap = s_len;
+    return h.get();
+}
+
+// mod.rs:44-66: where a main file's labels go (nowhere: --no-out, or an existing file that is not to be overwritten);
+// false = the main file is skipped, because its output exists.
+static bool output_path(const Arguments& args, const std::string& main_file, std::optional<std::string>& out_path) {
+    out_path = args.out_file;
+    if (!out_path && !args.no_out) out_path = auto_out_file(main_file);
+    if (out_path && file_exists(*out_path)) {
+        if (args.skip_existing || ask_consent(args, "Ausgabe Datei \"" + *out_path + "\" existiert bereits, möchtest du skippen"))
+            return false;
+        if (!ask_consent(args, "soll die existierende Datei überschrieben werden")) out_path.reset();
     }
+    return true;
+}
+
+// mod.rs:92-99: the label file of a recording's hits (sorted by start), or with --dry-run its text on stdout.  Returns the
+// exit status this asks for: 0, or 4 where the file cannot be written.
+static int write_labels(const Arguments& args, const std::string& out_path, const std::vector<am_peak>& hits, std::uint32_t sr) {
+    const std::string text = format_labels(timelabel_from_peaks(hits.data(), hits.size(), sr, 7.0, "Segment #"));
+    if (args.dry_run) {
+        std::printf("would write to '%s':\n%s", out_path.c_str(), text.c_str());
+        return 0;
+    }
+    std::ofstream f(out_path, std::ios::binary | std::ios::trunc);
+    if (!f) { std::fprintf(stderr, "couldn't find file '%s'\n", out_path.c_str()); return 4; }
+    f << text;
+    return 0;
+}
+
+// mod.rs:81-87: the hits of one snippet in one main file
+static std::vector<am_peak> match_hits(const am_needle* algo, const std::vector<float>& samples, const am_match_params& p) {
+    std::vector<am_peak> peaks(1024);
+    size_t n = 0;
+    int rc = am_match(algo, samples.data(), samples.size(), &p, peaks.data(), peaks.size(), &n);
+    if (rc == AM_ERR_CAPACITY) {
+        peaks.resize(n);
+        rc = am_match(algo, samples.data(), samples.size(), &p, peaks.data(), peaks.size(), &n);
+    }
+    if (rc != AM_OK) throw std::runtime_error(std::string("am_match: ") + am_last_error_string());
+    peaks.resize(n);
+    return peaks;
+}
+
+// extension: several --snippet files without --normalize and --best.  ONE am_match_multi_varlen call for a main file (the
+// snippets may differ in length: each is matched with its own overlap); [j] = the hits of snippet j.
+static std::vector<std::vector<am_peak>> match_hits_multi(const std::vector<const am_needle*>& handles, const std::vector<std::uint64_t>& overlaps,
+                                                          const std::vector<float>& samples, const am_match_params& p) {
+    const size_t k = handles.size();
+    size_t cap = 1024;
+    std::vector<am_peak> peaks(cap * k);
+    std::vector<size_t> n(k, 0);
+    int rc = am_match_multi_varlen(handles.data(), k, overlaps.data(), samples.data(), samples.size(), AM_FMT_F32_MONO, &p, peaks.data(), cap, n.data());
+    if (rc == AM_ERR_CAPACITY) {
+        for (size_t j = 0; j < k; ++j) cap = std::max(cap, n[j]);
+        peaks.assign(cap * k, am_peak{});
+        rc = am_match_multi_varlen(handles.data(), k, overlaps.data(), samples.data(), samples.size(), AM_FMT_F32_MONO, &p, peaks.data(), cap, n.data());
+    }
+    if (rc != AM_OK) throw std::runtime_error(std::string("am_match_multi_varlen: ") + am_last_error_string());
+    std::vector<std::vector<am_peak>> each(k);
+    for (size_t j = 0; j < k; ++j) each[j].assign(peaks.begin() + (std::ptrdiff_t)(j * cap), peaks.begin() + (std::ptrdiff_t)(j * cap + n[j]));
+    return each;
+}
+
+// One snippet's hits in one main file, from the match to the report: the filters (--min-confidence, on the corrected NCC
+// with --warp; --min-significance) drop hits from `hits`, the learner takes its rows of those that are left, and they
+// are printed, every line with `prefix` in front: the offset line (mod.rs:89) and under it the hit's --warp, --segments
+// and --bands lines.
+static void report_hits(const Arguments& args, const am_needle* algo, const std::vector<float>& m_samples, std::uint32_t m_sr,
+                        std::vector<am_peak>& hits, const std::string& prefix, Learner& learner) {
+    am_peak* pk = hits.data();
+    size_t n = hits.size();
+    const WarpSet warp = WarpSet::compute(args, algo, m_samples, pk, n);
+    if (args.min_confidence && n > 0)
+        n = args.warp_ppm ? warp_confidence_filter(args, warp, pk, n, prefix) : confidence_filter(args, algo, m_samples, pk, n, prefix);
+    if (args.min_significance) n = significance_filter(args, algo, m_samples, m_sr, pk, n, prefix);
+    hits.resize(n);
+    if (!args.learn_needle.empty()) learner.take(args, algo, m_samples, m_sr, pk, n, warp.of(pk, n));
+    if (args.verbosity < 1) return;
+    const std::vector<std::string> none;
+    const std::vector<std::string> lines = offset_lines(pk, n, m_sr);
+    const std::vector<std::string> segs = args.segments ? segment_lines(args, algo, m_samples, pk, n) : none;
+    const std::vector<std::string> bands = args.bands ? band_lines(args, algo, m_samples, m_sr, pk, n) : none;
+    const std::vector<std::string> warps = args.warp_ppm ? warp_lines(warp.of(pk, n)) : none;
+    for (size_t i = 0; i < lines.size(); ++i)
+        for (const std::vector<std::string>* l : {&lines, &warps, &segs, &bands})
+            if (i < l->size()) std::printf("%s%s\n", prefix.c_str(), (*l)[i].c_str());
+}
+
+// The file mode: the per-file loop of matcher::run (mod.rs:42-100) for one or several --snippet files.  One snippet is
+// matched by am_match, as the reference does.  Several (an extension) are matched by ONE am_match_multi_varlen call for a
+// main file; with --normalize, which that call refuses, snippet by snippet with am_match; every line of a snippet's
+// report then starts with the snippet's file name, and the label file holds the hits of all snippets, sorted by start
+// (equal starts in --snippet order).  --best N (an extension) takes am_match_best's hits instead, snippet by snippet.
+static int run_files(const Arguments& args) {
+    // (set ahead of everything else: the parser admits 0..200 only, which is the option's whole range, so the call
+    // cannot fail, and the library reads the value when a call is made, not when a handle is created)
+    if (args.normalize_floor_db && am_set_option("score_norm_floor_db", *args.normalize_floor_db) != AM_OK)
+        throw std::runtime_error(std::string("--normalize-floor: ") + am_last_error_string());
+    const size_t k = args.snippets.size();
+    // extension: --whiten / --preemphasis.  Designing the filter reads the main files: with several snippets ahead of
+    // the first snippet, with one after it (load_snippet) -- which of two unreadable files an error names
+    std::optional<std::vector<float>> taps;
+    if (k > 1) taps = filter_taps(args);
+    std::vector<Snippet> snips;
+    for (const std::string& path : args.snippets) snips.push_back(load_snippet(args, path, taps));
+    if (args.verbosity >= 2) am_set_progress_callback(progress, nullptr);
+    int rc_all = 0;
+    Learner learner;                                                      // extension: --learn-needle (one snippet only)
+    for (const std::string& main_file : args.within) {                    // mod.rs:42
+        std::optional<std::string> out_path;
+        if (!output_path(args, main_file, out_path)) continue;
+        if (args.verbosity >= (args.within.size() == 1 ? 3 : 1))
+            std::printf("preparing data of '%s'\n", main_file.c_str());
+        const Pcm m = read_wav(main_file);                                // mod.rs:71
+        const std::uint32_t m_sr = m.sample_rate;
+        std::vector<const am_needle*> handles(k);
+        std::vector<std::uint64_t> overlaps(k);
+        for (size_t j = 0; j < k; ++j) {
+            if (m_sr != snips[j].sr && !args.resample) {                  // mod.rs:72-74 SampleRateMismatch
+                std::fprintf(stderr, "sample rate of snippet (%u) and main file (%u) don't match\n", snips[j].sr, m_sr);
+                return 3;
+            }
+            handles[j] = needle_at(args, snips[j], m_sr, *taps, overlaps[j]);
+        }
+        const std::vector<float> m_samples = filtered(args, to_mono_f32(m, args.device), *taps);
+        am_match_params p = make_params(args, m_sr, snips[0].duration);
+        std::vector<std::vector<am_peak>> hits(k);
+        if (k > 1 && !args.best && !args.normalize) {
+            hits = match_hits_multi(handles, overlaps, m_samples, p);
+        } else {
+            for (size_t j = 0; j < k; ++j) {
+                p.overlap = overlaps[j];
+                hits[j] = args.best ? best_hits(args, handles[j], m_samples, m_sr) : match_hits(handles[j], m_samples, p);
+            }
+        }
+        for (size_t j = 0; j < k; ++j)
+            report_hits(args, handles[j], m_samples, m_sr, hits[j], k > 1 ? snips[j].name + ": " : std::string(), learner);
+        if (out_path) {                                                   // mod.rs:92-99
+            std::vector<am_peak> all;
+            for (const std::vector<am_peak>& h : hits) all.insert(all.end(), h.begin(), h.end());
+            if (k > 1) std::stable_sort(all.begin(), all.end(), [](const am_peak& a, const am_peak& b) { return a.start < b.start; });
+            if (const int rc = write_labels(args, *out_path, all, m_sr)) rc_all = rc;
+        }
+    }
+    if (!args.learn_needle.empty())
+        if (const int rc = learner.finish(args)) rc_all = rc;
+    return rc_all;
 }
 
 // extension: --live.  Raw PCM from stdin through one monitor (am_monitor_*, all snippets in it): every chunk of input is
 // turned into the f32 mono samples the file mode would have made of the same frames (to_mono_f32), pushed, and the hits
 // that became final are printed at once, numbered per snippet as the file mode numbers them.  At end of input the
-// label file is written exactly as the file mode writes it for that recording (timelabel_from_peaks over the hits of
-// all snippets by start, equal starts in --snippet order: the monitor's own order).
+// label file is written exactly as the file mode writes it for that recording (the hits of all snippets by start, equal
+// starts in --snippet order: the monitor's own order).
 static int run_live(const Arguments& args) {
     struct Snip {
         std::string name;
-        am_needle* h = nullptr;
-        am_needle* resampled = nullptr;
+        Needle h, resampled;
         am_match_params p{};
         size_t hits = 0;
     };
     const std::uint32_t sr = args.rate;
     const size_t k = args.snippets.size();
     std::vector<Snip> snips(k);
-    am_monitor* mon = nullptr;
-    auto release = [&]() {
-        if (mon) am_monitor_destroy(mon);
-        for (Snip& sn : snips) {
-            if (sn.h) am_needle_destroy(sn.h);
-            if (sn.resampled) am_needle_destroy(sn.resampled);
+    std::vector<const am_needle*> handles(k);
+    std::vector<am_match_params> params(k);
+    for (size_t j = 0; j < k; ++j) {
+        Snip& sn = snips[j];
+        const Pcm pcm = read_wav(args.snippets[j]);
+        sn.name = base_name(args.snippets[j]);
+        const double duration = (double)pcm.frames() / (double)pcm.sample_rate;
+        const std::vector<float> data = to_mono_f32(pcm, args.device);
+        am_needle* h = nullptr;
+        if (am_needle_create(args.device, data.data(), data.size(), &h) != AM_OK)
+            throw std::runtime_error(std::string("am_needle_create: ") + am_last_error_string());
+        sn.h.reset(h);
+        sn.p = make_params(args, sr, duration);
+        handles[j] = sn.h.get();
+        if (pcm.sample_rate != sr) {
+            if (!args.resample) {
+                std::fprintf(stderr, "sample rate of snippet (%u) and main file (%u) don't match\n", pcm.sample_rate, sr);
+                return 3;
+            }
+            am_needle* r = nullptr;
+            if (am_needle_create_resampled(args.device, data.data(), data.size(), AM_FMT_F32_MONO, pcm.sample_rate, sr, &r) != AM_OK)
+                throw std::runtime_error(std::string("am_needle_create_resampled: ") + am_last_error_string());
+            sn.resampled.reset(r);
+            size_t s_len = 0;   // the overlap = the resampled snippet's length
+            am_needle_len(sn.resampled.get(), &s_len);
+            sn.p.overlap = s_len;
+            handles[j] = sn.resampled.get();
         }
-    };
-    try {
-        std::vector<const am_needle*> handles(k);
-        std::vector<am_match_params> params(k);
-        for (size_t j = 0; j < k; ++j) {
-            Snip& sn = snips[j];
-            const Pcm pcm = read_wav(args.snippets[j]);
-            sn.name = base_name(args.snippets[j]);
-            const double duration = (double)pcm.frames() / (double)pcm.sample_rate;
-            const std::vector<float> data = to_mono_f32(pcm, args.device);
-            if (am_needle_create(args.device, data.data(), data.size(), &sn.h) != AM_OK)
-                throw std::runtime_error(std::string("am_needle_create: ") + am_last_error_string());
-            sn.p = make_params(args, sr, duration);
-            handles[j] = sn.h;
-            if (pcm.sample_rate != sr) {
-                if (!args.resample) {
-                    std::fprintf(stderr, "sample rate of snippet (%u) and main file (%u) don't match\n", pcm.sample_rate, sr);
-                    release();
-                    return 3;
-                }
-                if (am_needle_create_resampled(args.device, data.data(), data.size(), AM_FMT_F32_MONO, pcm.sample_rate, sr, &sn.resampled) != AM_OK)
-                    throw std::runtime_error(std::string("am_needle_create_resampled: ") + am_last_error_string());
-                size_t s_len = 0;   // the overlap = the resampled snippet's length
-                am_needle_len(sn.resampled, &s_len);
-                sn.p.overlap = s_len;
-                handles[j] = sn.resampled;
-            }
-            params[j] = sn.p;
-        }
-        if (am_monitor_begin(handles.data(), k, params.data(), AM_FMT_F32_MONO, 1, &mon) != AM_OK)
-            throw std::runtime_error(std::string("am_monitor_begin: ") + am_last_error_string());
-        std::vector<am_peak> all;            // every hit, in the monitor's order: (start, snippet)
-        std::vector<am_peak> got(256);
-        std::vector<std::uint32_t> which(256);
-        auto report = [&](size_t n) {
-            for (size_t i = 0; i < n; ++i) {
-                Snip& sn = snips[which[i]];
-                if (args.verbosity >= 1) {
-                    const std::string line = offset_line(got[i], sn.hits, sr);
-                    if (k > 1) std::printf("%s: %s\n", sn.name.c_str(), line.c_str());
-                    else std::printf("%s\n", line.c_str());
-                }
-                ++sn.hits;
-                all.push_back(got[i]);
-            }
-            std::fflush(stdout);
-        };
-        auto take = [&](int (*fn)(am_monitor*, am_peak*, std::uint32_t*, size_t, size_t*), const char* what) {
-            size_t n = 0;
-            int rc = fn(mon, got.data(), which.data(), got.size(), &n);
-            if (rc == AM_ERR_CAPACITY) {
-                got.resize(n); which.resize(n);
-                rc = fn(mon, got.data(), which.data(), got.size(), &n);
-            }
-            if (rc != AM_OK) throw std::runtime_error(std::string(what) + ": " + am_last_error_string());
-            report(n);
-        };
-        // stdin in pieces as they come (read(2): a pipe hands over what it holds), whole frames only
-        const size_t in_frame = (args.encoding == "f32le" ? 4u : 2u) * (size_t)args.channels;
-        std::vector<char> raw((size_t)1 << 16);
-        size_t have = 0;
-        Pcm piece;
-        piece.sample_rate = sr;
-        piece.channels = (std::uint16_t)args.channels;
-        piece.is_float = args.encoding == "f32le";
-        for (;;) {
-            const ssize_t got_bytes = ::read(0, raw.data() + have, raw.size() - have);
-            if (got_bytes < 0) throw std::runtime_error("reading stdin failed");
-            if (got_bytes == 0) break;
-            have += (size_t)got_bytes;
-            const size_t frames = have / in_frame;
-            if (frames == 0) continue;
-            if (piece.is_float) {
-                piece.f32.resize(frames);
-                std::memcpy(piece.f32.data(), raw.data(), frames * 4);
-            } else {
-                piece.s16.resize(frames * (size_t)args.channels);
-                std::memcpy(piece.s16.data(), raw.data(), frames * in_frame);
-            }
-            const std::vector<float> mono = to_mono_f32(piece, args.device);
-            if (am_monitor_push(mon, mono.data(), mono.size()) != AM_OK)
-                throw std::runtime_error(std::string("am_monitor_push: ") + am_last_error_string());
-            take(am_monitor_poll, "am_monitor_poll");
-            std::memmove(raw.data(), raw.data() + frames * in_frame, have - frames * in_frame);
-            have -= frames * in_frame;
-        }
-        take(am_monitor_end, "am_monitor_end");
-        if (args.verbosity >= 1)
-            for (const Snip& sn : snips)
-                if (sn.hits == 0) {
-                    if (k > 1) std::printf("%s: no offsets found\n", sn.name.c_str());
-                    else std::printf("no offsets found\n");
-                }
-        std::fflush(stdout);
-        int rc_all = 0;
-        if (args.out_file && !args.no_out) {
-            const std::string text = format_labels(timelabel_from_peaks(all.data(), all.size(), sr, 7.0, "Segment #"));
-            if (args.dry_run) {
-                std::printf("would write to '%s':\n%s", args.out_file->c_str(), text.c_str());
-            } else {
-                std::ofstream f(*args.out_file, std::ios::binary | std::ios::trunc);
-                if (!f) { std::fprintf(stderr, "couldn't find file '%s'\n", args.out_file->c_str()); rc_all = 4; }
-                else f << text;
-            }
-        }
-        release();
-        return rc_all;
-    } catch (const std::exception& e) {
-        release();
-        std::fprintf(stderr, "error: %s\n", e.what());
-        return 1;
+        params[j] = sn.p;
     }
+    am_monitor* opened = nullptr;
+    if (am_monitor_begin(handles.data(), k, params.data(), AM_FMT_F32_MONO, 1, &opened) != AM_OK)
+        throw std::runtime_error(std::string("am_monitor_begin: ") + am_last_error_string());
+    const Monitor mon(opened);           // (declared after snips: destroyed ahead of the handles it holds)
+    std::vector<am_peak> all;            // every hit, in the monitor's order: (start, snippet)
+    std::vector<am_peak> got(256);
+    std::vector<std::uint32_t> which(256);
+    auto report = [&](size_t n) {
+        for (size_t i = 0; i < n; ++i) {
+            Snip& sn = snips[which[i]];
+            if (args.verbosity >= 1) {
+                const std::string line = offset_line(got[i], sn.hits, sr);
+                if (k > 1) std::printf("%s: %s\n", sn.name.c_str(), line.c_str());
+                else std::printf("%s\n", line.c_str());
+            }
+            ++sn.hits;
+            all.push_back(got[i]);
+        }
+        std::fflush(stdout);
+    };
+    auto take = [&](int (*fn)(am_monitor*, am_peak*, std::uint32_t*, size_t, size_t*), const char* what) {
+        size_t n = 0;
+        int rc = fn(mon.get(), got.data(), which.data(), got.size(), &n);
+        if (rc == AM_ERR_CAPACITY) {
+            got.resize(n); which.resize(n);
+            rc = fn(mon.get(), got.data(), which.data(), got.size(), &n);
+        }
+        if (rc != AM_OK) throw std::runtime_error(std::string(what) + ": " + am_last_error_string());
+        report(n);
+    };
+    // stdin in pieces as they come (read(2): a pipe hands over what it holds), whole frames only
+    const size_t in_frame = (args.encoding == "f32le" ? 4u : 2u) * (size_t)args.channels;
+    std::vector<char> raw((size_t)1 << 16);
+    size_t have = 0;
+    Pcm piece;
+    piece.sample_rate = sr;
+    piece.channels = (std::uint16_t)args.channels;
+    piece.is_float = args.encoding == "f32le";
+    for (;;) {
+        const ssize_t got_bytes = ::read(0, raw.data() + have, raw.size() - have);
+        if (got_bytes < 0) throw std::runtime_error("reading stdin failed");
+        if (got_bytes == 0) break;
+        have += (size_t)got_bytes;
+        const size_t frames = have / in_frame;
+        if (frames == 0) continue;
+        if (piece.is_float) {
+            piece.f32.resize(frames);
+            std::memcpy(piece.f32.data(), raw.data(), frames * 4);
+        } else {
+            piece.s16.resize(frames * (size_t)args.channels);
+            std::memcpy(piece.s16.data(), raw.data(), frames * in_frame);
+        }
+        const std::vector<float> mono = to_mono_f32(piece, args.device);
+        if (am_monitor_push(mon.get(), mono.data(), mono.size()) != AM_OK)
+            throw std::runtime_error(std::string("am_monitor_push: ") + am_last_error_string());
+        take(am_monitor_poll, "am_monitor_poll");
+        std::memmove(raw.data(), raw.data() + frames * in_frame, have - frames * in_frame);
+        have -= frames * in_frame;
+    }
+    take(am_monitor_end, "am_monitor_end");
+    if (args.verbosity >= 1)
+        for (const Snip& sn : snips)
+            if (sn.hits == 0) {
+                if (k > 1) std::printf("%s: no offsets found\n", sn.name.c_str());
+                else std::printf("no offsets found\n");
+            }
+    std::fflush(stdout);
+    return args.out_file && !args.no_out ? write_labels(args, *args.out_file, all, sr) : 0;
 }
 
 int main(int argc, char** argv) {
@@ -645,123 +666,8 @@ int main(int argc, char** argv) {
         std::printf("%s", usage_text());
         return 0;
     }
-    if (args.live) return run_live(args);
-    if (args.snippets.size() > 1) return run_multi(args);
     try {
-        const Pcm snippet = read_wav(args.snippet);                           // mod.rs:29
-        const std::uint32_t sr = snippet.sample_rate;
-        const double s_duration = (double)snippet.frames() / (double)sr;      // mod.rs:30 (mp3_duration)
-        const std::vector<float> sample_data = to_mono_f32(snippet, args.device);   // mod.rs:32
-        const std::vector<float> taps = filter_taps(args);                    // extension: --whiten / --preemphasis
-        am_needle* snippet_algo = make_needle(args, sample_data, sr, sr, taps);   // mod.rs:34: LibConvolve::new
-        if (args.normalize_floor_db && am_set_option("score_norm_floor_db", *args.normalize_floor_db) != AM_OK)
-            throw std::runtime_error(std::string("--normalize-floor: ") + am_last_error_string());
-        if (args.normalize && am_needle_set_option(snippet_algo, "score_norm", 1) != AM_OK)
-            throw std::runtime_error(std::string("--normalize: ") + am_last_error_string());
-        // extension --resample: one handle per main-file rate other than the snippet's, made on first use and kept
-        std::map<std::uint32_t, am_needle*> resampled;
-        if (args.verbosity >= 2) am_set_progress_callback(progress, nullptr);
-        int rc_all = 0;
-        Learner learner;                                                      // extension: --learn-needle
-        for (const std::string& main_file : args.within) {                    // mod.rs:42
-            std::optional<std::string> out_path = args.out_file;
-            if (!out_path && !args.no_out) out_path = auto_out_file(main_file);
-            if (out_path && file_exists(*out_path)) {                         // mod.rs:48-66
-                if (args.skip_existing ||
-                    ask_consent(args, "Ausgabe Datei \"" + *out_path + "\" existiert bereits, möchtest du skippen"))
-                    continue;
-                if (!ask_consent(args, "soll die existierende Datei überschrieben werden")) out_path.reset();
-            }
-            if (args.verbosity >= (args.within.size() == 1 ? 3 : 1))
-                std::printf("preparing data of '%s'\n", main_file.c_str());
-            const Pcm m = read_wav(main_file);                                // mod.rs:71
-            am_needle* algo = snippet_algo;
-            if (m.sample_rate != sr && !args.resample) {                      // mod.rs:72-74 SampleRateMismatch
-                std::fprintf(stderr, "sample rate of snippet (%u) and main file (%u) don't match\n", sr, m.sample_rate);
-                return 3;
-            }
-            if (m.sample_rate != sr) {                                        // extension: --resample
-                am_needle*& h = resampled[m.sample_rate];
-                if (!h) {
-                    h = make_needle(args, sample_data, sr, m.sample_rate, taps);
-                    if (args.normalize && am_needle_set_option(h, "score_norm", 1) != AM_OK)
-                        throw std::runtime_error(std::string("--normalize: ") + am_last_error_string());
-                }
-                algo = h;
-            }
-            const std::uint32_t m_sr = m.sample_rate;
-            const std::vector<float> m_samples = filtered(args, to_mono_f32(m, args.device), taps);
-            am_match_params p = make_params(args, m_sr, s_duration);          // mod.rs:81-87
-            if (m_sr != sr) {                                                 // the overlap = the resampled snippet's length
-                size_t s_len = 0;
-                am_needle_len(algo, &s_len);
-                p.overlap = s_len;
-            }
-            std::vector<am_peak> peaks(1024);
-            size_t n = 0;
-            if (args.best) {                                                  // extension: --best N
-                peaks = best_hits(args, algo, m_samples, m_sr);
-                n = peaks.size();
-            } else {
-                int rc = am_match(algo, m_samples.data(), m_samples.size(), &p, peaks.data(), peaks.size(), &n);
-                if (rc == AM_ERR_CAPACITY) {
-                    peaks.resize(n);
-                    rc = am_match(algo, m_samples.data(), m_samples.size(), &p, peaks.data(), peaks.size(), &n);
-                }
-                if (rc != AM_OK) throw std::runtime_error(std::string("am_match: ") + am_last_error_string());
-            }
-            const WarpSet warp = WarpSet::compute(args, algo, m_samples, peaks.data(), n);   // extension: --warp
-            if (args.min_confidence && args.warp_ppm && n > 0) {              // ... the corrected NCC decides
-                n = warp_confidence_filter(args, warp, peaks.data(), n, "");
-            } else if (args.min_confidence && n > 0) {                        // extension: --min-confidence
-                std::vector<am_hit_score> sc(n);
-                if (am_hit_scores(algo, m_samples.data(), m_samples.size(), AM_FMT_F32_MONO, peaks.data(), n, sc.data()) != AM_OK)
-                    throw std::runtime_error(std::string("am_hit_scores: ") + am_last_error_string());
-                size_t kept = 0;
-                for (size_t i = 0; i < n; ++i) {
-                    if (args.verbosity >= 2)
-                        std::printf("hit %zu: position %.3f ncc %.6f gain %.6g window %.2f dB%s\n", i + 1, sc[i].position,
-                                    (double)sc[i].ncc, (double)sc[i].gain, (double)sc[i].window_db,
-                                    sc[i].ncc >= *args.min_confidence ? "" : " (dropped)");
-                    if (sc[i].ncc >= *args.min_confidence) peaks[kept++] = peaks[i];   // (a NaN ncc is dropped too)
-                }
-                n = kept;
-            }
-            if (args.min_significance) n = significance_filter(args, algo, m_samples, m_sr, peaks.data(), n, "");   // extension: --min-significance
-            if (!args.learn_needle.empty()) learner.take(args, algo, m_samples, m_sr, peaks.data(), n, warp.of(peaks.data(), n));           // extension: --learn-needle
-            if (args.verbosity >= 1) {
-                const std::vector<std::string> lines = offset_lines(peaks.data(), n, m_sr);                       // mod.rs:89
-                const std::vector<std::string> segs =
-                    args.segments ? segment_lines(args, algo, m_samples, peaks.data(), n) : std::vector<std::string>();   // extension: --segments
-                const std::vector<std::string> bands =
-                    args.bands ? band_lines(args, algo, m_samples, m_sr, peaks.data(), n) : std::vector<std::string>();   // extension: --bands
-                const std::vector<std::string> warps =
-                    args.warp_ppm ? warp_lines(warp.of(peaks.data(), n)) : std::vector<std::string>();   // extension: --warp
-                for (size_t i = 0; i < lines.size(); ++i) {
-                    std::printf("%s\n", lines[i].c_str());
-                    if (i < warps.size()) std::printf("%s\n", warps[i].c_str());
-                    if (i < segs.size()) std::printf("%s\n", segs[i].c_str());
-                    if (i < bands.size()) std::printf("%s\n", bands[i].c_str());
-                }
-            }
-            if (out_path) {                                                   // mod.rs:92-99
-                const std::string text = format_labels(timelabel_from_peaks(peaks.data(), n, m_sr, 7.0, "Segment #"));
-                if (args.dry_run) {
-                    std::printf("would write to '%s':\n%s", out_path->c_str(), text.c_str());
-                } else {
-                    std::ofstream f(*out_path, std::ios::binary | std::ios::trunc);
-                    if (!f) { std::fprintf(stderr, "couldn't find file '%s'\n", out_path->c_str()); rc_all = 4; continue; }
-                    f << text;
-                }
-            }
-        }
-        if (!args.learn_needle.empty()) {
-            const int rc = learner.finish(args);
-            if (rc) rc_all = rc;
-        }
-        am_needle_destroy(snippet_algo);
-        for (auto& kv : resampled) am_needle_destroy(kv.second);
-        return rc_all;
+        return args.live ? run_live(args) : run_files(args);
     } catch (const std::exception& e) {
         std::fprintf(stderr, "error: %s\n", e.what());
         return 1;

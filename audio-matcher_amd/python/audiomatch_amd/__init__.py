@@ -666,11 +666,6 @@ def warp_params(max_ppm: float, steps: int = 8, radius: int = 4, centre_ppm: flo
     return AmWarpParams(float(centre_ppm), float(max_ppm), int(steps), int(radius))
 
 
-def _hit_warps(buf, idx):
-    """Copies of the records (they outlive the call's buffer)."""
-    return [HitWarp.from_buffer_copy(bytes(buf[i])) for i in idx]
-
-
 def _estimate_out(length: int):
     return np.empty(length, dtype=np.float32), np.empty(length, dtype=np.float32), np.empty(length, dtype=np.uint32)
 
@@ -749,24 +744,13 @@ class HitScore:
     flags: int
 
 
+def _am_peak(q) -> AmPeak:
+    return AmPeak(int(q.start), int(q.end), float(q.height), float(q.prominence))
+
+
 def _peak_array(peaks):
     k = len(peaks)
-    return (AmPeak * max(1, k))(*[AmPeak(int(q.start), int(q.end), float(q.height), float(q.prominence)) for q in peaks])
-
-
-def _hit_scores(buf, idx):
-    return [HitScore(buf[i].position, buf[i].ncc, buf[i].gain, buf[i].window_db, int(buf[i].flags)) for i in idx]
-
-
-def _hit_significance(buf, idx):
-    """Copies of the records at `idx` (they outlive the call's buffer)."""
-    return [HitSignificance.from_buffer_copy(buf[i]) for i in idx]
-
-
-def _hit_segments(buf, first, m):
-    """The m records of one hit as a list of HitSegment (copies: they outlive the call's buffer)."""
-    return [HitSegment(buf[first + j].lag, buf[first + j].ncc, buf[first + j].gain, buf[first + j].level_db,
-                       buf[first + j].flags) for j in range(m)]
+    return (AmPeak * max(1, k))(*[_am_peak(q) for q in peaks])
 
 
 @dataclass
@@ -808,11 +792,6 @@ def band_edges_log(sr: int, frame_log2: int, lo_hz: float, hi_hz: float, n_bands
     return out
 
 
-def _hit_bands(buf, first, nb):
-    """The nb records of one hit as a list of HitBand (copies: they outlive the call's buffer)."""
-    return [HitBand.from_buffer_copy(buf[first + b]) for b in range(nb)]
-
-
 @dataclass
 class BandSummary:
     """am_band_summary: how much of the needle's spectrum one hit holds, from its band records."""
@@ -833,6 +812,74 @@ def hit_bands_summary(bands, min_coherence: float = 0.5) -> BandSummary:
     _check(lib().am_hit_bands_summary(buf, nb, float(min_coherence), C.byref(out)))
     return BandSummary(out.coverage, out.weighted_coherence, out.gain_db_spread, out.first_present, out.last_present,
                        out.n_present, out.n_countable)
+
+
+# ---------------------------------------------------------------------------
+# Per-hit records.  A family is one kind of record: `symbol` names its host entry point (symbol + "_device" and symbol +
+# "_batch_device" are the other two), `record` is its ctypes type, params(*public arguments after the peaks) gives the
+# parameter struct (None: the family has none) and m, the records per hit, and unpack(out, i, m) is what the caller gets
+# for hit i of the call -- one object, or the list of its m records.  Every unpacked record is a copy: it outlives `out`.
+class _HitFamily:
+    def __init__(self, symbol, record, params, unpack):
+        self.symbol, self.record, self.params, self.unpack = symbol, record, params, unpack
+
+
+_SCORES = _HitFamily(
+    "am_hit_scores", AmHitScore, lambda: (None, 1),
+    lambda out, i, m: HitScore(out[i].position, out[i].ncc, out[i].gain, out[i].window_db, int(out[i].flags)))
+_SEGMENTS = _HitFamily(
+    "am_hit_segments", HitSegment, lambda segments, radius: (AmSegmentParams(int(segments), int(radius)), int(segments)),
+    lambda out, i, m: [HitSegment(q.lag, q.ncc, q.gain, q.level_db, q.flags) for q in (out[i * m + j] for j in range(m))])
+_WARP = _HitFamily(
+    "am_hit_warp", HitWarp, lambda wp: (wp, 1), lambda out, i, m: HitWarp.from_buffer_copy(bytes(out[i])))
+_BANDS = _HitFamily(
+    "am_hit_bands", HitBand, lambda bp: (bp, int(bp.n_bands)),
+    lambda out, i, m: [HitBand.from_buffer_copy(out[i * m + b]) for b in range(m)])
+_SIGNIFICANCE = _HitFamily(
+    "am_hit_significance", HitSignificance, lambda guard, radius: (AmSignificanceParams(int(guard), int(radius)), 1),
+    lambda out, i, m: HitSignificance.from_buffer_copy(out[i]))
+
+
+def _hit_call(fam, form, lead, n_hits, args):
+    """One form's call: `lead`, then the parameter struct if the family has one, then `out`, sized for n_hits hits (a
+    negative m sizes it as 0 and goes to the library, which refuses it).  Returns (out, m)."""
+    params, m = fam.params(*args)
+    out = (fam.record * max(1, n_hits * max(m, 0)))()
+    tail = (out,) if params is None else (C.byref(params), out)
+    _check(getattr(lib(), fam.symbol + form)(*lead, *tail))
+    return out, m
+
+
+def _hit_device(fam, algo, ptr, length, peaks, fmt, args, form="_device"):
+    """[i] = the records of peaks[i] in a haystack resident on the needle's device."""
+    k = len(peaks)
+    out, m = _hit_call(fam, form, (algo._h, ptr, length, int(fmt), _peak_array(peaks), k), k, args)
+    return [fam.unpack(out, i, m) for i in range(k)]
+
+
+def _hit_host(fam, algo, haystack, peaks, args):
+    """The same for a host haystack: an f32 array, or an i16 (frames, 2) array of interleaved stereo."""
+    a, fmt, length = _samples(haystack)
+    return _hit_device(fam, algo, a.ctypes.data, length, peaks, fmt, args, form="")
+
+
+def _hit_batch(fam, algos, ptrs, lengths, peaks_per_pair, fmt, args):
+    """[h][j][i] = the records of hit i of peaks_per_pair[h][j] (resident haystack h against needle j): the pair's hits
+    stand in slot h * nn + j of a table of `cap` rows a slot, its records in the same rows of `out`."""
+    nn, k = len(algos), len(ptrs)
+    pairs = [peaks_per_pair[h][j] for h in range(k) for j in range(nn)]
+    cap = max([1] + [len(hits) for hits in pairs])
+    handles = (C.c_void_p * max(1, nn))(*[a._h for a in algos])
+    arr_p = (C.c_void_p * max(1, k))(*ptrs)
+    arr_l = (C.c_size_t * max(1, k))(*lengths)
+    buf = (AmPeak * max(1, cap * k * nn))()
+    counts = (C.c_size_t * max(1, k * nn))(*[len(hits) for hits in pairs])
+    for q, hits in enumerate(pairs):
+        for i, p in enumerate(hits):
+            buf[q * cap + i] = _am_peak(p)
+    out, m = _hit_call(fam, "_batch_device", (handles, nn, arr_p, arr_l, k, int(fmt), buf, cap, counts), cap * k * nn, args)
+    return [[[fam.unpack(out, (h * nn + j) * cap + i, m) for i in range(counts[h * nn + j])] for j in range(nn)]
+            for h in range(k)]
 
 
 # ---------------------------------------------------------------------------
@@ -1030,13 +1077,7 @@ class HipConvolve:
     def match_best(self, haystack, k: int, min_distance: int = 0, min_prominence: float = 0.0, scale=Scale.LIB):
         """am_match_best: the k best peaks of the haystack's Valid scores (one array, no chunks), by descending height.
         haystack: an f32 array, or an i16 (frames, 2) array of interleaved stereo."""
-        a = np.asarray(haystack)
-        if a.dtype == np.int16:
-            a = np.ascontiguousarray(a)
-            fmt, length = Fmt.S16_STEREO, a.size // 2
-        else:
-            a = np.ascontiguousarray(a, dtype=np.float32)
-            fmt, length = Fmt.F32_MONO, a.size
+        a, fmt, length = _samples(haystack)
         bp = best_params(k, min_distance, min_prominence, scale)
         buf = (AmPeak * max(1, int(k)))()
         n = C.c_size_t(0)
@@ -1065,120 +1106,51 @@ class HipConvolve:
     def hit_scores(self, haystack, peaks):
         """am_hit_scores: score `peaks` (Peak / AmPeak) of a host haystack -- an f32 array, or an i16 (frames, 2) array
         of interleaved stereo.  Only the hits' spans are copied to the device."""
-        a = np.asarray(haystack)
-        if a.dtype == np.int16:
-            a = np.ascontiguousarray(a)
-            fmt, length = Fmt.S16_STEREO, a.size // 2
-        else:
-            a = np.ascontiguousarray(a, dtype=np.float32)
-            fmt, length = Fmt.F32_MONO, a.size
-        k = len(peaks)
-        out = (AmHitScore * max(1, k))()
-        _check(lib().am_hit_scores(self._h, a.ctypes.data, length, int(fmt), _peak_array(peaks), k, out))
-        return _hit_scores(out, range(k))
+        return _hit_host(_SCORES, self, haystack, peaks, ())
 
     def hit_scores_device(self, ptr: int, length: int, peaks, fmt: int = Fmt.F32_MONO):
         """am_hit_scores_device: score `peaks` of a haystack resident on this needle's device."""
-        k = len(peaks)
-        out = (AmHitScore * max(1, k))()
-        _check(lib().am_hit_scores_device(self._h, ptr, length, int(fmt), _peak_array(peaks), k, out))
-        return _hit_scores(out, range(k))
+        return _hit_device(_SCORES, self, ptr, length, peaks, fmt, ())
 
     # -- per-segment hit scoring --
     def hit_segments(self, haystack, peaks, segments: int, radius: int = 4):
         """am_hit_segments: for each of `peaks` of a host haystack (as in hit_scores) the list of its `segments`
         HitSegment records, lags -radius .. radius examined."""
-        a = np.asarray(haystack)
-        if a.dtype == np.int16:
-            a = np.ascontiguousarray(a)
-            fmt, length = Fmt.S16_STEREO, a.size // 2
-        else:
-            a = np.ascontiguousarray(a, dtype=np.float32)
-            fmt, length = Fmt.F32_MONO, a.size
-        k, m = len(peaks), int(segments)
-        out = (HitSegment * max(1, k * max(m, 0)))()
-        sp = AmSegmentParams(m, int(radius))
-        _check(lib().am_hit_segments(self._h, a.ctypes.data, length, int(fmt), _peak_array(peaks), k, C.byref(sp), out))
-        return [_hit_segments(out, i * m, m) for i in range(k)]
+        return _hit_host(_SEGMENTS, self, haystack, peaks, (segments, radius))
 
     def hit_segments_device(self, ptr: int, length: int, peaks, segments: int, radius: int = 4, fmt: int = Fmt.F32_MONO):
         """am_hit_segments_device: the same for a haystack resident on this needle's device."""
-        k, m = len(peaks), int(segments)
-        out = (HitSegment * max(1, k * max(m, 0)))()
-        sp = AmSegmentParams(m, int(radius))
-        _check(lib().am_hit_segments_device(self._h, ptr, length, int(fmt), _peak_array(peaks), k, C.byref(sp), out))
-        return [_hit_segments(out, i * m, m) for i in range(k)]
+        return _hit_device(_SEGMENTS, self, ptr, length, peaks, fmt, (segments, radius))
 
     # -- per-hit drift scoring --
     def hit_warp(self, haystack, peaks, wp: AmWarpParams):
         """am_hit_warp: for each of `peaks` of a host haystack (as in hit_scores) its HitWarp record over the grid `wp`
         (warp_params)."""
-        a = np.asarray(haystack)
-        if a.dtype == np.int16:
-            a = np.ascontiguousarray(a)
-            fmt, length = Fmt.S16_STEREO, a.size // 2
-        else:
-            a = np.ascontiguousarray(a, dtype=np.float32)
-            fmt, length = Fmt.F32_MONO, a.size
-        k = len(peaks)
-        out = (HitWarp * max(1, k))()
-        _check(lib().am_hit_warp(self._h, a.ctypes.data, length, int(fmt), _peak_array(peaks), k, C.byref(wp), out))
-        return _hit_warps(out, range(k))
+        return _hit_host(_WARP, self, haystack, peaks, (wp,))
 
     def hit_warp_device(self, ptr: int, length: int, peaks, wp: AmWarpParams, fmt: int = Fmt.F32_MONO):
         """am_hit_warp_device: the same for a haystack resident on this needle's device."""
-        k = len(peaks)
-        out = (HitWarp * max(1, k))()
-        _check(lib().am_hit_warp_device(self._h, ptr, length, int(fmt), _peak_array(peaks), k, C.byref(wp), out))
-        return _hit_warps(out, range(k))
+        return _hit_device(_WARP, self, ptr, length, peaks, fmt, (wp,))
 
     # -- per-band hit scoring --
     def hit_bands(self, haystack, peaks, bp: AmBandParams):
         """am_hit_bands: for each of `peaks` of a host haystack (as in hit_scores) the list of its bp.n_bands HitBand
         records (bp: band_params or band_edges_log)."""
-        a = np.asarray(haystack)
-        if a.dtype == np.int16:
-            a = np.ascontiguousarray(a)
-            fmt, length = Fmt.S16_STEREO, a.size // 2
-        else:
-            a = np.ascontiguousarray(a, dtype=np.float32)
-            fmt, length = Fmt.F32_MONO, a.size
-        k, nb = len(peaks), int(bp.n_bands)
-        out = (HitBand * max(1, k * nb))()
-        _check(lib().am_hit_bands(self._h, a.ctypes.data, length, int(fmt), _peak_array(peaks), k, C.byref(bp), out))
-        return [_hit_bands(out, i * nb, nb) for i in range(k)]
+        return _hit_host(_BANDS, self, haystack, peaks, (bp,))
 
     def hit_bands_device(self, ptr: int, length: int, peaks, bp: AmBandParams, fmt: int = Fmt.F32_MONO):
         """am_hit_bands_device: the same for a haystack resident on this needle's device."""
-        k, nb = len(peaks), int(bp.n_bands)
-        out = (HitBand * max(1, k * nb))()
-        _check(lib().am_hit_bands_device(self._h, ptr, length, int(fmt), _peak_array(peaks), k, C.byref(bp), out))
-        return [_hit_bands(out, i * nb, nb) for i in range(k)]
+        return _hit_device(_BANDS, self, ptr, length, peaks, fmt, (bp,))
 
     # -- per-hit significance --
     def hit_significance(self, haystack, peaks, guard: int, radius: int):
         """am_hit_significance: for each of `peaks` of a host haystack (as in hit_scores) its HitSignificance -- the
         hit's score against the scores at lags guard < |lag| <= radius around it."""
-        a = np.asarray(haystack)
-        if a.dtype == np.int16:
-            a = np.ascontiguousarray(a)
-            fmt, length = Fmt.S16_STEREO, a.size // 2
-        else:
-            a = np.ascontiguousarray(a, dtype=np.float32)
-            fmt, length = Fmt.F32_MONO, a.size
-        k = len(peaks)
-        out = (HitSignificance * max(1, k))()
-        sp = AmSignificanceParams(int(guard), int(radius))
-        _check(lib().am_hit_significance(self._h, a.ctypes.data, length, int(fmt), _peak_array(peaks), k, C.byref(sp), out))
-        return _hit_significance(out, range(k))
+        return _hit_host(_SIGNIFICANCE, self, haystack, peaks, (guard, radius))
 
     def hit_significance_device(self, ptr: int, length: int, peaks, guard: int, radius: int, fmt: int = Fmt.F32_MONO):
         """am_hit_significance_device: the same for a haystack resident on this needle's device."""
-        k = len(peaks)
-        out = (HitSignificance * max(1, k))()
-        sp = AmSignificanceParams(int(guard), int(radius))
-        _check(lib().am_hit_significance_device(self._h, ptr, length, int(fmt), _peak_array(peaks), k, C.byref(sp), out))
-        return _hit_significance(out, range(k))
+        return _hit_device(_SIGNIFICANCE, self, ptr, length, peaks, fmt, (guard, radius))
 
 
 class MatchStream:
@@ -1481,13 +1453,7 @@ def match_multi_varlen_batch_device(algos, ptrs, lengths, params: AmMatchParams,
 def match_multi_varlen(algos, haystack, params: AmMatchParams, overlaps=None, cap_per_needle: int = 256):
     """Several needles of any lengths against ONE haystack in host memory (am_match_multi_varlen): a numpy f32 mono
     array, or an interleaved i16 stereo array (int16 dtype, frames x 2 or flat).  Result [j] = the hits of needle j."""
-    h = np.asarray(haystack)
-    if h.dtype == np.int16:
-        h = np.ascontiguousarray(h, dtype=np.int16).reshape(-1)
-        fmt, length = Fmt.S16_STEREO, h.size // 2
-    else:
-        h = np.ascontiguousarray(h, dtype=np.float32)
-        fmt, length = Fmt.F32_MONO, h.size
+    h, fmt, length = _samples(haystack)
     nn = len(algos)
     handles = (C.c_void_p * max(1, nn))(*[a._h for a in algos])
     buf = (AmPeak * max(1, cap_per_needle * nn))()
@@ -1500,113 +1466,31 @@ def match_multi_varlen(algos, haystack, params: AmMatchParams, overlaps=None, ca
 def hit_scores_batch_device(algos, ptrs, lengths, peaks_per_pair, fmt: int = Fmt.F32_MONO):
     """am_hit_scores_batch_device: peaks_per_pair[k][j] = the hits of haystack k against needle j (the shape
     match_multi_batch_device returns; needles may differ in length); result [k][j] = their HitScores."""
-    nn, k = len(algos), len(ptrs)
-    cap = max([1] + [len(peaks_per_pair[h][j]) for h in range(k) for j in range(nn)])
-    handles = (C.c_void_p * max(1, nn))(*[a._h for a in algos])
-    arr_p = (C.c_void_p * max(1, k))(*ptrs)
-    arr_l = (C.c_size_t * max(1, k))(*lengths)
-    buf = (AmPeak * max(1, cap * k * nn))()
-    counts = (C.c_size_t * max(1, k * nn))()
-    for h in range(k):
-        for j in range(nn):
-            q = h * nn + j
-            counts[q] = len(peaks_per_pair[h][j])
-            for i, p in enumerate(peaks_per_pair[h][j]):
-                buf[q * cap + i] = AmPeak(int(p.start), int(p.end), float(p.height), float(p.prominence))
-    out = (AmHitScore * max(1, cap * k * nn))()
-    _check(lib().am_hit_scores_batch_device(handles, nn, arr_p, arr_l, k, int(fmt), buf, cap, counts, out))
-    return [[_hit_scores(out, range((h * nn + j) * cap, (h * nn + j) * cap + counts[h * nn + j])) for j in range(nn)]
-            for h in range(k)]
+    return _hit_batch(_SCORES, algos, ptrs, lengths, peaks_per_pair, fmt, ())
 
 
 def hit_segments_batch_device(algos, ptrs, lengths, peaks_per_pair, segments: int, radius: int = 4, fmt: int = Fmt.F32_MONO):
     """am_hit_segments_batch_device: peaks_per_pair[k][j] as in hit_scores_batch_device; result [k][j][i] = the
     `segments` HitSegment records of hit i of haystack k against needle j."""
-    nn, k, m = len(algos), len(ptrs), int(segments)
-    cap = max([1] + [len(peaks_per_pair[h][j]) for h in range(k) for j in range(nn)])
-    handles = (C.c_void_p * max(1, nn))(*[a._h for a in algos])
-    arr_p = (C.c_void_p * max(1, k))(*ptrs)
-    arr_l = (C.c_size_t * max(1, k))(*lengths)
-    buf = (AmPeak * max(1, cap * k * nn))()
-    counts = (C.c_size_t * max(1, k * nn))()
-    for h in range(k):
-        for j in range(nn):
-            q = h * nn + j
-            counts[q] = len(peaks_per_pair[h][j])
-            for i, p in enumerate(peaks_per_pair[h][j]):
-                buf[q * cap + i] = AmPeak(int(p.start), int(p.end), float(p.height), float(p.prominence))
-    out = (HitSegment * max(1, cap * k * nn * max(m, 0)))()
-    sp = AmSegmentParams(m, int(radius))
-    _check(lib().am_hit_segments_batch_device(handles, nn, arr_p, arr_l, k, int(fmt), buf, cap, counts, C.byref(sp), out))
-    return [[[_hit_segments(out, ((h * nn + j) * cap + i) * m, m) for i in range(counts[h * nn + j])] for j in range(nn)]
-            for h in range(k)]
+    return _hit_batch(_SEGMENTS, algos, ptrs, lengths, peaks_per_pair, fmt, (segments, radius))
 
 
 def hit_warp_batch_device(algos, ptrs, lengths, peaks_per_pair, wp: AmWarpParams, fmt: int = Fmt.F32_MONO):
     """am_hit_warp_batch_device: peaks_per_pair[k][j] as in hit_scores_batch_device; result [k][j] = the HitWarp records
     of haystack k against needle j."""
-    nn, k = len(algos), len(ptrs)
-    cap = max([1] + [len(peaks_per_pair[h][j]) for h in range(k) for j in range(nn)])
-    handles = (C.c_void_p * max(1, nn))(*[a._h for a in algos])
-    arr_p = (C.c_void_p * max(1, k))(*ptrs)
-    arr_l = (C.c_size_t * max(1, k))(*lengths)
-    buf = (AmPeak * max(1, cap * k * nn))()
-    counts = (C.c_size_t * max(1, k * nn))()
-    for h in range(k):
-        for j in range(nn):
-            q = h * nn + j
-            counts[q] = len(peaks_per_pair[h][j])
-            for i, p in enumerate(peaks_per_pair[h][j]):
-                buf[q * cap + i] = AmPeak(int(p.start), int(p.end), float(p.height), float(p.prominence))
-    out = (HitWarp * max(1, cap * k * nn))()
-    _check(lib().am_hit_warp_batch_device(handles, nn, arr_p, arr_l, k, int(fmt), buf, cap, counts, C.byref(wp), out))
-    return [[_hit_warps(out, range((h * nn + j) * cap, (h * nn + j) * cap + counts[h * nn + j])) for j in range(nn)]
-            for h in range(k)]
+    return _hit_batch(_WARP, algos, ptrs, lengths, peaks_per_pair, fmt, (wp,))
 
 
 def hit_bands_batch_device(algos, ptrs, lengths, peaks_per_pair, bp: AmBandParams, fmt: int = Fmt.F32_MONO):
     """am_hit_bands_batch_device: peaks_per_pair[k][j] as in hit_scores_batch_device; result [k][j][i] = the bp.n_bands
     HitBand records of hit i of haystack k against needle j."""
-    nn, k, nb = len(algos), len(ptrs), int(bp.n_bands)
-    cap = max([1] + [len(peaks_per_pair[h][j]) for h in range(k) for j in range(nn)])
-    handles = (C.c_void_p * max(1, nn))(*[a._h for a in algos])
-    arr_p = (C.c_void_p * max(1, k))(*ptrs)
-    arr_l = (C.c_size_t * max(1, k))(*lengths)
-    buf = (AmPeak * max(1, cap * k * nn))()
-    counts = (C.c_size_t * max(1, k * nn))()
-    for h in range(k):
-        for j in range(nn):
-            q = h * nn + j
-            counts[q] = len(peaks_per_pair[h][j])
-            for i, p in enumerate(peaks_per_pair[h][j]):
-                buf[q * cap + i] = AmPeak(int(p.start), int(p.end), float(p.height), float(p.prominence))
-    out = (HitBand * max(1, cap * k * nn * nb))()
-    _check(lib().am_hit_bands_batch_device(handles, nn, arr_p, arr_l, k, int(fmt), buf, cap, counts, C.byref(bp), out))
-    return [[[_hit_bands(out, ((h * nn + j) * cap + i) * nb, nb) for i in range(counts[h * nn + j])] for j in range(nn)]
-            for h in range(k)]
+    return _hit_batch(_BANDS, algos, ptrs, lengths, peaks_per_pair, fmt, (bp,))
 
 
 def hit_significance_batch_device(algos, ptrs, lengths, peaks_per_pair, guard: int, radius: int, fmt: int = Fmt.F32_MONO):
     """am_hit_significance_batch_device: peaks_per_pair[k][j] as in hit_scores_batch_device; result [k][j][i] = the
     HitSignificance of hit i of haystack k against needle j."""
-    nn, k = len(algos), len(ptrs)
-    cap = max([1] + [len(peaks_per_pair[h][j]) for h in range(k) for j in range(nn)])
-    handles = (C.c_void_p * max(1, nn))(*[a._h for a in algos])
-    arr_p = (C.c_void_p * max(1, k))(*ptrs)
-    arr_l = (C.c_size_t * max(1, k))(*lengths)
-    buf = (AmPeak * max(1, cap * k * nn))()
-    counts = (C.c_size_t * max(1, k * nn))()
-    for h in range(k):
-        for j in range(nn):
-            q = h * nn + j
-            counts[q] = len(peaks_per_pair[h][j])
-            for i, p in enumerate(peaks_per_pair[h][j]):
-                buf[q * cap + i] = AmPeak(int(p.start), int(p.end), float(p.height), float(p.prominence))
-    out = (HitSignificance * max(1, cap * k * nn))()
-    sp = AmSignificanceParams(int(guard), int(radius))
-    _check(lib().am_hit_significance_batch_device(handles, nn, arr_p, arr_l, k, int(fmt), buf, cap, counts, C.byref(sp), out))
-    return [[_hit_significance(out, range((h * nn + j) * cap, (h * nn + j) * cap + counts[h * nn + j])) for j in range(nn)]
-            for h in range(k)]
+    return _hit_batch(_SIGNIFICANCE, algos, ptrs, lengths, peaks_per_pair, fmt, (guard, radius))
 
 
 class MultiPool:
