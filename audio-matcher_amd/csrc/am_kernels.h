@@ -374,6 +374,31 @@ hipError_t launch_warp_needles(hipStream_t st, const WarpJob* d_jobs, int n_jobs
 hipError_t launch_warp_combine(hipStream_t st, const SegDesc* tab, long long n, const WarpGrid& grid, const double* parts,
                                const unsigned* pflags, am_warp_hit* d_out);
 
+// ---- am_channel.hip: per-hit channel estimation (am_hit_channel*) ----
+constexpr int kLagTile = 32;                           // lags per workgroup of the slice kernel
+constexpr size_t kChanRoundBytes = (size_t)64 << 20;   // a round of items: its partial records at most this much (one item at the least)
+constexpr int lag_tiles(int nlag) { return (nlag + kLagTile - 1) / kLagTile; }
+constexpr int lag_record_len(int nt) { return nt * kLagTile + 2; }   // doubles per partial record: the tiles' sums, E_w, E_x
+constexpr int lag_sums_len(int nlag) { return nlag + 3; }            // doubles per item's sums record: the lags' sums, E_w, E_x, the flag (0 or 1)
+// One item of a call, as the kernels read it: a signal x around t against a needle, the lags lag0 .. lag0 + nlag - 1
+struct LagDesc {
+    const void* win;      // device: sample t of x (f32 mono, or an i16 stereo frame for kind 1)
+    const float* needle;  // device: the whole needle
+    long long s;          // needle length
+    long long ulo, uhi;   // x[t + u] exists (and is read) for ulo <= u < uhi only
+    long long part0;      // first partial record of the item: slice k at part0 + k
+    int lag0, nlag;       // lag0 <= 0
+    int head;             // P: E_x adds x[t - P, t) and x[t + S, t + S + P) to E_w
+    int pad;
+};
+// items [first, first + n) of the table, all of one kind and with nt = lag_tiles(nlag) tiles; parts: lag_record_len(nt)
+// doubles per slice, pflags: nt words per slice
+hipError_t launch_lag_slices(hipStream_t st, const LagDesc* tab, long long first, long long n, int nt, int max_nsl, int kind, double* parts,
+                             unsigned* pflags);
+// one wave per item of [0, n): sums: lag_sums_len(nlag_max) doubles per item
+hipError_t launch_lag_combine(hipStream_t st, const LagDesc* tab, long long n, int nt, int nlag_max, const double* parts,
+                              const unsigned* pflags, double* sums);
+
 // ---- am_bands.hip: per-band hit scoring (am_hit_bands*) ----
 constexpr int kBandGroup = 8;   // consecutive frames per workgroup of the frame kernel, counted from the hit's first frame
 inline int band_record_len(int n_bands) { return 4 * n_bands + 1; }   // doubles per partial record: (Re C, Im C, E_x, E_n) per band, E_n over every bin

@@ -80,6 +80,9 @@ struct Arguments {
     std::optional<double> warp_ppm;           // extension: --warp PPM[:STEPS[:RADIUS]], drift and corrected NCC of every hit (am_hit_warp)
     std::uint32_t warp_steps = 8;             // ... drifts -PPM .. PPM in 2 STEPS + 1 steps
     std::uint32_t warp_radius = 4;            // ... the lags -RADIUS .. RADIUS
+    std::optional<std::uint32_t> channel_radius;   // extension: --channel P[:NOISE_DB], the filter every printed hit went through (am_hit_channel): taps -P .. P
+    double channel_noise_db = 60.0;           // ... the white-noise correction of the solve
+    std::string residual_prefix;              // extension: --residual PREFIX, what is left of each printed hit's span (am_hit_residual) as PREFIX<file index>_<start>.wav; empty = off
     std::uint32_t bands = 0;                  // extension: --bands B[:LOG2F], per-band scoring of every printed hit (am_hit_bands), 0 = off
     std::uint32_t band_frame_log2 = 11;       // ... in frames of 2^LOG2F samples
     std::optional<float> min_significance;    // extension: --min-significance Z, drop hits whose z against the local background is below Z (am_hit_significance)
@@ -141,6 +144,15 @@ inline const char* usage_text() {
            "                         PPM in 2 STEPS + 1 steps (STEPS in 1..32, default 8), lags -RADIUS .. RADIUS (0..16,\n"
            "                         default 4); PPM up to 50000.  --min-confidence then applies to the corrected NCC and\n"
            "                         --learn-needle cuts its rows on the snippet's clock.  Does not apply with --live\n"
+           "  --channel P[:NOISE_DB] for hits that went through another chain (an EQ, a codec, an echo): after each hit's\n"
+           "                         offset line, print the plain NCC, the NCC against the snippet filtered by the hit's own\n"
+           "                         least-squares taps -P .. P (P in 0..128), the filter's gain and the unexplained share of\n"
+           "                         the span in dB, the lag of the largest tap and its share of the taps' energy; NOISE_DB\n"
+           "                         (0..200, default 60) steadies the solve.  Does not apply with --live\n"
+           "  --residual PREFIX      with --channel: for each printed hit write PREFIX<file index>_<start>.wav, the hit's\n"
+           "                         span (P samples each side) minus the filtered snippet: what lies over or under the\n"
+           "                         jingle; mono 32-bit float, samples outside the file as 0.  Not with --whiten or\n"
+           "                         --preemphasis, nor for a file whose rate differs from the snippet's\n"
            "  --bands B[:LOG2F]      after each hit's offset line, print which of B log-spaced frequency bands of the\n"
            "                         snippet (50 Hz up to 16 kHz or half the sample rate) the hit holds ('#' present,\n"
            "                         '.' absent: the band's coherence against --min-confidence if given, else 0.5),\n"
@@ -286,6 +298,23 @@ inline Arguments parse_arguments(int argc, const char* const* argv) {
             a.warp_steps = (std::uint32_t)k;
             a.warp_radius = (std::uint32_t)r;
         }
+        else if (s == "--channel") {
+            const std::string v = need(i);
+            const std::size_t colon = v.find(':');
+            const std::string vp = v.substr(0, colon), vn = colon == std::string::npos ? "60" : v.substr(colon + 1);
+            char* end = nullptr;
+            const unsigned long p = std::strtoul(vp.c_str(), &end, 10);
+            const bool p_ok = !vp.empty() && vp[0] >= '0' && vp[0] <= '9' && *end == '\0' && p <= AM_CHAN_MAX_RADIUS;
+            const double db = std::strtod(vn.c_str(), &end);
+            if (!p_ok || vn.empty() || *end != '\0' || !(db >= 0.0 && db <= 200.0))
+                throw ArgError("invalid value '" + v + "' for --channel (P[:NOISE_DB], P in 0..128 taps each side, NOISE_DB in 0..200)");
+            a.channel_radius = (std::uint32_t)p;
+            a.channel_noise_db = db;
+        }
+        else if (s == "--residual") {
+            a.residual_prefix = need(i);
+            if (a.residual_prefix.empty()) throw ArgError("invalid value '' for --residual (a file name prefix)");
+        }
         else if (s == "--bands") {
             const std::string v = need(i);
             const std::size_t colon = v.find(':');
@@ -371,6 +400,9 @@ inline Arguments parse_arguments(int argc, const char* const* argv) {
     if (a.snippet.empty()) throw ArgError("--snippet <FILE> is required");
     if (a.whiten && a.preemphasis) throw ArgError("--whiten and --preemphasis are mutually exclusive");
     if (a.learn_margin_ms && a.learn_needle.empty()) throw ArgError("--learn-margin needs --learn-needle");
+    if (!a.residual_prefix.empty() && !a.channel_radius) throw ArgError("--residual needs --channel");
+    if (!a.residual_prefix.empty() && (a.whiten || a.preemphasis))
+        throw ArgError("--residual does not apply with --whiten or --preemphasis (the span would be that of the filtered signal)");
     if (!a.learn_needle.empty()) {
         if (a.live) throw ArgError("--live: --learn-needle does not apply");
         if (a.best) throw ArgError("--learn-needle and --best are mutually exclusive");
@@ -385,6 +417,7 @@ inline Arguments parse_arguments(int argc, const char* const* argv) {
         if (a.segments) throw ArgError("--live: --segments does not apply");
         if (a.bands) throw ArgError("--live: --bands does not apply");
         if (a.warp_ppm) throw ArgError("--live: --warp does not apply");
+        if (a.channel_radius) throw ArgError("--live: --channel does not apply");
         if (a.whiten || a.preemphasis) throw ArgError("--live: --whiten and --preemphasis do not apply (not supported on a live feed yet)");
         if (a.min_significance || a.significance_zone_ms) throw ArgError("--live: --min-significance and --significance-zone do not apply");
         return a;

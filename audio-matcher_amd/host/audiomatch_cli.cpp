@@ -151,6 +151,57 @@ static std::vector<std::string> warp_lines(const std::vector<am_warp_hit>& recs)
     return out;
 }
 
+// extension: --channel P[:NOISE_DB].  The records and the taps of the printed hits (am_hit_channel): what each hit went
+// through on its way into the recording.
+struct ChannelSet {
+    std::uint32_t radius = 0;
+    std::vector<am_channel_hit> recs;
+    std::vector<float> taps;   // hit i at i * (2 radius + 1)
+};
+
+static ChannelSet channel_of(const Arguments& args, const am_needle* algo, const std::vector<float>& samples, const am_peak* peaks, size_t n) {
+    ChannelSet cs;
+    cs.radius = *args.channel_radius;
+    cs.recs.resize(n);
+    cs.taps.resize(n * (2 * (size_t)cs.radius + 1));
+    const am_channel_params cp{cs.radius, 0, args.channel_noise_db};
+    if (n > 0 && am_hit_channel(algo, samples.data(), samples.size(), AM_FMT_F32_MONO, peaks, n, &cp, cs.recs.data(), cs.taps.data()) != AM_OK)
+        throw std::runtime_error(std::string("am_hit_channel: ") + am_last_error_string());
+    return cs;
+}
+
+// ... one line per hit, to follow the hit's offset line
+static std::vector<std::string> channel_lines(const ChannelSet& cs) {
+    std::vector<std::string> out;
+    for (const am_channel_hit& q : cs.recs) {
+        char line[256];
+        std::snprintf(line, sizeof line, "  channel ncc %.6f ncc_eq %.6f gain_db %.2f residual_db %.2f main_tap %d main_share %.4f%s%s%s%s", (double)q.ncc,
+                      (double)q.ncc_eq, (double)q.gain_db, (double)q.residual_db, (int)q.main_tap, (double)q.main_share,
+                      (q.flags & AM_HIT_BELOW_FLOOR) ? " (below the floor)" : "", (q.flags & AM_HIT_NONFINITE) ? " (non-finite samples)" : "",
+                      (q.flags & AM_HIT_EMPTY_SEGMENT) ? " (silent snippet)" : "", (q.flags & AM_HIT_ILL_CONDITIONED) ? " (ill-conditioned: plain gain)" : "");
+        out.push_back(line);
+    }
+    return out;
+}
+
+// extension: --residual PREFIX.  Per printed hit PREFIX<file index>_<start>.wav: the hit's span minus the snippet filtered
+// by the hit's taps (am_hit_residual), samples the file does not hold (or that are not finite) as 0.  `needle`: the
+// snippet's samples as the handle holds them.
+static void write_residuals(const Arguments& args, const std::vector<float>& samples, std::uint32_t m_sr, const std::vector<float>& needle,
+                            size_t file_index, const am_peak* peaks, size_t n, const ChannelSet& cs) {
+    const size_t nt = 2 * (size_t)cs.radius + 1;
+    std::vector<float> resid(needle.size() + nt - 1);
+    for (size_t i = 0; i < n; ++i) {
+        if (cs.recs[i].flags & AM_HIT_NONFINITE) continue;   // (no taps)
+        if (am_hit_residual(samples.data(), samples.size(), AM_FMT_F32_MONO, peaks[i].start, needle.data(), needle.size(), cs.taps.data() + i * nt,
+                            cs.radius, nullptr, resid.data()) != AM_OK)
+            throw std::runtime_error(std::string("am_hit_residual: ") + am_last_error_string());
+        for (float& v : resid)
+            if (!std::isfinite(v)) v = 0.0f;
+        write_wav_f32(args.residual_prefix + std::to_string(file_index) + "_" + std::to_string(peaks[i].start) + ".wav", resid, m_sr);
+    }
+}
+
 // ... with --min-confidence: keeps the hits whose corrected NCC is at least X, in place (ws holds the records of exactly
 // these n hits); returns how many are left.  With --debug one line per hit (`prefix` in front).
 static size_t warp_confidence_filter(const Arguments& args, const WarpSet& ws, am_peak* peaks, size_t n, const std::string& prefix) {
@@ -456,9 +507,10 @@ static std::vector<std::vector<am_peak>> match_hits_multi(const std::vector<cons
 // One snippet's hits in one main file, from the match to the report: the filters (--min-confidence, on the corrected NCC
 // with --warp; --min-significance) drop hits from `hits`, the learner takes its rows of those that are left, and they
 // are printed, every line with `prefix` in front: the offset line (mod.rs:89) and under it the hit's --warp, --segments
-// and --bands lines.
+// and --bands lines; with --channel the hit's channel line, and with --residual its residual file (`snip`: the snippet as
+// read, `file_index`: the main file's place among the FILE arguments).
 static void report_hits(const Arguments& args, const am_needle* algo, const std::vector<float>& m_samples, std::uint32_t m_sr,
-                        std::vector<am_peak>& hits, const std::string& prefix, Learner& learner) {
+                        std::vector<am_peak>& hits, const std::string& prefix, Learner& learner, const Snippet& snip, size_t file_index) {
     am_peak* pk = hits.data();
     size_t n = hits.size();
     const WarpSet warp = WarpSet::compute(args, algo, m_samples, pk, n);
@@ -473,8 +525,18 @@ static void report_hits(const Arguments& args, const am_needle* algo, const std:
     const std::vector<std::string> segs = args.segments ? segment_lines(args, algo, m_samples, pk, n) : none;
     const std::vector<std::string> bands = args.bands ? band_lines(args, algo, m_samples, m_sr, pk, n) : none;
     const std::vector<std::string> warps = args.warp_ppm ? warp_lines(warp.of(pk, n)) : none;
+    std::vector<std::string> chan_lines;
+    const std::vector<std::string>& chans = chan_lines;
+    if (args.channel_radius) {
+        const ChannelSet cs = channel_of(args, algo, m_samples, pk, n);
+        chan_lines = channel_lines(cs);
+        if (!args.residual_prefix.empty()) {
+            if (m_sr != snip.sr) throw std::runtime_error("--residual: the snippet was resampled for this file; its samples at the file's rate are not kept");
+            write_residuals(args, m_samples, m_sr, snip.data, file_index, pk, n, cs);
+        }
+    }
     for (size_t i = 0; i < lines.size(); ++i)
-        for (const std::vector<std::string>* l : {&lines, &warps, &segs, &bands})
+        for (const std::vector<std::string>* l : {&lines, &warps, &chans, &segs, &bands})
             if (i < l->size()) std::printf("%s%s\n", prefix.c_str(), (*l)[i].c_str());
 }
 
@@ -498,7 +560,9 @@ static int run_files(const Arguments& args) {
     if (args.verbosity >= 2) am_set_progress_callback(progress, nullptr);
     int rc_all = 0;
     Learner learner;                                                      // extension: --learn-needle (one snippet only)
+    size_t file_index = (size_t)-1;                                       // (of --residual's file names: the main file's place among the FILE arguments)
     for (const std::string& main_file : args.within) {                    // mod.rs:42
+        ++file_index;
         std::optional<std::string> out_path;
         if (!output_path(args, main_file, out_path)) continue;
         if (args.verbosity >= (args.within.size() == 1 ? 3 : 1))
@@ -526,7 +590,7 @@ static int run_files(const Arguments& args) {
             }
         }
         for (size_t j = 0; j < k; ++j)
-            report_hits(args, handles[j], m_samples, m_sr, hits[j], k > 1 ? snips[j].name + ": " : std::string(), learner);
+            report_hits(args, handles[j], m_samples, m_sr, hits[j], k > 1 ? snips[j].name + ": " : std::string(), learner, snips[j], file_index);
         if (out_path) {                                                   // mod.rs:92-99
             std::vector<am_peak> all;
             for (const std::vector<am_peak>& h : hits) all.insert(all.end(), h.begin(), h.end());

@@ -104,6 +104,27 @@ AM_HIT_DRIFT_UNREFINED = 256
 AM_WARP_PHASES, AM_WARP_TAPS, AM_WARP_MAX_STEPS, AM_WARP_MAX_PPM = 4096, 32, 32, 50000
 
 
+class AmChannelParams(C.Structure):   # am_channel_params (include/audiomatch.h, per-hit channel estimation)
+    _fields_ = [("radius", C.c_uint32), ("reserved", C.c_uint32), ("noise_db", C.c_double)]
+
+
+class HitChannel(C.Structure):        # am_channel_hit: how well the needle, filtered by the hit's own taps, explains the span
+    _fields_ = [("ncc", C.c_float), ("ncc_eq", C.c_float), ("gain_db", C.c_float), ("residual_db", C.c_float),
+                ("main_tap", C.c_int32), ("main_share", C.c_float), ("flags", C.c_uint32), ("reserved", C.c_uint32)]
+
+    def __repr__(self):
+        return (f"HitChannel(ncc={self.ncc!r}, ncc_eq={self.ncc_eq!r}, gain_db={self.gain_db!r}, residual_db={self.residual_db!r}, "
+                f"main_tap={self.main_tap}, main_share={self.main_share!r}, flags={self.flags})")
+
+    def pack(self) -> bytes:
+        """The record's 32 bytes (for bit-for-bit comparisons)."""
+        return bytes(self)
+
+
+AM_HIT_ILL_CONDITIONED = 512
+AM_CHAN_MAX_RADIUS = 128
+
+
 class AmBandParams(C.Structure):      # am_band_params (include/audiomatch.h, per-band hit scoring)
     _fields_ = [("frame_log2", C.c_uint32), ("n_bands", C.c_uint32), ("edges", C.c_uint32 * 33)]
 
@@ -369,6 +390,16 @@ _SIGNATURES = {
                                            C.POINTER(AmWarpParams), C.POINTER(HitWarp)]),
     "am_hit_window_warped": (C.c_int, [C.c_void_p, C.c_size_t, C.c_int, C.c_uint64, C.c_float, C.c_double, C.c_double,
                                        C.c_uint64, C.c_uint64, C.c_void_p]),
+    "am_hit_channel_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.POINTER(AmPeak), C.c_size_t,
+                                        C.POINTER(AmChannelParams), C.POINTER(HitChannel), C.c_void_p]),
+    "am_hit_channel": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.POINTER(AmPeak), C.c_size_t,
+                                 C.POINTER(AmChannelParams), C.POINTER(HitChannel), C.c_void_p]),
+    "am_hit_channel_batch_device": (C.c_int, [C.POINTER(C.c_void_p), C.c_size_t, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t),
+                                              C.c_size_t, C.c_int, C.POINTER(AmPeak), C.c_size_t, C.POINTER(C.c_size_t),
+                                              C.POINTER(AmChannelParams), C.POINTER(HitChannel), C.c_void_p]),
+    "am_channel_solve": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_double, C.c_void_p, C.POINTER(C.c_int)]),
+    "am_hit_residual": (C.c_int, [C.c_void_p, C.c_size_t, C.c_int, C.c_uint64, C.c_void_p, C.c_size_t, C.c_void_p, C.c_uint32,
+                                  C.c_void_p, C.c_void_p]),
     "am_needle_estimate_rows": (C.c_int, [C.c_int, C.c_void_p, C.c_size_t, C.POINTER(AmEstimateParams), C.c_void_p, C.c_void_p,
                                           C.c_void_p]),
     "am_needle_estimate_device": (C.c_int, [C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.c_size_t, C.c_int,
@@ -666,6 +697,40 @@ def warp_params(max_ppm: float, steps: int = 8, radius: int = 4, centre_ppm: flo
     return AmWarpParams(float(centre_ppm), float(max_ppm), int(steps), int(radius))
 
 
+def channel_params(radius: int, noise_db: float = 60.0) -> AmChannelParams:
+    return AmChannelParams(int(radius), 0, float(noise_db))
+
+
+def channel_solve(r, c, noise_db: float = 60.0):
+    """am_channel_solve (pure host function): (h, ill) -- the taps h[-P .. P] (f64, h[l] at l + P) of the needle's
+    autocorrelation r[0 .. 2P] and the cross-correlation c[-P .. P], by the Levinson recursion for a general right-hand
+    side; ill: it fell back to the plain gain."""
+    r = np.ascontiguousarray(r, dtype=np.float64)
+    c = np.ascontiguousarray(c, dtype=np.float64)
+    if r.size != c.size or r.size % 2 == 0:
+        raise ValueError("channel_solve: r and c hold 2P + 1 values each")
+    h = np.empty(r.size, dtype=np.float64)
+    ill = C.c_int(0)
+    _check(lib().am_channel_solve(r.ctypes.data, c.ctypes.data, r.size // 2, float(noise_db), h.ctypes.data, C.byref(ill)))
+    return h, bool(ill.value)
+
+
+def hit_residual(haystack, start: int, needle, taps):
+    """am_hit_residual (pure host function): (model, resid) over the S + 2P elements from start - P on -- the needle
+    filtered by the hit's taps (hit_channel), and the host haystack minus that; resid is NaN where the haystack has no
+    finite sample."""
+    a, fmt, n = _samples(haystack)
+    nd = np.ascontiguousarray(needle, dtype=np.float32)
+    t = np.ascontiguousarray(taps, dtype=np.float32)
+    if t.size % 2 == 0:
+        raise ValueError("hit_residual: taps hold 2P + 1 values")
+    model = np.empty(nd.size + t.size - 1, dtype=np.float32)
+    resid = np.empty_like(model)
+    _check(lib().am_hit_residual(a.ctypes.data, n, int(fmt), int(start), nd.ctypes.data, nd.size, t.ctypes.data, t.size // 2,
+                                 model.ctypes.data, resid.ctypes.data))
+    return model, resid
+
+
 def _estimate_out(length: int):
     return np.empty(length, dtype=np.float32), np.empty(length, dtype=np.float32), np.empty(length, dtype=np.uint32)
 
@@ -880,6 +945,21 @@ def _hit_batch(fam, algos, ptrs, lengths, peaks_per_pair, fmt, args):
     out, m = _hit_call(fam, "_batch_device", (handles, nn, arr_p, arr_l, k, int(fmt), buf, cap, counts), cap * k * nn, args)
     return [[[fam.unpack(out, (h * nn + j) * cap + i, m) for i in range(counts[h * nn + j])] for j in range(nn)]
             for h in range(k)]
+
+
+def _channel_call(form, lead, n_hits, cp):
+    """One form of am_hit_channel: `lead`, the parameters, then the records and the taps, sized for n_hits hits.  Returns
+    (records, taps [n_hits, 2P + 1])."""
+    out = (HitChannel * max(1, n_hits))()
+    taps = np.zeros((max(1, n_hits), 2 * int(cp.radius) + 1), dtype=np.float32)
+    _check(getattr(lib(), "am_hit_channel" + form)(*lead, C.byref(cp), out, taps.ctypes.data))
+    return out, taps
+
+
+def _channel_device(algo, ptr, length, peaks, fmt, cp, form="_device"):
+    k = len(peaks)
+    out, taps = _channel_call(form, (algo._h, ptr, length, int(fmt), _peak_array(peaks), k), k, cp)
+    return [HitChannel.from_buffer_copy(out[i]) for i in range(k)], taps[:k].copy()
 
 
 # ---------------------------------------------------------------------------
@@ -1127,6 +1207,16 @@ class HipConvolve:
         """am_hit_warp: for each of `peaks` of a host haystack (as in hit_scores) its HitWarp record over the grid `wp`
         (warp_params)."""
         return _hit_host(_WARP, self, haystack, peaks, (wp,))
+
+    def hit_channel(self, haystack, peaks, cp: AmChannelParams):
+        """am_hit_channel: for each of `peaks` of a host haystack (as in hit_scores) its HitChannel record and its taps
+        h[-P .. P] under `cp` (channel_params): (records, taps ndarray [n, 2P + 1])."""
+        a, fmt, length = _samples(haystack)
+        return _channel_device(self, a.ctypes.data, length, peaks, fmt, cp, form="")
+
+    def hit_channel_device(self, ptr: int, length: int, peaks, cp: AmChannelParams, fmt: int = Fmt.F32_MONO):
+        """am_hit_channel_device: the same for a haystack resident on this needle's device."""
+        return _channel_device(self, ptr, length, peaks, fmt, cp)
 
     def hit_warp_device(self, ptr: int, length: int, peaks, wp: AmWarpParams, fmt: int = Fmt.F32_MONO):
         """am_hit_warp_device: the same for a haystack resident on this needle's device."""
@@ -1473,6 +1563,25 @@ def hit_segments_batch_device(algos, ptrs, lengths, peaks_per_pair, segments: in
     """am_hit_segments_batch_device: peaks_per_pair[k][j] as in hit_scores_batch_device; result [k][j][i] = the
     `segments` HitSegment records of hit i of haystack k against needle j."""
     return _hit_batch(_SEGMENTS, algos, ptrs, lengths, peaks_per_pair, fmt, (segments, radius))
+
+
+def hit_channel_batch_device(algos, ptrs, lengths, peaks_per_pair, cp: AmChannelParams, fmt: int = Fmt.F32_MONO):
+    """am_hit_channel_batch_device: peaks_per_pair[k][j] as in hit_scores_batch_device; result [k][j] = (records, taps
+    [n, 2P + 1]) of that pair's hits."""
+    nn, k = len(algos), len(ptrs)
+    pairs = [peaks_per_pair[h][j] for h in range(k) for j in range(nn)]
+    cap = max([1] + [len(hits) for hits in pairs])
+    handles = (C.c_void_p * max(1, nn))(*[a._h for a in algos])
+    arr_p = (C.c_void_p * max(1, k))(*ptrs)
+    arr_l = (C.c_size_t * max(1, k))(*lengths)
+    buf = (AmPeak * max(1, cap * k * nn))()
+    counts = (C.c_size_t * max(1, k * nn))(*[len(hits) for hits in pairs])
+    for q, hits in enumerate(pairs):
+        for i, p in enumerate(hits):
+            buf[q * cap + i] = _am_peak(p)
+    out, taps = _channel_call("_batch_device", (handles, nn, arr_p, arr_l, k, int(fmt), buf, cap, counts), cap * k * nn, cp)
+    return [[([HitChannel.from_buffer_copy(out[(h * nn + j) * cap + i]) for i in range(counts[h * nn + j])],
+              taps[(h * nn + j) * cap:(h * nn + j) * cap + counts[h * nn + j]].copy()) for j in range(nn)] for h in range(k)]
 
 
 def hit_warp_batch_device(algos, ptrs, lengths, peaks_per_pair, wp: AmWarpParams, fmt: int = Fmt.F32_MONO):

@@ -110,6 +110,29 @@ pub const AM_WARP_PHASES: usize = 4096;
 pub const AM_WARP_TAPS: usize = 32;
 pub const AM_WARP_MAX_STEPS: u32 = 32;
 pub const AM_WARP_MAX_PPM: f64 = 50000.0;
+/// am_channel_params: per-hit channel estimation (am_hit_channel*), 16 bytes
+#[repr(C)]
+#[derive(Clone, Copy, Default, Debug)]
+pub struct AmChannelParams {
+    pub radius: u32,
+    pub reserved: u32,
+    pub noise_db: f64,
+}
+/// am_channel_hit: how well the needle, filtered by the hit's own taps, explains the span (32 bytes)
+#[repr(C)]
+#[derive(Clone, Copy, Default, Debug)]
+pub struct AmChannelHit {
+    pub ncc: f32,
+    pub ncc_eq: f32,
+    pub gain_db: f32,
+    pub residual_db: f32,
+    pub main_tap: i32,
+    pub main_share: f32,
+    pub flags: u32,
+    pub reserved: u32,
+}
+pub const AM_HIT_ILL_CONDITIONED: u32 = 512;
+pub const AM_CHAN_MAX_RADIUS: u32 = 128;
 /// am_band_params: per-band hit scoring (am_hit_bands*)
 #[repr(C)]
 #[derive(Clone, Copy, Debug)]
@@ -378,6 +401,26 @@ extern "C" {
     pub fn am_hit_window_warped(
         haystack: *const std::ffi::c_void, len: usize, sample_format: c_int, start: u64, scale: f32, lag: f64, drift_ppm: f64,
         lead: u64, length: u64, row: *mut f32,
+    ) -> c_int;
+    /// per-hit channel estimation: the filter a hit went through, and what is left of its span (audiomatch.h);
+    /// taps: n x (2 radius + 1) f32 in host memory
+    pub fn am_hit_channel(
+        h: *const AmNeedle, haystack: *const std::ffi::c_void, len: usize, sample_format: c_int, peaks: *const AmPeak, n: usize,
+        cp: *const AmChannelParams, out: *mut AmChannelHit, taps: *mut f32,
+    ) -> c_int;
+    pub fn am_hit_channel_device(
+        h: *const AmNeedle, d_haystack: *const std::ffi::c_void, len: usize, sample_format: c_int, peaks: *const AmPeak, n: usize,
+        cp: *const AmChannelParams, out: *mut AmChannelHit, taps: *mut f32,
+    ) -> c_int;
+    pub fn am_hit_channel_batch_device(
+        needles: *const *const AmNeedle, n_needles: usize, d_haystacks: *const *const std::ffi::c_void, lens: *const usize,
+        n_hay: usize, sample_format: c_int, peaks: *const AmPeak, cap_per_pair: usize, n_peaks: *const usize,
+        cp: *const AmChannelParams, out: *mut AmChannelHit, taps: *mut f32,
+    ) -> c_int;
+    pub fn am_channel_solve(r: *const f64, c: *const f64, radius: u32, noise_db: f64, h: *mut f64, ill: *mut c_int) -> c_int;
+    pub fn am_hit_residual(
+        haystack: *const std::ffi::c_void, len: usize, sample_format: c_int, start: u64, needle: *const f32, s: usize,
+        taps: *const f32, radius: u32, model: *mut f32, resid: *mut f32,
     ) -> c_int;
     /// per-band hit scoring: which frequencies of the needle a hit holds (audiomatch.h)
     pub fn am_hit_bands(

@@ -812,6 +812,105 @@ int am_hit_warp_batch_device(const am_needle* const* needles, size_t n_needles,
 int am_hit_window_warped(const void* haystack, size_t len, int sample_format, uint64_t start, float scale,
                          double lag, double drift_ppm, uint64_t lead, uint64_t length, float* row);
 
+/* ---- per-hit channel estimation: the filter a hit went through ------------------- */
+/* The reference has no such stage (it reports one offset and one height per hit, matcher/mod.rs:110-125).  A jingle played
+ * through another chain -- an EQ, a codec's pre-echo, a short echo, a sub-sample delay -- scores a low broadband NCC, and
+ * the families above can only say that it is low.  This family estimates, per hit, the short filter that turns the needle
+ * into what the recording holds, and reports how well the filtered needle explains the span.
+ *
+ * For a hit with t = peak.start: n[0 .. S) the handle's whole needle, n~ the needle with 0 outside [0, S), x the haystack
+ * (f32 mono, or the bit-exact down-mix for AM_FMT_S16_STEREO), 0 outside [0, len), P = cp->radius, everything in f64 (a
+ * product of two f32 values is exact there):
+ *     c[l] = sum_{i<S} x[t + l + i] n[i],        l = -P .. P    (the cross-correlation around the hit)
+ *     r[k] = sum_{i=k}^{S-1} n[i] n[i - k],      k = 0 .. 2P    (the needle's autocorrelation)
+ *     E_n = r[0],   E_w = sum_{i<S} x[t + i]^2,   E_x = sum_{u=-P}^{S+P-1} x[t + u]^2
+ *   Order of the sums.  The needle is cut into slices of 4096 samples from its start.  Within a slice, work item w of 256
+ *   adds the products of its 16 consecutive needle samples 16 w .. 16 w + 15 in ascending order; the 256 values are added
+ *   by a butterfly over each wave of 64 (distances 32, 16, .. 1), then the four waves in order; the slices are added in
+ *   slice order.  E_w adds the squares the same way.  E_x adds, per work item, behind its 16 squares of [0, S): in slice 0
+ *   the square of x[t - P + w] (w < P, the head), then in the last slice the square of x[t + S + w] (w < P, the tail).
+ *   r is summed like c, with the needle in the place of x; it is computed once per distinct needle of a call.
+ * Taps.  h[-P .. P] is the least-squares filter with x[t + u] ~ sum_l h[l] n~[u - l] over all u (the autocorrelation
+ *   method): T h = c, T[a][b] = r[|a - b|] with the diagonal multiplied by 1 + 10^(-noise_db / 10) (the white-noise
+ *   correction of am_whiten_taps; noise_db in [0, 200]).  T is symmetric Toeplitz; it is solved on the host by the Levinson
+ *   recursion for a general right-hand side in f64, in one fixed order (am_channel_solve).  taps[l + P] = fl32(h[l]),
+ *   rounded once.  P = 0: h[0] = c[0] / (r[0] (1 + lambda)).
+ * The record, from the unrounded h, with q = h^T R h, R[a][b] = r[|a - b|] (uncorrected), h.c = sum_l h[l] c[l]:
+ *   ncc          c[0] / sqrt(E_n E_w); 0 with AM_HIT_BELOW_FLOOR by the floor rule of am_hit_scores.
+ *   ncc_eq       (h . c) / sqrt(E_x q): the NCC of the span against the filtered needle, in [-1, 1].  0 with
+ *                AM_HIT_BELOW_FLOOR when E_x = 0, when q <= 0 or when E_x < E_n 10^(-score_norm_floor_db / 10).
+ *   gain_db      10 log10(q / E_n), the channel's energy gain; -inf for q <= 0.
+ *   residual_db  10 log10(max(E_x - 2 h.c + q, 0) / E_x): the share of the span the filtered needle does not explain;
+ *                -inf when the numerator is 0, NaN when E_x = 0.
+ *   main_tap     the l with the largest |h[l]|; ties go to the smaller |l|, then to the negative l.
+ *   main_share   h[main_tap]^2 / sum_l h[l]^2: 1 for a pure gain and delay; 0 if all taps are 0.
+ *   flags        AM_HIT_NONFINITE: a needle sample, or a sample of x[t - P, t + S + P) inside [0, len), is not finite; the
+ *                five floats and all taps are NaN, main_tap = 0, no other flag.
+ *                AM_HIT_EMPTY_SEGMENT (reused): E_n = 0; the taps are 0, ncc = ncc_eq = 0, main_tap = 0, main_share = 0,
+ *                gain_db NaN, residual_db 0 for E_x > 0 and NaN for E_x = 0, no other flag.
+ *                AM_HIT_ILL_CONDITIONED: the recursion met a prediction error <= 0, a reflection coefficient with
+ *                |k| >= 1, or a value that is not finite; the taps fall back to the plain gain, h[0] = c[0] / r[0], the
+ *                rest 0, and the record is computed from that.
+ * A hit's record and taps depend on the needle, the samples in [t - P, t + S + P), P, noise_db and the floor only: the three
+ * forms agree bit for bit, whatever else the call holds.  The host form stages [t - P, t + S + P) of each hit only, clipped
+ * and merged.  The cost is proportional to hits x (2P + 1 rounded up to 32) x S; a large call runs its hits in rounds of
+ * bounded scratch memory.  out[i] and taps[i (2P+1) ..] belong to peaks[i]; taps is host memory.
+ * Measured on an MI355X (64 hits of a 10 s needle at 44.1 kHz in a resident 1 h haystack): 8.9 us per hit with P = 16 and
+ * 92.9 us per hit with P = 128, of which the kernels take 6.9 and 30.3 us and the host's solve the rest; the kernels at
+ * P = 128 take 0.61 of the eight am_hit_segments calls (m = 1, R = 16) that cover the same 257 lags
+ * (tools/hit_channel_bench.py, profiles/r20/).
+ * AM_ERR_INVALID_ARG, naming the hit (and pair) or the field: cp's radius > AM_CHAN_MAX_RADIUS, reserved != 0, noise_db
+ * outside [0, 200] or not finite, an unknown sample format (these are checked first, whatever n is); a null pointer with
+ * n > 0 (taps included); peak.start + S > len; a haystack on another device.  n = 0 returns AM_OK and launches nothing. */
+enum { AM_HIT_ILL_CONDITIONED = 512 };
+#define AM_CHAN_MAX_RADIUS 128
+typedef struct am_channel_params {
+    uint32_t radius;     /* P, 0 .. AM_CHAN_MAX_RADIUS: taps -P .. P */
+    uint32_t reserved;   /* 0 */
+    double noise_db;     /* the white-noise correction, 0 .. 200 (60 is a good choice) */
+} am_channel_params;     /* 16 bytes, no padding */
+typedef struct am_channel_hit {
+    float ncc;           /* the plain NCC of the window */
+    float ncc_eq;        /* the NCC of the span against the filtered needle */
+    float gain_db;       /* the channel's energy gain */
+    float residual_db;   /* the unexplained share of the span */
+    int32_t main_tap;    /* the lag of the largest tap */
+    float main_share;    /* its share of the taps' energy */
+    uint32_t flags;      /* AM_HIT_* */
+    uint32_t reserved;   /* 0 */
+} am_channel_hit;        /* 32 bytes, no padding */
+int am_hit_channel_device(const am_needle* h, const void* d_haystack, size_t len, int sample_format,
+                          const am_peak* peaks, size_t n, const am_channel_params* cp,
+                          am_channel_hit* out, float* taps /* n x (2P+1), host */);
+int am_hit_channel(const am_needle* h, const void* haystack, size_t len, int sample_format,
+                   const am_peak* peaks, size_t n, const am_channel_params* cp,
+                   am_channel_hit* out, float* taps /* n x (2P+1) */);
+/* pair (k, j) = haystack k against needle j, slots as in am_hit_scores_batch_device; the taps of slot q of pair p at
+ * (p cap_per_pair + q)(2P+1); untouched slots stay untouched */
+int am_hit_channel_batch_device(const am_needle* const* needles, size_t n_needles,
+                                const void* const* d_haystacks, const size_t* lens, size_t n_hay, int sample_format,
+                                const am_peak* peaks, size_t cap_per_pair, const size_t* n_peaks,
+                                const am_channel_params* cp, am_channel_hit* out, float* taps);
+/* Pure host function (no device): the solve above.  r: 2P+1 doubles r[0 .. 2P], c: 2P+1 doubles c[-P .. P] (c[l] at l + P),
+ * h: 2P+1 doubles (h[l] at l + P).  The recursion, for the matrix t[0] = r[0] (1 + lambda), t[k] = r[k], in f64, every sum
+ * in ascending index order: a = {1}, err = t[0], h[0] = c[0] / t[0]; for m = 1 .. 2P: k = -(t[m] + sum_{i=1}^{m-1} a[i]
+ * t[m-i]) / err; a'[i] = a[i] + k a[m-i] (0 < i < m), a'[m] = k; err = err (1 - k^2); d = (c[m] - sum_{i<m} t[m-i] h[i])
+ * / err; h[i] += d a'[m-i] (i <= m).  *ill != 0 when it fell back to the plain gain (h[P] = c[P] / r[0], the rest 0), as
+ * AM_HIT_ILL_CONDITIONED says; with r[0] <= 0 every h is 0 and *ill != 0.
+ * AM_ERR_INVALID_ARG: a null pointer, radius > AM_CHAN_MAX_RADIUS, noise_db out of range, a non-finite r[k] or c[l]. */
+int am_channel_solve(const double* r, const double* c, uint32_t radius, double noise_db, double* h, int* ill);
+/* Pure host function (no device): the filtered needle under a hit and what is left of the span.  For u in [0, S + 2P),
+ * haystack element e = start - P + u:
+ *   model[u] = fl32( sum_{l=-P..P} (double)taps[l+P] (double)n[u - P - l] ), over the l with u - P - l in [0, S), in f64,
+ *              in the order l = -P .. P, rounded once;
+ *   resid[u] = x[e] - model[u] (one f32 subtraction); NaN where e lies outside [0, len) or x[e] is not finite.
+ * needle: S f32 samples in host memory; model or resid may be null.  What lies over the hit -- the voice-over, the start of
+ * the next item -- is resid; x - gain n leaves most of an equalised jingle in place.
+ * AM_ERR_INVALID_ARG: an unknown sample format, a null pointer (haystack: with len > 0), s = 0, radius >
+ * AM_CHAN_MAX_RADIUS, start or s >= 2^62. */
+int am_hit_residual(const void* haystack, size_t len, int sample_format, uint64_t start, const float* needle, size_t s,
+                    const float* taps, uint32_t radius, float* model, float* resid);
+
 /* ---- device memory plumbing (for hosts without their own HIP allocator) -- */
 int am_device_malloc(int device, size_t bytes, void** out);
 int am_device_free(int device, void* p);

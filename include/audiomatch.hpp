@@ -239,6 +239,44 @@ public:
         check(am_hit_window_warped(haystack, len, sample_format, start, scale, lag, drift_ppm, lead, length, row.data()));
         return row;
     }
+    // per-hit channel estimation (am_hit_channel): each peak's record, and its taps h[-P .. P] at taps[i (2P + 1) ..]
+    struct ChannelHits {
+        std::vector<am_channel_hit> records;
+        std::vector<float> taps;
+    };
+    ChannelHits hit_channel(const void* haystack, std::size_t len, int sample_format, const std::vector<am_peak>& peaks,
+                            const am_channel_params& cp) const {
+        ChannelHits out{std::vector<am_channel_hit>(peaks.size()), std::vector<float>(peaks.size() * (2 * static_cast<std::size_t>(cp.radius) + 1))};
+        check(am_hit_channel(h_, haystack, len, sample_format, peaks.data(), peaks.size(), &cp, out.records.data(), out.taps.data()));
+        return out;
+    }
+    ChannelHits hit_channel_device(const void* d_haystack, std::size_t len, int sample_format, const std::vector<am_peak>& peaks,
+                                   const am_channel_params& cp) const {
+        ChannelHits out{std::vector<am_channel_hit>(peaks.size()), std::vector<float>(peaks.size() * (2 * static_cast<std::size_t>(cp.radius) + 1))};
+        check(am_hit_channel_device(h_, d_haystack, len, sample_format, peaks.data(), peaks.size(), &cp, out.records.data(), out.taps.data()));
+        return out;
+    }
+    // the solve by itself (am_channel_solve) and the filtered needle under a hit with what is left (am_hit_residual); no
+    // device needed.  The batch form is am_hit_channel_batch_device of the C interface.
+    static std::vector<double> channel_solve(const std::vector<double>& r, const std::vector<double>& c, double noise_db, bool* ill = nullptr) {
+        std::vector<double> h(r.size());
+        int fell_back = 0;
+        if (r.size() != c.size() || r.size() % 2 == 0) throw Error(AM_ERR_INVALID_ARG, "channel_solve: r and c hold 2P + 1 values each");
+        check(am_channel_solve(r.data(), c.data(), static_cast<std::uint32_t>(r.size() / 2), noise_db, h.data(), &fell_back));
+        if (ill) *ill = fell_back != 0;
+        return h;
+    }
+    struct Residual {
+        std::vector<float> model, resid;
+    };
+    static Residual hit_residual(const void* haystack, std::size_t len, int sample_format, std::uint64_t start, const std::vector<float>& needle,
+                                 const std::vector<float>& taps) {
+        if (taps.size() % 2 == 0) throw Error(AM_ERR_INVALID_ARG, "hit_residual: taps hold 2P + 1 values");
+        Residual out{std::vector<float>(needle.size() + taps.size() - 1), std::vector<float>(needle.size() + taps.size() - 1)};
+        check(am_hit_residual(haystack, len, sample_format, start, needle.data(), needle.size(), taps.data(),
+                              static_cast<std::uint32_t>(taps.size() / 2), out.model.data(), out.resid.data()));
+        return out;
+    }
     // per-band hit scoring (am_hit_bands): bp.n_bands records per peak, peak i band b at i * n_bands + b
     std::vector<am_hit_band> hit_bands(const void* haystack, std::size_t len, int sample_format, const std::vector<am_peak>& peaks,
                                        const am_band_params& bp) const {
