@@ -399,6 +399,26 @@ hipError_t launch_lag_slices(hipStream_t st, const LagDesc* tab, long long first
 hipError_t launch_lag_combine(hipStream_t st, const LagDesc* tab, long long n, int nt, int nlag_max, const double* parts,
                               const unsigned* pflags, double* sums);
 
+// ---- am_stereo.hip: per-hit stereo image (am_hit_stereo*) and the stereo mix (am_pcm_s16_stereo_mix*) ----
+// The slice kernel exists for the radii of kSegRadii, as seg_slices does.  A partial record: C_L(-RT .. RT), C_R(-RT .. RT)
+// as doubles, then S_LL, S_RR, S_LR as 64-bit integers in the same 8-byte slots.
+constexpr int stereo_record_len(int rt) { return 2 * (2 * rt + 1) + 3; }
+// One hit of a call, as the kernels read it (the call's table, uploaded once); R is the call's
+struct StereoDesc {
+    const void* win;      // device: frame t of the haystack (i16 stereo)
+    const float* needle;  // device: the whole needle
+    long long s;          // needle length
+    long long ulo, uhi;   // frame t + u exists (and is read) for ulo <= u < uhi only: [-R, s + R) clipped to the haystack
+    long long part0;      // first partial record of the hit: slice k at part0 + k
+    double en;            // sum(needle^2)
+    double floor_ratio;   // 10^(-score_norm_floor_db / 10)
+};
+// parts: stereo_record_len(seg_kernel_radius(r)) doubles per slice, pflags: one word per slice; d_out: n records
+hipError_t launch_hit_stereo(hipStream_t st, const StereoDesc* d_hits, long long n, int r, long long max_slices, double* parts,
+                             unsigned* pflags, am_stereo_hit* d_out);
+// out[i] = f32((f64(a) L[i] + f64(b) R[i]) k), k = (double)(1.0f / 65535.0f)
+hipError_t launch_pcm_mix(hipStream_t st, const int16_t* in, long long frames, float a, float b, float* out);
+
 // ---- am_bands.hip: per-band hit scoring (am_hit_bands*) ----
 constexpr int kBandGroup = 8;   // consecutive frames per workgroup of the frame kernel, counted from the hit's first frame
 inline int band_record_len(int n_bands) { return 4 * n_bands + 1; }   // doubles per partial record: (Re C, Im C, E_x, E_n) per band, E_n over every bin

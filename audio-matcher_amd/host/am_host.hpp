@@ -83,6 +83,10 @@ struct Arguments {
     std::optional<std::uint32_t> channel_radius;   // extension: --channel P[:NOISE_DB], the filter every printed hit went through (am_hit_channel): taps -P .. P
     double channel_noise_db = 60.0;           // ... the white-noise correction of the solve
     std::string residual_prefix;              // extension: --residual PREFIX, what is left of each printed hit's span (am_hit_residual) as PREFIX<file index>_<start>.wav; empty = off
+    bool mix_set = false;                     // extension: --mix left|right|mid|side|A,B, a two-channel file through am_pcm_s16_stereo_mix instead of the down-mix
+    float mix_a = 0.5f, mix_b = 0.5f;         // ... out = a L + b R; mid (0.5, 0.5) is the down-mix itself
+    std::optional<std::uint32_t> stereo_radius;   // extension: --stereo R[:MIN_NCC], where every printed hit sits between the channels (am_hit_stereo): lags -R .. R
+    float stereo_min_ncc = 0.5f;              // ... what a channel's |NCC| must reach to count (am_hit_stereo_summary)
     std::uint32_t bands = 0;                  // extension: --bands B[:LOG2F], per-band scoring of every printed hit (am_hit_bands), 0 = off
     std::uint32_t band_frame_log2 = 11;       // ... in frames of 2^LOG2F samples
     std::optional<float> min_significance;    // extension: --min-significance Z, drop hits whose z against the local background is below Z (am_hit_significance)
@@ -153,6 +157,17 @@ inline const char* usage_text() {
            "                         span (P samples each side) minus the filtered snippet: what lies over or under the\n"
            "                         jingle; mono 32-bit float, samples outside the file as 0.  Not with --whiten or\n"
            "                         --preemphasis, nor for a file whose rate differs from the snippet's\n"
+           "  --mix M                what a 16-bit two-channel file (main file or snippet) is matched as: left, right, mid\n"
+           "                         (the default: the down-mix (l + r) / 2), side ((l - r) / 2: finds an insert that sits\n"
+           "                         polarity-inverted in the two channels and cancels in the down-mix), or A,B for\n"
+           "                         A l + B r.  Refused for a mono or float file and with --live\n"
+           "  --stereo R[:MIN_NCC]   after each hit's offset line, print where the hit sits between the channels of the\n"
+           "                         16-bit two-channel main file: the image (centre, left, right, panned, inverted or\n"
+           "                         absent), the NCC of the left and the right channel (the sign is the polarity), of the\n"
+           "                         side signal and of the best fixed mix, the balance in dB, the delay between the\n"
+           "                         channels in frames (lags -R .. R, R in 0..16) and what the down-mix cost in dB; a\n"
+           "                         channel counts when its |NCC| reaches MIN_NCC (default 0.5).  Not with --live,\n"
+           "                         --resample, --whiten or --preemphasis\n"
            "  --bands B[:LOG2F]      after each hit's offset line, print which of B log-spaced frequency bands of the\n"
            "                         snippet (50 Hz up to 16 kHz or half the sample rate) the hit holds ('#' present,\n"
            "                         '.' absent: the band's coherence against --min-confidence if given, else 0.5),\n"
@@ -315,6 +330,37 @@ inline Arguments parse_arguments(int argc, const char* const* argv) {
             a.residual_prefix = need(i);
             if (a.residual_prefix.empty()) throw ArgError("invalid value '' for --residual (a file name prefix)");
         }
+        else if (s == "--mix") {
+            const std::string v = need(i);
+            a.mix_set = true;
+            if (v == "left") { a.mix_a = 1.0f; a.mix_b = 0.0f; }
+            else if (v == "right") { a.mix_a = 0.0f; a.mix_b = 1.0f; }
+            else if (v == "mid") { a.mix_a = 0.5f; a.mix_b = 0.5f; }
+            else if (v == "side") { a.mix_a = 0.5f; a.mix_b = -0.5f; }
+            else {
+                const std::size_t comma = v.find(',');
+                const std::string va = v.substr(0, comma), vb = comma == std::string::npos ? "" : v.substr(comma + 1);
+                char *ea = nullptr, *eb = nullptr;
+                const float fa = std::strtof(va.c_str(), &ea), fb = std::strtof(vb.c_str(), &eb);
+                if (va.empty() || vb.empty() || *ea != '\0' || *eb != '\0' || !std::isfinite(fa) || !std::isfinite(fb))
+                    throw ArgError("invalid value '" + v + "' for --mix (left, right, mid, side or A,B)");
+                a.mix_a = fa;
+                a.mix_b = fb;
+            }
+        }
+        else if (s == "--stereo") {
+            const std::string v = need(i);
+            const std::size_t colon = v.find(':');
+            const std::string vr = v.substr(0, colon), vm = colon == std::string::npos ? "0.5" : v.substr(colon + 1);
+            char* end = nullptr;
+            const unsigned long r = std::strtoul(vr.c_str(), &end, 10);
+            const bool r_ok = !vr.empty() && vr[0] >= '0' && vr[0] <= '9' && *end == '\0' && r <= AM_STEREO_MAX_RADIUS;
+            const float mn = std::strtof(vm.c_str(), &end);
+            if (!r_ok || vm.empty() || *end != '\0' || !(mn >= 0.0f && mn <= 1.0f))
+                throw ArgError("invalid value '" + v + "' for --stereo (R[:MIN_NCC], R in 0..16 lags each side, MIN_NCC in 0..1)");
+            a.stereo_radius = (std::uint32_t)r;
+            a.stereo_min_ncc = mn;
+        }
         else if (s == "--bands") {
             const std::string v = need(i);
             const std::size_t colon = v.find(':');
@@ -403,6 +449,10 @@ inline Arguments parse_arguments(int argc, const char* const* argv) {
     if (!a.residual_prefix.empty() && !a.channel_radius) throw ArgError("--residual needs --channel");
     if (!a.residual_prefix.empty() && (a.whiten || a.preemphasis))
         throw ArgError("--residual does not apply with --whiten or --preemphasis (the span would be that of the filtered signal)");
+    if (a.stereo_radius && (a.resample || a.whiten || a.preemphasis))
+        throw ArgError("--stereo does not apply with --resample, --whiten or --preemphasis (the snippet would no longer be on the frames' footing)");
+    if (a.live && a.mix_set) throw ArgError("--live: --mix does not apply");
+    if (a.live && a.stereo_radius) throw ArgError("--live: --stereo does not apply");
     if (!a.learn_needle.empty()) {
         if (a.live) throw ArgError("--live: --learn-needle does not apply");
         if (a.best) throw ArgError("--learn-needle and --best are mutually exclusive");
@@ -510,6 +560,19 @@ inline std::vector<float> to_mono_f32(const Pcm& pcm, int device) {
         const int rc = am_pcm_s16_stereo_to_mono(device, src, frames, out.data());
         if (rc != AM_OK) throw std::runtime_error(std::string("am_pcm_s16_stereo_to_mono: ") + am_last_error_string());
     }
+    return out;
+}
+
+// extension: --mix.  f32 mono samples of a file under the run's mix: without --mix, and with `mid`, the down-mix above,
+// byte for byte; otherwise a l + b r through am_pcm_s16_stereo_mix.  --mix is refused for a file that is not 16-bit
+// two-channel (`path` names it).
+inline std::vector<float> to_mono_f32(const Arguments& args, const Pcm& pcm, const std::string& path) {
+    if (!args.mix_set) return to_mono_f32(pcm, args.device);
+    if (pcm.is_float || pcm.channels != 2) throw std::runtime_error("--mix: '" + path + "' is not a 16-bit two-channel file");
+    if (args.mix_a == 0.5f && args.mix_b == 0.5f) return to_mono_f32(pcm, args.device);
+    std::vector<float> out(pcm.frames());
+    if (!out.empty() && am_pcm_s16_stereo_mix(args.device, pcm.s16.data(), out.size(), args.mix_a, args.mix_b, out.data()) != AM_OK)
+        throw std::runtime_error(std::string("am_pcm_s16_stereo_mix: ") + am_last_error_string());
     return out;
 }
 

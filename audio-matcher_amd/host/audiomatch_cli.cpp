@@ -202,6 +202,29 @@ static void write_residuals(const Arguments& args, const std::vector<float>& sam
     }
 }
 
+// extension: --stereo R[:MIN_NCC].  One line per hit, to follow the hit's offset line: where the hit sits between the
+// channels of the main file's own i16 frames (am_hit_stereo, am_hit_stereo_summary).
+static std::vector<std::string> stereo_lines(const Arguments& args, const am_needle* algo, const Pcm& m, const am_peak* peaks, size_t n) {
+    if (m.is_float || m.channels != 2) throw std::runtime_error("--stereo: the main file is not a 16-bit two-channel file");
+    std::vector<am_stereo_hit> recs(n);
+    const am_stereo_params sp{*args.stereo_radius, 0};
+    if (n > 0 && am_hit_stereo(algo, m.s16.data(), m.frames(), AM_FMT_S16_STEREO, peaks, n, &sp, recs.data()) != AM_OK)
+        throw std::runtime_error(std::string("am_hit_stereo: ") + am_last_error_string());
+    static const char* const images[] = {"absent", "centre", "left", "right", "panned", "inverted"};
+    std::vector<std::string> out;
+    for (const am_stereo_hit& q : recs) {
+        am_stereo_summary sm{};
+        if (am_hit_stereo_summary(&q, args.stereo_min_ncc, &sm) != AM_OK)
+            throw std::runtime_error(std::string("am_hit_stereo_summary: ") + am_last_error_string());
+        char line[320];
+        std::snprintf(line, sizeof line, "  stereo image %s ncc_left %.6f ncc_right %.6f ncc_side %.6f ncc_best %.6f balance_db %.2f delay %.3f downmix_loss_db %.2f%s%s",
+                      images[sm.image], (double)q.ncc_left, (double)q.ncc_right, (double)q.ncc_side, (double)q.ncc_best, sm.balance_db, sm.delay,
+                      sm.downmix_loss_db, (q.flags & AM_HIT_COLLINEAR) ? " (collinear channels)" : "", (q.flags & AM_HIT_NONFINITE) ? " (non-finite samples)" : "");
+        out.push_back(line);
+    }
+    return out;
+}
+
 // ... with --min-confidence: keeps the hits whose corrected NCC is at least X, in place (ws holds the records of exactly
 // these n hits); returns how many are left.  With --debug one line per hit (`prefix` in front).
 static size_t warp_confidence_filter(const Arguments& args, const WarpSet& ws, am_peak* peaks, size_t n, const std::string& prefix) {
@@ -343,7 +366,7 @@ static std::vector<float> filter_taps(const Arguments& args) {
     if (!args.whiten) return {};
     std::vector<double> r(args.whiten + 1, 0.0), part(args.whiten + 1);
     for (const std::string& main_file : args.within) {
-        const std::vector<float> x = to_mono_f32(read_wav(main_file), args.device);
+        const std::vector<float> x = to_mono_f32(args, read_wav(main_file), main_file);
         if (am_lag_products(args.device, x.data(), x.size(), AM_FMT_F32_MONO, args.whiten, part.data()) != AM_OK)
             throw std::runtime_error(std::string("am_lag_products: ") + am_last_error_string());
         for (size_t k = 0; k < r.size(); ++k) r[k] += part[k];
@@ -424,7 +447,7 @@ static Snippet load_snippet(const Arguments& args, const std::string& path, std:
     sn.name = base_name(path);
     sn.sr = pcm.sample_rate;
     sn.duration = (double)pcm.frames() / (double)sn.sr;
-    sn.data = to_mono_f32(pcm, args.device);
+    sn.data = to_mono_f32(args, pcm, path);
     if (!taps) taps = filter_taps(args);
     sn.h = make_needle(args, sn.data, sn.sr, sn.sr, *taps);
     return sn;
@@ -508,9 +531,11 @@ static std::vector<std::vector<am_peak>> match_hits_multi(const std::vector<cons
 // with --warp; --min-significance) drop hits from `hits`, the learner takes its rows of those that are left, and they
 // are printed, every line with `prefix` in front: the offset line (mod.rs:89) and under it the hit's --warp, --segments
 // and --bands lines; with --channel the hit's channel line, and with --residual its residual file (`snip`: the snippet as
-// read, `file_index`: the main file's place among the FILE arguments).
+// read, `file_index`: the main file's place among the FILE arguments); with --stereo the hit's stereo line (`m`: the main
+// file as read, its i16 frames kept).
 static void report_hits(const Arguments& args, const am_needle* algo, const std::vector<float>& m_samples, std::uint32_t m_sr,
-                        std::vector<am_peak>& hits, const std::string& prefix, Learner& learner, const Snippet& snip, size_t file_index) {
+                        std::vector<am_peak>& hits, const std::string& prefix, Learner& learner, const Snippet& snip, size_t file_index,
+                        const Pcm& m) {
     am_peak* pk = hits.data();
     size_t n = hits.size();
     const WarpSet warp = WarpSet::compute(args, algo, m_samples, pk, n);
@@ -535,8 +560,9 @@ static void report_hits(const Arguments& args, const am_needle* algo, const std:
             write_residuals(args, m_samples, m_sr, snip.data, file_index, pk, n, cs);
         }
     }
+    const std::vector<std::string> stereo = args.stereo_radius ? stereo_lines(args, algo, m, pk, n) : none;
     for (size_t i = 0; i < lines.size(); ++i)
-        for (const std::vector<std::string>* l : {&lines, &warps, &chans, &segs, &bands})
+        for (const std::vector<std::string>* l : {&lines, &stereo, &warps, &chans, &segs, &bands})
             if (i < l->size()) std::printf("%s%s\n", prefix.c_str(), (*l)[i].c_str());
 }
 
@@ -578,7 +604,7 @@ static int run_files(const Arguments& args) {
             }
             handles[j] = needle_at(args, snips[j], m_sr, *taps, overlaps[j]);
         }
-        const std::vector<float> m_samples = filtered(args, to_mono_f32(m, args.device), *taps);
+        const std::vector<float> m_samples = filtered(args, to_mono_f32(args, m, main_file), *taps);
         am_match_params p = make_params(args, m_sr, snips[0].duration);
         std::vector<std::vector<am_peak>> hits(k);
         if (k > 1 && !args.best && !args.normalize) {
@@ -590,7 +616,7 @@ static int run_files(const Arguments& args) {
             }
         }
         for (size_t j = 0; j < k; ++j)
-            report_hits(args, handles[j], m_samples, m_sr, hits[j], k > 1 ? snips[j].name + ": " : std::string(), learner, snips[j], file_index);
+            report_hits(args, handles[j], m_samples, m_sr, hits[j], k > 1 ? snips[j].name + ": " : std::string(), learner, snips[j], file_index, m);
         if (out_path) {                                                   // mod.rs:92-99
             std::vector<am_peak> all;
             for (const std::vector<am_peak>& h : hits) all.insert(all.end(), h.begin(), h.end());

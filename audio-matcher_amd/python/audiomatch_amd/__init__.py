@@ -125,6 +125,34 @@ AM_HIT_ILL_CONDITIONED = 512
 AM_CHAN_MAX_RADIUS = 128
 
 
+class AmStereoParams(C.Structure):    # am_stereo_params (include/audiomatch.h, per-hit stereo image)
+    _fields_ = [("radius", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class HitStereo(C.Structure):         # am_stereo_hit: where a hit sits between the channels
+    _fields_ = [("lag_left", C.c_double), ("lag_right", C.c_double), ("ncc_left", C.c_float), ("ncc_right", C.c_float),
+                ("ncc_mid", C.c_float), ("ncc_side", C.c_float), ("ncc_best", C.c_float), ("gain_left", C.c_float),
+                ("gain_right", C.c_float), ("mix_left", C.c_float), ("mix_right", C.c_float), ("flags", C.c_uint32)]
+
+    def __repr__(self):
+        return "HitStereo(" + ", ".join(f"{n}={getattr(self, n)!r}" for n, _ in self._fields_) + ")"
+
+    def pack(self) -> bytes:
+        """The record's 56 bytes (for bit-for-bit comparisons)."""
+        return bytes(self)
+
+
+class AmStereoSummary(C.Structure):   # am_stereo_summary
+    _fields_ = [("balance_db", C.c_double), ("delay", C.c_double), ("downmix_loss_db", C.c_double), ("image", C.c_int32),
+                ("reserved", C.c_uint32)]
+
+
+AM_HIT_LEFT_SILENT, AM_HIT_RIGHT_SILENT, AM_HIT_SIDE_SILENT, AM_HIT_COLLINEAR = 1024, 2048, 4096, 8192
+AM_HIT_LEFT_UNREFINED, AM_HIT_RIGHT_UNREFINED = 16384, 32768
+AM_STEREO_MAX_RADIUS, AM_STEREO_MIN_INDEPENDENCE = 16, 1e-6
+AM_IMAGE_ABSENT, AM_IMAGE_CENTRE, AM_IMAGE_LEFT, AM_IMAGE_RIGHT, AM_IMAGE_PANNED, AM_IMAGE_INVERTED = range(6)
+
+
 class AmBandParams(C.Structure):      # am_band_params (include/audiomatch.h, per-band hit scoring)
     _fields_ = [("frame_log2", C.c_uint32), ("n_bands", C.c_uint32), ("edges", C.c_uint32 * 33)]
 
@@ -400,6 +428,16 @@ _SIGNATURES = {
     "am_channel_solve": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_double, C.c_void_p, C.POINTER(C.c_int)]),
     "am_hit_residual": (C.c_int, [C.c_void_p, C.c_size_t, C.c_int, C.c_uint64, C.c_void_p, C.c_size_t, C.c_void_p, C.c_uint32,
                                   C.c_void_p, C.c_void_p]),
+    "am_hit_stereo_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.POINTER(AmPeak), C.c_size_t,
+                                       C.POINTER(AmStereoParams), C.POINTER(HitStereo)]),
+    "am_hit_stereo": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.POINTER(AmPeak), C.c_size_t,
+                                C.POINTER(AmStereoParams), C.POINTER(HitStereo)]),
+    "am_hit_stereo_batch_device": (C.c_int, [C.POINTER(C.c_void_p), C.c_size_t, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t),
+                                             C.c_size_t, C.c_int, C.POINTER(AmPeak), C.c_size_t, C.POINTER(C.c_size_t),
+                                             C.POINTER(AmStereoParams), C.POINTER(HitStereo)]),
+    "am_hit_stereo_summary": (C.c_int, [C.POINTER(HitStereo), C.c_float, C.POINTER(AmStereoSummary)]),
+    "am_pcm_s16_stereo_mix": (C.c_int, [C.c_int, C.c_void_p, C.c_size_t, C.c_float, C.c_float, C.c_void_p]),
+    "am_pcm_s16_stereo_mix_device": (C.c_int, [C.c_int, C.c_void_p, C.c_size_t, C.c_float, C.c_float, C.c_void_p]),
     "am_needle_estimate_rows": (C.c_int, [C.c_int, C.c_void_p, C.c_size_t, C.POINTER(AmEstimateParams), C.c_void_p, C.c_void_p,
                                           C.c_void_p]),
     "am_needle_estimate_device": (C.c_int, [C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.c_size_t, C.c_int,
@@ -569,6 +607,21 @@ def pcm_s16_stereo_to_mono(interleaved: np.ndarray, device: int = 0) -> np.ndarr
     out = np.empty(frames, dtype=np.float32)
     _check(lib().am_pcm_s16_stereo_to_mono(device, a.ctypes.data, frames, out.ctypes.data))
     return out
+
+
+def pcm_s16_stereo_mix(interleaved: np.ndarray, a: float, b: float, device: int = 0) -> np.ndarray:
+    """am_pcm_s16_stereo_mix: f32((f64(a) L + f64(b) R) k) of interleaved i16 stereo frames; (0.5, 0.5) is the down-mix,
+    (1, 0) left, (0, 1) right, (0.5, -0.5) side."""
+    x = np.ascontiguousarray(interleaved, dtype=np.int16)
+    frames = x.size // 2
+    out = np.empty(frames, dtype=np.float32)
+    _check(lib().am_pcm_s16_stereo_mix(device, x.ctypes.data, frames, float(a), float(b), out.ctypes.data))
+    return out
+
+
+def pcm_s16_stereo_mix_device(device: int, src_ptr: int, frames: int, a: float, b: float, dst_ptr: int):
+    """am_pcm_s16_stereo_mix_device: the same between two buffers resident on `device`."""
+    _check(lib().am_pcm_s16_stereo_mix_device(device, src_ptr, int(frames), float(a), float(b), dst_ptr))
 
 
 def _samples(x):
@@ -841,6 +894,22 @@ def hit_segments_summary(segments, needle_len: int, min_ncc: float = 0.5) -> Seg
                           out.last_present, out.n_present, out.n_usable)
 
 
+@dataclass
+class StereoSummary:
+    """am_stereo_summary: where one hit sits between the channels, from its HitStereo record."""
+    image: int
+    balance_db: float
+    delay: float
+    downmix_loss_db: float
+
+
+def hit_stereo_summary(rec, min_ncc: float = 0.5) -> StereoSummary:
+    """am_hit_stereo_summary (pure host code): `rec` = one hit's HitStereo record."""
+    out = AmStereoSummary()
+    _check(lib().am_hit_stereo_summary(C.byref(HitStereo.from_buffer_copy(bytes(rec))), float(min_ncc), C.byref(out)))
+    return StereoSummary(int(out.image), out.balance_db, out.delay, out.downmix_loss_db)
+
+
 def band_params(frame_log2: int, edges) -> AmBandParams:
     """am_band_params for F = 2^frame_log2 and the bands [edges[b], edges[b + 1]) (bin indices)."""
     edges = [int(e) for e in edges]
@@ -900,6 +969,9 @@ _WARP = _HitFamily(
 _BANDS = _HitFamily(
     "am_hit_bands", HitBand, lambda bp: (bp, int(bp.n_bands)),
     lambda out, i, m: [HitBand.from_buffer_copy(out[i * m + b]) for b in range(m)])
+_STEREO = _HitFamily(
+    "am_hit_stereo", HitStereo, lambda radius: (AmStereoParams(int(radius), 0), 1),
+    lambda out, i, m: HitStereo.from_buffer_copy(out[i]))
 _SIGNIFICANCE = _HitFamily(
     "am_hit_significance", HitSignificance, lambda guard, radius: (AmSignificanceParams(int(guard), int(radius)), 1),
     lambda out, i, m: HitSignificance.from_buffer_copy(out[i]))
@@ -1217,6 +1289,16 @@ class HipConvolve:
     def hit_channel_device(self, ptr: int, length: int, peaks, cp: AmChannelParams, fmt: int = Fmt.F32_MONO):
         """am_hit_channel_device: the same for a haystack resident on this needle's device."""
         return _channel_device(self, ptr, length, peaks, fmt, cp)
+
+    def hit_stereo(self, haystack, peaks, radius: int = 4):
+        """am_hit_stereo: for each of `peaks` of a host haystack of i16 stereo frames ((frames, 2) or flat) its HitStereo
+        record: per channel the best of the lags -radius .. radius, the polarity and the NCC, and the NCC of the mid, the
+        side and the best fixed mix."""
+        return _hit_host(_STEREO, self, haystack, peaks, (radius,))
+
+    def hit_stereo_device(self, ptr: int, length: int, peaks, radius: int = 4, fmt: int = Fmt.S16_STEREO):
+        """am_hit_stereo_device: the same for a haystack resident on this needle's device."""
+        return _hit_device(_STEREO, self, ptr, length, peaks, fmt, (radius,))
 
     def hit_warp_device(self, ptr: int, length: int, peaks, wp: AmWarpParams, fmt: int = Fmt.F32_MONO):
         """am_hit_warp_device: the same for a haystack resident on this needle's device."""
@@ -1563,6 +1645,12 @@ def hit_segments_batch_device(algos, ptrs, lengths, peaks_per_pair, segments: in
     """am_hit_segments_batch_device: peaks_per_pair[k][j] as in hit_scores_batch_device; result [k][j][i] = the
     `segments` HitSegment records of hit i of haystack k against needle j."""
     return _hit_batch(_SEGMENTS, algos, ptrs, lengths, peaks_per_pair, fmt, (segments, radius))
+
+
+def hit_stereo_batch_device(algos, ptrs, lengths, peaks_per_pair, radius: int = 4, fmt: int = Fmt.S16_STEREO):
+    """am_hit_stereo_batch_device: peaks_per_pair[k][j] as in hit_scores_batch_device; result [k][j] = the HitStereo records
+    of haystack k (i16 stereo frames) against needle j."""
+    return _hit_batch(_STEREO, algos, ptrs, lengths, peaks_per_pair, fmt, (radius,))
 
 
 def hit_channel_batch_device(algos, ptrs, lengths, peaks_per_pair, cp: AmChannelParams, fmt: int = Fmt.F32_MONO):

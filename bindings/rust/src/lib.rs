@@ -133,6 +133,54 @@ pub struct AmChannelHit {
 }
 pub const AM_HIT_ILL_CONDITIONED: u32 = 512;
 pub const AM_CHAN_MAX_RADIUS: u32 = 128;
+/// am_stereo_params: per-hit stereo image (am_hit_stereo*), 8 bytes
+#[repr(C)]
+#[derive(Clone, Copy, Default, Debug)]
+pub struct AmStereoParams {
+    pub radius: u32,
+    pub reserved: u32,
+}
+/// am_stereo_hit: where a hit sits between the channels of a haystack of i16 stereo frames (56 bytes)
+#[repr(C)]
+#[derive(Clone, Copy, Default, Debug)]
+pub struct AmStereoHit {
+    pub lag_left: f64,
+    pub lag_right: f64,
+    pub ncc_left: f32,
+    pub ncc_right: f32,
+    pub ncc_mid: f32,
+    pub ncc_side: f32,
+    pub ncc_best: f32,
+    pub gain_left: f32,
+    pub gain_right: f32,
+    pub mix_left: f32,
+    pub mix_right: f32,
+    pub flags: u32,
+}
+/// am_stereo_summary: image (AM_IMAGE_*), balance, inter-channel delay and what the down-mix cost (32 bytes)
+#[repr(C)]
+#[derive(Clone, Copy, Default, Debug)]
+pub struct AmStereoSummary {
+    pub balance_db: f64,
+    pub delay: f64,
+    pub downmix_loss_db: f64,
+    pub image: i32,
+    pub reserved: u32,
+}
+pub const AM_HIT_LEFT_SILENT: u32 = 1024;
+pub const AM_HIT_RIGHT_SILENT: u32 = 2048;
+pub const AM_HIT_SIDE_SILENT: u32 = 4096;
+pub const AM_HIT_COLLINEAR: u32 = 8192;
+pub const AM_HIT_LEFT_UNREFINED: u32 = 16384;
+pub const AM_HIT_RIGHT_UNREFINED: u32 = 32768;
+pub const AM_STEREO_MAX_RADIUS: u32 = 16;
+pub const AM_STEREO_MIN_INDEPENDENCE: f64 = 1e-6;
+pub const AM_IMAGE_ABSENT: i32 = 0;
+pub const AM_IMAGE_CENTRE: i32 = 1;
+pub const AM_IMAGE_LEFT: i32 = 2;
+pub const AM_IMAGE_RIGHT: i32 = 3;
+pub const AM_IMAGE_PANNED: i32 = 4;
+pub const AM_IMAGE_INVERTED: i32 = 5;
 /// am_band_params: per-band hit scoring (am_hit_bands*)
 #[repr(C)]
 #[derive(Clone, Copy, Debug)]
@@ -417,6 +465,24 @@ extern "C" {
         n_hay: usize, sample_format: c_int, peaks: *const AmPeak, cap_per_pair: usize, n_peaks: *const usize,
         cp: *const AmChannelParams, out: *mut AmChannelHit, taps: *mut f32,
     ) -> c_int;
+    /// per-hit stereo image: channel, polarity and delay of a hit (audiomatch.h); AM_FMT_S16_STEREO only
+    pub fn am_hit_stereo(
+        h: *const AmNeedle, haystack: *const std::ffi::c_void, len: usize, sample_format: c_int, peaks: *const AmPeak, n: usize,
+        sp: *const AmStereoParams, out: *mut AmStereoHit,
+    ) -> c_int;
+    pub fn am_hit_stereo_device(
+        h: *const AmNeedle, d_haystack: *const std::ffi::c_void, len: usize, sample_format: c_int, peaks: *const AmPeak, n: usize,
+        sp: *const AmStereoParams, out: *mut AmStereoHit,
+    ) -> c_int;
+    pub fn am_hit_stereo_batch_device(
+        needles: *const *const AmNeedle, n_needles: usize, d_haystacks: *const *const std::ffi::c_void, lens: *const usize,
+        n_hay: usize, sample_format: c_int, peaks: *const AmPeak, cap_per_pair: usize, n_peaks: *const usize,
+        sp: *const AmStereoParams, out: *mut AmStereoHit,
+    ) -> c_int;
+    pub fn am_hit_stereo_summary(rec: *const AmStereoHit, min_ncc: f32, out: *mut AmStereoSummary) -> c_int;
+    /// a stereo mix other than the down-mix: f32((a L + b R) k) of interleaved i16 frames (audiomatch.h)
+    pub fn am_pcm_s16_stereo_mix(device: c_int, interleaved: *const i16, frames: usize, a: f32, b: f32, out: *mut f32) -> c_int;
+    pub fn am_pcm_s16_stereo_mix_device(device: c_int, d_interleaved: *const i16, frames: usize, a: f32, b: f32, d_out: *mut f32) -> c_int;
     pub fn am_channel_solve(r: *const f64, c: *const f64, radius: u32, noise_db: f64, h: *mut f64, ill: *mut c_int) -> c_int;
     pub fn am_hit_residual(
         haystack: *const std::ffi::c_void, len: usize, sample_format: c_int, start: u64, needle: *const f32, s: usize,
@@ -579,7 +645,45 @@ pub fn segment_summary(seg: &[AmHitSegment], needle_len: usize, min_ncc: f32) ->
     Ok(out)
 }
 
+/// Image, balance, inter-channel delay and what the down-mix cost, from one hit's record (am_hit_stereo_summary; no device needed).
+pub fn stereo_summary(rec: &AmStereoHit, min_ncc: f32) -> Result<AmStereoSummary, Box<dyn std::error::Error>> {
+    let mut out = AmStereoSummary::default();
+    let rc = unsafe { am_hit_stereo_summary(rec, min_ncc, &mut out) };
+    if rc != AM_OK {
+        return Err(am_err(rc));
+    }
+    Ok(out)
+}
+
+/// A stereo mix other than the down-mix (am_pcm_s16_stereo_mix): f32((a L + b R) k) of interleaved i16 stereo frames on device 0;
+/// (0.5, 0.5) is the down-mix bit for bit, (0.5, -0.5) the side signal.
+pub fn pcm_s16_stereo_mix(interleaved: &[i16], a: f32, b: f32) -> Result<Vec<f32>, Box<dyn std::error::Error>> {
+    let frames = interleaved.len() / 2;
+    let mut out = vec![0f32; frames];
+    let rc = unsafe { am_pcm_s16_stereo_mix(0, interleaved.as_ptr(), frames, a, b, out.as_mut_ptr()) };
+    if rc != AM_OK {
+        return Err(am_err(rc));
+    }
+    Ok(out)
+}
+
 impl HipConvolve {
+    /// Per-hit stereo image (am_hit_stereo): where each of `peaks` sits between the channels of a haystack of interleaved
+    /// i16 stereo frames -- per channel the best of the lags -radius .. radius, the polarity and the NCC, and the NCC of
+    /// the mid, the side and the best fixed mix.
+    pub fn hit_stereo(&self, interleaved: &[i16], peaks: &[AmPeak], radius: u32) -> Result<Vec<AmStereoHit>, Box<dyn std::error::Error>> {
+        let sp = AmStereoParams { radius, reserved: 0 };
+        let mut out = vec![AmStereoHit::default(); peaks.len()];
+        let rc = unsafe {
+            am_hit_stereo(self.h, interleaved.as_ptr() as *const std::ffi::c_void, interleaved.len() / 2, AM_FMT_S16_STEREO, peaks.as_ptr(),
+                          peaks.len(), &sp, out.as_mut_ptr())
+        };
+        if rc != AM_OK {
+            return Err(am_err(rc));
+        }
+        Ok(out)
+    }
+
     pub fn new(sample_data: Box<[f32]>) -> Result<Self, Box<dyn std::error::Error>> {
         let mut h = std::ptr::null_mut();
         let rc = unsafe { am_needle_create(0, sample_data.as_ptr(), sample_data.len(), &mut h) };

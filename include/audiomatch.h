@@ -536,6 +536,16 @@ int am_find_peaks_top_device(int device, const float* d_scores, size_t n, float 
 int am_pcm_s16_stereo_to_mono(int device, const int16_t* interleaved, size_t frames, float* out);
 int am_pcm_s16_stereo_to_mono_device(int device, const int16_t* d_interleaved, size_t frames,
                                      float* d_out);
+/* A stereo mix other than the down-mix (an extension; the reference knows the down-mix only):
+ *     out[i] = fl32( ((double)a L[i] + (double)b R[i]) k ),   k = (double)(1.0f / 65535.0f)
+ * Both products are exact in f64 (an f32 times an i16 value): one f64 sum, one f64 product, one rounding to f32, so the
+ * result is defined bit for bit.  a = b = 0.5 gives exactly the bits of am_pcm_s16_stereo_to_mono; (1, 0) is left, (0, 1)
+ * right, (0.5, -0.5) side.  Matching the f32 path on the side signal finds an insert that sits polarity-inverted in the
+ * two channels and cancels in the down-mix; its hit positions are frame positions, so am_hit_stereo applies to them
+ * unchanged.  Arguments and refusals as am_pcm_s16_stereo_to_mono*. */
+int am_pcm_s16_stereo_mix(int device, const int16_t* interleaved, size_t frames, float a, float b, float* out);
+int am_pcm_s16_stereo_mix_device(int device, const int16_t* d_interleaved, size_t frames, float a, float b,
+                                 float* d_out);
 
 /* ---- sample-rate conversion ---------------------------------------------- */
 /* The reference refuses a snippet and a main file of different rates (matcher/mod.rs:72-74,
@@ -910,6 +920,110 @@ int am_channel_solve(const double* r, const double* c, uint32_t radius, double n
  * AM_CHAN_MAX_RADIUS, start or s >= 2^62. */
 int am_hit_residual(const void* haystack, size_t len, int sample_format, uint64_t start, const float* needle, size_t s,
                     const float* taps, uint32_t radius, float* model, float* resid);
+
+/* ---- per-hit stereo image: channel, polarity and delay of a hit -------------------- */
+/* Every entry point that takes AM_FMT_S16_STEREO first collapses a frame to (l + r) * 0.5 * (1/65535), as the reference
+ * does (mp3_reader.rs:28-37), and everything behind that sees the down-mix only.  A jingle on one channel comes out at half
+ * gain, an insert that sits polarity-inverted in the two channels cancels, and a hit that is found cannot be placed between
+ * the channels.  This family reads the i16 frames themselves.  AM_FMT_S16_STEREO only.
+ *
+ * For a hit with t = peak.start, everything in f64: k = (double)(2 kappa), kappa the f32 constant 0.5f * (1.0f / 65535.0f)
+ * of the down-mix; l[u] = k L[u], r[u] = k R[u] for the i16 values of frame u, 0 outside [0, len); n[0 .. S) the handle's
+ * needle, E_n the handle's energy, R = sp->radius:
+ *     c_L(lam) = sum_{i<S} l[t + lam + i] n[i],   c_R(lam) likewise,   lam = -R .. R
+ *     E_L = sum_i l[t+i]^2,  E_R = sum_i r[t+i]^2,  E_LR = sum_i l[t+i] r[t+i]          (lag 0)
+ *     E_M = (E_L + 2 E_LR + E_R) / 4,   E_D = (E_L - 2 E_LR + E_R) / 4                   (mid = (l+r)/2, side = (l-r)/2)
+ *   How they are evaluated.  c_ch(lam) = k C, C = sum_i L[t + lam + i] n[i] with exact products (an i16 times an f32
+ *   value), summed in the order of am_hit_channel: the needle in slices of 4096 samples, work item w of 256 its 16
+ *   consecutive samples ascending, a butterfly over each wave of 64 (distances 32 .. 1), the four waves in order, the
+ *   slices in order.  The energies are exact: 64-bit integer sums S_LL, S_RR, S_LR of the i16 products, E = (double)S (k k);
+ *   E_M and E_D from the integers S_LL +- 2 S_LR + S_RR, times (k k), times 0.25.
+ * The record:
+ *   lag_left, lag_right    per channel the lag lam* with the largest |c_ch(lam)|; ties go to the smaller |lam|, then to the
+ *                          negative lag; plus the vertex of the parabola through |c| at lam* - 1, lam*, lam* + 1, clamped to
+ *                          +-0.5: the rule of am_hit_segments applied to |c|, so that an inverted channel gets its true
+ *                          lag.  lag_left - lag_right is the inter-channel delay.
+ *   ncc_left, ncc_right    c_ch(0) / sqrt(E_n E_ch); the sign is the polarity.
+ *   ncc_mid, ncc_side      (c_L(0) + c_R(0)) / 2 / sqrt(E_n E_M) and (c_L(0) - c_R(0)) / 2 / sqrt(E_n E_D).  ncc_mid is
+ *                          the NCC of am_hit_scores up to the down-mix's f32 rounding.
+ *   ncc_best               the largest NCC any fixed mix a l + b r reaches: sqrt(max(q, 0) / E_n), q = (c_L^2 E_R - 2 c_L c_R
+ *                          E_LR + c_R^2 E_L) / det, det = E_L E_R - E_LR^2, the c at lag 0.
+ *   gain_left, gain_right  c_ch(0) / E_n.
+ *   mix_left, mix_right    the mix that reaches ncc_best: (c_L E_R - c_R E_LR) / det and (c_R E_L - c_L E_LR) / det.
+ *   flags                  AM_HIT_LEFT_SILENT, AM_HIT_RIGHT_SILENT, AM_HIT_SIDE_SILENT, and for the mid the existing
+ *                          AM_HIT_BELOW_FLOOR: the energy (E_L, E_R, E_D, E_M) is 0 or below E_n 10^(-score_norm_floor_db /
+ *                          10), the process option am_hit_scores reads; that NCC is then 0.
+ *                          AM_HIT_LEFT_UNREFINED, AM_HIT_RIGHT_UNREFINED: under the conditions of am_hit_segments (R = 0,
+ *                          |lam*| = R, or no maximum) the channel's vertex term is 0.
+ *                          AM_HIT_COLLINEAR: det <= AM_STEREO_MIN_INDEPENDENCE E_L E_R, or a channel is silent.  ncc_best
+ *                          and the mix then come from the channel with the larger energy alone (left wins a tie):
+ *                          |c_ch(0)| / sqrt(E_n E_ch) and c_ch(0) / E_ch, the other mix weight 0; both channels silent:
+ *                          ncc_best = mix = 0.
+ *                          AM_HIT_NONFINITE: a needle sample is not finite; every float is NaN, both lags are 0, no other
+ *                          flag.  AM_HIT_EMPTY_SEGMENT (reused): E_n = 0, a needle of zeros; every float and both lags
+ *                          are 0, no other flag.
+ * A hit's record depends on the needle, the frames in [t - R, t + S + R), R and the floor only: the three forms agree bit
+ * for bit, whatever else the call holds.  The host form stages [t - R, t + S + R) of each hit only, clipped and merged.
+ * The cost is proportional to hits x S x 2 (2R + 1), the radius rounded up to 1, 4 or 16.
+ * Measured on an MI355X (64 hits of a 10 s needle at 44.1 kHz in a resident 1 h haystack, R = 8): 7.0 us per hit, of which
+ * the kernels take 6.5; the two am_hit_segments_device calls (m = 1, R = 8) on de-interleaved f32 copies of L and R that
+ * give the same lags take 13.3 and 12.4 (tools/hit_stereo_bench.py, profiles/r21/).
+ * AM_ERR_INVALID_ARG, naming the hit (and pair) or the field: AM_FMT_F32_MONO ("am_hit_stereo: needs interleaved i16 stereo
+ * frames"), radius > AM_STEREO_MAX_RADIUS, reserved != 0, a null pointer with n > 0, peak.start + S > len, a haystack on
+ * another device.  n = 0 returns AM_OK and launches nothing.
+ * The record type is am_stereo_hit: a typedef am_hit_stereo cannot stand beside the function of that name. */
+enum {
+    AM_HIT_LEFT_SILENT = 1024,
+    AM_HIT_RIGHT_SILENT = 2048,
+    AM_HIT_SIDE_SILENT = 4096,
+    AM_HIT_COLLINEAR = 8192,
+    AM_HIT_LEFT_UNREFINED = 16384,
+    AM_HIT_RIGHT_UNREFINED = 32768
+};
+#define AM_STEREO_MAX_RADIUS 16
+#define AM_STEREO_MIN_INDEPENDENCE 1e-6
+typedef struct am_stereo_params {
+    uint32_t radius;     /* R, 0 .. AM_STEREO_MAX_RADIUS: lags -R .. R */
+    uint32_t reserved;   /* 0 */
+} am_stereo_params;      /* 8 bytes */
+typedef struct am_stereo_hit {
+    double lag_left, lag_right;
+    float ncc_left, ncc_right;
+    float ncc_mid, ncc_side;
+    float ncc_best;
+    float gain_left, gain_right;
+    float mix_left, mix_right;
+    uint32_t flags;      /* AM_HIT_* */
+} am_stereo_hit;         /* 56 bytes, no padding */
+int am_hit_stereo_device(const am_needle* h, const void* d_haystack, size_t len, int sample_format,
+                         const am_peak* peaks, size_t n, const am_stereo_params* sp, am_stereo_hit* out);
+int am_hit_stereo(const am_needle* h, const void* haystack, size_t len, int sample_format,
+                  const am_peak* peaks, size_t n, const am_stereo_params* sp, am_stereo_hit* out);
+/* pair (k, j) = haystack k against needle j, slots as in am_hit_scores_batch_device; untouched slots stay untouched */
+int am_hit_stereo_batch_device(const am_needle* const* needles, size_t n_needles,
+                               const void* const* d_haystacks, const size_t* lens, size_t n_hay, int sample_format,
+                               const am_peak* peaks, size_t cap_per_pair, const size_t* n_peaks,
+                               const am_stereo_params* sp, am_stereo_hit* out);
+/* Pure host function (no device): where one hit sits between the channels, from its record.
+ *   balance_db       20 log10(|gain_left| / |gain_right|); +-inf when one gain is 0, NaN when both are.
+ *   delay            lag_left - lag_right; NaN unless |ncc_left| >= min_ncc and |ncc_right| >= min_ncc.
+ *   downmix_loss_db  20 log10(ncc_best / |ncc_mid|): what matching the down-mix cost; +inf when ncc_mid is 0.
+ *   image, by the first rule that applies:
+ *     1. ncc_best < min_ncc (or not a number)                          AM_IMAGE_ABSENT
+ *     2. of |ncc_left|, |ncc_right| only the left reaches min_ncc      AM_IMAGE_LEFT; only the right: AM_IMAGE_RIGHT
+ *     3. both reach it, with opposite signs                            AM_IMAGE_INVERTED
+ *     4. both reach it, same sign, |balance_db| <= 3                   AM_IMAGE_CENTRE
+ *     5. anything else                                                 AM_IMAGE_PANNED
+ * AM_ERR_INVALID_ARG: a null pointer. */
+enum { AM_IMAGE_ABSENT = 0, AM_IMAGE_CENTRE = 1, AM_IMAGE_LEFT = 2, AM_IMAGE_RIGHT = 3, AM_IMAGE_PANNED = 4, AM_IMAGE_INVERTED = 5 };
+typedef struct am_stereo_summary {
+    double balance_db;
+    double delay;
+    double downmix_loss_db;
+    int32_t image;       /* AM_IMAGE_* */
+    uint32_t reserved;   /* 0 */
+} am_stereo_summary;     /* 32 bytes */
+int am_hit_stereo_summary(const am_stereo_hit* rec, float min_ncc, am_stereo_summary* out);
 
 /* ---- device memory plumbing (for hosts without their own HIP allocator) -- */
 int am_device_malloc(int device, size_t bytes, void** out);

@@ -304,6 +304,33 @@ public:
         check(am_hit_significance_device(h_, d_haystack, len, sample_format, peaks.data(), peaks.size(), &sp, out.data()));
         return out;
     }
+    // per-hit stereo image (am_hit_stereo): where each peak sits between the channels of a haystack of i16 stereo frames
+    // (AM_FMT_S16_STEREO only), one record per peak.  The batch form is am_hit_stereo_batch_device of the C interface.
+    std::vector<am_stereo_hit> hit_stereo(const void* haystack, std::size_t len, int sample_format, const std::vector<am_peak>& peaks,
+                                          const am_stereo_params& sp) const {
+        std::vector<am_stereo_hit> out(peaks.size());
+        check(am_hit_stereo(h_, haystack, len, sample_format, peaks.data(), peaks.size(), &sp, out.data()));
+        return out;
+    }
+    std::vector<am_stereo_hit> hit_stereo_device(const void* d_haystack, std::size_t len, int sample_format,
+                                                 const std::vector<am_peak>& peaks, const am_stereo_params& sp) const {
+        std::vector<am_stereo_hit> out(peaks.size());
+        check(am_hit_stereo_device(h_, d_haystack, len, sample_format, peaks.data(), peaks.size(), &sp, out.data()));
+        return out;
+    }
+    // image, balance, delay and what the down-mix cost, from one record (am_hit_stereo_summary; no device needed)
+    static am_stereo_summary stereo_summary(const am_stereo_hit& rec, float min_ncc) {
+        am_stereo_summary out{};
+        check(am_hit_stereo_summary(&rec, min_ncc, &out));
+        return out;
+    }
+    // a stereo mix other than the down-mix (am_pcm_s16_stereo_mix): f32((a L + b R) k) of `frames` interleaved i16 frames;
+    // the resident form is am_pcm_s16_stereo_mix_device of the C interface
+    static std::vector<float> pcm_s16_stereo_mix(int device, const std::int16_t* interleaved, std::size_t frames, float a, float b) {
+        std::vector<float> out(frames);
+        check(am_pcm_s16_stereo_mix(device, interleaved, frames, a, b, out.data()));
+        return out;
+    }
     // coverage, drift and refined start of one hit from its records (am_hit_segments_summary; no device needed)
     static am_segment_summary segment_summary(const am_hit_segment* seg, std::uint32_t segments, std::size_t needle_len, float min_ncc) {
         am_segment_summary out{};
