@@ -471,18 +471,15 @@ int valid_scores(am_needle* h, const Opts& o0, const NormSpec& nrm, float factor
     return AM_OK;
 }
 
-// am_match_best on one resident haystack (include/audiomatch.h): its Valid scores into best_scores, then best_select.
-// The caller holds the context's lock and has checked the arguments.  Synchronous.
-int match_best_one(am_needle* h, const void* d_hay, size_t len, int sample_format, const am_best_params* bp, am_peak* out,
-                   size_t* n_out) {
+// The score array of one resident haystack (am_internal.h): what am_match_best selects from and am_match_trace reduces.
+// The caller holds the context's lock and has checked the arguments (len >= S).  Synchronous.
+int haystack_scores(am_needle* h, const Opts& o, const void* d_hay, size_t len, int sample_format, int scale, const float** d_scores,
+                    long long* n_scores) {
     Ctx* c = h->ctx;
     const size_t s = h->n;
-    *n_out = 0;
-    if (len < s) return AM_OK;
     int rc;
-    const Opts o = snapshot_opts(h);
     const NormSpec nrm = norm_spec(h, o);
-    const float factor = nrm.on ? norm_factor(nrm) : scale_factor(h, bp->scale, len);
+    const float factor = nrm.on ? norm_factor(nrm) : scale_factor(h, scale, len);
     const float* d_x = static_cast<const float*>(d_hay);
     if (sample_format == AM_FMT_S16_STEREO) {   // the bit-exact down-mix first
         if ((rc = c->best_mono.ensure(len * sizeof(float)))) return rc;
@@ -508,6 +505,23 @@ int match_best_one(am_needle* h, const void* d_hay, size_t len, int sample_forma
             if (i + 1 < t.size()) p = t[i + 1];
         }
     }
+    *d_scores = d_sc;
+    *n_scores = n;
+    return AM_OK;
+}
+
+// am_match_best on one resident haystack (include/audiomatch.h): its Valid scores (haystack_scores), then best_select.
+// The caller holds the context's lock and has checked the arguments.  Synchronous.
+int match_best_one(am_needle* h, const void* d_hay, size_t len, int sample_format, const am_best_params* bp, am_peak* out,
+                   size_t* n_out) {
+    Ctx* c = h->ctx;
+    *n_out = 0;
+    if (len < h->n) return AM_OK;
+    int rc;
+    const Opts o = snapshot_opts(h);
+    const float* d_sc = nullptr;
+    long long n = 0;
+    if ((rc = haystack_scores(h, o, d_hay, len, sample_format, bp->scale, &d_sc, &n))) return rc;
     std::vector<am_peak> res;
     if ((rc = best_select(c, d_sc, n, bp->min_prominence, (long long)std::min<uint64_t>(bp->min_distance, (uint64_t)LLONG_MAX),
                           (size_t)bp->k, o.peak_policy(), res))) return rc;

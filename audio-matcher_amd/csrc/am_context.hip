@@ -48,6 +48,7 @@ static const char* opt_needle_group(long long& v) { return v < 1 || v > kMaxNeed
 static const char* opt_pairs(long long& v) { return v < 1 || v > 64 ? "pairs_per_group out of range" : nullptr; }
 static const char* opt_score_norm(long long& v) { return v < 0 || v > 1 ? "score_norm out of range (0 = off, 1 = NCC)" : nullptr; }
 static const char* opt_floor_db(long long& v) { return v < 0 || v > 200 ? "score_norm_floor_db out of range (0..200)" : nullptr; }
+static const char* opt_trace_form(long long& v) { return v < 0 || v > 2 ? "trace_form out of range (0 = by bin length, 1 = wave form, 2 = sliced form)" : nullptr; }
 static const char* opt_distance(long long& v) {
     return v < 0 || v > 3 ? "distance_rule out of range (bit 0: inclusive, bit 1: between plateau starts)" : nullptr;
 }
@@ -77,6 +78,7 @@ static Option g_options[] = {
     // test hooks (defaults = production behaviour)
     {"debug_no_realloc", {0}, opt_bool, &Opts::debug_no_realloc},     // 1 = a scratch buffer that would be (re)allocated while a call is queueing fails the call
     {"debug_redo_arm_at", {-2}, opt_arm_at, &Opts::debug_redo_arm_at},   // >= 0: the device-side redo of a batch arms at that haystack; -1: never; -2: when a failure is seen
+    {"trace_form", {0}, opt_trace_form, &Opts::trace_form},           // score traces (am_trace.hip): 0 = the form the bin length decides, 1 = one wave per bin, 2 = slices and a finish
     // The semantics nothing available offline pins (the crates find_peaks 0.1 and common are absent, no
     // reference test covers these rules).  Defaults = the documented choices of oracle/oracle.c; every alternative exists
     // in the kernels, on the host AND in the checker, so that one run by someone who has the crates settles each with an
@@ -111,7 +113,7 @@ int realloc_refused(const char* what, size_t bytes, size_t cap) {
     return fail(AM_ERR_HIP, buf);
 }
 
-static const char* kKernelNames[] = {"k1_cols_fwd", "k2_rows", "k3_cols_inv", "tile_stats", "peaks", "other"};
+static const char* kKernelNames[] = {"k1_cols_fwd", "k2_rows", "k3_cols_inv", "tile_stats", "peaks", "other", "trace"};
 static std::mutex g_ctx_mu;
 static std::map<int, Ctx*> g_ctx;
 
@@ -514,7 +516,7 @@ int am_shutdown(void) {
         for (DevBuf* b : {&c->hit_tab, &c->hit_parts, &c->hit_flags, &c->hit_out, &c->hit_stage}) b->release();
         c->hit_io.release();
         for (DevBuf* b : {&c->sig_span, &c->sig_scores, &c->sig_psum, &c->sig_pmax, &c->sig_mean, &c->sig_hmax}) b->release();
-        for (DevBuf* b : {&c->best_stats, &c->best_lmax, &c->best_ctl, &c->best_trans, &c->best_list, &c->best_scores, &c->best_mono}) b->release();
+        for (DevBuf* b : {&c->best_stats, &c->best_lmax, &c->best_ctl, &c->best_trans, &c->best_list, &c->best_scores, &c->best_mono, &c->trace_out, &c->trace_parts}) b->release();
         for (auto& kv : c->rs_taps) kv.second.release();
         c->rs_taps.clear();
         c->lag_parts.release(); c->lag_r.release();

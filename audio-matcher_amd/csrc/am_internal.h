@@ -45,6 +45,7 @@ struct Opts {
     long long peak_filter_order, distance_rule, tail_window, surrounding_from, k3_group, pick_group, tail_block, host_pick_wait;
     long long profile_mask, profile_every, pick_priority;
     long long score_norm, score_norm_floor_db;
+    long long trace_form;
     PeakPolicy peak_policy() const { return PeakPolicy{(int)peak_filter_order, (int)(distance_rule & 1), (int)((distance_rule >> 1) & 1)}; }
 };
 static const float kHalfGain = 1024.0f;      // keeps the stored values of a normalised score near 1
@@ -134,7 +135,7 @@ struct Plan {
 struct ScoreSide { DevBuf scores, stats, stats32, wflags, peaks, work; };
 
 struct ProfRec { int name; hipEvent_t e0, e1; };
-enum { KN_K1 = 0, KN_K2, KN_K3, KN_STATS, KN_PEAKS, KN_OTHER, KN_COUNT };
+enum { KN_K1 = 0, KN_K2, KN_K3, KN_STATS, KN_PEAKS, KN_OTHER, KN_TRACE, KN_COUNT };
 
 struct Ctx {
     int device = -1;
@@ -184,6 +185,7 @@ struct Ctx {
     // the k best matches (am_best.hip): tile summaries, per-tile top keys, histograms and counters, the finite/non-finite
     // transitions, the candidate list; the score array and the down-mixed haystack of am_match_best
     DevBuf best_stats, best_lmax, best_ctl, best_trans, best_list, best_scores, best_mono;
+    DevBuf trace_out, trace_parts;   // score traces (am_trace.hip): a call's records and, in the sliced form, the slices' partials
     // the chunk list currently resident in `segs` (re-uploaded only when it changes)
     std::vector<Segment> segs_resident;
     // profiling
@@ -635,8 +637,18 @@ int valid_scores(am_needle* h, const Opts& o0, const NormSpec& nrm, float factor
 int best_transitions(Ctx* c, const float* d_x, long long n, std::vector<long long>& trans);
 int best_select(Ctx* c, const float* d_g, long long n, float min_prom, long long min_dist, size_t k, const PeakPolicy& pol,
                 std::vector<am_peak>& res);
+// The score array am_match_best selects from and am_match_trace reduces: the AM_MODE_VALID scores of one resident haystack
+// (len >= S) in the context's best_scores, after the bit-exact down-mix of an i16 stereo haystack; a window that holds
+// a non-finite sample scores NaN, every finite stretch of at least S samples is correlated on its own.  *n = len - S + 1.
+int haystack_scores(am_needle* h, const Opts& o, const void* d_hay, size_t len, int sample_format, int scale, const float** d_scores,
+                    long long* n);
 int match_best_one(am_needle* h, const void* d_hay, size_t len, int sample_format, const am_best_params* bp, am_peak* out,
                    size_t* n_out);
+// ---- am_trace.hip ----
+int trace_check_bin(uint64_t bin);
+int trace_reduce(Ctx* c, const float* d_g, long long n, uint64_t bin, am_trace_bin* out, size_t cap, size_t* n_out);
+int match_trace_one(am_needle* h, const void* d_hay, size_t len, int sample_format, const am_trace_params* tp, am_trace_bin* out,
+                    size_t cap, size_t* n_out);
 int merge_peaks(std::vector<am_peak>& all, const am_match_params* p, bool from_filtered, am_peak* out, size_t cap, size_t* n_out);
 // what merge_settle carries from one piece of a sorted list to the next: the element before the next one, the last one kept
 struct MergeCursor { am_peak prev{}, kept{}; bool has_prev = false, has_kept = false; };

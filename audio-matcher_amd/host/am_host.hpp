@@ -99,6 +99,8 @@ struct Arguments {
     std::uint32_t learn_trim = 0;             // ... P of trimmed=P, in 1/1000 (0..500)
     std::optional<std::uint64_t> learn_margin_ms;   // ... --learn-margin D: read D in front of and behind the snippet as well (default 0)
     std::optional<std::uint64_t> best;        // extension: --best N, the N best hits per main file, no prominence threshold (am_match_best)
+    std::string trace_prefix;                 // extension: --score-trace PREFIX[:BIN], the score curve of each main file (am_match_trace) as PREFIX<file index>[_<snippet index>].csv; empty = off
+    std::uint64_t trace_bin_ms = 1000;        // ... one line per BIN of scores (a duration, default 1 s)
     bool live = false;                        // extension: --live, raw PCM from stdin through a monitor (am_monitor_*)
     std::uint32_t rate = 0;                   // --live: --rate R (samples per second of the stream)
     std::string encoding = "s16le";           // --live: --encoding s16le | f32le
@@ -203,6 +205,13 @@ inline const char* usage_text() {
            "                         --snippet only; not with --live, --best, --whiten or --preemphasis\n"
            "  --learn-margin D       with --learn-needle: also read D (a duration, default 0) in front of and behind the\n"
            "                         snippet; the spread shows where the jingle really begins and ends\n"
+           "  --score-trace PREFIX[:BIN]  what the scores look like between the hits (am_match_trace): per main file (and\n"
+           "                         per snippet, when there are several) PREFIX<file index>[_<snippet index>].csv with one\n"
+           "                         line per BIN (a duration, default 1s) of scores: start_s, max, max_at_s, min, min_at_s,\n"
+           "                         mean, rms, count ('nan' where a bin holds no score); and under the file's offset lines\n"
+           "                         one line 'Trace: max V at hh:mm:ss.mmm, bin maxima median V mad V, peak z V'.  The\n"
+           "                         scores are those that were matched: --normalize, --resample, --whiten / --preemphasis\n"
+           "                         and --mix apply.  Not with --live\n"
            "  --live                 read raw PCM from stdin instead of files (no FILE arguments): a live feed, matched\n"
            "                         as it arrives; each hit's offset line is printed (and flushed) as soon as it is\n"
            "                         final -- a hit is final once the next hit is found, or once --distance of audio\n"
@@ -421,6 +430,20 @@ inline Arguments parse_arguments(int argc, const char* const* argv) {
                 throw ArgError("invalid value '" + v + "' for --best (a whole number of hits, at least 1)");
             a.best = (std::uint64_t)k;
         }
+        else if (s == "--score-trace") {
+            // PREFIX[:BIN]: what follows the last ':' is the bin when it reads as a duration (a prefix may hold ':' itself)
+            const std::string v = need(i);
+            a.trace_prefix = v;
+            const auto colon = v.rfind(':');
+            if (colon != std::string::npos) {
+                if (const auto d = parse_duration_ms(v.substr(colon + 1))) {
+                    a.trace_prefix = v.substr(0, colon);
+                    a.trace_bin_ms = *d;
+                }
+            }
+            if (a.trace_prefix.empty() || a.trace_bin_ms == 0)
+                throw ArgError("invalid value '" + v + "' for --score-trace (PREFIX[:BIN], a file name prefix and a duration longer than 0)");
+        }
         else if (s == "--live") a.live = true;
         else if (s == "--rate") {
             const std::string v = need(i);
@@ -453,6 +476,7 @@ inline Arguments parse_arguments(int argc, const char* const* argv) {
         throw ArgError("--stereo does not apply with --resample, --whiten or --preemphasis (the snippet would no longer be on the frames' footing)");
     if (a.live && a.mix_set) throw ArgError("--live: --mix does not apply");
     if (a.live && a.stereo_radius) throw ArgError("--live: --stereo does not apply");
+    if (a.live && !a.trace_prefix.empty()) throw ArgError("--live: --score-trace does not apply");
     if (!a.learn_needle.empty()) {
         if (a.live) throw ArgError("--live: --learn-needle does not apply");
         if (a.best) throw ArgError("--learn-needle and --best are mutually exclusive");
@@ -661,6 +685,51 @@ inline std::vector<am_peak> best_hits(const Arguments& a, const am_needle* h, co
     out.resize(n);
     std::stable_sort(out.begin(), out.end(), [](const am_peak& x, const am_peak& y) { return x.start < y.start; });
     return out;
+}
+
+// --score-trace: the records of one main file against one snippet (am_match_trace over the samples that were matched;
+// scale LIB, BIN rounded to samples of the file's rate), *bin = the scores per record
+inline std::vector<am_trace_bin> trace_of(const Arguments& a, const am_needle* h, const std::vector<float>& samples, std::uint32_t sr,
+                                          std::uint64_t* bin) {
+    am_trace_params tp{};
+    tp.bin = std::max<std::uint64_t>(1, round_samples_ms(a.trace_bin_ms, sr));
+    tp.scale = AM_SCALE_LIB;
+    *bin = tp.bin;
+    size_t s = 0, nb = 0, n = 0;
+    if (am_needle_len(h, &s) != AM_OK || am_trace_len(samples.size() >= s ? samples.size() - s + 1 : 0, tp.bin, &nb) != AM_OK)
+        throw std::runtime_error(std::string("--score-trace: ") + am_last_error_string());
+    std::vector<am_trace_bin> out(nb);
+    if (am_match_trace(h, samples.data(), samples.size(), AM_FMT_F32_MONO, &tp, out.data(), out.size(), &n) != AM_OK)
+        throw std::runtime_error(std::string("am_match_trace: ") + am_last_error_string());
+    out.resize(std::min(n, out.size()));
+    return out;
+}
+
+// ... as the text of its CSV file: values with %.9g, so that an f32 reads back to its bits; a bin without a score shows nan
+inline std::string trace_csv(const std::vector<am_trace_bin>& bins, std::uint64_t bin, std::uint32_t sr) {
+    std::string s = "start_s,max,max_at_s,min,min_at_s,mean,rms,count\n";
+    char buf[256];
+    for (std::size_t b = 0; b < bins.size(); ++b) {
+        const am_trace_bin& r = bins[b];
+        const double t0 = (double)(b * bin), nan = std::nan(""), c = (double)r.count;
+        std::snprintf(buf, sizeof buf, "%.9g,%.9g,%.9g,%.9g,%.9g,%.9g,%.9g,%u\n", t0 / sr, r.count ? (double)r.max : nan,
+                      r.count ? (t0 + r.argmax) / sr : nan, r.count ? (double)r.min : nan, r.count ? (t0 + r.argmin) / sr : nan,
+                      r.count ? r.sum / c : nan, r.count ? std::sqrt(r.sumsq / c) : nan, r.count);
+        s += buf;
+    }
+    return s;
+}
+
+// ... and its line under the offset lines (am_trace_summary)
+inline std::string trace_line(const std::vector<am_trace_bin>& bins, std::uint64_t bin, std::uint32_t sr) {
+    am_trace_stats st{};
+    if (am_trace_summary(bins.data(), bins.size(), bin, &st) != AM_OK)
+        throw std::runtime_error(std::string("am_trace_summary: ") + am_last_error_string());
+    const std::uint64_t ms = st.count ? (std::uint64_t)((double)st.argmax * 1000.0 / (double)sr) : 0;
+    char buf[256];
+    std::snprintf(buf, sizeof buf, "Trace: max %.9g at %02" PRIu64 ":%02" PRIu64 ":%02" PRIu64 ".%03" PRIu64 ", bin maxima median %.9g mad %.9g, peak z %.9g",
+                  st.max, ms / 3600000, (ms / 60000) % 60, (ms / 1000) % 60, ms % 1000, st.median_max, st.mad_max, st.peak_z);
+    return buf;
 }
 
 inline am_match_params make_params(const Arguments& a, std::uint32_t sr, double snippet_duration_s) {

@@ -566,6 +566,21 @@ static void report_hits(const Arguments& args, const am_needle* algo, const std:
             if (i < l->size()) std::printf("%s%s\n", prefix.c_str(), (*l)[i].c_str());
 }
 
+// extension: --score-trace.  The score curve of one snippet in one main file: its CSV file (`snippet_index`: set when the
+// run has several snippets) and, under the offset lines, its summary line.  Returns 0, or 4 where the file cannot be
+// written.
+static int write_trace(const Arguments& args, const am_needle* algo, const std::vector<float>& m_samples, std::uint32_t m_sr,
+                       size_t file_index, std::optional<size_t> snippet_index, const std::string& prefix) {
+    std::uint64_t bin = 0;
+    const std::vector<am_trace_bin> bins = trace_of(args, algo, m_samples, m_sr, &bin);
+    if (args.verbosity >= 1) std::printf("%s%s\n", prefix.c_str(), trace_line(bins, bin, m_sr).c_str());
+    const std::string path = args.trace_prefix + std::to_string(file_index) + (snippet_index ? "_" + std::to_string(*snippet_index) : std::string()) + ".csv";
+    std::ofstream f(path, std::ios::binary | std::ios::trunc);
+    if (!f) { std::fprintf(stderr, "couldn't write file '%s'\n", path.c_str()); return 4; }
+    f << trace_csv(bins, bin, m_sr);
+    return 0;
+}
+
 // The file mode: the per-file loop of matcher::run (mod.rs:42-100) for one or several --snippet files.  One snippet is
 // matched by am_match, as the reference does.  Several (an extension) are matched by ONE am_match_multi_varlen call for a
 // main file; with --normalize, which that call refuses, snippet by snippet with am_match; every line of a snippet's
@@ -617,6 +632,11 @@ static int run_files(const Arguments& args) {
         }
         for (size_t j = 0; j < k; ++j)
             report_hits(args, handles[j], m_samples, m_sr, hits[j], k > 1 ? snips[j].name + ": " : std::string(), learner, snips[j], file_index, m);
+        if (!args.trace_prefix.empty())
+            for (size_t j = 0; j < k; ++j)
+                if (const int rc = write_trace(args, handles[j], m_samples, m_sr, file_index, k > 1 ? std::optional<size_t>(j) : std::nullopt,
+                                               k > 1 ? snips[j].name + ": " : std::string()))
+                    rc_all = rc;
         if (out_path) {                                                   // mod.rs:92-99
             std::vector<am_peak> all;
             for (const std::vector<am_peak>& h : hits) all.insert(all.end(), h.begin(), h.end());

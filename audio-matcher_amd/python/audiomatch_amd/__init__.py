@@ -228,6 +228,22 @@ class AmBestParams(C.Structure):     # am_best_params (include/audiomatch.h, the
     _fields_ = [("k", C.c_uint64), ("min_distance", C.c_uint64), ("min_prominence", C.c_float), ("scale", C.c_int)]
 
 
+class AmTraceParams(C.Structure):    # am_trace_params (include/audiomatch.h, score traces)
+    _fields_ = [("bin", C.c_uint64), ("scale", C.c_int), ("reserved", C.c_uint32)]
+
+
+class AmTraceStats(C.Structure):     # am_trace_stats: what am_trace_summary returns
+    _fields_ = [("count", C.c_uint64), ("argmax", C.c_uint64), ("argmin", C.c_uint64), ("max", C.c_double), ("min", C.c_double),
+                ("mean", C.c_double), ("std", C.c_double), ("median_max", C.c_double), ("mad_max", C.c_double),
+                ("peak_z", C.c_double)]
+
+
+# am_trace_bin as a numpy structured dtype (40 bytes, no padding): what the trace calls return arrays of
+TRACE_BIN_DTYPE = np.dtype([("max", "<f4"), ("min", "<f4"), ("argmax", "<u4"), ("argmin", "<u4"), ("count", "<u4"),
+                            ("reserved", "<u4"), ("sum", "<f8"), ("sumsq", "<f8")])
+AM_TRACE_WAVE_BIN_MAX, AM_TRACE_SLICE, AM_TRACE_MAX_BIN = 2048, 8192, 1 << 30
+
+
 class AmMonitorInfo(C.Structure):  # am_monitor_info (include/audiomatch.h, live monitoring)
     _fields_ = [("received", C.c_uint64), ("horizon", C.c_uint64), ("resident_bytes", C.c_uint64), ("pending", C.c_uint64)]
 
@@ -452,6 +468,17 @@ _SIGNATURES = {
                                              C.POINTER(AmBestParams), C.POINTER(AmPeak), C.POINTER(C.c_size_t)]),
     "am_find_peaks_top": (C.c_int, [C.c_int, C.c_void_p, C.c_size_t, C.c_float, C.c_uint64, C.c_size_t,
                                     C.POINTER(AmPeak), C.POINTER(C.c_size_t)]),
+    "am_trace_len": (C.c_int, [C.c_size_t, C.c_uint64, C.POINTER(C.c_size_t)]),
+    "am_trace_scores": (C.c_int, [C.c_int, C.c_void_p, C.c_size_t, C.c_uint64, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "am_trace_scores_device": (C.c_int, [C.c_int, C.c_void_p, C.c_size_t, C.c_uint64, C.c_void_p, C.c_size_t,
+                                         C.POINTER(C.c_size_t)]),
+    "am_match_trace": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.POINTER(AmTraceParams), C.c_void_p, C.c_size_t,
+                                 C.POINTER(C.c_size_t)]),
+    "am_match_trace_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.POINTER(AmTraceParams), C.c_void_p,
+                                        C.c_size_t, C.POINTER(C.c_size_t)]),
+    "am_match_trace_batch_device": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.c_size_t, C.c_int,
+                                              C.POINTER(AmTraceParams), C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "am_trace_summary": (C.c_int, [C.c_void_p, C.c_size_t, C.c_uint64, C.POINTER(AmTraceStats)]),
     "am_find_peaks_top_device": (C.c_int, [C.c_int, C.c_void_p, C.c_size_t, C.c_float, C.c_uint64, C.c_size_t,
                                            C.POINTER(AmPeak), C.POINTER(C.c_size_t)]),
     "am_get_option": (C.c_int, [C.c_char_p, C.POINTER(C.c_longlong)]),
@@ -844,6 +871,50 @@ def find_peaks_top_device(device: int, ptr: int, n: int, k: int, min_prominence:
     _check(lib().am_find_peaks_top_device(device, ptr, int(n), float(min_prominence), int(min_distance), int(k),
                                           buf, C.byref(got)))
     return _peaks(buf, got.value)
+
+
+def trace_len(n_scores: int, bin: int) -> int:
+    """am_trace_len: ceil(n_scores / bin), the records a trace of n_scores scores has (pure host)."""
+    n = C.c_size_t(0)
+    _check(lib().am_trace_len(int(n_scores), int(bin), C.byref(n)))
+    return n.value
+
+
+def trace_params(bin: int, scale=Scale.LIB) -> AmTraceParams:
+    """am_trace_params (scale: Scale.NONE or Scale.LIB, or a bool as in correlate_with_sample)."""
+    sc = int(Scale.LIB if scale is True else Scale.NONE if scale is False else scale)
+    return AmTraceParams(bin=int(bin), scale=sc, reserved=0)
+
+
+def _trace_call(fn, n_scores: int, bin: int, cap):
+    """Runs fn(out_ptr, cap, byref(n)) on a record array of `cap` slots (default: all bins); the records written."""
+    nb = trace_len(n_scores, bin)
+    cap = nb if cap is None else int(cap)
+    out = np.zeros(max(1, cap), dtype=TRACE_BIN_DTYPE)
+    n = C.c_size_t(0)
+    _check(fn(out.ctypes.data, cap, C.byref(n)))
+    return out[:min(n.value, cap)]
+
+
+def trace_scores(y_data, bin: int, device: int = 0, cap=None):
+    """am_trace_scores: per bin of `bin` scores of the host array y_data one record (TRACE_BIN_DTYPE): max, min, their
+    offsets in the bin, the count of scores that are not NaN, their f64 sum and sum of squares."""
+    a = np.ascontiguousarray(y_data, dtype=np.float32)
+    return _trace_call(lambda o, c, n: lib().am_trace_scores(device, a.ctypes.data, a.size, int(bin), o, c, n), a.size, bin, cap)
+
+
+def trace_scores_device(device: int, ptr: int, n: int, bin: int, cap=None):
+    """am_trace_scores_device: the same on n f32 scores resident on `device` (any 4-byte alignment)."""
+    return _trace_call(lambda o, c, m: lib().am_trace_scores_device(device, ptr, int(n), int(bin), o, c, m), n, bin, cap)
+
+
+def trace_summary(bins, bin: int) -> AmTraceStats:
+    """am_trace_summary: count, global max / min with their score offsets, mean, std, the median and MAD of the bin
+    maxima and peak_z of a trace's records (pure host)."""
+    a = np.ascontiguousarray(bins, dtype=TRACE_BIN_DTYPE)
+    st = AmTraceStats()
+    _check(lib().am_trace_summary(a.ctypes.data if a.size else None, a.size, int(bin), C.byref(st)))
+    return st
 
 
 def best_params(k: int, min_distance: int = 0, min_prominence: float = 0.0, scale=Scale.LIB) -> AmBestParams:
@@ -1253,6 +1324,32 @@ class HipConvolve:
         counts = (C.c_size_t * max(1, nh))()
         _check(lib().am_match_best_batch_device(self._h, arr_p, arr_l, nh, int(fmt), C.byref(params), buf, counts))
         return _split_batch(buf, counts, nh, k)
+
+    # -- score traces --
+    def match_trace(self, haystack, bin: int, scale=Scale.LIB, cap=None):
+        """am_match_trace: one TRACE_BIN_DTYPE record per `bin` Valid scores of the haystack (the array match_best
+        selects from).  haystack: an f32 array, or an i16 (frames, 2) array of interleaved stereo."""
+        a, fmt, length = _samples(haystack)
+        tp = trace_params(bin, scale)
+        return _trace_call(lambda o, c, n: lib().am_match_trace(self._h, a.ctypes.data, length, int(fmt), C.byref(tp), o, c, n),
+                           max(0, length - self.sample_len + 1), bin, cap)
+
+    def match_trace_device(self, ptr: int, length: int, params: AmTraceParams, fmt: int = Fmt.F32_MONO, cap=None):
+        """am_match_trace_device on a haystack resident on this needle's device."""
+        return _trace_call(lambda o, c, n: lib().am_match_trace_device(self._h, ptr, length, int(fmt), C.byref(params), o, c, n),
+                           max(0, length - self.sample_len + 1), params.bin, cap)
+
+    def match_trace_batch_device(self, ptrs, lengths, params: AmTraceParams, fmt: int = Fmt.F32_MONO, cap_per_hay=None):
+        """am_match_trace_batch_device: one record array per resident haystack."""
+        nh = len(ptrs)
+        nbs = [trace_len(max(0, int(l) - self.sample_len + 1), params.bin) for l in lengths]
+        cap = max(nbs, default=0) if cap_per_hay is None else int(cap_per_hay)
+        arr_p = (C.c_void_p * max(1, nh))(*ptrs)
+        arr_l = (C.c_size_t * max(1, nh))(*lengths)
+        out = np.zeros(max(1, cap * nh), dtype=TRACE_BIN_DTYPE)
+        counts = (C.c_size_t * max(1, nh))()
+        _check(lib().am_match_trace_batch_device(self._h, arr_p, arr_l, nh, int(fmt), C.byref(params), out.ctypes.data, cap, counts))
+        return [out[i * cap:i * cap + min(counts[i], cap)].copy() for i in range(nh)]
 
     # -- per-hit scoring --
     def hit_scores(self, haystack, peaks):

@@ -264,6 +264,45 @@ pub struct AmBestParams {
     pub min_prominence: f32,
     pub scale: c_int,
 }
+/// am_trace_bin: one bin of a score trace (am_trace_*, am_match_trace*), 40 bytes
+#[repr(C)]
+#[derive(Clone, Copy, Default, Debug)]
+pub struct AmTraceBin {
+    pub max: f32,
+    pub min: f32,
+    pub argmax: u32,
+    pub argmin: u32,
+    pub count: u32,
+    pub reserved: u32,
+    pub sum: f64,
+    pub sumsq: f64,
+}
+/// am_trace_params: scores per bin (1 ..= 2^30) and the scale (AM_SCALE_NONE or AM_SCALE_LIB); reserved = 0
+#[repr(C)]
+#[derive(Clone, Copy, Default, Debug)]
+pub struct AmTraceParams {
+    pub bin: u64,
+    pub scale: c_int,
+    pub reserved: u32,
+}
+/// am_trace_stats: what am_trace_summary returns
+#[repr(C)]
+#[derive(Clone, Copy, Default, Debug)]
+pub struct AmTraceStats {
+    pub count: u64,
+    pub argmax: u64,
+    pub argmin: u64,
+    pub max: f64,
+    pub min: f64,
+    pub mean: f64,
+    pub std: f64,
+    pub median_max: f64,
+    pub mad_max: f64,
+    pub peak_z: f64,
+}
+pub const AM_TRACE_WAVE_BIN_MAX: u64 = 2048;
+pub const AM_TRACE_SLICE: u64 = 8192;
+pub const AM_TRACE_MAX_BIN: u64 = 1 << 30;
 
 pub const AM_HIT_UNREFINED: u32 = 1;
 pub const AM_HIT_BELOW_FLOOR: u32 = 2;
@@ -539,6 +578,27 @@ extern "C" {
         device: c_int, d_scores: *const f32, n: usize, min_prominence: f32, min_distance: u64, k: usize, out: *mut AmPeak,
         n_out: *mut usize,
     ) -> c_int;
+    /// score traces: per bin of `bin` scores the max, min, their offsets, the count and the f64 sums (audiomatch.h)
+    pub fn am_trace_len(n_scores: usize, bin: u64, n_bins: *mut usize) -> c_int;
+    pub fn am_trace_scores(
+        device: c_int, scores: *const f32, n: usize, bin: u64, out: *mut AmTraceBin, cap: usize, n_out: *mut usize,
+    ) -> c_int;
+    pub fn am_trace_scores_device(
+        device: c_int, d_scores: *const f32, n: usize, bin: u64, out: *mut AmTraceBin, cap: usize, n_out: *mut usize,
+    ) -> c_int;
+    pub fn am_match_trace(
+        h: *const AmNeedle, haystack: *const std::ffi::c_void, len: usize, sample_format: c_int, tp: *const AmTraceParams,
+        out: *mut AmTraceBin, cap: usize, n_out: *mut usize,
+    ) -> c_int;
+    pub fn am_match_trace_device(
+        h: *const AmNeedle, d_haystack: *const std::ffi::c_void, len: usize, sample_format: c_int, tp: *const AmTraceParams,
+        out: *mut AmTraceBin, cap: usize, n_out: *mut usize,
+    ) -> c_int;
+    pub fn am_match_trace_batch_device(
+        h: *const AmNeedle, d_haystacks: *const *const std::ffi::c_void, lens: *const usize, n_hay: usize, sample_format: c_int,
+        tp: *const AmTraceParams, out: *mut AmTraceBin, cap_per_hay: usize, n_out: *mut usize,
+    ) -> c_int;
+    pub fn am_trace_summary(bins: *const AmTraceBin, n_bins: usize, bin: u64, out: *mut AmTraceStats) -> c_int;
     /// calc_chunks on the lazy sample iterator (audio_matcher.rs:88-104, mp3_reader.rs:13-41)
     pub fn am_match_stream_begin(
         h: *const AmNeedle, sample_format: c_int, expected_len: usize, p: *const AmMatchParams, out: *mut *mut AmStream,

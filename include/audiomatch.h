@@ -530,6 +530,88 @@ int am_find_peaks_top(int device, const float* scores, size_t n, float min_promi
 int am_find_peaks_top_device(int device, const float* d_scores, size_t n, float min_prominence,
                              uint64_t min_distance, size_t k, am_peak* out, size_t* n_out);
 
+/* ---- score traces ------------------------------------------------------------------------------------------------
+ * "What do the scores look like where there is no hit?" ("What the scores look like between the
+ * hits"): per bin of D consecutive scores the largest and the smallest score with their places, how many scores are
+ * not NaN, and their sum and sum of squares -- 40 bytes per bin instead of 4 bytes per score, the score array itself
+ * never leaves the device.
+ *
+ * Scores.  am_match_trace(h, haystack, len, fmt, tp) reduces r[0, n), n = len - S + 1: exactly the array
+ * am_match_best selects from.  On a finite f32 haystack these are the scores am_correlate_device(h, haystack, len,
+ * AM_MODE_VALID, tp->scale) writes under the options in force, "score_norm" (NCC) and the half-precision redo
+ * included.  AM_FMT_S16_STEREO: the bit-exact down-mix, then as for f32.  A window that holds a non-finite sample has
+ * score NaN; every finite stretch of at least S samples is correlated on its own.  len < S: 0 bins, AM_OK.  tp->scale
+ * must be AM_SCALE_NONE or AM_SCALE_LIB (AM_SCALE_MY depends on a chunk: AM_ERR_INVALID_ARG).  Device memory: 4 bytes
+ * per score, as for am_match_best.
+ *
+ * Bins.  Bin b holds the scores [b D, min(n, (b + 1) D)), D = tp->bin, 1 <= D <= AM_TRACE_MAX_BIN; there are
+ * nb = ceil(n / D) bins, one am_trace_bin each.  NaN scores are skipped; +-inf are scores like any other; -0.0 and
+ * +0.0 compare equal, so the first one wins and its bits are returned.
+ *
+ * The order of the f64 additions depends on D and on a score's offset in its bin only -- not on the array's address
+ * or alignment, the other bins, the batch or the entry point.  A span is the whole bin when D <=
+ * AM_TRACE_WAVE_BIN_MAX, otherwise the bin's scores [s AM_TRACE_SLICE, (s + 1) AM_TRACE_SLICE) for s = 0, 1, ...
+ * Within a span the score at offset j of the span belongs to class j mod 256; each class adds its scores (as f64; a
+ * skipped score as +0.0) in ascending j, starting from +0.0; with c[k] the sum of class k,
+ *     t[l] = (c[4l] + c[4l + 1]) + (c[4l + 2] + c[4l + 3]),  l = 0 .. 63,
+ * and for m = 32, 16, 8, 4, 2, 1 in turn every t[l] becomes t[l] + t[l ^ m]; the span's sum is t[0].  A bin of several
+ * spans adds their sums in ascending s, starting from +0.0.  sumsq likewise over (double)r (double)r, which is
+ * exact, so only the additions round.  (The debug option "trace_form", 1 or 2, forces the first or the second rule
+ * for every D: every field but sum / sumsq keeps its bits.)
+ *
+ * All entry points fill what fits and return AM_ERR_CAPACITY with *n_out = nb when cap < nb, like am_match; `out` is
+ * host memory.  am_trace_scores / am_trace_scores_device are the reduction on any score array (host memory / memory
+ * of `device` at any 4-byte alignment), as am_find_peaks / am_find_peaks_top_device are for the pick.
+ * am_match_trace_batch_device: n_hay resident haystacks, cap_per_hay slots and one count per haystack; each
+ * haystack's records are bit-identical to its single call.  AM_ERR_INVALID_ARG: a null pointer with work to do,
+ * bin == 0 or bin > AM_TRACE_MAX_BIN, reserved != 0, an unknown format, AM_SCALE_MY, a haystack that is not on the
+ * needle's device.
+ *
+ * am_trace_summary (pure host, f64) over the records of one array: the count, the global max and min with their
+ * absolute score offsets (ties to the first), mean and population standard deviation from the sums (var =
+ * sumsq / count - mean^2, clamped at 0), the median and the MAD of the bin maxima over the bins with count > 0, and
+ * peak_z = (max - median) / (1.4826 MAD) (+inf when MAD = 0 and max > median, otherwise 0 when MAD = 0).  No bins or
+ * no counted score: count 0, offsets 0, every other field NaN, AM_OK.  Infinite scores follow IEEE arithmetic (a mean or
+ * std of inf - inf is NaN) with two rules of their own: a bin maximum equal to the median deviates from it by 0, also
+ * when both are infinite, and when +inf and -inf are the two middle maxima there is no median: median_max, mad_max and
+ * peak_z are NaN. */
+#define AM_TRACE_WAVE_BIN_MAX 2048            /* bins up to this many scores: one wavefront per bin */
+#define AM_TRACE_SLICE 8192                   /* longer bins: slices of this many scores, from the bin's start */
+#define AM_TRACE_MAX_BIN (1ull << 30)
+typedef struct am_trace_bin {
+    float    max, min;        /* bits of the score at argmax / argmin; NaN when count == 0 */
+    uint32_t argmax, argmin;  /* offset in the bin of the FIRST score equal (==) to max / min; 0 when count == 0 */
+    uint32_t count;           /* scores of the bin that are not NaN */
+    uint32_t reserved;        /* 0 */
+    double   sum, sumsq;      /* over the counted scores, each converted to f64 first; +0.0 when count == 0 */
+} am_trace_bin;               /* 40 bytes, no padding */
+typedef struct am_trace_params {
+    uint64_t bin;             /* D: scores per bin, 1 .. AM_TRACE_MAX_BIN */
+    int scale;                /* AM_SCALE_NONE or AM_SCALE_LIB */
+    uint32_t reserved;        /* 0 */
+} am_trace_params;
+typedef struct am_trace_stats {
+    uint64_t count;           /* counted scores of all bins */
+    uint64_t argmax, argmin;  /* absolute score offsets of the global max / min */
+    double max, min;
+    double mean, std;         /* of the counted scores */
+    double median_max, mad_max;   /* median of the bin maxima and their median absolute deviation from it */
+    double peak_z;
+} am_trace_stats;             /* 80 bytes, no padding */
+
+int am_trace_len(size_t n_scores, uint64_t bin, size_t* n_bins);
+int am_trace_scores(int device, const float* scores, size_t n, uint64_t bin, am_trace_bin* out, size_t cap, size_t* n_out);
+int am_trace_scores_device(int device, const float* d_scores, size_t n, uint64_t bin, am_trace_bin* out, size_t cap,
+                           size_t* n_out);
+int am_match_trace(const am_needle* h, const void* haystack, size_t len, int sample_format, const am_trace_params* tp,
+                   am_trace_bin* out, size_t cap, size_t* n_out);
+int am_match_trace_device(const am_needle* h, const void* d_haystack, size_t len, int sample_format,
+                          const am_trace_params* tp, am_trace_bin* out, size_t cap, size_t* n_out);
+int am_match_trace_batch_device(const am_needle* h, const void* const* d_haystacks, const size_t* lens, size_t n_hay,
+                                int sample_format, const am_trace_params* tp, am_trace_bin* out, size_t cap_per_hay,
+                                size_t* n_out);
+int am_trace_summary(const am_trace_bin* bins, size_t n_bins, uint64_t bin, am_trace_stats* out);
+
 
 /* ---- ingest: PCM -> f32 mono -------------------------------------------- */
 /* mp3_reader.rs:12, 28-37: mono = (l as f32 + r as f32) * 0.5 * (1/65535) */
@@ -1214,7 +1296,7 @@ int am_set_chunk_progress_callback(am_chunk_progress_fn fn, void* user);
  * HIP events on the stream it is launched on.  am_profile_query returns the
  * summed elapsed time and launch count of kernels whose name matches `kernel`
  * exactly ("k1_cols_fwd", "k2_rows", "k3_cols_inv", "tile_stats",
- * "peaks", or "*" for all). */
+ * "peaks", "other", "trace" -- the score-trace kernels -- or "*" for all). */
 int am_profile_enable(int device, int on);
 int am_profile_reset(int device);
 int am_profile_query(int device, const char* kernel, double* total_ms, uint64_t* launches);
@@ -1282,7 +1364,9 @@ int am_debug_column_bench(int device, int wide, int npairs, int iters, int dense
  *       is being queued fails the call with AM_ERR_HIP instead (every such buffer is sized before the queueing
  *       loop; this makes a violation visible); "debug_redo_arm_at" (k >= 0: the device-side redo of a batch is
  *       armed from haystack k of the call on; -1: never; -2, the default: when a failed certificate has been
- *       seen) -- pins the otherwise timing-dependent choice between the device and the host redo path. */
+ *       seen) -- pins the otherwise timing-dependent choice between the device and the host redo path;
+ *       "trace_form" (0, the default: the bin length decides; 1: one wavefront per bin; 2: slices and a finish) -- runs
+ *       either kernel form of the score traces at every bin length. */
 /*
  * Window-energy normalised scores (normalised cross-correlation, NCC):
  *   "score_norm" (0/1, default 0): 1 = every score a call returns or picks from is
@@ -1295,7 +1379,7 @@ int am_debug_column_bench(int device, int wide, int npairs, int iters, int dense
  *     Also per needle handle (am_needle_set_option); pools use the process default (their needles are internal).
  *     Supported by am_correlate*, am_match, am_match_device, am_match_batch_device, am_match_pcm16*,
  *     am_pool_match_batch and am_pool_match_batch_pcm16 (and their _device forms), am_match_best,
- *     am_match_best_device and am_match_best_batch_device.  NOT supported -- AM_ERR_INVALID_ARG,
+ *     am_match_best_device, am_match_best_batch_device and am_match_trace*.  NOT supported -- AM_ERR_INVALID_ARG,
  *     "score_norm: not supported by this entry point" -- by am_match_multi*, am_match_multi_varlen_batch_device,
  *     am_match_multi_varlen, am_pool_match_multi*, am_match_stream_*, am_match_part_device and am_pool_match_long*.  am_find_peaks is unaffected.
  *     Non-finite samples cost exactly the windows that hold them (they count as 0 in every other window's energy); a

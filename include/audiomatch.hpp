@@ -376,10 +376,50 @@ public:
         for (std::size_t i = 0; i < nh; ++i) out[i].assign(buf.begin() + (std::ptrdiff_t)(i * k), buf.begin() + (std::ptrdiff_t)(i * k + n[i]));
         return out;
     }
+    // score traces (am_match_trace): one am_trace_bin per tp.bin Valid scores of the haystack -- the array match_best
+    // selects from; am_match_trace_device / _batch_device for resident haystacks
+    std::vector<am_trace_bin> match_trace(const void* haystack, std::size_t len, int sample_format, const am_trace_params& tp) const {
+        return trace_filled(len, tp, [&](am_trace_bin* out, std::size_t cap, std::size_t* n) {
+            return am_match_trace(h_, haystack, len, sample_format, &tp, out, cap, n);
+        });
+    }
+    std::vector<am_trace_bin> match_trace_device(const void* d_haystack, std::size_t len, int sample_format, const am_trace_params& tp) const {
+        return trace_filled(len, tp, [&](am_trace_bin* out, std::size_t cap, std::size_t* n) {
+            return am_match_trace_device(h_, d_haystack, len, sample_format, &tp, out, cap, n);
+        });
+    }
+    std::vector<std::vector<am_trace_bin>> match_trace_batch_device(const std::vector<const void*>& d_haystacks, const std::vector<std::size_t>& lens,
+                                                                    int sample_format, const am_trace_params& tp) const {
+        if (d_haystacks.size() != lens.size()) check(AM_ERR_INVALID_ARG);
+        const std::size_t nh = d_haystacks.size();
+        std::size_t cap = 0;
+        for (std::size_t len : lens) cap = std::max(cap, trace_bins_of(len, tp));
+        std::vector<am_trace_bin> buf(std::max<std::size_t>(1, nh * cap));
+        std::vector<std::size_t> n(std::max<std::size_t>(1, nh), 0);
+        check(am_match_trace_batch_device(h_, d_haystacks.data(), lens.data(), nh, sample_format, &tp, buf.data(), cap, n.data()));
+        std::vector<std::vector<am_trace_bin>> out(nh);
+        for (std::size_t i = 0; i < nh; ++i) out[i].assign(buf.begin() + (std::ptrdiff_t)(i * cap), buf.begin() + (std::ptrdiff_t)(i * cap + n[i]));
+        return out;
+    }
     // per-handle "log_n" / "half_pipeline" / "score_norm" (-1 = follow the process default)
     void set_option(const char* key, long long value) { check(am_needle_set_option(h_, key, value)); }
 
 private:
+    // the records a haystack of len samples has under tp (am_trace_len over its Valid scores)
+    std::size_t trace_bins_of(std::size_t len, const am_trace_params& tp) const {
+        std::size_t s = 0, nb = 0;
+        check(am_needle_len(h_, &s));
+        check(am_trace_len(len >= s ? len - s + 1 : 0, tp.bin, &nb));
+        return nb;
+    }
+    template <class Call>
+    std::vector<am_trace_bin> trace_filled(std::size_t len, const am_trace_params& tp, Call call) const {
+        std::vector<am_trace_bin> out(trace_bins_of(len, tp));
+        std::size_t n = 0;
+        check(call(out.data(), out.size(), &n));
+        out.resize(std::min(n, out.size()));
+        return out;
+    }
     am_needle* h_ = nullptr;
 };
 
@@ -399,6 +439,28 @@ inline std::vector<am_peak> find_peaks_top_device(const float* d_scores, std::si
     std::size_t got = 0;
     check(am_find_peaks_top_device(device, d_scores, n, min_prominence, min_distance, k, out.data(), &got));
     out.resize(got);
+    return out;
+}
+
+// am_trace_scores: one am_trace_bin per `bin` scores of any score array; trace_scores_device for scores resident on
+// `device` (any 4-byte alignment); trace_summary: am_trace_summary of a trace's records (no device needed)
+inline std::vector<am_trace_bin> trace_scores(const float* scores, std::size_t n, std::uint64_t bin, int device = 0) {
+    std::size_t nb = 0, got = 0;
+    check(am_trace_len(n, bin, &nb));
+    std::vector<am_trace_bin> out(nb);
+    check(am_trace_scores(device, scores, n, bin, out.data(), nb, &got));
+    return out;
+}
+inline std::vector<am_trace_bin> trace_scores_device(const float* d_scores, std::size_t n, std::uint64_t bin, int device = 0) {
+    std::size_t nb = 0, got = 0;
+    check(am_trace_len(n, bin, &nb));
+    std::vector<am_trace_bin> out(nb);
+    check(am_trace_scores_device(device, d_scores, n, bin, out.data(), nb, &got));
+    return out;
+}
+inline am_trace_stats trace_summary(const std::vector<am_trace_bin>& bins, std::uint64_t bin) {
+    am_trace_stats out{};
+    check(am_trace_summary(bins.data(), bins.size(), bin, &out));
     return out;
 }
 
