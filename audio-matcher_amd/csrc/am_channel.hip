@@ -5,20 +5,19 @@
 //
 // Two kernels on the context's stream:
 //   lag_slices    one workgroup of 256 per (slice of kHitSlice needle samples, tile of kLagTile lags, item).  It stages x
-//                 over the slice plus 31 samples in LDS once, as f32, at index q + (q >> 4): work item w takes the 16
-//                 consecutive needle samples 16 w .. 16 w + 15 (in registers) and reads the 47 staged samples its 32 lags
-//                 reach into registers, once -- 47 LDS reads for 512 products, where the strided form of seg_slices reads
-//                 one sample per product; the padding makes the stride between lanes 17 words, so that every one of those
-//                 reads is free of bank conflicts.  The tile's 32 sums stay in 32 f64 accumulators; they are reduced in
-//                 the order of seg_slices (a butterfly over the wave, then the waves in order) and leave as one 64-bit
-//                 store per lane.  The tile that holds lag 0 adds E_w and E_x from the same staged samples; the head
+//                 over the slice plus 31 samples in LDS once, as f32, at index pad16(q) (stage_load): work item w takes
+//                 the 16 consecutive needle samples 16 w .. 16 w + 15 (in registers) and reads the 47 staged samples its 32
+//                 lags reach into registers, once (lag_dot) -- 47 LDS reads for 512 products, where the strided form of
+//                 seg_slices reads one sample per product.  The tile's 32 sums stay in 32 f64 accumulators; they are added
+//                 over the workgroup by wave_sums and add_waves and leave as one 64-bit store per lane.
+//                 The tile that holds lag 0 adds E_w and E_x from the same staged samples; the head
 //                 [t - P, t) is attached to slice 0 and the tail [t + S, t + S + P) to the last slice, one sample per work
 //                 item (the order is stated in the header).  Every workgroup flags a non-finite sample among what it
 //                 staged; over the tiles and slices that is exactly [t - P, t + S + P) and the needle.
 //                 An item is a descriptor (LagDesc).  The hits' items use the lags -P .. P; the needle's autocorrelation
 //                 is the same kernel on one more item per distinct needle of the call: the needle as both signals, t = 0,
 //                 len = S, lags 0 .. 2P.
-//   lag_combine   one wave per item: adds the partials in slice order and writes the item's sums record (the lags' sums,
+//   lag_combine   one wave per item: adds the partials (sum_slices) and writes the item's sums record (the lags' sums,
 //                 E_w, E_x, the flag).
 // The sums go down through the frame's pinned hit_io; the host solves and fills the records and the taps.  The partial
 // records grow with items x slices x tiles: a call runs its items in rounds that hold at most kChanRoundBytes of them (one
@@ -26,6 +25,7 @@
 // three forms run in the frame of am_hits.hip (am_internal.h: hit_call, hit_call_batch) and agree bit for bit.
 #include <cmath>
 
+#include "am_hit_device.h"
 #include "am_internal.h"
 
 namespace am {
@@ -34,14 +34,11 @@ namespace {
 
 constexpr int kChanThreads = 256;
 constexpr int kLagPer = kHitSlice / kChanThreads;     // consecutive needle samples per work item
-constexpr int kLagSpan = kLagPer + kLagTile - 1;      // staged samples a work item's lags reach
 constexpr int kLagStaged = kHitSlice + kLagTile - 1;  // staged samples of a slice
 constexpr int kLagNV = kLagTile + 2;                  // values a workgroup reduces: the tile's sums, E_w, E_x
-static_assert(kLagPer == 16, "the LDS layout pads one word per 16 samples: lanes are 17 words apart");
+static_assert(kLagPer == 16, "pad16: the LDS layout pads one word per 16 samples");
 static_assert(kLagTile <= 32 && kLagNV + 1 <= kChanThreads && AM_CHAN_MAX_RADIUS <= kChanThreads,
               "one head and one tail sample, one record value per work item");
-
-__device__ __forceinline__ int lag_pad(int q) { return q + (q >> 4); }
 
 template <int KIND>
 __global__ __launch_bounds__(kChanThreads, 2) void lag_slices_kernel(const LagDesc* __restrict__ items, long long g0, int nt,
@@ -57,22 +54,10 @@ __global__ __launch_bounds__(kChanThreads, 2) void lag_slices_kernel(const LagDe
     const int ztile = -d.lag0 / kLagTile, zoff = -d.lag0 - ztile * kLagTile;   // the tile that holds lag 0, and where in it
     const bool energies = tile == ztile;
     const bool last = i0 + cnt == d.s;
-    // every load of the slice in flight at once: xs[pad(q)] = x[t + i0 + lag0 + q] for q < cnt + 31, 0 beyond and where
-    // the item reads no sample; the work item's needle samples; its head and tail sample
-    const long long u0 = i0 + lag0;
-    float xv[kLagPer], nv[kLagPer];
-#pragma unroll
-    for (int k = 0; k < kLagPer; ++k) {
-        const int q = tid + k * kChanThreads;
-        const long long u = u0 + q;
-        xv[k] = q < cnt + kLagTile - 1 && u >= d.ulo && u < d.uhi ? hit_sample<KIND>(d.win, u) : 0.0f;
-    }
-    float xt = 0.0f;
-    if (tid < kLagTile - 1) {
-        const int q = kHitSlice + tid;
-        const long long u = u0 + q;
-        xt = q < cnt + kLagTile - 1 && u >= d.ulo && u < d.uhi ? hit_sample<KIND>(d.win, u) : 0.0f;
-    }
+    // every load of the slice in flight at once: xs[pad16(q)] = x[t + i0 + lag0 + q] (stage_load, stage_store); the work
+    // item's needle samples; its head and tail sample
+    float xv[kLagPer], nv[kLagPer], xt;
+    stage_load<KIND, kChanThreads>(d.win, i0 + lag0, cnt, kLagTile - 1, d.ulo, d.uhi, xv, xt);
     gfloat* nd = (gfloat*)d.needle + (i0 + tid * kLagPer);
 #pragma unroll
     for (int j = 0; j < kLagPer; ++j) nv[j] = tid * kLagPer + j < cnt ? nd[j] : 0.0f;
@@ -82,33 +67,22 @@ __global__ __launch_bounds__(kChanThreads, 2) void lag_slices_kernel(const LagDe
         if (blockIdx.x == 0 && uh >= d.ulo) xh = hit_sample<KIND>(d.win, uh);
         if (last && ul < d.uhi) xl = hit_sample<KIND>(d.win, ul);
     }
-    bool bad = !__builtin_isfinite(xt) || !__builtin_isfinite(xh) || !__builtin_isfinite(xl);
+    bool bad = !__builtin_isfinite(xh) || !__builtin_isfinite(xl);
+    stage_store<kChanThreads>(StagePad16{}, xs, kLagTile - 1, xv, xt, [&](int, float x) { bad |= !__builtin_isfinite(x); });
 #pragma unroll
-    for (int k = 0; k < kLagPer; ++k) {
-        xs[lag_pad(tid + k * kChanThreads)] = xv[k];
-        bad |= !__builtin_isfinite(xv[k]) || !__builtin_isfinite(nv[k]);
-    }
-    if (tid < kLagTile - 1) xs[lag_pad(kHitSlice + tid)] = xt;
+    for (int k = 0; k < kLagPer; ++k) bad |= !__builtin_isfinite(nv[k]);
     __syncthreads();
     double acc[kLagNV];   // the tile's c, then E_w and E_x
 #pragma unroll
     for (int k = 0; k < kLagNV; ++k) acc[k] = 0.0;
     const int q0 = tid * kLagPer;
     if (q0 < cnt) {
-        double xd[kLagSpan];
-#pragma unroll
-        for (int j = 0; j < kLagSpan; ++j) xd[j] = (double)xs[lag_pad(q0 + j)];
-#pragma unroll
-        for (int j = 0; j < kLagPer; ++j) {
-            const double dn = (double)nv[j];
-#pragma unroll
-            for (int l = 0; l < kLagTile; ++l) acc[l] += xd[j + l] * dn;   // (a product of two f32 values is exact in f64)
-        }
+        lag_dot<kLagTile>(xs, nv, q0, acc);
         if (energies) {
             double e = 0.0;
 #pragma unroll
             for (int j = 0; j < kLagPer; ++j) {
-                const double dx = q0 + j < cnt ? (double)xs[lag_pad(q0 + j + zoff)] : 0.0;
+                const double dx = q0 + j < cnt ? (double)xs[pad16(q0 + j + zoff)] : 0.0;
                 e += dx * dx;
             }
             acc[kLagTile] = e;
@@ -120,28 +94,17 @@ __global__ __launch_bounds__(kChanThreads, 2) void lag_slices_kernel(const LagDe
         e += (double)xl * (double)xl;
         acc[kLagTile + 1] = e;
     }
-    // the sums of the workgroup in the order of seg_slices: a butterfly over the wave, then the waves in order
-    const int lane = tid & 63, w = tid >> 6;
-#pragma unroll
-    for (int k = 0; k < kLagNV; ++k) {
-        double v = acc[k];
-        for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-        if (lane == 0) ws[k][w] = v;
-    }
+    wave_sums<kChanThreads>(acc, ws);
     const int any_bad = __syncthreads_or(bad ? 1 : 0);
     // one 64-bit store per lane: no record leaves as one wide store (tools/check_store_hazard.py)
     const long long p = d.part0 + blockIdx.x;
     double* rec = parts + (long long)lag_record_len(nt) * p;
-    if (tid < kLagTile || (energies && tid < kLagNV)) {
-        double t = 0.0;
-        for (int i = 0; i < kChanThreads / 64; ++i) t += ws[tid][i];
-        rec[tid < kLagTile ? tile * kLagTile + tid : nt * kLagTile + (tid - kLagTile)] = t;
-    } else if (tid == kLagNV) {
-        pflags[p * nt + tile] = (unsigned)any_bad;
-    }
+    if (tid < kLagTile || (energies && tid < kLagNV))
+        rec[tid < kLagTile ? tile * kLagTile + tid : nt * kLagTile + (tid - kLagTile)] = add_waves<kChanThreads>(ws[tid]);
+    else if (tid == kLagNV) pflags[p * nt + tile] = (unsigned)any_bad;
 }
 
-// One wave per item: lane k adds value k (and k + 64, ...) of the item's partial records in slice order.
+// One wave per item: lane k adds value k (and k + 64, ...) of the item's partial records (sum_slices).
 __global__ __launch_bounds__(64) void lag_combine_kernel(const LagDesc* __restrict__ items, int nt, int nlag_max,
                                                          const double* __restrict__ parts, const unsigned* __restrict__ pflags,
                                                          double* __restrict__ sums) {
@@ -151,13 +114,9 @@ __global__ __launch_bounds__(64) void lag_combine_kernel(const LagDesc* __restri
     double* o = sums + (long long)lag_sums_len(nlag_max) * blockIdx.x;
     for (int k = lane; k < d.nlag + 2; k += 64) {
         const int col = k < d.nlag ? k : nt * kLagTile + (k - d.nlag);
-        double t = 0.0;
-        for (long long i = 0; i < ns; ++i) t += parts[nv * (d.part0 + i) + col];   // (slice order)
-        o[k < d.nlag ? k : nlag_max + (k - d.nlag)] = t;
+        o[k < d.nlag ? k : nlag_max + (k - d.nlag)] = sum_slices(parts, nv, d.part0, ns, col);
     }
-    unsigned b = 0;
-    for (long long i = lane; i < ns * nt; i += 64) b |= pflags[d.part0 * nt + i];
-    const int bad = __syncthreads_or(b != 0 ? 1 : 0);
+    const int bad = __syncthreads_or(or_flags(pflags, d.part0 * nt, ns * nt, lane, 64) != 0 ? 1 : 0);
     if (lane == 0) o[nlag_max + 2] = bad ? 1.0 : 0.0;
 }
 
@@ -165,14 +124,11 @@ __global__ __launch_bounds__(64) void lag_combine_kernel(const LagDesc* __restri
 
 hipError_t launch_lag_slices(hipStream_t st, const LagDesc* tab, long long first, long long n, int nt, int max_nsl, int kind, double* parts,
                              unsigned* pflags) {
-    for (long long g0 = 0; g0 < n; g0 += kHitMaxGridY) {   // (more items than one grid column holds: a few launches)
-        const dim3 grid((unsigned)max_nsl, (unsigned)nt, (unsigned)std::min<long long>(kHitMaxGridY, n - g0));
+    return for_each_grid_y(n, [&](long long g0, unsigned ng) {   // (the items are grid.z here; its limit is grid.y's)
+        const dim3 grid((unsigned)max_nsl, (unsigned)nt, ng);
         if (kind) hipLaunchKernelGGL(lag_slices_kernel<1>, grid, dim3(kChanThreads), 0, st, tab, first + g0, nt, parts, pflags);
         else hipLaunchKernelGGL(lag_slices_kernel<0>, grid, dim3(kChanThreads), 0, st, tab, first + g0, nt, parts, pflags);
-        hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return e;
-    }
-    return hipSuccess;
+    });
 }
 
 hipError_t launch_lag_combine(hipStream_t st, const LagDesc* tab, long long n, int nt, int nlag_max, const double* parts,

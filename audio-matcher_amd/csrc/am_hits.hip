@@ -5,17 +5,19 @@
 //
 // Two kernels on the context's stream:
 //   hit_slices    one workgroup per slice of kHitSlice needle samples of one hit (blockIdx.x = slice, blockIdx.y =
-//                 hit): stages x over the slice plus one sample each side in LDS, accumulates the four sums from that
-//                 one read and writes one partial record (four doubles, one 64-bit store each, and a flag word).
-//   hit_combine   one wave per hit: adds the hit's partials in slice order and writes its am_hit_score.
+//                 hit): stages x over the slice plus one sample each side in LDS (stage_load), accumulates the four
+//                 sums from that one read, adds them over the workgroup (wave_sums, add_waves) and writes one partial
+//                 record (four doubles, one 64-bit store each, and a flag word).
+//   hit_combine   one wave per hit: adds the hit's partials in the order of sum_slices and writes its am_hit_score.
 // A hit's result depends on its needle, the samples it reads and the floor only (the slices of a hit start at
-// multiples of kHitSlice of the needle, every reduction runs in a fixed order): the single, batch and host forms agree
-// bit for bit, whatever else a call holds.
+// multiples of kHitSlice of the needle, every reduction runs in the fixed order am_hit_device.h states): the single,
+// batch and host forms agree bit for bit, whatever else a call holds.
 //
 // Below the kernels: the host side every per-hit family shares (this file, am_segments.hip, am_bands.hip,
 // am_significance.hip) -- the preludes of the three call forms, span staging for the host forms and the table's trip to
 // the device and back; the templates that tie them together (hit_call, hit_call_batch, hit_round_trip) are in
 // am_internal.h, which also says what a family supplies.  Then am_hit_scores* itself, as the first such family.
+#include "am_hit_device.h"
 #include "am_internal.h"
 
 namespace am {
@@ -26,52 +28,23 @@ constexpr int kHitThreads = 256;
 constexpr int kHitPer = kHitSlice / kHitThreads;   // needle samples per thread and slice
 static_assert(kHitSlice % kHitThreads == 0, "slice must split evenly over the workgroup");
 
-// Sums of four values per thread, each in a fixed order (every thread gets the results).
-__device__ void hit_block_sum4(double v[4]) {
-    __shared__ double ws[4][kHitThreads / 64];
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    for (int k = 0; k < 4; ++k) {
-        for (int off = 32; off > 0; off >>= 1) v[k] += __shfl_xor(v[k], off, 64);
-        if (lane == 0) ws[k][w] = v[k];
-    }
-    __syncthreads();
-    for (int k = 0; k < 4; ++k) {
-        double t = 0.0;
-        for (int i = 0; i < kHitThreads / 64; ++i) t += ws[k][i];
-        v[k] = t;
-    }
-}
-
 template <int KIND>
 __global__ __launch_bounds__(kHitThreads) void hit_slices_kernel(const HitDesc* __restrict__ hits, long long hit0,
                                                                  double* __restrict__ parts, unsigned* __restrict__ pflags) {
     __shared__ float xs[kHitSlice + 2];
+    __shared__ double ws[4][kHitThreads / 64];
     const HitDesc d = hits[hit0 + blockIdx.y];
     const long long i0 = (long long)blockIdx.x * kHitSlice;
     if (i0 >= d.s) return;   // (a shorter needle than the launch's longest: whole workgroups leave together)
     const int tid = threadIdx.x;
     const int m = (int)min((long long)kHitSlice, d.s - i0);
-    // every load of the slice in flight at once: xs[q] = x[t + i0 - 1 + q] (q < m + 2, 0 where the hit reads no
-    // sample) and the thread's needle samples n[i0 + q]
+    // every load of the slice in flight at once: xs[q] = x[t + i0 - 1 + q] (stage_load, stage_store; the samples the hit
+    // reads are [ulo, uhi)) and the thread's needle samples n[i0 + q]
     gfloat* nd = (gfloat*)d.needle + i0;
-    const long long ulo = (d.edge & 1) ? -1 : 0, uhi = (d.edge & 2) ? d.s + 1 : d.s;   // the samples the hit reads
-    float xv[kHitPer], nv[kHitPer];
-#pragma unroll
-    for (int r = 0; r < kHitPer; ++r) {
-        const int q = tid + r * kHitThreads;
-        const long long u = i0 - 1 + q;
-        xv[r] = q < m + 2 && u >= ulo && u < uhi ? hit_sample<KIND>(d.win, u) : 0.0f;
-        nv[r] = q < m ? nd[q] : 0.0f;
-    }
-    float xt = 0.0f;
-    if (tid < 2) {
-        const int q = kHitSlice + tid;
-        const long long u = i0 - 1 + q;
-        xt = q < m + 2 && u >= ulo && u < uhi ? hit_sample<KIND>(d.win, u) : 0.0f;
-    }
-#pragma unroll
-    for (int r = 0; r < kHitPer; ++r) xs[tid + r * kHitThreads] = xv[r];
-    if (tid < 2) xs[kHitSlice + tid] = xt;
+    float xv[kHitPer], nv[kHitPer], xt;
+    stage_load<KIND, kHitThreads>(d.win, i0 - 1, m, 2, (d.edge & 1) ? -1 : 0, (d.edge & 2) ? d.s + 1 : d.s, xv, xt,
+                                  [&](int r, int q) { nv[r] = q < m ? nd[q] : 0.0f; });
+    stage_store<kHitThreads>(StageFlat{}, xs, 2, xv, xt);   // (the non-finite test is on what the sums read, below)
     __syncthreads();
     double c0 = 0.0, c1 = 0.0, c2 = 0.0, ew = 0.0;
     bool bad = false;
@@ -88,16 +61,18 @@ __global__ __launch_bounds__(kHitThreads) void hit_slices_kernel(const HitDesc* 
             bad |= !__builtin_isfinite(x) || !__builtin_isfinite(n);
         }
     }
+    const double v[4] = {c0, c1, c2, ew};
+    wave_sums<kHitThreads>(v, ws);
     const int any_bad = __syncthreads_or(bad ? 1 : 0);
-    double v[4] = {c0, c1, c2, ew};
-    hit_block_sum4(v);
     // one 64-bit store per lane: no record leaves as one wide store (tools/check_store_hazard.py)
     const long long p = d.part0 + blockIdx.x;
-    if (tid < 4) parts[4 * p + tid] = v[tid];
+    if (tid < 4) parts[4 * p + tid] = add_waves<kHitThreads>(ws[tid]);
     else if (tid == 4) pflags[p] = (unsigned)any_bad;
 }
 
-// One wave per hit: the lanes fetch 64 partial records at a time into LDS, lane 0 adds them in slice order.
+// One wave per hit: the lanes fetch 64 partial records at a time into LDS, lane 0 adds them to 0 in slice order -- the
+// order of sum_slices, not its loop: with a column per lane (four lanes, each walking its column's loads one behind the
+// other) a call of few hits took 0.6 to 1.5 us longer (profiles/r23).
 __global__ __launch_bounds__(64) void hit_combine_kernel(const HitDesc* __restrict__ hits, const double* __restrict__ parts,
                                                          const unsigned* __restrict__ pflags, am_hit_score* __restrict__ out) {
     __shared__ double ps[4][64];
@@ -137,21 +112,14 @@ __global__ __launch_bounds__(64) void hit_combine_kernel(const HitDesc* __restri
         flags = AM_HIT_NONFINITE;
         ncc = gain = wdb = (float)nan;
     } else {
-        const double den = a - 2.0 * b + c;
-        if ((d.edge & 3) != 3 || !__builtin_isfinite(a) || !__builtin_isfinite(c) || !(den < 0.0)) {
-            flags |= AM_HIT_UNREFINED;
-        } else {
-            const double delta = 0.5 * (a - c) / den;
-            pos += fmin(fmax(delta, -0.5), 0.5);
-        }
-        if (ew == 0.0 || ew < d.thr) {
-            flags |= AM_HIT_BELOW_FLOOR;
-            ncc = 0.0f;
-        } else {
-            ncc = (float)(b / sqrt(d.en * ew));
-        }
+        bool refined, below;
+        const double delta = parabola_vertex(a, b, c, &refined);
+        if ((d.edge & 3) != 3 || !__builtin_isfinite(a) || !__builtin_isfinite(c) || !refined) flags |= AM_HIT_UNREFINED;
+        else pos += delta;
+        ncc = (float)ncc_or_floor(b, d.en, ew, d.thr, &below);
+        if (below) flags |= AM_HIT_BELOW_FLOOR;
         gain = d.en > 0.0 ? (float)(b / d.en) : 0.0f;
-        wdb = ew == 0.0 ? -__builtin_inff() : (float)(10.0 * log10(ew / d.en));
+        wdb = level_db(ew, d.en);
     }
     am_hit_score* o = out + h;
     o->position = pos;
@@ -166,13 +134,12 @@ __global__ __launch_bounds__(64) void hit_combine_kernel(const HitDesc* __restri
 hipError_t launch_hit_scores(hipStream_t st, const HitDesc* d_hits, long long n, long long max_slices, int kind, double* parts,
                              unsigned* pflags, am_hit_score* d_out) {
     if (n <= 0) return hipSuccess;
-    for (long long h0 = 0; h0 < n; h0 += kHitMaxGridY) {   // (more hits than one grid column holds: a few launches)
-        const long long nh = std::min<long long>(kHitMaxGridY, n - h0);
-        if (kind) hipLaunchKernelGGL(hit_slices_kernel<1>, dim3((unsigned)max_slices, (unsigned)nh), dim3(kHitThreads), 0, st, d_hits, h0, parts, pflags);
-        else hipLaunchKernelGGL(hit_slices_kernel<0>, dim3((unsigned)max_slices, (unsigned)nh), dim3(kHitThreads), 0, st, d_hits, h0, parts, pflags);
-        hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return e;
-    }
+    const hipError_t e = for_each_grid_y(n, [&](long long h0, unsigned nh) {
+        const dim3 grid((unsigned)max_slices, nh);
+        if (kind) hipLaunchKernelGGL(hit_slices_kernel<1>, grid, dim3(kHitThreads), 0, st, d_hits, h0, parts, pflags);
+        else hipLaunchKernelGGL(hit_slices_kernel<0>, grid, dim3(kHitThreads), 0, st, d_hits, h0, parts, pflags);
+    });
+    if (e != hipSuccess) return e;
     hipLaunchKernelGGL(hit_combine_kernel, dim3((unsigned)n), dim3(64), 0, st, d_hits, (const double*)parts, (const unsigned*)pflags, d_out);
     return hipGetLastError();
 }

@@ -13,6 +13,7 @@
 //                  tile's kNormTile + S - 1 samples.
 // Every score depends on its index, the samples and the needle only (tiles start at multiples of kNormTile of the
 // score array, the reductions run in a fixed order): a haystack's bits do not depend on the batch it travels in.
+#include "am_hit_device.h"
 #include "am_internal.h"
 
 namespace am {
@@ -35,14 +36,10 @@ __device__ __forceinline__ double norm_sq(const void* __restrict__ src, long lon
 }
 __device__ __forceinline__ long long floor_div(long long x, long long b) { return x >= 0 ? x / b : -((-x + b - 1) / b); }
 
-// Sum of one value per thread, in a fixed order (every thread gets the result).  `ws`: kNormThreads / 64 doubles.
-__device__ double block_sum(double v, double* ws) {
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    if (lane == 0) ws[w] = v;
-    __syncthreads();
-    double t = 0.0;
-    for (int i = 0; i < kNormThreads / 64; ++i) t += ws[i];
+// Sum of one value per thread, in the order of block_sum (am_hit_device.h; every thread gets the result), and ws free
+// again.  `ws`: kNormThreads / 64 doubles.
+__device__ double norm_block_sum(double v, double* ws) {
+    const double t = block_sum<kNormThreads>(v, ws);
     __syncthreads();
     return t;
 }
@@ -82,7 +79,7 @@ __global__ __launch_bounds__(kNormThreads) void block_energy_kernel(const void* 
     const long long base = (long long)blockIdx.x * kNormBlock;
     double s = 0.0;
     for (int r = 0; r < kNormBlock / kNormThreads; ++r) s += norm_sq(src, base + threadIdx.x + r * kNormThreads, len, kind);
-    s = block_sum(s, ws);
+    s = norm_block_sum(s, ws);
     if (threadIdx.x == 0) blk[blockIdx.x] = s;
 }
 
@@ -112,7 +109,7 @@ __global__ __launch_bounds__(kNormThreads) void norm_scores_kernel(NormJob j, lo
         const long long jlo = max(A / B, 0ll), jhi = min(Z / B, j.nblk);
         double m = 0.0;
         for (long long q = jlo + tid; q < jhi; q += kNormThreads) m += j.blk[q];
-        m = block_sum(m, ws);
+        m = norm_block_sum(m, ws);
         // tail pieces [Z, u + S): prefix sums over [Z, u0 + kNormTile - 1 + S)
         const int nt = (int)(u0 + kNormTile - 1 + S - Z);
         for (int q = tid; q < nt; q += kNormThreads) buf[q] = norm_sq(j.src, Z + q, j.src_len, j.src_kind);

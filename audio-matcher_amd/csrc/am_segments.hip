@@ -8,17 +8,19 @@
 // Two kernels on the context's stream:
 //   seg_slices    one workgroup per slice of kHitSlice needle samples counted from the segment's start (blockIdx.x =
 //                 slice within the segment, blockIdx.y = hit * m + segment): stages x over the slice plus RT samples each
-//                 side in LDS once, keeps the thread's needle samples in registers, accumulates the 2 RT + 1 pairs
-//                 (c, E_w) and E_n from that one read and writes one partial record, one 64-bit store per lane.  RT is
-//                 the smallest of kSegRadii that holds R: three instances per sample format, the accumulators in registers.
-//   seg_combine   one wave per (hit, segment): adds the segment's partials in slice order, picks l*, the vertex and the
-//                 flags and writes the am_hit_segment.
+//                 side in LDS once (stage_load), keeps the thread's needle samples in registers, accumulates the
+//                 2 RT + 1 pairs (c, E_w) and E_n from that one read, adds them over the workgroup (wave_sums, add_waves)
+//                 and writes one partial record, one 64-bit store per lane.  RT is the smallest of kSegRadii that holds
+//                 R: three instances per sample format, the accumulators in registers.
+//   seg_combine   one wave per (hit, segment): adds the segment's partials (sum_slices), picks l* (pick_lag), the vertex
+//                 (refine_lag) and the flags and writes the am_hit_segment.
 // The kernels read x[t + u] for u in [-R, S + R) inside the haystack only (SegDesc::ulo, uhi), whatever RT is: that is
 // what the host form stages, and lags beyond R never reach a result.  A segment's result depends on the needle, the
 // samples it reads, m, R and the floor only (slices start at multiples of kHitSlice from a_j, every reduction runs in
-// a fixed order): the single, batch and host forms agree bit for bit.  The three forms run in the frame of am_hits.hip
+// the fixed order am_hit_device.h states): the single, batch and host forms agree bit for bit.  The three forms run in the frame of am_hits.hip
 // (am_internal.h: hit_call, hit_call_batch, hit_round_trip); SegFamily below is what this family adds to it.
 // am_warp.hip runs seg_slices alone (launch_seg_slices, m = 1) over a table of its own and combines the records itself.
+#include "am_hit_device.h"
 #include "am_internal.h"
 
 namespace am {
@@ -48,38 +50,19 @@ __global__ __launch_bounds__(kSegThreads) void seg_slices_kernel(const SegDesc* 
     if (i0 >= a1 - a0) return;   // (a shorter segment than the launch's longest: whole workgroups leave together)
     const int tid = threadIdx.x;
     const int cnt = (int)min((long long)kHitSlice, a1 - a0 - i0);
-    // every load of the slice in flight at once: xs[q] = x[t + a0 + i0 - RT + q] (q < cnt + 2 RT, 0 where the hit reads
-    // no sample) and the thread's needle samples n[a0 + i0 + q]; a staged sample counts for the segment's non-finite
-    // flag when one of the lags -r .. r reads it
+    // every load of the slice in flight at once: xs[q] = x[t + a0 + i0 - RT + q] (stage_load, stage_store) and the
+    // thread's needle samples n[a0 + i0 + q]; a staged sample counts for the segment's non-finite flag when one of the
+    // lags -r .. r reads it
     gfloat* nd = (gfloat*)d.needle + (a0 + i0);
-    const long long u0 = a0 + i0 - RT;
     const int qlo = RT - r, qhi = cnt + RT + r;
-    float xv[kSegPer], nv[kSegPer];
-#pragma unroll
-    for (int k = 0; k < kSegPer; ++k) {
-        const int q = tid + k * kSegThreads;
-        const long long u = u0 + q;
-        xv[k] = q < cnt + 2 * RT && u >= d.ulo && u < d.uhi ? hit_sample<KIND>(d.win, u) : 0.0f;
-        nv[k] = q < cnt ? nd[q] : 0.0f;
-    }
-    float xt = 0.0f;
-    if (tid < 2 * RT) {
-        const int q = kHitSlice + tid;
-        const long long u = u0 + q;
-        xt = q < cnt + 2 * RT && u >= d.ulo && u < d.uhi ? hit_sample<KIND>(d.win, u) : 0.0f;
-    }
+    float xv[kSegPer], nv[kSegPer], xt;
+    stage_load<KIND, kSegThreads>(d.win, a0 + i0 - RT, cnt, 2 * RT, d.ulo, d.uhi, xv, xt, [&](int k, int q) { nv[k] = q < cnt ? nd[q] : 0.0f; });
     bool bad = false;
+    // (the needle's test stands ahead of stage_store on purpose: behind it the compiler takes 84 and 180 VGPRs at RT = 4
+    // and 16 instead of 82 and 178; results do not depend on the place)
 #pragma unroll
-    for (int k = 0; k < kSegPer; ++k) {
-        const int q = tid + k * kSegThreads;
-        xs[q] = xv[k];
-        bad |= (q >= qlo && q < qhi && !__builtin_isfinite(xv[k])) || !__builtin_isfinite(nv[k]);
-    }
-    if (tid < 2 * RT) {
-        const int q = kHitSlice + tid;
-        xs[q] = xt;
-        bad |= q >= qlo && q < qhi && !__builtin_isfinite(xt);
-    }
+    for (int k = 0; k < kSegPer; ++k) bad |= !__builtin_isfinite(nv[k]);
+    stage_store<kSegThreads>(StageFlat{}, xs, 2 * RT, xv, xt, [&](int q, float x) { bad |= q >= qlo && q < qhi && !__builtin_isfinite(x); });
     __syncthreads();
     double acc[NV];   // the record: c(-RT .. RT), E_w(-RT .. RT), E_n
 #pragma unroll
@@ -98,27 +81,15 @@ __global__ __launch_bounds__(kSegThreads) void seg_slices_kernel(const SegDesc* 
             }
         }
     }
-    // the sums of the workgroup in the order of hit_block_sum4: a butterfly over the wave, then the waves in order
-    const int lane = tid & 63, w = tid >> 6;
-#pragma unroll
-    for (int k = 0; k < NV; ++k) {
-        double v = acc[k];
-        for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-        if (lane == 0) ws[k][w] = v;
-    }
+    wave_sums<kSegThreads>(acc, ws);
     const int any_bad = __syncthreads_or(bad ? 1 : 0);
     // one 64-bit store per lane: no record leaves as one wide store (tools/check_store_hazard.py)
     const long long p = d.part0 + (long long)j * d.nsl + blockIdx.x;
-    if (tid < NV) {
-        double t = 0.0;
-        for (int i = 0; i < kSegThreads / 64; ++i) t += ws[tid][i];
-        parts[NV * p + tid] = t;
-    } else if (tid == NV) {
-        pflags[p] = (unsigned)any_bad;
-    }
+    if (tid < NV) parts[NV * p + tid] = add_waves<kSegThreads>(ws[tid]);
+    else if (tid == NV) pflags[p] = (unsigned)any_bad;
 }
 
-// One wave per (hit, segment): lane k adds value k (and k + 64) of the segment's partial records in slice order, lane 0
+// One wave per (hit, segment): lane k adds value k (and k + 64) of the segment's partial records (sum_slices), lane 0
 // turns the sums into the record.
 __global__ __launch_bounds__(64) void seg_combine_kernel(const SegDesc* __restrict__ hits, int m, int r, int rt,
                                                          const double* __restrict__ parts, const unsigned* __restrict__ pflags,
@@ -131,14 +102,8 @@ __global__ __launch_bounds__(64) void seg_combine_kernel(const SegDesc* __restri
     const long long a0 = seg_start(j, d.s, m), a1 = seg_start(j + 1, d.s, m);
     const long long ns = (a1 - a0 + kHitSlice - 1) / kHitSlice, p0 = d.part0 + (long long)j * d.nsl;
     const int nl = 2 * rt + 1, nv = 2 * nl + 1;
-    for (int k = lane; k < nv; k += 64) {
-        double t = 0.0;
-        for (long long i = 0; i < ns; ++i) t += parts[nv * (p0 + i) + k];
-        sh[k] = t;
-    }
-    unsigned b = 0;
-    for (long long i = lane; i < ns; i += 64) b |= pflags[p0 + i];
-    const int bad = __syncthreads_or(b != 0 ? 1 : 0);
+    for (int k = lane; k < nv; k += 64) sh[k] = sum_slices(parts, nv, p0, ns, k);
+    const int bad = __syncthreads_or(or_flags(pflags, p0, ns, lane, 64) != 0 ? 1 : 0);
     if (lane != 0) return;
     const double* cc = sh + rt;        // cc[l] = c_j(l), ee[l] = E_w,j(l) for -rt <= l <= rt
     const double* ee = sh + nl + rt;
@@ -155,28 +120,15 @@ __global__ __launch_bounds__(64) void seg_combine_kernel(const SegDesc* __restri
         ncc = gain = 0.0f;
         ldb = ee[0] > 0.0 ? __builtin_inff() : (float)nan;
     } else {
-        int ls = 0;   // ties: the smaller |l|, then the negative lag
-        for (int k = 1; k <= r; ++k) {
-            if (cc[-k] > cc[ls]) ls = -k;
-            if (cc[k] > cc[ls]) ls = k;
-        }
-        lag = (double)ls;
+        const int ls = pick_lag<false>(cc, r);
         const double bb = cc[ls], ew = ee[ls];
-        if (r == 0 || ls == r || ls == -r) {
-            flags |= AM_HIT_UNREFINED;
-        } else {
-            const double a = cc[ls - 1], c = cc[ls + 1], den = a - 2.0 * bb + c;
-            if (!(den < 0.0)) flags |= AM_HIT_UNREFINED;
-            else lag += fmin(fmax(0.5 * (a - c) / den, -0.5), 0.5);
-        }
-        if (ew == 0.0 || ew < en * d.floor_ratio) {
-            flags |= AM_HIT_BELOW_FLOOR;
-            ncc = 0.0f;
-        } else {
-            ncc = (float)(bb / sqrt(en * ew));
-        }
+        bool refined, below;
+        lag = refine_lag<false>(cc, r, ls, &refined);
+        if (!refined) flags |= AM_HIT_UNREFINED;
+        ncc = (float)ncc_or_floor(bb, en, ew, en * d.floor_ratio, &below);
+        if (below) flags |= AM_HIT_BELOW_FLOOR;
         gain = (float)(bb / en);
-        ldb = ew == 0.0 ? -__builtin_inff() : (float)(10.0 * log10(ew / en));
+        ldb = level_db(ew, en);
     }
     am_hit_segment* o = out + g;
     o->lag = lag;
@@ -204,15 +156,11 @@ void launch_seg_slices_rt(hipStream_t st, int rt, dim3 grid, const SegDesc* d_hi
 hipError_t launch_seg_slices(hipStream_t st, const SegDesc* d_hits, long long n, int m, int r, int max_nsl, int kind, double* parts,
                              unsigned* pflags) {
     const int rt = seg_kernel_radius(r);
-    const long long total = n * m;
-    for (long long g0 = 0; g0 < total; g0 += kHitMaxGridY) {   // (more segments than one grid column holds: a few launches)
-        const dim3 grid((unsigned)max_nsl, (unsigned)std::min<long long>(kHitMaxGridY, total - g0));
+    return for_each_grid_y(n * m, [&](long long g0, unsigned ng) {
+        const dim3 grid((unsigned)max_nsl, ng);
         if (kind) launch_seg_slices_rt<1>(st, rt, grid, d_hits, g0, m, r, parts, pflags);
         else launch_seg_slices_rt<0>(st, rt, grid, d_hits, g0, m, r, parts, pflags);
-        hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return e;
-    }
-    return hipSuccess;
+    });
 }
 
 hipError_t launch_hit_segments(hipStream_t st, const SegDesc* d_hits, long long n, int m, int r, int max_nsl, int kind,

@@ -10,11 +10,13 @@
 //   sig_mean      one wave per hit: walks the hit's partials in slice order; count, mean and the largest score.
 //   sig_devs      the grid of sig_sums: the f64 sum of (r - mean)^2 over the slice's background lags.
 //   sig_finish    one wave per hit: adds those partials in slice order and writes the am_significance record.
-// No atomics: a thread adds its scores in index order, a wave by a butterfly, the waves and the slices in index order.
+// No atomics: a thread adds its scores in index order, the workgroup by block_sum (am_hit_device.h), the slices in index
+// order.
 // Slices start at multiples of kSigSlice from the zone's first lag, so a hit's record depends on its own zone only --
 // not on the group, the call or the entry point.  The three call forms run in the frame of am_hits.hip (am_internal.h:
 // hit_call, hit_call_batch); SigFamily below is what this family adds to it, and score_significance uses the frame's
 // table and result halves per group.
+#include "am_hit_device.h"
 #include "am_internal.h"
 
 #include <climits>
@@ -55,16 +57,6 @@ __device__ __forceinline__ void sig_load(const SigDesc& d, const float* __restri
     }
 }
 
-// the workgroup's sum of v: a butterfly over each wave, then the waves in order (every thread gets it)
-__device__ __forceinline__ double sig_block_sum(double v, double* ws) {
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-    if ((threadIdx.x & 63) == 0) ws[threadIdx.x >> 6] = v;
-    __syncthreads();
-    double t = 0.0;
-    for (int i = 0; i < kSigThreads / 64; ++i) t += ws[i];
-    return t;
-}
-
 __global__ __launch_bounds__(kSigThreads) void sig_sums_kernel(const SigDesc* __restrict__ hits, long long hit0,
                                                                const float* __restrict__ scores, double* __restrict__ psum,
                                                                unsigned* __restrict__ pmax) {
@@ -96,7 +88,7 @@ __global__ __launch_bounds__(kSigThreads) void sig_sums_kernel(const SigDesc* __
     }
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
     if (lane == 0) { wc[w] = cnt; wv[w] = bv; wd[w] = bd; }
-    const double total = sig_block_sum(sum, ws);   // (its barrier also publishes wc, wv, wd)
+    const double total = block_sum<kSigThreads>(sum, ws);   // (its barrier also publishes wc, wv, wd)
     cnt = 0; bv = 0.0f; bd = 0;
     for (int i = 0; i < kSigThreads / 64; ++i) sig_fold(cnt, bv, bd, wc[i], wv[i], wd[i]);
     // one store of at most 64 bits per lane: no record leaves as one wide store (tools/check_store_hazard.py)
@@ -168,7 +160,7 @@ __global__ __launch_bounds__(kSigThreads) void sig_devs_kernel(const SigDesc* __
             ss += e * e;
         }
     }
-    const double total = sig_block_sum(ss, ws);
+    const double total = block_sum<kSigThreads>(ss, ws);
     if (threadIdx.x == 0) psum[d.part0 + blockIdx.x] = total;
 }
 
@@ -236,19 +228,16 @@ __global__ __launch_bounds__(64) void sig_finish_kernel(const SigDesc* __restric
 hipError_t launch_hit_significance(hipStream_t st, const SigDesc* d_hits, long long n, long long max_slices, const float* scores,
                                    double* psum, unsigned* pmax, double* mean, unsigned* hmax, am_significance* d_out) {
     if (n <= 0) return hipSuccess;
-    hipError_t e;
-    for (long long h0 = 0; h0 < n; h0 += kHitMaxGridY) {   // (more hits than one grid column holds: a few launches)
-        const dim3 grid((unsigned)max_slices, (unsigned)std::min<long long>(kHitMaxGridY, n - h0));
-        hipLaunchKernelGGL(sig_sums_kernel, grid, dim3(kSigThreads), 0, st, d_hits, h0, scores, psum, pmax);
-        if ((e = hipGetLastError()) != hipSuccess) return e;
-    }
+    hipError_t e = for_each_grid_y(n, [&](long long h0, unsigned nh) {
+        hipLaunchKernelGGL(sig_sums_kernel, dim3((unsigned)max_slices, nh), dim3(kSigThreads), 0, st, d_hits, h0, scores, psum, pmax);
+    });
+    if (e != hipSuccess) return e;
     hipLaunchKernelGGL(sig_mean_kernel, dim3((unsigned)n), dim3(64), 0, st, d_hits, (const double*)psum, (const unsigned*)pmax, mean, hmax);
     if ((e = hipGetLastError()) != hipSuccess) return e;
-    for (long long h0 = 0; h0 < n; h0 += kHitMaxGridY) {
-        const dim3 grid((unsigned)max_slices, (unsigned)std::min<long long>(kHitMaxGridY, n - h0));
-        hipLaunchKernelGGL(sig_devs_kernel, grid, dim3(kSigThreads), 0, st, d_hits, h0, scores, (const double*)mean, psum);
-        if ((e = hipGetLastError()) != hipSuccess) return e;
-    }
+    e = for_each_grid_y(n, [&](long long h0, unsigned nh) {
+        hipLaunchKernelGGL(sig_devs_kernel, dim3((unsigned)max_slices, nh), dim3(kSigThreads), 0, st, d_hits, h0, scores, (const double*)mean, psum);
+    });
+    if (e != hipSuccess) return e;
     hipLaunchKernelGGL(sig_finish_kernel, dim3((unsigned)n), dim3(64), 0, st, d_hits, scores, (const double*)psum, (const double*)mean,
                        (const unsigned*)hmax, d_out);
     return hipGetLastError();

@@ -9,15 +9,15 @@
 // Three kernels on the context's stream:
 //   stereo_slices   one workgroup of 256 per slice of kHitSlice needle samples of one hit (blockIdx.x = slice, blockIdx.y
 //                   = hit).  It reads each frame of [t + i0 - RT, t + i0 + cnt + RT) once, as one 32-bit load, and stages
-//                   both channels in LDS as f32 (an i16 value is exact there) at index q + (q >> 4): work item w takes the
+//                   both channels in LDS as f32 (an i16 value is exact there) at index pad16(q): work item w takes the
 //                   16 consecutive needle samples 16 w .. 16 w + 15 (in registers) and reads the 16 + 2 RT staged samples
-//                   its lags reach into registers once per channel -- the layout of lag_slices (am_channel.hip): lanes
-//                   are 17 words apart, every one of those reads free of bank conflicts.  One channel at a time: its
-//                   2 RT + 1 sums in f64 accumulators, reduced in the order of seg_slices (a butterfly over the wave, then
-//                   the waves in order) before the other channel's begin, so that one channel's registers serve both.  RT
-//                   is the smallest of kSegRadii that holds R, as in seg_slices.  The three integer sums come from the
-//                   same staged samples.  One partial record per slice, one 64-bit store per lane.
-//   stereo_combine  one wave per hit: adds the partials in slice order and writes the am_stereo_hit.
+//                   its lags reach into registers once per channel (lag_dot).  One channel at a time: its 2 RT + 1 sums
+//                   in f64 accumulators, added over each wave (wave_sums) before the other channel's begin, so that one
+//                   channel's registers serve both; add_waves finishes them.  RT is the smallest of kSegRadii that holds
+//                   R.  The three integer sums come from the same staged samples and take the same helpers.  One partial
+//                   record per slice, one 64-bit store per lane.
+//   stereo_combine  one wave per hit: adds the partials (sum_slices), picks each channel's lag on |c| (pick_lag,
+//                   refine_lag) and writes the am_stereo_hit.
 //   pcm_mix         grid-stride: four frames per 16-byte load and four floats per 16-byte store where the pointers allow,
 //                   ragged ends scalar.
 // The kernels read frame t + u for u in [-R, S + R) inside the haystack only (StereoDesc::ulo, uhi), whatever RT is: that
@@ -26,6 +26,7 @@
 // hit_round_trip) and agree bit for bit.
 #include <cmath>
 
+#include "am_hit_device.h"
 #include "am_internal.h"
 
 namespace am {
@@ -35,39 +36,20 @@ namespace {
 constexpr int kStThreads = 256;
 constexpr int kStPer = kHitSlice / kStThreads;   // consecutive needle samples per work item
 constexpr long long kMixMaxBlocks = 1 << 20;     // workgroups of pcm_mix
-static_assert(kStPer == 16, "the LDS layout pads one word per 16 samples: lanes are 17 words apart");
+static_assert(kStPer == 16, "pad16: the LDS layout pads one word per 16 samples");
 static_assert(kSegRadii[2] == AM_STEREO_MAX_RADIUS, "the widest kernel holds every radius");
 static_assert(2 * AM_STEREO_MAX_RADIUS <= kStThreads && stereo_record_len(AM_STEREO_MAX_RADIUS) < kStThreads,
               "one staged tail frame and one record value per work item");
 
-__device__ __forceinline__ int st_pad(int q) { return q + (q >> 4); }
-
-// The 2 RT + 1 sums of one channel over the work item's needle samples nv[0 .. 16), ascending, from the staged samples
-// xs[pad(q0 ..)]; then the workgroup's sums into ws[l][wave].
+// The 2 RT + 1 sums of one channel over the work item's needle samples (lag_dot), then over each wave into ws[l][wave].
 template <int RT>
 __device__ __forceinline__ void st_channel(const float* xs, const float (&nv)[kStPer], int q0, bool active, double (*ws)[kStThreads / 64]) {
-    constexpr int NL = 2 * RT + 1, SPAN = kStPer + 2 * RT;
+    constexpr int NL = 2 * RT + 1;
     double acc[NL];
 #pragma unroll
     for (int l = 0; l < NL; ++l) acc[l] = 0.0;
-    if (active) {
-        double xd[SPAN];
-#pragma unroll
-        for (int j = 0; j < SPAN; ++j) xd[j] = (double)xs[st_pad(q0 + j)];
-#pragma unroll
-        for (int j = 0; j < kStPer; ++j) {
-            const double dn = (double)nv[j];
-#pragma unroll
-            for (int l = 0; l < NL; ++l) acc[l] += xd[j + l] * dn;   // (exact products)
-        }
-    }
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-#pragma unroll
-    for (int l = 0; l < NL; ++l) {
-        double v = acc[l];
-        for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-        if (lane == 0) ws[l][w] = v;
-    }
+    if (active) lag_dot<NL>(xs, nv, q0, acc);
+    wave_sums<kStThreads>(acc, ws);
 }
 
 template <int RT>
@@ -84,7 +66,7 @@ __global__ __launch_bounds__(kStThreads, 2) void stereo_slices_kernel(const Ster
     const int tid = threadIdx.x;
     const int cnt = (int)min((long long)kHitSlice, d.s - i0);
     // every load of the slice in flight at once: frame t + i0 - RT + q for q < cnt + 2 RT (0 where the hit reads no
-    // frame), and the work item's needle samples
+    // frame), and the work item's needle samples.  (stage_load and stage_store written out: one 32-bit load feeds two arrays.)
     const long long u0 = i0 - RT;
     guint* fr = (guint*)d.win;
     unsigned fv[kStPer], ft = 0u;
@@ -110,12 +92,12 @@ __global__ __launch_bounds__(kStThreads, 2) void stereo_slices_kernel(const Ster
     }
 #pragma unroll
     for (int k = 0; k < kStPer; ++k) {
-        const int q = st_pad(tid + k * kStThreads);
+        const int q = pad16(tid + k * kStThreads);
         xl[q] = (float)(short)(fv[k] & 0xffffu);
         xr[q] = (float)(short)(fv[k] >> 16);
     }
     if (tid < 2 * RT) {
-        const int q = st_pad(kHitSlice + tid);
+        const int q = pad16(kHitSlice + tid);
         xl[q] = (float)(short)(ft & 0xffffu);
         xr[q] = (float)(short)(ft >> 16);
     }
@@ -124,64 +106,35 @@ __global__ __launch_bounds__(kStThreads, 2) void stereo_slices_kernel(const Ster
     st_channel<RT>(xl, nv, q0, active, ws);
     st_channel<RT>(xr, nv, q0, active, ws + NL);
     // the energies at lag 0, in integers: the order of an integer sum does not matter
-    long long sll = 0, srr = 0, slr = 0;
+    long long si[3] = {0, 0, 0};   // S_LL, S_RR, S_LR
     if (active) {
 #pragma unroll
         for (int j = 0; j < kStPer; ++j) {
-            const int q = st_pad(q0 + j + RT);
+            const int q = pad16(q0 + j + RT);
             const int a = q0 + j < cnt ? (int)xl[q] : 0, b = q0 + j < cnt ? (int)xr[q] : 0;
-            sll += a * a;     // (|a|, |b| <= 2^15: a product fits an int)
-            srr += b * b;
-            slr += a * b;
+            si[0] += a * a;     // (|a|, |b| <= 2^15: a product fits an int)
+            si[1] += b * b;
+            si[2] += a * b;
         }
     }
-    const int lane = tid & 63, w = tid >> 6;
-    for (int off = 32; off > 0; off >>= 1) {
-        sll += __shfl_xor(sll, off, 64);
-        srr += __shfl_xor(srr, off, 64);
-        slr += __shfl_xor(slr, off, 64);
-    }
-    if (lane == 0) {
-        wi[0][w] = sll;
-        wi[1][w] = srr;
-        wi[2][w] = slr;
-    }
+    wave_sums<kStThreads>(si, wi);
     const int any_bad = __syncthreads_or(bad ? 1 : 0);
     // one 64-bit store per lane: no record leaves as one wide store (tools/check_store_hazard.py)
     const long long p = d.part0 + blockIdx.x;
-    if (tid < 2 * NL) {
-        double t = 0.0;
-        for (int i = 0; i < kStThreads / 64; ++i) t += ws[tid][i];
-        parts[NV * p + tid] = t;
-    } else if (tid < NV) {
-        long long t = 0;
-        for (int i = 0; i < kStThreads / 64; ++i) t += wi[tid - 2 * NL][i];
-        reinterpret_cast<long long*>(parts)[NV * p + tid] = t;
-    } else if (tid == NV) {
-        pflags[p] = (unsigned)any_bad;
-    }
+    if (tid < 2 * NL) parts[NV * p + tid] = add_waves<kStThreads>(ws[tid]);
+    else if (tid < NV) reinterpret_cast<long long*>(parts)[NV * p + tid] = add_waves<kStThreads>(wi[tid - 2 * NL]);
+    else if (tid == NV) pflags[p] = (unsigned)any_bad;
 }
 
-// the best lag of one channel over |c(l)|, l = -r .. r, with its parabola vertex: the rule of seg_combine on |c|
+// the best lag of one channel over |c(l)|, l = -r .. r, with its parabola vertex
 __device__ double st_lag(const double* cc, int r, bool* unrefined) {
-    int ls = 0;   // ties: the smaller |l|, then the negative lag
-    for (int k = 1; k <= r; ++k) {
-        if (fabs(cc[-k]) > fabs(cc[ls])) ls = -k;
-        if (fabs(cc[k]) > fabs(cc[ls])) ls = k;
-    }
-    double lag = (double)ls;
-    *unrefined = true;
-    if (r != 0 && ls != r && ls != -r) {
-        const double a = fabs(cc[ls - 1]), b = fabs(cc[ls]), c = fabs(cc[ls + 1]), den = a - 2.0 * b + c;
-        if (den < 0.0) {
-            *unrefined = false;
-            lag += fmin(fmax(0.5 * (a - c) / den, -0.5), 0.5);
-        }
-    }
+    bool refined;
+    const double lag = refine_lag<true>(cc, r, pick_lag<true>(cc, r), &refined);
+    *unrefined = !refined;
     return lag;
 }
 
-// One wave per hit: lane k adds value k (and k + 64) of the hit's partial records in slice order, lane 0 turns the sums
+// One wave per hit: lane k adds value k (and k + 64) of the hit's partial records (sum_slices), lane 0 turns the sums
 // into the record.
 __global__ __launch_bounds__(64) void stereo_combine_kernel(const StereoDesc* __restrict__ hits, int r, int rt,
                                                             const double* __restrict__ parts, const unsigned* __restrict__ pflags,
@@ -194,19 +147,10 @@ __global__ __launch_bounds__(64) void stereo_combine_kernel(const StereoDesc* __
     const long long ns = (d.s + kHitSlice - 1) / kHitSlice, p0 = d.part0;
     const int nl = 2 * rt + 1, nv = stereo_record_len(rt);
     for (int k = lane; k < nv; k += 64) {
-        if (k < 2 * nl) {
-            double t = 0.0;
-            for (long long i = 0; i < ns; ++i) t += parts[nv * (p0 + i) + k];
-            sh[k] = t;
-        } else {
-            long long t = 0;
-            for (long long i = 0; i < ns; ++i) t += reinterpret_cast<const long long*>(parts)[nv * (p0 + i) + k];
-            si[k - 2 * nl] = t;
-        }
+        if (k < 2 * nl) sh[k] = sum_slices(parts, nv, p0, ns, k);
+        else si[k - 2 * nl] = sum_slices(reinterpret_cast<const long long*>(parts), nv, p0, ns, k);
     }
-    unsigned b = 0;
-    for (long long i = lane; i < ns; i += 64) b |= pflags[p0 + i];
-    const int bad = __syncthreads_or(b != 0 ? 1 : 0);
+    const int bad = __syncthreads_or(or_flags(pflags, p0, ns, lane, 64) != 0 ? 1 : 0);
     if (lane != 0) return;
     const double kk = (double)(1.0f / 65535.0f), k2 = kk * kk;   // k = 2 kappa of norm_downmix
     const double* cl = sh + rt;   // cl[l] = C_L(l), cr[l] = C_R(l) for -rt <= l <= rt
@@ -324,14 +268,13 @@ hipError_t launch_hit_stereo(hipStream_t st, const StereoDesc* d_hits, long long
                              unsigned* pflags, am_stereo_hit* d_out) {
     if (n <= 0) return hipSuccess;
     const int rt = seg_kernel_radius(r);
-    for (long long h0 = 0; h0 < n; h0 += kHitMaxGridY) {   // (more hits than one grid column holds: a few launches)
-        const dim3 grid((unsigned)max_slices, (unsigned)std::min<long long>(kHitMaxGridY, n - h0));
+    const hipError_t e = for_each_grid_y(n, [&](long long h0, unsigned nh) {
+        const dim3 grid((unsigned)max_slices, nh);
         if (rt == kSegRadii[0]) hipLaunchKernelGGL(stereo_slices_kernel<kSegRadii[0]>, grid, dim3(kStThreads), 0, st, d_hits, h0, parts, pflags);
         else if (rt == kSegRadii[1]) hipLaunchKernelGGL(stereo_slices_kernel<kSegRadii[1]>, grid, dim3(kStThreads), 0, st, d_hits, h0, parts, pflags);
         else hipLaunchKernelGGL(stereo_slices_kernel<kSegRadii[2]>, grid, dim3(kStThreads), 0, st, d_hits, h0, parts, pflags);
-        const hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return e;
-    }
+    });
+    if (e != hipSuccess) return e;
     hipLaunchKernelGGL(stereo_combine_kernel, dim3((unsigned)n), dim3(64), 0, st, d_hits, r, rt, (const double*)parts, (const unsigned*)pflags, d_out);
     return hipGetLastError();
 }

@@ -11,13 +11,15 @@
 //   seg_slices     am_segments.hip's slice kernel, unchanged, over a table with one entry per (hit, rate): the entry's
 //                  needle pointer and length are the warped needle's.  Its records carry E_n(q) as well, summed in the
 //                  same slice order as c and E_w.
-//   warp_combine   one workgroup per hit: adds each rate's partials in slice order, forms the Q x (2 R + 1) cells, and one
-//                  thread applies the tie rule, the two vertices and the flags.  (A workgroup of four waves, not one
-//                  wave: a hit has up to 65 x 67 sums of up to S / 4096 partials each, and the sums are what takes time.)
+//   warp_combine   one workgroup per hit: adds each rate's partials (the loop of sum_slices), forms the Q x (2 R + 1)
+//                  cells (ncc_or_floor), and one thread applies the tie rule, the two vertices (parabola_vertex,
+//                  refine_lag) and the flags.  (A workgroup of four waves, not one wave: a hit has up to 65 x 67 sums of
+//                  up to S / 4096 partials each, and the sums are what takes time.)
 // The partial records grow with hits x Q x slices and the warped needles with needles x Q x S: a call runs its hits in
 // rounds that hold at most kWarpRoundBytes of each (one hit and its needle at the least).
 // A hit's record depends on the needle, the samples it reads, the parameters and the floor only; the three forms run in
 // the frame of am_hits.hip (am_internal.h: hit_call, hit_call_batch) and agree bit for bit.
+#include "am_hit_device.h"
 #include "am_internal.h"
 
 namespace am {
@@ -66,23 +68,21 @@ __global__ __launch_bounds__(kWarpCombineThreads) void warp_combine_kernel(const
     for (int it = tid; it < nq * nv; it += kWarpCombineThreads) {
         const int q = it / nv, k = it - q * nv;
         const long long ns = (hd[q].s + kHitSlice - 1) / kHitSlice, p0 = hd[q].part0;
-        double t = 0.0;
+        double t = 0.0;   // (sum_slices<4>, written out: through the helper this kernel takes two more VGPRs)
 #pragma unroll 4
-        for (long long i = 0; i < ns; ++i) t += parts[nv * (p0 + i) + k];   // (slice order)
+        for (long long i = 0; i < ns; ++i) t += parts[nv * (p0 + i) + k];
         sums[it] = t;
     }
     unsigned b = 0;
-    for (int q = 0; q < nq; ++q) {
-        const long long ns = (hd[q].s + kHitSlice - 1) / kHitSlice, p0 = hd[q].part0;
-        for (long long i = tid; i < ns; i += kWarpCombineThreads) b |= pflags[p0 + i];
-    }
+    for (int q = 0; q < nq; ++q) b |= or_flags(pflags, hd[q].part0, (hd[q].s + kHitSlice - 1) / kHitSlice, tid, kWarpCombineThreads);
     const int bad = __syncthreads_or(b != 0 ? 1 : 0);   // (and the sums are visible)
     const double ratio = hd[0].floor_ratio;
     for (int it = tid; it < nq * nc; it += kWarpCombineThreads) {
         const int q = it / nc, l = it - q * nc - r;
         const double* s = sums + q * nv;
         const double c = s[rt + l], ew = s[nl + rt + l], en = s[2 * nl];
-        cell[it] = (en == 0.0 || ew == 0.0 || ew < en * ratio) ? 0.0 : c / sqrt(en * ew);
+        bool below;   // (the cell is 0 either way; the flag is the best cell's, below)
+        cell[it] = en == 0.0 ? 0.0 : ncc_or_floor(c, en, ew, en * ratio, &below);
     }
     __syncthreads();
     if (tid != 0) return;
@@ -121,24 +121,17 @@ __global__ __launch_bounds__(kWarpCombineThreads) void warp_combine_kernel(const
         ncc = gain = 0.0f;
         ldb = ew > 0.0 ? __builtin_inff() : (float)nan;
     } else {
-        if (kk == 0 || qs == 0 || qs == 2 * kk) {
-            flags |= AM_HIT_DRIFT_UNREFINED;
-        } else {
-            const double a = cell[(qs - 1) * nc + r + ls], c = cell[(qs + 1) * nc + r + ls], den = a - 2.0 * best + c;
-            if (!(den < 0.0)) flags |= AM_HIT_DRIFT_UNREFINED;
-            else drift += fmin(fmax(0.5 * (a - c) / den, -0.5), 0.5) * g.step_ppm;
-        }
-        if (r == 0 || ls == r || ls == -r) {
-            flags |= AM_HIT_UNREFINED;
-        } else {
-            const double a = cc[ls - 1], c = cc[ls + 1], den = a - 2.0 * bb + c;
-            if (!(den < 0.0)) flags |= AM_HIT_UNREFINED;
-            else lag += fmin(fmax(0.5 * (a - c) / den, -0.5), 0.5);
-        }
+        bool refined = false;
+        double v = 0.0;
+        if (kk != 0 && qs != 0 && qs != 2 * kk) v = parabola_vertex(cell[(qs - 1) * nc + r + ls], best, cell[(qs + 1) * nc + r + ls], &refined);
+        if (!refined) flags |= AM_HIT_DRIFT_UNREFINED;
+        else drift += v * g.step_ppm;
+        lag = refine_lag<false>(cc, r, ls, &refined);
+        if (!refined) flags |= AM_HIT_UNREFINED;
         if (ew == 0.0 || ew < en * ratio) flags |= AM_HIT_BELOW_FLOOR;
         ncc = (float)best;
         gain = (float)(bb / en);
-        ldb = ew == 0.0 ? -__builtin_inff() : (float)(10.0 * log10(ew / en));
+        ldb = level_db(ew, en);
     }
     o->drift_ppm = drift;
     o->lag = lag;
@@ -155,13 +148,9 @@ __global__ __launch_bounds__(kWarpCombineThreads) void warp_combine_kernel(const
 hipError_t launch_warp_needles(hipStream_t st, const WarpJob* d_jobs, int n_jobs, long long max_len, const float* table) {
     if (n_jobs <= 0 || max_len <= 0) return hipSuccess;
     const unsigned gx = (unsigned)((max_len + kWarpThreads - 1) / kWarpThreads);
-    for (int j0 = 0; j0 < n_jobs; j0 += (int)kHitMaxGridY) {
-        const dim3 grid(gx, (unsigned)std::min<long long>(kHitMaxGridY, n_jobs - j0));
-        hipLaunchKernelGGL(warp_needle_kernel, grid, dim3(kWarpThreads), 0, st, d_jobs, j0, table);
-        hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return e;
-    }
-    return hipSuccess;
+    return for_each_grid_y(n_jobs, [&](long long j0, unsigned nj) {
+        hipLaunchKernelGGL(warp_needle_kernel, dim3(gx, nj), dim3(kWarpThreads), 0, st, d_jobs, (int)j0, table);
+    });
 }
 
 hipError_t launch_warp_combine(hipStream_t st, const SegDesc* tab, long long n, const WarpGrid& grid, const double* parts,
