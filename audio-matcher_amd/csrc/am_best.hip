@@ -471,27 +471,34 @@ int valid_scores(am_needle* h, const Opts& o0, const NormSpec& nrm, float factor
     return AM_OK;
 }
 
-// The score array of one resident haystack (am_internal.h): what am_match_best selects from and am_match_trace reduces.
-// The caller holds the context's lock and has checked the arguments (len >= S).  Synchronous.
-int haystack_scores(am_needle* h, const Opts& o, const void* d_hay, size_t len, int sample_format, int scale, const float** d_scores,
-                    long long* n_scores) {
+// The samples a haystack is correlated as (am_internal.h): the bit-exact down-mix of an i16 stereo haystack into `mono`,
+// and the non-finite runs of the samples (one grid-wide pass: best_scan's transition mode); usually there are none.
+// Synchronous.
+int haystack_prepare(Ctx* c, const void* d_hay, size_t len, int sample_format, DevBuf& mono, HaySamples* hs) {
+    int rc;
+    const float* d_x = static_cast<const float*>(d_hay);
+    if (sample_format == AM_FMT_S16_STEREO) {
+        if ((rc = mono.ensure(len * sizeof(float)))) return rc;
+        AM_HIP(launch_pcm_downmix(c->stream, static_cast<const int16_t*>(d_hay), (long long)len, (float*)mono.p));
+        d_x = (const float*)mono.p;
+    }
+    hs->d_x = d_x;
+    hs->len = len;
+    return best_transitions(c, d_x, (long long)len, hs->trans);
+}
+
+// The Valid scores of prepared samples (len >= S) into the context's best_scores.  Synchronous.
+int prepared_scores(am_needle* h, const Opts& o, const HaySamples& hs, int scale, const float** d_scores, long long* n_scores) {
     Ctx* c = h->ctx;
-    const size_t s = h->n;
+    const size_t s = h->n, len = hs.len;
     int rc;
     const NormSpec nrm = norm_spec(h, o);
     const float factor = nrm.on ? norm_factor(nrm) : scale_factor(h, scale, len);
-    const float* d_x = static_cast<const float*>(d_hay);
-    if (sample_format == AM_FMT_S16_STEREO) {   // the bit-exact down-mix first
-        if ((rc = c->best_mono.ensure(len * sizeof(float)))) return rc;
-        AM_HIP(launch_pcm_downmix(c->stream, static_cast<const int16_t*>(d_hay), (long long)len, (float*)c->best_mono.p));
-        d_x = (const float*)c->best_mono.p;
-    }
+    const float* d_x = hs.d_x;
+    const std::vector<long long>& t = hs.trans;
     const long long n = (long long)(len - s + 1);
     if ((rc = c->best_scores.ensure(sizeof(float) * (size_t)n))) return rc;
     float* d_sc = (float*)c->best_scores.p;
-    // the non-finite runs of the samples (one grid-wide pass: best_scan's transition mode); usually there are none
-    std::vector<long long> t;
-    if ((rc = best_transitions(c, d_x, (long long)len, t))) return rc;
     if (t.empty()) {
         if ((rc = valid_scores(h, o, nrm, factor, d_x, (long long)len, d_sc))) return rc;
     } else {
@@ -508,6 +515,16 @@ int haystack_scores(am_needle* h, const Opts& o, const void* d_hay, size_t len, 
     *d_scores = d_sc;
     *n_scores = n;
     return AM_OK;
+}
+
+// The score array of one resident haystack (am_internal.h): what am_match_best selects from and am_match_trace reduces.
+// The caller holds the context's lock and has checked the arguments (len >= S).  Synchronous.
+int haystack_scores(am_needle* h, const Opts& o, const void* d_hay, size_t len, int sample_format, int scale, const float** d_scores,
+                    long long* n_scores) {
+    HaySamples hs;
+    int rc;
+    if ((rc = haystack_prepare(h->ctx, d_hay, len, sample_format, h->ctx->best_mono, &hs))) return rc;
+    return prepared_scores(h, o, hs, scale, d_scores, n_scores);
 }
 
 // am_match_best on one resident haystack (include/audiomatch.h): its Valid scores (haystack_scores), then best_select.

@@ -113,7 +113,7 @@ int realloc_refused(const char* what, size_t bytes, size_t cap) {
     return fail(AM_ERR_HIP, buf);
 }
 
-static const char* kKernelNames[] = {"k1_cols_fwd", "k2_rows", "k3_cols_inv", "tile_stats", "peaks", "other", "trace"};
+static const char* kKernelNames[] = {"k1_cols_fwd", "k2_rows", "k3_cols_inv", "tile_stats", "peaks", "other", "trace", "discover"};
 static std::mutex g_ctx_mu;
 static std::map<int, Ctx*> g_ctx;
 
@@ -517,6 +517,7 @@ int am_shutdown(void) {
         c->hit_io.release();
         for (DevBuf* b : {&c->sig_span, &c->sig_scores, &c->sig_psum, &c->sig_pmax, &c->sig_mean, &c->sig_hmax}) b->release();
         for (DevBuf* b : {&c->best_stats, &c->best_lmax, &c->best_ctl, &c->best_trans, &c->best_list, &c->best_scores, &c->best_mono, &c->trace_out, &c->trace_parts}) b->release();
+        for (DevBuf* b : {&c->disc_a, &c->disc_probe, &c->disc_energy, &c->disc_parts, &c->disc_out}) b->release();
         for (auto& kv : c->rs_taps) kv.second.release();
         c->rs_taps.clear();
         c->lag_parts.release(); c->lag_r.release();

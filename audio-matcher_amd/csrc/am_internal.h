@@ -135,7 +135,7 @@ struct Plan {
 struct ScoreSide { DevBuf scores, stats, stats32, wflags, peaks, work; };
 
 struct ProfRec { int name; hipEvent_t e0, e1; };
-enum { KN_K1 = 0, KN_K2, KN_K3, KN_STATS, KN_PEAKS, KN_OTHER, KN_TRACE, KN_COUNT };
+enum { KN_K1 = 0, KN_K2, KN_K3, KN_STATS, KN_PEAKS, KN_OTHER, KN_TRACE, KN_DISCOVER, KN_COUNT };
 
 struct Ctx {
     int device = -1;
@@ -186,6 +186,9 @@ struct Ctx {
     // transitions, the candidate list; the score array and the down-mixed haystack of am_match_best
     DevBuf best_stats, best_lmax, best_ctl, best_trans, best_list, best_scores, best_mono;
     DevBuf trace_out, trace_parts;   // score traces (am_trace.hip): a call's records and, in the sliced form, the slices' partials
+    // needle discovery (am_discover.hip): recording A down-mixed, the probe being matched, the energy parts, the slices'
+    // partials and a call's records
+    DevBuf disc_a, disc_probe, disc_energy, disc_parts, disc_out;
     // the chunk list currently resident in `segs` (re-uploaded only when it changes)
     std::vector<Segment> segs_resident;
     // profiling
@@ -642,6 +645,12 @@ int best_select(Ctx* c, const float* d_g, long long n, float min_prom, long long
 // a non-finite sample scores NaN, every finite stretch of at least S samples is correlated on its own.  *n = len - S + 1.
 int haystack_scores(am_needle* h, const Opts& o, const void* d_hay, size_t len, int sample_format, int scale, const float** d_scores,
                     long long* n);
+// ... in its two steps, for a caller that scores one haystack against many needles (am_discover.hip): the samples the
+// haystack is correlated as (an i16 stereo haystack down-mixed into `mono`) with their non-finite runs, once; then the
+// scores of one needle over them
+struct HaySamples { const float* d_x = nullptr; size_t len = 0; std::vector<long long> trans; };
+int haystack_prepare(Ctx* c, const void* d_hay, size_t len, int sample_format, DevBuf& mono, HaySamples* hs);
+int prepared_scores(am_needle* h, const Opts& o, const HaySamples& hs, int scale, const float** d_scores, long long* n);
 int match_best_one(am_needle* h, const void* d_hay, size_t len, int sample_format, const am_best_params* bp, am_peak* out,
                    size_t* n_out);
 // ---- am_trace.hip ----

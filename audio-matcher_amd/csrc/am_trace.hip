@@ -18,6 +18,7 @@
 // trace_finish folds a bin's partials in ascending slice order, one wave per bin.  Which form runs is decided by D
 // alone (D <= AM_TRACE_WAVE_BIN_MAX: the wave form), or by the debug option "trace_form".
 #include "am_internal.h"
+#include "am_wave_steps.h"
 
 #include <climits>
 
@@ -52,14 +53,13 @@ __device__ __forceinline__ double shfl_xor_f64(double v, int mask) {
 // Every lane of the wave must be here.  The record is complete in every lane.
 __device__ __forceinline__ am_trace_bin trace_span(const float* __restrict__ p, int len, unsigned off0) {
     const int lane = threadIdx.x & 63;
-    const int a = (int)((reinterpret_cast<uintptr_t>(p) >> 2) & 3);
-    const float* __restrict__ base = p - a;     // 16-byte aligned; floats before p are never read
+    const int a = wave_align(p);
     double s[4] = {0.0, 0.0, 0.0, 0.0}, q[4] = {0.0, 0.0, 0.0, 0.0};
     float mx = 0.0f, mn = 0.0f;
     unsigned omx = kTraceNone, omn = kTraceNone, cnt = 0u;
-    const int end = a + len;                    // floats of `base` the span ends at
-    // the lane's four floats of the step at f0 into its accumulators, in ascending offset
-    auto take = [&](int f0, const float (&v)[4]) {
+    // the lane's four floats of a step into its accumulators, in ascending offset; the order in which a class adds its
+    // scores is the order of the steps (wave_steps, am_wave_steps.h)
+    wave_steps(p, len, [&](int f0, const float (&v)[4]) {
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             const float x = v[i];
@@ -74,35 +74,7 @@ __device__ __forceinline__ am_trace_bin trace_span(const float* __restrict__ p, 
                 if (omn == kTraceNone || x < mn) { mn = x; omn = o; }
             }
         }
-    };
-    // one step with its ragged ends guarded
-    auto step = [&](int f0) {
-        float v[4];
-        if (f0 >= a && f0 + 4 <= end) {
-            const float4 w = *reinterpret_cast<const float4*>(base + f0);
-            v[0] = w.x; v[1] = w.y; v[2] = w.z; v[3] = w.w;
-        } else {
-#pragma unroll
-            for (int i = 0; i < 4; ++i) v[i] = (f0 + i >= a && f0 + i < end) ? base[f0 + i] : __uint_as_float(0x7FC00000u);
-        }
-        take(f0, v);
-    };
-    // The first step (its head may be ragged), then four whole steps at a time with their loads in flight together
-    // (one load per wave in flight leaves the kernel waiting for memory latency), then what is left.  The order in
-    // which a class adds its scores is the order of the steps either way.
-    int f0 = 4 * lane;
-    if (f0 < end) { step(f0); f0 += 256; }
-    for (; f0 + 3 * 256 + 4 <= end; f0 += 4 * 256) {
-        float4 w[4];
-#pragma unroll
-        for (int k = 0; k < 4; ++k) w[k] = *reinterpret_cast<const float4*>(base + f0 + 256 * k);
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            const float v[4] = {w[k].x, w[k].y, w[k].z, w[k].w};
-            take(f0 + 256 * k, v);
-        }
-    }
-    for (; f0 < end; f0 += 256) step(f0);
+    });
     // the rotation: lane l, place i takes class 4l + i, which sits a places further on
     if (a) {
         double rs[4], rq[4];

@@ -101,6 +101,11 @@ struct Arguments {
     std::optional<std::uint64_t> best;        // extension: --best N, the N best hits per main file, no prominence threshold (am_match_best)
     std::string trace_prefix;                 // extension: --score-trace PREFIX[:BIN], the score curve of each main file (am_match_trace) as PREFIX<file index>[_<snippet index>].csv; empty = off
     std::uint64_t trace_bin_ms = 1000;        // ... one line per BIN of scores (a duration, default 1 s)
+    std::optional<std::uint64_t> discover_ms; // extension: --discover DUR[:HOP], no snippet: what the first FILE shares with itself and with every further FILE (am_discover)
+    std::uint64_t discover_hop_ms = 0;        // ... the hop between probes (default DUR / 2)
+    float discover_min_ncc = 0.6f;            // ... --discover-min-ncc X: what a probe must score to count
+    bool discover_min_ncc_set = false;
+    std::string discover_out;                 // ... --discover-out PREFIX: each region's samples of the first FILE as PREFIX<file index>_<a_start>.wav; empty = off
     bool live = false;                        // extension: --live, raw PCM from stdin through a monitor (am_monitor_*)
     std::uint32_t rate = 0;                   // --live: --rate R (samples per second of the stream)
     std::string encoding = "s16le";           // --live: --encoding s16le | f32le
@@ -212,6 +217,20 @@ inline const char* usage_text() {
            "                         one line 'Trace: max V at hh:mm:ss.mmm, bin maxima median V mad V, peak z V'.  The\n"
            "                         scores are those that were matched: --normalize, --resample, --whiten / --preemphasis\n"
            "                         and --mix apply.  Not with --live\n"
+           "  --discover DUR[:HOP]   no --snippet: find what the first FILE shares with itself and with every further FILE\n"
+           "                         (am_discover): probes of DUR (a duration) every HOP (default DUR/2) of the first FILE\n"
+           "                         are matched under NCC, and probes that agree on one displacement (within HOP/8, at\n"
+           "                         least 2 of them, gaps of 1 bridged, probes 40 dB below the file's level skipped) form\n"
+           "                         a region; one line per region: 'Region: hh:mm:ss.mmm +LENGTHs -> FILE hh:mm:ss.mmm,\n"
+           "                         ncc mean V min V, G/N probes'.  A repeat inside the first FILE is reported once.  No\n"
+           "                         label file is written.  Not with --snippet, --live, --best, --score-trace or any\n"
+           "                         per-hit option; --resample, --whiten, --preemphasis, --distance, --chunk-size, --out,\n"
+           "                         --dry-run and --skip-existing do not apply (an error); --normalize is what discovery\n"
+           "                         does anyway, --prominence has nothing to act on; --mix and --normalize-floor apply\n"
+           "  --discover-min-ncc X   with --discover: the NCC a probe must reach to count (default 0.6)\n"
+           "  --discover-out PREFIX  with --discover: write the first FILE's samples of each region as\n"
+           "                         PREFIX<file index>_<start sample>.wav (file index 0: the first FILE against itself),\n"
+           "                         usable as --snippet as they are\n"
            "  --live                 read raw PCM from stdin instead of files (no FILE arguments): a live feed, matched\n"
            "                         as it arrives; each hit's offset line is printed (and flushed) as soon as it is\n"
            "                         final -- a hit is final once the next hit is found, or once --distance of audio\n"
@@ -444,6 +463,29 @@ inline Arguments parse_arguments(int argc, const char* const* argv) {
             if (a.trace_prefix.empty() || a.trace_bin_ms == 0)
                 throw ArgError("invalid value '" + v + "' for --score-trace (PREFIX[:BIN], a file name prefix and a duration longer than 0)");
         }
+        else if (s == "--discover") {
+            const std::string v = need(i);
+            const auto colon = v.find(':');
+            const auto d = parse_duration_ms(v.substr(0, colon));
+            const auto h = colon == std::string::npos ? std::optional<std::uint64_t>(d ? *d / 2 : 0) : parse_duration_ms(v.substr(colon + 1));
+            if (!d || !h || *d == 0 || *h == 0)
+                throw ArgError("invalid value '" + v + "' for --discover (DUR[:HOP], two durations longer than 0)");
+            a.discover_ms = *d;
+            a.discover_hop_ms = *h;
+        }
+        else if (s == "--discover-min-ncc") {
+            const std::string v = need(i);
+            char* end = nullptr;
+            const float x = std::strtof(v.c_str(), &end);
+            if (v.empty() || *end || !(x >= -1.0f && x <= 1.0f))
+                throw ArgError("invalid value '" + v + "' for --discover-min-ncc (a number in -1 .. 1)");
+            a.discover_min_ncc = x;
+            a.discover_min_ncc_set = true;
+        }
+        else if (s == "--discover-out") {
+            a.discover_out = need(i);
+            if (a.discover_out.empty()) throw ArgError("invalid value '' for --discover-out (a file name prefix)");
+        }
         else if (s == "--live") a.live = true;
         else if (s == "--rate") {
             const std::string v = need(i);
@@ -466,6 +508,29 @@ inline Arguments parse_arguments(int argc, const char* const* argv) {
         else if (!s.empty() && s[0] == '-' && s != "-") throw ArgError("unknown option " + s);
         else if (!s.empty()) a.within.push_back(s);
     }
+    if (a.discover_ms) {
+        // (no needle in this mode: nothing that takes one, or the hits of one, applies)
+        const std::pair<bool, const char*> others[] = {
+            {!a.snippet.empty(), "--snippet"}, {a.live, "--live"}, {a.best.has_value(), "--best"}, {!a.trace_prefix.empty(), "--score-trace"},
+            {a.min_confidence.has_value(), "--min-confidence"}, {a.segments != 0, "--segments"}, {a.bands != 0, "--bands"},
+            {a.warp_ppm.has_value(), "--warp"}, {a.channel_radius.has_value(), "--channel"}, {!a.residual_prefix.empty(), "--residual"},
+            {a.stereo_radius.has_value(), "--stereo"}, {a.min_significance.has_value(), "--min-significance"},
+            {a.significance_zone_ms.has_value(), "--significance-zone"}, {!a.learn_needle.empty(), "--learn-needle"}};
+        for (const auto& o : others)
+            if (o.first) throw ArgError(std::string("--discover and ") + o.second + " are mutually exclusive");
+        // ... and what would be ignored without a word (--normalize is what discovery does anyway; --mix and
+        // --normalize-floor apply)
+        const std::pair<bool, const char*> ignored[] = {
+            {a.resample, "--resample"}, {a.whiten != 0, "--whiten"}, {a.preemphasis.has_value(), "--preemphasis"},
+            {a.learn_margin_ms.has_value(), "--learn-margin"}, {a.out_file.has_value(), "--out"}, {a.distance_ms.has_value(), "--distance"},
+            {a.chunk_ms.has_value(), "--chunk-size"}, {a.dry_run, "--dry-run"}, {a.skip_existing, "--skip-existing"}};
+        for (const auto& o : ignored)
+            if (o.first) throw ArgError(std::string("--discover: ") + o.second + " does not apply");
+        if (a.within.empty()) throw ArgError("--discover needs at least one FILE");
+        return a;
+    }
+    if (a.discover_min_ncc_set) throw ArgError("--discover-min-ncc needs --discover");
+    if (!a.discover_out.empty()) throw ArgError("--discover-out needs --discover");
     if (a.snippet.empty()) throw ArgError("--snippet <FILE> is required");
     if (a.whiten && a.preemphasis) throw ArgError("--whiten and --preemphasis are mutually exclusive");
     if (a.learn_margin_ms && a.learn_needle.empty()) throw ArgError("--learn-margin needs --learn-needle");

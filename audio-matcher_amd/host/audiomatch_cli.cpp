@@ -649,6 +649,77 @@ static int run_files(const Arguments& args) {
     return rc_all;
 }
 
+// extension: --discover DUR[:HOP].  No snippet: the first FILE is searched against itself (AM_DISCOVER_SELF, exclude = the
+// probe length, AM_REGION_FOLD) and then against every further FILE; one line per region, and with --discover-out the
+// region's samples of the first FILE as a WAV file.  The region settings other than --discover-min-ncc are fixed:
+// tolerance HOP / 8, at least 2 good probes, gaps of 1 bridged, probes 40 dB below the file's level skipped.
+static int run_discover(const Arguments& args) {
+    if (args.normalize_floor_db && am_set_option("score_norm_floor_db", *args.normalize_floor_db) != AM_OK)
+        throw std::runtime_error(std::string("--normalize-floor: ") + am_last_error_string());
+    const Pcm a_pcm = read_wav(args.within[0]);
+    const std::uint32_t sr = a_pcm.sample_rate;
+    const std::vector<float> a = to_mono_f32(args, a_pcm, args.within[0]);
+    am_discover_params dp{};
+    dp.probe_len = std::max<std::uint64_t>(1, round_samples_ms(*args.discover_ms, sr));
+    dp.hop = std::max<std::uint64_t>(1, round_samples_ms(args.discover_hop_ms, sr));
+    dp.min_level_db = 40.0f;
+    am_region_params rp{};
+    rp.min_ncc = args.discover_min_ncc;
+    rp.tolerance = dp.hop / 8;
+    rp.min_good = 2;
+    rp.max_gap = 1;
+    auto stamp = [&](std::uint64_t sample) {
+        const std::uint64_t ms = (std::uint64_t)((double)sample * 1000.0 / (double)sr);
+        char buf[64];
+        std::snprintf(buf, sizeof buf, "%02" PRIu64 ":%02" PRIu64 ":%02" PRIu64 ".%03" PRIu64, ms / 3600000, (ms / 60000) % 60, (ms / 1000) % 60, ms % 1000);
+        return std::string(buf);
+    };
+    int rc_all = 0;
+    for (size_t file_index = 0; file_index < args.within.size(); ++file_index) {
+        const bool self = file_index == 0;
+        std::vector<float> b_own;
+        if (!self) {
+            const Pcm b_pcm = read_wav(args.within[file_index]);
+            if (b_pcm.sample_rate != sr) {
+                std::fprintf(stderr, "sample rate of '%s' (%u) and '%s' (%u) don't match\n", args.within[file_index].c_str(), b_pcm.sample_rate,
+                             args.within[0].c_str(), sr);
+                return 3;
+            }
+            b_own = to_mono_f32(args, b_pcm, args.within[file_index]);
+        }
+        const std::vector<float>& b = self ? a : b_own;
+        dp.flags = self ? AM_DISCOVER_SELF : 0u;
+        dp.exclude = self ? dp.probe_len : 0;
+        rp.flags = self ? AM_REGION_FOLD : 0u;
+        size_t np = 0, got = 0, nr = 0;
+        if (am_discover_len(a.size(), &dp, &np) != AM_OK) throw std::runtime_error(std::string("am_discover_len: ") + am_last_error_string());
+        std::vector<am_probe_hit> hits(np);
+        if (am_discover(args.device, a.data(), a.size(), b.data(), b.size(), AM_FMT_F32_MONO, &dp, hits.data(), hits.size(), &got) != AM_OK)
+            throw std::runtime_error(std::string("am_discover: ") + am_last_error_string());
+        std::vector<am_region> regions(np);
+        if (am_discover_regions(hits.data(), hits.size(), &dp, &rp, regions.data(), regions.size(), &nr) != AM_OK)
+            throw std::runtime_error(std::string("am_discover_regions: ") + am_last_error_string());
+        regions.resize(nr);
+        for (const am_region& r : regions) {
+            if (args.verbosity >= 1)
+                std::printf("Region: %s +%.3fs -> %s %s, ncc mean %.3f min %.3f, %u/%u probes\n", stamp(r.a_start).c_str(),
+                            (double)r.length / (double)sr, args.within[file_index].c_str(),
+                            stamp((std::uint64_t)((std::int64_t)r.a_start + r.displacement)).c_str(), r.mean_ncc, (double)r.min_ncc, r.good, r.count);
+            if (!args.discover_out.empty()) {
+                const std::string path = args.discover_out + std::to_string(file_index) + "_" + std::to_string(r.a_start) + ".wav";
+                const std::vector<float> cut(a.begin() + (std::ptrdiff_t)r.a_start, a.begin() + (std::ptrdiff_t)(r.a_start + r.length));
+                try {
+                    write_wav_f32(path, cut, sr);
+                } catch (const std::exception& e) {
+                    std::fprintf(stderr, "%s\n", e.what());
+                    rc_all = 4;
+                }
+            }
+        }
+    }
+    return rc_all;
+}
+
 // extension: --live.  Raw PCM from stdin through one monitor (am_monitor_*, all snippets in it): every chunk of input is
 // turned into the f32 mono samples the file mode would have made of the same frames (to_mono_f32), pushed, and the hits
 // that became final are printed at once, numbered per snippet as the file mode numbers them.  At end of input the
@@ -777,7 +848,7 @@ int main(int argc, char** argv) {
         return 0;
     }
     try {
-        return args.live ? run_live(args) : run_files(args);
+        return args.discover_ms ? run_discover(args) : args.live ? run_live(args) : run_files(args);
     } catch (const std::exception& e) {
         std::fprintf(stderr, "error: %s\n", e.what());
         return 1;

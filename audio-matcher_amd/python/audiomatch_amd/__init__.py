@@ -244,6 +244,25 @@ TRACE_BIN_DTYPE = np.dtype([("max", "<f4"), ("min", "<f4"), ("argmax", "<u4"), (
 AM_TRACE_WAVE_BIN_MAX, AM_TRACE_SLICE, AM_TRACE_MAX_BIN = 2048, 8192, 1 << 30
 
 
+class AmDiscoverParams(C.Structure):   # am_discover_params (include/audiomatch.h, needle discovery)
+    _fields_ = [("probe_len", C.c_uint64), ("hop", C.c_uint64), ("exclude", C.c_uint64), ("separation", C.c_uint64),
+                ("min_level_db", C.c_float), ("flags", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class AmRegionParams(C.Structure):     # am_region_params
+    _fields_ = [("min_ncc", C.c_float), ("max_second", C.c_float), ("tolerance", C.c_uint64), ("min_good", C.c_uint32),
+                ("max_gap", C.c_uint32), ("flags", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+# am_probe_hit (40 bytes) and am_region (56 bytes) as numpy structured dtypes: what the discovery calls return arrays of
+PROBE_HIT_DTYPE = np.dtype([("probe", "<u8"), ("best", "<u8"), ("second", "<u8"), ("ncc", "<f4"), ("ncc_second", "<f4"),
+                            ("flags", "<u4"), ("reserved", "<u4")])
+REGION_DTYPE = np.dtype([("a_start", "<u8"), ("length", "<u8"), ("displacement", "<i8"), ("first", "<u8"), ("count", "<u4"),
+                         ("good", "<u4"), ("mean_ncc", "<f8"), ("min_ncc", "<f4"), ("worst_second", "<f4")])
+AM_DISCOVER_SELF, AM_REGION_FOLD, AM_DISCOVER_SLICE = 1, 1, 8192
+AM_PROBE_NO_BEST, AM_PROBE_NO_SECOND, AM_PROBE_NONFINITE, AM_PROBE_QUIET = 1, 2, 4, 8
+
+
 class AmMonitorInfo(C.Structure):  # am_monitor_info (include/audiomatch.h, live monitoring)
     _fields_ = [("received", C.c_uint64), ("horizon", C.c_uint64), ("resident_bytes", C.c_uint64), ("pending", C.c_uint64)]
 
@@ -481,6 +500,15 @@ _SIGNATURES = {
     "am_trace_summary": (C.c_int, [C.c_void_p, C.c_size_t, C.c_uint64, C.POINTER(AmTraceStats)]),
     "am_find_peaks_top_device": (C.c_int, [C.c_int, C.c_void_p, C.c_size_t, C.c_float, C.c_uint64, C.c_size_t,
                                            C.POINTER(AmPeak), C.POINTER(C.c_size_t)]),
+    "am_discover_len": (C.c_int, [C.c_size_t, C.POINTER(AmDiscoverParams), C.POINTER(C.c_size_t)]),
+    "am_discover": (C.c_int, [C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_int, C.POINTER(AmDiscoverParams),
+                              C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "am_discover_device": (C.c_int, [C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_int,
+                                     C.POINTER(AmDiscoverParams), C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "am_probe_scores": (C.c_int, [C.c_int, C.c_void_p, C.c_size_t, C.c_uint64, C.c_uint64, C.c_uint64, C.c_void_p]),
+    "am_probe_scores_device": (C.c_int, [C.c_int, C.c_void_p, C.c_size_t, C.c_uint64, C.c_uint64, C.c_uint64, C.c_void_p]),
+    "am_discover_regions": (C.c_int, [C.c_void_p, C.c_size_t, C.POINTER(AmDiscoverParams), C.POINTER(AmRegionParams),
+                                      C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]),
     "am_get_option": (C.c_int, [C.c_char_p, C.POINTER(C.c_longlong)]),
 }
 
@@ -915,6 +943,81 @@ def trace_summary(bins, bin: int) -> AmTraceStats:
     st = AmTraceStats()
     _check(lib().am_trace_summary(a.ctypes.data if a.size else None, a.size, int(bin), C.byref(st)))
     return st
+
+
+def discover_params(probe_len: int, hop: int, exclude: int = 0, separation: int = 0, min_level_db: float = 40.0,
+                    flags: int = 0) -> AmDiscoverParams:
+    """am_discover_params (flags: AM_DISCOVER_SELF; separation 0 = probe_len)."""
+    return AmDiscoverParams(probe_len=int(probe_len), hop=int(hop), exclude=int(exclude), separation=int(separation),
+                            min_level_db=float(min_level_db), flags=int(flags), reserved=0)
+
+
+def region_params(min_ncc: float, tolerance: int, min_good: int = 2, max_gap: int = 1, max_second: float = 0.0,
+                  flags: int = 0) -> AmRegionParams:
+    """am_region_params (flags: AM_REGION_FOLD, only for records of an AM_DISCOVER_SELF search)."""
+    return AmRegionParams(min_ncc=float(min_ncc), max_second=float(max_second), tolerance=int(tolerance),
+                          min_good=int(min_good), max_gap=int(max_gap), flags=int(flags), reserved=0)
+
+
+def discover_len(len_a: int, params: AmDiscoverParams) -> int:
+    """am_discover_len: the probes a recording of len_a samples has (pure host)."""
+    n = C.c_size_t(0)
+    _check(lib().am_discover_len(int(len_a), C.byref(params), C.byref(n)))
+    return n.value
+
+
+def _discover_call(fn, len_a: int, params: AmDiscoverParams, cap):
+    cap = discover_len(len_a, params) if cap is None else int(cap)
+    out = np.zeros(max(1, cap), dtype=PROBE_HIT_DTYPE)
+    n = C.c_size_t(0)
+    _check(fn(out.ctypes.data, cap, C.byref(n)))
+    return out[:min(n.value, cap)]
+
+
+def discover(a, b, params: AmDiscoverParams, device: int = 0, cap=None):
+    """am_discover: one PROBE_HIT_DTYPE record per probe of recording `a` matched against recording `b` (both f32
+    arrays, or both i16 (frames, 2) arrays of interleaved stereo); pass b = a with AM_DISCOVER_SELF for a self search."""
+    xa, fa, la = _samples(a)
+    xb, fb, lb = _samples(b)
+    if fa != fb:
+        raise ValueError("discover: both recordings must have one sample format")
+    return _discover_call(lambda o, c, n: lib().am_discover(device, xa.ctypes.data, la, xb.ctypes.data, lb, int(fa), C.byref(params),
+                                                            o, c, n), la, params, cap)
+
+
+def discover_device(device: int, ptr_a: int, len_a: int, ptr_b: int, len_b: int, params: AmDiscoverParams,
+                    fmt: int = Fmt.F32_MONO, cap=None):
+    """am_discover_device: the same on recordings resident on `device`."""
+    return _discover_call(lambda o, c, n: lib().am_discover_device(device, ptr_a, int(len_a), ptr_b, int(len_b), int(fmt),
+                                                                   C.byref(params), o, c, n), len_a, params, cap)
+
+
+def probe_scores(y_data, ex_lo: int, ex_hi: int, separation: int, device: int = 0):
+    """am_probe_scores: the record rule of discovery on the host score array y_data -- the best candidate outside
+    [ex_lo, ex_hi) and the largest one at least `separation` away from it (one PROBE_HIT_DTYPE record)."""
+    a = np.ascontiguousarray(y_data, dtype=np.float32)
+    out = np.zeros(1, dtype=PROBE_HIT_DTYPE)
+    _check(lib().am_probe_scores(device, a.ctypes.data if a.size else None, a.size, int(ex_lo), int(ex_hi), int(separation),
+                                 out.ctypes.data))
+    return out[0]
+
+
+def probe_scores_device(device: int, ptr: int, n: int, ex_lo: int, ex_hi: int, separation: int):
+    """am_probe_scores_device: the same on n f32 scores resident on `device` (any 4-byte alignment)."""
+    out = np.zeros(1, dtype=PROBE_HIT_DTYPE)
+    _check(lib().am_probe_scores_device(device, ptr, int(n), int(ex_lo), int(ex_hi), int(separation), out.ctypes.data))
+    return out[0]
+
+
+def discover_regions(hits, params: AmDiscoverParams, rparams: AmRegionParams, cap=None):
+    """am_discover_regions: the regions (REGION_DTYPE) the probes' records chain into (pure host)."""
+    h = np.ascontiguousarray(hits, dtype=PROBE_HIT_DTYPE)
+    cap = h.size if cap is None else int(cap)
+    out = np.zeros(max(1, cap), dtype=REGION_DTYPE)
+    n = C.c_size_t(0)
+    _check(lib().am_discover_regions(h.ctypes.data if h.size else None, h.size, C.byref(params), C.byref(rparams),
+                                     out.ctypes.data, cap, C.byref(n)))
+    return out[:min(n.value, cap)]
 
 
 def best_params(k: int, min_distance: int = 0, min_prominence: float = 0.0, scale=Scale.LIB) -> AmBestParams:

@@ -300,6 +300,64 @@ pub struct AmTraceStats {
     pub mad_max: f64,
     pub peak_z: f64,
 }
+/// am_probe_hit: one probe of a discovery (am_discover*, am_probe_scores*), 40 bytes
+#[repr(C)]
+#[derive(Clone, Copy, Default, Debug)]
+pub struct AmProbeHit {
+    pub probe: u64,
+    pub best: u64,
+    pub second: u64,
+    pub ncc: f32,
+    pub ncc_second: f32,
+    pub flags: u32,
+    pub reserved: u32,
+}
+/// am_discover_params: probe length and hop (at least 1), the exclusion of a self search, the runner-up's least
+/// distance (0 = probe_len), the level rule, AM_DISCOVER_SELF; reserved = 0
+#[repr(C)]
+#[derive(Clone, Copy, Default, Debug)]
+pub struct AmDiscoverParams {
+    pub probe_len: u64,
+    pub hop: u64,
+    pub exclude: u64,
+    pub separation: u64,
+    pub min_level_db: f32,
+    pub flags: u32,
+    pub reserved: u32,
+}
+/// am_region_params: the region rule of am_discover_regions; reserved = 0
+#[repr(C)]
+#[derive(Clone, Copy, Default, Debug)]
+pub struct AmRegionParams {
+    pub min_ncc: f32,
+    pub max_second: f32,
+    pub tolerance: u64,
+    pub min_good: u32,
+    pub max_gap: u32,
+    pub flags: u32,
+    pub reserved: u32,
+}
+/// am_region: one region two recordings share, 56 bytes
+#[repr(C)]
+#[derive(Clone, Copy, Default, Debug)]
+pub struct AmRegion {
+    pub a_start: u64,
+    pub length: u64,
+    pub displacement: i64,
+    pub first: u64,
+    pub count: u32,
+    pub good: u32,
+    pub mean_ncc: f64,
+    pub min_ncc: f32,
+    pub worst_second: f32,
+}
+pub const AM_DISCOVER_SELF: u32 = 1;
+pub const AM_REGION_FOLD: u32 = 1;
+pub const AM_PROBE_NO_BEST: u32 = 1;
+pub const AM_PROBE_NO_SECOND: u32 = 2;
+pub const AM_PROBE_NONFINITE: u32 = 4;
+pub const AM_PROBE_QUIET: u32 = 8;
+pub const AM_DISCOVER_SLICE: u64 = 8192;
 pub const AM_TRACE_WAVE_BIN_MAX: u64 = 2048;
 pub const AM_TRACE_SLICE: u64 = 8192;
 pub const AM_TRACE_MAX_BIN: u64 = 1 << 30;
@@ -599,6 +657,26 @@ extern "C" {
         tp: *const AmTraceParams, out: *mut AmTraceBin, cap_per_hay: usize, n_out: *mut usize,
     ) -> c_int;
     pub fn am_trace_summary(bins: *const AmTraceBin, n_bins: usize, bin: u64, out: *mut AmTraceStats) -> c_int;
+    /// needle discovery: probes of recording A matched against recording B, one record per probe (audiomatch.h)
+    pub fn am_discover_len(len_a: usize, dp: *const AmDiscoverParams, n_probes: *mut usize) -> c_int;
+    pub fn am_discover_device(
+        device: c_int, d_a: *const std::ffi::c_void, len_a: usize, d_b: *const std::ffi::c_void, len_b: usize, sample_format: c_int,
+        dp: *const AmDiscoverParams, out: *mut AmProbeHit, cap: usize, n_out: *mut usize,
+    ) -> c_int;
+    pub fn am_discover(
+        device: c_int, a: *const std::ffi::c_void, len_a: usize, b: *const std::ffi::c_void, len_b: usize, sample_format: c_int,
+        dp: *const AmDiscoverParams, out: *mut AmProbeHit, cap: usize, n_out: *mut usize,
+    ) -> c_int;
+    pub fn am_probe_scores(
+        device: c_int, scores: *const f32, n: usize, ex_lo: u64, ex_hi: u64, separation: u64, out: *mut AmProbeHit,
+    ) -> c_int;
+    pub fn am_probe_scores_device(
+        device: c_int, d_scores: *const f32, n: usize, ex_lo: u64, ex_hi: u64, separation: u64, out: *mut AmProbeHit,
+    ) -> c_int;
+    pub fn am_discover_regions(
+        hits: *const AmProbeHit, n: usize, dp: *const AmDiscoverParams, rp: *const AmRegionParams, out: *mut AmRegion, cap: usize,
+        n_out: *mut usize,
+    ) -> c_int;
     /// calc_chunks on the lazy sample iterator (audio_matcher.rs:88-104, mp3_reader.rs:13-41)
     pub fn am_match_stream_begin(
         h: *const AmNeedle, sample_format: c_int, expected_len: usize, p: *const AmMatchParams, out: *mut *mut AmStream,

@@ -612,6 +612,119 @@ int am_match_trace_batch_device(const am_needle* h, const void* const* d_haystac
                                 size_t* n_out);
 int am_trace_summary(const am_trace_bin* bins, size_t n_bins, uint64_t bin, am_trace_stats* out);
 
+/* ---- needle discovery ----------------------------------------------------------------------------------------------
+ * "What do these two recordings share?" when nobody has cut a needle yet ("When there is no needle
+ * yet"): probes cut from recording A at a fixed hop are matched against recording B, one record per probe says where
+ * in B it scores best and how far ahead of its runner-up, and am_discover_regions (pure host) chains the probes that
+ * agree on one displacement into regions.  A region's samples of A are a needle.
+ *
+ * Recordings.  A has len_a samples, B has len_b, both in sample_format (AM_FMT_F32_MONO, or AM_FMT_S16_STEREO with the
+ * bit-exact down-mix of am_pcm16_downmix, done once per recording per call).
+ *
+ * Probes.  L = probe_len, H = hop.  Probe i is A[p_i, p_i + L), p_i = i H, i = 0 .. P - 1, P = (len_a - L) / H + 1, and
+ * P = 0 when len_a < L (AM_OK, no records, as am_match_trace for len < S).  am_discover_len returns P.
+ *
+ * Scores of a probe: r_i[0, n), n = len_b - L + 1 -- exactly the array am_match_trace reduces for a needle created with
+ * am_needle_create_device from the probe's (down-mixed) samples, with "score_norm" = 1 and AM_SCALE_LIB.  Discovery is
+ * always NCC, whatever the process default of "score_norm" is; "score_norm_floor_db", "log_n" and "half_pipeline"
+ * apply as they do to such a needle, the half-precision redo included.  A window of B that holds a non-finite sample
+ * scores NaN.  len_b < L: n = 0, no probe has a candidate.
+ *
+ * Candidates of probe i: the offsets j in [0, n) whose score is not NaN and which are not excluded.  With flag
+ * AM_DISCOVER_SELF the offsets p_i - exclude < j < p_i + exclude are excluded: the probe's own place and its overlap
+ * (by position; pointers are never compared).  Without the flag `exclude` must be 0.
+ *
+ * Record of a probe (am_probe_hit).  best: the largest candidate, ties (==, so -0.0 and +0.0 tie) to the lowest
+ * offset.  second: the largest candidate with |j - best| >= separation, the same tie rule; separation = 0 means L.
+ * +-inf are scores like any other.  No candidate: AM_PROBE_NO_BEST | AM_PROBE_NO_SECOND, offsets 0, NaN scores.  A best
+ * but no runner-up: AM_PROBE_NO_SECOND, second 0, ncc_second NaN.  Only comparisons are involved: every field is
+ * defined to the bit.
+ *
+ * Skipped probes are not correlated: offsets 0, NaN scores and AM_PROBE_NONFINITE (the probe holds a non-finite
+ * sample) or, checked second, AM_PROBE_QUIET: with E_i the probe's f64 sum of squares and E_ref = (f64 sum of squares
+ * of A's finite samples) L / len_a, the probe is quiet when E_i = 0 or E_i < E_ref 10^(-min_level_db / 10) -- the NCC
+ * of silence against anything is noise.  The order of these f64 additions is not part of the contract.
+ *
+ * am_probe_scores / am_probe_scores_device: the record rule on any score array (host memory / memory of `device` at
+ * any 4-byte alignment) with the excluded range [ex_lo, ex_hi) (empty when ex_lo >= ex_hi) and separation >= 1;
+ * `probe` of the record is 0.  It is to discovery what am_trace_scores is to the traces.
+ *
+ * Regions (am_discover_regions; integers and f64).  A probe is good when it has no flag other than
+ * AM_PROBE_NO_SECOND, ncc >= min_ncc and -- when max_second > 0 and it has a runner-up -- (double)ncc_second <=
+ * (double)max_second (double)ncc.  Its displacement is d = best - probe, signed.  The records are walked in index
+ * order; their `probe` fields must ascend strictly (else AM_ERR_INVALID_ARG).  A chain starts at a good probe; with g
+ * the chain's last good probe a later good probe joins when |d - d_g| <= tolerance, otherwise the chain ends at g and
+ * the new probe starts the next chain; probes that are not good are bridged while no more than max_gap of them lie in
+ * a row behind g, one more ends the chain at g.  A chain with at least min_good good probes is a region: a_start =
+ * the first good probe's p, length = the last good probe's p + L - a_start, displacement = the lower median of the
+ * good d (the B-side start is a_start + displacement), first = the index of the first good probe, count = the probes
+ * from the first to the last good one, good = the good ones among them, mean_ncc = (f64 sum of the good ncc in index
+ * order) / good, min_ncc = the smallest good ncc, worst_second = the largest ncc_second of the good probes that have a
+ * runner-up (NaN: none has).  AM_REGION_FOLD (only with AM_DISCOVER_SELF in dp->flags): a region R with negative
+ * displacement is dropped when an earlier kept region K with positive displacement has |K.d + R.d| <= tolerance and
+ * [K.a_start + K.d, + K.length) overlaps [R.a_start, + R.length): in a self search every repeat is seen from both of
+ * its occurrences, and the fold reports it once.  A region is exact to one hop; am_hit_segments on the cut refines it.
+ *
+ * Outputs are host memory; cap < count: AM_ERR_CAPACITY with what fits filled and the full count in *n_out.
+ * AM_ERR_INVALID_ARG (the message names the field): a null pointer, reserved != 0, probe_len = 0, hop = 0, exclude
+ * without AM_DISCOVER_SELF, unknown flags, a NaN min_level_db / min_ncc / max_second, a bad format, a pointer that is
+ * not on `device` (am_discover_device, am_probe_scores_device), separation = 0 (am_probe_scores*).
+ * Device memory: 4 bytes per score of one probe (the context's score buffer, as for am_match_best) and a mono copy of
+ * each i16 recording. */
+#define AM_DISCOVER_SELF 1u                   /* am_discover_params.flags: B is A; exclude each probe's own place */
+#define AM_REGION_FOLD 1u                     /* am_region_params.flags: report a repeat of a self search once */
+#define AM_PROBE_NO_BEST 1u                   /* am_probe_hit.flags */
+#define AM_PROBE_NO_SECOND 2u
+#define AM_PROBE_NONFINITE 4u
+#define AM_PROBE_QUIET 8u
+#define AM_DISCOVER_SLICE 8192                /* scores one wavefront reduces; the finish kernel folds the slices */
+typedef struct am_probe_hit {
+    uint64_t probe;           /* p_i: the probe's first sample in A */
+    uint64_t best, second;    /* score offsets (first sample of the window in B) */
+    float    ncc, ncc_second; /* bits of the scores at best / second; NaN where there is none */
+    uint32_t flags;           /* AM_PROBE_* */
+    uint32_t reserved;        /* 0 */
+} am_probe_hit;               /* 40 bytes, no padding */
+typedef struct am_discover_params {
+    uint64_t probe_len, hop;  /* L, H: at least 1 */
+    uint64_t exclude;         /* with AM_DISCOVER_SELF: p - exclude < j < p + exclude is no candidate; else 0 */
+    uint64_t separation;      /* least distance of the runner-up from the best; 0 = L */
+    float    min_level_db;    /* a probe more than this many dB below A's level is AM_PROBE_QUIET */
+    uint32_t flags;           /* AM_DISCOVER_SELF */
+    uint32_t reserved;        /* 0 */
+} am_discover_params;
+typedef struct am_region_params {
+    float    min_ncc;         /* a good probe scores at least this */
+    float    max_second;      /* > 0: ... and its runner-up at most max_second ncc */
+    uint64_t tolerance;       /* displacements of one chain differ by at most this from one good probe to the next */
+    uint32_t min_good;        /* good probes a region needs */
+    uint32_t max_gap;         /* probes that are not good a chain bridges in a row */
+    uint32_t flags;           /* AM_REGION_FOLD */
+    uint32_t reserved;        /* 0 */
+} am_region_params;
+typedef struct am_region {
+    uint64_t a_start, length; /* samples of A */
+    int64_t  displacement;    /* B-side start = a_start + displacement */
+    uint64_t first;           /* index of the first good probe */
+    uint32_t count, good;     /* probes from the first to the last good one; the good ones among them */
+    double   mean_ncc;
+    float    min_ncc, worst_second;
+} am_region;                  /* 56 bytes, no padding */
+
+int am_discover_len(size_t len_a, const am_discover_params* dp, size_t* n_probes);
+int am_discover_device(int device, const void* d_a, size_t len_a, const void* d_b, size_t len_b,
+                       int sample_format, const am_discover_params* dp,
+                       am_probe_hit* out, size_t cap, size_t* n_out);
+int am_discover(int device, const void* a, size_t len_a, const void* b, size_t len_b,
+                int sample_format, const am_discover_params* dp,
+                am_probe_hit* out, size_t cap, size_t* n_out);
+int am_probe_scores(int device, const float* scores, size_t n, uint64_t ex_lo, uint64_t ex_hi,
+                    uint64_t separation, am_probe_hit* out);
+int am_probe_scores_device(int device, const float* d_scores, size_t n, uint64_t ex_lo, uint64_t ex_hi,
+                           uint64_t separation, am_probe_hit* out);
+int am_discover_regions(const am_probe_hit* hits, size_t n, const am_discover_params* dp,
+                        const am_region_params* rp, am_region* out, size_t cap, size_t* n_out);
+
 
 /* ---- ingest: PCM -> f32 mono -------------------------------------------- */
 /* mp3_reader.rs:12, 28-37: mono = (l as f32 + r as f32) * 0.5 * (1/65535) */
@@ -1296,7 +1409,8 @@ int am_set_chunk_progress_callback(am_chunk_progress_fn fn, void* user);
  * HIP events on the stream it is launched on.  am_profile_query returns the
  * summed elapsed time and launch count of kernels whose name matches `kernel`
  * exactly ("k1_cols_fwd", "k2_rows", "k3_cols_inv", "tile_stats",
- * "peaks", "other", "trace" -- the score-trace kernels -- or "*" for all). */
+ * "peaks", "other", "trace" -- the score-trace kernels --, "discover" -- the
+ * kernels of needle discovery -- or "*" for all). */
 int am_profile_enable(int device, int on);
 int am_profile_reset(int device);
 int am_profile_query(int device, const char* kernel, double* total_ms, uint64_t* launches);
@@ -1379,7 +1493,7 @@ int am_debug_column_bench(int device, int wide, int npairs, int iters, int dense
  *     Also per needle handle (am_needle_set_option); pools use the process default (their needles are internal).
  *     Supported by am_correlate*, am_match, am_match_device, am_match_batch_device, am_match_pcm16*,
  *     am_pool_match_batch and am_pool_match_batch_pcm16 (and their _device forms), am_match_best,
- *     am_match_best_device, am_match_best_batch_device and am_match_trace*.  NOT supported -- AM_ERR_INVALID_ARG,
+ *     am_match_best_device, am_match_best_batch_device and am_match_trace* (am_discover* is always NCC).  NOT supported -- AM_ERR_INVALID_ARG,
  *     "score_norm: not supported by this entry point" -- by am_match_multi*, am_match_multi_varlen_batch_device,
  *     am_match_multi_varlen, am_pool_match_multi*, am_match_stream_*, am_match_part_device and am_pool_match_long*.  am_find_peaks is unaffected.
  *     Non-finite samples cost exactly the windows that hold them (they count as 0 in every other window's energy); a

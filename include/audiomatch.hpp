@@ -464,6 +464,51 @@ inline am_trace_stats trace_summary(const std::vector<am_trace_bin>& bins, std::
     return out;
 }
 
+// needle discovery (am_discover*): one am_probe_hit per probe of recording A matched against recording B (host memory /
+// memory of `device`); probe_scores*: the record rule on any score array; discover_regions: the regions the records
+// chain into (no device needed)
+inline std::size_t discover_len(std::size_t len_a, const am_discover_params& dp) {
+    std::size_t n = 0;
+    check(am_discover_len(len_a, &dp, &n));
+    return n;
+}
+inline std::vector<am_probe_hit> discover(const void* a, std::size_t len_a, const void* b, std::size_t len_b, int sample_format,
+                                          const am_discover_params& dp, int device = 0) {
+    std::vector<am_probe_hit> out(discover_len(len_a, dp));
+    std::size_t n = 0;
+    check(am_discover(device, a, len_a, b, len_b, sample_format, &dp, out.data(), out.size(), &n));
+    out.resize(std::min(n, out.size()));
+    return out;
+}
+inline std::vector<am_probe_hit> discover_device(const void* d_a, std::size_t len_a, const void* d_b, std::size_t len_b, int sample_format,
+                                                 const am_discover_params& dp, int device = 0) {
+    std::vector<am_probe_hit> out(discover_len(len_a, dp));
+    std::size_t n = 0;
+    check(am_discover_device(device, d_a, len_a, d_b, len_b, sample_format, &dp, out.data(), out.size(), &n));
+    out.resize(std::min(n, out.size()));
+    return out;
+}
+inline am_probe_hit probe_scores(const float* scores, std::size_t n, std::uint64_t ex_lo, std::uint64_t ex_hi, std::uint64_t separation,
+                                 int device = 0) {
+    am_probe_hit out{};
+    check(am_probe_scores(device, scores, n, ex_lo, ex_hi, separation, &out));
+    return out;
+}
+inline am_probe_hit probe_scores_device(const float* d_scores, std::size_t n, std::uint64_t ex_lo, std::uint64_t ex_hi,
+                                        std::uint64_t separation, int device = 0) {
+    am_probe_hit out{};
+    check(am_probe_scores_device(device, d_scores, n, ex_lo, ex_hi, separation, &out));
+    return out;
+}
+inline std::vector<am_region> discover_regions(const std::vector<am_probe_hit>& hits, const am_discover_params& dp,
+                                               const am_region_params& rp) {
+    std::vector<am_region> out(hits.size());   // (a region holds at least one probe)
+    std::size_t n = 0;
+    check(am_discover_regions(hits.data(), hits.size(), &dp, &rp, out.data(), out.size(), &n));
+    out.resize(std::min(n, out.size()));
+    return out;
+}
+
 // calc_chunks(sr, m_samples, &algo, scale, config) (audio_matcher.rs:88-141):
 // peaks sorted by position.start, overshadowed neighbours removed.
 inline std::vector<Peak> calc_chunks(std::uint16_t sr, const float* m_samples, std::size_t len,
