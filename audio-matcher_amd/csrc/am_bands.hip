@@ -225,6 +225,8 @@ long long band_frames(long long s, int lf) { return (s - (1ll << lf)) / (1ll << 
 // the samples a hit reads, counted from its start: (J - 1) H + F
 size_t band_span(size_t s, int lf) { return (size_t)((band_frames((long long)s, lf) - 1) * (1ll << (lf - 1)) + (1ll << lf)); }
 
+}  // namespace
+
 // the table of F on c's device, built on first use and kept until am_shutdown: w[0 .. F), then (cos, -sin)(2 pi k / F), k < F / 2
 int band_table(Ctx* c, int lf, const double** d_tab) {
     DevBuf& b = c->band_tabs[lf];
@@ -261,6 +263,8 @@ int band_check_params(const am_band_params* bp) {
                                             std::to_string(top) + ")");
     return AM_OK;
 }
+
+namespace {
 
 // ... and unless a needle of s samples holds one frame (`who`: "" or "needle j: ")
 int band_check_needle(const am_band_params* bp, size_t s, const std::string& who) {

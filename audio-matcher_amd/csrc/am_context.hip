@@ -113,7 +113,8 @@ int realloc_refused(const char* what, size_t bytes, size_t cap) {
     return fail(AM_ERR_HIP, buf);
 }
 
-static const char* kKernelNames[] = {"k1_cols_fwd", "k2_rows", "k3_cols_inv", "tile_stats", "peaks", "other", "trace", "discover"};
+static const char* kKernelNames[] = {"k1_cols_fwd", "k2_rows", "k3_cols_inv", "tile_stats", "peaks", "other", "trace", "discover",
+                                     "envelope_frames", "envelope_prefix", "envelope_correlate"};
 static std::mutex g_ctx_mu;
 static std::map<int, Ctx*> g_ctx;
 
@@ -518,6 +519,7 @@ int am_shutdown(void) {
         for (DevBuf* b : {&c->sig_span, &c->sig_scores, &c->sig_psum, &c->sig_pmax, &c->sig_mean, &c->sig_hmax}) b->release();
         for (DevBuf* b : {&c->best_stats, &c->best_lmax, &c->best_ctl, &c->best_trans, &c->best_list, &c->best_scores, &c->best_mono, &c->trace_out, &c->trace_parts}) b->release();
         for (DevBuf* b : {&c->disc_a, &c->disc_probe, &c->disc_energy, &c->disc_parts, &c->disc_out}) b->release();
+        for (DevBuf* b : {&c->env_jobs, &c->env_needles, &c->env_hay, &c->env_bank, &c->env_desc, &c->env_prefix, &c->env_blocks, &c->env_out}) b->release();
         for (auto& kv : c->rs_taps) kv.second.release();
         c->rs_taps.clear();
         c->lag_parts.release(); c->lag_r.release();
@@ -580,7 +582,9 @@ int am_profile_query(int device, const char* kernel, double* total_ms, uint64_t*
     prof_harvest(c);
     double ms = 0; uint64_t n = 0; bool found = false;
     for (int i = 0; i < KN_COUNT; ++i) {
-        if (!strcmp(kernel, "*") || !strcmp(kernel, kKernelNames[i])) { ms += c->prof_ms[i]; n += c->prof_n[i]; found = true; }
+        // ("envelope": the three classes of envelope matching together)
+        const bool family = !strcmp(kernel, "envelope") && !strncmp(kKernelNames[i], "envelope_", 9);
+        if (!strcmp(kernel, "*") || !strcmp(kernel, kKernelNames[i]) || family) { ms += c->prof_ms[i]; n += c->prof_n[i]; found = true; }
     }
     if (!found) return fail(AM_ERR_INVALID_ARG, "unknown kernel name");
     *total_ms = ms; *launches = n;

@@ -135,7 +135,7 @@ struct Plan {
 struct ScoreSide { DevBuf scores, stats, stats32, wflags, peaks, work; };
 
 struct ProfRec { int name; hipEvent_t e0, e1; };
-enum { KN_K1 = 0, KN_K2, KN_K3, KN_STATS, KN_PEAKS, KN_OTHER, KN_TRACE, KN_DISCOVER, KN_COUNT };
+enum { KN_K1 = 0, KN_K2, KN_K3, KN_STATS, KN_PEAKS, KN_OTHER, KN_TRACE, KN_DISCOVER, KN_ENV_FRAMES, KN_ENV_PREFIX, KN_ENV_CORR, KN_COUNT };
 
 struct Ctx {
     int device = -1;
@@ -189,6 +189,9 @@ struct Ctx {
     // needle discovery (am_discover.hip): recording A down-mixed, the probe being matched, the energy parts, the slices'
     // partials and a call's records
     DevBuf disc_a, disc_probe, disc_energy, disc_parts, disc_out;
+    // envelope matching (am_envelope.hip): the frame jobs of a launch, the needle bank's and the haystack's levels, the
+    // bank padded to whole chunks with its per-needle sums, the haystack's prefix sums and their block sums, z and qi
+    DevBuf env_jobs, env_needles, env_hay, env_bank, env_desc, env_prefix, env_blocks, env_out;
     // the chunk list currently resident in `segs` (re-uploaded only when it changes)
     std::vector<Segment> segs_resident;
     // profiling
@@ -580,6 +583,12 @@ int hit_round_trip(Ctx* c, const std::vector<Desc>& hits, size_t part_bytes, siz
     for (size_t i = 0; i < n; ++i) std::memcpy(out[i], static_cast<const Rec*>(res) + i * recs, sizeof(Rec) * recs);
     return AM_OK;
 }
+
+// ---- am_bands.hip ----
+// the window and twiddle table of F = 2^lf on c's device (w[0 .. F), then (cos, -sin)(2 pi k / F), k < F / 2), built on
+// first use; AM_ERR_INVALID_ARG unless bp is a valid request
+int band_table(Ctx* c, int lf, const double** d_tab);
+int band_check_params(const am_band_params* bp);
 
 // ---- am_estimate.hip ----
 // slots of the sorting network a call with n rows runs: 0 for AM_EST_MEAN (no sort), else 8, 16, 32 or 64; -1: too many rows

@@ -106,6 +106,9 @@ struct Arguments {
     float discover_min_ncc = 0.6f;            // ... --discover-min-ncc X: what a probe must score to count
     bool discover_min_ncc_set = false;
     std::string discover_out;                 // ... --discover-out PREFIX: each region's samples of the first FILE as PREFIX<file index>_<a_start>.wav; empty = off
+    std::optional<double> envelope_pct;       // extension: --envelope PCT[:STEPS[:MIN_SCORE]], occurrences at another speed, found through band-level envelopes (am_match_envelope)
+    std::uint32_t envelope_steps = 20;        // ... drifts -PCT % .. PCT % in 2 STEPS + 1 steps
+    float envelope_min_score = 0.4f;          // ... what an envelope hit must score
     bool live = false;                        // extension: --live, raw PCM from stdin through a monitor (am_monitor_*)
     std::uint32_t rate = 0;                   // --live: --rate R (samples per second of the stream)
     std::string encoding = "s16le";           // --live: --encoding s16le | f32le
@@ -217,6 +220,16 @@ inline const char* usage_text() {
            "                         one line 'Trace: max V at hh:mm:ss.mmm, bin maxima median V mad V, peak z V'.  The\n"
            "                         scores are those that were matched: --normalize, --resample, --whiten / --preemphasis\n"
            "                         and --mix apply.  Not with --live\n"
+           "  --envelope PCT[:STEPS[:MIN_SCORE]]  also find occurrences that run at another speed (a playout machine a few\n"
+           "                         percent fast, a tape transfer) or whose phases are scrambled, which no waveform match\n"
+           "                         sees: the snippet's band-level envelope (8 log bands from 150 Hz to 6 kHz or 0.45 of\n"
+           "                         the sample rate, frames of 1024 samples) is matched against the file's at the lengths\n"
+           "                         -PCT .. +PCT percent (up to 25) in 2 STEPS + 1 steps (STEPS in 1..128, default 20); under\n"
+           "                         a snippet's offset lines one line per place that scores at least MIN_SCORE (-1..1,\n"
+           "                         default 0.4): 'Envelope: hh:mm:ss.mmm speed +S % score V' (speed: that of the\n"
+           "                         occurrence against the snippet).  The start is good to a few frames and the speed to a\n"
+           "                         step or two, less for snippets of a few seconds.  Such places go into the label file\n"
+           "                         unless a hit lies within half a snippet of them.  Not with --live or --discover\n"
            "  --discover DUR[:HOP]   no --snippet: find what the first FILE shares with itself and with every further FILE\n"
            "                         (am_discover): probes of DUR (a duration) every HOP (default DUR/2) of the first FILE\n"
            "                         are matched under NCC, and probes that agree on one displacement (within HOP/8, at\n"
@@ -463,6 +476,23 @@ inline Arguments parse_arguments(int argc, const char* const* argv) {
             if (a.trace_prefix.empty() || a.trace_bin_ms == 0)
                 throw ArgError("invalid value '" + v + "' for --score-trace (PREFIX[:BIN], a file name prefix and a duration longer than 0)");
         }
+        else if (s == "--envelope") {
+            const std::string v = need(i);
+            const std::size_t c1 = v.find(':'), c2 = c1 == std::string::npos ? c1 : v.find(':', c1 + 1);
+            const std::string vp = v.substr(0, c1);
+            const std::string vs = c1 == std::string::npos ? "20" : v.substr(c1 + 1, c2 == std::string::npos ? c2 : c2 - c1 - 1);
+            const std::string vm = c2 == std::string::npos ? "0.4" : v.substr(c2 + 1);
+            char *e1 = nullptr, *e2 = nullptr, *e3 = nullptr;
+            const double pct = std::strtod(vp.c_str(), &e1);
+            const unsigned long k = std::strtoul(vs.c_str(), &e2, 10);
+            const float ms = std::strtof(vm.c_str(), &e3);
+            if (vp.empty() || *e1 != '\0' || !(pct > 0.0) || pct > AM_ENV_MAX_PPM * 1e-4 || vs.empty() || vs[0] < '0' || vs[0] > '9' || *e2 != '\0' ||
+                k == 0 || k > AM_ENV_MAX_STEPS || vm.empty() || *e3 != '\0' || !(ms >= -1.0f && ms <= 1.0f))
+                throw ArgError("invalid value '" + v + "' for --envelope (PCT[:STEPS[:MIN_SCORE]], PCT above 0 up to 25, STEPS in 1..128, MIN_SCORE in -1..1)");
+            a.envelope_pct = pct;
+            a.envelope_steps = (std::uint32_t)k;
+            a.envelope_min_score = ms;
+        }
         else if (s == "--discover") {
             const std::string v = need(i);
             const auto colon = v.find(':');
@@ -515,7 +545,8 @@ inline Arguments parse_arguments(int argc, const char* const* argv) {
             {a.min_confidence.has_value(), "--min-confidence"}, {a.segments != 0, "--segments"}, {a.bands != 0, "--bands"},
             {a.warp_ppm.has_value(), "--warp"}, {a.channel_radius.has_value(), "--channel"}, {!a.residual_prefix.empty(), "--residual"},
             {a.stereo_radius.has_value(), "--stereo"}, {a.min_significance.has_value(), "--min-significance"},
-            {a.significance_zone_ms.has_value(), "--significance-zone"}, {!a.learn_needle.empty(), "--learn-needle"}};
+            {a.significance_zone_ms.has_value(), "--significance-zone"}, {!a.learn_needle.empty(), "--learn-needle"},
+            {a.envelope_pct.has_value(), "--envelope"}};
         for (const auto& o : others)
             if (o.first) throw ArgError(std::string("--discover and ") + o.second + " are mutually exclusive");
         // ... and what would be ignored without a word (--normalize is what discovery does anyway; --mix and
@@ -556,6 +587,7 @@ inline Arguments parse_arguments(int argc, const char* const* argv) {
         if (a.segments) throw ArgError("--live: --segments does not apply");
         if (a.bands) throw ArgError("--live: --bands does not apply");
         if (a.warp_ppm) throw ArgError("--live: --warp does not apply");
+        if (a.envelope_pct) throw ArgError("--live: --envelope does not apply");
         if (a.channel_radius) throw ArgError("--live: --channel does not apply");
         if (a.whiten || a.preemphasis) throw ArgError("--live: --whiten and --preemphasis do not apply (not supported on a live feed yet)");
         if (a.min_significance || a.significance_zone_ms) throw ArgError("--live: --min-significance and --significance-zone do not apply");
@@ -698,6 +730,15 @@ inline std::vector<std::string> offset_lines(const am_peak* peaks, std::size_t n
     if (n == 0) { out.push_back("no offsets found"); return out; }
     for (std::size_t i = 0; i < n; ++i) out.push_back(offset_line(peaks[i], i, sr));
     return out;
+}
+
+// extension: --envelope.  "Envelope: hh:mm:ss.mmm speed +S % score V": the speed of the occurrence against the snippet
+inline std::string envelope_line(const am_env_hit& hit, std::uint32_t sr) {
+    const std::uint64_t ms = (std::uint64_t)((double)hit.start * 1000.0 / (double)sr);
+    char buf[160];
+    std::snprintf(buf, sizeof buf, "Envelope: %02" PRIu64 ":%02" PRIu64 ":%02" PRIu64 ".%03" PRIu64 " speed %+.2f %% score %.3f", ms / 3600000,
+                  (ms / 60000) % 60, (ms / 1000) % 60, ms % 1000, 100.0 * (1.0 / (1.0 + hit.drift_ppm * 1e-6) - 1.0), (double)hit.score);
+    return buf;
 }
 
 struct TimeLabel { double start_s, end_s; std::string name; };

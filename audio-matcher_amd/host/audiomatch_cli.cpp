@@ -566,6 +566,40 @@ static void report_hits(const Arguments& args, const am_needle* algo, const std:
             if (i < l->size()) std::printf("%s%s\n", prefix.c_str(), (*l)[i].c_str());
 }
 
+// extension: --envelope.  The places where one snippet occurs at another speed in one main file (am_match_envelope), printed
+// under the snippet's offset lines; those without a hit within half a snippet of them join `hits` (height and prominence:
+// the envelope score), which then stays sorted by start.
+static void envelope_hits(const Arguments& args, const am_needle* algo, const std::vector<float>& m_samples, std::uint32_t m_sr,
+                          std::vector<am_peak>& hits, const std::string& prefix) {
+    am_env_params ep{};
+    if (am_band_edges_log(m_sr, 10, 150.0, std::min(6000.0, 0.45 * (double)m_sr), 8, &ep.bands) != AM_OK)
+        throw std::runtime_error(std::string("--envelope: am_band_edges_log: ") + am_last_error_string());
+    ep.floor_db = 80.0;
+    am_env_grid grid{};
+    grid.max_ppm = *args.envelope_pct * 1e4;
+    grid.steps = args.envelope_steps;
+    std::vector<am_env_hit> env(256);
+    size_t n = 0;
+    int rc = am_match_envelope(algo, m_samples.data(), m_samples.size(), AM_FMT_F32_MONO, &ep, &grid, args.envelope_min_score, env.data(), env.size(), &n);
+    if (rc == AM_ERR_CAPACITY) {
+        env.resize(n);
+        rc = am_match_envelope(algo, m_samples.data(), m_samples.size(), AM_FMT_F32_MONO, &ep, &grid, args.envelope_min_score, env.data(), env.size(), &n);
+    }
+    if (rc != AM_OK) throw std::runtime_error(std::string("am_match_envelope: ") + am_last_error_string());
+    env.resize(n);
+    size_t s_len = 0;
+    am_needle_len(algo, &s_len);
+    const std::vector<am_peak> found = hits;
+    for (const am_env_hit& e : env) {
+        if (args.verbosity >= 1) std::printf("%s%s\n", prefix.c_str(), envelope_line(e, m_sr).c_str());
+        bool known = false;
+        for (const am_peak& pk : found)
+            known = known || (pk.start > e.start ? pk.start - e.start : e.start - pk.start) <= s_len / 2;
+        if (!known) hits.push_back(am_peak{e.start, e.start + e.length, e.score, e.score});
+    }
+    std::stable_sort(hits.begin(), hits.end(), [](const am_peak& a, const am_peak& b) { return a.start < b.start; });
+}
+
 // extension: --score-trace.  The score curve of one snippet in one main file: its CSV file (`snippet_index`: set when the
 // run has several snippets) and, under the offset lines, its summary line.  Returns 0, or 4 where the file cannot be
 // written.
@@ -630,8 +664,11 @@ static int run_files(const Arguments& args) {
                 hits[j] = args.best ? best_hits(args, handles[j], m_samples, m_sr) : match_hits(handles[j], m_samples, p);
             }
         }
-        for (size_t j = 0; j < k; ++j)
-            report_hits(args, handles[j], m_samples, m_sr, hits[j], k > 1 ? snips[j].name + ": " : std::string(), learner, snips[j], file_index, m);
+        for (size_t j = 0; j < k; ++j) {
+            const std::string prefix = k > 1 ? snips[j].name + ": " : std::string();
+            report_hits(args, handles[j], m_samples, m_sr, hits[j], prefix, learner, snips[j], file_index, m);
+            if (args.envelope_pct) envelope_hits(args, handles[j], m_samples, m_sr, hits[j], prefix);
+        }
         if (!args.trace_prefix.empty())
             for (size_t j = 0; j < k; ++j)
                 if (const int rc = write_trace(args, handles[j], m_samples, m_sr, file_index, k > 1 ? std::optional<size_t>(j) : std::nullopt,

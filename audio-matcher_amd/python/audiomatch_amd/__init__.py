@@ -263,6 +263,22 @@ AM_DISCOVER_SELF, AM_REGION_FOLD, AM_DISCOVER_SLICE = 1, 1, 8192
 AM_PROBE_NO_BEST, AM_PROBE_NO_SECOND, AM_PROBE_NONFINITE, AM_PROBE_QUIET = 1, 2, 4, 8
 
 
+class AmEnvParams(C.Structure):        # am_env_params (include/audiomatch.h, envelope matching)
+    _fields_ = [("bands", AmBandParams), ("reserved", C.c_uint32), ("floor_db", C.c_double)]
+
+
+class AmEnvGrid(C.Structure):          # am_env_grid: 2 K + 1 drifts centre_ppm + max_ppm (q - K) / K
+    _fields_ = [("centre_ppm", C.c_double), ("max_ppm", C.c_double), ("steps", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+# am_env_pick (24 bytes) and am_env_hit (32 bytes) as numpy structured dtypes
+ENV_PICK_DTYPE = np.dtype([("frame", "<u8"), ("pos", "<f8"), ("score", "<f4"), ("q", "<u4")])
+ENV_HIT_DTYPE = np.dtype([("start", "<u8"), ("length", "<u8"), ("drift_ppm", "<f8"), ("score", "<f4"), ("q", "<u4")])
+AM_ENV_STEPS_PER_DB, AM_ENV_MAX_LEVEL, AM_ENV_ABSENT, AM_ENV_NO_Q = 8, 1023, 0xFFFF, 0xFFFFFFFF
+AM_ENV_MAX_PPM, AM_ENV_MAX_FRAMES, AM_ENV_MAX_NEEDLES, AM_ENV_MAX_STEPS = 250000, 16384, 257, 128
+AM_ENV_MAX_LEN, AM_ENV_MAX_HAY_FRAMES, AM_ENV_TILE, AM_ENV_CHUNK = 1 << 31, 1 << 24, 512, 8
+
+
 class AmMonitorInfo(C.Structure):  # am_monitor_info (include/audiomatch.h, live monitoring)
     _fields_ = [("received", C.c_uint64), ("horizon", C.c_uint64), ("resident_bytes", C.c_uint64), ("pending", C.c_uint64)]
 
@@ -509,6 +525,21 @@ _SIGNATURES = {
     "am_probe_scores_device": (C.c_int, [C.c_int, C.c_void_p, C.c_size_t, C.c_uint64, C.c_uint64, C.c_uint64, C.c_void_p]),
     "am_discover_regions": (C.c_int, [C.c_void_p, C.c_size_t, C.POINTER(AmDiscoverParams), C.POINTER(AmRegionParams),
                                       C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "am_envelope_len": (C.c_int, [C.c_size_t, C.POINTER(AmEnvParams), C.c_double, C.POINTER(C.c_size_t)]),
+    "am_envelope": (C.c_int, [C.c_int, C.c_void_p, C.c_size_t, C.c_int, C.POINTER(AmEnvParams), C.c_double, C.c_void_p, C.c_size_t,
+                              C.POINTER(C.c_size_t)]),
+    "am_envelope_device": (C.c_int, [C.c_int, C.c_void_p, C.c_size_t, C.c_int, C.POINTER(AmEnvParams), C.c_double, C.c_void_p,
+                                     C.c_size_t, C.POINTER(C.c_size_t)]),
+    "am_envelope_scores": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_size_t, C.c_void_p,
+                                     C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "am_envelope_scores_device": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_size_t,
+                                            C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "am_envelope_pick": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_float, C.c_uint64, C.c_void_p, C.c_size_t,
+                                   C.POINTER(C.c_size_t)]),
+    "am_match_envelope": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.POINTER(AmEnvParams), C.POINTER(AmEnvGrid),
+                                    C.c_float, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "am_match_envelope_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.POINTER(AmEnvParams), C.POINTER(AmEnvGrid),
+                                           C.c_float, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]),
     "am_get_option": (C.c_int, [C.c_char_p, C.POINTER(C.c_longlong)]),
 }
 
@@ -1020,6 +1051,116 @@ def discover_regions(hits, params: AmDiscoverParams, rparams: AmRegionParams, ca
     return out[:min(n.value, cap)]
 
 
+def env_params(bands: AmBandParams, floor_db: float = 80.0) -> AmEnvParams:
+    """am_env_params: the bands (band_params or band_edges_log) and the level floor in dB below a full-scale sine."""
+    ep = AmEnvParams()
+    ep.bands = bands
+    ep.reserved = 0
+    ep.floor_db = float(floor_db)
+    return ep
+
+
+def env_grid(max_ppm: float, steps: int, centre_ppm: float = 0.0) -> AmEnvGrid:
+    """am_env_grid: the 2 * steps + 1 drifts centre_ppm - max_ppm .. centre_ppm + max_ppm."""
+    return AmEnvGrid(centre_ppm=float(centre_ppm), max_ppm=float(max_ppm), steps=int(steps), reserved=0)
+
+
+def env_grid_drifts(grid: AmEnvGrid):
+    """The drifts d_q of a grid, in ppm (the rule of include/audiomatch.h in f64)."""
+    k = int(grid.steps)
+    if k == 0:
+        return np.array([grid.centre_ppm], dtype=np.float64)
+    return np.array([grid.centre_ppm + grid.max_ppm * float(q - k) / float(k) for q in range(2 * k + 1)], dtype=np.float64)
+
+
+def envelope_len(length: int, ep: AmEnvParams, drift_ppm: float = 0.0) -> int:
+    """am_envelope_len: the frames J of a signal of `length` samples at drift_ppm (pure host)."""
+    n = C.c_size_t(0)
+    _check(lib().am_envelope_len(int(length), C.byref(ep), float(drift_ppm), C.byref(n)))
+    return n.value
+
+
+def _envelope_call(fn, length: int, ep: AmEnvParams, drift_ppm: float, cap):
+    j = envelope_len(length, ep, drift_ppm)
+    cap = j if cap is None else int(cap)
+    nb = int(ep.bands.n_bands)
+    out = np.zeros(max(1, nb * cap), dtype=np.uint16)
+    n = C.c_size_t(0)
+    _check(fn(out.ctypes.data, cap, C.byref(n)))
+    return out[:nb * n.value].reshape(nb, n.value)   # (band-major with J frames per band, whatever cap was)
+
+
+def envelope(signal, ep: AmEnvParams, drift_ppm: float = 0.0, device: int = 0, cap=None):
+    """am_envelope: the (B, J) uint16 band levels of a host signal (f32, or i16 (frames, 2) interleaved stereo) read at
+    drift_ppm; AM_ENV_ABSENT marks a frame with a non-finite sample."""
+    a, fmt, length = _samples(signal)
+    return _envelope_call(lambda o, c, n: lib().am_envelope(device, a.ctypes.data, length, int(fmt), C.byref(ep), float(drift_ppm), o, c, n),
+                          length, ep, drift_ppm, cap)
+
+
+def envelope_device(device: int, ptr: int, length: int, ep: AmEnvParams, drift_ppm: float = 0.0, fmt: int = Fmt.F32_MONO, cap=None):
+    """am_envelope_device: the same of a signal resident on `device`."""
+    return _envelope_call(lambda o, c, n: lib().am_envelope_device(device, ptr, int(length), int(fmt), C.byref(ep), float(drift_ppm), o, c, n),
+                          length, ep, drift_ppm, cap)
+
+
+def _env_bank(needles):
+    mats = [np.ascontiguousarray(m, dtype=np.uint16) for m in needles]
+    frames = np.array([m.shape[1] for m in mats], dtype=np.uint32)
+    bank = np.concatenate([m.reshape(-1) for m in mats]) if mats else np.zeros(0, dtype=np.uint16)
+    return mats, frames, bank
+
+
+def _env_scores_call(fn, frames, hay_frames: int, cap):
+    n_all = max([hay_frames - int(j) + 1 for j in frames if hay_frames >= int(j)], default=0)
+    cap = n_all if cap is None else int(cap)
+    z = np.zeros(max(1, cap), dtype=np.float32)
+    qi = np.zeros(max(1, cap), dtype=np.uint32)
+    n = C.c_size_t(0)
+    _check(fn(z.ctypes.data, qi.ctypes.data, cap, C.byref(n)))
+    m = min(n.value, cap)
+    return z[:m], qi[:m]
+
+
+def envelope_scores(needles, hay, device: int = 0, cap=None):
+    """am_envelope_scores: (z, qi) of a list of (B, J_q) uint16 needle matrices against the (B, Jh) haystack matrix --
+    per place t the largest score over the needles and its needle (AM_ENV_NO_Q beside a NaN)."""
+    mats, frames, bank = _env_bank(needles)
+    e = np.ascontiguousarray(hay, dtype=np.uint16)
+    nb = e.shape[0]
+    return _env_scores_call(lambda z, q, c, n: lib().am_envelope_scores(device, bank.ctypes.data, frames.ctypes.data, len(mats), nb,
+                                                                        e.ctypes.data if e.size else None, e.shape[1], z, q, c, n),
+                            frames, e.shape[1], cap)
+
+
+def envelope_scores_device(device: int, ptr_needles: int, frames, n_bands: int, ptr_hay: int, hay_frames: int, cap=None):
+    """am_envelope_scores_device: the same on matrices resident on `device` (the needle matrices one behind the other)."""
+    fr = np.ascontiguousarray(frames, dtype=np.uint32)
+    return _env_scores_call(lambda z, q, c, n: lib().am_envelope_scores_device(device, ptr_needles, fr.ctypes.data, fr.size, int(n_bands),
+                                                                               ptr_hay, int(hay_frames), z, q, c, n),
+                            fr, int(hay_frames), cap)
+
+
+def envelope_pick(z, qi, min_score: float, separation: int, cap=None):
+    """am_envelope_pick: the places (ENV_PICK_DTYPE) of a score array that are its largest within +-separation (pure host)."""
+    zz = np.ascontiguousarray(z, dtype=np.float32)
+    qq = np.ascontiguousarray(qi, dtype=np.uint32)
+    cap = zz.size if cap is None else int(cap)
+    out = np.zeros(max(1, cap), dtype=ENV_PICK_DTYPE)
+    n = C.c_size_t(0)
+    _check(lib().am_envelope_pick(zz.ctypes.data if zz.size else None, qq.ctypes.data if qq.size else None, zz.size, float(min_score),
+                                  int(separation), out.ctypes.data, cap, C.byref(n)))
+    return out[:min(n.value, cap)]
+
+
+def _env_match_call(fn, cap):
+    cap = 1024 if cap is None else int(cap)
+    out = np.zeros(max(1, cap), dtype=ENV_HIT_DTYPE)
+    n = C.c_size_t(0)
+    _check(fn(out.ctypes.data, cap, C.byref(n)))
+    return out[:min(n.value, cap)]
+
+
 def best_params(k: int, min_distance: int = 0, min_prominence: float = 0.0, scale=Scale.LIB) -> AmBestParams:
     """am_best_params of the k best matches (scale: Scale.NONE or Scale.LIB, or a bool as in correlate_with_sample)."""
     sc = int(Scale.LIB if scale is True else Scale.NONE if scale is False else scale)
@@ -1453,6 +1594,20 @@ class HipConvolve:
         counts = (C.c_size_t * max(1, nh))()
         _check(lib().am_match_trace_batch_device(self._h, arr_p, arr_l, nh, int(fmt), C.byref(params), out.ctypes.data, cap, counts))
         return [out[i * cap:i * cap + min(counts[i], cap)].copy() for i in range(nh)]
+
+    # -- envelope matching --
+    def match_envelope(self, haystack, ep: AmEnvParams, grid: AmEnvGrid, min_score: float, cap=None):
+        """am_match_envelope: the occurrences (ENV_HIT_DTYPE) of this needle played at any speed of `grid` in a host
+        haystack (f32, or i16 (frames, 2) interleaved stereo): start good to a few frames, drift to a grid step or two."""
+        a, fmt, length = _samples(haystack)
+        return _env_match_call(lambda o, c, n: lib().am_match_envelope(self._h, a.ctypes.data, length, int(fmt), C.byref(ep), C.byref(grid),
+                                                                       float(min_score), o, c, n), cap)
+
+    def match_envelope_device(self, ptr: int, length: int, ep: AmEnvParams, grid: AmEnvGrid, min_score: float,
+                              fmt: int = Fmt.F32_MONO, cap=None):
+        """am_match_envelope_device on a haystack resident on this needle's device."""
+        return _env_match_call(lambda o, c, n: lib().am_match_envelope_device(self._h, ptr, int(length), int(fmt), C.byref(ep), C.byref(grid),
+                                                                              float(min_score), o, c, n), cap)
 
     # -- per-hit scoring --
     def hit_scores(self, haystack, peaks):

@@ -351,6 +351,50 @@ pub struct AmRegion {
     pub min_ncc: f32,
     pub worst_second: f32,
 }
+/// am_env_params: the bands (as for am_hit_bands) and the level floor of envelope matching, 152 bytes; reserved = 0
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct AmEnvParams {
+    pub bands: AmBandParams,
+    pub reserved: u32,
+    pub floor_db: f64,
+}
+/// am_env_grid: the 2 * steps + 1 drifts centre_ppm + max_ppm (q - steps) / steps; reserved = 0
+#[repr(C)]
+#[derive(Clone, Copy, Default, Debug)]
+pub struct AmEnvGrid {
+    pub centre_ppm: f64,
+    pub max_ppm: f64,
+    pub steps: u32,
+    pub reserved: u32,
+}
+/// am_env_pick: one place the pick rule keeps, 24 bytes
+#[repr(C)]
+#[derive(Clone, Copy, Default, Debug)]
+pub struct AmEnvPick {
+    pub frame: u64,
+    pub pos: f64,
+    pub score: f32,
+    pub q: u32,
+}
+/// am_env_hit: one occurrence found through its envelope, 32 bytes: start good to a few frames, drift to a grid step or two
+#[repr(C)]
+#[derive(Clone, Copy, Default, Debug)]
+pub struct AmEnvHit {
+    pub start: u64,
+    pub length: u64,
+    pub drift_ppm: f64,
+    pub score: f32,
+    pub q: u32,
+}
+pub const AM_ENV_STEPS_PER_DB: u32 = 8;
+pub const AM_ENV_MAX_LEVEL: u16 = 1023;
+pub const AM_ENV_ABSENT: u16 = 0xFFFF;
+pub const AM_ENV_NO_Q: u32 = 0xFFFF_FFFF;
+pub const AM_ENV_MAX_PPM: f64 = 250000.0;
+pub const AM_ENV_MAX_FRAMES: u32 = 16384;
+pub const AM_ENV_MAX_NEEDLES: u32 = 257;
+pub const AM_ENV_MAX_STEPS: u32 = 128;
 pub const AM_DISCOVER_SELF: u32 = 1;
 pub const AM_REGION_FOLD: u32 = 1;
 pub const AM_PROBE_NO_BEST: u32 = 1;
@@ -677,6 +721,35 @@ extern "C" {
         hits: *const AmProbeHit, n: usize, dp: *const AmDiscoverParams, rp: *const AmRegionParams, out: *mut AmRegion, cap: usize,
         n_out: *mut usize,
     ) -> c_int;
+    /// envelope matching: a needle played at another speed, found through band-level envelopes (audiomatch.h)
+    pub fn am_envelope_len(len: usize, ep: *const AmEnvParams, drift_ppm: f64, n_frames: *mut usize) -> c_int;
+    pub fn am_envelope(
+        device: c_int, signal: *const std::ffi::c_void, len: usize, sample_format: c_int, ep: *const AmEnvParams, drift_ppm: f64,
+        out: *mut u16, cap: usize, n_frames: *mut usize,
+    ) -> c_int;
+    pub fn am_envelope_device(
+        device: c_int, d_signal: *const std::ffi::c_void, len: usize, sample_format: c_int, ep: *const AmEnvParams, drift_ppm: f64,
+        out: *mut u16, cap: usize, n_frames: *mut usize,
+    ) -> c_int;
+    pub fn am_envelope_scores(
+        device: c_int, needles: *const u16, frames: *const u32, n_needles: u32, n_bands: u32, hay: *const u16, hay_frames: usize,
+        z: *mut f32, qi: *mut u32, cap: usize, n_out: *mut usize,
+    ) -> c_int;
+    pub fn am_envelope_scores_device(
+        device: c_int, d_needles: *const u16, frames: *const u32, n_needles: u32, n_bands: u32, d_hay: *const u16, hay_frames: usize,
+        z: *mut f32, qi: *mut u32, cap: usize, n_out: *mut usize,
+    ) -> c_int;
+    pub fn am_envelope_pick(
+        z: *const f32, qi: *const u32, n: usize, min_score: f32, separation: u64, out: *mut AmEnvPick, cap: usize, n_out: *mut usize,
+    ) -> c_int;
+    pub fn am_match_envelope(
+        h: *const AmNeedle, haystack: *const std::ffi::c_void, len: usize, sample_format: c_int, ep: *const AmEnvParams,
+        grid: *const AmEnvGrid, min_score: f32, out: *mut AmEnvHit, cap: usize, n_out: *mut usize,
+    ) -> c_int;
+    pub fn am_match_envelope_device(
+        h: *const AmNeedle, d_haystack: *const std::ffi::c_void, len: usize, sample_format: c_int, ep: *const AmEnvParams,
+        grid: *const AmEnvGrid, min_score: f32, out: *mut AmEnvHit, cap: usize, n_out: *mut usize,
+    ) -> c_int;
     /// calc_chunks on the lazy sample iterator (audio_matcher.rs:88-104, mp3_reader.rs:13-41)
     pub fn am_match_stream_begin(
         h: *const AmNeedle, sample_format: c_int, expected_len: usize, p: *const AmMatchParams, out: *mut *mut AmStream,
@@ -972,6 +1045,30 @@ impl HipConvolve {
         if rc != AM_OK {
             return Err(am_err(rc));
         }
+        Ok(out)
+    }
+
+    /// Envelope matching (am_match_envelope): the occurrences of this needle in the host haystack `m_samples` at any speed of
+    /// `grid`, found through the band-level envelopes of `bands` (floor 80 dB).  Starts are good to a few frames, drifts to a
+    /// grid step or two; a waveform search around a hit refines it.
+    pub fn match_envelope(&self, m_samples: &[f32], bands: &AmBandParams, grid: &AmEnvGrid, min_score: f32)
+                          -> Result<Vec<AmEnvHit>, Box<dyn std::error::Error>> {
+        let ep = AmEnvParams { bands: *bands, reserved: 0, floor_db: 80.0 };
+        let mut out = vec![AmEnvHit::default(); 64];
+        let mut n = 0usize;
+        let call = |out: &mut Vec<AmEnvHit>, n: &mut usize| unsafe {
+            am_match_envelope(self.h, m_samples.as_ptr() as *const std::ffi::c_void, m_samples.len(), AM_FMT_F32_MONO, &ep, grid,
+                              min_score, out.as_mut_ptr(), out.len(), n)
+        };
+        let mut rc = call(&mut out, &mut n);
+        if rc == AM_ERR_CAPACITY {
+            out.resize(n, AmEnvHit::default());
+            rc = call(&mut out, &mut n);
+        }
+        if rc != AM_OK {
+            return Err(am_err(rc));
+        }
+        out.truncate(n);
         Ok(out)
     }
 

@@ -725,6 +725,143 @@ int am_probe_scores_device(int device, const float* d_scores, size_t n, uint64_t
 int am_discover_regions(const am_probe_hit* hits, size_t n, const am_discover_params* dp,
                         const am_region_params* rp, am_region* out, size_t cap, size_t* n_out);
 
+/* ---- envelope matching: a needle played at another speed --------------------------------------------------------
+ * Every entry point above that FINDS a needle correlates waveforms: it finds an occurrence that runs on the needle's
+ * clock and keeps the needle's phases ("When a hit runs on another clock": a 10 s needle is followed to
+ * about 72 ppm).  A jingle from a playout machine running 3 % fast, a tape transfer or a chain that scrambles phases is
+ * never a hit.  This family matches band-level envelopes instead: a few wide frequency bands, one level per band and
+ * frame of a few milliseconds, the needle's level matrix correlated against the haystack's for each speed of a coarse
+ * grid.  The reference has no such stage.
+ *
+ * WHAT IT IS GOOD FOR.  Positions are good to a few frames, not to the sample.  The drift is good to about one or two
+ * grid steps on a 10 s needle and gets worse on shorter ones: its resolution is about (width of the envelope
+ * correlation peak, in frames) / J -- with a 2 s needle detection still works but the drift is crude, 1 - 2 %.  Bands
+ * should be wide, a third of an octave or more, so that the pitch shift of a speed change stays inside a band.
+ * Refining such a hit to the sample is deliberately not part of this family: it would be a local waveform search over
+ * +-H lags and a fine drift grid around each hit (am_hit_warp measures drift only up to AM_WARP_MAX_PPM).
+ *
+ * 1. The envelope of a signal (am_envelope_len, am_envelope, am_envelope_device).  ep->bands is an am_band_params as for
+ *    am_hit_bands (am_band_edges_log fills one); F = 2^frame_log2, H = F / 2, B = n_bands.  d = drift_ppm, |d| <=
+ *    AM_ENV_MAX_PPM.
+ *   frames     inc = llround(2^32 / (1 + d 1e-6)) in f64 on the host (the convention of am_hit_warp); frame j starts at
+ *              a_j = (j H inc + 2^31) >> 32 (u64; exactly j H for d = 0) and reads x[a_j .. a_j + F).  J = the count of j
+ *              with a_j + F <= len, 0 for len < F; am_envelope_len returns it.  Positive d: the frames sit closer
+ *              together -- the signal as it sounds when the occurrence is longer than the needle.  len <= AM_ENV_MAX_LEN.
+ *   band power window w[i] = 0.5 - 0.5 cos(2 pi i / F), X_j[k] the F-point spectrum of the windowed frame in f64,
+ *              P_b[j] = sum of |X_j[k]|^2 over the bins [edges[b], edges[b + 1]).  x is the f32 sample or the bit-exact
+ *              down-mix for AM_FMT_S16_STEREO.  Window and twiddles come from the host f64 table of am_hit_bands.
+ *   level      P0 = (F / 4)^2 10^(-floor_db / 10) ((F / 4)^2: the band power of a full-scale sine), v = 10 log10((P_b[j] +
+ *              P0) / P0), u_b[j] = min(llround(AM_ENV_STEPS_PER_DB v), AM_ENV_MAX_LEVEL) as uint16_t.  A frame of zeros
+ *              gives exactly 0.  The order of the f64 additions is not part of the contract: an implementation may differ
+ *              from another by 1 in cells whose 8 v lies within rounding of a half-integer (about 2 cells in a million).
+ *   absent     a frame that reads a non-finite sample is ABSENT: every band of it holds AM_ENV_ABSENT.
+ *   output     B x J levels, band-major (band b frame j at out[b J + j]), host memory.  cap counts frames: with cap < J
+ *              nothing is written and the call returns AM_ERR_CAPACITY with J in *n_frames.
+ *   Levels are integers on purpose: everything downstream is exact integer arithmetic, any order of additions gives
+ *   the same bits.
+ *
+ * 2. Scores of a bank of needle envelopes against a haystack envelope (am_envelope_scores, am_envelope_scores_device).
+ *   Q = n_needles matrices n_q of B x J_q levels (J_q = frames[q], 1 .. AM_ENV_MAX_FRAMES; 1 <= Q <= AM_ENV_MAX_NEEDLES;
+ *   B <= AM_BAND_MAX_BANDS), one behind the other in `needles` (matrix q starts at B sum_{p < q} J_p), and one haystack
+ *   matrix e of B x Jh levels (Jh <= AM_ENV_MAX_HAY_FRAMES).  A level is 0 .. AM_ENV_MAX_LEVEL or AM_ENV_ABSENT; a frame
+ *   is absent when a band of it holds AM_ENV_ABSENT.
+ *   T_q = Jh - J_q + 1 (0 if negative), n_out = max_q T_q.  For t < T_q, with J = J_q, all integers:
+ *     xc_b = sum_j n_q,b[j] e_b[t + j],  s1_b = sum_j e_b[t + j],  s2_b = sum_j e_b[t + j]^2,
+ *     N1_b = sum_j n_q,b[j],  N2_b = sum_j n_q,b[j]^2,
+ *     num = sum_b (J xc_b - N1_b s1_b),   D = sum_b (J s2_b - s1_b^2),   E = sum_b (J N2_b - N1_b^2),
+ *     score_q[t] = fl32((double)num / sqrt((double)E (double)D)).
+ *   The three integers are below 2^53 within the limits (16384^2 32 1023^2 < 2^53): their conversion is exact, the f64
+ *   multiply, sqrt and divide are rounded once each, so every score is defined to the bit.  The score is 0 where E = 0
+ *   or D = 0 (exact tests: a flat needle, a flat window such as digital silence) and NaN where the window or the needle
+ *   matrix holds an absent frame.
+ *   z[t] = the largest non-NaN score_q[t] over the q with t < T_q (NaN if there is none), qi[t] = its q, ties to the
+ *   lower q (AM_ENV_NO_Q beside a NaN).  Both have n_out entries in host memory; cap < n_out: AM_ERR_CAPACITY with what
+ *   fits filled and n_out in *n_out.
+ *   The kernels (am_envelope.hip): the haystack's prefix sums of e, e^2 and the absent marks (64-bit integers), then ONE
+ *   correlation launch in which a workgroup owns AM_ENV_TILE consecutive t, keeps the haystack rows it needs in LDS,
+ *   walks every needle in chunks of AM_ENV_CHUNK frames with packed 16-bit dot products (32-bit sums over at most 4096
+ *   products, then 64-bit) and folds the best (score, q) in registers: one haystack tile is read once for all Q.
+ *
+ * 3. The pick rule (am_envelope_pick, pure host).  Position t is kept iff z[t] is not NaN, z[t] >= min_score, no t' with
+ *   |t' - t| <= separation has z[t'] > z[t], and no such t' < t has z[t'] == z[t].  The output ascends in t.  Record:
+ *   frame = t; pos = t + e, e the vertex (a - c) / (2 (a - 2 b + c)) of the parabola through a = z[t - 1], b = z[t],
+ *   c = z[t + 1] in f64, clamped to +-0.5, and e = 0 at an end, beside a NaN or without a maximum (a - 2 b + c >= 0);
+ *   score = z[t]; q = qi[t].
+ *
+ * 4. The composition (am_match_envelope, am_match_envelope_device).  The grid's Q = 2 K + 1 drifts are d_q = centre_ppm +
+ *   max_ppm (q - K) / K as for am_warp_params (K = 0: the one drift centre_ppm), K <= AM_ENV_MAX_STEPS, max_ppm >= 0 and
+ *   > 0 when K > 0, |centre_ppm| + max_ppm <= AM_ENV_MAX_PPM.  The needle's envelope at each d_q comes from the handle's
+ *   whole needle on the device, the haystack's envelope at d = 0; then the scores, then the pick with separation = J_K
+ *   (the needle's frames at the centre drift).  Record am_env_hit: start = llround(pos H) clamped into [0, len),
+ *   drift_ppm = d_q, score, q, length = llround(S (1 + d_q 1e-6)).  Envelopes and scores stay on the device; only z and qi
+ *   (4 + 4 bytes per frame) and the hits come up.  The result does not depend on "score_norm" or any other process option.
+ *   A needle shorter than F (the first frame starts at 0 at every rate), or with more than AM_ENV_MAX_FRAMES frames at a
+ *   rate of the grid (use a larger frame_log2), is AM_ERR_INVALID_ARG.
+ *   len < F or fewer haystack frames than every needle envelope: AM_OK, no hits.
+ *
+ * AM_ERR_INVALID_ARG (the message names the field): a null pointer, reserved != 0, the rules of am_band_params, floor_db
+ * outside (0, 200] or NaN, |drift_ppm| > AM_ENV_MAX_PPM or NaN, len > AM_ENV_MAX_LEN, a bad sample format, a pointer that
+ * is not on the device (_device forms), n_needles = 0 or > AM_ENV_MAX_NEEDLES, n_bands = 0 or > AM_BAND_MAX_BANDS,
+ * frames[q] = 0 or > AM_ENV_MAX_FRAMES, hay_frames > AM_ENV_MAX_HAY_FRAMES, a level above AM_ENV_MAX_LEVEL other than
+ * AM_ENV_ABSENT, a NaN min_score, the grid's rules.
+ * Measured on an MI355X: tools/envelope_bench.py, profiles/r25/. */
+#define AM_ENV_STEPS_PER_DB   8
+#define AM_ENV_MAX_LEVEL      1023
+#define AM_ENV_ABSENT         0xFFFFu
+#define AM_ENV_NO_Q           0xFFFFFFFFu
+#define AM_ENV_MAX_PPM        250000
+#define AM_ENV_MAX_FRAMES     16384
+#define AM_ENV_MAX_NEEDLES    257
+#define AM_ENV_MAX_STEPS      128
+#define AM_ENV_MAX_LEN        (1ull << 31)
+#define AM_ENV_MAX_HAY_FRAMES (1u << 24)
+#define AM_ENV_TILE           512               /* consecutive t one workgroup of the correlation kernel owns */
+#define AM_ENV_CHUNK          8                 /* needle frames per step of its inner loop */
+typedef struct am_env_params {
+    am_band_params bands;     /* frame_log2, B and the band edges, as for am_hit_bands */
+    uint32_t reserved;        /* 0 */
+    double   floor_db;        /* P0 lies this many dB below a full-scale sine; 80 is a good default */
+} am_env_params;              /* 152 bytes, no padding */
+typedef struct am_env_grid {
+    double   centre_ppm;      /* the middle of the drift grid */
+    double   max_ppm;         /* its half width */
+    uint32_t steps;           /* K, 0 .. AM_ENV_MAX_STEPS: 2 K + 1 drifts */
+    uint32_t reserved;        /* 0 */
+} am_env_grid;                /* 24 bytes, no padding */
+typedef struct am_env_pick {
+    uint64_t frame;           /* t */
+    double   pos;             /* t + the parabola's vertex, in frames */
+    float    score;           /* z[t] */
+    uint32_t q;               /* qi[t] */
+} am_env_pick;                /* 24 bytes, no padding */
+typedef struct am_env_hit {
+    uint64_t start;           /* llround(pos H), clamped into [0, len): good to a few frames */
+    uint64_t length;          /* llround(S (1 + d_q 1e-6)): the occurrence's length in haystack samples */
+    double   drift_ppm;       /* d_q */
+    float    score;
+    uint32_t q;
+} am_env_hit;                 /* 32 bytes, no padding */
+int am_envelope_len(size_t len, const am_env_params* ep, double drift_ppm, size_t* n_frames);
+int am_envelope(int device, const void* signal, size_t len, int sample_format, const am_env_params* ep,
+                double drift_ppm, uint16_t* out, size_t cap, size_t* n_frames);
+int am_envelope_device(int device, const void* d_signal, size_t len, int sample_format, const am_env_params* ep,
+                       double drift_ppm, uint16_t* out, size_t cap, size_t* n_frames);
+int am_envelope_scores(int device, const uint16_t* needles, const uint32_t* frames, uint32_t n_needles,
+                       uint32_t n_bands, const uint16_t* hay, size_t hay_frames,
+                       float* z, uint32_t* qi, size_t cap, size_t* n_out);
+/* needles and hay in memory of `device` (2-byte aligned); frames, z and qi in host memory */
+int am_envelope_scores_device(int device, const uint16_t* d_needles, const uint32_t* frames, uint32_t n_needles,
+                              uint32_t n_bands, const uint16_t* d_hay, size_t hay_frames,
+                              float* z, uint32_t* qi, size_t cap, size_t* n_out);
+int am_envelope_pick(const float* z, const uint32_t* qi, size_t n, float min_score, uint64_t separation,
+                     am_env_pick* out, size_t cap, size_t* n_out);
+int am_match_envelope(const am_needle* h, const void* haystack, size_t len, int sample_format,
+                      const am_env_params* ep, const am_env_grid* grid, float min_score,
+                      am_env_hit* out, size_t cap, size_t* n_out);
+int am_match_envelope_device(const am_needle* h, const void* d_haystack, size_t len, int sample_format,
+                             const am_env_params* ep, const am_env_grid* grid, float min_score,
+                             am_env_hit* out, size_t cap, size_t* n_out);
+
 
 /* ---- ingest: PCM -> f32 mono -------------------------------------------- */
 /* mp3_reader.rs:12, 28-37: mono = (l as f32 + r as f32) * 0.5 * (1/65535) */
@@ -1410,7 +1547,9 @@ int am_set_chunk_progress_callback(am_chunk_progress_fn fn, void* user);
  * summed elapsed time and launch count of kernels whose name matches `kernel`
  * exactly ("k1_cols_fwd", "k2_rows", "k3_cols_inv", "tile_stats",
  * "peaks", "other", "trace" -- the score-trace kernels --, "discover" -- the
- * kernels of needle discovery -- or "*" for all). */
+ * kernels of needle discovery --, "envelope_frames", "envelope_prefix",
+ * "envelope_correlate" -- the levels, the prefix sums and the correlation of
+ * envelope matching; "envelope" adds the three -- or "*" for all). */
 int am_profile_enable(int device, int on);
 int am_profile_reset(int device);
 int am_profile_query(int device, const char* kernel, double* total_ms, uint64_t* launches);

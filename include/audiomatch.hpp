@@ -401,6 +401,41 @@ public:
         for (std::size_t i = 0; i < nh; ++i) out[i].assign(buf.begin() + (std::ptrdiff_t)(i * cap), buf.begin() + (std::ptrdiff_t)(i * cap + n[i]));
         return out;
     }
+    // runs call(out, cap, &n) on a growing record buffer until it fits
+    template <class Call>
+    static std::vector<am_env_hit> env_hits_filled(Call call) {
+        std::vector<am_env_hit> out(64);
+        std::size_t n = 0;
+        int rc = call(out.data(), out.size(), &n);
+        if (rc == AM_ERR_CAPACITY) {
+            out.resize(n);
+            rc = call(out.data(), out.size(), &n);
+        }
+        check(rc);
+        out.resize(std::min(n, out.size()));
+        return out;
+    }
+    // envelope matching (am_match_envelope): this needle played at any speed of `grid`, found through its band-level
+    // envelopes -- starts good to a few frames, drifts to a grid step or two; am_match_envelope_device for a resident haystack
+    std::vector<am_env_hit> match_envelope(const void* haystack, std::size_t len, int sample_format, const am_env_params& ep,
+                                           const am_env_grid& grid, float min_score) const {
+        return env_hits_filled([&](am_env_hit* out, std::size_t cap, std::size_t* n) {
+            return am_match_envelope(h_, haystack, len, sample_format, &ep, &grid, min_score, out, cap, n);
+        });
+    }
+    std::vector<am_env_hit> match_envelope_device(const void* d_haystack, std::size_t len, int sample_format, const am_env_params& ep,
+                                                  const am_env_grid& grid, float min_score) const {
+        return env_hits_filled([&](am_env_hit* out, std::size_t cap, std::size_t* n) {
+            return am_match_envelope_device(h_, d_haystack, len, sample_format, &ep, &grid, min_score, out, cap, n);
+        });
+    }
+    // am_env_params over bands (band_edges_log) with the level floor in dB below a full-scale sine
+    static am_env_params env_params(const am_band_params& bands, double floor_db = 80.0) {
+        am_env_params ep{};
+        ep.bands = bands;
+        ep.floor_db = floor_db;
+        return ep;
+    }
     // per-handle "log_n" / "half_pipeline" / "score_norm" (-1 = follow the process default)
     void set_option(const char* key, long long value) { check(am_needle_set_option(h_, key, value)); }
 
@@ -505,6 +540,57 @@ inline std::vector<am_region> discover_regions(const std::vector<am_probe_hit>& 
     std::vector<am_region> out(hits.size());   // (a region holds at least one probe)
     std::size_t n = 0;
     check(am_discover_regions(hits.data(), hits.size(), &dp, &rp, out.data(), out.size(), &n));
+    out.resize(std::min(n, out.size()));
+    return out;
+}
+
+// envelope matching on its own (am_envelope*, am_envelope_scores*, am_envelope_pick): the band levels of a signal read at
+// drift_ppm (n_bands x J uint16, band-major; host memory / memory of `device`), the scores of a bank of needle level
+// matrices against a haystack's, and the pick rule on any (z, qi) (no device needed)
+inline std::size_t envelope_len(std::size_t len, const am_env_params& ep, double drift_ppm = 0.0) {
+    std::size_t n = 0;
+    check(am_envelope_len(len, &ep, drift_ppm, &n));
+    return n;
+}
+inline std::vector<std::uint16_t> envelope(const void* signal, std::size_t len, int sample_format, const am_env_params& ep,
+                                           double drift_ppm = 0.0, int device = 0) {
+    const std::size_t j = envelope_len(len, ep, drift_ppm);
+    std::vector<std::uint16_t> out(std::max<std::size_t>(1, ep.bands.n_bands * j));
+    std::size_t n = 0;
+    check(am_envelope(device, signal, len, sample_format, &ep, drift_ppm, out.data(), j, &n));
+    out.resize(ep.bands.n_bands * n);
+    return out;
+}
+inline std::vector<std::uint16_t> envelope_device(const void* d_signal, std::size_t len, int sample_format, const am_env_params& ep,
+                                                  double drift_ppm = 0.0, int device = 0) {
+    const std::size_t j = envelope_len(len, ep, drift_ppm);
+    std::vector<std::uint16_t> out(std::max<std::size_t>(1, ep.bands.n_bands * j));
+    std::size_t n = 0;
+    check(am_envelope_device(device, d_signal, len, sample_format, &ep, drift_ppm, out.data(), j, &n));
+    out.resize(ep.bands.n_bands * n);
+    return out;
+}
+struct EnvScores { std::vector<float> z; std::vector<std::uint32_t> qi; };
+inline EnvScores envelope_scores(const std::uint16_t* needles, const std::vector<std::uint32_t>& frames, std::uint32_t n_bands,
+                                 const std::uint16_t* hay, std::size_t hay_frames, int device = 0, bool resident = false) {
+    std::size_t cap = 0;
+    for (std::uint32_t j : frames)
+        if (hay_frames >= j) cap = std::max(cap, hay_frames - j + 1);
+    EnvScores r{std::vector<float>(std::max<std::size_t>(1, cap)), std::vector<std::uint32_t>(std::max<std::size_t>(1, cap))};
+    std::size_t n = 0;
+    const std::uint32_t q = (std::uint32_t)frames.size();
+    check(resident ? am_envelope_scores_device(device, needles, frames.data(), q, n_bands, hay, hay_frames, r.z.data(), r.qi.data(), cap, &n)
+                   : am_envelope_scores(device, needles, frames.data(), q, n_bands, hay, hay_frames, r.z.data(), r.qi.data(), cap, &n));
+    r.z.resize(n);
+    r.qi.resize(n);
+    return r;
+}
+inline std::vector<am_env_pick> envelope_pick(const std::vector<float>& z, const std::vector<std::uint32_t>& qi, float min_score,
+                                              std::uint64_t separation) {
+    if (z.size() != qi.size()) check(AM_ERR_INVALID_ARG);
+    std::vector<am_env_pick> out(z.size());
+    std::size_t n = 0;
+    check(am_envelope_pick(z.data(), qi.data(), z.size(), min_score, separation, out.data(), out.size(), &n));
     out.resize(std::min(n, out.size()));
     return out;
 }
