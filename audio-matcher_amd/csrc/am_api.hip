@@ -81,13 +81,12 @@ static int correlate_impl(const am_needle* hc, const float* within, size_t w, in
     const long long lead = (long long)(s - 1) - (long long)start;
     Ctx* c = h->ctx;
     std::lock_guard<std::recursive_mutex> lk(c->mu);
-    const float* d_in = within;
+    const void* d_within = nullptr;
+    if ((rc = resident_input(c, device_io, within, sample_bytes(w), &d_within))) return rc;
+    const float* d_in = static_cast<const float*>(d_within);
     float* d_out = out;
     if (!device_io) {
-        if ((rc = c->io_in.ensure(w * sizeof(float)))) return rc;
         if ((rc = c->io_out.ensure(len * sizeof(float)))) return rc;
-        AM_HIP(copy_on_stream(c, c->io_in.p, within, w * sizeof(float), hipMemcpyHostToDevice));
-        d_in = (const float*)c->io_in.p;
         d_out = (float*)c->io_out.p;
     }
     Opts o = snapshot_opts(h);
@@ -117,8 +116,7 @@ static int correlate_impl(const am_needle* hc, const float* within, size_t w, in
         if (flag) AM_HIP(hipMemsetD32Async((hipDeviceptr_t)d_out, 0x7FC00000, len, c->stream));
     }
     AM_HIP(hipStreamSynchronize(c->stream));
-    if (!device_io) AM_HIP(copy_on_stream(c, out, d_out, len * sizeof(float), hipMemcpyDeviceToHost));
-    return AM_OK;
+    return device_io ? AM_OK : download(c, out, d_out, len * sizeof(float));
 }
 
 int am_correlate(const am_needle* h, const float* within, size_t w, int mode, int scale,
@@ -131,20 +129,9 @@ int am_correlate_device(const am_needle* h, const float* d_within, size_t w, int
     return correlate_impl(h, d_within, w, mode, scale, d_out, cap, out_len, true);
 }
 
-int am_match_device(const am_needle* hc, const float* d_haystack, size_t len,
-                    const am_match_params* p, am_peak* out, size_t cap, size_t* n_out) {
-    am_needle* h = const_cast<am_needle*>(hc);
-    int rc = check_needle(h);
-    if (rc) return rc;
-    if (!d_haystack || !p || !n_out || (!out && cap)) return fail(AM_ERR_INVALID_ARG, "null pointer");
-    if (len == 0) { *n_out = 0; return AM_OK; }
-    std::lock_guard<std::recursive_mutex> lk(h->ctx->mu);
-    const void* src = d_haystack;
-    return match_many(h, &src, &len, 1, p, out, cap, n_out);
-}
-
-int am_match(const am_needle* hc, const float* haystack, size_t len,
-             const am_match_params* p, am_peak* out, size_t cap, size_t* n_out) {
+// am_match / am_match_pcm16 (src_kind 1: interleaved i16 stereo) and their _device forms
+static int match_impl(const am_needle* hc, const void* haystack, size_t len, const am_match_params* p, am_peak* out, size_t cap,
+                      size_t* n_out, int src_kind, bool device_io) {
     am_needle* h = const_cast<am_needle*>(hc);
     int rc = check_needle(h);
     if (rc) return rc;
@@ -152,10 +139,19 @@ int am_match(const am_needle* hc, const float* haystack, size_t len,
     if (len == 0) { *n_out = 0; return AM_OK; }
     Ctx* c = h->ctx;
     std::lock_guard<std::recursive_mutex> lk(c->mu);
-    if ((rc = c->io_in.ensure(len * sizeof(float)))) return rc;
-    AM_HIP(copy_on_stream(c, c->io_in.p, haystack, len * sizeof(float), hipMemcpyHostToDevice));
-    const void* d_in = c->io_in.p;
-    return match_many(h, &d_in, &len, 1, p, out, cap, n_out);
+    const void* d_in = nullptr;
+    if ((rc = resident_input(c, device_io, haystack, sample_bytes(len), &d_in))) return rc;
+    return match_many(h, &d_in, &len, 1, p, out, cap, n_out, src_kind);
+}
+
+int am_match_device(const am_needle* h, const float* d_haystack, size_t len,
+                    const am_match_params* p, am_peak* out, size_t cap, size_t* n_out) {
+    return match_impl(h, d_haystack, len, p, out, cap, n_out, 0, true);
+}
+
+int am_match(const am_needle* h, const float* haystack, size_t len,
+             const am_match_params* p, am_peak* out, size_t cap, size_t* n_out) {
+    return match_impl(h, haystack, len, p, out, cap, n_out, 0, false);
 }
 
 int am_match_batch_device(const am_needle* hc, const float* const* d_haystacks, const size_t* lens,
@@ -190,12 +186,12 @@ int am_match_multi_batch_device(const am_needle* const* needles, size_t n_needle
                                 am_peak* out, size_t cap_per_pair, size_t* n_out) {
     if (!needles || n_needles == 0 || !d_haystacks || !lens || !p || !n_out || (!out && cap_per_pair))
         return fail(AM_ERR_INVALID_ARG, "null pointer");
-    if (sample_format != AM_FMT_F32_MONO && sample_format != AM_FMT_S16_STEREO) return fail(AM_ERR_INVALID_ARG, "bad sample format");
+    int rc = check_format(sample_format);
+    if (rc) return rc;
     for (size_t k = 0; k < n_needles; ++k)
         if (!needles[k] || !needles[k]->ctx) return fail(AM_ERR_INVALID_ARG, "null needle handle");
     am_needle* h0 = const_cast<am_needle*>(needles[0]);
-    int rc = check_needle(h0);
-    if (rc) return rc;
+    if ((rc = check_needle(h0))) return rc;
     if (n_hay == 0) return AM_OK;
     if (snapshot_opts(h0).score_norm) return fail(AM_ERR_INVALID_ARG, AM_NORM_UNSUPPORTED);
     std::lock_guard<std::recursive_mutex> lk(h0->ctx->mu);
@@ -206,14 +202,14 @@ int am_match_multi_batch_device(const am_needle* const* needles, size_t n_needle
 // ---- several needles of any lengths (match_multi_many with `varlen`) ----
 static int check_multi_varlen(const am_needle* const* needles, size_t n_needles, int sample_format, const am_match_params* p, am_needle** h0) {
     if (!needles || n_needles == 0 || !p) return fail(AM_ERR_INVALID_ARG, "null pointer");
-    if (sample_format != AM_FMT_F32_MONO && sample_format != AM_FMT_S16_STEREO) return fail(AM_ERR_INVALID_ARG, "bad sample format");
+    int rc = check_format(sample_format);
+    if (rc) return rc;
     for (size_t k = 0; k < n_needles; ++k)
         if (!needles[k] || !needles[k]->ctx) return fail(AM_ERR_INVALID_ARG, "null needle handle");
     for (size_t k = 1; k < n_needles; ++k)
         if (needles[k]->ctx != needles[0]->ctx) return fail(AM_ERR_INVALID_ARG, "needles must live on one device");
     *h0 = const_cast<am_needle*>(needles[0]);
-    int rc = check_needle(*h0);
-    if (rc) return rc;
+    if ((rc = check_needle(*h0))) return rc;
     if (snapshot_opts(*h0).score_norm) return fail(AM_ERR_INVALID_ARG, AM_NORM_UNSUPPORTED);
     return AM_OK;
 }
@@ -245,41 +241,22 @@ int am_match_multi_varlen(const am_needle* const* needles, size_t n_needles, con
     }
     Ctx* c = h0->ctx;
     std::lock_guard<std::recursive_mutex> lk(c->mu);
-    const size_t bytes = len * (sample_format == AM_FMT_S16_STEREO ? 2 * sizeof(int16_t) : sizeof(float));
-    if ((rc = c->io_in.ensure(bytes))) return rc;
-    AM_HIP(copy_on_stream(c, c->io_in.p, haystack, bytes, hipMemcpyHostToDevice));
-    const void* d_in = c->io_in.p;
+    const void* d_in = nullptr;
+    if ((rc = upload_input(c, haystack, sample_bytes(len), &d_in))) return rc;
     return match_multi_many(const_cast<am_needle* const*>(needles), n_needles, &d_in, &len, 1, sample_format, p, out, cap_per_needle, n_out,
                             0, 1, overlaps, true);
 }
 
 // ---- the same three entry points on interleaved i16 stereo PCM: the down-mix of
 // mp3_reader.rs:28-37 happens inside K1's loads, so the haystack is read once ----
-int am_match_pcm16_device(const am_needle* hc, const int16_t* d_interleaved, size_t frames,
+int am_match_pcm16_device(const am_needle* h, const int16_t* d_interleaved, size_t frames,
                           const am_match_params* p, am_peak* out, size_t cap, size_t* n_out) {
-    am_needle* h = const_cast<am_needle*>(hc);
-    int rc = check_needle(h);
-    if (rc) return rc;
-    if (!d_interleaved || !p || !n_out || (!out && cap)) return fail(AM_ERR_INVALID_ARG, "null pointer");
-    if (frames == 0) { *n_out = 0; return AM_OK; }
-    std::lock_guard<std::recursive_mutex> lk(h->ctx->mu);
-    const void* src = d_interleaved;
-    return match_many(h, &src, &frames, 1, p, out, cap, n_out, 1);
+    return match_impl(h, d_interleaved, frames, p, out, cap, n_out, 1, true);
 }
 
-int am_match_pcm16(const am_needle* hc, const int16_t* interleaved, size_t frames,
+int am_match_pcm16(const am_needle* h, const int16_t* interleaved, size_t frames,
                    const am_match_params* p, am_peak* out, size_t cap, size_t* n_out) {
-    am_needle* h = const_cast<am_needle*>(hc);
-    int rc = check_needle(h);
-    if (rc) return rc;
-    if (!interleaved || !p || !n_out || (!out && cap)) return fail(AM_ERR_INVALID_ARG, "null pointer");
-    if (frames == 0) { *n_out = 0; return AM_OK; }
-    Ctx* c = h->ctx;
-    std::lock_guard<std::recursive_mutex> lk(c->mu);
-    if ((rc = c->io_in.ensure(frames * 2 * sizeof(int16_t)))) return rc;
-    AM_HIP(copy_on_stream(c, c->io_in.p, interleaved, frames * 2 * sizeof(int16_t), hipMemcpyHostToDevice));
-    const void* d_in = c->io_in.p;
-    return match_many(h, &d_in, &frames, 1, p, out, cap, n_out, 1);
+    return match_impl(h, interleaved, frames, p, out, cap, n_out, 1, false);
 }
 
 int am_match_pcm16_batch_device(const am_needle* hc, const int16_t* const* d_interleaved, const size_t* frames,
@@ -304,15 +281,12 @@ int am_find_peaks(int device, const float* scores, size_t n, float min_prominenc
     *n_out = 0;
     if (n == 0) return AM_OK;
     std::lock_guard<std::recursive_mutex> lk(c->mu);
-    if ((rc = c->io_in.ensure(n * sizeof(float)))) return rc;
-    AM_HIP(copy_on_stream(c, c->io_in.p, scores, n * sizeof(float), hipMemcpyHostToDevice));
+    const void* d_scores = nullptr;
+    if ((rc = upload_input(c, scores, sample_bytes(n), &d_scores))) return rc;
     std::vector<am_peak> all;
-    if ((rc = find_peaks_host_array(c, (const float*)c->io_in.p, (long long)n, min_prominence,
+    if ((rc = find_peaks_host_array(c, (const float*)d_scores, (long long)n, min_prominence,
                                     (long long)min_distance, all))) return rc;
-    *n_out = all.size();
-    for (size_t i = 0; i < all.size() && i < cap; ++i) out[i] = all[i];
-    if (all.size() > cap) return fail(AM_ERR_CAPACITY, "peak output buffer too small");
-    return AM_OK;
+    return hand_back(all, out, cap, n_out, "peak output buffer too small");
 }
 
 // ---- the k best matches (am_best.hip) ----
@@ -320,37 +294,38 @@ static int best_check(const am_needle* h, int sample_format, const am_best_param
     int rc = check_needle(h);
     if (rc) return rc;
     if (!bp) return fail(AM_ERR_INVALID_ARG, "null pointer");
-    if (sample_format != AM_FMT_F32_MONO && sample_format != AM_FMT_S16_STEREO) return fail(AM_ERR_INVALID_ARG, "bad sample format");
+    if ((rc = check_format(sample_format))) return rc;
     if (bp->k == 0) return fail(AM_ERR_INVALID_ARG, "k must be at least 1");
     if (bp->scale != AM_SCALE_NONE && bp->scale != AM_SCALE_LIB)
         return fail(AM_ERR_INVALID_ARG, "am_match_best: scale must be AM_SCALE_NONE or AM_SCALE_LIB (AM_SCALE_MY depends on a chunk)");
     return norm_check(norm_spec(h, snapshot_opts(h)), bp->scale);
 }
 
-int am_match_best_device(const am_needle* hc, const void* d_haystack, size_t len, int sample_format,
-                         const am_best_params* bp, am_peak* out, size_t* n_out) {
-    am_needle* h = const_cast<am_needle*>(hc);
-    int rc = best_check(h, sample_format, bp);
-    if (rc) return rc;
-    if (!d_haystack || !out || !n_out) return fail(AM_ERR_INVALID_ARG, "null pointer");
-    std::lock_guard<std::recursive_mutex> lk(h->ctx->mu);
-    return match_best_one(h, d_haystack, len, sample_format, bp, out, n_out);
-}
-
-int am_match_best(const am_needle* hc, const void* haystack, size_t len, int sample_format,
-                  const am_best_params* bp, am_peak* out, size_t* n_out) {
+static int match_best_impl(const am_needle* hc, const void* haystack, size_t len, int sample_format, const am_best_params* bp,
+                           am_peak* out, size_t* n_out, bool device_io) {
     am_needle* h = const_cast<am_needle*>(hc);
     int rc = best_check(h, sample_format, bp);
     if (rc) return rc;
     if (!haystack || !out || !n_out) return fail(AM_ERR_INVALID_ARG, "null pointer");
-    *n_out = 0;
-    if (len < h->n) return AM_OK;
+    if (!device_io) {   // (the host form answers a haystack shorter than the needle here, the _device form in match_best_one)
+        *n_out = 0;
+        if (len < h->n) return AM_OK;
+    }
     Ctx* c = h->ctx;
     std::lock_guard<std::recursive_mutex> lk(c->mu);
-    const size_t bytes = len * (sample_format == AM_FMT_S16_STEREO ? 2 * sizeof(int16_t) : sizeof(float));
-    if ((rc = c->io_in.ensure(bytes))) return rc;
-    AM_HIP(copy_on_stream(c, c->io_in.p, haystack, bytes, hipMemcpyHostToDevice));
-    return match_best_one(h, c->io_in.p, len, sample_format, bp, out, n_out);
+    const void* d_hay = nullptr;
+    if ((rc = resident_input(c, device_io, haystack, sample_bytes(len), &d_hay))) return rc;
+    return match_best_one(h, d_hay, len, sample_format, bp, out, n_out);
+}
+
+int am_match_best_device(const am_needle* h, const void* d_haystack, size_t len, int sample_format,
+                         const am_best_params* bp, am_peak* out, size_t* n_out) {
+    return match_best_impl(h, d_haystack, len, sample_format, bp, out, n_out, true);
+}
+
+int am_match_best(const am_needle* h, const void* haystack, size_t len, int sample_format,
+                  const am_best_params* bp, am_peak* out, size_t* n_out) {
+    return match_best_impl(h, haystack, len, sample_format, bp, out, n_out, false);
 }
 
 int am_match_best_batch_device(const am_needle* hc, const void* const* d_haystacks, const size_t* lens,
@@ -387,14 +362,10 @@ static int find_peaks_top_impl(int device, const float* scores, size_t n, float 
     *n_out = 0;
     if (n == 0) return AM_OK;
     std::lock_guard<std::recursive_mutex> lk(c->mu);
-    const float* d_scores = scores;
-    if (!device_io) {
-        if ((rc = c->io_in.ensure(n * sizeof(float)))) return rc;
-        AM_HIP(copy_on_stream(c, c->io_in.p, scores, n * sizeof(float), hipMemcpyHostToDevice));
-        d_scores = (const float*)c->io_in.p;
-    }
+    const void* d_scores = nullptr;
+    if ((rc = resident_input(c, device_io, scores, sample_bytes(n), &d_scores))) return rc;
     std::vector<am_peak> res;
-    if ((rc = best_select(c, d_scores, (long long)n, min_prominence, (long long)std::min<uint64_t>(min_distance, (uint64_t)LLONG_MAX),
+    if ((rc = best_select(c, (const float*)d_scores, (long long)n, min_prominence, (long long)std::min<uint64_t>(min_distance, (uint64_t)LLONG_MAX),
                           k, snapshot_opts(nullptr).peak_policy(), res))) return rc;
     for (size_t i = 0; i < res.size(); ++i) out[i] = res[i];
     *n_out = res.size();
@@ -430,13 +401,11 @@ int am_pcm_s16_stereo_to_mono(int device, const int16_t* interleaved, size_t fra
     if (rc) return rc;
     if (frames == 0) return AM_OK;
     std::lock_guard<std::recursive_mutex> lk(c->mu);
-    if ((rc = c->io_in.ensure(frames * 2 * sizeof(int16_t)))) return rc;
-    if ((rc = c->io_out.ensure(frames * sizeof(float)))) return rc;
-    AM_HIP(copy_on_stream(c, c->io_in.p, interleaved, frames * 2 * sizeof(int16_t), hipMemcpyHostToDevice));
-    AM_HIP(launch_pcm_downmix(c->stream, (const int16_t*)c->io_in.p, (long long)frames, (float*)c->io_out.p));
+    const void* d_in = nullptr;
+    if ((rc = upload_input(c, interleaved, sample_bytes(frames), &d_in)) || (rc = c->io_out.ensure(frames * sizeof(float)))) return rc;
+    AM_HIP(launch_pcm_downmix(c->stream, (const int16_t*)d_in, (long long)frames, (float*)c->io_out.p));
     AM_HIP(hipStreamSynchronize(c->stream));
-    AM_HIP(copy_on_stream(c, out, c->io_out.p, frames * sizeof(float), hipMemcpyDeviceToHost));
-    return AM_OK;
+    return download(c, out, c->io_out.p, frames * sizeof(float));
 }
 
 int am_device_malloc(int device, size_t bytes, void** out) {

@@ -292,11 +292,10 @@ int scan_with_transitions(Ctx* c, BestScan s, std::vector<long long>& trans) {
         AM_HIP(hipGetLastError());
     }
     BestCounters cnt{};
-    AM_HIP(hipMemcpyAsync(&cnt, bb.cnt, sizeof(cnt), hipMemcpyDeviceToHost, c->stream));
-    AM_HIP(hipStreamSynchronize(c->stream));
+    int rc;
+    if ((rc = download(c, &cnt, bb.cnt, sizeof(cnt)))) return rc;
     trans.clear();
     if (cnt.ntrans == 0) return AM_OK;
-    int rc;
     if (cnt.ntrans > kBestTransCap) {
         if ((rc = c->best_trans.ensure(sizeof(long long) * cnt.ntrans))) return rc;
         BestScan t = s;
@@ -306,8 +305,7 @@ int scan_with_transitions(Ctx* c, BestScan s, std::vector<long long>& trans) {
         AM_HIP(hipGetLastError());
     }
     trans.resize(cnt.ntrans);
-    AM_HIP(hipMemcpyAsync(trans.data(), c->best_trans.p, sizeof(long long) * cnt.ntrans, hipMemcpyDeviceToHost, c->stream));
-    AM_HIP(hipStreamSynchronize(c->stream));
+    if ((rc = download(c, trans.data(), c->best_trans.p, sizeof(long long) * cnt.ntrans))) return rc;
     std::sort(trans.begin(), trans.end());
     return AM_OK;
 }
@@ -346,8 +344,7 @@ int best_select(Ctx* c, const float* d_g, long long n, float min_prom, long long
     std::vector<unsigned> hist(kBestBins), hist2(kBestBins);
     BestCounters cnt{};
     AM_HIP(hipMemcpyAsync(hist.data(), bb.hist, 4 * kBestBins, hipMemcpyDeviceToHost, c->stream));
-    AM_HIP(hipMemcpyAsync(&cnt, bb.cnt, sizeof(cnt), hipMemcpyDeviceToHost, c->stream));
-    AM_HIP(hipStreamSynchronize(c->stream));
+    if ((rc = download(c, &cnt, bb.cnt, sizeof(cnt)))) return rc;
     const long long total = (long long)cnt.nmax;
     if (total == 0) return AM_OK;
     if (!finite) {   // (sorted, for the walks' binary search)
@@ -364,8 +361,7 @@ int best_select(Ctx* c, const float* d_g, long long n, float min_prom, long long
                 hipLaunchKernelGGL(best_refine, dim3(grid_for(ntiles)), dim3(256), 0, c->stream, d_g, n, ntiles,
                                    (const unsigned*)c->best_lmax.p, (unsigned)b, bb.hist2);
                 AM_HIP(hipGetLastError());
-                AM_HIP(hipMemcpyAsync(hist2.data(), bb.hist2, 4 * kBestBins, hipMemcpyDeviceToHost, c->stream));
-                AM_HIP(hipStreamSynchronize(c->stream));
+                if ((rc = download(c, hist2.data(), bb.hist2, 4 * kBestBins))) return rc;
                 refined_bin = b;
             }
             if (refined_bin == b) {
@@ -415,8 +411,7 @@ int best_select(Ctx* c, const float* d_g, long long n, float min_prom, long long
             AM_HIP(hipMemcpyAsync(&got, &bb.cnt->nlist, sizeof(unsigned), hipMemcpyDeviceToHost, c->stream));
             const size_t old = cands.size();
             cands.resize(old + (size_t)fresh);
-            AM_HIP(hipMemcpyAsync(cands.data() + old, c->best_list.p, sizeof(BestCand) * (size_t)fresh, hipMemcpyDeviceToHost, c->stream));
-            AM_HIP(hipStreamSynchronize(c->stream));
+            if ((rc = download(c, cands.data() + old, c->best_list.p, sizeof(BestCand) * (size_t)fresh))) return rc;
             if ((long long)got != fresh) return fail(AM_ERR_PEAK_OVERFLOW, "k-best selection: candidate list does not match its histogram");
             std::sort(cands.begin() + old, cands.end(), [](const BestCand& x, const BestCand& y) {
                 return x.h > y.h || (x.h == y.h && x.ps < y.ps);

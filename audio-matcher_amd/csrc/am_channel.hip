@@ -393,7 +393,7 @@ struct ChanFamily {
 // the format and the parameters, before anything that needs a device
 int chan_prelude(int sample_format, const am_channel_params* cp) {
     int rc;
-    if ((rc = hit_check_format(sample_format))) return rc;
+    if ((rc = check_format(sample_format))) return rc;
     return cp ? chan_check_params(cp) : AM_OK;
 }
 
@@ -445,7 +445,7 @@ int am_channel_solve(const double* r, const double* c, uint32_t radius, double n
 int am_hit_residual(const void* haystack, size_t len, int sample_format, uint64_t start, const float* needle, size_t s, const float* taps,
                     uint32_t radius, float* model, float* resid) {
     int rc;
-    if ((rc = hit_check_format(sample_format))) return rc;
+    if ((rc = check_format(sample_format))) return rc;
     if (!needle || !taps || (!haystack && len > 0)) return fail(AM_ERR_INVALID_ARG, "null pointer");
     if (s == 0) return fail(AM_ERR_INVALID_ARG, "residual: the needle must hold at least 1 sample");
     if (radius > AM_CHAN_MAX_RADIUS)

@@ -202,6 +202,37 @@ hipError_t copy_on_stream(Ctx* c, void* dst, const void* src, size_t bytes, hipM
     return hipStreamSynchronize(c->stream);
 }
 
+// ---- the steps the entry points share (contracts: am_internal.h) ----------------
+int check_format(int sample_format, const char* who) {
+    if (sample_format == AM_FMT_F32_MONO || sample_format == AM_FMT_S16_STEREO) return AM_OK;
+    const std::string text = "bad sample format";
+    return fail(AM_ERR_INVALID_ARG, who ? std::string(who) + ": " + text + " " + std::to_string(sample_format) : text);
+}
+
+int upload_input(Ctx* c, const void* host, size_t bytes, const void** d) {
+    int rc = c->io_in.ensure(bytes);
+    if (rc) return rc;
+    AM_HIP(copy_on_stream(c, c->io_in.p, host, bytes, hipMemcpyHostToDevice));
+    *d = c->io_in.p;
+    return AM_OK;
+}
+
+int download(Ctx* c, void* host, const void* dev, size_t bytes) {
+    AM_HIP(copy_on_stream(c, host, dev, bytes, hipMemcpyDeviceToHost));
+    return AM_OK;
+}
+
+int check_device_arg(const void* p, int device, const char* prefix) {
+    const int rc = hit_check_device(p, device, HitWhere{-1, 0, 0, 0});
+    return rc ? fail(rc, prefix + t_err) : AM_OK;
+}
+
+int resident_input(Ctx* c, bool device_io, const void* p, size_t bytes, const void** d, const char* check_prefix) {
+    if (!device_io) return upload_input(c, p, bytes, d);
+    *d = p;
+    return check_prefix ? check_device_arg(p, c->device, check_prefix) : AM_OK;
+}
+
 // ---- plans --------------------------------------------------------------------
 static void fill_twiddles(std::vector<float2>& v, size_t off, size_t count, double denom, double mult) {
     for (size_t k = 0; k < count; ++k) {
@@ -488,11 +519,11 @@ int am_needle_create_pcm16(int device, const int16_t* interleaved, size_t frames
     int rc = get_ctx(device, &c);
     if (rc) return rc;
     std::lock_guard<std::recursive_mutex> lk(c->mu);
-    if ((rc = c->io_in.ensure(frames * 2 * sizeof(int16_t)))) return rc;
-    AM_HIP(copy_on_stream(c, c->io_in.p, interleaved, frames * 2 * sizeof(int16_t), hipMemcpyHostToDevice));
+    const void* d_in = nullptr;
+    if ((rc = upload_input(c, interleaved, sample_bytes(frames), &d_in))) return rc;
     float* d = nullptr;
     AM_HIP(hipMalloc((void**)&d, frames * sizeof(float)));
-    hipError_t e = launch_pcm_downmix(c->stream, (const int16_t*)c->io_in.p, (long long)frames, d);
+    hipError_t e = launch_pcm_downmix(c->stream, (const int16_t*)d_in, (long long)frames, d);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
     if (e != hipSuccess) { (void)hipFree(d); return hip_fail(e, "needle down-mix"); }
     return create_needle_common(c, d, frames, out);

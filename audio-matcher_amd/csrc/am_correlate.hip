@@ -453,8 +453,7 @@ int pick_chunk_big(Ctx* c, const float* d_scores, long long n_scores, int seg_id
     AM_HIP(hipMemcpyAsync(c->wide_ctl.p, &ctl, sizeof(ctl), hipMemcpyHostToDevice, c->stream));
     AM_HIP(launch_peaks_wide_one(c->stream, d_scores, n_scores, (const float2*)stats.p, d_seg, min_prom, min_dist, sp, wide, pol));
     unsigned n = 0;
-    AM_HIP(hipMemcpyAsync(&n, wide.count, sizeof(unsigned), hipMemcpyDeviceToHost, c->stream));
-    AM_HIP(hipStreamSynchronize(c->stream));
+    if ((rc = download(c, &n, wide.count, sizeof(unsigned)))) return rc;
     if (n == 0) return AM_OK;
     if (n >= 0x40000000u) return fail(AM_ERR_PEAK_OVERFLOW, "peak list build failed");
     // one allocation: list | out | keys (2n) | table | idx (2n) | out_n
@@ -472,14 +471,12 @@ int pick_chunk_big(Ctx* c, const float* d_scores, long long n_scores, int seg_id
                                    reinterpret_cast<unsigned*>(base + off_idx), reinterpret_cast<long long*>(base + off_table),
                                    reinterpret_cast<am_peak*>(base + off_out), reinterpret_cast<unsigned*>(base + off_n), pol));
     unsigned kept = 0;
-    AM_HIP(hipMemcpyAsync(&kept, base + off_n, sizeof(unsigned), hipMemcpyDeviceToHost, c->stream));
-    AM_HIP(hipStreamSynchronize(c->stream));
+    if ((rc = download(c, &kept, base + off_n, sizeof(unsigned)))) return rc;
     if (kept > n) return fail(AM_ERR_PEAK_OVERFLOW, "peak filter failed");
     const size_t old = all.size();
     all.resize(old + kept);
     if (kept) {
-        AM_HIP(hipMemcpyAsync(all.data() + old, base + off_out, sizeof(am_peak) * (size_t)kept, hipMemcpyDeviceToHost, c->stream));
-        AM_HIP(hipStreamSynchronize(c->stream));
+        if ((rc = download(c, all.data() + old, base + off_out, sizeof(am_peak) * (size_t)kept))) return rc;
     }
     return AM_OK;
 }
@@ -509,11 +506,7 @@ int merge_peaks(std::vector<am_peak>& all, const am_match_params* p, bool from_f
     MergeCursor cur;
     std::vector<am_peak> kept;
     merge_settle(p, from_filtered, cur, all.data(), all.size(), 0, true, &kept);
-    const size_t n = kept.size();
-    for (size_t i = 0; i < n && i < cap; ++i) out[i] = kept[i];
-    *n_out = n;
-    if (n > cap) return fail(AM_ERR_CAPACITY, "peak output buffer too small");
-    return AM_OK;
+    return hand_back(kept, out, cap, n_out, "peak output buffer too small");
 }
 
 // The filter of merge_peaks over a list that grows at its end (am_monitor).  An element's fate depends on its two
@@ -574,8 +567,7 @@ int nonfinite_flags(Ctx* c, const float* d_src, const Segment* ranges, int n, in
     AM_HIP(hipMemcpyAsync(c->ranges.p, ranges, sizeof(Segment) * n, hipMemcpyHostToDevice, c->stream));
     AM_HIP(hipMemsetAsync(c->range_flags.p, 0, sizeof(int) * n, c->stream));
     AM_HIP(launch_nonfinite_ranges(c->stream, d_src, (const Segment*)c->ranges.p, n, (int*)c->range_flags.p));
-    AM_HIP(hipMemcpyAsync(flags, c->range_flags.p, sizeof(int) * n, hipMemcpyDeviceToHost, c->stream));
-    AM_HIP(hipStreamSynchronize(c->stream));
+    if ((rc = download(c, flags, c->range_flags.p, sizeof(int) * n))) return rc;
     return AM_OK;
 }
 }  // namespace am

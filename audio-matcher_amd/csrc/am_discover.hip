@@ -253,8 +253,7 @@ int discover_resident(Ctx* c, const void* d_a, size_t len_a, const void* d_b, si
         std::vector<double> sums(blocks);
         std::vector<unsigned> flags(blocks);
         AM_HIP(hipMemcpyAsync(sums.data(), d_sums, blocks * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-        AM_HIP(hipMemcpyAsync(flags.data(), d_flags, blocks * sizeof(unsigned), hipMemcpyDeviceToHost, c->stream));
-        AM_HIP(hipStreamSynchronize(c->stream));
+        if ((rc = download(c, flags.data(), d_flags, blocks * sizeof(unsigned)))) return rc;
         double e_a = 0.0;
         for (int k = 0; k < a_parts; ++k) e_a += sums[P * (size_t)parts + (size_t)k];
         const double e_ref = e_a * (double)L / (double)len_a, bound = e_ref * std::pow(10.0, -(double)dp->min_level_db / 10.0);
@@ -300,8 +299,7 @@ int discover_resident(Ctx* c, const void* d_a, size_t len_a, const void* d_b, si
             am_needle_destroy(h);   // (waits for the stream: the probe buffer and the spectra are free for the next probe)
             if (rc) return rc;
         }
-        AM_HIP(hipMemcpyAsync(out, d_rec, sizeof(am_probe_hit) * P, hipMemcpyDeviceToHost, c->stream));
-        AM_HIP(hipStreamSynchronize(c->stream));
+        if ((rc = download(c, out, d_rec, sizeof(am_probe_hit) * P))) return rc;
         for (size_t i = 0; i < P; ++i)
             if (is_skipped[i]) out[i] = skipped[i];
     }
@@ -313,7 +311,7 @@ int discover_check(const am_discover_params* dp, int sample_format, const void* 
                    am_probe_hit* out, size_t cap, size_t* n_out) {
     int rc = check_discover_params(dp);
     if (rc) return rc;
-    if (sample_format != AM_FMT_F32_MONO && sample_format != AM_FMT_S16_STEREO) return fail(AM_ERR_INVALID_ARG, "bad sample format");
+    if ((rc = check_format(sample_format))) return rc;
     if (!n_out || (!a && len_a) || (!b && len_b) || (!out && cap)) return fail(AM_ERR_INVALID_ARG, "null pointer");
     return AM_OK;
 }
@@ -328,19 +326,11 @@ int probe_scores_impl(int device, const float* scores, size_t n, uint64_t ex_lo,
     if ((rc = get_ctx(device, &c))) return rc;
     if (n == 0) { *out = empty_record(0, AM_PROBE_NO_BEST | AM_PROBE_NO_SECOND); return AM_OK; }
     std::lock_guard<std::recursive_mutex> lk(c->mu);
-    const float* d_scores = scores;
-    if (device_io) {
-        if ((rc = hit_check_device(scores, c->device, HitWhere{-1, 0, 0, 0}))) return fail(rc, "am_probe_scores_device: d_scores: " + t_err);
-    } else {
-        if ((rc = c->io_in.ensure(n * sizeof(float)))) return rc;
-        AM_HIP(copy_on_stream(c, c->io_in.p, scores, n * sizeof(float), hipMemcpyHostToDevice));
-        d_scores = (const float*)c->io_in.p;
-    }
+    const void* d_scores = nullptr;
+    if ((rc = resident_input(c, device_io, scores, sample_bytes(n), &d_scores, "am_probe_scores_device: d_scores: "))) return rc;
     if ((rc = c->disc_out.ensure(sizeof(am_probe_hit)))) return rc;
-    if ((rc = probe_reduce(c, d_scores, (long long)n, ex_lo, ex_hi, separation, 0, (am_probe_hit*)c->disc_out.p))) return rc;
-    AM_HIP(hipMemcpyAsync(out, c->disc_out.p, sizeof(am_probe_hit), hipMemcpyDeviceToHost, c->stream));
-    AM_HIP(hipStreamSynchronize(c->stream));
-    return AM_OK;
+    if ((rc = probe_reduce(c, (const float*)d_scores, (long long)n, ex_lo, ex_hi, separation, 0, (am_probe_hit*)c->disc_out.p))) return rc;
+    return download(c, out, c->disc_out.p, sizeof(am_probe_hit));
 }
 
 }  // namespace
@@ -358,22 +348,8 @@ int am_discover_len(size_t len_a, const am_discover_params* dp, size_t* n_probes
     return AM_OK;
 }
 
-int am_discover_device(int device, const void* d_a, size_t len_a, const void* d_b, size_t len_b, int sample_format,
-                       const am_discover_params* dp, am_probe_hit* out, size_t cap, size_t* n_out) {
-    int rc = discover_check(dp, sample_format, d_a, len_a, d_b, len_b, out, cap, n_out);
-    if (rc) return rc;
-    Ctx* c = nullptr;
-    if ((rc = get_ctx(device, &c))) return rc;
-    *n_out = 0;
-    if (len_a < dp->probe_len) return AM_OK;
-    std::lock_guard<std::recursive_mutex> lk(c->mu);
-    if ((rc = hit_check_device(d_a, c->device, HitWhere{-1, 0, 0, 0}))) return fail(rc, "am_discover_device: d_a: " + t_err);
-    if (len_b && (rc = hit_check_device(d_b, c->device, HitWhere{-1, 0, 0, 0}))) return fail(rc, "am_discover_device: d_b: " + t_err);
-    return discover_resident(c, d_a, len_a, d_b, len_b, sample_format, dp, out, cap, n_out);
-}
-
-int am_discover(int device, const void* a, size_t len_a, const void* b, size_t len_b, int sample_format, const am_discover_params* dp,
-                am_probe_hit* out, size_t cap, size_t* n_out) {
+static int discover_impl(int device, const void* a, size_t len_a, const void* b, size_t len_b, int sample_format,
+                         const am_discover_params* dp, am_probe_hit* out, size_t cap, size_t* n_out, bool device_io) {
     int rc = discover_check(dp, sample_format, a, len_a, b, len_b, out, cap, n_out);
     if (rc) return rc;
     Ctx* c = nullptr;
@@ -381,14 +357,30 @@ int am_discover(int device, const void* a, size_t len_a, const void* b, size_t l
     *n_out = 0;
     if (len_a < dp->probe_len) return AM_OK;
     std::lock_guard<std::recursive_mutex> lk(c->mu);
-    // both recordings side by side in the context's input buffer, B at a 256-byte boundary
-    const size_t per = sample_format == AM_FMT_S16_STEREO ? 2 * sizeof(int16_t) : sizeof(float);
-    const size_t off_b = (len_a * per + 255) & ~(size_t)255;
-    if ((rc = c->io_in.ensure(off_b + len_b * per))) return rc;
-    char* base = static_cast<char*>(c->io_in.p);
-    AM_HIP(copy_on_stream(c, base, a, len_a * per, hipMemcpyHostToDevice));
-    if (len_b) AM_HIP(copy_on_stream(c, base + off_b, b, len_b * per, hipMemcpyHostToDevice));
-    return discover_resident(c, base, len_a, base + off_b, len_b, sample_format, dp, out, cap, n_out);
+    if (device_io) {
+        if ((rc = check_device_arg(a, c->device, "am_discover_device: d_a: "))) return rc;
+        if (len_b && (rc = check_device_arg(b, c->device, "am_discover_device: d_b: "))) return rc;
+    } else {
+        // both recordings side by side in the context's input buffer, sized once, B at a 256-byte boundary
+        const size_t off_b = (sample_bytes(len_a) + 255) & ~(size_t)255;
+        if ((rc = c->io_in.ensure(off_b + sample_bytes(len_b)))) return rc;
+        char* base = static_cast<char*>(c->io_in.p);
+        AM_HIP(copy_on_stream(c, base, a, sample_bytes(len_a), hipMemcpyHostToDevice));
+        if (len_b) AM_HIP(copy_on_stream(c, base + off_b, b, sample_bytes(len_b), hipMemcpyHostToDevice));
+        a = base;
+        b = base + off_b;
+    }
+    return discover_resident(c, a, len_a, b, len_b, sample_format, dp, out, cap, n_out);
+}
+
+int am_discover_device(int device, const void* d_a, size_t len_a, const void* d_b, size_t len_b, int sample_format,
+                       const am_discover_params* dp, am_probe_hit* out, size_t cap, size_t* n_out) {
+    return discover_impl(device, d_a, len_a, d_b, len_b, sample_format, dp, out, cap, n_out, true);
+}
+
+int am_discover(int device, const void* a, size_t len_a, const void* b, size_t len_b, int sample_format, const am_discover_params* dp,
+                am_probe_hit* out, size_t cap, size_t* n_out) {
+    return discover_impl(device, a, len_a, b, len_b, sample_format, dp, out, cap, n_out, false);
 }
 
 int am_probe_scores(int device, const float* scores, size_t n, uint64_t ex_lo, uint64_t ex_hi, uint64_t separation, am_probe_hit* out) {
@@ -480,8 +472,5 @@ int am_discover_regions(const am_probe_hit* hits, size_t n, const am_discover_pa
         }
         regs.swap(kept);
     }
-    *n_out = regs.size();
-    for (size_t i = 0; i < regs.size() && i < cap; ++i) out[i] = regs[i];
-    if (regs.size() > cap) return fail(AM_ERR_CAPACITY, "region output buffer too small");
-    return AM_OK;
+    return hand_back(regs, out, cap, n_out, "region output buffer too small");
 }

@@ -543,8 +543,7 @@ int env_scores_resident(Ctx* c, const uint16_t* d_needles, const uint32_t* frame
     if (!trusted) {   // a level above AM_ENV_MAX_LEVEL that is not AM_ENV_ABSENT: the flags the two kernels left
         std::vector<unsigned long long> marks((size_t)nblk);
         AM_HIP(hipMemcpyAsync(nd.data(), d_nd, sizeof(EnvNeedle) * Q, hipMemcpyDeviceToHost, c->stream));
-        AM_HIP(hipMemcpyAsync(marks.data(), d_sums + (size_t)(B + 1) * (size_t)nblk, sizeof(uint64_t) * (size_t)nblk, hipMemcpyDeviceToHost, c->stream));
-        AM_HIP(hipStreamSynchronize(c->stream));
+        if ((rc = download(c, marks.data(), d_sums + (size_t)(B + 1) * (size_t)nblk, sizeof(uint64_t) * (size_t)nblk))) return rc;
         for (uint32_t q = 0; q < Q; ++q)
             if (nd[q].bad) return fail(AM_ERR_INVALID_ARG, "needles: matrix " + std::to_string(q) + " holds a level above AM_ENV_MAX_LEVEL that is not AM_ENV_ABSENT");
         for (unsigned long long m : marks)
@@ -589,8 +588,8 @@ int env_scores_impl(int device, const uint16_t* needles, const uint32_t* frames,
     const uint16_t* d_needles = needles;
     const uint16_t* d_hay = hay;
     if (device_io) {
-        if ((rc = hit_check_device(needles, c->device, HitWhere{-1, 0, 0, 0}))) return fail(rc, "am_envelope_scores_device: d_needles: " + t_err);
-        if (Jh && (rc = hit_check_device(hay, c->device, HitWhere{-1, 0, 0, 0}))) return fail(rc, "am_envelope_scores_device: d_hay: " + t_err);
+        if ((rc = check_device_arg(needles, c->device, "am_envelope_scores_device: d_needles: "))) return rc;
+        if (Jh && (rc = check_device_arg(hay, c->device, "am_envelope_scores_device: d_hay: "))) return rc;
     } else {
         if ((rc = c->env_needles.ensure(sizeof(uint16_t) * total)) || (rc = c->env_hay.ensure(sizeof(uint16_t) * std::max<size_t>((size_t)B * Jh, 1)))) return rc;
         AM_HIP(copy_on_stream(c, c->env_needles.p, needles, sizeof(uint16_t) * total, hipMemcpyHostToDevice));
@@ -604,7 +603,7 @@ int env_scores_impl(int device, const uint16_t* needles, const uint32_t* frames,
 int env_envelope_impl(int device, const void* signal, size_t len, int sample_format, const am_env_params* ep, double drift_ppm, uint16_t* out,
                       size_t cap, size_t* n_frames, bool device_io) {
     int rc;
-    if ((rc = env_check_params(ep)) || (rc = env_check_drift(drift_ppm)) || (rc = hit_check_format(sample_format)) || (rc = env_check_len(len))) return rc;
+    if ((rc = env_check_params(ep)) || (rc = env_check_drift(drift_ppm)) || (rc = check_format(sample_format)) || (rc = env_check_len(len))) return rc;
     if (!n_frames || (!signal && len) || (!out && cap)) return fail(AM_ERR_INVALID_ARG, "null pointer");
     Ctx* c = nullptr;
     if ((rc = get_ctx(device, &c))) return rc;
@@ -614,21 +613,13 @@ int env_envelope_impl(int device, const void* signal, size_t len, int sample_for
     if (J == 0) return AM_OK;
     if ((size_t)J > cap) return fail(AM_ERR_CAPACITY, "envelope output buffer too small");
     std::lock_guard<std::recursive_mutex> lk(c->mu);
-    const void* d_src = signal;
-    if (device_io) {
-        if ((rc = hit_check_device(signal, c->device, HitWhere{-1, 0, 0, 0}))) return fail(rc, "am_envelope_device: d_signal: " + t_err);
-    } else {
-        if ((rc = c->io_in.ensure(len * 4))) return rc;
-        AM_HIP(copy_on_stream(c, c->io_in.p, signal, len * 4, hipMemcpyHostToDevice));
-        d_src = c->io_in.p;
-    }
+    const void* d_src = nullptr;
+    if ((rc = resident_input(c, device_io, signal, sample_bytes(len), &d_src, "am_envelope_device: d_signal: "))) return rc;
     const size_t bytes = sizeof(uint16_t) * (size_t)ep->bands.n_bands * (size_t)J;
     if ((rc = c->env_hay.ensure(bytes))) return rc;
     const EnvJob jb = env_job(d_src, sample_format == AM_FMT_S16_STEREO ? 1 : 0, inc, J, (unsigned short*)c->env_hay.p);
     if ((rc = env_launch_frames(c, {jb}, jb.ngroups, *ep))) return rc;
-    AM_HIP(hipMemcpyAsync(out, c->env_hay.p, bytes, hipMemcpyDeviceToHost, c->stream));
-    AM_HIP(hipStreamSynchronize(c->stream));
-    return AM_OK;
+    return download(c, out, c->env_hay.p, bytes);
 }
 
 // the pick rule on host arrays
@@ -701,10 +692,9 @@ int env_match_resident(const am_needle* h, const void* d_hay, size_t len, int sa
         return rc;
     std::vector<am_env_pick> picks;
     env_pick(z.data(), qi.data(), n, min_score, (uint64_t)frames[K], picks);
-    *n_out = picks.size();
     const double H = (double)(1u << (lf - 1));
-    for (size_t i = 0; i < picks.size() && i < cap; ++i) {
-        const am_env_pick& p = picks[i];
+    std::vector<am_env_hit> hits;
+    for (const am_env_pick& p : picks) {
         const double d = drift[p.q];
         const long long s = std::llround(p.pos * H);
         am_env_hit r{};
@@ -713,30 +703,23 @@ int env_match_resident(const am_needle* h, const void* d_hay, size_t len, int sa
         r.drift_ppm = d;
         r.score = p.score;
         r.q = p.q;
-        out[i] = r;
+        hits.push_back(r);
     }
-    if (picks.size() > cap) return fail(AM_ERR_CAPACITY, "envelope hit buffer too small");
-    return AM_OK;
+    return hand_back(hits, out, cap, n_out, "envelope hit buffer too small");
 }
 
 int env_match_impl(const am_needle* h, const void* hay, size_t len, int sample_format, const am_env_params* ep, const am_env_grid* grid,
                    float min_score, am_env_hit* out, size_t cap, size_t* n_out, bool device_io) {
     int rc;
-    if ((rc = check_needle(h)) || (rc = env_check_params(ep)) || (rc = env_check_grid(grid)) || (rc = hit_check_format(sample_format)) ||
+    if ((rc = check_needle(h)) || (rc = env_check_params(ep)) || (rc = env_check_grid(grid)) || (rc = check_format(sample_format)) ||
         (rc = env_check_len(len)) || (rc = env_check_len(h->n)))
         return rc;
     if (!n_out || (!hay && len) || (!out && cap)) return fail(AM_ERR_INVALID_ARG, "null pointer");
     if (min_score != min_score) return fail(AM_ERR_INVALID_ARG, "min_score is NaN");
     Ctx* c = h->ctx;
     std::lock_guard<std::recursive_mutex> lk(c->mu);
-    const void* d_hay = hay;
-    if (device_io) {
-        if (len && (rc = hit_check_device(hay, c->device, HitWhere{-1, 0, 0, 0}))) return fail(rc, "am_match_envelope_device: d_haystack: " + t_err);
-    } else if (len) {
-        if ((rc = c->io_in.ensure(len * 4))) return rc;
-        AM_HIP(copy_on_stream(c, c->io_in.p, hay, len * 4, hipMemcpyHostToDevice));
-        d_hay = c->io_in.p;
-    }
+    const void* d_hay = hay;   // (an empty haystack is neither checked nor uploaded)
+    if (len && (rc = resident_input(c, device_io, hay, sample_bytes(len), &d_hay, "am_match_envelope_device: d_haystack: "))) return rc;
     return env_match_resident(h, d_hay, len, sample_format, ep, grid, min_score, out, cap, n_out);
 }
 
@@ -782,10 +765,7 @@ int am_envelope_pick(const float* z, const uint32_t* qi, size_t n, float min_sco
     if (min_score != min_score) return fail(AM_ERR_INVALID_ARG, "min_score is NaN");
     std::vector<am_env_pick> picks;
     env_pick(z, qi, n, min_score, separation, picks);
-    *n_out = picks.size();
-    for (size_t i = 0; i < picks.size() && i < cap; ++i) out[i] = picks[i];
-    if (picks.size() > cap) return fail(AM_ERR_CAPACITY, "envelope pick buffer too small");
-    return AM_OK;
+    return hand_back(picks, out, cap, n_out, "envelope pick buffer too small");
 }
 
 int am_match_envelope(const am_needle* h, const void* haystack, size_t len, int sample_format, const am_env_params* ep,

@@ -188,12 +188,6 @@ namespace {
 constexpr size_t kEstMeanMaxHits = 65535;
 constexpr uint64_t kEstMaxIndex = (uint64_t)1 << 62;   // lead, length and a hit's start stay below it (no overflow in start - lead + n)
 
-int est_check_format(int sample_format) {
-    if (sample_format != AM_FMT_F32_MONO && sample_format != AM_FMT_S16_STEREO)
-        return fail(AM_ERR_INVALID_ARG, "estimate: bad sample format " + std::to_string(sample_format));
-    return AM_OK;
-}
-
 bool est_scale_ok(float scale) { return std::isfinite(scale) && scale != 0.0f; }
 
 // the parameter block and the hit count of the two compute forms
@@ -260,7 +254,7 @@ extern "C" {
 int am_hit_window(const void* haystack, size_t len, int sample_format, uint64_t start, float scale, uint64_t lead, uint64_t length,
                   float* row) {
     int rc;
-    if ((rc = est_check_format(sample_format))) return rc;
+    if ((rc = check_format(sample_format, "estimate"))) return rc;
     if (!row || (!haystack && len > 0)) return fail(AM_ERR_INVALID_ARG, "null pointer");
     if (length == 0) return fail(AM_ERR_INVALID_ARG, "estimate: length must be at least 1");
     if (!est_scale_ok(scale)) return fail(AM_ERR_INVALID_ARG, "estimate: scale must be finite and not zero");
@@ -290,16 +284,16 @@ int am_needle_estimate_rows(int device, const float* rows, size_t n, const am_es
     if ((rc = get_ctx(device, &c))) return rc;
     std::lock_guard<std::recursive_mutex> lk(c->mu);
     const size_t bytes = sizeof(float) * n * (size_t)ep->length;
-    if ((rc = c->io_in.ensure(bytes)) || (rc = hit_io_reserve(c, 0, est_out_bytes(ep, dev, count)))) return rc;
-    AM_HIP(hipMemcpyAsync(c->io_in.p, rows, bytes, hipMemcpyHostToDevice, c->stream));
-    return run_estimate(c, c->io_in.p, 0, 0, n, ep, est, dev, count);
+    const void* d_rows = nullptr;
+    if ((rc = upload_input(c, rows, bytes, &d_rows)) || (rc = hit_io_reserve(c, 0, est_out_bytes(ep, dev, count)))) return rc;
+    return run_estimate(c, d_rows, 0, 0, n, ep, est, dev, count);
 }
 
 int am_needle_estimate_device(int device, const void* const* d_haystacks, const size_t* lens, size_t n_hay, int sample_format,
                               const am_est_hit* hits, size_t n, const am_estimate_params* ep, float* est, float* dev, uint32_t* count) {
     int rc;
     if (!d_haystacks || !lens || !hits || !ep || !est) return fail(AM_ERR_INVALID_ARG, "null pointer");
-    if ((rc = est_check_format(sample_format)) || (rc = est_check_params(ep, n))) return rc;
+    if ((rc = check_format(sample_format, "estimate")) || (rc = est_check_params(ep, n))) return rc;
     for (size_t i = 0; i < n; ++i) {
         const std::string hit = "hit " + std::to_string(i) + ": ";
         if (hits[i].haystack >= n_hay)

@@ -146,11 +146,6 @@ hipError_t launch_hit_scores(hipStream_t st, const HitDesc* d_hits, long long n,
 
 // ---- host side -------------------------------------------------------------------------------------------------------
 
-int hit_check_format(int sample_format) {
-    if (sample_format != AM_FMT_F32_MONO && sample_format != AM_FMT_S16_STEREO) return fail(AM_ERR_INVALID_ARG, "bad sample format");
-    return AM_OK;
-}
-
 std::string hit_pair_name(const HitWhere& w) {
     if (w.pair < 0) return "";
     return "pair " + std::to_string(w.pair) + " (haystack " + std::to_string(w.hay) + ", needle " + std::to_string(w.needle) + "): ";
@@ -206,7 +201,7 @@ int hit_single_prelude(const am_needle* h, int sample_format, size_t n, const vo
                        const void* params, bool* done) {
     int rc = check_needle(h);
     if (rc) return rc;
-    if ((rc = hit_check_format(sample_format))) return rc;
+    if ((rc = check_format(sample_format))) return rc;
     *done = n == 0;
     if (*done) return AM_OK;
     if (!hay || !peaks || !out || !params) return fail(AM_ERR_INVALID_ARG, "null pointer");
@@ -217,7 +212,7 @@ int hit_batch_counts(size_t n_needles, size_t n_hay, int sample_format, const vo
                      const am_peak* peaks, size_t cap_per_pair, const size_t* n_peaks, const void* out, const void* params, size_t* total) {
     int rc;
     *total = 0;
-    if ((rc = hit_check_format(sample_format))) return rc;
+    if ((rc = check_format(sample_format))) return rc;
     if (n_needles == 0 || n_hay == 0) return AM_OK;
     if (!needles || !d_haystacks || !lens || !n_peaks) return fail(AM_ERR_INVALID_ARG, "null pointer");
     size_t sum = 0;
@@ -271,10 +266,8 @@ int hit_table_put(Ctx* c, const void* rows, size_t off, size_t bytes) {
 
 int hit_results_get(Ctx* c, size_t tab_bytes, size_t out_bytes, const void** res) {
     void* pinned = static_cast<char*>(c->hit_io.p) + tab_bytes;
-    AM_HIP(hipMemcpyAsync(pinned, c->hit_out.p, out_bytes, hipMemcpyDeviceToHost, c->stream));
-    AM_HIP(hipStreamSynchronize(c->stream));
     *res = pinned;
-    return AM_OK;
+    return download(c, pinned, c->hit_out.p, out_bytes);
 }
 
 namespace {

@@ -224,6 +224,34 @@ struct ProfScope {
     }
 };
 hipError_t copy_on_stream(Ctx* c, void* dst, const void* src, size_t bytes, hipMemcpyKind kind);
+
+// ---- the steps the entry points share (am_context.hip, beside copy_on_stream) ----
+// AM_ERR_INVALID_ARG "bad sample format" unless sample_format is AM_FMT_F32_MONO or AM_FMT_S16_STEREO; with `who` the
+// message is "<who>: bad sample format <sample_format>"
+int check_format(int sample_format, const char* who = nullptr);
+// one f32 mono sample and one interleaved i16 stereo frame are both 4 bytes
+inline size_t sample_bytes(size_t elements) { return 4 * elements; }
+// A host form's input: sizes c->io_in for `bytes`, copies them up on c's stream and waits (copy_on_stream); *d is
+// c->io_in.p.  The caller holds c's lock; the input stays there until the context's next upload.
+int upload_input(Ctx* c, const void* host, size_t bytes, const void** d);
+// `bytes` of device memory into the caller's host memory on c's stream, waited for (copy_on_stream)
+int download(Ctx* c, void* host, const void* dev, size_t bytes);
+// AM_ERR_INVALID_ARG unless p is device memory of `device`: hit_check_device's message behind `prefix`
+// ("am_xxx_device: d_name: ", or "" for the message as it is)
+int check_device_arg(const void* p, int device, const char* prefix);
+// The resident form *d of a call's input p: a host form (device_io false) uploads it (upload_input); a _device form
+// takes p as it is.  check_prefix says whether that _device form checks residency: nullptr = it trusts its caller,
+// anything else = check_device_arg(p, c->device, check_prefix) first.
+int resident_input(Ctx* c, bool device_io, const void* p, size_t bytes, const void** d, const char* check_prefix = nullptr);
+// A call's list to its caller: *n_out = v.size() and the first min(v.size(), cap) elements in out; AM_ERR_CAPACITY with
+// the message `too_small` when the list is longer than cap
+template <class T>
+int hand_back(const std::vector<T>& v, T* out, size_t cap, size_t* n_out, const char* too_small) {
+    *n_out = v.size();
+    for (size_t i = 0; i < v.size() && i < cap; ++i) out[i] = v[i];
+    if (v.size() > cap) return fail(AM_ERR_CAPACITY, too_small);
+    return AM_OK;
+}
 // force_logN1: another factorisation than the production one (am_debug_column_bench: 2^23 as 512 x 16384)
 int get_plan(Ctx* c, int logN, const Plan** out, int force_logN1 = 0);
 
@@ -403,8 +431,7 @@ struct StreamPre {
 };
 
 inline const void* advance_src(const void* src, size_t elements) {
-    // one f32 mono sample and one interleaved i16 stereo frame are both 4 bytes
-    return static_cast<const char*>(src) + 4 * elements;
+    return static_cast<const char*>(src) + sample_bytes(elements);
 }
 
 // ---- am_context.hip ----
@@ -438,7 +465,6 @@ int normalise_scores(Ctx* c, hipStream_t st, const NormSpec& ns, const void* src
 #define AM_NORM_UNSUPPORTED "score_norm: not supported by this entry point"
 
 // ---- am_hits.hip: per-hit scoring, and the frame every per-hit family's three call forms run in ----
-int hit_check_format(int sample_format);
 double hit_floor(const am_needle* h);         // the floor on E_w the NCC path applies (process option score_norm_floor_db)
 double hit_floor_ratio(const am_needle* h);   // ... as a ratio to the needle's energy: 10^(-score_norm_floor_db / 10)
 // Which hit of a call (for error messages): hit `hit` of pair `pair` = (haystack `hay`, needle `needle`), pair < 0: a

@@ -230,7 +230,7 @@ int slot_run_host(am_pool::Slot& sl, const PoolJob& job, size_t first, size_t st
 int pool_run(am_pool* pool, const PoolJob& job, const void* const* hays, const size_t* lens, size_t n_hay, const am_match_params* p,
              am_peak* out, size_t cap, size_t* n_out, bool host) {
     if (!pool || !hays || !lens || !p || !n_out || (!out && cap)) return fail(AM_ERR_INVALID_ARG, "null pointer");
-    if (job.fmt != AM_FMT_F32_MONO && job.fmt != AM_FMT_S16_STEREO) return fail(AM_ERR_INVALID_ARG, "bad sample format");
+    if (int rc = check_format(job.fmt)) return rc;
     if (job.multi && snapshot_opts(nullptr).score_norm) return fail(AM_ERR_INVALID_ARG, AM_NORM_UNSUPPORTED);
     std::lock_guard<std::mutex> lk(pool->mu);
     const size_t nslots = pool->slots.size();
@@ -329,7 +329,7 @@ int am_match_part_device(const am_needle* hc, const void* d_part, size_t n_sampl
     int rc = check_needle(h);
     if (rc) return rc;
     if (!p || !n_out || (!out && cap)) return fail(AM_ERR_INVALID_ARG, "null pointer");
-    if (sample_format != AM_FMT_F32_MONO && sample_format != AM_FMT_S16_STEREO) return fail(AM_ERR_INVALID_ARG, "bad sample format");
+    if ((rc = check_format(sample_format))) return rc;
     if (snapshot_opts(h).score_norm) return fail(AM_ERR_INVALID_ARG, AM_NORM_UNSUPPORTED);
     *n_out = 0;
     if (n_windows == 0 || n_samples == 0) return AM_OK;
@@ -339,10 +339,7 @@ int am_match_part_device(const am_needle* hc, const void* d_part, size_t n_sampl
     PartSpec part{n_windows, first_sample, 0, n_windows, &raw};
     size_t n = 0;
     if ((rc = match_many(h, &d_part, &n_samples, 1, p, nullptr, 0, &n, sample_format, 0, 1, true, nullptr, &part))) return rc;
-    *n_out = raw.size();
-    for (size_t i = 0; i < raw.size() && i < cap; ++i) out[i] = raw[i];
-    if (raw.size() > cap) return fail(AM_ERR_CAPACITY, "peak output buffer too small");
-    return AM_OK;
+    return hand_back(raw, out, cap, n_out, "peak output buffer too small");
 }
 
 int am_merge_peaks(const am_match_params* p, const am_peak* peaks, size_t n, am_peak* out, size_t cap, size_t* n_out) {
@@ -356,7 +353,7 @@ namespace {
 int pool_long(am_pool* pool, const void* host_hay, const void* const* d_parts, size_t len, int fmt, const am_match_params* p,
               am_peak* out, size_t cap, size_t* n_out) {
     if (!pool || !p || !n_out || (!out && cap) || (!host_hay && !d_parts)) return fail(AM_ERR_INVALID_ARG, "null pointer");
-    if (fmt != AM_FMT_F32_MONO && fmt != AM_FMT_S16_STEREO) return fail(AM_ERR_INVALID_ARG, "bad sample format");
+    if (int rc = check_format(fmt)) return rc;
     std::lock_guard<std::mutex> lk(pool->mu);
     *n_out = 0;
     const size_t nslots = pool->slots.size();

@@ -271,12 +271,6 @@ int rs_taps(Ctx* c, const Ratio& r, const float** d_taps, int* ts_out) {
     return AM_OK;
 }
 
-int rs_check_format(int sample_format) {
-    if (sample_format != AM_FMT_F32_MONO && sample_format != AM_FMT_S16_STEREO)
-        return fail(AM_ERR_INVALID_ARG, "resample: bad sample format " + std::to_string(sample_format));
-    return AM_OK;
-}
-
 }  // namespace
 
 // y = resample(in) on c's stream, both resident on c's device; n_out = rs_len(n_in).  Equal rates copy the input (f32) or
@@ -321,27 +315,11 @@ int am_resample_len(size_t n_in, uint32_t src_rate, uint32_t dst_rate, size_t* n
     return rs_len(n_in, r, n_out);
 }
 
-int am_resample_device(int device, const void* d_in, size_t n_in, int sample_format, uint32_t src_rate, uint32_t dst_rate,
-                       float* d_out, size_t cap, size_t* n_out) {
+static int resample_impl(int device, const void* in, size_t n_in, int sample_format, uint32_t src_rate, uint32_t dst_rate, float* out,
+                         size_t cap, size_t* n_out, bool device_io) {
     int rc;
     if (!n_out) return fail(AM_ERR_INVALID_ARG, "null pointer");
-    if ((rc = rs_check_format(sample_format)) || (rc = am_resample_len(n_in, src_rate, dst_rate, n_out))) return rc;
-    if (*n_out > cap) return fail(AM_ERR_CAPACITY, "resample: output buffer too small (" + std::to_string(*n_out) + " samples needed)");
-    if (n_in == 0) return AM_OK;
-    if (!d_in || !d_out) return fail(AM_ERR_INVALID_ARG, "null pointer");
-    Ctx* c = nullptr;
-    if ((rc = get_ctx(device, &c))) return rc;
-    std::lock_guard<std::recursive_mutex> lk(c->mu);
-    if ((rc = resample_on_device(c, d_in, n_in, sample_format, src_rate, dst_rate, d_out, *n_out))) return rc;
-    AM_HIP(hipStreamSynchronize(c->stream));
-    return AM_OK;
-}
-
-int am_resample(int device, const void* in, size_t n_in, int sample_format, uint32_t src_rate, uint32_t dst_rate,
-                float* out, size_t cap, size_t* n_out) {
-    int rc;
-    if (!n_out) return fail(AM_ERR_INVALID_ARG, "null pointer");
-    if ((rc = rs_check_format(sample_format)) || (rc = am_resample_len(n_in, src_rate, dst_rate, n_out))) return rc;
+    if ((rc = check_format(sample_format, "resample")) || (rc = am_resample_len(n_in, src_rate, dst_rate, n_out))) return rc;
     if (*n_out > cap) return fail(AM_ERR_CAPACITY, "resample: output buffer too small (" + std::to_string(*n_out) + " samples needed)");
     if (n_in == 0) return AM_OK;
     if (!in || !out) return fail(AM_ERR_INVALID_ARG, "null pointer");
@@ -349,11 +327,24 @@ int am_resample(int device, const void* in, size_t n_in, int sample_format, uint
     if ((rc = get_ctx(device, &c))) return rc;
     std::lock_guard<std::recursive_mutex> lk(c->mu);
     const size_t no = *n_out;
-    if ((rc = c->io_in.ensure(4 * n_in)) || (rc = c->io_out.ensure(sizeof(float) * no))) return rc;   // (4 bytes per sample or frame)
-    AM_HIP(hipMemcpyAsync(c->io_in.p, in, 4 * n_in, hipMemcpyHostToDevice, c->stream));
-    if ((rc = resample_on_device(c, c->io_in.p, n_in, sample_format, src_rate, dst_rate, static_cast<float*>(c->io_out.p), no))) return rc;
-    AM_HIP(copy_on_stream(c, out, c->io_out.p, sizeof(float) * no, hipMemcpyDeviceToHost));
+    const void* d_in = nullptr;
+    if ((rc = resident_input(c, device_io, in, sample_bytes(n_in), &d_in))) return rc;
+    if (!device_io && (rc = c->io_out.ensure(sizeof(float) * no))) return rc;
+    float* d_out = device_io ? out : static_cast<float*>(c->io_out.p);
+    if ((rc = resample_on_device(c, d_in, n_in, sample_format, src_rate, dst_rate, d_out, no))) return rc;
+    if (!device_io) return download(c, out, d_out, sizeof(float) * no);
+    AM_HIP(hipStreamSynchronize(c->stream));
     return AM_OK;
+}
+
+int am_resample_device(int device, const void* d_in, size_t n_in, int sample_format, uint32_t src_rate, uint32_t dst_rate,
+                       float* d_out, size_t cap, size_t* n_out) {
+    return resample_impl(device, d_in, n_in, sample_format, src_rate, dst_rate, d_out, cap, n_out, true);
+}
+
+int am_resample(int device, const void* in, size_t n_in, int sample_format, uint32_t src_rate, uint32_t dst_rate,
+                float* out, size_t cap, size_t* n_out) {
+    return resample_impl(device, in, n_in, sample_format, src_rate, dst_rate, out, cap, n_out, false);
 }
 
 int am_needle_create_resampled(int device, const void* needle, size_t n, int sample_format, uint32_t src_rate, uint32_t dst_rate,
@@ -361,15 +352,15 @@ int am_needle_create_resampled(int device, const void* needle, size_t n, int sam
     int rc;
     if (!needle || !out || n == 0) return fail(AM_ERR_INVALID_ARG, "needle must be non-empty");
     size_t no = 0;
-    if ((rc = rs_check_format(sample_format)) || (rc = am_resample_len(n, src_rate, dst_rate, &no))) return rc;
+    if ((rc = check_format(sample_format, "resample")) || (rc = am_resample_len(n, src_rate, dst_rate, &no))) return rc;
     Ctx* c = nullptr;
     if ((rc = get_ctx(device, &c))) return rc;
     std::lock_guard<std::recursive_mutex> lk(c->mu);
-    if ((rc = c->io_in.ensure(4 * n))) return rc;
-    AM_HIP(hipMemcpyAsync(c->io_in.p, needle, 4 * n, hipMemcpyHostToDevice, c->stream));
+    const void* d_in = nullptr;
+    if ((rc = upload_input(c, needle, sample_bytes(n), &d_in))) return rc;
     float* d = nullptr;
     AM_HIP(hipMalloc((void**)&d, no * sizeof(float)));
-    rc = resample_on_device(c, c->io_in.p, n, sample_format, src_rate, dst_rate, d, no);
+    rc = resample_on_device(c, d_in, n, sample_format, src_rate, dst_rate, d, no);
     if (!rc) {
         const hipError_t e = hipStreamSynchronize(c->stream);
         if (e != hipSuccess) rc = hip_fail(e, "resample: needle");

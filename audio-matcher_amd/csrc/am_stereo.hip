@@ -408,13 +408,11 @@ int am_pcm_s16_stereo_mix(int device, const int16_t* interleaved, size_t frames,
     if (rc) return rc;
     if (frames == 0) return AM_OK;
     std::lock_guard<std::recursive_mutex> lk(c->mu);
-    if ((rc = c->io_in.ensure(frames * 2 * sizeof(int16_t)))) return rc;
-    if ((rc = c->io_out.ensure(frames * sizeof(float)))) return rc;
-    AM_HIP(copy_on_stream(c, c->io_in.p, interleaved, frames * 2 * sizeof(int16_t), hipMemcpyHostToDevice));
-    AM_HIP(launch_pcm_mix(c->stream, (const int16_t*)c->io_in.p, (long long)frames, a, b, (float*)c->io_out.p));
+    const void* d_in = nullptr;
+    if ((rc = upload_input(c, interleaved, sample_bytes(frames), &d_in)) || (rc = c->io_out.ensure(frames * sizeof(float)))) return rc;
+    AM_HIP(launch_pcm_mix(c->stream, (const int16_t*)d_in, (long long)frames, a, b, (float*)c->io_out.p));
     AM_HIP(hipStreamSynchronize(c->stream));
-    AM_HIP(copy_on_stream(c, out, c->io_out.p, frames * sizeof(float), hipMemcpyDeviceToHost));
-    return AM_OK;
+    return download(c, out, c->io_out.p, frames * sizeof(float));
 }
 
 }  // extern "C"

@@ -70,7 +70,7 @@ int am_match_stream_begin(const am_needle* hc, int sample_format, size_t expecte
     int rc = check_needle(h);
     if (rc) return rc;
     if (!p || !out) return fail(AM_ERR_INVALID_ARG, "null pointer");
-    if (sample_format != AM_FMT_F32_MONO && sample_format != AM_FMT_S16_STEREO) return fail(AM_ERR_INVALID_ARG, "bad sample format");
+    if ((rc = check_format(sample_format))) return rc;
     if (p->chunk == 0) return fail(AM_ERR_INVALID_ARG, "chunk must be > 0");
     if (p->scale < AM_SCALE_NONE || p->scale > AM_SCALE_MY) return fail(AM_ERR_INVALID_ARG, "bad scale");
     if (snapshot_opts(h).score_norm) return fail(AM_ERR_INVALID_ARG, AM_NORM_UNSUPPORTED);

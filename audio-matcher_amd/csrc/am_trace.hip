@@ -216,8 +216,7 @@ int trace_reduce(Ctx* c, const float* d_g, long long n, uint64_t bin, am_trace_b
                                (const am_trace_bin*)d_parts, nb, per_bin, d_out);
             AM_HIP(hipGetLastError());
         }
-        AM_HIP(hipMemcpyAsync(out, d_out, sizeof(am_trace_bin) * (size_t)nb, hipMemcpyDeviceToHost, c->stream));
-        AM_HIP(hipStreamSynchronize(c->stream));
+        if ((rc = download(c, out, d_out, sizeof(am_trace_bin) * (size_t)nb))) return rc;
     }
     if ((uint64_t)nb_all > cap) return fail(AM_ERR_CAPACITY, "trace output buffer too small");
     return AM_OK;
@@ -260,13 +259,9 @@ static int trace_scores_impl(int device, const float* scores, size_t n, uint64_t
     *n_out = 0;
     if (n == 0) return AM_OK;
     std::lock_guard<std::recursive_mutex> lk(c->mu);
-    const float* d_scores = scores;
-    if (!device_io) {
-        if ((rc = c->io_in.ensure(n * sizeof(float)))) return rc;
-        AM_HIP(copy_on_stream(c, c->io_in.p, scores, n * sizeof(float), hipMemcpyHostToDevice));
-        d_scores = (const float*)c->io_in.p;
-    }
-    return trace_reduce(c, d_scores, (long long)n, bin, out, cap, n_out);
+    const void* d_scores = nullptr;
+    if ((rc = resident_input(c, device_io, scores, sample_bytes(n), &d_scores))) return rc;
+    return trace_reduce(c, (const float*)d_scores, (long long)n, bin, out, cap, n_out);
 }
 
 int am_trace_scores(int device, const float* scores, size_t n, uint64_t bin, am_trace_bin* out, size_t cap, size_t* n_out) {
@@ -281,29 +276,15 @@ static int trace_check(const am_needle* h, int sample_format, const am_trace_par
     int rc = check_needle(h);
     if (rc) return rc;
     if (!tp) return fail(AM_ERR_INVALID_ARG, "null pointer");
-    if (sample_format != AM_FMT_F32_MONO && sample_format != AM_FMT_S16_STEREO) return fail(AM_ERR_INVALID_ARG, "bad sample format");
-    if ((rc = trace_check_bin(tp->bin))) return rc;
+    if ((rc = check_format(sample_format)) || (rc = trace_check_bin(tp->bin))) return rc;
     if (tp->reserved != 0) return fail(AM_ERR_INVALID_ARG, "am_trace_params: reserved must be 0");
     if (tp->scale != AM_SCALE_NONE && tp->scale != AM_SCALE_LIB)
         return fail(AM_ERR_INVALID_ARG, "am_match_trace: scale must be AM_SCALE_NONE or AM_SCALE_LIB (AM_SCALE_MY depends on a chunk)");
     return norm_check(norm_spec(h, snapshot_opts(h)), tp->scale);
 }
 
-int am_match_trace_device(const am_needle* hc, const void* d_haystack, size_t len, int sample_format, const am_trace_params* tp,
-                          am_trace_bin* out, size_t cap, size_t* n_out) {
-    am_needle* h = const_cast<am_needle*>(hc);
-    int rc = trace_check(h, sample_format, tp);
-    if (rc) return rc;
-    if (!n_out || (!d_haystack && len) || (!out && cap)) return fail(AM_ERR_INVALID_ARG, "null pointer");
-    *n_out = 0;
-    if (len < h->n) return AM_OK;
-    std::lock_guard<std::recursive_mutex> lk(h->ctx->mu);
-    if ((rc = hit_check_device(d_haystack, h->ctx->device, HitWhere{-1, 0, 0, 0}))) return rc;
-    return match_trace_one(h, d_haystack, len, sample_format, tp, out, cap, n_out);
-}
-
-int am_match_trace(const am_needle* hc, const void* haystack, size_t len, int sample_format, const am_trace_params* tp,
-                   am_trace_bin* out, size_t cap, size_t* n_out) {
+static int match_trace_impl(const am_needle* hc, const void* haystack, size_t len, int sample_format, const am_trace_params* tp,
+                            am_trace_bin* out, size_t cap, size_t* n_out, bool device_io) {
     am_needle* h = const_cast<am_needle*>(hc);
     int rc = trace_check(h, sample_format, tp);
     if (rc) return rc;
@@ -312,10 +293,19 @@ int am_match_trace(const am_needle* hc, const void* haystack, size_t len, int sa
     if (len < h->n) return AM_OK;
     Ctx* c = h->ctx;
     std::lock_guard<std::recursive_mutex> lk(c->mu);
-    const size_t bytes = len * (sample_format == AM_FMT_S16_STEREO ? 2 * sizeof(int16_t) : sizeof(float));
-    if ((rc = c->io_in.ensure(bytes))) return rc;
-    AM_HIP(copy_on_stream(c, c->io_in.p, haystack, bytes, hipMemcpyHostToDevice));
-    return match_trace_one(h, c->io_in.p, len, sample_format, tp, out, cap, n_out);
+    const void* d_hay = nullptr;
+    if ((rc = resident_input(c, device_io, haystack, sample_bytes(len), &d_hay, ""))) return rc;
+    return match_trace_one(h, d_hay, len, sample_format, tp, out, cap, n_out);
+}
+
+int am_match_trace_device(const am_needle* h, const void* d_haystack, size_t len, int sample_format, const am_trace_params* tp,
+                          am_trace_bin* out, size_t cap, size_t* n_out) {
+    return match_trace_impl(h, d_haystack, len, sample_format, tp, out, cap, n_out, true);
+}
+
+int am_match_trace(const am_needle* h, const void* haystack, size_t len, int sample_format, const am_trace_params* tp,
+                   am_trace_bin* out, size_t cap, size_t* n_out) {
+    return match_trace_impl(h, haystack, len, sample_format, tp, out, cap, n_out, false);
 }
 
 int am_match_trace_batch_device(const am_needle* hc, const void* const* d_haystacks, const size_t* lens, size_t n_hay,

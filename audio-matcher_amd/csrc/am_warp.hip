@@ -416,7 +416,7 @@ struct WarpFamily {
 // the format and the parameters, before anything that needs a device
 int warp_prelude(int sample_format, const am_warp_params* wp) {
     int rc;
-    if ((rc = hit_check_format(sample_format))) return rc;
+    if ((rc = check_format(sample_format))) return rc;
     return wp ? warp_check_params(wp) : AM_OK;
 }
 
@@ -460,7 +460,7 @@ int am_hit_warp_batch_device(const am_needle* const* needles, size_t n_needles, 
 int am_hit_window_warped(const void* haystack, size_t len, int sample_format, uint64_t start, float scale, double lag, double drift_ppm,
                          uint64_t lead, uint64_t length, float* row) {
     int rc;
-    if ((rc = hit_check_format(sample_format))) return rc;
+    if ((rc = check_format(sample_format))) return rc;
     if (!row || (!haystack && len > 0)) return fail(AM_ERR_INVALID_ARG, "null pointer");
     if (length == 0) return fail(AM_ERR_INVALID_ARG, "window: length must be at least 1");
     if (!std::isfinite(scale) || scale == 0.0f) return fail(AM_ERR_INVALID_ARG, "window: scale must be finite and not zero");

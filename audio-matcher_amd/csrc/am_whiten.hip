@@ -224,12 +224,6 @@ hipError_t launch_fir(hipStream_t st, const FirJob& j, int kind) {
 
 namespace {
 
-int wh_check_format(int sample_format) {
-    if (sample_format != AM_FMT_F32_MONO && sample_format != AM_FMT_S16_STEREO)
-        return fail(AM_ERR_INVALID_ARG, "whiten: bad sample format " + std::to_string(sample_format));
-    return AM_OK;
-}
-
 int wh_check_order(uint32_t order) {
     if (order < 1 || order > AM_WHITEN_MAX_ORDER)
         return fail(AM_ERR_INVALID_ARG, "whiten: order must be in 1.." + std::to_string(AM_WHITEN_MAX_ORDER) + " (got " + std::to_string(order) + ")");
@@ -249,7 +243,7 @@ int wh_check_taps(const float* taps, uint32_t n_taps) {
 int lag_args(const void* in, size_t n, int sample_format, uint32_t order, double* r, bool* done) {
     int rc;
     *done = false;
-    if ((rc = wh_check_order(order)) || (rc = wh_check_format(sample_format))) return rc;
+    if ((rc = wh_check_order(order)) || (rc = check_format(sample_format, "whiten"))) return rc;
     if (!r) return fail(AM_ERR_INVALID_ARG, "null pointer");
     if (n == 0) {
         for (uint32_t k = 0; k <= order; ++k) r[k] = 0.0;
@@ -266,7 +260,7 @@ int fir_args(const void* in, size_t n_in, int sample_format, const float* taps, 
     int rc;
     *done = false;
     if (!n_out) return fail(AM_ERR_INVALID_ARG, "null pointer");
-    if ((rc = wh_check_format(sample_format)) || (rc = wh_check_taps(taps, n_taps))) return rc;
+    if ((rc = check_format(sample_format, "whiten")) || (rc = wh_check_taps(taps, n_taps))) return rc;
     if (lead > n_in) return fail(AM_ERR_INVALID_ARG, "fir: lead (" + std::to_string(lead) + ") is larger than n_in (" + std::to_string(n_in) + ")");
     *n_out = n_in - lead;
     if (*n_out > cap) return fail(AM_ERR_CAPACITY, "fir: output buffer too small (" + std::to_string(*n_out) + " samples needed)");
@@ -315,26 +309,24 @@ using namespace am;
 
 extern "C" {
 
-int am_lag_products_device(int device, const void* d_in, size_t n, int sample_format, uint32_t order, double* r) {
-    int rc;
-    bool done;
-    if ((rc = lag_args(d_in, n, sample_format, order, r, &done)) || done) return rc;
-    Ctx* c = nullptr;
-    if ((rc = get_ctx(device, &c))) return rc;
-    std::lock_guard<std::recursive_mutex> lk(c->mu);
-    return lag_products_on_device(c, d_in, n, sample_format, order, r);
-}
-
-int am_lag_products(int device, const void* in, size_t n, int sample_format, uint32_t order, double* r) {
+static int lag_products_impl(int device, const void* in, size_t n, int sample_format, uint32_t order, double* r, bool device_io) {
     int rc;
     bool done;
     if ((rc = lag_args(in, n, sample_format, order, r, &done)) || done) return rc;
     Ctx* c = nullptr;
     if ((rc = get_ctx(device, &c))) return rc;
     std::lock_guard<std::recursive_mutex> lk(c->mu);
-    if ((rc = c->io_in.ensure(4 * n))) return rc;   // (4 bytes per sample or frame)
-    AM_HIP(hipMemcpyAsync(c->io_in.p, in, 4 * n, hipMemcpyHostToDevice, c->stream));
-    return lag_products_on_device(c, c->io_in.p, n, sample_format, order, r);
+    const void* d_in = nullptr;
+    if ((rc = resident_input(c, device_io, in, sample_bytes(n), &d_in))) return rc;
+    return lag_products_on_device(c, d_in, n, sample_format, order, r);
+}
+
+int am_lag_products_device(int device, const void* d_in, size_t n, int sample_format, uint32_t order, double* r) {
+    return lag_products_impl(device, d_in, n, sample_format, order, r, true);
+}
+
+int am_lag_products(int device, const void* in, size_t n, int sample_format, uint32_t order, double* r) {
+    return lag_products_impl(device, in, n, sample_format, order, r, false);
 }
 
 int am_whiten_taps(const double* r, uint32_t order, double noise_db, float* taps) {
@@ -362,48 +354,48 @@ int am_whiten_taps(const double* r, uint32_t order, double noise_db, float* taps
     return AM_OK;
 }
 
-int am_fir_device(int device, const void* d_in, size_t n_in, int sample_format, const float* taps, uint32_t n_taps, size_t lead,
-                  float* d_out, size_t cap, size_t* n_out) {
-    int rc;
-    bool done;
-    if ((rc = fir_args(d_in, n_in, sample_format, taps, n_taps, lead, d_out, cap, n_out, &done)) || done) return rc;
-    Ctx* c = nullptr;
-    if ((rc = get_ctx(device, &c))) return rc;
-    std::lock_guard<std::recursive_mutex> lk(c->mu);
-    if ((rc = fir_on_device(c, d_in, n_in, sample_format, taps, n_taps, lead, d_out))) return rc;
-    AM_HIP(hipStreamSynchronize(c->stream));
-    return AM_OK;
-}
-
-int am_fir(int device, const void* in, size_t n_in, int sample_format, const float* taps, uint32_t n_taps, size_t lead, float* out,
-           size_t cap, size_t* n_out) {
+static int fir_impl(int device, const void* in, size_t n_in, int sample_format, const float* taps, uint32_t n_taps, size_t lead, float* out,
+                    size_t cap, size_t* n_out, bool device_io) {
     int rc;
     bool done;
     if ((rc = fir_args(in, n_in, sample_format, taps, n_taps, lead, out, cap, n_out, &done)) || done) return rc;
     Ctx* c = nullptr;
     if ((rc = get_ctx(device, &c))) return rc;
     std::lock_guard<std::recursive_mutex> lk(c->mu);
-    const size_t no = *n_out;
-    if ((rc = c->io_in.ensure(4 * n_in)) || (rc = c->io_out.ensure(sizeof(float) * no))) return rc;   // (4 bytes per sample or frame)
-    AM_HIP(hipMemcpyAsync(c->io_in.p, in, 4 * n_in, hipMemcpyHostToDevice, c->stream));
-    if ((rc = fir_on_device(c, c->io_in.p, n_in, sample_format, taps, n_taps, lead, static_cast<float*>(c->io_out.p)))) return rc;
-    AM_HIP(copy_on_stream(c, out, c->io_out.p, sizeof(float) * no, hipMemcpyDeviceToHost));
+    const size_t out_bytes = sizeof(float) * *n_out;
+    const void* d_in = nullptr;
+    if ((rc = resident_input(c, device_io, in, sample_bytes(n_in), &d_in))) return rc;
+    if (!device_io && (rc = c->io_out.ensure(out_bytes))) return rc;
+    float* d_out = device_io ? out : static_cast<float*>(c->io_out.p);
+    if ((rc = fir_on_device(c, d_in, n_in, sample_format, taps, n_taps, lead, d_out))) return rc;
+    if (!device_io) return download(c, out, d_out, out_bytes);
+    AM_HIP(hipStreamSynchronize(c->stream));
     return AM_OK;
+}
+
+int am_fir_device(int device, const void* d_in, size_t n_in, int sample_format, const float* taps, uint32_t n_taps, size_t lead,
+                  float* d_out, size_t cap, size_t* n_out) {
+    return fir_impl(device, d_in, n_in, sample_format, taps, n_taps, lead, d_out, cap, n_out, true);
+}
+
+int am_fir(int device, const void* in, size_t n_in, int sample_format, const float* taps, uint32_t n_taps, size_t lead, float* out,
+           size_t cap, size_t* n_out) {
+    return fir_impl(device, in, n_in, sample_format, taps, n_taps, lead, out, cap, n_out, false);
 }
 
 int am_needle_create_filtered(int device, const void* needle, size_t n, int sample_format, const float* taps, uint32_t n_taps,
                               am_needle** out) {
     int rc;
     if (!needle || !out || n == 0) return fail(AM_ERR_INVALID_ARG, "needle must be non-empty");
-    if ((rc = wh_check_format(sample_format)) || (rc = wh_check_taps(taps, n_taps))) return rc;
+    if ((rc = check_format(sample_format, "whiten")) || (rc = wh_check_taps(taps, n_taps))) return rc;
     Ctx* c = nullptr;
     if ((rc = get_ctx(device, &c))) return rc;
     std::lock_guard<std::recursive_mutex> lk(c->mu);
-    if ((rc = c->io_in.ensure(4 * n))) return rc;
-    AM_HIP(hipMemcpyAsync(c->io_in.p, needle, 4 * n, hipMemcpyHostToDevice, c->stream));
+    const void* d_in = nullptr;
+    if ((rc = upload_input(c, needle, sample_bytes(n), &d_in))) return rc;
     float* d = nullptr;
     AM_HIP(hipMalloc((void**)&d, n * sizeof(float)));
-    rc = fir_on_device(c, c->io_in.p, n, sample_format, taps, n_taps, 0, d);
+    rc = fir_on_device(c, d_in, n, sample_format, taps, n_taps, 0, d);
     if (!rc) {
         const hipError_t e = hipStreamSynchronize(c->stream);
         if (e != hipSuccess) rc = hip_fail(e, "fir: needle");

@@ -945,14 +945,19 @@ def trace_params(bin: int, scale=Scale.LIB) -> AmTraceParams:
     return AmTraceParams(bin=int(bin), scale=sc, reserved=0)
 
 
-def _trace_call(fn, n_scores: int, bin: int, cap):
-    """Runs fn(out_ptr, cap, byref(n)) on a record array of `cap` slots (default: all bins); the records written."""
-    nb = trace_len(n_scores, bin)
-    cap = nb if cap is None else int(cap)
-    out = np.zeros(max(1, cap), dtype=TRACE_BIN_DTYPE)
+def _records_call(fn, dtype, cap):
+    """Runs fn(out_ptr, cap, byref(n)) on an array of `cap` records of `dtype`; the records written."""
+    cap = int(cap)
+    out = np.zeros(max(1, cap), dtype=dtype)
     n = C.c_size_t(0)
     _check(fn(out.ctypes.data, cap, C.byref(n)))
     return out[:min(n.value, cap)]
+
+
+def _trace_call(fn, n_scores: int, bin: int, cap):
+    """_records_call on `cap` trace records (default: all bins)."""
+    nb = trace_len(n_scores, bin)
+    return _records_call(fn, TRACE_BIN_DTYPE, nb if cap is None else cap)
 
 
 def trace_scores(y_data, bin: int, device: int = 0, cap=None):
@@ -998,11 +1003,7 @@ def discover_len(len_a: int, params: AmDiscoverParams) -> int:
 
 
 def _discover_call(fn, len_a: int, params: AmDiscoverParams, cap):
-    cap = discover_len(len_a, params) if cap is None else int(cap)
-    out = np.zeros(max(1, cap), dtype=PROBE_HIT_DTYPE)
-    n = C.c_size_t(0)
-    _check(fn(out.ctypes.data, cap, C.byref(n)))
-    return out[:min(n.value, cap)]
+    return _records_call(fn, PROBE_HIT_DTYPE, discover_len(len_a, params) if cap is None else cap)
 
 
 def discover(a, b, params: AmDiscoverParams, device: int = 0, cap=None):
@@ -1043,12 +1044,9 @@ def probe_scores_device(device: int, ptr: int, n: int, ex_lo: int, ex_hi: int, s
 def discover_regions(hits, params: AmDiscoverParams, rparams: AmRegionParams, cap=None):
     """am_discover_regions: the regions (REGION_DTYPE) the probes' records chain into (pure host)."""
     h = np.ascontiguousarray(hits, dtype=PROBE_HIT_DTYPE)
-    cap = h.size if cap is None else int(cap)
-    out = np.zeros(max(1, cap), dtype=REGION_DTYPE)
-    n = C.c_size_t(0)
-    _check(lib().am_discover_regions(h.ctypes.data if h.size else None, h.size, C.byref(params), C.byref(rparams),
-                                     out.ctypes.data, cap, C.byref(n)))
-    return out[:min(n.value, cap)]
+    return _records_call(lambda o, c, n: lib().am_discover_regions(h.ctypes.data if h.size else None, h.size, C.byref(params),
+                                                                   C.byref(rparams), o, c, n),
+                         REGION_DTYPE, h.size if cap is None else cap)
 
 
 def env_params(bands: AmBandParams, floor_db: float = 80.0) -> AmEnvParams:
@@ -1145,20 +1143,13 @@ def envelope_pick(z, qi, min_score: float, separation: int, cap=None):
     """am_envelope_pick: the places (ENV_PICK_DTYPE) of a score array that are its largest within +-separation (pure host)."""
     zz = np.ascontiguousarray(z, dtype=np.float32)
     qq = np.ascontiguousarray(qi, dtype=np.uint32)
-    cap = zz.size if cap is None else int(cap)
-    out = np.zeros(max(1, cap), dtype=ENV_PICK_DTYPE)
-    n = C.c_size_t(0)
-    _check(lib().am_envelope_pick(zz.ctypes.data if zz.size else None, qq.ctypes.data if qq.size else None, zz.size, float(min_score),
-                                  int(separation), out.ctypes.data, cap, C.byref(n)))
-    return out[:min(n.value, cap)]
+    return _records_call(lambda o, c, n: lib().am_envelope_pick(zz.ctypes.data if zz.size else None, qq.ctypes.data if qq.size else None,
+                                                                zz.size, float(min_score), int(separation), o, c, n),
+                         ENV_PICK_DTYPE, zz.size if cap is None else cap)
 
 
 def _env_match_call(fn, cap):
-    cap = 1024 if cap is None else int(cap)
-    out = np.zeros(max(1, cap), dtype=ENV_HIT_DTYPE)
-    n = C.c_size_t(0)
-    _check(fn(out.ctypes.data, cap, C.byref(n)))
-    return out[:min(n.value, cap)]
+    return _records_call(fn, ENV_HIT_DTYPE, 1024 if cap is None else cap)
 
 
 def best_params(k: int, min_distance: int = 0, min_prominence: float = 0.0, scale=Scale.LIB) -> AmBestParams:
