@@ -7,10 +7,8 @@
 //
 // Two kernels on the context's stream:
 //   band_frames   one workgroup per (hit, group of kBandGroup consecutive frames): per frame it loads F samples of x and
-//                 of n, widens and windows them, packs z = x + i n and runs ONE F-point complex f64 FFT in LDS (radix 2,
-//                 decimation in time: the samples are stored bit-reversed, the spectrum comes out in order; both
-//                 parities of frame_log2 alike), untangles X[k] = (Z[k] + conj Z[F-k]) / 2, N[k] = (Z[k] - conj Z[F-k]) / 2i
-//                 and adds the three products to the thread's bins (registers).  After the group's frames the bins go
+//                 of n, widens and windows them, packs z = x + i n, runs ONE F-point complex f64 FFT in LDS and untangles
+//                 X[k] and N[k] (am_frames.h), and adds the three products to the thread's bins (registers).  After the group's frames the bins go
 //                 through LDS to one sum per band and value, in a fixed order, and the workgroup writes one partial
 //                 record: (Re C, Im C, E_x, E_n) per band and E_n over every bin, one 64-bit store per lane.
 //   band_combine  one wave per hit: adds the hit's partials in group order, forms the B records and sets the flags.
@@ -22,22 +20,16 @@
 // needle, the samples it reads, the parameters and the floor only (groups start at multiples of kBandGroup frames, every
 // reduction runs in a fixed order; one kernel serves both sample formats): the single, batch and host forms agree
 // bit for bit.  The three forms run in the frame of am_hits.hip (am_internal.h: hit_call, hit_call_batch,
-// hit_round_trip); BandFamily below is what this family adds to it.
-#include "am_internal.h"
+// hit_round_trip); BandFamily below is what this family adds to it; the combine's sums are those of am_hit_device.h.
+#include "am_frames.h"
+#include "am_hit_device.h"
 
 namespace am {
 
 namespace {
 
-constexpr int kBandThreads = 256;
-constexpr int kBandMaxF = 1 << 12;
-constexpr int kBandLds = kBandMaxF + (kBandMaxF >> 5) + (kBandMaxF >> 10);   // one padded array of F doubles
-constexpr int kBandBins = (kBandMaxF / 2) / kBandThreads + 1;                // bins per thread: k = tid + m * kBandThreads <= F / 2
+constexpr int kBandThreads = kFrameThreads, kBandLds = kFrameLds, kBandBins = kFrameBins;
 static_assert(AM_BAND_MAX_BANDS <= 64, "band_combine forms one record per lane");
-
-// Element i of an LDS array of 8-byte values, one pad per 32 and per 1024: the bit-reversed store of a frame (stride
-// F / 2, F / 4, ...) and the butterflies of the first stages (stride 2, 4, ...) then spread over the banks.
-__device__ __forceinline__ int lpad(int i) { return i + (i >> 5) + (i >> 10); }
 
 struct BandArgs {
     am_band_params bp;
@@ -71,40 +63,19 @@ __global__ __launch_bounds__(kBandThreads) void band_frames_kernel(const BandDes
             bad |= !__builtin_isfinite(xv) || !__builtin_isfinite(nv);
             nz |= (xv != 0.0f ? 1u : 0u) | (nv != 0.0f ? 2u : 0u);
             const double w = tab[i];
-            const int p = lpad((int)(__brev((unsigned)i) >> (32 - lf)));
+            const int p = frame_slot(i, lf);
             re[p] = (double)xv * w;
             im[p] = (double)nv * w;
         }
-        for (int off = 32; off > 0; off >>= 1) nz |= __shfl_xor(nz, off, 64);
-        if (lane == 0) wbits[wv] = nz;
-        __syncthreads();
-        for (int s = 1; s <= lf; ++s) {
-            const int h = 1 << (s - 1);
-            for (int b = tid; b < H; b += kBandThreads) {
-                const int pos = b & (h - 1);
-                const int i = lpad(((b >> (s - 1)) << s) + pos), j = lpad(((b >> (s - 1)) << s) + pos + h);
-                const double2 w = tw[pos << (lf - s)];
-                const double ar = re[i], ai = im[i], br = re[j], bi = im[j];
-                const double tr = w.x * br - w.y * bi, ti = w.x * bi + w.y * br;
-                re[i] = ar + tr;
-                im[i] = ai + ti;
-                re[j] = ar - tr;
-                im[j] = ai - ti;
-            }
-            __syncthreads();
-        }
-        unsigned any = 0;
-#pragma unroll
-        for (int i = 0; i < kBandThreads / 64; ++i) any |= wbits[i];
+        const unsigned any = frame_transform(re, im, tw, lf, nz, wbits);
         const bool has_x = any & 1u, has_n = any & 2u;
 #pragma unroll
         for (int m = 0; m < kBandBins; ++m) {
             const int k = tid + m * kBandThreads;
             if (k <= H) {
-                const int p = lpad(k), q = lpad((F - k) & (F - 1));
-                const double zr = re[p], zi = im[p], mr = re[q], mi = im[q];
-                const double xr = has_x ? 0.5 * (zr + mr) : 0.0, xi = has_x ? 0.5 * (zi - mi) : 0.0;
-                const double nr = has_n ? 0.5 * (zi + mi) : 0.0, ni = has_n ? 0.5 * (mr - zr) : 0.0;
+                const FrameBin z = frame_untangle(re, im, F, k);   // X: the haystack's spectrum, Y: the needle's
+                const double xr = has_x ? z.xr : 0.0, xi = has_x ? z.xi : 0.0;
+                const double nr = has_n ? z.yr : 0.0, ni = has_n ? z.yi : 0.0;
                 acc[m][0] += xr * nr + xi * ni;
                 acc[m][1] += xi * nr - xr * ni;
                 acc[m][2] += xr * xr + xi * xi;
@@ -113,8 +84,7 @@ __global__ __launch_bounds__(kBandThreads) void band_frames_kernel(const BandDes
         }
         __syncthreads();   // (the next frame's samples go where these were read)
     }
-    // bins to bands, two values at a time through LDS: wave w sums quantity w, w + 4, ... (lane l the bins lo + l, lo + l + 64,
-    // ..., then a butterfly over the wave) and its lane 0 stores the sum: one 64-bit store per lane and quantity
+    // bins to bands, two values at a time through LDS: wave w sums quantity w, w + 4, ... and its lane 0 stores the sum
     const int nb = (int)a.bp.n_bands;
     double* out = parts + (d.part0 + blockIdx.x) * (long long)a.nrec;
     for (int pass = 0; pass < 2; ++pass) {
@@ -132,9 +102,7 @@ __global__ __launch_bounds__(kBandThreads) void band_frames_kernel(const BandDes
             const int b = q >> 1;
             const int lo = b < nb ? (int)a.bp.edges[b] : 0, hi = b < nb ? (int)a.bp.edges[b + 1] : H + 1;
             const double* src = (q & 1) || b == nb ? im : re;
-            double v = 0.0;
-            for (int k = lo + lane; k < hi; k += 64) v += src[k];
-            for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+            const double v = wave_bin_sum(src, lo, hi);
             if (lane == 0) out[b < nb ? 4 * b + 2 * pass + (q & 1) : 4 * nb] = v;
         }
         __syncthreads();
@@ -152,13 +120,8 @@ __global__ __launch_bounds__(64) void band_combine_kernel(const BandDesc* __rest
     const int lane = threadIdx.x;
     const BandDesc d = hits[h];
     const int nrec = 4 * nb + 1;
-    for (int k = lane; k < nrec; k += 64) {
-        double t = 0.0;
-        for (long long g = 0; g < d.ngroups; ++g) t += parts[(d.part0 + g) * nrec + k];
-        sh[k] = t;
-    }
-    unsigned bf = 0;
-    for (long long g = lane; g < d.ngroups; g += 64) bf |= pflags[d.part0 + g];
+    for (int k = lane; k < nrec; k += 64) sh[k] = sum_slices(parts, nrec, d.part0, d.ngroups, k);
+    const unsigned bf = or_flags(pflags, d.part0, d.ngroups, lane, 64);
     const int bad = __syncthreads_or(bf != 0 ? 1 : 0);
     if (lane >= nb) return;
     const double cr = sh[4 * lane], ci = sh[4 * lane + 1], ex = sh[4 * lane + 2], en = sh[4 * lane + 3], ent = sh[4 * nb];
@@ -185,7 +148,7 @@ __global__ __launch_bounds__(64) void band_combine_kernel(const BandDesc* __rest
                 coh = (float)(sqrt(cr * cr + ci * ci) / den);
             }
             gain = (float)(cr / en);
-            ldb = ex == 0.0 ? -__builtin_inff() : (float)(10.0 * log10(ex / en));
+            ldb = level_db(ex, en);
         }
     }
     // three 64-bit stores per lane (volatile: the compiler does not merge them): no record leaves as one wide store
@@ -204,12 +167,10 @@ hipError_t launch_hit_bands(hipStream_t st, const BandDesc* d_hits, long long n,
     BandArgs a{};
     a.bp = bp;
     a.nrec = band_record_len((int)bp.n_bands);
-    for (long long h0 = 0; h0 < n; h0 += kHitMaxGridY) {   // (more hits than one grid column holds: a few launches)
-        const dim3 grid((unsigned)max_groups, (unsigned)std::min<long long>(kHitMaxGridY, n - h0));
-        hipLaunchKernelGGL(band_frames_kernel, grid, dim3(kBandThreads), 0, st, d_hits, h0, a, tab, parts, pflags);
-        hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return e;
-    }
+    const hipError_t e = for_each_grid_y(n, [&](long long h0, unsigned ny) {
+        hipLaunchKernelGGL(band_frames_kernel, dim3((unsigned)max_groups, ny), dim3(kBandThreads), 0, st, d_hits, h0, a, tab, parts, pflags);
+    });
+    if (e != hipSuccess) return e;
     hipLaunchKernelGGL(band_combine_kernel, dim3((unsigned)n), dim3(64), 0, st, d_hits, (int)bp.n_bands, empty_ratio, (const double*)parts,
                        (const unsigned*)pflags, d_out);
     return hipGetLastError();
@@ -227,7 +188,7 @@ size_t band_span(size_t s, int lf) { return (size_t)((band_frames((long long)s, 
 
 }  // namespace
 
-// the table of F on c's device, built on first use and kept until am_shutdown: w[0 .. F), then (cos, -sin)(2 pi k / F), k < F / 2
+// the table of F on c's device (am_frames.h)
 int band_table(Ctx* c, int lf, const double** d_tab) {
     DevBuf& b = c->band_tabs[lf];
     if (b.p) { *d_tab = static_cast<const double*>(b.p); return AM_OK; }

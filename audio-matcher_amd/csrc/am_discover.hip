@@ -19,9 +19,9 @@
 // are decided by the offsets, so the order of the folds does not matter.  The records stay on the device until the
 // call's single copy at the end.
 #include "am_internal.h"
+#include "am_reduce.h"
 #include "am_wave_steps.h"
 
-#include <float.h>
 #include <climits>
 #include <cmath>
 
@@ -48,8 +48,7 @@ __device__ __forceinline__ Cand wave_best(Cand c) {
     for (int m = 32; m > 0; m >>= 1) {
         Cand b;
         b.v = __shfl_xor(c.v, m, 64);
-        const int lo = __shfl_xor((int)(c.o & 0xFFFFFFFFll), m, 64), hi = __shfl_xor((int)(c.o >> 32), m, 64);
-        b.o = ((long long)hi << 32) | (unsigned)lo;
+        b.o = __shfl_xor(c.o, m, 64);
         take_cand(c, b);
     }
     return c;
@@ -146,8 +145,8 @@ __global__ void __launch_bounds__(64) probe_finish(const float* __restrict__ g, 
     }
 }
 
-// Block b < n_probes * parts: part (b mod parts) of probe (b / parts), in the order of additions of sumsq_kernel
-// (am_peaks.hip) over the probe's samples with `parts` workgroups -- so the host's sum of a probe's parts in index order
+// Block b < n_probes * parts: part (b mod parts) of probe (b / parts), the share block_sumsq (am_reduce.h) gives that
+// workgroup of sumsq_kernel (am_peaks.hip) over the probe's samples -- so the host's sum of a probe's parts in index order
 // has the bits of the energy am_needle_create_device gives a needle made from the probe.  The other blocks: the same
 // over all of A with `a_parts` workgroups, a non-finite sample counting as 0.  flag[b]: the block met a non-finite sample.
 __global__ void __launch_bounds__(256) probe_energy(const float* __restrict__ a, long long len_a, long long L, long long H, long long n_probes,
@@ -159,21 +158,9 @@ __global__ void __launch_bounds__(256) probe_energy(const float* __restrict__ a,
     const long long pr = whole ? 0 : b / parts, blk = whole ? b - n_probes * parts : b - pr * parts;
     const float* __restrict__ x = whole ? a : a + pr * H;
     const long long n = whole ? len_a : L, stride = (long long)(whole ? a_parts : parts) * 256;
-    double acc = 0.0;
-    int nf = 0;
-    for (long long i = blk * 256 + threadIdx.x; i < n; i += stride) {
-        const float f = x[i];
-        const bool fin = fabsf(f) <= FLT_MAX;
-        nf |= !fin;
-        const double v = (whole && !fin) ? 0.0 : (double)f;
-        acc += v * v;
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) { acc += __shfl_xor(acc, o); nf |= __shfl_xor(nf, o); }
-    if ((threadIdx.x & 63) == 0) { part[threadIdx.x >> 6] = acc; bad[threadIdx.x >> 6] = nf; }
-    __syncthreads();
+    const double t = block_sumsq(x, blk * 256, stride, n, whole, part, bad);
     if (threadIdx.x == 0) {
-        sums[b] = (part[0] + part[1]) + (part[2] + part[3]);
+        sums[b] = t;
         flags[b] = (unsigned)(bad[0] | bad[1] | bad[2] | bad[3]);
     }
 }

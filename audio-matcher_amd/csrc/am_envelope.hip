@@ -6,8 +6,7 @@
 // The kernels, on the context's stream:
 //   env_frames      one workgroup per (job, group of kEnvGroup consecutive frames), a job being one signal at one speed.
 //                   Two frames share ONE F-point complex f64 FFT in LDS (z = x_j + i x_{j+1}; the transform of
-//                   am_bands.hip: radix 2, decimation in time, padded LDS, window and twiddles from the host's f64
-//                   table), are untangled into |X_j[k]|^2 and |X_{j+1}[k]|^2, summed per band by one wave each and
+//                   am_frames.h, window and twiddles from the host's f64 table), are untangled into |X_j[k]|^2 and |X_{j+1}[k]|^2, summed per band by one wave each and
 //                   turned into levels.  A non-finite sample enters the transform as 0 and marks its frame ABSENT; a
 //                   frame of zeros counts as X = 0 exactly.
 //   env_needle_prep one workgroup per needle matrix: the matrix copied into the bank the correlation reads (rows padded
@@ -26,7 +25,8 @@
 //                   (4096 products of at most 1023^2 < 2^32), then 64-bit.  The score of (t, q) is formed from the sum,
 //                   the prefix sums and the needle's sums as the header defines it, the running best (score, q) stays
 //                   in registers, and the four waves fold theirs through LDS: one haystack tile is read once for all Q.
-#include "am_internal.h"
+#include "am_frames.h"
+#include "am_reduce.h"
 
 #include <climits>
 
@@ -34,10 +34,7 @@ namespace am {
 
 namespace {
 
-constexpr int kEnvThreads = 256;
-constexpr int kEnvMaxF = 1 << 12;
-constexpr int kEnvLds = kEnvMaxF + (kEnvMaxF >> 5) + (kEnvMaxF >> 10);   // one padded array of F doubles
-constexpr int kEnvBins = (kEnvMaxF / 2) / kEnvThreads + 1;               // bins per thread: k = tid + m * kEnvThreads <= F / 2
+constexpr int kEnvThreads = kFrameThreads, kEnvLds = kFrameLds, kEnvBins = kFrameBins;
 constexpr int kEnvGroup = 8;                                             // frames per workgroup: four transforms
 constexpr int kEnvBlock = 4096;                                          // frames per block of the prefix sums: 16 per thread
 constexpr int kTile = AM_ENV_TILE, kChunk = AM_ENV_CHUNK;
@@ -48,8 +45,6 @@ static_assert(kTile == 64 * 8 && kChunk == 8, "a lane owns 8 consecutive t and a
 static_assert((unsigned long long)kFlush * kChunk * AM_ENV_MAX_LEVEL * AM_ENV_MAX_LEVEL < (1ull << 32), "a 32-bit sum holds kFlush chunks");
 static_assert(sizeof(am_env_params) == 152 && sizeof(am_env_grid) == 24 && sizeof(am_env_pick) == 24 && sizeof(am_env_hit) == 32,
               "the envelope records have no padding");
-
-__device__ __forceinline__ int lpad(int i) { return i + (i >> 5) + (i >> 10); }
 
 // One signal at one speed: frame j < nframes starts at (j H inc + 2^31) >> 32 and goes to out[b nframes + j]
 struct EnvJob {
@@ -95,43 +90,21 @@ __global__ __launch_bounds__(kEnvThreads) void env_frames_kernel(const EnvJob* _
             const bool f0 = __builtin_isfinite(x0), f1 = __builtin_isfinite(x1);
             st |= (x0 != 0.0f ? 1u : 0u) | (x1 != 0.0f ? 2u : 0u) | (f0 ? 0u : 4u) | (f1 ? 0u : 8u);
             const double w = tab[i];
-            const int p = lpad((int)(__brev((unsigned)i) >> (32 - lf)));
+            const int p = frame_slot(i, lf);
             re[p] = f0 ? (double)x0 * w : 0.0;
             im[p] = f1 ? (double)x1 * w : 0.0;
         }
-        for (int off = 32; off > 0; off >>= 1) st |= __shfl_xor(st, off, 64);
-        if (lane == 0) wbits[wv] = st;
-        __syncthreads();
-        for (int s = 1; s <= lf; ++s) {
-            const int h = 1 << (s - 1);
-            for (int b = tid; b < H; b += kEnvThreads) {
-                const int pos = b & (h - 1);
-                const int i = lpad(((b >> (s - 1)) << s) + pos), j = lpad(((b >> (s - 1)) << s) + pos + h);
-                const double2 w = tw[pos << (lf - s)];
-                const double ar = re[i], ai = im[i], br = re[j], bi = im[j];
-                const double tr = w.x * br - w.y * bi, ti = w.x * bi + w.y * br;
-                re[i] = ar + tr;
-                im[i] = ai + ti;
-                re[j] = ar - tr;
-                im[j] = ai - ti;
-            }
-            __syncthreads();
-        }
-        unsigned any = 0;
-#pragma unroll
-        for (int i = 0; i < kEnvThreads / 64; ++i) any |= wbits[i];
-        // X_j[k] = (Z[k] + conj Z[F - k]) / 2, X_{j+1}[k] = (Z[k] - conj Z[F - k]) / 2i: the two power spectra
+        const unsigned any = frame_transform(re, im, tw, lf, st, wbits);
+        // the two power spectra: X of frame j, Y of frame j + 1
         double pw[kEnvBins][2];
 #pragma unroll
         for (int m = 0; m < kEnvBins; ++m) {
             const int k = tid + m * kEnvThreads;
             pw[m][0] = pw[m][1] = 0.0;
             if (k <= H) {
-                const int p = lpad(k), q = lpad((F - k) & (F - 1));
-                const double zr = re[p], zi = im[p], mr = re[q], mi = im[q];
-                const double xr = 0.5 * (zr + mr), xi = 0.5 * (zi - mi), yr = 0.5 * (zi + mi), yi = 0.5 * (mr - zr);
-                pw[m][0] = (any & 1u) ? xr * xr + xi * xi : 0.0;
-                pw[m][1] = (any & 2u) ? yr * yr + yi * yi : 0.0;
+                const FrameBin z = frame_untangle(re, im, F, k);
+                pw[m][0] = (any & 1u) ? z.xr * z.xr + z.xi * z.xi : 0.0;
+                pw[m][1] = (any & 2u) ? z.yr * z.yr + z.yi * z.yi : 0.0;
             }
         }
         __syncthreads();   // (every spectrum value is read: the powers go where they were)
@@ -149,9 +122,7 @@ __global__ __launch_bounds__(kEnvThreads) void env_frames_kernel(const EnvJob* _
             const int b = q >> 1, which = q & 1;
             if (which && !two) continue;
             const double* src = which ? im : re;
-            double v = 0.0;
-            for (int k = (int)a.bp.edges[b] + lane; k < (int)a.bp.edges[b + 1]; k += 64) v += src[k];
-            for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+            const double v = wave_bin_sum(src, (int)a.bp.edges[b], (int)a.bp.edges[b + 1]);
             if (lane == 0) {
                 unsigned short u = (unsigned short)AM_ENV_ABSENT;
                 if (!(any & (which ? 8u : 4u))) {
@@ -165,21 +136,10 @@ __global__ __launch_bounds__(kEnvThreads) void env_frames_kernel(const EnvJob* _
     }
 }
 
-__device__ __forceinline__ unsigned long long shfl_up_u64(unsigned long long v, int d) {
-    const unsigned lo = (unsigned)__shfl_up((int)(v & 0xFFFFFFFFull), d, 64), hi = (unsigned)__shfl_up((int)(v >> 32), d, 64);
-    return ((unsigned long long)hi << 32) | lo;
-}
-__device__ __forceinline__ unsigned long long shfl_xor_u64(unsigned long long v, int d) {
-    const unsigned lo = (unsigned)__shfl_xor((int)(v & 0xFFFFFFFFull), d, 64), hi = (unsigned)__shfl_xor((int)(v >> 32), d, 64);
-    return ((unsigned long long)hi << 32) | lo;
-}
-// the workgroup's sum of v, in every thread (sh: 4 words)
-__device__ __forceinline__ unsigned long long block_sum_u64(unsigned long long v, unsigned long long* sh) {
-    for (int off = 32; off > 0; off >>= 1) v += shfl_xor_u64(v, off);
-    __syncthreads();   // (sh may still be read from the call before)
-    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
+// the workgroup's sum of v in every thread (integers: any order gives these bits), behind a barrier: sh (4 words) may still be read
+__device__ __forceinline__ unsigned long long env_block_sum(unsigned long long v, unsigned long long* sh) {
     __syncthreads();
-    return (sh[0] + sh[1]) + (sh[2] + sh[3]);
+    return block_sum<kEnvThreads>(v, sh);
 }
 
 // frame i of row `row` of the haystack matrix e (B x n): see the file's head
@@ -207,7 +167,7 @@ __global__ __launch_bounds__(kEnvThreads) void env_block_sums_kernel(const unsig
     const long long i0 = (long long)blockIdx.x * kEnvBlock;
     unsigned long long v = 0;
     for (int k = threadIdx.x; k < kEnvBlock && i0 + k < n; k += kEnvThreads) v += env_row_value(e, n, B, row, i0 + k);
-    v = block_sum_u64(v, sh);
+    v = env_block_sum(v, sh);
     if (threadIdx.x == 0) sums[(long long)row * nblk + blockIdx.x] = v;
 }
 
@@ -218,7 +178,7 @@ __global__ __launch_bounds__(kEnvThreads) void env_prefix_kernel(const unsigned 
     const int row = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     unsigned long long carry = 0;
     for (long long k = tid; k < (long long)blockIdx.x; k += kEnvThreads) carry += sums[(long long)row * nblk + k];
-    carry = block_sum_u64(carry, sh);
+    carry = env_block_sum(carry, sh);
     constexpr int kPer = kEnvBlock / kEnvThreads;
     const long long i0 = (long long)blockIdx.x * kEnvBlock + (long long)tid * kPer;
     unsigned long long v[kPer], tot = 0;
@@ -228,11 +188,7 @@ __global__ __launch_bounds__(kEnvThreads) void env_prefix_kernel(const unsigned 
         tot += v[k];
         v[k] = tot;   // inclusive within the thread
     }
-    unsigned long long inc = tot;   // inclusive over the wave's threads
-    for (int d = 1; d < 64; d <<= 1) {
-        const unsigned long long o = shfl_up_u64(inc, d);
-        if (lane >= d) inc += o;
-    }
+    const unsigned long long inc = wave_scan_inclusive(tot);   // inclusive over the wave's threads
     __syncthreads();
     if (lane == 63) sh[wv] = inc;
     __syncthreads();
@@ -264,12 +220,12 @@ __global__ __launch_bounds__(kEnvThreads) void env_needle_prep_kernel(const unsi
             s1 += x;
             s2 += (unsigned long long)(x * x);
         }
-        s1 = block_sum_u64(s1, sh);
-        s2 = block_sum_u64(s2, sh);
+        s1 = env_block_sum(s1, sh);
+        s2 = env_block_sum(s2, sh);
         E += (long long)J * (long long)s2 - (long long)s1 * (long long)s1;
         if (threadIdx.x == 0) d.N1[b] = (int)s1;
     }
-    const unsigned long long f1 = block_sum_u64(flags & 1, sh), f2 = block_sum_u64(flags >> 1, sh);
+    const unsigned long long f1 = env_block_sum(flags & 1, sh), f2 = env_block_sum(flags >> 1, sh);
     if (threadIdx.x == 0) {
         d.E = E;
         d.absent = f1 != 0;

@@ -1,45 +1,16 @@
 // am_hit_device.h -- the device steps the per-hit kernels share (am_hits.hip, am_segments.hip, am_channel.hip,
-// am_stereo.hip, am_warp.hip, am_significance.hip; am_norm.hip takes the workgroup sum), and the host loop that launches
-// them.  The families promise results that are bit for bit the same across call forms, and some are checked against each
-// other: that holds while every one of them adds in the same order.  The order is written down here and nowhere else.
-// Included by those .hip files only.
+// am_stereo.hip, am_warp.hip, am_significance.hip, am_bands.hip), and the host loop that launches them.  The families
+// promise results that are bit for bit the same across call forms, and some are checked against each other: that holds
+// while every one of them adds in the same order.  The order is written down here, the workgroup sum's in am_reduce.h, and
+// nowhere else (am_bands.hip: the combine's sums, level_db and the host loop).  Included by those .hip files only.
 #pragma once
 
 #include <algorithm>
 
 #include "am_kernels.h"
+#include "am_reduce.h"
 
 namespace am {
-
-// ---- the workgroup sum ---------------------------------------------------------------------------------------------
-// Of NV values per thread, for a workgroup of THREADS: wave_sums adds value k over each wave by an xor butterfly with the
-// offsets 32, 16, .. 1 and lane 0 writes the wave's sum to ws[k][wave]; after a barrier, add_waves(ws[k]) adds the waves
-// of one value to 0 in ascending order.  Two calls on one ws need a barrier between the reads and the next writes.
-template <int THREADS, int NV, typename T>
-__device__ __forceinline__ void wave_sums(const T (&v)[NV], T (*ws)[THREADS / 64]) {
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-#pragma unroll
-    for (int k = 0; k < NV; ++k) {
-        T t = v[k];
-        for (int off = 32; off > 0; off >>= 1) t += __shfl_xor(t, off, 64);
-        if (lane == 0) ws[k][w] = t;
-    }
-}
-template <int THREADS, typename T>
-__device__ __forceinline__ T add_waves(const T (&row)[THREADS / 64]) {
-    T t = 0;
-    for (int i = 0; i < THREADS / 64; ++i) t += row[i];
-    return t;
-}
-// one value per thread, barrier included: every thread gets the sum.  ws: THREADS / 64 doubles.
-template <int THREADS>
-__device__ __forceinline__ double block_sum(double v, double* ws) {
-    typedef double Row[THREADS / 64];
-    const double one[1] = {v};
-    wave_sums<THREADS>(one, reinterpret_cast<Row*>(ws));
-    __syncthreads();
-    return add_waves<THREADS>(*reinterpret_cast<Row*>(ws));
-}
 
 // ---- staging a slice in LDS ----------------------------------------------------------------------------------------
 // LDS index of staged sample q where a work item reads 16 consecutive samples: one word of padding per 16, so that lanes

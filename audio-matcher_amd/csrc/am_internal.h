@@ -611,9 +611,7 @@ int hit_round_trip(Ctx* c, const std::vector<Desc>& hits, size_t part_bytes, siz
 }
 
 // ---- am_bands.hip ----
-// the window and twiddle table of F = 2^lf on c's device (w[0 .. F), then (cos, -sin)(2 pi k / F), k < F / 2), built on
-// first use; AM_ERR_INVALID_ARG unless bp is a valid request
-int band_table(Ctx* c, int lf, const double** d_tab);
+// AM_ERR_INVALID_ARG unless bp is a valid request (the table of a frame size: band_table, am_frames.h)
 int band_check_params(const am_band_params* bp);
 
 // ---- am_estimate.hip ----

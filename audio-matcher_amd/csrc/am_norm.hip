@@ -13,8 +13,8 @@
 //                  tile's kNormTile + S - 1 samples.
 // Every score depends on its index, the samples and the needle only (tiles start at multiples of kNormTile of the
 // score array, the reductions run in a fixed order): a haystack's bits do not depend on the batch it travels in.
-#include "am_hit_device.h"
 #include "am_internal.h"
+#include "am_reduce.h"
 
 namespace am {
 
@@ -36,7 +36,7 @@ __device__ __forceinline__ double norm_sq(const void* __restrict__ src, long lon
 }
 __device__ __forceinline__ long long floor_div(long long x, long long b) { return x >= 0 ? x / b : -((-x + b - 1) / b); }
 
-// Sum of one value per thread, in the order of block_sum (am_hit_device.h; every thread gets the result), and ws free
+// Sum of one value per thread, in the order of block_sum (am_reduce.h; every thread gets the result), and ws free
 // again.  `ws`: kNormThreads / 64 doubles.
 __device__ double norm_block_sum(double v, double* ws) {
     const double t = block_sum<kNormThreads>(v, ws);
@@ -54,11 +54,7 @@ __device__ void block_scan(double* buf, int n, double* ws) {
     const int lo = min(tid * per, n), hi = min(lo + per, n);
     double s = 0.0;
     for (int q = lo; q < hi; ++q) s += buf[REV ? n - 1 - q : q];
-    double incl = s;
-    for (int off = 1; off < 64; off <<= 1) {
-        const double v = __shfl_up(incl, off, 64);
-        if (lane >= off) incl += v;
-    }
+    const double incl = wave_scan_inclusive(s);
     double excl = __shfl_up(incl, 1, 64);
     if (lane == 0) excl = 0.0;
     if (lane == 63) ws[w] = incl;

@@ -21,6 +21,7 @@
 //   64 lanes look at 64 samples / 64 tile summaries per step and agree on the
 //   stopping point with a ballot.
 #include "am_kernels.h"
+#include "am_reduce.h"
 
 #include <float.h>
 
@@ -1004,19 +1005,11 @@ peaks_finish(const float* g, long long g_len, const float2* stats,
 // sum of squares in f64 (CorrelateAlgo::inverse_sample_auto_correlation,
 // audio_matcher.rs:321-329: element 0 of the needle's autocorrelation).  One
 // partial sum per workgroup; the host adds them in index order, so the result
-// does not depend on the order in which workgroups finish.
+// does not depend on the order in which workgroups finish (block_sumsq, am_reduce.h).
 __global__ void __launch_bounds__(256) sumsq_kernel(const float* __restrict__ x, long long n, double* out) {
     __shared__ double part[4];
-    double acc = 0.0;
-    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) {
-        const double v = (double)x[i];
-        acc += v * v;
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o);
-    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = acc;
-    __syncthreads();
-    if (threadIdx.x == 0) out[blockIdx.x] = (part[0] + part[1]) + (part[2] + part[3]);
+    const double t = block_sumsq(x, (long long)blockIdx.x * 256, (long long)gridDim.x * 256, n, false, part, nullptr);
+    if (threadIdx.x == 0) out[blockIdx.x] = t;
 }
 
 __device__ __forceinline__ uint32_t fmix32(uint32_t h) {

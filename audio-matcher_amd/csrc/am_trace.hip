@@ -40,15 +40,6 @@ __device__ __forceinline__ void take_min(float& v, unsigned& o, float vb, unsign
     if (ob != kTraceNone && (o == kTraceNone || vb < v || (vb == v && ob < o))) { v = vb; o = ob; }
 }
 
-__device__ __forceinline__ double shfl_f64(double v, int src) {
-    const int lo = __shfl(__double2loint(v), src, 64), hi = __shfl(__double2hiint(v), src, 64);
-    return __hiloint2double(hi, lo);
-}
-__device__ __forceinline__ double shfl_xor_f64(double v, int mask) {
-    const int lo = __shfl_xor(__double2loint(v), mask, 64), hi = __shfl_xor(__double2hiint(v), mask, 64);
-    return __hiloint2double(hi, lo);
-}
-
 // One wavefront reduces the span p[0, len) (len >= 0; p at any 4-byte alignment); offsets are reported from off0 on.
 // Every lane of the wave must be here.  The record is complete in every lane.
 __device__ __forceinline__ am_trace_bin trace_span(const float* __restrict__ p, int len, unsigned off0) {
@@ -83,8 +74,8 @@ __device__ __forceinline__ am_trace_bin trace_span(const float* __restrict__ p, 
             const int c = (i + a) & 3, src = (lane + ((i + a) >> 2)) & 63;
             const double ms = c == 0 ? s[0] : c == 1 ? s[1] : c == 2 ? s[2] : s[3];
             const double mq = c == 0 ? q[0] : c == 1 ? q[1] : c == 2 ? q[2] : q[3];
-            rs[i] = shfl_f64(ms, src);
-            rq[i] = shfl_f64(mq, src);
+            rs[i] = __shfl(ms, src, 64);
+            rq[i] = __shfl(mq, src, 64);
         }
 #pragma unroll
         for (int i = 0; i < 4; ++i) { s[i] = rs[i]; q[i] = rq[i]; }
@@ -92,8 +83,8 @@ __device__ __forceinline__ am_trace_bin trace_span(const float* __restrict__ p, 
     double sum = (s[0] + s[1]) + (s[2] + s[3]), sq = (q[0] + q[1]) + (q[2] + q[3]);
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) {
-        sum += shfl_xor_f64(sum, o);
-        sq += shfl_xor_f64(sq, o);
+        sum += __shfl_xor(sum, o, 64);
+        sq += __shfl_xor(sq, o, 64);
         cnt += __shfl_xor(cnt, o, 64);
         const float bx = __shfl_xor(mx, o, 64), bn = __shfl_xor(mn, o, 64);
         const unsigned box = __shfl_xor(omx, o, 64), bon = __shfl_xor(omn, o, 64);
@@ -154,8 +145,8 @@ __global__ void __launch_bounds__(kTraceThreads) trace_finish(const am_trace_bin
             if (lane < here) mine = p[s0 + lane];
             for (int k = 0; k < here; ++k) {
                 const unsigned c = __shfl(mine.count, k, 64);
-                sum += shfl_f64(mine.sum, k);
-                sq += shfl_f64(mine.sumsq, k);
+                sum += __shfl(mine.sum, k, 64);
+                sq += __shfl(mine.sumsq, k, 64);
                 const float vx = __shfl(mine.max, k, 64), vn = __shfl(mine.min, k, 64);
                 const unsigned ox = __shfl(mine.argmax, k, 64), on = __shfl(mine.argmin, k, 64);
                 if (!c) continue;

@@ -25,6 +25,7 @@
 #include <cmath>
 
 #include "am_internal.h"
+#include "am_reduce.h"
 
 namespace am {
 
@@ -72,8 +73,8 @@ template <int KIND>
 __global__ __launch_bounds__(kLagThreads) void lag_products_kernel(const void* src, long long n, int vec, int order, double* __restrict__ parts,
                                                                     long long nblk, long long blk0) {
     __shared__ float4 xs4[(kLagHist + kLagBlock) / 4];
-    __shared__ double ws[kLagThreads / 64][kLagChunk];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    __shared__ double ws[kLagChunk][kLagThreads / 64];
+    const int tid = threadIdx.x;
     const long long b = blk0 + (long long)blockIdx.x;
     const long long g0 = b * kLagBlock - kLagHist;   // the sample xs4[0] starts at
     for (int q = tid; q < (kLagHist + kLagBlock) / 4; q += kLagThreads) {
@@ -100,18 +101,9 @@ __global__ __launch_bounds__(kLagThreads) void lag_products_kernel(const void* s
 #pragma unroll
                 for (int l = 0; l < kLagChunk; ++l) acc[l] += x[s] * w[8 + s - l];   // x[i + s] x[i + s - (k0 + l)]
         }
-#pragma unroll
-        for (int l = 0; l < kLagChunk; ++l) {
-            double v = acc[l];
-            for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-            if (lane == 0) ws[wave][l] = v;
-        }
+        wave_sums<kLagThreads>(acc, ws);
         __syncthreads();
-        if (tid < kLagChunk && k0 + tid <= order) {
-            double t = 0.0;
-            for (int i = 0; i < kLagThreads / 64; ++i) t += ws[i][tid];
-            parts[(long long)(k0 + tid) * nblk + b] = t;
-        }
+        if (tid < kLagChunk && k0 + tid <= order) parts[(long long)(k0 + tid) * nblk + b] = add_waves<kLagThreads>(ws[tid]);
         __syncthreads();
     }
 }
