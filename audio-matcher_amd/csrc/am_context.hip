@@ -114,7 +114,7 @@ int realloc_refused(const char* what, size_t bytes, size_t cap) {
 }
 
 static const char* kKernelNames[] = {"k1_cols_fwd", "k2_rows", "k3_cols_inv", "tile_stats", "peaks", "other", "trace", "discover",
-                                     "envelope_frames", "envelope_prefix", "envelope_correlate"};
+                                     "envelope_frames", "envelope_prefix", "envelope_correlate", "edges"};
 static std::mutex g_ctx_mu;
 static std::map<int, Ctx*> g_ctx;
 
@@ -496,6 +496,7 @@ void am_needle_destroy(am_needle* h) {
         };
         for (am_needle* sub : h->segments) { free_spectra(sub); delete sub; }
         free_spectra(h);
+        if (h->d_edge_scans) (void)hipFree(h->d_edge_scans);
         if (h->d_needle && h->owns_data) (void)hipFree(h->d_needle);
     }
     delete h;

@@ -165,6 +165,8 @@ __global__ void __launch_bounds__(256) probe_energy(const float* __restrict__ a,
     }
 }
 
+}  // namespace
+
 // The record of the resident scores d_g[0, n) (n >= 1) into d_out, on the context's stream.  sep >= 1.
 int probe_reduce(Ctx* c, const float* d_g, long long n, uint64_t ex_lo, uint64_t ex_hi, uint64_t sep, uint64_t probe, am_probe_hit* d_out) {
     const long long nsl = (n + kSlice - 1) / kSlice;
@@ -181,6 +183,8 @@ int probe_reduce(Ctx* c, const float* d_g, long long n, uint64_t ex_lo, uint64_t
     AM_HIP(hipGetLastError());
     return AM_OK;
 }
+
+namespace {
 
 am_probe_hit empty_record(uint64_t probe, uint32_t flags) {
     am_probe_hit r{};

@@ -135,7 +135,7 @@ struct Plan {
 struct ScoreSide { DevBuf scores, stats, stats32, wflags, peaks, work; };
 
 struct ProfRec { int name; hipEvent_t e0, e1; };
-enum { KN_K1 = 0, KN_K2, KN_K3, KN_STATS, KN_PEAKS, KN_OTHER, KN_TRACE, KN_DISCOVER, KN_ENV_FRAMES, KN_ENV_PREFIX, KN_ENV_CORR, KN_COUNT };
+enum { KN_K1 = 0, KN_K2, KN_K3, KN_STATS, KN_PEAKS, KN_OTHER, KN_TRACE, KN_DISCOVER, KN_ENV_FRAMES, KN_ENV_PREFIX, KN_ENV_CORR, KN_EDGES, KN_COUNT };
 
 struct Ctx {
     int device = -1;
@@ -189,6 +189,9 @@ struct Ctx {
     // needle discovery (am_discover.hip): recording A down-mixed, the probe being matched, the energy parts, the slices'
     // partials and a call's records
     DevBuf disc_a, disc_probe, disc_energy, disc_parts, disc_out;
+    // edge matching (am_edges.hip): both sanitised spans, their coarse scores, their energy scans with the tile totals,
+    // the non-finite marks, the exact stage's partial sums, the probe records and the edge records of one haystack
+    DevBuf edge_span, edge_scores, edge_scan, edge_tot, edge_ctl, edge_parts, edge_rec;
     // envelope matching (am_envelope.hip): the frame jobs of a launch, the needle bank's and the haystack's levels, the
     // bank padded to whole chunks with its per-needle sums, the haystack's prefix sums and their block sums, z and qi
     DevBuf env_jobs, env_needles, env_hay, env_bank, env_desc, env_prefix, env_blocks, env_out;
@@ -301,6 +304,9 @@ struct am_needle {
     std::vector<am_needle*> segments;
     std::vector<long long> seg_off;
     bool owns_data = true;
+    // edge matching (am_edges.hip): the needle's f64 energy scans, n prefix sums and n suffix sums behind them, made by
+    // the first call that needs them
+    double* d_edge_scans = nullptr;
 };
 
 namespace am {
@@ -686,6 +692,10 @@ int haystack_prepare(Ctx* c, const void* d_hay, size_t len, int sample_format, D
 int prepared_scores(am_needle* h, const Opts& o, const HaySamples& hs, int scale, const float** d_scores, long long* n);
 int match_best_one(am_needle* h, const void* d_hay, size_t len, int sample_format, const am_best_params* bp, am_peak* out,
                    size_t* n_out);
+// ---- am_discover.hip ----
+// The record of the resident scores d_g[0, n) (n >= 1) into d_out (device memory), on the context's stream: the rule of
+// am_probe_scores with the excluded range [ex_lo, ex_hi) and sep >= 1
+int probe_reduce(Ctx* c, const float* d_g, long long n, uint64_t ex_lo, uint64_t ex_hi, uint64_t sep, uint64_t probe, am_probe_hit* d_out);
 // ---- am_trace.hip ----
 int trace_check_bin(uint64_t bin);
 int trace_reduce(Ctx* c, const float* d_g, long long n, uint64_t bin, am_trace_bin* out, size_t cap, size_t* n_out);

@@ -44,32 +44,6 @@ __device__ double norm_block_sum(double v, double* ws) {
     return t;
 }
 
-// In-place inclusive scan of buf[0 .. n): prefix sums (REV = false) or suffix sums (REV = true).  Thread i takes a
-// contiguous run of the (logical) sequence; its start value is the wave's exclusive scan of the runs before plus the
-// totals of the waves before.  Every entry is a sum of non-negative terms (no subtraction).
-template <bool REV>
-__device__ void block_scan(double* buf, int n, double* ws) {
-    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-    const int per = (n + kNormThreads - 1) / kNormThreads;
-    const int lo = min(tid * per, n), hi = min(lo + per, n);
-    double s = 0.0;
-    for (int q = lo; q < hi; ++q) s += buf[REV ? n - 1 - q : q];
-    const double incl = wave_scan_inclusive(s);
-    double excl = __shfl_up(incl, 1, 64);
-    if (lane == 0) excl = 0.0;
-    if (lane == 63) ws[w] = incl;
-    __syncthreads();
-    double run = 0.0;
-    for (int i = 0; i < w; ++i) run += ws[i];
-    run += excl;
-    for (int q = lo; q < hi; ++q) {
-        const int k = REV ? n - 1 - q : q;
-        run += buf[k];
-        buf[k] = run;
-    }
-    __syncthreads();
-}
-
 __global__ __launch_bounds__(kNormThreads) void block_energy_kernel(const void* __restrict__ src, long long len, int kind, double* __restrict__ blk) {
     __shared__ double ws[kNormThreads / 64];
     const long long base = (long long)blockIdx.x * kNormBlock;
@@ -95,7 +69,7 @@ __global__ __launch_bounds__(kNormThreads) void norm_scores_kernel(NormJob j, lo
         const int nh = (int)(A - u0);
         for (int q = tid; q < nh; q += kNormThreads) buf[q] = norm_sq(j.src, u0 + q, j.src_len, j.src_kind);
         __syncthreads();
-        block_scan<true>(buf, nh, ws);
+        block_scan<kNormThreads, true>(buf, nh, ws);
         for (int r = 0; r < kNormPer; ++r) {
             const int k = tid + r * kNormThreads;
             e[r] = k < nh ? buf[k] : 0.0;
@@ -110,7 +84,7 @@ __global__ __launch_bounds__(kNormThreads) void norm_scores_kernel(NormJob j, lo
         const int nt = (int)(u0 + kNormTile - 1 + S - Z);
         for (int q = tid; q < nt; q += kNormThreads) buf[q] = norm_sq(j.src, Z + q, j.src_len, j.src_kind);
         __syncthreads();
-        block_scan<false>(buf, nt, ws);
+        block_scan<kNormThreads, false>(buf, nt, ws);
         for (int r = 0; r < kNormPer; ++r) {
             const long long k = u0 + tid + r * kNormThreads + S - Z;   // tail piece length
             e[r] = (e[r] + m) + (k > 0 ? buf[k - 1] : 0.0);
@@ -120,7 +94,7 @@ __global__ __launch_bounds__(kNormThreads) void norm_scores_kernel(NormJob j, lo
         const int n = (int)(kNormTile - 1 + S);
         for (int q = tid; q < n; q += kNormThreads) buf[q] = norm_sq(j.src, u0 + q, j.src_len, j.src_kind);
         __syncthreads();
-        block_scan<false>(buf, n, ws);
+        block_scan<kNormThreads, false>(buf, n, ws);
         for (int r = 0; r < kNormPer; ++r) {
             const int k = tid + r * kNormThreads;
             e[r] = buf[k + S - 1] - (k > 0 ? buf[k - 1] : 0.0);   // (local sums: a window of zeros gives exactly 0)

@@ -78,5 +78,36 @@ __device__ __forceinline__ T wave_scan_inclusive(T v) {
     }
     return v;
 }
+// The workgroup's (THREADS) inclusive scan of a sequence of n values that load(k) gives and store(k, sum) takes, k = 0
+// .. n - 1.  Thread i takes a contiguous run; its start value is the wave's exclusive scan of the runs before plus the
+// totals of the waves before (ws: THREADS / 64 values, free again on return).  Every value stored is a sum of the loaded
+// values, no subtraction.  load(k) is called twice per k and must give the same value both times.
+template <int THREADS, class Load, class Store>
+__device__ __forceinline__ void block_scan_with(int n, double* ws, Load load, Store store) {
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const int per = (n + THREADS - 1) / THREADS;
+    const int lo = min(tid * per, n), hi = min(lo + per, n);
+    double s = 0.0;
+    for (int q = lo; q < hi; ++q) s += load(q);
+    const double incl = wave_scan_inclusive(s);
+    double excl = __shfl_up(incl, 1, 64);
+    if (lane == 0) excl = 0.0;
+    if (lane == 63) ws[w] = incl;
+    __syncthreads();
+    double run = 0.0;
+    for (int i = 0; i < w; ++i) run += ws[i];
+    run += excl;
+    for (int q = lo; q < hi; ++q) {
+        run += load(q);
+        store(q, run);
+    }
+    __syncthreads();
+}
+// In-place inclusive scan of buf[0 .. n): prefix sums (REV = false) or suffix sums (REV = true)
+template <int THREADS, bool REV>
+__device__ __forceinline__ void block_scan(double* buf, int n, double* ws) {
+    block_scan_with<THREADS>(
+        n, ws, [&](int q) { return buf[REV ? n - 1 - q : q]; }, [&](int q, double v) { buf[REV ? n - 1 - q : q] = v; });
+}
 
 }  // namespace am

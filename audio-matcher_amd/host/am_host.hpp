@@ -109,6 +109,9 @@ struct Arguments {
     std::optional<double> envelope_pct;       // extension: --envelope PCT[:STEPS[:MIN_SCORE]], occurrences at another speed, found through band-level envelopes (am_match_envelope)
     std::uint32_t envelope_steps = 20;        // ... drifts -PCT % .. PCT % in 2 STEPS + 1 steps
     float envelope_min_score = 0.4f;          // ... what an envelope hit must score
+    std::optional<std::uint64_t> edges_ms;    // extension: --edges DUR[:MIN_NCC[:MAX_SECOND]], a snippet cut off by the file's start or end (am_match_edges); DUR: the least overlap
+    float edges_min_ncc = 0.5f;               // ... what an edge record must score
+    float edges_max_second = 0.5f;            // ... and its runner-up at most this share of it
     bool live = false;                        // extension: --live, raw PCM from stdin through a monitor (am_monitor_*)
     std::uint32_t rate = 0;                   // --live: --rate R (samples per second of the stream)
     std::string encoding = "s16le";           // --live: --encoding s16le | f32le
@@ -230,6 +233,14 @@ inline const char* usage_text() {
            "                         occurrence against the snippet).  The start is good to a few frames and the speed to a\n"
            "                         step or two, less for snippets of a few seconds.  Such places go into the label file\n"
            "                         unless a hit lies within half a snippet of them.  Not with --live or --discover\n"
+           "  --edges DUR[:MIN_NCC[:MAX_SECOND]]  also look for the snippet cut off by the file's start or by its end\n"
+           "                         (am_match_edges): the overlap must be at least DUR (a duration) and hold 5 % of the\n"
+           "                         snippet's energy; an edge counts when its score over the part of the snippet inside the\n"
+           "                         file is at least MIN_NCC (default 0.5) and its runner-up at most MAX_SECOND (default 0.5)\n"
+           "                         of that.  After the file's offset lines one line per such edge, 'Offset head: -hh:mm:ss.mmm\n"
+           "                         with ncc V overlap P %' (where the snippet would start; negative: before the file) or\n"
+           "                         'Offset tail: ...', and in the label file a label 'head P %' / 'tail P %' over the part\n"
+           "                         of the file the snippet covers.  Not with --live or --discover\n"
            "  --discover DUR[:HOP]   no --snippet: find what the first FILE shares with itself and with every further FILE\n"
            "                         (am_discover): probes of DUR (a duration) every HOP (default DUR/2) of the first FILE\n"
            "                         are matched under NCC, and probes that agree on one displacement (within HOP/8, at\n"
@@ -493,6 +504,20 @@ inline Arguments parse_arguments(int argc, const char* const* argv) {
             a.envelope_steps = (std::uint32_t)k;
             a.envelope_min_score = ms;
         }
+        else if (s == "--edges") {
+            const std::string v = need(i);
+            const std::size_t c1 = v.find(':'), c2 = c1 == std::string::npos ? c1 : v.find(':', c1 + 1);
+            const auto d = parse_duration_ms(v.substr(0, c1));
+            const std::string vn = c1 == std::string::npos ? "0.5" : v.substr(c1 + 1, c2 == std::string::npos ? c2 : c2 - c1 - 1);
+            const std::string vm = c2 == std::string::npos ? "0.5" : v.substr(c2 + 1);
+            char *e1 = nullptr, *e2 = nullptr;
+            const float mn = std::strtof(vn.c_str(), &e1), mx = std::strtof(vm.c_str(), &e2);
+            if (!d || *d == 0 || vn.empty() || *e1 != '\0' || !(mn >= -1.0f && mn <= 1.0f) || vm.empty() || *e2 != '\0' || !(mx >= 0.0f && mx <= 1.0f))
+                throw ArgError("invalid value '" + v + "' for --edges (DUR[:MIN_NCC[:MAX_SECOND]], a duration longer than 0, MIN_NCC in -1..1, MAX_SECOND in 0..1)");
+            a.edges_ms = *d;
+            a.edges_min_ncc = mn;
+            a.edges_max_second = mx;
+        }
         else if (s == "--discover") {
             const std::string v = need(i);
             const auto colon = v.find(':');
@@ -546,7 +571,7 @@ inline Arguments parse_arguments(int argc, const char* const* argv) {
             {a.warp_ppm.has_value(), "--warp"}, {a.channel_radius.has_value(), "--channel"}, {!a.residual_prefix.empty(), "--residual"},
             {a.stereo_radius.has_value(), "--stereo"}, {a.min_significance.has_value(), "--min-significance"},
             {a.significance_zone_ms.has_value(), "--significance-zone"}, {!a.learn_needle.empty(), "--learn-needle"},
-            {a.envelope_pct.has_value(), "--envelope"}};
+            {a.envelope_pct.has_value(), "--envelope"}, {a.edges_ms.has_value(), "--edges"}};
         for (const auto& o : others)
             if (o.first) throw ArgError(std::string("--discover and ") + o.second + " are mutually exclusive");
         // ... and what would be ignored without a word (--normalize is what discovery does anyway; --mix and
@@ -573,6 +598,7 @@ inline Arguments parse_arguments(int argc, const char* const* argv) {
     if (a.live && a.mix_set) throw ArgError("--live: --mix does not apply");
     if (a.live && a.stereo_radius) throw ArgError("--live: --stereo does not apply");
     if (a.live && !a.trace_prefix.empty()) throw ArgError("--live: --score-trace does not apply");
+    if (a.live && a.edges_ms) throw ArgError("--live: --edges does not apply");
     if (!a.learn_needle.empty()) {
         if (a.live) throw ArgError("--live: --learn-needle does not apply");
         if (a.best) throw ArgError("--learn-needle and --best are mutually exclusive");
@@ -742,6 +768,29 @@ inline std::string envelope_line(const am_env_hit& hit, std::uint32_t sr) {
 }
 
 struct TimeLabel { double start_s, end_s; std::string name; };
+
+// extension: --edges.  An edge record counts when it has no flag but AM_EDGE_NO_SECOND, scores at least min_ncc and, where
+// there is a runner-up, that scores at most max_second of it
+inline bool edge_passes(const am_edge_hit& r, float min_ncc, float max_second) {
+    if (r.flags & ~AM_EDGE_NO_SECOND) return false;
+    if (!(r.ncc >= min_ncc)) return false;
+    return (r.flags & AM_EDGE_NO_SECOND) || (double)r.ncc_second <= (double)max_second * (double)r.ncc;
+}
+inline const char* edge_tag(const am_edge_hit& r) { return r.edge == AM_EDGE_HEAD ? "head" : "tail"; }
+inline int edge_percent(const am_edge_hit& r, std::size_t s_len) { return (int)std::llround(100.0 * (double)r.overlap / (double)s_len); }
+// "Offset head: -hh:mm:ss.mmm with ncc V overlap P %": where the snippet would start, before the file when negative
+inline std::string edge_line(const am_edge_hit& r, std::size_t s_len, std::uint32_t sr) {
+    const std::uint64_t ms = (std::uint64_t)((double)(r.start < 0 ? -r.start : r.start) * 1000.0 / (double)sr);
+    char buf[160];
+    std::snprintf(buf, sizeof buf, "Offset %s: %s%02" PRIu64 ":%02" PRIu64 ":%02" PRIu64 ".%03" PRIu64 " with ncc %.3f overlap %d %%", edge_tag(r),
+                  r.start < 0 ? "-" : "", ms / 3600000, (ms / 60000) % 60, (ms / 1000) % 60, ms % 1000, (double)r.ncc, edge_percent(r, s_len));
+    return buf;
+}
+// the label of a counted edge: the part of the file the snippet covers, [max(0, start), min(len, start + S))
+inline TimeLabel edge_label(const am_edge_hit& r, std::size_t s_len, std::size_t len, std::uint32_t sr) {
+    const std::int64_t a = std::max<std::int64_t>(0, r.start), b = std::min<std::int64_t>((std::int64_t)len, r.start + (std::int64_t)s_len);
+    return TimeLabel{(double)a / (double)sr, (double)b / (double)sr, std::string(edge_tag(r)) + " " + std::to_string(edge_percent(r, s_len)) + " %"};
+}
 
 // archive/data.rs:87-107: consecutive peak pairs -> [start_i + delay, start_{i+1}], name_pattern with '#' -> i (from 1)
 inline std::vector<TimeLabel> timelabel_from_peaks(const am_peak* peaks, std::size_t n, std::uint32_t sr,

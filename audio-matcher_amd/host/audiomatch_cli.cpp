@@ -481,8 +481,10 @@ static bool output_path(const Arguments& args, const std::string& main_file, std
 
 // mod.rs:92-99: the label file of a recording's hits (sorted by start), or with --dry-run its text on stdout.  Returns the
 // exit status this asks for: 0, or 4 where the file cannot be written.
-static int write_labels(const Arguments& args, const std::string& out_path, const std::vector<am_peak>& hits, std::uint32_t sr) {
-    const std::string text = format_labels(timelabel_from_peaks(hits.data(), hits.size(), sr, 7.0, "Segment #"));
+// `extra`: labels behind those of the hits (--edges).
+static int write_labels(const Arguments& args, const std::string& out_path, const std::vector<am_peak>& hits, std::uint32_t sr,
+                        const std::vector<TimeLabel>& extra = {}) {
+    const std::string text = format_labels(timelabel_from_peaks(hits.data(), hits.size(), sr, 7.0, "Segment #")) + format_labels(extra);
     if (args.dry_run) {
         std::printf("would write to '%s':\n%s", out_path.c_str(), text.c_str());
         return 0;
@@ -600,6 +602,26 @@ static void envelope_hits(const Arguments& args, const am_needle* algo, const st
     std::stable_sort(hits.begin(), hits.end(), [](const am_peak& a, const am_peak& b) { return a.start < b.start; });
 }
 
+// extension: --edges.  One snippet cut off by the start or the end of one main file (am_match_edges): a line per edge that
+// counts (edge_passes), printed behind the snippet's other lines, and its label into `labels`.
+static void edge_hits(const Arguments& args, const am_needle* algo, const std::vector<float>& m_samples, std::uint32_t m_sr,
+                      const std::string& prefix, std::vector<TimeLabel>& labels) {
+    if (m_samples.empty()) return;
+    am_edge_params ep{};
+    ep.min_overlap = std::max<std::uint64_t>(1, round_samples_ms(*args.edges_ms, m_sr));
+    ep.min_share = 0.05f;
+    am_edge_hit recs[2];
+    if (am_match_edges(algo, m_samples.data(), m_samples.size(), AM_FMT_F32_MONO, &ep, recs) != AM_OK)
+        throw std::runtime_error(std::string("am_match_edges: ") + am_last_error_string());
+    size_t s_len = 0;
+    am_needle_len(algo, &s_len);
+    for (const am_edge_hit& r : recs) {
+        if (!edge_passes(r, args.edges_min_ncc, args.edges_max_second)) continue;
+        if (args.verbosity >= 1) std::printf("%s%s\n", prefix.c_str(), edge_line(r, s_len, m_sr).c_str());
+        labels.push_back(edge_label(r, s_len, m_samples.size(), m_sr));
+    }
+}
+
 // extension: --score-trace.  The score curve of one snippet in one main file: its CSV file (`snippet_index`: set when the
 // run has several snippets) and, under the offset lines, its summary line.  Returns 0, or 4 where the file cannot be
 // written.
@@ -664,10 +686,12 @@ static int run_files(const Arguments& args) {
                 hits[j] = args.best ? best_hits(args, handles[j], m_samples, m_sr) : match_hits(handles[j], m_samples, p);
             }
         }
+        std::vector<TimeLabel> edge_labels;                               // extension: --edges
         for (size_t j = 0; j < k; ++j) {
             const std::string prefix = k > 1 ? snips[j].name + ": " : std::string();
             report_hits(args, handles[j], m_samples, m_sr, hits[j], prefix, learner, snips[j], file_index, m);
             if (args.envelope_pct) envelope_hits(args, handles[j], m_samples, m_sr, hits[j], prefix);
+            if (args.edges_ms) edge_hits(args, handles[j], m_samples, m_sr, prefix, edge_labels);
         }
         if (!args.trace_prefix.empty())
             for (size_t j = 0; j < k; ++j)
@@ -678,7 +702,7 @@ static int run_files(const Arguments& args) {
             std::vector<am_peak> all;
             for (const std::vector<am_peak>& h : hits) all.insert(all.end(), h.begin(), h.end());
             if (k > 1) std::stable_sort(all.begin(), all.end(), [](const am_peak& a, const am_peak& b) { return a.start < b.start; });
-            if (const int rc = write_labels(args, *out_path, all, m_sr)) rc_all = rc;
+            if (const int rc = write_labels(args, *out_path, all, m_sr, edge_labels)) rc_all = rc;
         }
     }
     if (!args.learn_needle.empty())

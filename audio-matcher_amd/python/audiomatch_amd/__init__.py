@@ -263,6 +263,17 @@ AM_DISCOVER_SELF, AM_REGION_FOLD, AM_DISCOVER_SLICE = 1, 1, 8192
 AM_PROBE_NO_BEST, AM_PROBE_NO_SECOND, AM_PROBE_NONFINITE, AM_PROBE_QUIET = 1, 2, 4, 8
 
 
+class AmEdgeParams(C.Structure):       # am_edge_params (include/audiomatch.h, edge matching), 24 bytes
+    _fields_ = [("min_overlap", C.c_uint64), ("separation", C.c_uint64), ("min_share", C.c_float), ("reserved", C.c_uint32)]
+
+
+# am_edge_hit (48 bytes, no padding) as a numpy structured dtype: what the edge calls return two of per haystack
+EDGE_HIT_DTYPE = np.dtype([("start", "<i8"), ("second", "<i8"), ("overlap", "<u8"), ("ncc", "<f4"), ("ncc_second", "<f4"),
+                           ("gain", "<f4"), ("share", "<f4"), ("edge", "<u4"), ("flags", "<u4")])
+AM_EDGE_HEAD, AM_EDGE_TAIL, AM_EDGE_TILE = 0, 1, 4096
+AM_EDGE_NO_BEST, AM_EDGE_NO_SECOND, AM_EDGE_NONFINITE, AM_EDGE_BELOW_FLOOR = 1, 2, 4, 8
+
+
 class AmEnvParams(C.Structure):        # am_env_params (include/audiomatch.h, envelope matching)
     _fields_ = [("bands", AmBandParams), ("reserved", C.c_uint32), ("floor_db", C.c_double)]
 
@@ -523,6 +534,15 @@ _SIGNATURES = {
                                      C.POINTER(AmDiscoverParams), C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]),
     "am_probe_scores": (C.c_int, [C.c_int, C.c_void_p, C.c_size_t, C.c_uint64, C.c_uint64, C.c_uint64, C.c_void_p]),
     "am_probe_scores_device": (C.c_int, [C.c_int, C.c_void_p, C.c_size_t, C.c_uint64, C.c_uint64, C.c_uint64, C.c_void_p]),
+    "am_edge_scores_len": (C.c_int, [C.c_size_t, C.c_size_t, C.c_int, C.POINTER(C.c_size_t), C.POINTER(C.c_int64)]),
+    "am_edge_scores": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.POINTER(AmEdgeParams), C.c_void_p,
+                                 C.c_size_t, C.POINTER(C.c_size_t)]),
+    "am_edge_scores_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.POINTER(AmEdgeParams), C.c_void_p,
+                                        C.c_size_t, C.POINTER(C.c_size_t)]),
+    "am_match_edges": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.POINTER(AmEdgeParams), C.c_void_p]),
+    "am_match_edges_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.POINTER(AmEdgeParams), C.c_void_p]),
+    "am_match_edges_batch_device": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.c_size_t, C.c_int,
+                                              C.POINTER(AmEdgeParams), C.c_void_p]),
     "am_discover_regions": (C.c_int, [C.c_void_p, C.c_size_t, C.POINTER(AmDiscoverParams), C.POINTER(AmRegionParams),
                                       C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]),
     "am_envelope_len": (C.c_int, [C.c_size_t, C.POINTER(AmEnvParams), C.c_double, C.POINTER(C.c_size_t)]),
@@ -1047,6 +1067,18 @@ def discover_regions(hits, params: AmDiscoverParams, rparams: AmRegionParams, ca
     return _records_call(lambda o, c, n: lib().am_discover_regions(h.ctypes.data if h.size else None, h.size, C.byref(params),
                                                                    C.byref(rparams), o, c, n),
                          REGION_DTYPE, h.size if cap is None else cap)
+
+
+def edge_params(min_overlap: int, separation: int = 0, min_share: float = 0.05) -> AmEdgeParams:
+    """am_edge_params (separation 0 = min_overlap; min_share: least E_n(u) / E_n of a candidate lag)."""
+    return AmEdgeParams(min_overlap=int(min_overlap), separation=int(separation), min_share=float(min_share), reserved=0)
+
+
+def edge_scores_len(length: int, s: int, edge: int):
+    """am_edge_scores_len: (n_lags, first_lag) of an edge for a haystack of `length` and a needle of `s` samples (pure host)."""
+    n, first = C.c_size_t(0), C.c_int64(0)
+    _check(lib().am_edge_scores_len(int(length), int(s), int(edge), C.byref(n), C.byref(first)))
+    return n.value, first.value
 
 
 def env_params(bands: AmBandParams, floor_db: float = 80.0) -> AmEnvParams:
@@ -1585,6 +1617,49 @@ class HipConvolve:
         counts = (C.c_size_t * max(1, nh))()
         _check(lib().am_match_trace_batch_device(self._h, arr_p, arr_l, nh, int(fmt), C.byref(params), out.ctypes.data, cap, counts))
         return [out[i * cap:i * cap + min(counts[i], cap)].copy() for i in range(nh)]
+
+    # -- edge matching --
+    def _edge_scores_call(self, fn, length: int, edge: int, cap):
+        cap = edge_scores_len(length, self.sample_len, edge)[0] if cap is None else int(cap)
+        out = np.zeros(max(1, cap), dtype=np.float32)
+        n = C.c_size_t(0)
+        _check(fn(out.ctypes.data, cap, C.byref(n)))
+        return out[:min(n.value, cap)]
+
+    def edge_scores(self, haystack, edge: int, params: AmEdgeParams, cap=None):
+        """am_edge_scores: the coarse partial-overlap NCC of every lag of one edge (AM_EDGE_HEAD / AM_EDGE_TAIL) of a host
+        haystack (f32, or i16 (frames, 2) interleaved stereo) in ascending lag, NaN where the lag is no candidate."""
+        a, fmt, length = _samples(haystack)
+        return self._edge_scores_call(lambda o, c, n: lib().am_edge_scores(self._h, a.ctypes.data, length, int(fmt), int(edge),
+                                                                           C.byref(params), o, c, n), length, edge, cap)
+
+    def edge_scores_device(self, ptr: int, length: int, edge: int, params: AmEdgeParams, fmt: int = Fmt.F32_MONO, cap=None):
+        """am_edge_scores_device on a haystack resident on this needle's device."""
+        return self._edge_scores_call(lambda o, c, n: lib().am_edge_scores_device(self._h, ptr, int(length), int(fmt), int(edge),
+                                                                                  C.byref(params), o, c, n), length, edge, cap)
+
+    def match_edges(self, haystack, params: AmEdgeParams):
+        """am_match_edges: the two EDGE_HIT_DTYPE records of a host haystack, [0] the head's (the recording starts inside
+        the needle), [1] the tail's (it ends inside it)."""
+        a, fmt, length = _samples(haystack)
+        out = np.zeros(2, dtype=EDGE_HIT_DTYPE)
+        _check(lib().am_match_edges(self._h, a.ctypes.data, length, int(fmt), C.byref(params), out.ctypes.data))
+        return out
+
+    def match_edges_device(self, ptr: int, length: int, params: AmEdgeParams, fmt: int = Fmt.F32_MONO):
+        """am_match_edges_device on a haystack resident on this needle's device."""
+        out = np.zeros(2, dtype=EDGE_HIT_DTYPE)
+        _check(lib().am_match_edges_device(self._h, ptr, int(length), int(fmt), C.byref(params), out.ctypes.data))
+        return out
+
+    def match_edges_batch_device(self, ptrs, lengths, params: AmEdgeParams, fmt: int = Fmt.F32_MONO):
+        """am_match_edges_batch_device: a (n_hay, 2) array of records, one pair per resident haystack."""
+        nh = len(ptrs)
+        arr_p = (C.c_void_p * max(1, nh))(*ptrs)
+        arr_l = (C.c_size_t * max(1, nh))(*lengths)
+        out = np.zeros((max(1, nh), 2), dtype=EDGE_HIT_DTYPE)
+        _check(lib().am_match_edges_batch_device(self._h, arr_p, arr_l, nh, int(fmt), C.byref(params), out.ctypes.data))
+        return out[:nh]
 
     # -- envelope matching --
     def match_envelope(self, haystack, ep: AmEnvParams, grid: AmEnvGrid, min_score: float, cap=None):

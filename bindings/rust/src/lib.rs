@@ -312,6 +312,30 @@ pub struct AmProbeHit {
     pub flags: u32,
     pub reserved: u32,
 }
+/// am_edge_params: least overlap (at least 1), the runner-up's least distance (0 = min_overlap), the least share of the
+/// needle's energy a candidate lag holds (in [0, 1]); reserved = 0.  24 bytes
+#[repr(C)]
+#[derive(Clone, Copy, Default, Debug)]
+pub struct AmEdgeParams {
+    pub min_overlap: u64,
+    pub separation: u64,
+    pub min_share: f32,
+    pub reserved: u32,
+}
+/// am_edge_hit: the record of one edge of a haystack (am_match_edges*), 48 bytes
+#[repr(C)]
+#[derive(Clone, Copy, Default, Debug)]
+pub struct AmEdgeHit {
+    pub start: i64,
+    pub second: i64,
+    pub overlap: u64,
+    pub ncc: f32,
+    pub ncc_second: f32,
+    pub gain: f32,
+    pub share: f32,
+    pub edge: u32,
+    pub flags: u32,
+}
 /// am_discover_params: probe length and hop (at least 1), the exclusion of a self search, the runner-up's least
 /// distance (0 = probe_len), the level rule, AM_DISCOVER_SELF; reserved = 0
 #[repr(C)]
@@ -402,6 +426,13 @@ pub const AM_PROBE_NO_SECOND: u32 = 2;
 pub const AM_PROBE_NONFINITE: u32 = 4;
 pub const AM_PROBE_QUIET: u32 = 8;
 pub const AM_DISCOVER_SLICE: u64 = 8192;
+pub const AM_EDGE_HEAD: c_int = 0;
+pub const AM_EDGE_TAIL: c_int = 1;
+pub const AM_EDGE_NO_BEST: u32 = 1;
+pub const AM_EDGE_NO_SECOND: u32 = 2;
+pub const AM_EDGE_NONFINITE: u32 = 4;
+pub const AM_EDGE_BELOW_FLOOR: u32 = 8;
+pub const AM_EDGE_TILE: u64 = 4096;
 pub const AM_TRACE_WAVE_BIN_MAX: u64 = 2048;
 pub const AM_TRACE_SLICE: u64 = 8192;
 pub const AM_TRACE_MAX_BIN: u64 = 1 << 30;
@@ -720,6 +751,28 @@ extern "C" {
     pub fn am_discover_regions(
         hits: *const AmProbeHit, n: usize, dp: *const AmDiscoverParams, rp: *const AmRegionParams, out: *mut AmRegion, cap: usize,
         n_out: *mut usize,
+    ) -> c_int;
+    /// edge matching: a needle cut off by a recording's start or end (audiomatch.h)
+    pub fn am_edge_scores_len(len: usize, s: usize, edge: c_int, n_lags: *mut usize, first_lag: *mut i64) -> c_int;
+    pub fn am_edge_scores_device(
+        h: *const AmNeedle, d_haystack: *const std::ffi::c_void, len: usize, sample_format: c_int, edge: c_int, ep: *const AmEdgeParams,
+        out: *mut f32, cap: usize, n_out: *mut usize,
+    ) -> c_int;
+    pub fn am_edge_scores(
+        h: *const AmNeedle, haystack: *const std::ffi::c_void, len: usize, sample_format: c_int, edge: c_int, ep: *const AmEdgeParams,
+        out: *mut f32, cap: usize, n_out: *mut usize,
+    ) -> c_int;
+    pub fn am_match_edges_device(
+        h: *const AmNeedle, d_haystack: *const std::ffi::c_void, len: usize, sample_format: c_int, ep: *const AmEdgeParams,
+        out: *mut AmEdgeHit,
+    ) -> c_int;
+    pub fn am_match_edges(
+        h: *const AmNeedle, haystack: *const std::ffi::c_void, len: usize, sample_format: c_int, ep: *const AmEdgeParams,
+        out: *mut AmEdgeHit,
+    ) -> c_int;
+    pub fn am_match_edges_batch_device(
+        h: *const AmNeedle, d_haystacks: *const *const std::ffi::c_void, lens: *const usize, n_hay: usize, sample_format: c_int,
+        ep: *const AmEdgeParams, out: *mut AmEdgeHit,
     ) -> c_int;
     /// envelope matching: a needle played at another speed, found through band-level envelopes (audiomatch.h)
     pub fn am_envelope_len(len: usize, ep: *const AmEnvParams, drift_ppm: f64, n_frames: *mut usize) -> c_int;

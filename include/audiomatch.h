@@ -725,6 +725,88 @@ int am_probe_scores_device(int device, const float* d_scores, size_t n, uint64_t
 int am_discover_regions(const am_probe_hit* hits, size_t n, const am_discover_params* dp,
                         const am_region_params* rp, am_region* out, size_t cap, size_t* n_out);
 
+/* ---- edge matching: a needle cut off by a recording's start or end -------------------------------------------------
+ * Every entry point above that finds a needle scores whole windows only: an occurrence that begins before the
+ * recording does, or ends after it, is invisible to them ("When a recording starts or ends inside the
+ * needle").  This family scores the partial overlaps at the two edges, each normalised by the energy of the part of
+ * the needle that lies inside the recording.
+ *
+ * Needle n[0, S), the handle's whole needle.  Haystack x[0, len), f32 mono or, for AM_FMT_S16_STEREO, the bit-exact
+ * down-mix of am_pcm16_downmix.  A lag u (signed) puts n[0] at x[u].
+ *   Head lags  u < 0 and u + S <= len: the needle's first k = -u samples are missing, the overlap is L = S + u.  In f64
+ *              c(u) = sum_{i<L} x[i] n[k+i],  E_n(u) = sum_{i>=k} n[i]^2 (a suffix sum),  E_x(u) = sum_{i<L} x[i]^2 (a prefix sum).
+ *              They are u = -(S - 1) .. min(-1, len - S): min(len, S - 1) lags.
+ *   Tail lags  u >= 0 and u + S > len: the overlap is L = len - u.  In f64
+ *              c(u) = sum_{i<L} x[u+i] n[i],  E_n(u) = sum_{i<L} n[i]^2 (a prefix sum),  E_x(u) = sum_{i>=u} x[i]^2 (a suffix sum).
+ *              They are u = max(0, len - S + 1) .. len - 1: min(len, S - 1) lags.
+ *   Lags cut at BOTH ends (u < 0 and u + S > len; they exist only when len < S) are not in scope: a clip that lies
+ *   inside the needle is am_match with the roles swapped -- a needle handle made from the clip, the needle as haystack.
+ *   A needle of one sample has no edge lags.  am_edge_scores_len (pure host) returns an edge's lag count and first lag.
+ * Every energy is a pure prefix or suffix sum of non-negative terms, never a difference of two prefix values.
+ *
+ * Score: ncc(u) = c(u) / sqrt(E_n(u) E_x(u)); 0 when E_x(u) = 0 or E_x(u) < E_n(u) 10^(-score_norm_floor_db / 10) (the
+ * process option, as am_hit_scores reads it) -- such a lag stays a candidate with score 0 -- and 0 when E_n(u) = 0.
+ * Candidates of an edge: its lags with L >= min_overlap, E_n(u) >= (double)min_share E_n (in f64; E_n the needle's
+ * energy) and no non-finite haystack sample in the overlap.  Non-finite haystack samples are zeroed in the copy of the
+ * span that is correlated, so they cost exactly the lags whose overlap contains them: at the head the lags with L
+ * greater than the index of the first non-finite sample, at the tail the lags u at or before the last one.  A non-finite
+ * needle sample: both records carry AM_EDGE_NONFINITE and NaN scores, every coarse score is NaN, nothing is launched.
+ * Spans read: head x[0, min(len, S - 1)), tail x[max(0, len - S + 1), len); the host forms copy only these.
+ *
+ * Two stages, as in discovery.  COARSE scores (am_edge_scores*): f32, one per lag of the edge in ascending u, NaN where
+ * the lag is no candidate.  c(u) comes from the f32 transforms of the overlap-save engine over the span -- always f32,
+ * whatever "half_pipeline" says, "score_norm" is ignored, "log_n" applies --, the quotient is taken with the f64
+ * energies and rounded once.  Coarse scores are not defined to the bit.  RECORD per edge (am_edge_hit): start is the
+ * largest coarse candidate, ties to the lowest u; second is the largest coarse candidate with |u - start| >= separation
+ * (separation = 0 means min_overlap), the same tie rule -- exactly the rule of am_probe_scores on the coarse array.  No
+ * candidate: AM_EDGE_NO_BEST | AM_EDGE_NO_SECOND, lags 0, overlap 0, NaN scores.  No runner-up: AM_EDGE_NO_SECOND, second
+ * 0, ncc_second NaN.  The two chosen lags are then scored again exactly, by direct f64 sums on the device (the order of
+ * the additions is not part of the contract): ncc, ncc_second, gain = c / E_n(u) (0 when E_n(u) = 0), share = E_n(u) /
+ * E_n, overlap = L, each rounded once to f32; AM_EDGE_BELOW_FLOOR when the best lag's exact score fell under the floor
+ * rule.  A record depends on the needle, the span and the parameters only: the three am_match_edges* forms agree bit
+ * for bit, alone and in any batch.
+ *
+ * The kernels (am_edges.hip): one pass per span (down-mix, zeroing, first / last non-finite index); four f64 energy
+ * scans (the needle's two are kept on the handle), each in three launches of a fixed order over tiles of AM_EDGE_TILE
+ * elements; the engine's transforms; one normalising launch; the record rule; one launch for the exact sums of the at
+ * most four chosen lags and one that folds them.  Profile class "edges".
+ *
+ * Outputs are host memory.  am_edge_scores*: cap < n_lags gives AM_ERR_CAPACITY with the count in *n_out.  out of
+ * am_match_edges*: [0] the head's record, [1] the tail's; the batch form writes two per haystack.
+ * AM_ERR_INVALID_ARG (the message names the field): a null pointer, reserved != 0, min_overlap = 0, min_share NaN or
+ * outside [0, 1], a bad format or edge, len = 0, a haystack that is not on the needle's device (_device forms). */
+enum { AM_EDGE_HEAD = 0, AM_EDGE_TAIL = 1 };
+#define AM_EDGE_NO_BEST 1u                    /* am_edge_hit.flags */
+#define AM_EDGE_NO_SECOND 2u
+#define AM_EDGE_NONFINITE 4u
+#define AM_EDGE_BELOW_FLOOR 8u
+#define AM_EDGE_TILE 4096                     /* elements per tile of the three-phase energy scans */
+typedef struct am_edge_params {
+    uint64_t min_overlap;     /* least overlap L of a candidate: at least 1 */
+    uint64_t separation;      /* least distance of the runner-up from the best; 0 = min_overlap */
+    float    min_share;       /* least E_n(u) / E_n of a candidate, in [0, 1] */
+    uint32_t reserved;        /* 0 */
+} am_edge_params;             /* 24 bytes */
+typedef struct am_edge_hit {
+    int64_t  start, second;   /* the lags u of the best and of the runner-up */
+    uint64_t overlap;         /* L of the best */
+    float    ncc, ncc_second; /* exact scores; NaN where there is none */
+    float    gain, share;     /* c / E_n(u) and E_n(u) / E_n of the best */
+    uint32_t edge, flags;     /* AM_EDGE_HEAD / AM_EDGE_TAIL; AM_EDGE_* */
+} am_edge_hit;                /* 48 bytes, no padding */
+
+int am_edge_scores_len(size_t len, size_t s, int edge, size_t* n_lags, int64_t* first_lag);
+int am_edge_scores_device(const am_needle* h, const void* d_haystack, size_t len, int sample_format, int edge,
+                          const am_edge_params* ep, float* out, size_t cap, size_t* n_out);
+int am_edge_scores(const am_needle* h, const void* haystack, size_t len, int sample_format, int edge,
+                   const am_edge_params* ep, float* out, size_t cap, size_t* n_out);
+int am_match_edges_device(const am_needle* h, const void* d_haystack, size_t len, int sample_format,
+                          const am_edge_params* ep, am_edge_hit* out);
+int am_match_edges(const am_needle* h, const void* haystack, size_t len, int sample_format,
+                   const am_edge_params* ep, am_edge_hit* out);
+int am_match_edges_batch_device(const am_needle* h, const void* const* d_haystacks, const size_t* lens, size_t n_hay,
+                                int sample_format, const am_edge_params* ep, am_edge_hit* out);
+
 /* ---- envelope matching: a needle played at another speed --------------------------------------------------------
  * Every entry point above that FINDS a needle correlates waveforms: it finds an occurrence that runs on the needle's
  * clock and keeps the needle's phases ("When a hit runs on another clock": a 10 s needle is followed to
@@ -1549,7 +1631,8 @@ int am_set_chunk_progress_callback(am_chunk_progress_fn fn, void* user);
  * "peaks", "other", "trace" -- the score-trace kernels --, "discover" -- the
  * kernels of needle discovery --, "envelope_frames", "envelope_prefix",
  * "envelope_correlate" -- the levels, the prefix sums and the correlation of
- * envelope matching; "envelope" adds the three -- or "*" for all). */
+ * envelope matching; "envelope" adds the three --, "edges" -- the span, scan,
+ * normalising and exact kernels of edge matching -- or "*" for all). */
 int am_profile_enable(int device, int on);
 int am_profile_reset(int device);
 int am_profile_query(int device, const char* kernel, double* total_ms, uint64_t* launches);

@@ -16,6 +16,7 @@
 #pragma once
 
 #include <algorithm>
+#include <array>
 #include <cmath>
 #include <cstddef>
 #include <cstdint>
@@ -399,6 +400,48 @@ public:
         check(am_match_trace_batch_device(h_, d_haystacks.data(), lens.data(), nh, sample_format, &tp, buf.data(), cap, n.data()));
         std::vector<std::vector<am_trace_bin>> out(nh);
         for (std::size_t i = 0; i < nh; ++i) out[i].assign(buf.begin() + (std::ptrdiff_t)(i * cap), buf.begin() + (std::ptrdiff_t)(i * cap + n[i]));
+        return out;
+    }
+    // edge matching (am_match_edges): the records of the two edges of a haystack, [0] the head's (the recording starts
+    // inside the needle), [1] the tail's (it ends inside it); edge_scores: the coarse score of every lag of one edge
+    std::array<am_edge_hit, 2> match_edges(const void* haystack, std::size_t len, int sample_format, const am_edge_params& ep) const {
+        std::array<am_edge_hit, 2> out{};
+        check(am_match_edges(h_, haystack, len, sample_format, &ep, out.data()));
+        return out;
+    }
+    std::array<am_edge_hit, 2> match_edges_device(const void* d_haystack, std::size_t len, int sample_format, const am_edge_params& ep) const {
+        std::array<am_edge_hit, 2> out{};
+        check(am_match_edges_device(h_, d_haystack, len, sample_format, &ep, out.data()));
+        return out;
+    }
+    std::vector<std::array<am_edge_hit, 2>> match_edges_batch_device(const std::vector<const void*>& d_haystacks, const std::vector<std::size_t>& lens,
+                                                                     int sample_format, const am_edge_params& ep) const {
+        if (d_haystacks.size() != lens.size()) check(AM_ERR_INVALID_ARG);
+        std::vector<std::array<am_edge_hit, 2>> out(d_haystacks.size());
+        static_assert(sizeof(std::array<am_edge_hit, 2>) == 2 * sizeof(am_edge_hit), "two records side by side");
+        check(am_match_edges_batch_device(h_, d_haystacks.data(), lens.data(), d_haystacks.size(), sample_format, &ep,
+                                          out.empty() ? nullptr : out[0].data()));
+        return out;
+    }
+    std::vector<float> edge_scores(const void* haystack, std::size_t len, int sample_format, int edge, const am_edge_params& ep) const {
+        return edge_scores_filled(len, edge, [&](float* out, std::size_t cap, std::size_t* n) {
+            return am_edge_scores(h_, haystack, len, sample_format, edge, &ep, out, cap, n);
+        });
+    }
+    std::vector<float> edge_scores_device(const void* d_haystack, std::size_t len, int sample_format, int edge, const am_edge_params& ep) const {
+        return edge_scores_filled(len, edge, [&](float* out, std::size_t cap, std::size_t* n) {
+            return am_edge_scores_device(h_, d_haystack, len, sample_format, edge, &ep, out, cap, n);
+        });
+    }
+    template <class Call>
+    std::vector<float> edge_scores_filled(std::size_t len, int edge, Call call) const {
+        std::size_t s = 0, n = 0;
+        std::int64_t first = 0;
+        check(am_needle_len(h_, &s));
+        check(am_edge_scores_len(len, s, edge, &n, &first));
+        std::vector<float> out(std::max<std::size_t>(1, n));
+        check(call(out.data(), n, &n));
+        out.resize(n);
         return out;
     }
     // runs call(out, cap, &n) on a growing record buffer until it fits
