@@ -16,7 +16,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(HERE, "build")
 LIB = os.path.join(HERE, "libaudiomatch_amd.so")
-SOURCES = ["am_fft.hip", "am_peaks.hip", "am_context.hip", "am_correlate.hip", "am_engine.hip", "am_stream.hip", "am_monitor.hip", "am_pool.hip", "am_norm.hip", "am_hits.hip", "am_segments.hip", "am_bands.hip", "am_significance.hip", "am_resample.hip", "am_whiten.hip", "am_estimate.hip", "am_warp.hip", "am_channel.hip", "am_stereo.hip",
+SOURCES = ["am_fft.hip", "am_peaks.hip", "am_context.hip", "am_correlate.hip", "am_engine.hip", "am_stream.hip", "am_monitor.hip", "am_pool.hip", "am_norm.hip", "am_hits.hip", "am_mask.hip", "am_segments.hip", "am_bands.hip", "am_significance.hip", "am_resample.hip", "am_whiten.hip", "am_estimate.hip", "am_warp.hip", "am_channel.hip", "am_stereo.hip",
            "am_best.hip", "am_trace.hip", "am_discover.hip", "am_edges.hip", "am_envelope.hip", "am_api.hip"]
 HEADERS = [os.path.join(CSRC, "am_kernels.h"), os.path.join(CSRC, "am_internal.h"), os.path.join(CSRC, "am_walk.h"), os.path.join(CSRC, "am_spans.h"), os.path.join(CSRC, "am_wave_steps.h"),
            os.path.join(CSRC, "am_hit_device.h"), os.path.join(CSRC, "am_reduce.h"), os.path.join(CSRC, "am_frames.h"),

@@ -114,7 +114,7 @@ int realloc_refused(const char* what, size_t bytes, size_t cap) {
 }
 
 static const char* kKernelNames[] = {"k1_cols_fwd", "k2_rows", "k3_cols_inv", "tile_stats", "peaks", "other", "trace", "discover",
-                                     "envelope_frames", "envelope_prefix", "envelope_correlate", "edges"};
+                                     "envelope_frames", "envelope_prefix", "envelope_correlate", "edges", "mask"};
 static std::mutex g_ctx_mu;
 static std::map<int, Ctx*> g_ctx;
 
@@ -451,11 +451,97 @@ int create_needle_common(Ctx* c, float* d_needle, size_t n, am_needle** out) {
     return AM_OK;
 }
 
+// ---- masked needles ---------------------------------------------------------------
+// the rules of include/audiomatch.h ("masked needles") for the gaps of an n-sample needle; needs no device
+static int check_gaps(size_t n, const am_span* gaps, size_t n_gaps) {
+    if (n_gaps > 0 && !gaps) return fail(AM_ERR_INVALID_ARG, "null gaps");
+    if (n_gaps > AM_MASK_MAX_GAPS)
+        return fail(AM_ERR_INVALID_ARG, "masked needle: " + std::to_string(n_gaps) + " gaps, at most " + std::to_string(AM_MASK_MAX_GAPS) + " (AM_MASK_MAX_GAPS)");
+    for (size_t i = 0; i < n_gaps; ++i) {
+        const std::string who = "masked needle: gap " + std::to_string(i) + " [" + std::to_string(gaps[i].begin) + ", " + std::to_string(gaps[i].end) + "): ";
+        if (gaps[i].begin >= gaps[i].end) return fail(AM_ERR_INVALID_ARG, who + "empty or reversed (begin < end required)");
+        if (gaps[i].end > n) return fail(AM_ERR_INVALID_ARG, who + "ends behind the needle's " + std::to_string(n) + " samples (end <= n required)");
+        if (i > 0 && gaps[i].begin < gaps[i - 1].end) return fail(AM_ERR_INVALID_ARG, who + "begins before gap " + std::to_string(i - 1) + " ends (gaps must ascend)");
+        if (i > 0 && gaps[i].begin == gaps[i - 1].end)
+            return fail(AM_ERR_INVALID_ARG, who + "touches gap " + std::to_string(i - 1) + " (merge touching gaps: every kept span must be non-empty)");
+    }
+    if (n_gaps == 1 && gaps[0].begin == 0 && gaps[0].end == n) return fail(AM_ERR_INVALID_ARG, "masked needle: gap 0 covers the whole needle (at least one sample must be kept)");
+    if (n_gaps > 0 && (long long)n > kSegmentFrom)
+        return fail(AM_ERR_INVALID_ARG, "masked needle: " + std::to_string(n) + " samples is long enough to be partitioned (more than " +
+                                            std::to_string(kSegmentFrom) + "); masked partitioned needles are not supported");
+    return AM_OK;
+}
+
+// The handle over d (n samples, owned from here on, freed if this fails) with the gaps' samples set to +0, the gaps and
+// the kept spans' device table.  No gaps: create_needle_common's handle.
+static int create_needle_masked(Ctx* c, float* d, size_t n, const am_span* gaps, size_t n_gaps, am_needle** out) {
+    std::vector<long long> kept;
+    for (size_t i = 0; i <= n_gaps && n_gaps > 0; ++i) {
+        const long long a = i == 0 ? 0 : (long long)gaps[i - 1].end, b = i == n_gaps ? (long long)n : (long long)gaps[i].begin;
+        if (b > a) { kept.push_back(a); kept.push_back(b); }   // (only the first and the last can be empty: a leading / trailing gap)
+    }
+    long long* d_kept = nullptr;
+    float* d_orig = nullptr;
+    hipError_t e = hipSuccess;
+    if (n_gaps > 0) e = hipMalloc((void**)&d_orig, sizeof(float) * n);
+    if (e == hipSuccess && n_gaps > 0) e = hipMemcpyAsync(d_orig, d, sizeof(float) * n, hipMemcpyDeviceToDevice, c->stream);
+    for (size_t q = 0; q + 1 < kept.size() && e == hipSuccess; q += 2)
+        e = hipMemsetAsync(d_orig + kept[q], 0, sizeof(float) * (size_t)(kept[q + 1] - kept[q]), c->stream);
+    for (size_t i = 0; i < n_gaps && e == hipSuccess; ++i)
+        e = hipMemsetAsync(d + gaps[i].begin, 0, sizeof(float) * (size_t)(gaps[i].end - gaps[i].begin), c->stream);
+    if (e == hipSuccess && n_gaps > 0) e = hipMalloc((void**)&d_kept, sizeof(long long) * kept.size());
+    if (e == hipSuccess && n_gaps > 0) e = copy_on_stream(c, d_kept, kept.data(), sizeof(long long) * kept.size(), hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+        (void)hipStreamSynchronize(c->stream);
+        (void)hipFree(d);
+        if (d_kept) (void)hipFree(d_kept);
+        if (d_orig) (void)hipFree(d_orig);
+        return hip_fail(e, "masked needle");
+    }
+    am_needle* h = nullptr;
+    const int rc = create_needle_common(c, d, n, &h);
+    if (rc) { if (d_kept) (void)hipFree(d_kept); if (d_orig) (void)hipFree(d_orig); return rc; }
+    h->gaps.assign(gaps, gaps + n_gaps);
+    h->d_kept = d_kept;
+    h->d_gap_orig = d_orig;
+    h->n_kept = (int)(kept.size() / 2);
+    *out = h;
+    return AM_OK;
+}
+
+static int needle_create_masked(bool device_io, int device, const float* needle, size_t n, const am_span* gaps, size_t n_gaps, am_needle** out) {
+    if (!needle || !out || n == 0) return fail(AM_ERR_INVALID_ARG, "needle must be non-empty");
+    int rc = check_gaps(n, gaps, n_gaps);
+    if (rc) return rc;
+    Ctx* c = nullptr;
+    if ((rc = get_ctx(device, &c))) return rc;
+    std::lock_guard<std::recursive_mutex> lk(c->mu);
+    float* d = nullptr;
+    AM_HIP(hipMalloc((void**)&d, n * sizeof(float)));
+    const hipError_t e = copy_on_stream(c, d, needle, n * sizeof(float), device_io ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice);
+    if (e != hipSuccess) { (void)hipFree(d); return hip_fail(e, device_io ? "copy_on_stream(c, needle d2d)" : "copy_on_stream(c, needle)"); }
+    return create_needle_masked(c, d, n, gaps, n_gaps, out);
+}
+
 }  // namespace am
 
 using namespace am;
 
 extern "C" {
+
+int am_needle_create_masked(int device, const float* needle, size_t n, const am_span* gaps, size_t n_gaps, am_needle** out) {
+    return needle_create_masked(false, device, needle, n, gaps, n_gaps, out);
+}
+
+int am_needle_create_masked_device(int device, const float* d_needle, size_t n, const am_span* gaps, size_t n_gaps, am_needle** out) {
+    return needle_create_masked(true, device, d_needle, n, gaps, n_gaps, out);
+}
+
+int am_needle_mask(const am_needle* h, am_span* gaps, size_t cap, size_t* n_gaps) {
+    if (!h || !h->ctx) return fail(AM_ERR_INVALID_ARG, "null needle handle");
+    if (!n_gaps || (cap > 0 && !gaps)) return fail(AM_ERR_INVALID_ARG, "null pointer");
+    return hand_back(h->gaps, gaps, cap, n_gaps, "am_needle_mask: more gaps than cap");
+}
 
 int am_needle_create(int device, const float* needle, size_t n, am_needle** out) {
     if (!needle || !out || n == 0) return fail(AM_ERR_INVALID_ARG, "needle must be non-empty");
@@ -497,6 +583,8 @@ void am_needle_destroy(am_needle* h) {
         for (am_needle* sub : h->segments) { free_spectra(sub); delete sub; }
         free_spectra(h);
         if (h->d_edge_scans) (void)hipFree(h->d_edge_scans);
+        if (h->d_kept) (void)hipFree(h->d_kept);
+        if (h->d_gap_orig) (void)hipFree(h->d_gap_orig);
         if (h->d_needle && h->owns_data) (void)hipFree(h->d_needle);
     }
     delete h;

@@ -1,5 +1,5 @@
 // am_hit_device.h -- the device steps the per-hit kernels share (am_hits.hip, am_segments.hip, am_channel.hip,
-// am_stereo.hip, am_warp.hip, am_significance.hip, am_bands.hip), and the host loop that launches them.  The families
+// am_stereo.hip, am_warp.hip, am_significance.hip, am_bands.hip, am_mask.hip), and the host loop that launches them.  The families
 // promise results that are bit for bit the same across call forms, and some are checked against each other: that holds
 // while every one of them adds in the same order.  The order is written down here, the workgroup sum's in am_reduce.h, and
 // nowhere else (am_bands.hip: the combine's sums, level_db and the host loop).  Included by those .hip files only.

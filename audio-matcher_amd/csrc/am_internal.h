@@ -135,7 +135,7 @@ struct Plan {
 struct ScoreSide { DevBuf scores, stats, stats32, wflags, peaks, work; };
 
 struct ProfRec { int name; hipEvent_t e0, e1; };
-enum { KN_K1 = 0, KN_K2, KN_K3, KN_STATS, KN_PEAKS, KN_OTHER, KN_TRACE, KN_DISCOVER, KN_ENV_FRAMES, KN_ENV_PREFIX, KN_ENV_CORR, KN_EDGES, KN_COUNT };
+enum { KN_K1 = 0, KN_K2, KN_K3, KN_STATS, KN_PEAKS, KN_OTHER, KN_TRACE, KN_DISCOVER, KN_ENV_FRAMES, KN_ENV_PREFIX, KN_ENV_CORR, KN_EDGES, KN_MASK, KN_COUNT };
 
 struct Ctx {
     int device = -1;
@@ -307,6 +307,15 @@ struct am_needle {
     // edge matching (am_edges.hip): the needle's f64 energy scans, n prefix sums and n suffix sums behind them, made by
     // the first call that needs them
     double* d_edge_scans = nullptr;
+    // masked needles (am_needle_create_masked): the gaps as given (none: an ordinary handle) and the kept spans between
+    // them, as the device table the masked normalising kernel reads (am_norm.hip): [a_0, b_0, a_1, b_1, ..], ascending.
+    // d_needle holds +0 in the gaps, so `energy` is the energy of the kept samples.
+    // d_gap_orig (n samples) is the complement: the needle's original samples in the gaps, +0 in the kept spans
+    // (am_hit_mask, am_mask.hip).
+    std::vector<am_span> gaps;
+    long long* d_kept = nullptr;
+    int n_kept = 0;
+    float* d_gap_orig = nullptr;
 };
 
 namespace am {
@@ -459,8 +468,9 @@ HalfScale half_scale(const am_needle* h, const Opts& o, const PlanDev& pl);
 int needle_k2_spectrum(am_needle* h, const Opts& o, const Plan* pl, const float2** hc, HalfScale* hs);
 
 // ---- am_norm.hip ----
-// Option "score_norm" as a call sees it: on, the needle's energy and the floor (scores of windows with less energy are 0)
-struct NormSpec { bool on; double energy, thr; };
+// Option "score_norm" as a call sees it: on, the needle's energy and the floor (scores of windows with less energy are 0);
+// for a masked handle the kept spans (device table of the handle, n_kept > 0) and the energy of the kept samples
+struct NormSpec { bool on; double energy, thr; const long long* kept; int n_kept; };
 NormSpec norm_spec(const am_needle* h, const Opts& o);
 int norm_check(const NormSpec& ns, int scale);   // AM_ERR_INVALID_ARG unless the scale is AM_SCALE_LIB (when on)
 float norm_factor(const NormSpec& ns);           // K3's factor under score_norm: 1 / sqrt(needle energy)
@@ -599,14 +609,15 @@ int hit_call_batch(const F& f, const am_needle* const* needles, size_t n_needles
 // `recs` records per hit: the table up through pinned memory (no staging in the runtime, which is most of a small
 // call's time), launch(table, parts, flags, results) on c's stream, the results back and out to out[i]
 template <class Desc, class Rec, class Launch>
-int hit_round_trip(Ctx* c, const std::vector<Desc>& hits, size_t part_bytes, size_t n_parts, size_t recs, Rec* const* out, Launch launch) {
+int hit_round_trip(Ctx* c, const std::vector<Desc>& hits, size_t part_bytes, size_t n_parts, size_t recs, Rec* const* out, Launch launch,
+                   int prof_class = KN_OTHER) {
     const size_t n = hits.size(), tab_bytes = sizeof(Desc) * n, out_bytes = sizeof(Rec) * recs * n;
     int rc;
     if ((rc = hit_io_reserve(c, tab_bytes, out_bytes)) || (rc = c->hit_parts.ensure(part_bytes * n_parts)) ||
         (rc = c->hit_flags.ensure(sizeof(unsigned) * n_parts)) || (rc = hit_table_put(c, hits.data(), 0, tab_bytes)))
         return rc;
     {
-        ProfScope ps(c, KN_OTHER, c->stream);
+        ProfScope ps(c, prof_class, c->stream);
         AM_HIP(launch(static_cast<const Desc*>(c->hit_tab.p), static_cast<double*>(c->hit_parts.p), static_cast<unsigned*>(c->hit_flags.p),
                       static_cast<Rec*>(c->hit_out.p)));
     }

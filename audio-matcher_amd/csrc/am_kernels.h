@@ -302,8 +302,14 @@ struct NormJob {
     double thr;
     float* scores;
     long long a, b;
+    // masked needles: the kept spans [kept[2q], kept[2q + 1]) of the needle, ascending (device memory), n_kept of them,
+    // at most kNormMaxKept; the energy is then the sum over these spans only.  n_kept = 0: the whole window [0, s).
+    const long long* kept;
+    int n_kept;
 };
-hipError_t launch_norm_scores(hipStream_t st, const NormJob& j);
+constexpr int kNormMaxKept = AM_MASK_MAX_GAPS + 1;
+hipError_t launch_norm_scores(hipStream_t st, const NormJob& j);          // n_kept = 0
+hipError_t launch_masked_norm_scores(hipStream_t st, const NormJob& j);   // n_kept > 0
 
 // ---- am_hits.hip: per-hit scoring (am_hit_scores*) ----
 constexpr int kHitSlice = 4096;                   // needle samples per workgroup of the slice kernel
@@ -322,6 +328,25 @@ struct HitDesc {
 // parts: 4 doubles per slice (corr(t - 1), corr(t), corr(t + 1), E_w), pflags: one word per slice; d_out: n records
 hipError_t launch_hit_scores(hipStream_t st, const HitDesc* d_hits, long long n, long long max_slices, int kind, double* parts,
                              unsigned* pflags, am_hit_score* d_out);
+
+// ---- am_mask.hip: the per-hit record of a masked handle (am_hit_mask*) ----
+constexpr int kMaskSums = 5;   // doubles per partial record: c_k, E_x^M, c_g, E_x,gaps, E_n,gaps
+// One hit of a call, as the kernels read it (the call's hit table, uploaded once)
+struct MaskDesc {
+    const void* win;         // device: sample t of the haystack (f32 mono, or an i16 stereo frame for kind 1)
+    const float* needle;     // device: the handle's needle (gap samples +0)
+    const float* orig;       // device: the original samples in the gaps, +0 in the kept spans; null without gaps
+    const long long* kept;   // device: the kept spans [kept[2q], kept[2q + 1]), n_kept of them; 0: no mask, every sample is kept
+    int n_kept;
+    int kind;                // 0 = f32 mono, 1 = i16 stereo (one kind per launch)
+    long long s;             // needle length
+    double en, thr;          // the kept samples' energy, the floor on E_x^M
+    long long part0;         // first partial record of the hit
+};
+// parts: kMaskSums doubles per slice of kHitSlice needle samples, pflags: one word per slice (bit 0: a non-finite sample
+// under a kept span, bit 1: under a gap); d_out: n records
+hipError_t launch_hit_mask(hipStream_t st, const MaskDesc* d_hits, long long n, long long max_slices, int kind, double* parts,
+                           unsigned* pflags, am_mask_hit* d_out);
 
 // ---- am_segments.hip: per-segment hit scoring (am_hit_segments*) ----
 // The slice kernel exists for three radii; a call runs the smallest that holds its R (kSegRadii) and reads the lags

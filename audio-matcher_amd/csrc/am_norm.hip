@@ -11,6 +11,9 @@
 //                  floor of a quiet needle, and a window of digital silence must come out as exactly 0.
 //                  Needles shorter than kNormTile + 2 kNormBlock take a direct path: one local prefix scan over the
 //                  tile's kNormTile + S - 1 samples.
+//   masked_norm_scores   the same for a masked needle (am_needle_create_masked): the energy of the kept samples only,
+//                  each kept span assembled as a needle of its own length (span_energy, shared with norm_scores), the
+//                  spans added in span order.  A handle without gaps never gets here.
 // Every score depends on its index, the samples and the needle only (tiles start at multiples of kNormTile of the
 // score array, the reductions run in a fixed order): a haystack's bits do not depend on the batch it travels in.
 #include "am_internal.h"
@@ -53,14 +56,12 @@ __global__ __launch_bounds__(kNormThreads) void block_energy_kernel(const void* 
     if (threadIdx.x == 0) blk[blockIdx.x] = s;
 }
 
-__global__ __launch_bounds__(kNormThreads) void norm_scores_kernel(NormJob j, long long tile0) {
-    __shared__ double buf[kNormSpan];
-    __shared__ double ws[kNormThreads / 64];
+// The energies e[r] of the kNormPer windows a thread owns, [u0 + k, u0 + k + S) for k = tid + r kNormThreads: whole
+// blocks plus head suffix and tail prefix (S >= kNormTile + 2 kNormBlock), or one local scan (shorter).  Every thread of
+// the workgroup calls it with the same u0 and S; a barrier must follow before buf is written again.
+__device__ __forceinline__ void span_energy(const NormJob& j, long long u0, long long S, double* buf, double* ws, double (&e)[kNormPer]) {
     const int tid = threadIdx.x;
-    const long long t0 = (tile0 + blockIdx.x) * kNormTile;
-    const long long u0 = t0 - j.lead;   // first sample of the tile's first window
-    const long long S = j.s, B = kNormBlock;
-    double e[kNormPer];
+    const long long B = kNormBlock;
     if (S >= kNormTile + 2 * kNormBlock) {
         // shared whole blocks [A, Z): A at or behind every window start of the tile, Z at or before every window end
         const long long A = floor_div(u0 + kNormTile - 1 + B - 1, B) * B;
@@ -100,14 +101,49 @@ __global__ __launch_bounds__(kNormThreads) void norm_scores_kernel(NormJob j, lo
             e[r] = buf[k + S - 1] - (k > 0 ? buf[k - 1] : 0.0);   // (local sums: a window of zeros gives exactly 0)
         }
     }
+}
+
+// the tile's scores [t0, t0 + kNormTile) within [a, b) divided by the root of their energies, or 0 below the floor
+__device__ __forceinline__ void norm_write(const NormJob& j, long long t0, const double (&e)[kNormPer]) {
     for (int r = 0; r < kNormPer; ++r) {
-        const long long t = t0 + tid + r * kNormThreads;
+        const long long t = t0 + threadIdx.x + r * kNormThreads;
         if (t < j.a || t >= j.b) continue;
         const float raw = j.scores[t];
         if (!__builtin_isfinite(raw)) continue;   // (a non-finite score stays what it is: the callers' classification reads it)
         const double E = e[r];
         j.scores[t] = (E >= j.thr && E > 0.0) ? (float)((double)raw / sqrt(E)) : 0.0f;
     }
+}
+
+__global__ __launch_bounds__(kNormThreads) void norm_scores_kernel(NormJob j, long long tile0) {
+    __shared__ double buf[kNormSpan];
+    __shared__ double ws[kNormThreads / 64];
+    const long long t0 = (tile0 + blockIdx.x) * kNormTile;
+    double e[kNormPer];
+    span_energy(j, t0 - j.lead, j.s, buf, ws, e);   // (t0 - lead: first sample of the tile's first window)
+    norm_write(j, t0, e);
+}
+
+// Masked needles: the same tile, the energy of each kept span [a_q, b_q) taken as above for a needle of length b_q - a_q
+// whose windows start a_q samples further on, and the spans' energies added in f64 in span order.  Never the whole
+// window minus the gaps: what lies under a gap is not read for the span beside it, so kept spans in digital silence
+// give exactly 0 however loud the gaps are.  One buf serves the spans in turn (no more LDS than norm_scores_kernel);
+// the block energies are the signal's, shared by all spans.
+__global__ __launch_bounds__(kNormThreads) void masked_norm_scores_kernel(NormJob j, long long tile0) {
+    __shared__ double buf[kNormSpan];
+    __shared__ double ws[kNormThreads / 64];
+    const long long t0 = (tile0 + blockIdx.x) * kNormTile;
+    const long long u0 = t0 - j.lead;
+    double E[kNormPer];
+    for (int r = 0; r < kNormPer; ++r) E[r] = 0.0;
+    for (int q = 0; q < j.n_kept; ++q) {
+        const long long a = j.kept[2 * q], b = j.kept[2 * q + 1];
+        double e[kNormPer];
+        span_energy(j, u0 + a, b - a, buf, ws, e);
+        for (int r = 0; r < kNormPer; ++r) E[r] += e[r];
+        __syncthreads();
+    }
+    norm_write(j, t0, E);
 }
 
 }  // namespace
@@ -126,6 +162,13 @@ hipError_t launch_norm_scores(hipStream_t st, const NormJob& j) {
     return hipGetLastError();
 }
 
+hipError_t launch_masked_norm_scores(hipStream_t st, const NormJob& j) {
+    if (j.b <= j.a) return hipSuccess;
+    const long long tile0 = j.a / kNormTile, tile1 = (j.b + kNormTile - 1) / kNormTile;
+    hipLaunchKernelGGL(masked_norm_scores_kernel, dim3((unsigned)(tile1 - tile0)), dim3(kNormThreads), 0, st, j, tile0);
+    return hipGetLastError();
+}
+
 // ---- host side -------------------------------------------------------------------------------------------------------
 
 NormSpec norm_spec(const am_needle* h, const Opts& o) {
@@ -133,6 +176,8 @@ NormSpec norm_spec(const am_needle* h, const Opts& o) {
     ns.on = o.score_norm != 0;
     ns.energy = h->energy;
     ns.thr = h->energy * std::pow(10.0, -(double)o.score_norm_floor_db / 10.0);
+    ns.kept = h->gaps.empty() ? nullptr : h->d_kept;
+    ns.n_kept = h->gaps.empty() ? 0 : h->n_kept;
     return ns;
 }
 
@@ -159,8 +204,9 @@ int normalise_scores(Ctx* c, hipStream_t st, const NormSpec& ns, const void* src
     j.src = src; j.src_len = src_len; j.src_kind = src_kind; j.lead = lead; j.s = s;
     j.blk = static_cast<const double*>(c->norm_blk.p); j.nblk = norm_blocks(src_len);
     j.thr = ns.thr; j.scores = scores; j.a = a; j.b = b;
+    j.kept = ns.kept; j.n_kept = ns.n_kept;
     { ProfScope ps(c, KN_OTHER, st); AM_HIP(launch_block_energy(st, src, src_len, src_kind, static_cast<double*>(c->norm_blk.p))); }
-    { ProfScope ps(c, KN_OTHER, st); AM_HIP(launch_norm_scores(st, j)); }
+    { ProfScope ps(c, KN_OTHER, st); AM_HIP(j.n_kept > 0 ? launch_masked_norm_scores(st, j) : launch_norm_scores(st, j)); }
     return AM_OK;
 }
 

@@ -112,6 +112,8 @@ struct Arguments {
     std::optional<std::uint64_t> edges_ms;    // extension: --edges DUR[:MIN_NCC[:MAX_SECOND]], a snippet cut off by the file's start or end (am_match_edges); DUR: the least overlap
     float edges_min_ncc = 0.5f;               // ... what an edge record must score
     float edges_max_second = 0.5f;            // ... and its runner-up at most this share of it
+    std::vector<std::pair<std::uint64_t, std::uint64_t>> ignore_ms;   // extension: --ignore FROM-TO (repeatable), spans of the snippet to ignore, from its start (am_needle_create_masked)
+    bool mask_report = false;                 // extension: --mask-report, one am_hit_mask line per hit
     bool live = false;                        // extension: --live, raw PCM from stdin through a monitor (am_monitor_*)
     std::uint32_t rate = 0;                   // --live: --rate R (samples per second of the stream)
     std::string encoding = "s16le";           // --live: --encoding s16le | f32le
@@ -148,6 +150,15 @@ inline const char* usage_text() {
            "                         of a perfect match, not of the snippet's energy (default: off)\n"
            "  --normalize-floor DB   with --normalize: windows more than DB decibels below the snippet's energy score 0\n"
            "                         (0..200, default 60)\n"
+           "  --ignore FROM-TO       ignore the span FROM-TO of the snippet (two durations from its start; may be given up\n"
+           "                         to 15 times): the part of a jingle that changes from one occurrence to the next.  With\n"
+           "                         --normalize the score is the NCC over the rest of the snippet only, whatever lies under\n"
+           "                         the span; --min-confidence then filters by the exact NCC over the rest (am_hit_mask's), the\n"
+           "                         other per-hit reports read the snippet with zeros in the span against everything under\n"
+           "                         it.  Not with --resample, --whiten, --preemphasis, --envelope, --edges, --live or\n"
+           "                         several --snippet\n"
+           "  --mask-report          with --ignore: under each hit, its exact NCC over the kept part and what its ignored\n"
+           "                         spans hold against the snippet's own samples there (am_hit_mask)\n"
            "  --min-confidence X     drop every hit whose normalised cross-correlation with the snippet, computed\n"
            "                         exactly for the hit's own window, is below X (0..1); with --debug, print each\n"
            "                         hit's position, ncc, gain and window level (default: keep every hit)\n"
@@ -429,6 +440,15 @@ inline Arguments parse_arguments(int argc, const char* const* argv) {
             a.band_frame_log2 = (std::uint32_t)lf;
         }
         else if (s == "--resample") a.resample = true;
+        else if (s == "--ignore") {
+            const std::string v = need(i);
+            const auto dash = v.find('-');
+            const auto from = parse_duration_ms(v.substr(0, dash));
+            const auto to = dash == std::string::npos ? std::nullopt : parse_duration_ms(v.substr(dash + 1));
+            if (!from || !to || *from >= *to) throw ArgError("invalid value '" + v + "' for --ignore (FROM-TO, two durations from the snippet's start, FROM before TO)");
+            a.ignore_ms.emplace_back(*from, *to);
+        }
+        else if (s == "--mask-report") a.mask_report = true;
         else if (s == "--whiten") {
             const std::string v = need(i);
             char* end = nullptr;
@@ -595,6 +615,17 @@ inline Arguments parse_arguments(int argc, const char* const* argv) {
         throw ArgError("--residual does not apply with --whiten or --preemphasis (the span would be that of the filtered signal)");
     if (a.stereo_radius && (a.resample || a.whiten || a.preemphasis))
         throw ArgError("--stereo does not apply with --resample, --whiten or --preemphasis (the snippet would no longer be on the frames' footing)");
+    if (!a.ignore_ms.empty()) {
+        // (a masked handle comes from am_needle_create_masked only, and these take or build another kind of needle)
+        const std::pair<bool, const char*> no_mask[] = {
+            {a.resample, "--resample"}, {a.whiten != 0, "--whiten"}, {a.preemphasis.has_value(), "--preemphasis"},
+            {a.envelope_pct.has_value(), "--envelope"}, {a.edges_ms.has_value(), "--edges"}, {a.live, "--live"},
+            {a.snippets.size() > 1, "several --snippet"}};
+        for (const auto& o : no_mask)
+            if (o.first) throw ArgError(std::string("--ignore and ") + o.second + " are mutually exclusive");
+        if (a.ignore_ms.size() > AM_MASK_MAX_GAPS) throw ArgError("--ignore: at most " + std::to_string(AM_MASK_MAX_GAPS) + " spans");
+    }
+    if (a.mask_report && a.ignore_ms.empty()) throw ArgError("--mask-report needs --ignore");
     if (a.live && a.mix_set) throw ArgError("--live: --mix does not apply");
     if (a.live && a.stereo_radius) throw ArgError("--live: --stereo does not apply");
     if (a.live && !a.trace_prefix.empty()) throw ArgError("--live: --score-trace does not apply");

@@ -151,6 +151,48 @@ static std::vector<std::string> warp_lines(const std::vector<am_warp_hit>& recs)
     return out;
 }
 
+// extension: --ignore.  The records of the hits of a masked snippet (am_hit_mask): the exact NCC, gain and level over the
+// kept part, and what the ignored spans hold against the snippet's own samples there.
+static std::vector<am_mask_hit> mask_records(const am_needle* algo, const std::vector<float>& samples, const am_peak* peaks, size_t n) {
+    std::vector<am_mask_hit> rec(n);
+    if (n > 0 && am_hit_mask(algo, samples.data(), samples.size(), AM_FMT_F32_MONO, peaks, n, rec.data()) != AM_OK)
+        throw std::runtime_error(std::string("am_hit_mask: ") + am_last_error_string());
+    return rec;
+}
+
+// ... --mask-report: one line per hit, to follow the hit's offset line
+static std::vector<std::string> mask_lines(const std::vector<am_mask_hit>& recs) {
+    std::vector<std::string> out;
+    for (const am_mask_hit& q : recs) {
+        char line[256];
+        std::snprintf(line, sizeof line, "  mask ncc %.6f gain %.6f kept_db %.2f ncc_gaps %.6f gaps_db %.2f flags %u%s%s%s%s", (double)q.ncc, (double)q.gain,
+                      (double)q.kept_db, (double)q.ncc_gaps, (double)q.gaps_db, (unsigned)q.flags,
+                      (q.flags & AM_MASK_BELOW_FLOOR) ? " (below the floor)" : "", (q.flags & AM_MASK_NONFINITE) ? " (non-finite samples)" : "",
+                      (q.flags & AM_MASK_GAPS_SILENT) ? " (silence in the ignored spans)" : "",
+                      (q.flags & AM_MASK_GAPS_NONFINITE) ? " (non-finite samples in the ignored spans)" : "");
+        out.push_back(line);
+    }
+    return out;
+}
+
+// ... --min-confidence X with --ignore.  am_hit_scores reads the whole window, ignored spans included, and would drop
+// exactly the occurrences the mask is there for: the filter takes am_hit_mask's NCC over the kept part instead (also
+// with --warp).  Keeps the hits whose masked NCC is at least X, in place; returns how many are left.  With --debug one
+// line per hit (`prefix` in front).
+static size_t mask_confidence_filter(const Arguments& args, const am_needle* algo, const std::vector<float>& samples, am_peak* peaks, size_t n,
+                                     const std::string& prefix) {
+    const std::vector<am_mask_hit> rec = mask_records(algo, samples, peaks, n);
+    size_t kept = 0;
+    for (size_t i = 0; i < n; ++i) {
+        const bool keep = rec[i].ncc >= *args.min_confidence;   // (a NaN ncc is dropped too)
+        if (args.verbosity >= 2)
+            std::printf("%shit %zu: masked ncc %.6f gain %.6g kept %.2f dB%s\n", prefix.c_str(), i + 1, (double)rec[i].ncc, (double)rec[i].gain,
+                        (double)rec[i].kept_db, keep ? "" : " (dropped)");
+        if (keep) peaks[kept++] = peaks[i];
+    }
+    return kept;
+}
+
 // extension: --channel P[:NOISE_DB].  The records and the taps of the printed hits (am_hit_channel): what each hit went
 // through on its way into the recording.
 struct ChannelSet {
@@ -397,6 +439,16 @@ static std::vector<float> filtered(const Arguments& args, std::vector<float> x, 
 static am_needle* create_needle(const Arguments& args, const std::vector<float>& data, std::uint32_t sr, std::uint32_t m_sr,
                                 const std::vector<float>& taps) {
     am_needle* h = nullptr;
+    if (!args.ignore_ms.empty()) {
+        // extension: --ignore (the parser admits it without --resample and a filter only): a masked handle, the spans in
+        // samples of the snippet's own rate, sorted; the library names the span that breaks a rule
+        std::vector<am_span> gaps;
+        for (const auto& g : args.ignore_ms) gaps.push_back(am_span{round_samples_ms(g.first, sr), round_samples_ms(g.second, sr)});
+        std::sort(gaps.begin(), gaps.end(), [](const am_span& a, const am_span& b) { return a.begin < b.begin; });
+        if (am_needle_create_masked(args.device, data.data(), data.size(), gaps.data(), gaps.size(), &h) != AM_OK)
+            throw std::runtime_error(std::string("--ignore: ") + am_last_error_string());
+        return h;
+    }
     if (taps.empty()) {
         if (sr == m_sr) {
             if (am_needle_create(args.device, data.data(), data.size(), &h) != AM_OK)
@@ -541,7 +593,8 @@ static void report_hits(const Arguments& args, const am_needle* algo, const std:
     am_peak* pk = hits.data();
     size_t n = hits.size();
     const WarpSet warp = WarpSet::compute(args, algo, m_samples, pk, n);
-    if (args.min_confidence && n > 0)
+    if (args.min_confidence && n > 0 && !args.ignore_ms.empty()) n = mask_confidence_filter(args, algo, m_samples, pk, n, prefix);
+    else if (args.min_confidence && n > 0)
         n = args.warp_ppm ? warp_confidence_filter(args, warp, pk, n, prefix) : confidence_filter(args, algo, m_samples, pk, n, prefix);
     if (args.min_significance) n = significance_filter(args, algo, m_samples, m_sr, pk, n, prefix);
     hits.resize(n);
@@ -563,8 +616,9 @@ static void report_hits(const Arguments& args, const am_needle* algo, const std:
         }
     }
     const std::vector<std::string> stereo = args.stereo_radius ? stereo_lines(args, algo, m, pk, n) : none;
+    const std::vector<std::string> masks = args.mask_report ? mask_lines(mask_records(algo, m_samples, pk, n)) : none;
     for (size_t i = 0; i < lines.size(); ++i)
-        for (const std::vector<std::string>* l : {&lines, &stereo, &warps, &chans, &segs, &bands})
+        for (const std::vector<std::string>* l : {&lines, &masks, &stereo, &warps, &chans, &segs, &bands})
             if (i < l->size()) std::printf("%s%s\n", prefix.c_str(), (*l)[i].c_str());
 }
 

@@ -300,9 +300,45 @@ class AudioMatchError(RuntimeError):
         self.code = code
 
 
+AM_MASK_MAX_GAPS = 15
+
+
+class AmSpan(C.Structure):
+    """am_span: samples [begin, end) of a needle (a gap of a masked needle)."""
+    _fields_ = [("begin", C.c_uint64), ("end", C.c_uint64)]
+
+
+AM_MASK_BELOW_FLOOR, AM_MASK_NONFINITE, AM_MASK_GAPS_SILENT, AM_MASK_GAPS_NONFINITE, AM_MASK_NO_GAPS = 1, 2, 4, 8, 16
+
+
+class HitMask(C.Structure):           # am_mask_hit: the per-hit record of a masked handle (am_hit_mask*)
+    _fields_ = [("ncc", C.c_float), ("gain", C.c_float), ("kept_db", C.c_float), ("ncc_gaps", C.c_float), ("gaps_db", C.c_float),
+                ("flags", C.c_uint32)]
+
+    def __repr__(self):
+        return "HitMask(" + ", ".join(f"{n}={getattr(self, n)!r}" for n, _ in self._fields_) + ")"
+
+
+def _spans(gaps):
+    """A list of (begin, end) as an am_span array and its length."""
+    gaps = [] if gaps is None else list(gaps)
+    arr = (AmSpan * max(len(gaps), 1))()
+    for i, (b, e) in enumerate(gaps):
+        arr[i].begin, arr[i].end = int(b), int(e)
+    return arr, len(gaps)
+
+
 # every symbol include/audiomatch.h declares: (name, restype, argtypes)
 _f32p = C.POINTER(C.c_float)
 _SIGNATURES = {
+    "am_needle_create_masked": (C.c_int, [C.c_int, C.c_void_p, C.c_size_t, C.POINTER(AmSpan), C.c_size_t, C.POINTER(C.c_void_p)]),
+    "am_needle_create_masked_device": (C.c_int, [C.c_int, C.c_void_p, C.c_size_t, C.POINTER(AmSpan), C.c_size_t, C.POINTER(C.c_void_p)]),
+    "am_needle_mask": (C.c_int, [C.c_void_p, C.POINTER(AmSpan), C.c_size_t, C.POINTER(C.c_size_t)]),
+    "am_hit_mask_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.POINTER(AmPeak), C.c_size_t, C.POINTER(HitMask)]),
+    "am_hit_mask": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.POINTER(AmPeak), C.c_size_t, C.POINTER(HitMask)]),
+    "am_hit_mask_batch_device": (C.c_int, [C.POINTER(C.c_void_p), C.c_size_t, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t),
+                                           C.c_size_t, C.c_int, C.POINTER(AmPeak), C.c_size_t, C.POINTER(C.c_size_t),
+                                           C.POINTER(HitMask)]),
     "am_abi_version": (C.c_int, []),
     "am_last_error_string": (C.c_char_p, []),
     "am_device_count": (C.c_int, [C.POINTER(C.c_int)]),
@@ -1310,6 +1346,7 @@ _BANDS = _HitFamily(
 _STEREO = _HitFamily(
     "am_hit_stereo", HitStereo, lambda radius: (AmStereoParams(int(radius), 0), 1),
     lambda out, i, m: HitStereo.from_buffer_copy(out[i]))
+_MASK = _HitFamily("am_hit_mask", HitMask, lambda: (None, 1), lambda out, i, m: HitMask.from_buffer_copy(out[i]))
 _SIGNIFICANCE = _HitFamily(
     "am_hit_significance", HitSignificance, lambda guard, radius: (AmSignificanceParams(int(guard), int(radius)), 1),
     lambda out, i, m: HitSignificance.from_buffer_copy(out[i]))
@@ -1415,25 +1452,42 @@ class HipConvolve:
     """CorrelateAlgo<f32> (audio_matcher.rs:65-76) backed by the HIP library.
 
     score_norm: None follows the process default; True / False fixes this handle's "score_norm" (NCC scores,
-    which need the LIB scale)."""
+    which need the LIB scale).
+    gaps: None, or [(begin, end), ..]: spans of the needle to ignore (am_needle_create_masked: a masked needle; with
+    score_norm the scores are NCC over the kept samples only).  An empty list gives the ordinary handle."""
 
-    def __init__(self, sample_data, device: int = 0, score_norm=None):
+    def __init__(self, sample_data, device: int = 0, score_norm=None, gaps=None):
         a = np.ascontiguousarray(sample_data, dtype=np.float32)
         self.device = device
         self._h = C.c_void_p()
-        _check(lib().am_needle_create(device, a.ctypes.data, a.size, C.byref(self._h)))
+        if gaps is None:
+            _check(lib().am_needle_create(device, a.ctypes.data, a.size, C.byref(self._h)))
+        else:
+            arr, n = _spans(gaps)
+            _check(lib().am_needle_create_masked(device, a.ctypes.data, a.size, arr, n, C.byref(self._h)))
         self.sample_len = int(a.size)
         if score_norm is not None:
             self.set_option(OPT_SCORE_NORM, int(bool(score_norm)))
 
     @classmethod
-    def from_device(cls, device: int, ptr: int, n: int) -> "HipConvolve":
+    def from_device(cls, device: int, ptr: int, n: int, gaps=None) -> "HipConvolve":
         self = cls.__new__(cls)
         self.device = device
         self._h = C.c_void_p()
-        _check(lib().am_needle_create_device(device, ptr, n, C.byref(self._h)))
+        if gaps is None:
+            _check(lib().am_needle_create_device(device, ptr, n, C.byref(self._h)))
+        else:
+            arr, k = _spans(gaps)
+            _check(lib().am_needle_create_masked_device(device, ptr, n, arr, k, C.byref(self._h)))
         self.sample_len = int(n)
         return self
+
+    def mask(self):
+        """am_needle_mask: the handle's gaps as [(begin, end), ..]; [] for an ordinary handle."""
+        arr = (AmSpan * AM_MASK_MAX_GAPS)()
+        n = C.c_size_t(0)
+        _check(lib().am_needle_mask(self._h, arr, AM_MASK_MAX_GAPS, C.byref(n)))
+        return [(int(g.begin), int(g.end)) for g in arr[:n.value]]
 
     @classmethod
     def from_pcm16(cls, interleaved, device: int = 0) -> "HipConvolve":
@@ -1684,6 +1738,16 @@ class HipConvolve:
     def hit_scores_device(self, ptr: int, length: int, peaks, fmt: int = Fmt.F32_MONO):
         """am_hit_scores_device: score `peaks` of a haystack resident on this needle's device."""
         return _hit_device(_SCORES, self, ptr, length, peaks, fmt, ())
+
+    # -- the per-hit record of a masked handle --
+    def hit_mask(self, haystack, peaks):
+        """am_hit_mask: one HitMask per hit of a host haystack (as in hit_scores): exact masked NCC, gain and level over
+        the kept samples, and what the gaps hold against the needle's original samples there."""
+        return _hit_host(_MASK, self, haystack, peaks, ())
+
+    def hit_mask_device(self, ptr: int, length: int, peaks, fmt: int = Fmt.F32_MONO):
+        """am_hit_mask_device: the same for a haystack resident on this needle's device."""
+        return _hit_device(_MASK, self, ptr, length, peaks, fmt, ())
 
     # -- per-segment hit scoring --
     def hit_segments(self, haystack, peaks, segments: int, radius: int = 4):
@@ -2060,6 +2124,11 @@ def hit_scores_batch_device(algos, ptrs, lengths, peaks_per_pair, fmt: int = Fmt
     """am_hit_scores_batch_device: peaks_per_pair[k][j] = the hits of haystack k against needle j (the shape
     match_multi_batch_device returns; needles may differ in length); result [k][j] = their HitScores."""
     return _hit_batch(_SCORES, algos, ptrs, lengths, peaks_per_pair, fmt, ())
+
+
+def hit_mask_batch_device(algos, ptrs, lengths, peaks_per_pair, fmt: int = Fmt.F32_MONO):
+    """am_hit_mask_batch_device: peaks_per_pair[k][j] as in hit_scores_batch_device; result [k][j] = their HitMask records."""
+    return _hit_batch(_MASK, algos, ptrs, lengths, peaks_per_pair, fmt, ())
 
 
 def hit_segments_batch_device(algos, ptrs, lengths, peaks_per_pair, segments: int, radius: int = 4, fmt: int = Fmt.F32_MONO):

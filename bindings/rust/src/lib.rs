@@ -441,6 +441,31 @@ pub const AM_HIT_UNREFINED: u32 = 1;
 pub const AM_HIT_BELOW_FLOOR: u32 = 2;
 pub const AM_HIT_NONFINITE: u32 = 4;
 
+/// am_span: samples [begin, end) of a needle (a gap of a masked needle, am_needle_create_masked)
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default, PartialEq, Eq)]
+pub struct AmSpan {
+    pub begin: u64,
+    pub end: u64,
+}
+pub const AM_MASK_MAX_GAPS: usize = 15;
+/// am_mask_hit: the per-hit record of a masked handle (24 bytes)
+#[repr(C)]
+#[derive(Clone, Copy, Default, Debug)]
+pub struct AmMaskHit {
+    pub ncc: f32,
+    pub gain: f32,
+    pub kept_db: f32,
+    pub ncc_gaps: f32,
+    pub gaps_db: f32,
+    pub flags: u32,
+}
+pub const AM_MASK_BELOW_FLOOR: u32 = 1;
+pub const AM_MASK_NONFINITE: u32 = 2;
+pub const AM_MASK_GAPS_SILENT: u32 = 4;
+pub const AM_MASK_GAPS_NONFINITE: u32 = 8;
+pub const AM_MASK_NO_GAPS: u32 = 16;
+
 pub const AM_OK: c_int = 0;
 pub const AM_ERR_INVALID_ARG: c_int = 1;
 pub const AM_ERR_CAPACITY: c_int = 2;
@@ -448,6 +473,9 @@ pub const AM_ERR_CAPACITY: c_int = 2;
 extern "C" {
     pub fn am_last_error_string() -> *const c_char;
     pub fn am_needle_create(device: c_int, needle: *const f32, n: usize, out: *mut *mut AmNeedle) -> c_int;
+    pub fn am_needle_create_masked(device: c_int, needle: *const f32, n: usize, gaps: *const AmSpan, n_gaps: usize, out: *mut *mut AmNeedle) -> c_int;
+    pub fn am_needle_create_masked_device(device: c_int, d_needle: *const f32, n: usize, gaps: *const AmSpan, n_gaps: usize, out: *mut *mut AmNeedle) -> c_int;
+    pub fn am_needle_mask(h: *const AmNeedle, gaps: *mut AmSpan, cap: usize, n_gaps: *mut usize) -> c_int;
     pub fn am_needle_destroy(h: *mut AmNeedle);
     pub fn am_needle_len(h: *const AmNeedle, n: *mut usize) -> c_int;
     pub fn am_needle_inv_autocorr(h: *const AmNeedle, out: *mut f32) -> c_int;
@@ -585,6 +613,19 @@ extern "C" {
     pub fn am_hit_scores_batch_device(
         needles: *const *const AmNeedle, n_needles: usize, d_haystacks: *const *const std::ffi::c_void, lens: *const usize,
         n_hay: usize, sample_format: c_int, peaks: *const AmPeak, cap_per_pair: usize, n_peaks: *const usize, out: *mut AmHitScore,
+    ) -> c_int;
+    /// the per-hit record of a masked handle (audiomatch.h, "masked needles")
+    pub fn am_hit_mask(
+        h: *const AmNeedle, haystack: *const std::ffi::c_void, len: usize, sample_format: c_int, peaks: *const AmPeak, n: usize,
+        out: *mut AmMaskHit,
+    ) -> c_int;
+    pub fn am_hit_mask_device(
+        h: *const AmNeedle, d_haystack: *const std::ffi::c_void, len: usize, sample_format: c_int, peaks: *const AmPeak, n: usize,
+        out: *mut AmMaskHit,
+    ) -> c_int;
+    pub fn am_hit_mask_batch_device(
+        needles: *const *const AmNeedle, n_needles: usize, d_haystacks: *const *const std::ffi::c_void, lens: *const usize,
+        n_hay: usize, sample_format: c_int, peaks: *const AmPeak, cap_per_pair: usize, n_peaks: *const usize, out: *mut AmMaskHit,
     ) -> c_int;
     /// per-segment hit scoring: which part of the needle a hit holds, and its drift (audiomatch.h)
     pub fn am_hit_segments(
@@ -957,6 +998,29 @@ impl HipConvolve {
         Ok(Self { h, len: sample_data.len() })
     }
 
+    /// `LibConvolve::new` on a snippet with spans to ignore (am_needle_create_masked): with the option "score_norm" the
+    /// scores are NCC over the kept samples only.  No gaps: the handle of `new`.
+    pub fn new_masked(sample_data: &[f32], gaps: &[AmSpan]) -> Result<Self, Box<dyn std::error::Error>> {
+        let mut h = std::ptr::null_mut();
+        let rc = unsafe { am_needle_create_masked(0, sample_data.as_ptr(), sample_data.len(), gaps.as_ptr(), gaps.len(), &mut h) };
+        if rc != AM_OK {
+            return Err(am_err(rc));
+        }
+        Ok(Self { h, len: sample_data.len() })
+    }
+
+    /// The handle's gaps (am_needle_mask); empty for an ordinary handle.
+    pub fn mask(&self) -> Result<Vec<AmSpan>, Box<dyn std::error::Error>> {
+        let mut gaps = vec![AmSpan::default(); AM_MASK_MAX_GAPS];
+        let mut n = 0usize;
+        let rc = unsafe { am_needle_mask(self.h, gaps.as_mut_ptr(), gaps.len(), &mut n) };
+        if rc != AM_OK {
+            return Err(am_err(rc));
+        }
+        gaps.truncate(n);
+        Ok(gaps)
+    }
+
     /// `LibConvolve::new` on a snippet recorded at `src_rate`, brought to the haystack's `dst_rate` on the GPU
     /// (am_needle_create_resampled): matching then runs on haystacks of that rate, offsets in their samples.  The
     /// reference stops with CliError::SampleRateMismatch instead (matcher/mod.rs:72-74).
@@ -1055,6 +1119,20 @@ impl HipConvolve {
         }
         buf.truncate(n);
         Ok(buf)
+    }
+
+    /// The per-hit record of a masked handle (am_hit_mask) for `peaks` found in the host haystack `m_samples`: exact
+    /// masked NCC, gain and level over the kept samples, and what the gaps hold against the original needle there.
+    pub fn hit_mask(&self, m_samples: &[f32], peaks: &[AmPeak]) -> Result<Vec<AmMaskHit>, Box<dyn std::error::Error>> {
+        let mut out = vec![AmMaskHit::default(); peaks.len()];
+        let rc = unsafe {
+            am_hit_mask(self.h, m_samples.as_ptr() as *const std::ffi::c_void, m_samples.len(), AM_FMT_F32_MONO, peaks.as_ptr(),
+                        peaks.len(), out.as_mut_ptr())
+        };
+        if rc != AM_OK {
+            return Err(am_err(rc));
+        }
+        Ok(out)
     }
 
     /// Per-hit scoring (am_hit_scores) of `peaks` found in the host haystack `m_samples`: exact NCC, gain, window

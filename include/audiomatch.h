@@ -115,6 +115,77 @@ int am_needle_len(const am_needle* h, size_t* n);
 /* CorrelateAlgo::inverse_sample_auto_correlation (audio_matcher.rs:66, 321-329) */
 int am_needle_inv_autocorr(const am_needle* h, float* out);
 
+/* ---- masked needles: spans to ignore, NCC over the rest -------------------------------------------------------------
+ * A jingle whose middle changes from one occurrence to the next (a spoken title over the theme, "the news at NINE", a
+ * sponsor line): the needle carries a mask, `gaps`, the spans [begin, end) of its samples to ignore.  The kept spans are
+ * what lies between them, [a_j, b_j), at most AM_MASK_MAX_GAPS + 1 of them.
+ *   gaps ascend; each has begin < end <= n; gaps[i].end < gaps[i+1].begin (touching gaps are the caller's to merge, so
+ *   every kept span is non-empty); the first may begin at 0, the last may end at n; at least one sample is kept;
+ *   n_gaps <= AM_MASK_MAX_GAPS.  A violation is AM_ERR_INVALID_ARG, the message names the gap and the rule.  n_gaps = 0
+ *   gives am_needle_create's handle in every respect.  A needle long enough to be partitioned (more than 2^22 samples)
+ *   is refused: masked partitioned needles are not supported.
+ * The handle's needle is the needle with its gap samples set to +0: every correlation value of every entry point is the
+ * masked numerator, and am_needle_inv_autocorr is 1 / E_n^M, E_n^M = the energy of the kept samples.  With "score_norm"
+ * = 0 a masked handle behaves as that zero-filled needle.  With "score_norm" = 1 every entry point that supports the
+ * option returns masked NCC,
+ *     mncc(t) = corr(t) / sqrt(E_n^M E_x^M(t)),   E_x^M(t) = sum_j sum_{i in [a_j, b_j)} x[t - lead + i]^2,
+ * x = 0 outside the signal: what lies under the gaps, however loud, enters neither the numerator nor the denominator.
+ * The score rule is that of "score_norm" with E_x^M in the window energy's place: 0 when E_x^M(t) = 0 or E_x^M(t) <
+ * E_n^M 10^(-score_norm_floor_db / 10), the quotient in f64 and rounded once, a non-finite raw score left as it is.
+ * E_x^M is added up span by span in ascending order, each span's energy from non-negative pieces only (never "whole
+ * window minus gaps"): kept spans in digital silence score exactly 0.  A haystack's bits are the same alone and in any
+ * batch.  Non-finite haystack samples cost the whole windows that hold them, gaps included (the numerator comes from a
+ * transform of all samples).  Entry points that refuse "score_norm" refuse it for a masked handle too.
+ * The per-hit families (am_hit_scores* and the others below) read the handle's needle and the whole window: on a
+ * masked handle they score the zero-filled needle against everything under it, gaps included.  am_hit_mask* below is
+ * the per-hit record of a masked handle. */
+#define AM_MASK_MAX_GAPS 15
+typedef struct am_span {
+    uint64_t begin, end;   /* samples of the needle, [begin, end) */
+} am_span;
+/* `needle` is host memory, copied (gap samples may hold anything, non-finite values included) */
+int am_needle_create_masked(int device, const float* needle, size_t n, const am_span* gaps, size_t n_gaps, am_needle** out);
+/* same, needle already resident on `device` (gaps is host memory) */
+int am_needle_create_masked_device(int device, const float* d_needle, size_t n, const am_span* gaps, size_t n_gaps, am_needle** out);
+/* The handle's gaps: *n_gaps = their number (0 for an ordinary handle), the first min(*n_gaps, cap) in gaps (which may
+ * be NULL when cap = 0); AM_ERR_CAPACITY when there are more than cap. */
+int am_needle_mask(const am_needle* h, am_span* gaps, size_t cap, size_t* n_gaps);
+
+/* The per-hit record of a masked handle: does an occurrence hold the original in its gaps, or something else, and how
+ * loud is that?  For a hit at t = peak.start, the zero-filled needle n, the ORIGINAL needle samples o under the gaps and
+ * the haystack's samples x (the down-mix for AM_FMT_S16_STEREO, as for am_hit_scores), in f64 by direct sums:
+ *     kept samples i:  c_k = sum x[t + i] n[i],  E_x^M = sum x[t + i]^2,  E_n^M = the handle's energy
+ *     gap samples i:   c_g = sum x[t + i] o[i],  E_x,gaps = sum x[t + i]^2,  E_n,gaps = sum o[i]^2
+ *   ncc       c_k / sqrt(E_n^M E_x^M); 0 with AM_MASK_BELOW_FLOOR when E_x^M = 0 or E_x^M < E_n^M 10^(-score_norm_floor_db / 10)
+ *             (the process option at call time, as am_hit_scores)
+ *   gain      c_k / E_n^M
+ *   kept_db   10 log10(E_x^M / E_n^M), -inf for E_x^M = 0
+ *   ncc_gaps  c_g / sqrt(E_n,gaps E_x,gaps); 0 when either energy is 0
+ *   gaps_db   10 log10(E_x,gaps / (gain^2 E_n,gaps)): what lies in the gaps against what the needle would put there at the
+ *             hit's gain; -inf for E_x,gaps = 0 (flag AM_MASK_GAPS_SILENT), +inf for gain^2 E_n,gaps = 0 < E_x,gaps
+ * AM_MASK_NONFINITE: a non-finite sample of the needle or the haystack under a kept span; every field is NaN.
+ * AM_MASK_GAPS_NONFINITE: a non-finite sample of the original needle or the haystack under a gap; ncc_gaps and gaps_db
+ * are NaN, the other fields are not affected.  AM_MASK_NO_GAPS: the handle has no mask; ncc_gaps and gaps_db are NaN.
+ * The sums run over slices of the needle in a fixed order: the three forms agree bit for bit and a hit's record does not
+ * depend on the other hits of the call.  The forms, their arguments and their refusals are am_hit_scores*'s (the host
+ * form copies only the hits' spans; the batch form takes the pair layout of am_match_multi_batch_device). */
+enum { AM_MASK_BELOW_FLOOR = 1, AM_MASK_NONFINITE = 2, AM_MASK_GAPS_SILENT = 4, AM_MASK_GAPS_NONFINITE = 8, AM_MASK_NO_GAPS = 16 };
+typedef struct am_mask_hit {
+    float ncc;        /* c_k / sqrt(E_n^M E_x^M(t)), exact: direct f64 sums over the kept samples */
+    float gain;       /* c_k / E_n^M */
+    float kept_db;    /* 10 log10(E_x^M / E_n^M) */
+    float ncc_gaps;   /* the same NCC over the gap samples, against the ORIGINAL needle samples there */
+    float gaps_db;    /* 10 log10(E_x,gaps / (gain^2 E_n,gaps)) */
+    uint32_t flags;   /* AM_MASK_* */
+} am_mask_hit;       /* 24 bytes */
+int am_hit_mask_device(const am_needle* h, const void* d_haystack, size_t len, int sample_format,
+                       const am_peak* peaks, size_t n, am_mask_hit* out);
+int am_hit_mask(const am_needle* h, const void* haystack, size_t len, int sample_format,
+                const am_peak* peaks, size_t n, am_mask_hit* out);
+int am_hit_mask_batch_device(const am_needle* const* needles, size_t n_needles,
+                             const void* const* d_haystacks, const size_t* lens, size_t n_hay, int sample_format,
+                             const am_peak* peaks, size_t cap_per_pair, const size_t* n_peaks, am_mask_hit* out);
+
 /* ---- level 1: one correlation (the trait method) ------------------------ */
 /* output length of a mode: audio_matcher.rs:450-456 */
 int am_correlate_len(size_t w, size_t s, int mode, size_t* out_len);
@@ -1632,7 +1703,8 @@ int am_set_chunk_progress_callback(am_chunk_progress_fn fn, void* user);
  * kernels of needle discovery --, "envelope_frames", "envelope_prefix",
  * "envelope_correlate" -- the levels, the prefix sums and the correlation of
  * envelope matching; "envelope" adds the three --, "edges" -- the span, scan,
- * normalising and exact kernels of edge matching -- or "*" for all). */
+ * normalising and exact kernels of edge matching --, "mask" -- the kernels of
+ * am_hit_mask* -- or "*" for all). */
 int am_profile_enable(int device, int on);
 int am_profile_reset(int device);
 int am_profile_query(int device, const char* kernel, double* total_ms, uint64_t* launches);
@@ -1722,7 +1794,8 @@ int am_debug_column_bench(int device, int wide, int npairs, int iters, int dense
  *     haystack's result is the same bit pattern alone, in a batch and on any pool; chunking, "tail_window", the peak
  *     rules and the overshadow filter apply to the NCC scores unchanged; "half_pipeline" keeps its offsets and
  *     tolerances.  The needle's write-threshold history (sparse raw scores) is neither read nor fed by such calls:
- *     their transforms write every raw score.
+ *     their transforms write every raw score.  On a masked handle (am_needle_create_masked) both energies run over
+ *     the kept samples only: "masked needles" above.
  *   "score_norm_floor_db" (0..200, default 60; process-wide): a window whose energy is more than that many dB below
  *     the needle's, E_w < E_n * 10^(-floor/10), scores exactly 0.  Digital silence gives 0 (never NaN or inf).  The
  *     floor exists because the transform's absolute error scales with the energy of the whole overlap-save block,

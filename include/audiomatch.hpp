@@ -166,6 +166,19 @@ public:
     HipConvolve(const void* needle, std::size_t n, int sample_format, const std::vector<float>& taps, int device = 0) {
         check(am_needle_create_filtered(device, needle, n, sample_format, taps.data(), static_cast<std::uint32_t>(taps.size()), &h_));
     }
+    // am_needle_create_masked: a masked needle, `gaps` the spans [begin, end) of its samples to ignore (under "score_norm"
+    // the scores are NCC over the kept samples only); no gaps: the ordinary handle
+    HipConvolve(const std::vector<float>& sample_data, const std::vector<am_span>& gaps, int device = 0) {
+        check(am_needle_create_masked(device, sample_data.data(), sample_data.size(), gaps.data(), gaps.size(), &h_));
+    }
+    // am_needle_mask: the handle's gaps (none for an ordinary handle)
+    std::vector<am_span> mask() const {
+        std::vector<am_span> g(AM_MASK_MAX_GAPS);
+        std::size_t n = 0;
+        check(am_needle_mask(h_, g.data(), g.size(), &n));
+        g.resize(n);
+        return g;
+    }
     HipConvolve(const HipConvolve&) = delete;
     HipConvolve& operator=(const HipConvolve&) = delete;
     HipConvolve(HipConvolve&& o) noexcept : h_(std::exchange(o.h_, nullptr)) {}
@@ -198,6 +211,20 @@ public:
                                                 const std::vector<am_peak>& peaks) const {
         std::vector<am_hit_score> out(peaks.size());
         check(am_hit_scores_device(h_, d_haystack, len, sample_format, peaks.data(), peaks.size(), out.data()));
+        return out;
+    }
+    // the per-hit record of a masked handle (am_hit_mask): exact masked NCC, gain and level over the kept samples, and what
+    // the gaps hold against the needle's original samples there; am_hit_mask_device for a resident haystack, and
+    // am_hit_mask_batch_device (the C call, pair layout of am_match_multi_batch_device) for several handles and haystacks
+    std::vector<am_mask_hit> hit_mask(const void* haystack, std::size_t len, int sample_format, const std::vector<am_peak>& peaks) const {
+        std::vector<am_mask_hit> out(peaks.size());
+        check(am_hit_mask(h_, haystack, len, sample_format, peaks.data(), peaks.size(), out.data()));
+        return out;
+    }
+    std::vector<am_mask_hit> hit_mask_device(const void* d_haystack, std::size_t len, int sample_format,
+                                             const std::vector<am_peak>& peaks) const {
+        std::vector<am_mask_hit> out(peaks.size());
+        check(am_hit_mask_device(h_, d_haystack, len, sample_format, peaks.data(), peaks.size(), out.data()));
         return out;
     }
     // per-segment hit scoring (am_hit_segments): sp.segments records per peak, peak i at [i * segments, (i + 1) * segments)
